@@ -5,7 +5,12 @@ A "step" is one pass of the hot path (cell sort -> exact kNN -> density / pressu
 viscosity sums -> dt -> leapfrog) over the whole particle set, state resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--particles PER_GPU] [--workload NAME]
+                  [--full] [--dump-outputs DIR]
 
+The K timed steps are taken in segments from the initial condition, each within the first FLOW_STEPS steps of the flow
+(the default workload falls apart after that under the reference's dt rule).
+A plain run sets up, warms up, times K steps and prints the headline; --full adds what takes work of its own (per-pass
+times from further steps, the with-species step, the state check, the CPU baseline, the single-GPU line of N > 1).
 N > 1 is launched by torch.distributed.run (one rank per GPU); see sph_code_amd/multigpu.py.
 Prints ONE JSON line on rank 0.
 """
@@ -85,6 +90,49 @@ def cpu_baseline(workload, n_cpu, k):
     return out
 
 
+# Steps from the initial condition that a timed step may lie in.  Under the reference's dt rule and hydro_update's sums the
+# default workload (the 1e6 polytrope) is a sane flow for 40 steps (max |v| 9.3e4 m/s, 1.6 ms per step); from step 42 on
+# it flies apart (max |v| 1e38 m/s by step 47, steps ~2 ms), and from step ~120 on densities and
+# pressures of stray particles are no longer finite.  Timed steps beyond this would time that other state.
+FLOW_STEPS = 40
+# stats fields that hold the last step's value (include/sphx.h sphx_stats); all others are sums over the steps
+LAST_STEP_STATS = ("n", "cells", "cell_size", "fallback_queries", "far_queries", "outlier_levels")
+
+
+def add_stats(a, b):
+    """Stats of two runs of timed steps as one (a may be None)."""
+    if a is None:
+        return dict(b)
+    return {k_: b[k_] if k_ in LAST_STEP_STATS else a[k_] + b[k_] for k_ in b}
+
+
+DUMP_BYTES = 48 << 20            # --dump-outputs: at most this many bytes of arrays (well under 64 MB with the .npy headers)
+DUMP_SEED = 12345
+
+
+def dump_outputs(path, arrays, n):
+    """Write what a caller of the timed path receives after its last step (Simulation.download, with the species pass
+    also download_species) as <path>/<name>.npy in float64.  Per-particle arrays keep every particle when they fit in
+    DUMP_BYTES, else the same seeded sample of particles (sorted indices) in every array, run and build; f_un_neighbor
+    is (S, N), the others have the particle axis first.  visc_heat is written as the step applies it to E_internal, with
+    the nan_to_num of drv:490: under hydro_update's sums the reference's viscous heat is NaN for every particle from the
+    second step on, and the step zeroes it.  Returns (particles written, visc_heat entries zeroed)."""
+    per_particle = sum(np.asarray(a).size // n * 8 for a in arrays.values() if np.ndim(a))
+    m = min(n, DUMP_BYTES // per_particle)
+    sel = np.sort(np.random.RandomState(DUMP_SEED).permutation(n)[:m]) if m < n else slice(None)
+    os.makedirs(path, exist_ok=True)
+    zeroed = 0
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim:
+            a = a[:, sel] if name == "f_un_neighbor" else a[sel]
+        if name == "visc_heat":
+            zeroed = int((~np.isfinite(a)).sum())
+            a = np.nan_to_num(a)
+        np.save(os.path.join(path, name + ".npy"), a)
+    return m, zeroed
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -96,7 +144,14 @@ def main():
                          "(configs[3]: the reference's own IC and its time loop's own sums, natural density)")
     ap.add_argument("--neigh", dest="k", type=int, default=40, help="N_NEIGH")
     ap.add_argument("--cpu-particles", dest="cpu_n", type=int, default=600_000)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take work of their own: per-pass times (5 further steps with timing "
+                         "events), the with-species step, the state check of the final state, the CPU baseline; at N > 1 "
+                         "GPUs the same workload on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the timed steps left (what Simulation.download / download_species return) as "
+                         "DIR/<name>.npy in float64, for a fixed seeded sample of the particles (dump_outputs)")
     ap.add_argument("--device-warmup", type=int, default=3,
                     help="runs of the same W + K steps on throw-away copies of the workload before the measured run "
                          "(clock ramp of a fresh box); 0: none")
@@ -117,8 +172,12 @@ def main():
     ap.add_argument("--gravity", default=None, choices=["direct", "tree"],
                     help="self-gravity in the timed step (off in the BASELINE metric; DESIGN 5.7)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs is not None and (args.gpus > 1 or world > 1 or os.environ.get("SPHX_FORCE_DIST") == "1"):
+        ap.error("--dump-outputs is implemented for the single-GPU path only")
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus > 1 and world == 1 and os.environ.get("SPHX_FORCE_DIST") != "1":
@@ -162,65 +221,87 @@ def main():
         if state.get("f_un") is None:
             raise SystemExit("--species needs a workload that carries f_un (two_phase, dusty_sphere)")
     fixed_dt = ics.cfl_dt(state, args.k) if args.dt == "cfl" else 0.0
-    # Device warm-up, apart from the W warm-up steps of the measured run: the same W + K steps on throw-away copies of the
-    # workload, so that a fresh box (clocks at idle, memory pools cold) times the kernels and not its own waking up.  (The
-    # same few steps again rather than one long run: under the reference's dt rule the polytrope itself stays sane for ~40
-    # steps)  The measured run starts from the initial condition again.
+
+    def start(ctx=None):
+        """The workload from its initial condition, after the W warm-up steps (uploaded into `ctx` when given)."""
+        s = Simulation(state, n_neigh=args.k, device=local_rank, gravity=args.gravity, clip_grad=args.clip_grad,
+                       forms=args.forms, d=d_loop, with_species=args.species, agb=agb_table, with_drag=args.drag, ctx=ctx)
+        s.step(args.warmup, fixed_dt=fixed_dt)
+        return s
+
+    # Device warm-up, apart from the W warm-up steps of the measured run: the same W + K steps (at most FLOW_STEPS) on
+    # throw-away copies of the workload, so that a fresh box (clocks at idle, memory pools cold) times the kernels and not
+    # its own waking up.  The measured run starts from the initial condition again.
     for _ in range(max(args.device_warmup, 0)):
         scratch = Simulation(state, n_neigh=args.k, device=local_rank, gravity=args.gravity, clip_grad=args.clip_grad,
                              forms=args.forms, d=d_loop, with_species=args.species, agb=agb_table, with_drag=args.drag)
-        scratch.step(args.warmup + args.steps, fixed_dt=fixed_dt)
+        scratch.step(min(args.warmup + args.steps, FLOW_STEPS), fixed_dt=fixed_dt)
         torch.cuda.synchronize()
         scratch.ctx.close()
         del scratch
-    sim = Simulation(state, n_neigh=args.k, device=local_rank, gravity=args.gravity, clip_grad=args.clip_grad,
-                     forms=args.forms, d=d_loop, with_species=args.species, agb=agb_table, with_drag=args.drag)
-    sim.step(args.warmup, fixed_dt=fixed_dt)
-    sim.reset_stats()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    sim.step(args.steps, fixed_dt=fixed_dt)      # returns after the library's stream has drained
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    st = sim.stats()
-    failures = sim.failures()
+    # The K timed steps, in segments of at most FLOW_STEPS - W: each segment is the initial condition uploaded again, its W
+    # warm-up steps untimed, then the segment's timed steps, so that every timed step is one of steps W+1 .. FLOW_STEPS of
+    # the flow.  K <= FLOW_STEPS - W is one segment: the measured run as it always was.
+    per_segment = max(FLOW_STEPS - args.warmup, 1)
+    sim, st, dt, done, segments = None, None, 0.0, 0, 0
+    while done < args.steps:
+        sim = start(sim.ctx if sim is not None else None)
+        sim.reset_stats()
+        torch.cuda.synchronize()
+        r = min(per_segment, args.steps - done)
+        t0 = time.perf_counter()
+        sim.step(r, fixed_dt=fixed_dt)           # returns after the library's stream has drained
+        torch.cuda.synchronize()
+        dt += time.perf_counter() - t0
+        st = add_stats(st, sim.stats())
+        done += r
+        segments += 1
     build_info = sim.ctx.build_info()
-    final = sim.download()
-    vmax = float(np.sqrt((final["velocities"] ** 2).sum(axis=1)).max())
-    sane = bool(np.isfinite(final["points"]).all() and np.isfinite(final["velocities"]).all())
-
-    # per-pass times: a few further steps with one timing event per pass (off in the timed steps: an event record between
-    # two dependent kernels costs the stream ~10 us); ms_grid, ms_search and ms_total are the timed steps' own
-    sim.ctx.set_timing_detail(True)
-    sim.reset_stats()
-    sim.step(5, fixed_dt=fixed_dt)
-    torch.cuda.synchronize()
-    st_detail = sim.stats()
-    sim.ctx.set_timing_detail(False)
     ms_step = dt / args.steps * 1e3
     value = args.n * args.steps / dt
     ms_search = st["ms_search"] / max(st["search_steps"], 1)      # HIP events on the library's stream, around the search launches
-    # (of the steps that carry them: replays of a step graph - SPHX_GRAPH - do not; when every timed step was a replay the
-    #  detail steps after them, which are real steps, supply the figure)
-    if not ms_search > 0.0:
-        ms_search = st_detail["ms_search"] / max(st_detail["search_steps"], 1)
+    final = sim.download() if (args.full or args.dump_outputs is not None) else None
+    dumped = None
+    if args.dump_outputs is not None:
+        dumped = dump_outputs(args.dump_outputs, dict(final, **(sim.download_species() if args.species else {})), args.n)
+
+    if args.full:
+        failures = {k_: int(st[k_]) for k_ in Simulation.FAILURE_COUNTERS}
+        vmax = float(np.sqrt((final["velocities"] ** 2).sum(axis=1)).max())
+        sane = bool(np.isfinite(final["points"]).all() and np.isfinite(final["velocities"]).all())
+        # per-pass times: a few further steps with one timing event per pass (off in the timed steps: an event record
+        # between two dependent kernels costs the stream ~10 us); ms_grid, ms_search and ms_total are the timed steps' own.
+        # They follow the last timed step, or a new segment where that would take the flow beyond FLOW_STEPS.
+        if args.warmup + r + 5 > FLOW_STEPS:
+            sim = start(sim.ctx)
+        sim.ctx.set_timing_detail(True)
+        sim.reset_stats()
+        sim.step(5, fixed_dt=fixed_dt)
+        torch.cuda.synchronize()
+        st_detail = sim.stats()
+        sim.ctx.set_timing_detail(False)
+        # (of the steps that carry them: replays of a step graph - SPHX_GRAPH - do not; when every timed step was a replay
+        #  the detail steps after them, which are real steps, supply the figure)
+        if not ms_search > 0.0:
+            ms_search = st_detail["ms_search"] / max(st_detail["search_steps"], 1)
+        # the a6-inclusive figure beside the core one (nsc.hydro_update always forms F[s,i], nsc:624-627; the headline's
+        # step leaves it out, as `config` says): the same workload with the species pass in the step, a short run outside
+        # the timed one
+        with_species_ms = None
+        if not args.species and state.get("f_un") is not None and os.environ.get("SPHX_BENCH_SPECIES_LINE", "1") != "0":
+            sp = Simulation(state, n_neigh=args.k, device=local_rank, gravity=args.gravity, clip_grad=args.clip_grad,
+                            forms=args.forms, d=d_loop, with_species=True, with_drag=args.drag)
+            sp.step(args.warmup, fixed_dt=fixed_dt)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            sp.step(10, fixed_dt=fixed_dt)
+            torch.cuda.synchronize()
+            with_species_ms = (time.perf_counter() - t1) / 10 * 1e3
+            sp.ctx.close()
+            del sp
     achieved = B_SEARCH * args.n / (ms_search * 1e-3) / 1e9 if ms_search > 0.0 else None
     tag = workload_tag(args.workload, args.forms, args.species, args.drag)
     prof = search_profile(tag, args.n, args.k)
-    # the a6-inclusive figure beside the core one (nsc.hydro_update always forms F[s,i], nsc:624-627; the headline's step
-    # leaves it out, as `config` says): the same workload with the species pass in the step, a short run outside the timed one
-    with_species_ms = None
-    if not args.species and state.get("f_un") is not None and os.environ.get("SPHX_BENCH_SPECIES_LINE", "1") != "0":
-        sp = Simulation(state, n_neigh=args.k, device=local_rank, gravity=args.gravity, clip_grad=args.clip_grad,
-                        forms=args.forms, d=d_loop, with_species=True, with_drag=args.drag)
-        sp.step(args.warmup, fixed_dt=fixed_dt)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        sp.step(10, fixed_dt=fixed_dt)
-        torch.cuda.synchronize()
-        with_species_ms = (time.perf_counter() - t1) / 10 * 1e3
-        sp.ctx.close()
-        del sp
     ipq = prof.get("valu_wave_instr_per_query")
     valu_achieved = (ipq * args.n / (ms_search * 1e-3) / 1e9) if (ipq and ms_search > 0.0) else None
     b_step = B_STEP_SPECIES if args.species else B_STEP_CORE
@@ -228,6 +309,7 @@ def main():
         "metric": "particle-steps/sec + achieved HBM GB/s, 10^6-particle 3D sphere, 1/2/4/8 GPUs",
         "value": value, "unit": "particle-steps/s", "n_gpus": 1, "steps": args.steps,
         "warmup": args.warmup, "device_warmup_runs_on_scratch_copies": args.device_warmup,
+        "timed_segments": {"segments": segments, "max_timed_steps_per_segment": per_segment, "flow_steps": FLOW_STEPS},
         "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": "%s, N=%d, K=%d, fp64, poly6 kernel, viscosity on" %
@@ -240,13 +322,13 @@ def main():
                    # "experiments=0" with no SPHX_* variable set
                    "build": build_info,
                    "env": {k_: v for k_, v in sorted(os.environ.items()) if k_.startswith("SPHX_")}},
-        "with_species_ms_per_step": with_species_ms,
-        # the reference's scheme can diverge: evidence that the timed window was a sane flow
-        "state_check": {"finite": sane, "max_speed_m_s": vmax,
-                        "max_drift_per_step_in_mean_h": vmax * float(final["dt"]) / float(final["sizes"].mean()),
-                        # the library's own failure counters over the timed steps (sphx_stats.bad_*: by ballot inside the
-                        # update kernels - what the reference's nan_to_num guards hid; no download needed)
-                        "failures": failures},
+        **({"with_species_ms_per_step": with_species_ms,
+            # the reference's scheme can diverge: evidence that the timed window was a sane flow
+            "state_check": {"finite": sane, "max_speed_m_s": vmax,
+                            "max_drift_per_step_in_mean_h": vmax * float(final["dt"]) / float(final["sizes"].mean()),
+                            # the library's own failure counters over the timed steps (sphx_stats.bad_*: by ballot inside
+                            # the update kernels - what the reference's nan_to_num guards hid; no download needed)
+                            "failures": failures}} if args.full else {}),
         # The dominant kernel is the search (knn_group_kernel + the list-mode knn_kernel for what it hands on).  SURVEY
         # 8(d) prices it against HBM (achieved / peak / frac below, live from this run's events); the counters say it
         # is bound by instruction issue and latency, not by HBM: `limiter` and the profiled fractions name that.
@@ -274,10 +356,11 @@ def main():
                        "achieved_GBs": b_step * value / 1e9,
                        "frac_of_hbm_peak": b_step * value / 1e9 / HBM_PEAK_GBS},
         "per_pass_ms": dict({"ms_search": ms_search, "ms_total": st["ms_total"] / max(st["steps"], 1)},
-                            **{k_: st_detail[k_] / max(st_detail["detail_steps"], 1) for k_ in
-                               ("ms_grid", "ms_prep", "ms_density", "ms_species", "ms_pi", "ms_visc", "ms_integrate", "ms_gravity")},
+                            **({k_: st_detail[k_] / max(st_detail["detail_steps"], 1) for k_ in
+                                ("ms_grid", "ms_prep", "ms_density", "ms_species", "ms_pi", "ms_visc", "ms_integrate",
+                                 "ms_gravity")} if args.full else {}),
                             source="ms_search / ms_total: the timed steps (events around the search's launches and around "
-                                   "the whole call); the others: 5 further steps with one timing event per pass "
+                                   "the whole call); the others (--full): 5 further steps with one timing event per pass "
                                    "(sphx_set_timing_detail)"),
         "search": {"candidates_per_particle_step": st["candidates"] / max(st["steps"], 1) / args.n,
                    "retries_per_step": st["retries"] / max(st["steps"], 1), "cells": st["cells"],
@@ -286,7 +369,10 @@ def main():
                    "refresh_steps": st["refresh_steps"], "rebuild_steps": st["rebuild_steps"],
                    "graph_steps": st.get("graph_steps", 0)},
     }
-    if not args.no_cpu:
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "particles": dumped[0], "of": args.n, "sample_seed": DUMP_SEED,
+                                 "visc_heat_nonfinite_zeroed": dumped[1]}
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_n, args.k)
     print(json.dumps(out))
 

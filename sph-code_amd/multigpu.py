@@ -1414,7 +1414,7 @@ def bench_main(args, rank, local_rank, world):
     # the same workload at the per-GPU size on ONE GPU through the fused single-GPU loop (rank 0, before the decomposed
     # run): the denominator a scaling efficiency for THIS workload needs, measured in the same process
     single = None
-    if rank == 0 and world > 1 and os.environ.get("SPHX_BENCH_SINGLE", "1") != "0":
+    if rank == 0 and world > 1 and getattr(args, "full", False) and os.environ.get("SPHX_BENCH_SINGLE", "1") != "0":
         from .sim import Simulation
         sc1 = 1.0 if dilution.startswith("none") else ics.bench_size_scale(args.n)
         s1 = ics.WORKLOADS[args.workload](args.n, size_scale=sc1) if full else ics.WORKLOADS[args.workload](args.n, light=True, size_scale=sc1)
