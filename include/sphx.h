@@ -86,8 +86,7 @@ typedef struct sphx_stats {
     int64_t bad_energy;    /* E or heat x dt NaN or inf before the nan_to_num of drv:490                                    */
     int64_t bad_state;     /* updated position or velocity NaN or inf (the next step's clamp, drv:233-238, catches them)    */
     int64_t bad_h;         /* kNN radius 0 (coincident points), NaN or inf                                                  */
-    int64_t graph_steps;   /* of `steps`: replays of a captured step graph (launch-bound sizes; SPHX_GRAPH)      */
-    int64_t search_steps;  /* steps accumulated in ms_search (replayed steps carry no timing events)                         */
+    int64_t search_steps;  /* steps accumulated in ms_search                                                                */
 } sphx_stats;
 
 /* ---- context ----------------------------------------------------------------------- */
@@ -95,10 +94,10 @@ int         sphx_create(sphx_ctx** out, int device);
 void        sphx_destroy(sphx_ctx* ctx);
 const char* sphx_last_error(const sphx_ctx* ctx);
 int         sphx_version(void);
-/* How the library was built ("gfx950 experiments=0" is the product: timing experiments and diagnostics that add
- * launches or change results exist only in -DSPHX_EXPERIMENTS builds), and the SPHX_* environment variables a context
- * read when it was created ("NAME=value ...": performance tunables only, read once, in sphx_create).  A benchmark line
- * carries both, so that it can be shown to be the configuration the parity tests ran.                           */
+/* How the library was built ("gfx950 experiments=0": it holds no timing experiments or diagnostics that add launches
+ * or change results), and the SPHX_* environment variables a context read when it was created ("NAME=value ...":
+ * performance tunables only, read once, in sphx_create).  A benchmark line carries both, so that it can be shown to be
+ * the configuration the parity tests ran.                                                                         */
 const char* sphx_build_info(void);
 const char* sphx_tunables(const sphx_ctx* ctx);
 /* Hardware self-test of the search's matrix-core cull (sphx_knn_group.hip, phase A): `blocks` random 32 x 32 blocks of

@@ -39,8 +39,8 @@ def _flag_stamp(extra):
 
 
 def _extra_flags():
-    """SPHX_EXTRA_FLAGS, e.g. -DSPHX_EXPERIMENTS (timing experiments / diagnostics: never in the product build) or
-    -DSPHX_KNN_PROF."""
+    """SPHX_EXTRA_FLAGS: further hipcc flags for every source, e.g. -DKNN_MIN_WAVES=5 to try another value of a
+    compile-time tuning constant."""
     return os.environ.get("SPHX_EXTRA_FLAGS", "").split()
 
 

@@ -282,9 +282,6 @@ __device__ __forceinline__ void density_batch(DensAcc& a, const unsigned (&sl)[N
 }
 
 // ---- pass 1: rho, rho_dust, n, grad P        nsc:588-619 --------------------------------------
-// EXP != 0: timing experiments on an extra, discarded launch (SPHX_BLOB_EXP): 1 = staging only,
-// 2 = neighbour loop only (image not filled), 3 = both but no global stores at the end.
-template <int EXP>
 __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_kernel(int n, int npad, int k, int nblk, int clip,
                                                               const int* __restrict__ nbr,
                                                               const u16* __restrict__ slot16,
@@ -303,17 +300,13 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_kernel(int n, 
         const int b = blob_sel_at(sel, bi, nsel);
         const int p = b * BLOB_P + t;
         const int i = (p < n) ? qorder[p] : 0;
-        if (EXP != 2)
-            stage<0>(img, nullptr, tile, rec, nullptr, 0, nullptr, 0, uniq + (size_t)b * BLOB_S, slot16, npad, k, b);
-        else
-            for (int q = threadIdx.x; q < KPAD(k) * BLOB_P; q += PASS_T) tile[q] = (u16)((q * 37 + b) % BLOB_S);
+        stage<0>(img, nullptr, tile, rec, nullptr, 0, nullptr, 0, uniq + (size_t)b * BLOB_S, slot16, npad, k, b);
         const double* self = reinterpret_cast<const double*>(&rec[i]);
         const Q4 s0 = gload4(self), s1 = gload4(self + 4);     // x y z h2 | c1 ms A Nw
         // outputs go to the caller's index o (device API: ghosts, o >= n_active, are candidates only)
         const int o = (p < n) ? (omap ? omap[i] : i) : 0x7FFFFFFF;
         __syncthreads();
-        if (o < n_active && EXP == 1 && s0.a == 1.2345e-300) rho[o] = img[threadIdx.x].x;
-        if (o < n_active && EXP != 1) {
+        if (o < n_active) {
             double xr = s0.a, yr = s0.b, zr = s0.c;
             {
                 const unsigned sl0 = tile[t];
@@ -339,9 +332,7 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_kernel(int n, 
             }
             const double s_rho = group_total(a.rho), s_rd = group_total(a.rd), s_n = group_total(a.n);
             const double gx = group_total(a.gx), gy = group_total(a.gy), gz = group_total(a.gz);
-            if (EXP == 3) {
-                if (s_rho + gx + s_n + s_rd + gy + gz == 1.2345e-300) rho[o] = 0.0;
-            } else if (!half) {
+            if (!half) {
                 rho[o] = s_rho; rhod[o] = s_rd; nden[o] = s_n;
                 rho_s[i] = s_rho;                                     // storage order: staged by pass 2
                 if (G) { G[3 * (size_t)o + 0] = -gx; G[3 * (size_t)o + 1] = -gy; G[3 * (size_t)o + 2] = -gz; }
@@ -1091,14 +1082,6 @@ int sphx_blob_drag(sphx_ctx* ctx, int64_t n, int k, bool count_only, const doubl
     return SPHX_OK;
 }
 
-int sphx_blob_join(sphx_ctx* ctx) {
-    if (ctx->dedup_pending) {
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        ctx->dedup_pending = false;
-    }
-    return SPHX_OK;
-}
-
 BlobSel sphx_blob_sel(sphx_ctx* ctx, int part) {
     if (!ctx->blob_split_valid) return BlobSel{nullptr, nullptr, 0};
     const int* list = ctx->blob_split.as<int>();
@@ -1116,16 +1099,8 @@ int sphx_blob_grid(sphx_ctx* ctx, int nblk) {
 
 static int blob_attr_once(sphx_ctx* ctx) {
     if (ctx->blob_attr_set) return SPHX_OK;
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_density_kernel<0>),
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_density_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(64, SPHX_MAX_K)));
-#ifdef SPHX_EXPERIMENTS
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_density_kernel<1>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_density_kernel<2>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_density_kernel<3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#endif
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_pi_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(72, SPHX_MAX_K)));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_visc_kernel),
@@ -1138,36 +1113,7 @@ int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k) {
     SPHX_TRY(blob_attr_once(ctx));
     const int64_t npad = sphx_pad64(n);
     const int nblk = (int)((npad + BLOB_P - 1) / BLOB_P);
-#ifdef SPHX_EXPERIMENTS
-    if (ctx->exp_blob) {        // timing experiments (SPHX_BLOB_EXP), outputs discarded
-        SPHX_TRY(sphx_ensure(ctx, ctx->in_j, (size_t)n * 12 * sizeof(double)));
-        double* d = ctx->in_j.as<double>();
-        size_t lds = IMG_BYTES(64, k);
-        if (ctx->exp_blob_lds) lds = ctx->exp_blob_lds;      // e.g. 100000: one workgroup per CU
-        for (int mode = 0; mode < 4; ++mode) {
-            if (!(ctx->exp_blob & (1 << mode))) continue;
-            hipEvent_t e0, e1;
-            HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-            HIPCHK(hipEventRecord(e0, ctx->stream));
-#define BLOB_EXP_LAUNCH(M)                                                                                           \
-            hipLaunchKernelGGL(blob_density_kernel<M>, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), lds, ctx->stream, (int)n, (int)npad, \
-                               k, nblk, ctx->clip_grad, ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(), ctx->qorder, \
-                               nullptr, (int)n, ctx->rec1.as<RecA>(), d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, d + 8 * n, \
-                               BlobSel{nullptr, nullptr, 0})
-            if (mode == 0) BLOB_EXP_LAUNCH(0);
-            else if (mode == 1) BLOB_EXP_LAUNCH(1);
-            else if (mode == 2) BLOB_EXP_LAUNCH(2);
-            else BLOB_EXP_LAUNCH(3);
-            HIPCHK(hipEventRecord(e1, ctx->stream));
-            HIPCHK(hipEventSynchronize(e1));
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-            fprintf(stderr, "[sphx] blob_density experiment %d (lds %zu): %.4f ms\n", mode, lds, ms);
-            (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        }
-    }
-#endif
-    hipLaunchKernelGGL(blob_density_kernel<0>, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(64, k), ctx->stream, (int)n, (int)npad, k, nblk, ctx->clip_grad,
+    hipLaunchKernelGGL(blob_density_kernel, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(64, k), ctx->stream, (int)n, (int)npad, k, nblk, ctx->clip_grad,
                        ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(),
                        ctx->qorder, ctx->map_perm, ctx->map_perm ? ctx->map_nactive : (int)n, ctx->rec1.as<RecA>(),
                        ctx->rho_s.as<double>(), ctx->rho.as<double>(),

@@ -356,19 +356,14 @@ __global__ __launch_bounds__(256) void lookback_scan_kernel(int n_items, int* __
         for (int q = 0; q < LBS_ITEMS; ++q) { if (base + q < n_items) out[base + q] = ex; ex += v[q]; }
     }
 }
-// zero_in: the items are put back to zero once read (*zeroed says whether that happened: rocPRIM's scan does not)
-static int excl_scan_plus_total(sphx_ctx* ctx, const int* in, int* out, int n, bool zero_in = false, bool* zeroed = nullptr) {
+// zero_in: the items are put back to zero once read (*zeroed says whether that happened: rocPRIM's scan does not).
+// rocPRIM's scan where the single-launch one cannot run (misaligned arrays, too many tiles), or where the caller asks for it.
+static int excl_scan_plus_total(sphx_ctx* ctx, const int* in, int* out, int n, bool zero_in = false, bool* zeroed = nullptr,
+                                bool use_rocprim = false) {
     if (zeroed) *zeroed = false;
-    if (ctx->scan_rocprim || (((uintptr_t)in | (uintptr_t)out) & 15)) {
-        size_t bytes = 0;
-        HIPCHK(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, (size_t)n + 1, rocprim::plus<int>(), ctx->stream));
-        SPHX_TRY(sphx_ensure(ctx, ctx->scan_tmp, bytes + 64));
-        HIPCHK(rocprim::exclusive_scan(ctx->scan_tmp.p, bytes, in, out, 0, (size_t)n + 1, rocprim::plus<int>(), ctx->stream));
-        return SPHX_OK;
-    }
     const int n_items = n + 1;
     const int ntiles = (n_items + LBS_TILE - 1) / LBS_TILE;
-    if (ntiles > LBS_MAXTILES) {
+    if (use_rocprim || (((uintptr_t)in | (uintptr_t)out) & 15) || ntiles > LBS_MAXTILES) {
         size_t bytes = 0;
         HIPCHK(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, (size_t)n + 1, rocprim::plus<int>(), ctx->stream));
         SPHX_TRY(sphx_ensure(ctx, ctx->scan_tmp, bytes + 64));
@@ -378,13 +373,11 @@ static int excl_scan_plus_total(sphx_ctx* ctx, const int* in, int* out, int n, b
     // (one set of tile words per stream the scans are launched on: launches on ONE stream are ordered, two streams are not)
     const int which = (ctx->stream == ctx->own_stream) ? 0 : 1;
     DevBuf& st = ctx->lbs_state[which];
-    const size_t need = ((size_t)LBS_MAXTILES + 8) * sizeof(u64);          // (one size for every scan: nothing to allocate later, e.g. while a step graph is recorded)
+    const size_t need = ((size_t)LBS_MAXTILES + 8) * sizeof(u64);          // (one size for every scan: allocated once)
     if (st.cap < need) {
         SPHX_TRY(sphx_ensure(ctx, st, need));
         HIPCHK(hipMemsetAsync(st.p, 0, st.cap, ctx->stream));
     }
-    // (a recorded launch is replayed with the epoch it was recorded with: its words are cleared by a node of the graph)
-    if (ctx->capturing) HIPCHK(hipMemsetAsync(st.as<u64>() + 2, 0, (size_t)ntiles * sizeof(u64), ctx->stream));
     unsigned& ep = ctx->lbs_epoch[which];
     ep = (ep + 1u) & 0x3FFFFFFFu;
     if (ep == 0u) ep = 1u;
@@ -427,12 +420,8 @@ extern "C" int sphx_selftest_scan(sphx_ctx* ctx, int n, unsigned seed, long long
         if ((rc = sphx_ensure(ctx, bad, 64)) != SPHX_OK) break;
         hipLaunchKernelGGL(scan_selftest_fill, dim3(1024), dim3(256), 0, ctx->stream, n, seed, in.as<int>());
         if (hipMemsetAsync(bad.p, 0, 8, ctx->stream) != hipSuccess) { rc = SPHX_E_HIP; break; }
-        const bool keep = ctx->scan_rocprim;
-        ctx->scan_rocprim = false;
         rc = excl_scan_plus_total(ctx, in.as<int>(), o1.as<int>(), n);
-        ctx->scan_rocprim = true;
-        if (rc == SPHX_OK) rc = excl_scan_plus_total(ctx, in.as<int>(), o2.as<int>(), n);
-        ctx->scan_rocprim = keep;
+        if (rc == SPHX_OK) rc = excl_scan_plus_total(ctx, in.as<int>(), o2.as<int>(), n, false, nullptr, true);
         if (rc != SPHX_OK) break;
         hipLaunchKernelGGL(scan_selftest_cmp, dim3(1024), dim3(256), 0, ctx->stream, n, o1.as<int>(), o2.as<int>(),
                            bad.as<unsigned long long>());
@@ -608,16 +597,7 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
     for (int c = 0; c < 3; ++c) { clip0.lo[c] = ctx->clip_lo[c]; clip0.hi[c] = ctx->clip_hi[c]; }
     bool fused = false;           // this step's statistics come out of the cell-count kernel itself
     int lag_cur = 0;
-    ctx->grid_fused = false;
-    if (!ctx->in_fused_step) sphx_graph_drop(ctx);      // (an array call or the device API between the loop's steps: its grid, its box statistics)
-    if (ctx->capturing) {
-        // recorded into a step graph: the box statistics the last real step sized its grid from, no host wait; this step's
-        // own statistics still come out of the count kernel (tbox, on the device), but are not copied out
-        if (!ctx->lag_on || !ctx->fuse_count) return sphx_set_err(ctx, SPHX_E_STATE, "only the fused loop's grid build can be captured");
-        for (int q = 0; q < 13; ++q) bb[q] = ctx->cap_bb[q];
-        fused = true;
-        ctx->grid_fused = true;
-    } else if (ctx->lag_on) {
+    if (ctx->lag_on) {
         // Fused step loop: this step's statistics are launched and copied out, the grid is sized from
         // the previous step's (already on the host) - the loop never waits for the step it launches.
         // One step of motion makes the box slightly stale, which only steers performance: particles
@@ -630,7 +610,7 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         const int64_t pn = ctx->lag_bn[prev];
         const int use = (ctx->lag_bvalid[prev] && pn > 0 && (n > pn ? n - pn : pn - n) * 4 <= n) ? prev : cur;
         lag_cur = cur;
-        fused = (use == prev) && ctx->fuse_count;
+        fused = use == prev;
         if (!fused) {
             if (ctx->clamp_vx) { SPHX_TRY(sphx_clamp(ctx, n, ctx->st)); ctx->clamp_vx = nullptr; }
             SPHX_TRY(bbox_launch(ctx, n, x, y, z, true, slot + 512 * cur));
@@ -642,18 +622,14 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         ctx->lag_bvalid[cur] = true;
         ctx->lag_bn[cur] = n;
         ctx->lag_bslot = cur;
-        ctx->grid_fused = fused;
     } else {
         if (ctx->clamp_vx) { SPHX_TRY(sphx_clamp(ctx, n, ctx->st)); ctx->clamp_vx = nullptr; }
         SPHX_TRY(sphx_bbox(ctx, n, x, y, z, bb, true));
     }
-    if (!ctx->capturing && ctx->clip_valid && bb[12] < 0.5 * (double)n) {     // the clip box lost the cloud: re-anchor
+    if (ctx->clip_valid && bb[12] < 0.5 * (double)n) {     // the clip box lost the cloud: re-anchor
         if (ctx->clamp_vx) { SPHX_TRY(sphx_clamp(ctx, n, ctx->st)); ctx->clamp_vx = nullptr; }
         SPHX_TRY(sphx_bbox(ctx, n, x, y, z, bb, false));
-        ctx->grid_fused = false;                // (a host wait: not a step to replay)
     }
-    if (!ctx->capturing)
-        for (int q = 0; q < 13; ++q) ctx->cap_bb[q] = bb[q];     // (what a captured step sizes its grid from)
     double tmin[3], tmax[3];
     for (int c = 0; c < 3; ++c) {
         if (!(bb[3 + c] >= bb[c])) { bb[c] = 0.0; bb[3 + c] = 0.0; }   // no finite coordinate
@@ -693,7 +669,6 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
     int64_t cap = 32 * n + 1024;      // cells per particle the grid may use when a diffuse halo stretches the box
     if (cap > SPHX_MAX_CELLS) cap = SPHX_MAX_CELLS;
     if (ctx->max_cells > 0 && cap > ctx->max_cells) cap = ctx->max_cells;
-    if (ctx->max_cells < 0) { cap = 32 * n + 1024; if (cap > -ctx->max_cells) cap = -ctx->max_cells; }   // experiment: beyond the default limit
     int nx, ny, nz;
     for (;;) {
         nx = (int)fmin(floor(L[0] / cell) + 1.0, 2047.0);
@@ -763,11 +738,8 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         fa.partial = part; fa.ticket = ticket; fa.fin = fin;
         fa.ct_reset = ctx->scal.as<u64>() + SC_CT_BITS;      // (read by the previous step's update, long done on this stream)
         fa.zero_int = nullptr;
-        fa.rank = nullptr;
-        if (ctx->scatter_by_rank) {
-            SPHX_TRY(sphx_ensure(ctx, ctx->cell_rank, (size_t)n * sizeof(int)));
-            fa.rank = ctx->cell_rank.as<int>();
-        }
+        SPHX_TRY(sphx_ensure(ctx, ctx->cell_rank, (size_t)n * sizeof(int)));
+        fa.rank = ctx->cell_rank.as<int>();
         rank_dev = fa.rank;
         if (ctx->fail_list.p && ctx->fail_list.cap >= ((size_t)sphx_pad64(n) + 64) * sizeof(int)) {
             fa.zero_int = ctx->fail_list.as<int>() + sphx_pad64(n);          // (where sphx_knn keeps the counter for this n)
@@ -793,12 +765,12 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
     SPHX_TRY(excl_scan_plus_total(ctx, fill, start, nc, rank_dev != nullptr, &hist_zeroed));
     // (the statistics folded by the scatter's first blocks go straight to the pinned slot the next step's host code reads:
     //  the 104-byte copy that followed was a launch of its own on the step's stream, 5 us + its gaps)
-    const bool to_host = bb_fold_part != nullptr && bb_fold_out && !ctx->capturing && pb >= BB_W && ctx->bb_direct;
+    const bool to_host = bb_fold_part != nullptr && bb_fold_out && pb >= BB_W;
     double* bb_host = to_host ? reinterpret_cast<double*>((char*)ctx->pinned + LAG_OFF + 512 * lag_cur) : nullptr;
     hipLaunchKernelGGL(cell_scatter, dim3(pb), dim3(256), 0, ctx->stream, (int)n,
                        ctx->cell_of.as<int>(), start, fill, ctx->perm.as<int>(), bb_fold_blocks, bb_fold_part, bb_fold_out, bb_host, rank_dev);
     if (rank_dev && !hist_zeroed) HIPCHK(hipMemsetAsync(fill, 0, ((size_t)nc + 1) * sizeof(int), ctx->stream));     // (rocPRIM's scan left the counts in place)
-    if (bb_fold_out && !ctx->capturing) {
+    if (bb_fold_out) {
         char* slot = (char*)ctx->pinned + LAG_OFF;
         if (!to_host)
             HIPCHK(hipMemcpyAsync(slot + 512 * lag_cur, bb_fold_out, BB_W * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

@@ -137,8 +137,8 @@ struct sphx_ctx {
     hipStream_t stream = nullptr;       // stream every launch goes to (own_stream or the caller's)
     hipStream_t own_stream = nullptr;
     hipStream_t side_stream = nullptr;  // independent work beside the main chain (record build while the lists are deduplicated)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_perm_fork = nullptr, ev_perm = nullptr;   // the state's permutation split over the two streams (sphx_permute_state)
+    hipEvent_t ev_join = nullptr;
+    hipEvent_t ev_perm = nullptr;       // the state's permutation split over the two streams (sphx_permute_state)
     double dev_hmean = 0.0;             // device API: mean h of the previous search (cell size)
     bool knn_hint_by_id = false;        // device API: search-radius hints are in caller order
     char err[512] = {0};
@@ -199,7 +199,6 @@ struct sphx_ctx {
     AgbTable agb;
     DevBuf agb_knots, Zmet, agb_dust;
     // the fused loop's first pass (sphx_grid.hip grid_count_fused): clamp + box statistics + cell histogram in one kernel
-    bool fuse_count = true;               // SPHX_FUSE_COUNT=0: the separate kernels
     double *clamp_vx = nullptr, *clamp_vy = nullptr, *clamp_vz = nullptr;   // set by the step: the grid build applies drv:233-238
     bool bbox_ticket_zeroed = false;
     bool defer_cell_sort = false, cells_unsorted = false;   // the per-cell member sort rides in the blob-order pass
@@ -209,7 +208,6 @@ struct sphx_ctx {
     BlobBits blob_scatter_bits;
     const int* blob_scatter_mstart = nullptr;
     bool species_lds = true;        // SPHX_SPECIES_LDS=0: the species pass by gathers (sphx_sums.hip) also when blob lists exist
-    bool split_perm = true;         // SPHX_SPLIT_PERM=0: the whole state permuted in one launch before the search
     bool use_group = true;          // hinted searches by the lane-per-query grouped kernel (SPHX_KNN_GROUP=0: off)
     bool knn_hinted = false;        // set by the callers of sphx_knn whose rsearch holds real previous radii
     DevBuf fail_list;               // queries the grouped kernel hands to the general one (+ their count)
@@ -225,14 +223,9 @@ struct sphx_ctx {
     int64_t farq_last = 0;          // far queries met by the previous hinted search
     DevBuf lbs_state[2];                   // tile words of the look-back scan (sphx_grid.hip), per launching stream
     unsigned lbs_epoch[2] = {0u, 0u};
-    bool bb_direct = true;                 // the grid build's box statistics written to pinned memory by the kernel that folds them
     bool species_fused = true;             // the step's species pass inside pass 1's kernel (SPHX_SPECIES_FUSED=0: a kernel of its own)
     DevBuf cell_rank;                       // the particles' arrival numbers in their cells (grid build)
-    bool scatter_by_rank = true;           // SPHX_SCATTER_RANK=0: the scatter hands out slots with an atomic of its own
-    bool stream_prio = true;               // main stream at the highest, side stream at the lowest device priority
-    bool scan_rocprim = false;             // SPHX_SCAN_ROCPRIM=1: rocPRIM's scan instead
     DevBuf tie_list;                       // int4 {query slot, rank, index a, index b}: near ties the grouped search leaves to the list-mode launch's tie blocks
-    bool tie_fix = true;
     const void* fcount_zeroed = nullptr;   // the fail-list allocation whose counter the grid build has zeroed for this step
     int64_t fcount_zeroed_n = 0;
     int64_t list_len_last = 0;      // queries the previous hinted search left to the general kernel (sizes the list-mode grid)
@@ -266,12 +259,7 @@ struct sphx_ctx {
     int blob_split_nblk = 0;
     bool loop2_interior_done = false;
     bool drag_attr_set = false, drag_lds = true;
-    bool dedup_pending = false;     // device API: the dedup of the last search runs on the side stream (joined by sphx_blob_join)
-    // (off: measured at one rank, 10^6 particles - dedup 109 -> 169 us and the record build 73 -> 95 us when they run side
-    //  by side, both HBM-bound: the pair takes the 182 us it takes back to back.  SPHX_DEV_FORK_DEDUP=1 to try it where
-    //  the main stream would otherwise wait for the network between the search and the first pass)
-    bool dev_fork_dedup = false;
-    int64_t max_cells = 0;          // SPHX_MAX_CELLS: > 0 lowers the limit on grid cells, < 0 (experiment) raises it to |value|
+    int64_t max_cells = 0;          // SPHX_MAX_CELLS: > 0 lowers the limit on grid cells
     double reach_cap = 0.0;         // sphx_dev_set_reach_cap: head-room of a claimed reach limited to this length (0: not)
     int pass_part = 0;              // which blobs hydro_update's passes and the record build take: 0 all, 1 interior, 2 boundary
     bool blob_attr_set = false;
@@ -297,30 +285,8 @@ struct sphx_ctx {
     // The update writes the new temperatures into alt.T (dead once the state has been permuted) and swaps it with st.T:
     // what is left in alt.T is T at the instant of the step's sums, in the step's sorted order like rho / nden - P_i = n_i
     // k_B T_i of ONE instant at no cost to the step (sphx_state_download_pressure).  (st.T and alt.T are then the same two
-    // buffers at the start of every step; the other arrays of st / alt swap roles every step: period 2, which the step
-    // graphs below rely on.)
+    // buffers at the start of every step; the other arrays of st / alt swap roles every step.)
     bool tprev_valid = false;
-    // ---- step graphs (sphx_api.hip sphx_step): the launch-bound sizes.  A quiet step's ~25 launches replayed as a hipGraph
-    // cost half the launch overhead of the stream (tools/graphrate.hip: 25 dependent small kernels 100 -> 50 us).  One REAL
-    // step sizes the grid and takes the search's decisions from the lagged read-backs as always; the next two steps are
-    // CAPTURED with those decisions frozen (one per parity of the double-buffered state) and then replayed alternately for
-    // up to graph_epoch steps - the grid box and cell size only steer performance (out-of-box particles are clamped into the
-    // boundary cells, which the search handles exactly), and every replayed step still computes its own true bounding box on
-    // the device.  Frozen too: the list-mode launch's grid, no outlier levels (a state that needs them is not replayed).
-    int graph_mode = 0;                 // SPHX_GRAPH: 0 never (default: measured slower), 1 whenever a step can be replayed, 2 for n <= graph_max_n
-    int64_t graph_max_n = 200000;       // SPHX_GRAPH_MAX_N
-    int graph_epoch = 64;               // SPHX_GRAPH_EPOCH: replays between two real steps
-    bool in_fused_step = false;         // sphx_build_grid is being called by the fused loop's step (any other grid build drops the graphs)
-    bool grid_fused = false;            // the last grid build took its statistics from the fused count kernel (no host wait)
-    bool capturing = false;             // one_step is being recorded, not run: no host waits, no timing events, no read-backs
-    bool replay_ok = false;             // the last real step left decisions a replay may freeze (hinted, fused, no levels ...)
-    hipGraphExec_t gexec[2] = {nullptr, nullptr};      // by parity of step_count
-    hipGraphExec_t retired[16] = {nullptr};            // forgotten, possibly still running: destroyed behind the next stream wait
-    int n_retired = 0;
-    int graph_k = 0; double graph_dist = 0.0, graph_fixed_dt = 0.0;     // the sphx_step arguments the graphs were captured with
-    int graph_left = 0;                 // replays left in this epoch
-    double cap_bb[13] = {0}, cap_cell_hint = 0.0, cap_h_clip = 0.0;   // what the real step read from the lagged slots
-    int64_t graph_steps = 0;            // steps that were replays (statistics)
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     bool has_state = false;
     int64_t step_count = 0;
@@ -331,8 +297,6 @@ struct sphx_ctx {
     // box statistics and mean h - are taken from the PREVIOUS step's copies (slots in `pinned` at
     // LAG_OFF; the grid box only steers performance: out-of-box particles are clamped into the
     // boundary cells, which the search handles exactly).
-    // timing experiments (SPHX_KNN_ABL / SPHX_BLOB_EXP / SPHX_BLOB_EXP_LDS / SPHX_PASS_EXP: an extra,
-    // discarded launch of a cut-down kernel), read from the environment once, at sphx_create
     const void* cell_fill_zeroed = nullptr;   // the cell_fill allocation known to be all zero between grid builds
     // the K-major list in `nbr` is the caller-order list of the last array-API call with this shape
     // (a later call may pass neighbor == NULL instead of uploading the same (N, K) int64 array again)
@@ -342,9 +306,6 @@ struct sphx_ctx {
     bool ct_primed = false;             // SC_CT_BITS holds "none yet" (left so by dt_kernel)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
     DevBuf hsum_tmp;                    // hsum_kernel's per-block partial sums + its ticket
-    int exp_knn = -1, exp_blob = 0, exp_pass = -1;      // (-DSPHX_EXPERIMENTS builds only: never set otherwise)
-    size_t exp_blob_lds = 0;
-    bool exp_no_agb = false, knn_prof_print = false, kg_debug_print = false;
     char tunables[1024] = {0};          // "NAME=value ..." of every SPHX_* variable sphx_create read (sphx_tunables)
     hipEvent_t evring[3][10] = {{nullptr}};
     bool timing_detail = false;         // per-pass timing events in sphx_step (sphx_set_timing_detail)
@@ -365,8 +326,6 @@ struct sphx_ctx {
 };
 
 int sphx_set_err(sphx_ctx* ctx, int code, const char* fmt, ...);
-void sphx_graph_drop(sphx_ctx* ctx);      // forget the step graphs (new state, other step mode ...)
-void sphx_graph_reap(sphx_ctx* ctx);      // ... and destroy them, once the stream has been waited for
 int sphx_ensure(sphx_ctx* ctx, DevBuf& b, size_t bytes);
 
 #define HIPCHK(expr)                                                                         \
@@ -424,8 +383,7 @@ enum {
     SC_CROWDED = 13,  // u64, only grows: cells of 17 .. 512 members met by blob_count (sorted by a launch of their own when many)
     SC_DENSEP = 14,   // u64, only grows: particles in cells of >= DENSE_CELL members (a tile's 27 such cells overflow it)
     SC_KGDBG = 16,    // u64[8]: grouped search, queries handed on by reason (diagnostics)
-    SC_KNNPROF = 24,  // u64[16]: general search, cycles / queries / longest / tries by query class (-DSPHX_KNN_PROF builds)
-    SC_NSLOTS = 48
+    SC_NSLOTS = 24
 };
 
 // Failure counters (the reference's only guard is the nan_to_num of drv:233-238, 460-463, 490-491), u64 and
@@ -468,8 +426,6 @@ static inline double sphx_cell_feedback(sphx_ctx* ctx, int64_t n) {
 int sphx_blob_translate(sphx_ctx* ctx, int64_t n, int k);
 int sphx_blob_density_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted,
                               double* F, double* Z, double* agb, int agb_on);
-// device API: the main stream waits for the slot lists of the last search (built beside the record build / the h_j phase)
-int sphx_blob_join(sphx_ctx* ctx);
 int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k);
 int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits);
 int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m);
@@ -531,7 +487,7 @@ int sphx_transpose_nbr(sphx_ctx* ctx, int64_t n, int k, const int64_t* nb_rowmaj
 
 // integrate / layout helpers (sphx_integrate.hip)
 int sphx_clamp(sphx_ctx* ctx, int64_t n, StateArrays& s);
-int sphx_permute_state(sphx_ctx* ctx, int64_t n, bool split = false, hipEvent_t after_first = nullptr);
+int sphx_permute_state(sphx_ctx* ctx, int64_t n, bool split, hipEvent_t after_first);
 int sphx_hsum(sphx_ctx* ctx, int64_t n, const double* h);
 int sphx_compute_dt(sphx_ctx* ctx, int first, double fixed_dt);
 int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt = 0, int first = 0, double fixed_dt = 0.0);

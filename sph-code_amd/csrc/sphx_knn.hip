@@ -71,7 +71,6 @@ struct KnnArgs {
 
 // Sort the `cnt` staged entries at ring position `head` ascending by (key, index) into (ck, cv);
 // lanes >= cnt get the (INF, ~0) padding.  r2 = trial radius^2 bounds every staged key.
-template <int ABL>
 __device__ __forceinline__ void sort_staged(const u64* skey, const u32* sid, int head, int cnt, double r2,
                                             int lane, u64& ck, u32& cv) {
     ck = KNN_INF;
@@ -80,7 +79,6 @@ __device__ __forceinline__ void sort_staged(const u64* skey, const u32* sid, int
         ck = skey[(head + lane) & 127];
         cv = sid[(head + lane) & 127];
     }
-    if (ABL == 1) return;              // timing experiment: no ordering network
     // degenerate radius (0 or overflowed): every key lands in bin 0 and the exact odd-even
     // fix-up below does all the ordering (slow, correct, practically never taken)
     // (any positive scale orders correctly - ties are repaired below - so the hardware reciprocal will do)
@@ -154,24 +152,19 @@ __device__ __forceinline__ void block27_count(const GridParams& g, const int* ce
 #ifndef KNN_MIN_WAVES
 #define KNN_MIN_WAVES 6      // waves per SIMD the register budget is held to (6 -> <= 80 VGPRs; measured fastest)
 #endif
-// ABL != 0: timing experiments with a section removed (outputs are then meaningless and are
-// never written: the wrapper passes null output pointers); ABL == 0 is the product kernel.
 // LEAN = 1: the step loop's variant - only the K-major list and h (sorted order) are produced,
 // so the API / Verlet-list pointers are never loaded (17 pointers in SGPRs otherwise: measured
 // 20 % slower).  LEAN = 2: the same for the device API (h written by id).
 // OUTL = 1 (list mode only): a query OUTSIDE the grid box whose search sphere is wider than OLEV_MIN_RC cells does not walk
 // the grid's boundary faces (every escaper hashed there: whole faces of one-particle rows) but the outlier levels its
 // sphere can reach (OutLevels) and then the grid with the outliers filtered out - the same candidates, each exactly once.
-#ifndef SPHX_KNN_PROF_LONG
-#define SPHX_KNN_PROF_LONG 10000000ull     // -DSPHX_KNN_PROF builds: a query taking more cycles than this is described
-#endif
 #ifndef KNN_LIST_WAVES
 #define KNN_LIST_WAVES 4     // list / outlier-level variants: fewer, fatter waves (the prefetched batch needs registers)
 #endif
 #ifndef KNN_OUTL_WAVES
 #define KNN_OUTL_WAVES 3     // the variants that also walk the outlier levels: 168 VGPRs instead of 128 + 130..170 B of scratch (search -1..2 % on the cube and the blast)
 #endif
-template <int ABL, int LEAN = 0, int LIST = 0, int OUTL = 0>
+template <int LEAN = 0, int LIST = 0, int OUTL = 0>
 __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_WAVES : KNN_MIN_WAVES) void knn_kernel(KnnArgs a) {
     extern __shared__ int tile_dyn[];                 // [K][KNN_PPB + 1] result tile (sized at launch)
 #define tile(kk, li) tile_dyn[(kk) * (KNN_PPB + 1) + (li)]
@@ -216,10 +209,6 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
     int* rbase = row_base[wave];
     for (int q = lane; q < KNN_FLAG_CAP / 4; q += 64) reinterpret_cast<u32*>(rflag)[q] = 0u;
     u64 ncand = 0, nretry = 0, nshort = 0, nfar = 0, nbad = 0;
-#ifdef SPHX_KNN_PROF
-    u64 p_sum[2] = {0, 0}, p_n[2] = {0, 0}, p_max[2] = {0, 0}, p_tries[2] = {0, 0};
-    u64 p_sec[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};      // row set-up, candidates, ranking (cycles); batches of rows
-#endif
 
     do {
     // list mode: 4 queries per wave and pass instead of 16 - the list is short (a few per cent of the queries), so
@@ -296,12 +285,6 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
             }
             occm = __builtin_amdgcn_ballot_w64(c_lv > 0);
         }
-#ifdef SPHX_KNN_PROF
-        const long long prof_t0 = clock64();
-        const u64 prof_c0 = ncand;
-        int prof_cat = q_out ? 3 : 0;
-        u64 q_sec[4] = {0, 0, 0, 0};
-#endif
         // A stale hint: the particle has moved (a diverging run moves it by several h per step) into a neighbourhood far
         // denser than its previous radius implies - the 3x3x3 block of cells around it alone holds many times what a sphere
         // of that radius should.  The hinted sphere would then cover thousands of times the candidates needed (the whole
@@ -319,9 +302,6 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
                     const double dens = (double)cnt / ((double)nc * g.cell * g.cell * g.cell);
                     const double Re = 1.3 * cbrt((double)K / (4.1887902047863905 * dens));
                     if (Re < R) { R_hint = R; R = Re; }
-#ifdef SPHX_KNN_PROF
-                    if (R_hint > 0.0) prof_cat = 1;
-#endif
                 }
             }
         }
@@ -365,9 +345,6 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
                     (void)frexp(mq / a.ol.hmax, &e);
                     lv_own = e < lv_lo ? lv_lo : (e > lv_hi ? lv_hi : e);
                     multi = true;
-#ifdef SPHX_KNN_PROF
-                    prof_cat = 2;
-#endif
                 }
             }
             bool own_done = false;
@@ -438,11 +415,7 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
             // (its fp64 quantities are recomputed per batch of rows from what is live anyway - held across the candidate
             //  loop they cost every query of the list-mode launch 40 B of scratch per lane: list mode +10..20 %)
 
-            for (int rb = 0; rb < (ABL == 3 ? 0 : nrows); rb += 64) {
-#ifdef SPHX_KNN_PROF
-                const long long ts0 = clock64();
-                u64 d_iter = 0;
-#endif
+            for (int rb = 0; rb < nrows; rb += 64) {
                 // ---- one lane per (cy,cz) row of cells: clip the row to the search SPHERE ----
                 const int r = rb + lane;
                 int s_row = 0, cnt = 0;
@@ -519,10 +492,6 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
                 const int sb = s_row - (incl - cnt);      // candidate slot t of row r is particle sb[r] + t
                 const int T = __builtin_amdgcn_readlane(incl, 63);
                 ncand += (u64)T;
-#ifdef SPHX_KNN_PROF
-                const long long ts1 = clock64();
-                q_sec[0] += (u64)(ts1 - ts0); q_sec[3] += 1;
-#endif
 
                 const int off = incl - cnt;
                 // Slot -> particle map.  Non-empty rows are compacted (rbase[ordinal] = sb) and each
@@ -567,7 +536,7 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
                 };
                 // list mode is bound by the latency of its longest queries (one wave walking thousands of batches): the
                 // next batch's positions are requested before this one's are looked at
-                constexpr bool PIPE = (LIST || OUTL) && ABL == 0;
+                constexpr bool PIPE = LIST || OUTL;
                 int p_next = 0;
                 double nxp = 0.0, nyp = 0.0, nzp = 0.0;
                 if (PIPE && T > 0) {
@@ -576,7 +545,7 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
                     nxp = *(const double*)((const char*)a.x + bo); nyp = *(const double*)((const char*)a.y + bo);
                     nzp = *(const double*)((const char*)a.z + bo);
                 }
-                for (int t0 = 0; t0 < (ABL == 2 ? 0 : T); t0 += 64) {
+                for (int t0 = 0; t0 < T; t0 += 64) {
                     const int t = t0 + lane;
                     const bool valid = t < T;
                     int p;
@@ -606,7 +575,7 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
                     const bool keep = valid && key < tk;
                     const u64 mask = __builtin_amdgcn_ballot_w64(valid) & __builtin_amdgcn_ballot_w64(key < tk);
                     const int c = __popcll(mask);
-                    if (c && ABL != 4) {
+                    if (c) {
                         if (keep) {
                             int pos = (head + nst + lanes_below(mask)) & 127;
                             skey[pos] = key;
@@ -614,12 +583,9 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
                         }
                         nst += c;
                         if (nst >= 64) {
-#ifdef SPHX_KNN_PROF
-                            const long long td0 = clock64();
-#endif
                             wave_sync();
                             u64 ck; u32 cv;
-                            sort_staged<ABL>(skey, sid, head, 64, R2, lane, ck, cv);
+                            sort_staged(skey, sid, head, 64, R2, lane, ck, cv);
                             wave_sync();
                             head = (head + 64) & 127;
                             nst -= 64;
@@ -641,9 +607,6 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
                                 const float rk = (float)rkd * 1.00001f + 2e-3f;
                                 Rc2 = fminf(Rc2, rk * rk);
                             }
-#ifdef SPHX_KNN_PROF
-                            d_iter += (u64)(clock64() - td0);
-#endif
                         }
                     }
                 }
@@ -652,16 +615,13 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
                     if (ne) rflag[off] = 0;
                     wave_sync();
                 }
-#ifdef SPHX_KNN_PROF
-                q_sec[1] += (u64)(clock64() - ts1) - d_iter; q_sec[2] += d_iter;
-#endif
             }
             if (!OUTL || !multi || lv == 0) break;
             // between structures: rank what is staged; with K candidates in hand nothing beyond the K-th can matter
             if (nst > 0) {
                 wave_sync();
                 u64 ck; u32 cv;
-                sort_staged<ABL>(skey, sid, head, nst, R2, lane, ck, cv);
+                sort_staged(skey, sid, head, nst, R2, lane, ck, cv);
                 wave_sync();
                 head = (head + nst) & 127;
                 nst = 0;
@@ -694,7 +654,7 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
             if (nst > 0) {
                 wave_sync();
                 u64 ck; u32 cv;
-                sort_staged<ABL>(skey, sid, head, nst, R2, lane, ck, cv);
+                sort_staged(skey, sid, head, nst, R2, lane, ck, cv);
                 wave_sync();
                 if (have_best) {
                     merge_sorted(bk, bv, ck, cv, lane);
@@ -717,8 +677,7 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
             }
             saw_all = covers;
             done = full || covers || at_bound || (++tries >= KNN_MAX_TRIES);
-            if (ABL == 0 && !full && !covers && !at_bound && tries >= KNN_MAX_TRIES) ++nshort;   // gave up short: reported
-            if (ABL != 0) done = true;    // timing experiments never retry
+            if (!full && !covers && !at_bound && tries >= KNN_MAX_TRIES) ++nshort;   // gave up short: reported
             if (!done) {
                 double grow = 1.6;
                 if (LIST || a.distrust) {
@@ -744,20 +703,6 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
         const double d = valid ? sqrt(__longlong_as_double((long long)bk)) : 0.0;
         const double dlast = __shfl(d, found > 0 ? found - 1 : 0, 64);
         const double hval = found > 0 ? dlast : 0.0;
-#ifdef SPHX_KNN_PROF
-        {
-            const u64 dtc = (u64)(clock64() - prof_t0);
-            const int pc = prof_cat >= 2 ? 1 : 0;
-            p_sum[pc] += dtc; p_n[pc] += 1; p_tries[pc] += (u64)(tries + 1);
-            for (int q = 0; q < 4; ++q) p_sec[pc][q] += q_sec[q];
-            if (dtc > p_max[pc]) p_max[pc] = dtc;
-            if (dtc > SPHX_KNN_PROF_LONG && lane == 0 && a.counters) {        // a monster: who is it?
-                double* dbg = (double*)(a.counters + SC_KNNPROF + 16);
-                dbg[0] = xi; dbg[1] = yi; dbg[2] = zi; dbg[3] = R_given; dbg[4] = hval; dbg[5] = (double)tries;
-                dbg[6] = (double)(ncand - prof_c0); dbg[7] = (double)dtc;
-            }
-        }
-#endif
         if (a.distrust && a.rsearch && (hval * a.rscale > 1.5 * R_given || hval * a.rscale < 0.5 * R_given)) ++nbad;
         if (lane < K) {
             if (LEAN || a.nbr) tile(lane, li) = valid ? (int)bv : -1;
@@ -803,16 +748,6 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
         if (nfar) atomicAdd(&a.counters[SC_FARQ], nfar);
         if (nbad) atomicAdd(&a.counters[SC_BADHINT], nbad);
         if (LIST && blockIdx.x == 0 && threadIdx.x == 0) a.counters[SC_NFAILQ] = (u64)(u32)total;      // this search's list length
-#ifdef SPHX_KNN_PROF
-        for (int pc = 0; pc < 2; ++pc)
-            if (p_n[pc]) {
-                atomicAdd(&a.counters[SC_KNNPROF + 2 * pc], p_sum[pc]);
-                atomicAdd(&a.counters[SC_KNNPROF + 4 + 2 * pc], p_n[pc]);
-                atomicMax(&a.counters[SC_KNNPROF + 8 + 2 * pc], p_max[pc]);
-                atomicAdd(&a.counters[SC_KNNPROF + 12 + 2 * pc], p_tries[pc]);
-                for (int q = 0; q < 4; ++q) atomicAdd(&a.counters[SC_KNNPROF + 4 * q + 2 * pc + 1], p_sec[pc][q]);
-            }
-#endif
     }
 }
 
@@ -848,29 +783,6 @@ int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const double* xs, const double* ys
     a.h_by_id = out.h_by_id;
     a.counters = ctx->scal.as<u64>();
     int blocks = (int)(sphx_pad64(n) / KNN_PPB);
-#ifdef SPHX_EXPERIMENTS
-    if (ctx->exp_knn >= 0) {       // timing experiment (SPHX_KNN_ABL), results discarded
-        KnnArgs b = a;
-        b.nbr = nullptr; b.list64 = nullptr; b.dref = nullptr; b.h_sorted = nullptr; b.idx64 = nullptr; b.dist = nullptr; b.nontriv = nullptr;
-        b.h_by_id = nullptr; b.counters = nullptr;
-        const int mode = ctx->exp_knn;
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, ctx->stream));
-        if (mode == 1) hipLaunchKernelGGL((knn_kernel<1, 0>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, b);
-        else if (mode == 2) hipLaunchKernelGGL((knn_kernel<2, 0>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, b);
-        else if (mode == 3) hipLaunchKernelGGL((knn_kernel<3, 0>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, b);
-        else if (mode == 4) hipLaunchKernelGGL((knn_kernel<4, 0>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, b);
-        else if (mode == 5 && a.nbr && a.h_sorted) hipLaunchKernelGGL((knn_kernel<5, 1>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, a);   // lean kernel, one try only (same outputs but for the few short queries; the real launch follows)
-        else hipLaunchKernelGGL((knn_kernel<0, 0>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, b);
-        HIPCHK(hipEventRecord(e1, ctx->stream));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        fprintf(stderr, "[sphx] knn ablation %d: %.4f ms\n", mode, ms);
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    }
-#endif
     a.qlist = nullptr; a.qcount = nullptr;
     a.distrust = 0;
     a.ol.L = 0; a.ol.start = nullptr; a.ol.list = nullptr; a.ol.cx = a.ol.cy = a.ol.cz = 0.0; a.ol.hmax = 1.0;
@@ -880,14 +792,14 @@ int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const double* xs, const double* ys
                        a.counters;
     // Hinted searches of the step loop and of the device API: the lane-per-query grouped kernel first, then this
     // kernel in list mode for whatever it could not certify (sphx_knn_group.hip).
-    if ((lean || lean2) && ctx->use_group && ctx->knn_hinted && rsearch && ctx->exp_knn < 0) {
+    if ((lean || lean2) && ctx->use_group && ctx->knn_hinted && rsearch) {
         const size_t tile_bytes = (size_t)k * (KNN_PPB + 1) * sizeof(int);
         // What the previous hinted search reported (copied out behind it, on the host long since: no wait): queries it
         // left to the general kernel, far queries (outside the grid box, wide spheres), radii that contradicted their hints
         // (the fused loop copies these slots out together with its mean-h read-back and hands them over: knn_lag_*)
         const bool lagged = ctx->olev_mode == 2 || ctx->distrust_mode == 2;
         const bool ext = ctx->knn_lag_external;
-        if (!ctx->capturing && lagged && (ext ? ctx->knn_lag_valid : ctx->olev_ev_valid)) {
+        if (lagged && (ext ? ctx->knn_lag_valid : ctx->olev_ev_valid)) {
             if (!ext) HIPCHK(hipEventSynchronize(ctx->olev_ev));
             const u64* v = ext ? ctx->knn_lag : (const u64*)((const char*)ctx->pinned + 3072);   // slots SC_NFAILQ .. SC_BADHINT
             const int64_t fb = (int64_t)(u32)v[0];
@@ -932,11 +844,11 @@ int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const double* xs, const double* ys
             // every query by the general kernel, radii seeded from the cell counts (the hint is one rung of the ladder)
             a.distrust = 1;
             if (a.ol.L > 0) {
-                if (lean) hipLaunchKernelGGL((knn_kernel<0, 1, 0, 1>), dim3(blocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
-                else hipLaunchKernelGGL((knn_kernel<0, 2, 0, 1>), dim3(blocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
+                if (lean) hipLaunchKernelGGL((knn_kernel<1, 0, 1>), dim3(blocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
+                else hipLaunchKernelGGL((knn_kernel<2, 0, 1>), dim3(blocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
             } else {
-                if (lean) hipLaunchKernelGGL((knn_kernel<0, 1>), dim3(blocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
-                else hipLaunchKernelGGL((knn_kernel<0, 2>), dim3(blocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
+                if (lean) hipLaunchKernelGGL((knn_kernel<1>), dim3(blocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
+                else hipLaunchKernelGGL((knn_kernel<2>), dim3(blocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
             }
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemsetAsync(ctx->scal.as<u64>() + SC_NFAILQ, 0, sizeof(u64), ctx->stream));
@@ -953,33 +865,27 @@ int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const double* xs, const double* ys
             ga.g = a.g; ga.rsearch = a.rsearch; ga.hint_by_id = a.hint_by_id; ga.rscale = a.rscale; ga.rbound = a.rbound;
             ga.nbr = a.nbr; ga.h_sorted = lean ? a.h_sorted : nullptr; ga.h_by_id = lean2 ? a.h_by_id : nullptr;
             ga.fail_list = flist; ga.fail_count = fcount; ga.counters = a.counters;
-            ga.tie_list = nullptr; ga.tie_count = fcount + 1; ga.tie_cap = 0;
-            if (ctx->tie_fix) {
-                ga.tie_cap = a.npad / 16 + 1024;
-                SPHX_TRY(sphx_ensure(ctx, ctx->tie_list, (size_t)ga.tie_cap * sizeof(int4)));
-                ga.tie_list = ctx->tie_list.as<int4>();
-            }
+            ga.tie_count = fcount + 1; ga.tie_cap = a.npad / 16 + 1024;
+            SPHX_TRY(sphx_ensure(ctx, ctx->tie_list, (size_t)ga.tie_cap * sizeof(int4)));
+            ga.tie_list = ctx->tie_list.as<int4>();
             SPHX_TRY(sphx_knn_group(ctx, ga));
             a.qlist = flist; a.qcount = fcount;
             int lblocks = (int)((ctx->list_len_last / 32 + 255) / 256) * 256;
             lblocks = lblocks < KNN_LIST_BLOCKS ? KNN_LIST_BLOCKS : (lblocks > KNN_LIST_BLOCKS_MAX ? KNN_LIST_BLOCKS_MAX : lblocks);
             if (lblocks > blocks) lblocks = blocks;
-            int tblocks = 0;                      // near ties: ordered by 16 further blocks of the same launch
-            if (ga.tie_list) {
-                a.tie_list = ga.tie_list; a.tie_count = ga.tie_count; a.tie_cap = ga.tie_cap; a.list_blocks = lblocks;
-                tblocks = 16;
-            }
+            const int tblocks = 16;               // near ties: ordered by 16 further blocks of the same launch
+            a.tie_list = ga.tie_list; a.tie_count = ga.tie_count; a.tie_cap = ga.tie_cap; a.list_blocks = lblocks;
             if (a.ol.L > 0) {
-                if (lean) hipLaunchKernelGGL((knn_kernel<0, 1, 1, 1>), dim3(lblocks + tblocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
-                else hipLaunchKernelGGL((knn_kernel<0, 2, 1, 1>), dim3(lblocks + tblocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
+                if (lean) hipLaunchKernelGGL((knn_kernel<1, 1, 1>), dim3(lblocks + tblocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
+                else hipLaunchKernelGGL((knn_kernel<2, 1, 1>), dim3(lblocks + tblocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
             } else {
-                if (lean) hipLaunchKernelGGL((knn_kernel<0, 1, 1>), dim3(lblocks + tblocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
-                else hipLaunchKernelGGL((knn_kernel<0, 2, 1>), dim3(lblocks + tblocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
+                if (lean) hipLaunchKernelGGL((knn_kernel<1, 1>), dim3(lblocks + tblocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
+                else hipLaunchKernelGGL((knn_kernel<2, 1>), dim3(lblocks + tblocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
             }
             HIPCHK(hipGetLastError());
             // (SC_NFAILQ is written by the list-mode launch itself)
         }
-        if (lagged && !ext && !ctx->capturing) {
+        if (lagged && !ext) {
             if (!ctx->olev_ev) HIPCHK(hipEventCreateWithFlags(&ctx->olev_ev, hipEventDisableTiming));
             HIPCHK(hipMemcpyAsync((char*)ctx->pinned + 3072, ctx->scal.as<u64>() + SC_NFAILQ, 10 * sizeof(u64), hipMemcpyDeviceToHost,
                                   ctx->stream));
@@ -988,9 +894,9 @@ int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const double* xs, const double* ys
         }
         return SPHX_OK;
     }
-    if (lean) hipLaunchKernelGGL((knn_kernel<0, 1>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, a);
-    else if (lean2) hipLaunchKernelGGL((knn_kernel<0, 2>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, a);
-    else hipLaunchKernelGGL((knn_kernel<0, 0>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, a);
+    if (lean) hipLaunchKernelGGL((knn_kernel<1>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, a);
+    else if (lean2) hipLaunchKernelGGL((knn_kernel<2>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, a);
+    else hipLaunchKernelGGL((knn_kernel<0>), dim3(blocks), dim3(KNN_BLOCK), (size_t)k * (KNN_PPB + 1) * sizeof(int), ctx->stream, a);
     HIPCHK(hipGetLastError());
     return SPHX_OK;
 }

@@ -33,7 +33,5 @@ struct KnnGroupArgs {
     int* fail_list;            // processing slots this kernel could not certify
     int* fail_count;
     u64* counters;
-    int exp_noamb;             // timing experiment (SPHX_KG_EXP_NOAMB): 0 in the product
-    u64* prof;                 // diagnostics (nullptr in the product): per-section cycle sums
 };
 int sphx_knn_group(sphx_ctx* ctx, const KnnGroupArgs& a);

@@ -189,9 +189,6 @@ __global__ __launch_bounds__(256, KG_MINWAVES) void knn_group_kernel(KnnGroupArg
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // in-kernel section clock (diagnostic launches only: a.prof == nullptr in the product)
-    u64 tprev = a.prof ? __builtin_readcyclecounter() : 0;
-#define KG_STAMP(sec) if (a.prof) { const u64 tn_ = __builtin_readcyclecounter(); if (tid == 0) atomicAdd(&a.prof[sec], tn_ - tprev); tprev = tn_; }
     // the latency-bound front of a group (queries, rows, staging: a handful of dependent round trips and few instructions)
     // goes ahead of the other resident groups' arithmetic (search 0.459 -> 0.443 ms; priority 3 the same)
     __builtin_amdgcn_s_setprio(KG_FRONT_PRIO);
@@ -254,7 +251,6 @@ __global__ __launch_bounds__(256, KG_MINWAVES) void knn_group_kernel(KnnGroupArg
         }
     }
     __syncthreads();
-    KG_STAMP(0)
     bool group_ok = sh.ok != 0;
     const double Ox = sh.Ox, Oy = sh.Oy, Oz = sh.Oz;
     // Phase A on the matrix cores (below) when its error bound KG_MFMA_KAPPA E^2 fits the acceptance pad of every query
@@ -324,7 +320,6 @@ __global__ __launch_bounds__(256, KG_MINWAVES) void knn_group_kernel(KnnGroupArg
             __syncthreads();
         }
         __syncthreads();
-        KG_STAMP(1)
         // ---- stage: one candidate per thread and pass (two passes' loads in flight).  The rows hold whole cells; a
         // candidate is kept only if it lies within Rcov of the group's box (the exact box + sphere region, not its cover
         // by cells: a quarter fewer slots for phase A), the kept ones compacted per wave (ballot + one LDS add). ----
@@ -382,7 +377,6 @@ __global__ __launch_bounds__(256, KG_MINWAVES) void knn_group_kernel(KnnGroupArg
         }
     }
     __syncthreads();                     // the tile is complete; rowof / rowbase are dead (the lists take their memory)
-    KG_STAMP(2)
     if (!group_ok) {
         if (is_query && !fail) why = 2;
         fail = is_query;
@@ -505,7 +499,6 @@ __global__ __launch_bounds__(256, KG_MINWAVES) void knn_group_kernel(KnnGroupArg
         }
     }
     __syncthreads();
-    KG_STAMP(3)
     // ---- the tail: wave w finishes queries 16 w .. 16 w + 15 with FOUR LANES PER QUERY ------------------------------
     // (lane = 4 * local query + part).  The query's slot list is dealt cyclically over its four lanes (slot = part +
     // 4 u: balanced by construction), each lane builds 16 keys, and the 64 keys of a query are ordered by a bitonic
@@ -568,7 +561,6 @@ __global__ __launch_bounds__(256, KG_MINWAVES) void knn_group_kernel(KnnGroupArg
             for (int u = 0; u < 8; ++u) key[c * 8 + u] = 0xFFFFFFFFu;
         }
     }
-    KG_STAMP(4)
     // ---- order: bitonic network on e = 16 * part + u (ascending) ----
     // for k = 2 .. 64, j = k/2 .. 1: compare-exchange (e, e | j), ascending where (e & k) == 0.  j < 16: both elements in
     // one lane; j = 16 / 32: partner in lane ^ 1 / lane ^ 2 (DPP quad_perm).  The direction is a compile-time property
@@ -675,9 +667,6 @@ __global__ __launch_bounds__(256, KG_MINWAVES) void knn_group_kernel(KnnGroupArg
         am |= __builtin_amdgcn_update_dpp(0, am, 0xB1, 0xF, 0xF, true);
         am |= __builtin_amdgcn_update_dpp(0, am, 0x4E, 0xF, 0xF, true);
         if (okq && (am & 2)) { okq = false; failq = true; q_why = 5; }
-        #ifdef SPHX_EXPERIMENTS
-        if (a.exp_noamb) am &= ~1;
-#endif
         if (okq && (am & 1)) { okq = false; failq = true; q_why = 6; }
         // room in the tie list is reserved here: a query whose entries do not fit fails over like any other near tie
         if (__builtin_amdgcn_ballot_w64(okq && res16 != 0u)) {          // (rare: under 1 % of the queries)
@@ -689,7 +678,6 @@ __global__ __launch_bounds__(256, KG_MINWAVES) void knn_group_kernel(KnnGroupArg
             if (okq && ov) { okq = false; failq = true; q_why = 6; }
         }
     }
-    KG_STAMP(5)
     // ---- outputs: rank r = 16 part + u ----
     __builtin_amdgcn_s_setprio(KG_FRONT_PRIO);          // (index and position loads of the K-th neighbour, row stores: -3 us)
     {
@@ -731,7 +719,6 @@ __global__ __launch_bounds__(256, KG_MINWAVES) void knn_group_kernel(KnnGroupArg
             }
         }
     }
-    KG_STAMP(6)
     const bool rep = part == 0;                            // one lane speaks for the query
     const u64 failmask = __builtin_amdgcn_ballot_w64(failq && rep);
     if (failmask) {
@@ -747,37 +734,11 @@ __global__ __launch_bounds__(256, KG_MINWAVES) void knn_group_kernel(KnnGroupArg
         }
     }
     if (tid == 0 && a.counters) atomicAdd(&a.counters[SC_CAND], (u64)T * (u64)__popcll(okmask));
-    KG_STAMP(7)
 }
 
-int sphx_knn_group(sphx_ctx* ctx, const KnnGroupArgs& a0) {
-    KnnGroupArgs a = a0;
-    const int blocks = a.npad / 64;
-    a.prof = nullptr;
-#ifdef SPHX_EXPERIMENTS
-    static const bool noamb = getenv("SPHX_KG_EXP_NOAMB") != nullptr;     // timing experiment only: near ties NOT handed on (wrong results)
-    a.exp_noamb = noamb ? 1 : 0;
-    static const bool prof = getenv("SPHX_KG_PROF") != nullptr;
-#else
-    a.exp_noamb = 0;
-    const bool prof = false;
-#endif
-    if (prof) {           // diagnostic: per-section shader cycles of one launch (summed over the waves' lane 0)
-        SPHX_TRY(sphx_ensure(ctx, ctx->scal_tmp, 4096));
-        u64* pd = ctx->scal_tmp.as<u64>() + 256;
-        HIPCHK(hipMemsetAsync(pd, 0, 64, ctx->stream));
-        a.prof = pd;
-    }
-    hipLaunchKernelGGL(knn_group_kernel, dim3(blocks), dim3(256), 0, ctx->stream, a);
+int sphx_knn_group(sphx_ctx* ctx, const KnnGroupArgs& a) {
+    hipLaunchKernelGGL(knn_group_kernel, dim3(a.npad / 64), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
-    if (prof) {
-        u64 h[8];
-        HIPCHK(hipMemcpyAsync(h, a.prof, 64, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        const double w = (double)blocks;
-        fprintf(stderr, "[sphx] grouped search cycles/group (thread 0): setup %.0f rows %.0f stage %.0f phaseA %.0f phaseB %.0f sort+certify %.0f output %.0f tail %.0f\n",
-                h[0] / w, h[1] / w, h[2] / w, h[3] / w, h[4] / w, h[5] / w, h[6] / w, h[7] / w);
-    }
     return SPHX_OK;
 }
 

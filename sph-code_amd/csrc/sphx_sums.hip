@@ -136,8 +136,6 @@ __device__ __forceinline__ double parts_total(const double (&a)[SPHX_SUM_PARTS])
 }
 
 // ---- pass 1 ---------------------------------------------------------------------------------
-// EXP != 0: timing experiments (extra discarded launch, SPHX_PASS_EXP); 1 = half the record loads
-template <int EXP>
 __global__ __launch_bounds__(256) void pass_density_kernel(int n, int npad, int k, int clip,
                                                            const int* __restrict__ nbr,
                                                            const RecA* __restrict__ rec, double* rho_s,
@@ -165,7 +163,7 @@ __global__ __launch_bounds__(256) void pass_density_kernel(int n, int npad, int 
 #pragma unroll
       for (int u = 0; u < NBATCH; ++u) {
           const double* q = reinterpret_cast<const double*>(&rec[jb[u] < 0 ? i : jb[u]]);
-          q0b[u] = load4(q); q1b[u] = (EXP == 1) ? q0b[u] : load4(q + 4);
+          q0b[u] = load4(q); q1b[u] = load4(q + 4);
       }
 #pragma unroll
       for (int u = 0; u < NBATCH; ++u) {
@@ -207,31 +205,7 @@ int sphx_pass_density(sphx_ctx* ctx, int64_t n, int k) {
     SPHX_TRY(sphx_ensure(ctx, ctx->G, (size_t)n * 3 * sizeof(double)));
     SPHX_TRY(sphx_ensure(ctx, ctx->ha, (size_t)n * 3 * sizeof(double)));
     if (ctx->qorder && ctx->blob_lists) return sphx_blob_density(ctx, n, k);
-#ifdef SPHX_EXPERIMENTS
-    if (ctx->exp_pass >= 0) {        // timing experiment (SPHX_PASS_EXP), outputs discarded
-        const int mode = ctx->exp_pass;
-        SPHX_TRY(sphx_ensure(ctx, ctx->in_j, (size_t)n * 12 * sizeof(double)));
-        double* d = ctx->in_j.as<double>();
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, ctx->stream));
-        if (mode == 1)
-            hipLaunchKernelGGL(pass_density_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                               (int)n, (int)sphx_pad64(n), k, ctx->clip_grad, ctx->nbr.as<int>(), ctx->rec1.as<RecA>(), d,
-                               ctx->qorder, OutMap{nullptr, (int)n}, d + n, d + 2 * n, d + 3 * n, d + 4 * n, d + 8 * n);
-        else
-            hipLaunchKernelGGL(pass_density_kernel<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                               (int)n, (int)sphx_pad64(n), k, ctx->clip_grad, ctx->nbr.as<int>(), ctx->rec1.as<RecA>(), d,
-                               ctx->qorder, OutMap{nullptr, (int)n}, d + n, d + 2 * n, d + 3 * n, d + 4 * n, d + 8 * n);
-        HIPCHK(hipEventRecord(e1, ctx->stream));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        fprintf(stderr, "[sphx] pass_density experiment %d: %.4f ms\n", mode, ms);
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    }
-#endif
-    hipLaunchKernelGGL(pass_density_kernel<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(pass_density_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
                        (int)n, (int)sphx_pad64(n), k, ctx->clip_grad, ctx->nbr.as<int>(), ctx->rec1.as<RecA>(),
                        ctx->rho_s.as<double>(), ctx->qorder, OutMap{ctx->map_perm, ctx->map_perm ? ctx->map_nactive : (int)n},
                        ctx->rho.as<double>(), ctx->rhod.as<double>(), ctx->nden.as<double>(),
@@ -745,10 +719,7 @@ __global__ __launch_bounds__(256) void step_species_kernel(int n, int npad, int 
 // the species pass on any set of sorted arrays (the step: the resident state; the device API: gathered copies)
 int sphx_species_on(sphx_ctx* ctx, int64_t n, int k, int S, int SP, const double* fun, const int* row_of, const double* m_sorted,
                     double* F, double* Z, double* agb) {
-    int agb_on = (ctx->agb_on && Z && agb) ? 1 : 0;
-#ifdef SPHX_EXPERIMENTS
-    if (ctx->exp_no_agb) agb_on = 0;          // timing experiment (SPHX_EXP_NO_AGB): the species sums alone
-#endif
+    const int agb_on = (ctx->agb_on && Z && agb) ? 1 : 0;
     // out of LDS when the step's blob lists are at hand (sphx_blob.hip); the gather form below otherwise
     if (ctx->use_lds && ctx->blob_lists && ctx->qorder && SP == 16 && S <= 16 && k <= SPHX_MAX_K && ctx->species_lds)
         return sphx_blob_species(ctx, n, k, S, fun, row_of, m_sorted, F, Z, agb, agb_on);
