@@ -59,8 +59,8 @@ typedef struct sphx_stats {
     double ms_search;      /* kNN kernel                                        */
     double ms_prep;        /* gather-record build                               */
     double ms_density;     /* pass 1: rho, rho_dust, n, grad P                  */
-    double ms_pi;          /* pass 2: Pi_i + crossing time                      */
-    double ms_visc;        /* pass 3: viscous accel + heat                      */
+    double ms_pi;          /* pass 2: Pi_i + crossing time (0 in pairwise steps)  */
+    double ms_visc;        /* pass 3: viscous accel + heat (pairwise steps: the fused pass, crossing time included) */
     double ms_integrate;   /* dt + leapfrog                                     */
     double ms_total;       /* events around the whole step                      */
     int64_t n;             /* particles                                         */
@@ -149,6 +149,18 @@ int sphx_neighbors(sphx_ctx* ctx, int64_t n, int k, const double* points, double
 /* ---- nsc.hydro_update(neighbor, points, mass, sizes, f_un, particle_type, T, mu_array,
  *                       gamma_array, velocities)                     nsc:556-671 ----- *
  * visc_mode 0 = "ref_axis0": Pi_i = sum_k pi_ik, the axis repair of nsc:649.
+ * visc_mode 1 = "pairwise": the per-pair pi_ik stays inside the force sum (the Monaghan form of the
+ *   loop version, nsc:802-808).  With dx, dv relative to neighbor[i,0], g_j = [type_j == 0], gb / ga
+ *   the kernel gradients of nsc:591 (clipped under sphx_set_clip_grad) / nsc:592, alpha = 1:
+ *     w_ik   = min(0, (dv . dx) / sqrt(r^2 + 0.01 h_j^2))                     nsc:643-644
+ *     rho_ab = (rho_j + rho_i) / 2,  c_ab = (c_j + c_i) / 2                   nsc:646-647
+ *     pi_ik  = -(alpha/2) (2 c_ab - 3 w_ik) w_ik / rho_ab                     nsc:649 term
+ *     B_ik   = 1/2 pi_ik [m_j g_j gb + m_i g_i ga]
+ *     visc_accel_i = -sum_k B_ik,  visc_heat_i = (m_i/2) sum_k B_ik . dv     nsc:651-654
+ *   gb, ga are non-negative multiples of -dx and pi_ik > 0 only where dv . dx < 0, so visc_heat >= 0 for
+ *   every particle.  Passes: density, then ONE viscous pass that forms pi_ik per pair and casts the
+ *   crossing-time vote (the Pi_i pass is not run).  The other outputs are those of mode 0, bit for bit.
+ *   Any other visc_mode: SPHX_E_ARG.  The argument alone decides (sphx_set_visc_mode plays no part).
  * Outputs keep the reference's sign (+grad P / rho) and layouts:
  *   hydro_accel, visc_accel (n,3); visc_heat, rho, nden, rho_dust (n,); f_un_nb (s,n).
  * Any output pointer may be NULL (that output is skipped).
@@ -293,6 +305,12 @@ int sphx_state_set_loop_forms(sphx_ctx* ctx, int on, double d);
  * which clip it (nsc:689).  on != 0 clips it (0 for h_j^2 - r^2 <= 0) in sphx_hydro_update, sphx_step and
  * the sphx_dev_* passes of this context.                                                          */
 int sphx_set_clip_grad(sphx_ctx* ctx, int on);
+/* Viscosity of sphx_step (hydro_update mode) and of the sphx_dev_* passes of this context: 0 = "ref_axis0" (the default),
+ * 1 = "pairwise" (the formula at sphx_hydro_update).  Pairwise steps run density, then one fused viscous pass (no Pi_i
+ * pass: stats.ms_pi stays 0, ms_visc covers the fused pass).  SPHX_E_ARG for any other mode, and for mode 1 in loop-form
+ * mode (sphx_state_set_loop_forms), whose viscosity is pairwise already; sphx_state_set_loop_forms(on) likewise refuses
+ * a context in mode 1.  Kept across sphx_state_upload.                                                                  */
+int sphx_set_visc_mode(sphx_ctx* ctx, int mode);
 /* Self-gravity inside the step loop (drv:448-449,477): mode 1 = direct summation with Plummer
  * softening eps = median(h) of the step (nsc:358), G m_j (x_j - x_i) / (|x_j - x_i|^2 + eps^2)^(3/2)
  * summed over ALL particles - the sum the reference's tree approximates (sphx_gravity_direct).
@@ -357,6 +375,13 @@ int sphx_dev_pi(sphx_ctx* ctx, const double* rho_complete, double* Pi, double* B
 /* nsc:651-654; Bw_complete (n_total) = m Pi [t==0]; mass (n_total)                           */
 int sphx_dev_visc(sphx_ctx* ctx, const double* Bw_complete, const double* mass, double* visc_accel,
                   double* visc_heat);
+/* Pairwise viscosity (sphx_set_visc_mode(ctx, 1); records from sphx_dev_prep after that call): replaces sphx_dev_pi +
+ * sphx_dev_visc after sphx_dev_density.  rho_complete (n_total): ghosts' densities from their owners, injected as
+ * sphx_dev_pi does; mass (n_total); outputs as sphx_dev_visc; ct_out as sphx_dev_pi.  No m Pi_j halo phase is needed.
+ * Honours sphx_dev_select_blobs (interior blobs while the rho_j halo phase is in flight).  SPHX_E_STATE in mode 0, and
+ * when the last sphx_dev_prep ran before the mode was set (its records carry no pairwise factor).                      */
+int sphx_dev_visc_pairwise(sphx_ctx* ctx, const double* rho_complete, const double* mass, double* visc_accel,
+                           double* visc_heat, double* ct_out);
 /* drv:233-238 and drv:460-491 on caller-order (n,3) arrays                                   */
 int sphx_dev_clamp(sphx_ctx* ctx, int64_t n, double* pos, double* vel);
 /* Halo / migration plumbing of the decomposed driver (sph_code_amd/multigpu.py): particles live in

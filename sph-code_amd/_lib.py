@@ -72,6 +72,7 @@ SIGNATURES = {
     "sphx_state_download_species": (C.c_int, [_P, _D, _D, _D]),
     "sphx_state_set_loop_forms": (C.c_int, [_P, C.c_int, C.c_double]),
     "sphx_set_clip_grad": (C.c_int, [_P, C.c_int]),
+    "sphx_set_visc_mode": (C.c_int, [_P, C.c_int]),
     "sphx_state_set_gravity": (C.c_int, [_P, C.c_int, C.c_double]),
     "sphx_set_gravity_order": (C.c_int, [_P, C.c_int]),
     "sphx_gravity_direct": (C.c_int, [_P, C.c_int64, _D, _D, _D, C.c_double, C.c_double, _D]),
@@ -91,6 +92,7 @@ SIGNATURES = {
     "sphx_dev_density": (C.c_int, [_P] + [_P] * 4),
     "sphx_dev_pi": (C.c_int, [_P] + [_P] * 4),
     "sphx_dev_visc": (C.c_int, [_P] + [_P] * 4),
+    "sphx_dev_visc_pairwise": (C.c_int, [_P] + [_P] * 5),
     "sphx_dev_clamp": (C.c_int, [_P, C.c_int64, _P, _P]),
     "sphx_dev_pack_rows": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), _P]),
     "sphx_dev_regroup": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int, C.POINTER(C.c_void_p),

@@ -142,11 +142,23 @@ def neighbors(points, dist, N_NEIGH, eps=0.1):
     return idx, None, dd, nontriv, h
 
 
+VISC_MODES = {"ref_axis0": 0, "pairwise": 1}
+
+
+def visc_mode_code(visc_mode):
+    """"ref_axis0" -> 0, "pairwise" -> 1 (include/sphx.h sphx_hydro_update); anything else: ValueError."""
+    if not isinstance(visc_mode, str) or visc_mode not in VISC_MODES:
+        raise ValueError("visc_mode must be 'ref_axis0' or 'pairwise', not %r" % (visc_mode,))
+    return VISC_MODES[visc_mode]
+
+
 def hydro_update(neighbor, points, mass, sizes, f_un, particle_type, T, mu_array, gamma_array, velocities,
-                 clip_grad=False):
+                 clip_grad=False, visc_mode="ref_axis0"):
     """nsc:556-671 -> (hydro_accel (N,3), visc_accel (N,3), visc_heat (N,), density_calc (N,),
     num_density_calc (N,), f_un_neighbor (S,N), dust_density_calc (N,)).  clip_grad=True: the physics option
-    of include/sphx.h sphx_set_clip_grad (not the reference's arithmetic)."""
+    of include/sphx.h sphx_set_clip_grad (not the reference's arithmetic).  visc_mode="pairwise": the per-pair
+    pi_ik inside the viscous sum (include/sphx.h sphx_hydro_update); "ref_axis0" (the default) is the reference's."""
+    mode = visc_mode_code(visc_mode)
     nb, n, K = _nk(neighbor)
     pts = f64(points, (n, 3)); vel = f64(velocities, (n, 3))
     m = f64(mass, (n,)); h = f64(sizes, (n,)); pt = f64(particle_type, (n,))
@@ -162,7 +174,7 @@ def hydro_update(neighbor, points, mass, sizes, f_un, particle_type, T, mu_array
     c.check(c.lib.sphx_set_clip_grad(c.h, 1 if clip_grad else 0))
     try:
         _with_nb(neighbor, nb, lambda nbp: c.lib.sphx_hydro_update(
-            c.h, n, K, S, nbp, dp(pts), dp(m), dp(h), dp(fu), dp(pt), dp(Tt), dp(mu), dp(gam), dp(vel), 0,
+            c.h, n, K, S, nbp, dp(pts), dp(m), dp(h), dp(fu), dp(pt), dp(Tt), dp(mu), dp(gam), dp(vel), mode,
             dp(ha), dp(va), dp(vh), dp(rho), dp(nden), dp(F), dp(rhod)))
     finally:
         c.lib.sphx_set_clip_grad(c.h, 0)

@@ -314,7 +314,8 @@ extern "C" int sphx_hydro_update(sphx_ctx* ctx, int64_t n, int k, int s, const i
     NEED(mu_array); NEED(gamma_array); NEED(velocities);
     if (n < 1 || n > 0x7FFFFFF0ll) return sphx_set_err(ctx, SPHX_E_ARG, "n=%lld out of range", (long long)n);
     if (k < 1 || k > 4096) return sphx_set_err(ctx, SPHX_E_ARG, "k=%d out of range", k);
-    if (visc_mode != 0) return sphx_set_err(ctx, SPHX_E_ARG, "visc_mode %d unknown (0 = ref_axis0)", visc_mode);
+    if (visc_mode != 0 && visc_mode != 1)
+        return sphx_set_err(ctx, SPHX_E_ARG, "visc_mode %d unknown (0 = ref_axis0, 1 = pairwise)", visc_mode);
     if (f_un_nb && (!f_un || s < 1 || s > SPHX_MAX_SPECIES))
         return sphx_set_err(ctx, SPHX_E_ARG, "species output needs f_un and 1 <= s <= %d", SPHX_MAX_SPECIES);
     HIPCHK(hipSetDevice(ctx->device));
@@ -337,13 +338,18 @@ extern "C" int sphx_hydro_update(sphx_ctx* ctx, int64_t n, int k, int s, const i
         SPHX_TRY(sphx_transpose_nbr(ctx, n, k, ctx->idx64.as<int64_t>()));
         ctx->nbr_api_valid = true; ctx->nbr_api_n = n; ctx->nbr_api_k = k;
     }
+    ctx->visc_pw = visc_mode == 1;          // (the call's own argument; the context's step mode plays no part)
     SPHX_TRY(sphx_prep(ctx, n, nullptr, nullptr, nullptr, ctx->in_a.as<double>(), nullptr, nullptr,
                        nullptr, ctx->in_b.as<double>(), ctx->in_c.as<double>(), ctx->in_d.as<double>(),
                        ctx->in_e.as<double>(), ctx->in_f.as<double>(), ctx->in_g.as<double>(),
                        ctx->in_h.as<double>()));
     SPHX_TRY(sphx_pass_density(ctx, n, k));
-    SPHX_TRY(sphx_pass_pi(ctx, n, k, ctx->in_d.as<double>(), ctx->in_h.as<double>()));
-    SPHX_TRY(sphx_pass_visc(ctx, n, k, ctx->in_c.as<double>()));
+    if (visc_mode == 1) {
+        SPHX_TRY(sphx_pass_visc_pw(ctx, n, k, ctx->in_c.as<double>()));
+    } else {
+        SPHX_TRY(sphx_pass_pi(ctx, n, k, ctx->in_d.as<double>(), ctx->in_h.as<double>()));
+        SPHX_TRY(sphx_pass_visc(ctx, n, k, ctx->in_c.as<double>()));
+    }
     if (f_un_nb) {
         SPHX_TRY(upload(ctx, ctx->in_i, f_un, (size_t)n * s * sizeof(double)));
         SPHX_TRY(sphx_ensure(ctx, ctx->F, (size_t)n * s * sizeof(double)));
@@ -454,6 +460,8 @@ extern "C" int sphx_state_set_loop_forms(sphx_ctx* ctx, int on, double d) {
     if (!ctx->has_state) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_state_set_loop_forms before sphx_state_upload");
     if (on && !(d > 0.0)) return sphx_set_err(ctx, SPHX_E_ARG, "the loop forms need the driver's global d > 0 (drv:68)");
     if (on && ctx->use_verlet) return sphx_set_err(ctx, SPHX_E_STATE, "loop-form steps are not combined with incremental search");
+    if (on && ctx->visc_mode != 0)
+        return sphx_set_err(ctx, SPHX_E_ARG, "loop-form steps have their own (pairwise) viscosity: visc_mode must be 0");
     ctx->loop_forms = on ? 1 : 0;
     ctx->loop_d = d;
     return SPHX_OK;
@@ -469,6 +477,16 @@ extern "C" int sphx_set_gravity_order(sphx_ctx* ctx, int order) {
 extern "C" int sphx_set_clip_grad(sphx_ctx* ctx, int on) {
     if (!ctx) return SPHX_E_ARG;
     ctx->clip_grad = on ? 1 : 0;
+    return SPHX_OK;
+}
+
+extern "C" int sphx_set_visc_mode(sphx_ctx* ctx, int mode) {
+    if (!ctx) return SPHX_E_ARG;
+    if (mode != 0 && mode != 1)
+        return sphx_set_err(ctx, SPHX_E_ARG, "visc_mode %d unknown (0 = ref_axis0, 1 = pairwise)", mode);
+    if (mode != 0 && ctx->loop_forms)
+        return sphx_set_err(ctx, SPHX_E_ARG, "loop-form steps have their own (pairwise) viscosity: visc_mode must be 0");
+    ctx->visc_mode = mode;
     return SPHX_OK;
 }
 
@@ -496,11 +514,12 @@ static int one_step(sphx_ctx* ctx, int k, double dist, int first, double fixed_d
     // (the step's own start and end events likewise: without them the call's first and last step bracket the call,
     //  whose time is then shared out over its steps)
     const bool rec0 = detail || call_first, rec7 = detail || call_last;
-    ctx->ev_has07[ring] = (rec0 ? 1 : 0) | (rec7 ? 2 : 0);
+    ctx->ev_has07[ring] = (rec0 ? 1 : 0) | (rec7 ? 2 : 0) | (ctx->visc_mode == 1 && !ctx->loop_forms ? 4 : 0);
     ctx->map_perm = nullptr;
     ctx->qorder = nullptr;
     ctx->blob_lists = false;
     ctx->blob_split_valid = false;
+    ctx->visc_pw = ctx->visc_mode == 1 && !ctx->loop_forms;     // (what sphx_prep builds RecBC.Bw for)
     ctx->pass_part = 0;
     ctx->nbr_api_valid = false;   // the step overwrites the K-major list (search or Verlet refresh)
     if (rec0) HIPCHK(hipEventRecord(ev[0], ctx->stream));
@@ -706,9 +725,13 @@ static int one_step(sphx_ctx* ctx, int k, double dist, int first, double fixed_d
     if (detail) HIPCHK(hipEventRecord(ev[9], ctx->stream));
     if (species && !sp_fused) SPHX_TRY(sphx_step_species(ctx, n, k));
     if (detail) HIPCHK(hipEventRecord(ev[4], ctx->stream));
-    SPHX_TRY(sphx_pass_pi(ctx, n, k, s.hprev.as<double>(), s.ptype.as<double>()));
-    if (detail) HIPCHK(hipEventRecord(ev[5], ctx->stream));
-    SPHX_TRY(sphx_pass_visc(ctx, n, k, s.m.as<double>()));
+    if (ctx->visc_mode == 1) {                 // passes 2 + 3 in one (pairwise viscosity): ms_pi stays 0
+        SPHX_TRY(sphx_pass_visc_pw(ctx, n, k, s.m.as<double>()));
+    } else {
+        SPHX_TRY(sphx_pass_pi(ctx, n, k, s.hprev.as<double>(), s.ptype.as<double>()));
+        if (detail) HIPCHK(hipEventRecord(ev[5], ctx->stream));
+        SPHX_TRY(sphx_pass_visc(ctx, n, k, s.m.as<double>()));
+    }
     if (ctx->drag)
         SPHX_TRY(sphx_pass_drag(ctx, n, k, s.m.as<double>(), s.ptype.as<double>(), s.mgm.as<double>(),
                                 s.mcs.as<double>()));
@@ -753,7 +776,11 @@ static int collect_stats(sphx_ctx* ctx, int ring) {
     HIPCHK(hipEventElapsedTime(&tot, ev[0], ev[7]));
     HIPCHK(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
     st.ms_grid += ms[0]; st.ms_total += tot;
-    for (int i = 2; i < 6; ++i) HIPCHK(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    for (int i = 2; i < 6; ++i) {
+        if ((has & 4) && i >= 4) break;             // pairwise viscosity: one pass between ev[4] and ev[6], no ev[5]
+        HIPCHK(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    }
+    if (has & 4) HIPCHK(hipEventElapsedTime(&ms[5], ev[4], ev[6]));
     st.ms_prep += ms[2];
     float mg = 0.f, mi = 0.f;
     HIPCHK(hipEventElapsedTime(&mg, ev[6], ev[8]));

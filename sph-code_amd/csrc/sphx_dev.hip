@@ -168,6 +168,7 @@ extern "C" int sphx_dev_prep(sphx_ctx* ctx, const double* pos, const double* vel
     NEED(pos); NEED(vel); NEED(mass); NEED(h); NEED(T); NEED(mu); NEED(gamma); NEED(ptype);
     if (!ctx->map_perm) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_dev_prep before sphx_dev_search");
     HIPCHK(hipSetDevice(ctx->device));
+    ctx->visc_pw = ctx->visc_mode == 1;
     return sphx_prep(ctx, ctx->n, nullptr, nullptr, nullptr, pos, nullptr, nullptr, nullptr, vel, mass, h, T,
                      mu, gamma, ptype);
 }
@@ -231,6 +232,33 @@ extern "C" int sphx_dev_visc(sphx_ctx* ctx, const double* Bw_complete, const dou
     HIPCHK(hipGetLastError());
     Borrow b1(ctx->va, visc_accel, 3 * (size_t)n * sizeof(double)), b2(ctx->vh, visc_heat, (size_t)n * sizeof(double));
     SPHX_TRY(sphx_pass_visc(ctx, n, ctx->k, mass));
+    return SPHX_OK;
+}
+
+// passes 2 + 3 fused (pairwise viscosity, sphx_set_visc_mode 1): the ghosts' densities injected as sphx_dev_pi does,
+// then one pass that forms pi_ik per pair and casts the crossing-time vote; no m Pi_j halo phase
+extern "C" int sphx_dev_visc_pairwise(sphx_ctx* ctx, const double* rho_complete, const double* mass,
+                                      double* visc_accel, double* visc_heat, double* ct_out) {
+    if (!ctx) return SPHX_E_ARG;
+    NEED(rho_complete); NEED(mass);
+    if (!ctx->map_perm) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_dev_visc_pairwise before sphx_dev_search");
+    if (ctx->visc_mode != 1) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_dev_visc_pairwise needs sphx_set_visc_mode(ctx, 1)");
+    if (!ctx->recs_pw)
+        return sphx_set_err(ctx, SPHX_E_STATE, "sphx_dev_visc_pairwise: the records were not built in pairwise mode "
+                                               "(sphx_set_visc_mode(ctx, 1) before sphx_dev_prep)");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t n = ctx->n;
+    if (ctx->pass_part != 1)
+        hipLaunchKernelGGL(inject_field_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n,
+                           ctx->map_perm, rho_complete, ctx->rho_s.as<double>(), 1);
+    HIPCHK(hipGetLastError());
+    if (ctx->pass_part == 2) ctx->ct_primed = true;
+    {
+        Borrow b1(ctx->va, visc_accel, 3 * (size_t)n * sizeof(double)), b2(ctx->vh, visc_heat, (size_t)n * sizeof(double));
+        SPHX_TRY(sphx_pass_visc_pw(ctx, n, ctx->k, mass));
+    }
+    if (ct_out)
+        HIPCHK(hipMemcpyAsync(ct_out, ctx->scal.as<u64>() + SC_CT_BITS, 8, hipMemcpyDeviceToDevice, ctx->stream));
     return SPHX_OK;
 }
 

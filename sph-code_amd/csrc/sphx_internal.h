@@ -28,6 +28,7 @@ struct DevBuf {
 // (two particles per 128-B line: cell-adjacent neighbours share lines) plus, where a ninth
 // value is needed, an 8/16-B gather from a compact array (16 / 8 particles per line):
 //   pass 1: RecA                      pass 2: RecB + rho_s[j]        pass 3: RecB + bc_s[j]
+//   pairwise viscosity (passes 2 + 3 fused, visc_mode 1): RecB + rho_s[j] + bc_s[j].Bw
 struct __attribute__((aligned(64))) RecA {
     double x, y, z;   // position
     double h2;        // h_j^2
@@ -43,6 +44,7 @@ struct __attribute__((aligned(64))) RecB {
 };
 struct __attribute__((aligned(16))) RecBC {   // pass-3 companion
     double Bw;        // m Pi [t==0], written by pass 2                     nsc:651
+                      // (pairwise viscosity: m [t==0] c1, written by sphx_prep)
     double c1;        // 315 / (64 pi h^9)
 };
 struct __attribute__((aligned(32))) RecSelf { // read only by the owner's thread (coalesced)
@@ -169,6 +171,9 @@ struct sphx_ctx {
     DevBuf lrec_a, lrec_v;        // loop-form records (sphx_loopforms.hip)
     bool loop_attr_set = false;
     int clip_grad = 0;            // physics option: neighbour-side gradient clipped beyond h_j (sphx_set_clip_grad)
+    int visc_mode = 0;            // hydro_update-mode viscosity of sphx_step and the sphx_dev_* passes (sphx_set_visc_mode)
+    bool visc_pw = false;         // the records being built feed the pairwise viscous pass (sphx_prep: RecBC.Bw)
+    bool recs_pw = false;         // the records sphx_prep built last were built so (sphx_dev_visc_pairwise checks it)
     int gravity = 0;              // 1: direct-sum self-gravity each step (sphx_state_set_gravity)
     double grav_G = 0.0;
     DevBuf grav, grav_sort, grav_tmp;   // (n,3) accelerations, sorted h, radix-sort scratch
@@ -429,6 +434,7 @@ int sphx_blob_density_species(sphx_ctx* ctx, int64_t n, int k, int S, const doub
 int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k);
 int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits);
 int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m);
+int sphx_blob_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m, u64* ct_bits);
 int sphx_blob_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted, double* F,
                       double* Z, double* agb, int agb_on);
 int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const double* y,
@@ -476,6 +482,7 @@ int sphx_prep(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const 
 int sphx_pass_density(sphx_ctx* ctx, int64_t n, int k);
 int sphx_pass_pi(sphx_ctx* ctx, int64_t n, int k, const double* h, const double* ptype);
 int sphx_pass_visc(sphx_ctx* ctx, int64_t n, int k, const double* m);
+int sphx_pass_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m);   // passes 2 + 3 fused, visc_mode 1
 int sphx_pass_species(sphx_ctx* ctx, int64_t n, int k, int s, const double* fun, double* F);
 int sphx_step_species(sphx_ctx* ctx, int64_t n, int k);
 // fun: composition rows; row_of (nullable: identity): the row of sorted particle j is fun + row_of[j] * SP

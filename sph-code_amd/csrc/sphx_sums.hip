@@ -27,6 +27,7 @@ struct PrepArgs {
     RecA* ra; RecB* rb; RecBC* bc; RecSelf* self;
     const int* perm;                       // sorted -> caller index of the inputs (nullptr: identity)
     int which, n_active;                   // decomposed runs: 0 every particle, 1 the owned ones (perm < n_active), 2 the ghosts
+    int pairwise;                          // the records feed the pairwise viscous pass (RecBC.Bw = m [t==0] c1)
 };
 
 __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
@@ -48,10 +49,10 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     v.x = r.x; v.y = r.y; v.z = r.z; v.h2 = h2;
     v.vx = a.vx[(size_t)i * a.vs]; v.vy = a.vy[(size_t)i * a.vs]; v.vz = a.vz[(size_t)i * a.vs];
     v.cs = sqrt(gam * a.kB * T / mu / a.amu * g);             // nsc:647 neighbour form
-    RecBC bc; bc.Bw = 0.0; bc.c1 = r.c1;
     RecSelf sf;
     sf.csi = sqrt(gam * a.kB * T / (mu * a.amu) * g);         // nsc:647 own form
     sf.h = h; sf.mg = m * g; sf.pad = 0.0;
+    RecBC bc; bc.Bw = a.pairwise ? sf.mg * r.c1 : 0.0; bc.c1 = r.c1;   // pairwise: m [t==0] C/h^9, no pass 2 to fill it
     a.ra[t] = r;
     a.rb[t] = v;
     a.bc[t] = bc;
@@ -82,6 +83,8 @@ int sphx_prep(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const 
     a.perm = ctx->map_perm;
     a.which = ctx->map_perm ? ctx->pass_part : 0;
     a.n_active = ctx->map_nactive;
+    a.pairwise = ctx->visc_pw ? 1 : 0;
+    ctx->recs_pw = ctx->visc_pw;
     hipLaunchKernelGGL(prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
     return SPHX_OK;
@@ -376,6 +379,103 @@ int sphx_pass_visc(sphx_ctx* ctx, int64_t n, int k, const double* m) {
                        ctx->bc_s.as<RecBC>(), ctx->qorder,
                        OutMap{ctx->map_perm, ctx->map_perm ? ctx->map_nactive : (int)n}, m,
                        ctx->va.as<double>(), ctx->vh.as<double>());
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
+}
+
+// ---- passes 2 + 3 fused: the pairwise viscosity (visc_mode 1) ------------------------------------
+// pi_ik of nsc:649 stays inside the sum (the Monaghan form of the loop version, nsc:802-808):
+//   B_ik = pi_ik (M_j c_b + M_i c_a) / 2 (dx, dy, dz),  M = m [t==0] C/h^9 (RecBC.Bw, sphx_prep),  c_b, c_a as pass 3
+// nothing needs Pi_j, so pass 2 is not run; this pass casts its crossing-time vote instead.  The heat term is added
+// as t_b * (dv . dx) with the very dot product whose sign made pi_ik > 0 (w < 0): every term is >= 0 by construction.
+__global__ __launch_bounds__(256) void pass_visc_pw_kernel(int n, int npad, int k, int clip,
+                                                           const int* __restrict__ nbr,
+                                                           const RecB* __restrict__ recb,
+                                                           const double* __restrict__ rho_s,
+                                                           const RecBC* __restrict__ bc,
+                                                           const RecSelf* __restrict__ selfr,
+                                                           const int* __restrict__ qorder, OutMap om,
+                                                           const double* __restrict__ m, double* va, double* vh,
+                                                           u64* ct_bits) {
+    const int p = xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
+    u64 my_ct = 0x7FF0000000000000ull;       // +inf: "no crossing time"
+    const int i = (p < n) ? (qorder ? qorder[p] : p) : n;
+    const int o = (i < n) ? out_index(om, i) : 0x7FFFFFFF;
+    if (i < n && o < om.n_active) {
+        int j0 = nbr[p];
+        if (j0 < 0) j0 = i;
+        const double* rq = reinterpret_cast<const double*>(&recb[j0]);
+        const Q4 r0 = load4(rq), rv = load4(rq + 4);
+        const RecSelf sf = selfr[i];
+        const double rho_i = rho_s[i], cs_i = sf.csi, h_i = sf.h;
+        const double hi2 = recb[i].h2, ci = -6.0 * bc[i].Bw;
+        double a_x[SPHX_SUM_PARTS] = {}, a_y[SPHX_SUM_PARTS] = {}, a_z[SPHX_SUM_PARTS] = {}, a_h[SPHX_SUM_PARTS] = {};
+        double maxrel = 0.0;
+        for (int kk0 = 0; kk0 < k; kk0 += NBATCH) {
+          int jb[NBATCH];
+          Q4 q0b[NBATCH], qvb[NBATCH];
+          double rhob[NBATCH], mcb[NBATCH];
+#pragma unroll
+          for (int u = 0; u < NBATCH; ++u) jb[u] = (kk0 + u < k) ? nbr[(size_t)(kk0 + u) * npad + p] : -1;
+#pragma unroll
+          for (int u = 0; u < NBATCH; ++u) {
+              const int jj = jb[u] < 0 ? i : jb[u];
+              const double* qb = reinterpret_cast<const double*>(&recb[jj]);
+              q0b[u] = load4(qb); qvb[u] = load4(qb + 4);
+              rhob[u] = rho_s[jj];
+              mcb[u] = bc[jj].Bw;
+          }
+#pragma unroll
+          for (int u = 0; u < NBATCH; ++u) {
+            if (jb[u] < 0) continue;
+            const Q4 q0 = q0b[u], qv = qvb[u];
+            const double dx = q0.a - r0.a, dy = q0.b - r0.b, dz = q0.c - r0.c;
+            const double dvx = qv.a - rv.a, dvy = qv.b - rv.b, dvz = qv.c - rv.c;
+            const double rr = dx * dx + dy * dy + dz * dz;
+            const double dot = dvx * dx + dvy * dy + dvz * dz;
+            double w = dot / sqrt(rr + 0.01 * q0.d);                        // nsc:643
+            w = (w > 0.0) ? 0.0 : w;                                        // nsc:644
+            const double rho_ab = (rhob[u] + rho_i) / 2.0;                  // nsc:646
+            const double c_ab = 0.5 * (qv.d + cs_i);                        // nsc:647
+            const double pi = -0.5 * (c_ab * 2.0 - 3.0 * w) * w / rho_ab;   // nsc:649, per pair
+            maxrel = fmax(maxrel, dvx * dvx + dvy * dvy + dvz * dvz);       // nsc:780
+            const double r = sqrt(rr);
+            const double r2 = r * r;
+            const double qj = q0.d - r2, qi = hi2 - r2;
+            const double cb = (clip && !(qj > 0.0)) ? 0.0 : -6.0 * mcb[u] * (qj * qj);
+            const double ca = ci * (qi * qi);
+            const double tb = pi * (cb + ca) / 2.0;
+            a_x[u & (SPHX_SUM_PARTS - 1)] += tb * dx; a_y[u & (SPHX_SUM_PARTS - 1)] += tb * dy; a_z[u & (SPHX_SUM_PARTS - 1)] += tb * dz;
+            a_h[u & (SPHX_SUM_PARTS - 1)] += tb * dot;                       // nsc:653
+          }
+        }
+        const double ax = parts_total(a_x), ay = parts_total(a_y), az = parts_total(a_z), heat = parts_total(a_h);
+        va[3 * (size_t)o + 0] = -ax; va[3 * (size_t)o + 1] = -ay; va[3 * (size_t)o + 2] = -az;
+        vh[o] = heat * m[o] / 2.0;                                          // nsc:654
+        if (sf.mg > 0.0) {                                                  // gas only     nsc:782
+            double ct = h_i / sqrt(maxrel);
+            if (ct != ct) ct = 0.0;                                         // nan_to_num
+            if (ct > DBL_MAX) ct = DBL_MAX;
+            if (ct > 0.0) my_ct = (u64)__double_as_longlong(ct);
+        }
+    }
+    u64 bm = block_min_u64(my_ct);
+    if (threadIdx.x == 0 && bm != 0x7FF0000000000000ull) atomicMin(ct_bits, bm);
+}
+
+int sphx_pass_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m) {
+    SPHX_TRY(sphx_ensure(ctx, ctx->va, (size_t)n * 3 * sizeof(double)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->vh, (size_t)n * sizeof(double)));
+    u64* ct = ctx->scal.as<u64>() + SC_CT_BITS;
+    // the crossing-time vote of pass 2 moves here, with its priming protocol
+    if (!ctx->ct_primed) SPHX_TRY(sphx_prime_ct(ctx, ct));
+    ctx->ct_primed = false;
+    if (ctx->qorder && ctx->blob_lists) return sphx_blob_visc_pw(ctx, n, k, m, ct);
+    hipLaunchKernelGGL(pass_visc_pw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (int)n, (int)sphx_pad64(n), k, ctx->clip_grad, ctx->nbr.as<int>(), ctx->recv.as<RecB>(),
+                       ctx->rho_s.as<double>(), ctx->bc_s.as<RecBC>(), ctx->self_s.as<RecSelf>(), ctx->qorder,
+                       OutMap{ctx->map_perm, ctx->map_perm ? ctx->map_nactive : (int)n}, m,
+                       ctx->va.as<double>(), ctx->vh.as<double>(), ct);
     HIPCHK(hipGetLastError());
     return SPHX_OK;
 }

@@ -198,11 +198,12 @@ class Exchanger:
 # compute backend on the GPU: libsphx sphx_dev_* (include/sphx.h)
 # ==============================================================================================
 class LibBackend:
-    def __init__(self, device_index, k=40, dist_bound=0.0, clip_grad=False):
+    def __init__(self, device_index, k=40, dist_bound=0.0, clip_grad=False, visc_mode="ref_axis0"):
         from . import _lib
         self.ctx = _lib.Context(device_index)
         self.ctx.check(self.ctx.lib.sphx_set_clip_grad(self.ctx.h, 1 if clip_grad else 0))
         self.lib = self.ctx.lib
+        self.set_visc_mode(visc_mode)
         self.k = k
         self.dist_bound = dist_bound
         self.device = torch.device("cuda", device_index)
@@ -378,6 +379,26 @@ class LibBackend:
         self._chk(self.lib.sphx_dev_pi(self.ctx.h, self._p(rho_complete), None, self._p(bw), self._p(ct)))
         return bw, ct
 
+    def set_visc_mode(self, visc_mode):
+        """"ref_axis0" (pi + visc) or "pairwise" (visc_pairwise): include/sphx.h sphx_set_visc_mode; applies to the
+        records prep() builds from now on."""
+        from .compat import visc_mode_code
+        self._chk(self.lib.sphx_set_visc_mode(self.ctx.h, visc_mode_code(visc_mode)))
+        self.visc_mode = visc_mode
+
+    def visc_pairwise(self, rho_complete, m, out=None):
+        """Pairwise viscosity (sphx_dev_visc_pairwise): needs only the ghosts' densities -> (va, vh, ct)."""
+        n, dev = self.n_total, self.device
+        if out is None:
+            va = torch.empty((n, 3), dtype=torch.float64, device=dev)
+            vh = torch.empty(n, dtype=torch.float64, device=dev)
+            ct = torch.zeros(1, dtype=torch.float64, device=dev)
+        else:
+            va, vh, ct = out
+        self._chk(self.lib.sphx_dev_visc_pairwise(self.ctx.h, self._p(rho_complete), self._p(m), self._p(va), self._p(vh),
+                                                  self._p(ct)))
+        return va, vh, ct
+
     def visc(self, bw_complete, m, out=None):
         n, dev = self.n_total, self.device
         if out is None:
@@ -512,12 +533,26 @@ class DistributedSim:
 
     def __init__(self, state, lo, hi, backend, rank=0, world=1, device="cpu", comm_device=None,
                  halo_scale=1.15, skin_frac=0.15, need_grid=96, migrate_every=4, forms="hydro_update", d=None,
-                 with_drag=False, with_species=False, agb=None):
+                 with_drag=False, with_species=False, agb=None, visc_mode=None):
         """forms: the sums of the step - "hydro_update" (nsc:556-671; four halo phases) or "loop", the loop forms the
         reference's time loop calls (drv:451-458, smoothing length from the driver's global `d`, drv:68; three halo
-        phases: state + E, h_j, rho_j - no Pi_j)."""
+        phases: state + E, h_j, rho_j - no Pi_j).  visc_mode (hydro_update forms): "ref_axis0" or "pairwise" - the
+        per-pair viscosity of include/sphx.h sphx_set_visc_mode, three halo phases (state, h_j, rho_j; no m Pi_j);
+        it needs a backend with visc_pairwise (LibBackend).  The backend holds the mode (LibBackend(visc_mode=...));
+        None takes the backend's, a value that disagrees with it is a ValueError."""
         if forms not in ("hydro_update", "loop"):
             raise ValueError("forms must be 'hydro_update' or 'loop'")
+        from .compat import visc_mode_code
+        be_mode = getattr(backend, "visc_mode", None)
+        if visc_mode is None:
+            visc_mode = be_mode or "ref_axis0"
+        if visc_mode_code(visc_mode) and forms == "loop":
+            raise ValueError("visc_mode='pairwise' is for forms='hydro_update': the loop forms' viscosity is pairwise already")
+        if be_mode is not None and be_mode != visc_mode:
+            raise ValueError("visc_mode=%r but the backend was made with visc_mode=%r" % (visc_mode, be_mode))
+        if visc_mode == "pairwise" and not hasattr(backend, "visc_pairwise"):
+            raise ValueError("visc_mode='pairwise' needs a backend with visc_pairwise (LibBackend)")
+        self.visc_mode = visc_mode
         if forms == "loop" and not (d is not None and d > 0):
             raise ValueError("forms='loop' needs the driver's global d (code_running.py:67-68)")
         self.forms, self.d = forms, (float(d) if d is not None else None)
@@ -1008,6 +1043,7 @@ class DistributedSim:
                     self._step_extras(be, no, ng, send_idx, recv_counts, m, ptype, extra, rho, rhod)
             else:
               with self._sec("sums+halo_scalars"):
+                pairwise = self.visc_mode == "pairwise"
                 xch = lambda a, defer=False: self._exchange(send_idx, recv_counts, [a[:no]], into=tail(a), send_cat=self.send_cat,
                                                             defer=defer)
                 if self.overlap and self.world > 1 and hasattr(be, "select_blobs") and be.select_blobs(1):
@@ -1020,22 +1056,30 @@ class DistributedSim:
                     be.prep(pos, vel, m, h, T, mu, gam, ptype)                 # (ghosts' records)
                     rho, nden, ha = be.density(self.with_drag, out=o1)
                     done = xch(rho, True); be.select_blobs(1)                  # rho_j
-                    o2 = be.pi(rho)
-                    done(); be.select_blobs(2)
-                    bw, ct = be.pi(rho, out=o2)
-                    done = xch(bw, True); be.select_blobs(1)                   # m Pi_j
-                    o3 = be.visc(bw, m)
-                    done(); be.select_blobs(2)
-                    va, vh = be.visc(bw, m, out=o3)
+                    if pairwise:                                               # (no m Pi_j phase)
+                        o2 = be.visc_pairwise(rho, m)
+                        done(); be.select_blobs(2)
+                        va, vh, ct = be.visc_pairwise(rho, m, out=o2)
+                    else:
+                        o2 = be.pi(rho)
+                        done(); be.select_blobs(2)
+                        bw, ct = be.pi(rho, out=o2)
+                        done = xch(bw, True); be.select_blobs(1)               # m Pi_j
+                        o3 = be.visc(bw, m)
+                        done(); be.select_blobs(2)
+                        va, vh = be.visc(bw, m, out=o3)
                     be.select_blobs(0)
                 else:
                     xch(h)                                                     # h_j
                     be.prep(pos, vel, m, h, T, mu, gam, ptype)
                     rho, nden, ha = be.density(True) if self.with_drag else be.density()
                     xch(rho)                                                   # rho_j
-                    bw, ct = be.pi(rho)
-                    xch(bw)                                                    # m Pi_j
-                    va, vh = be.visc(bw, m)
+                    if pairwise:
+                        va, vh, ct = be.visc_pairwise(rho, m)
+                    else:
+                        bw, ct = be.pi(rho)
+                        xch(bw)                                                # m Pi_j
+                        va, vh = be.visc(bw, m)
                 self._step_extras(be, no, ng, send_idx, recv_counts, m, ptype, extra, rho,
                                   getattr(be, "rhod", None) if self.with_drag else None)
             # ---- ONE reduction and ONE host read for the step's scalars: halo verdict (max), global
@@ -1223,7 +1267,7 @@ class DistributedSim:
                    T=c(s["T"]), sizes=c(s["h"]), mass=c(s["m"]), mu_array=c(s["mu"]), gamma_array=c(s["gam"]),
                    particle_type=c(s["ptype"]), lo=c(self.lo), hi=c(self.hi), first=np.int64(1 if self.first else 0),
                    dt_last=np.float64(self.dt_last), hmean_prev=np.float64(self.hmean_prev), hmax_prev=np.float64(self.hmax_prev),
-                   world=np.int64(self.world), forms=np.array(self.forms), d=np.float64(self.d if self.d is not None else 0.0),
+                   world=np.int64(self.world), forms=np.array(self.forms), visc_mode=np.array(self.visc_mode), d=np.float64(self.d if self.d is not None else 0.0),
                    steps=np.int64(self.stats["steps"]),
                    # what the step does beyond the core sums, and the per-particle fields that go with it (they migrate
                    # with the particles: the snapshot holds them in the owned order like everything else)
@@ -1256,6 +1300,7 @@ class DistributedSim:
             raise ValueError("the snapshot's run carried an AGB table (metallicity + yields in the species pass): pass agb=(splines, "
                              "mapto, divisor) to from_snapshot")
         forms = str(z["forms"])
+        kw.setdefault("visc_mode", str(z["visc_mode"]) if "visc_mode" in z else "ref_axis0")    # (older files: none)
         sim = cls(state, z["lo"], z["hi"], backend, rank, world, forms=forms, d=(float(z["d"]) if forms == "loop" else None), **kw)
         sim.s["h"] = torch.as_tensor(np.ascontiguousarray(z["sizes"], dtype=np.float64)).to(sim.device)
         sim.first = bool(int(z["first"]))

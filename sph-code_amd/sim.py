@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import dp, f64
+from .compat import visc_mode_code
 
 log = logging.getLogger("sph_code_amd")
 
@@ -19,11 +20,16 @@ log = logging.getLogger("sph_code_amd")
 class Simulation:
     def __init__(self, state, n_neigh=40, dist=None, device=None, with_species=False, ctx=None,
                  incremental=False, with_drag=False, gravity=None, G=6.67430e-11, clip_grad=False,
-                 forms="hydro_update", d=None, gravity_order=2, agb=None):
+                 forms="hydro_update", d=None, gravity_order=2, agb=None, visc_mode="ref_axis0"):
         """with_species: carry f_un on the device; every step (hydro_update mode) then also forms the species number
         densities F[s,i] of nsc:624-627 on its own neighbour list.  agb = (splines, mapto, divisor) as
         sph_code_amd.agb.interpolate_amounts returns them: the same pass also leaves the per-particle metallicity
-        (the expression of code_running.py:663) and the AGB dust yields of config_helper.py:183-189 (download_species)."""
+        (the expression of code_running.py:663) and the AGB dust yields of config_helper.py:183-189 (download_species).
+        visc_mode="pairwise": the per-pair viscosity of include/sphx.h sphx_set_visc_mode (hydro_update mode only; the
+        loop forms' viscosity is pairwise already)."""
+        vmode = visc_mode_code(visc_mode)
+        if vmode and forms == "loop":
+            raise ValueError("visc_mode='pairwise' is for forms='hydro_update': the loop forms' viscosity is pairwise already")
         self.ctx = ctx if ctx is not None else _lib.Context(device)
         self.ctx.set_incremental(incremental)
         self.k = int(n_neigh)
@@ -43,6 +49,7 @@ class Simulation:
             dp(f64(state["mu_array"], (n,))), dp(f64(state["gamma_array"], (n,))),
             dp(f64(state["E_internal"], (n,))), dp(acc)))
         c.check(c.lib.sphx_set_clip_grad(c.h, 1 if clip_grad else 0))
+        c.check(c.lib.sphx_set_visc_mode(c.h, vmode))
         if forms not in ("hydro_update", "loop"):
             raise ValueError("forms must be 'hydro_update' or 'loop'")
         if forms == "loop":            # the reference's time loop: nsc.density, del_pressure, ... with the global d
