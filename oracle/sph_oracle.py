@@ -119,7 +119,7 @@ def _pair_geometry(nb, pts, vel, h, lo, hi, clip_grad=False):
 
 def hydro_update(neighbor, points, mass, sizes, f_un, particle_type, T, mu_array, gamma_array,
                  velocities, chunk=32768, return_intermediates=False, rho_in=None, Bj_in=None,
-                 clip_grad=False):
+                 clip_grad=False, visc_mode="ref_axis0"):
     """Restatement of nsc:556-671 with the axis repair of SURVEY F5 (Pi_i = sum_k pi_ik).
 
     Returns (hydro_accel (N,3), visc_accel (N,3), visc_heat (N,), density (N,),
@@ -127,7 +127,23 @@ def hydro_update(neighbor, points, mass, sizes, f_un, particle_type, T, mu_array
     reference's sign convention (+grad P / rho).  Rows with idx == N contribute 0.
     rho_in / Bj_in replace the neighbour-side rho_j (nsc:646) and m Pi_j [t==0] (nsc:651) - used
     by the domain-decomposition tests, where ghost rows carry values computed by their owners.
+
+    visc_mode (not the reference's arithmetic beyond "ref_axis0"; include/sphx.h sphx_hydro_update):
+      "ref_axis0"      B_ik = 1/2 [m_j g_j Pi_j gb + m_i g_i Pi_i ga],  Pi_i = sum_k pi_ik   (nsc:649-652 repaired)
+      "pairwise"       B_ik = 1/2 pi_ik [m_j g_j gb + m_i g_i ga]       (pi_ik, the nsc:649 term, inside the sum)
+      "axis0_restated" the pairwise statements with Pi_j / Pi_i in place of pi_ik: the same sums as "ref_axis0" in
+                       another order of operations - it ties the pairwise code path to the golden fixtures.
+    visc_accel_i = -sum_k B_ik,  visc_heat_i = (m_i/2) sum_k B_ik . dv  in every mode.
+
+    return_intermediates: True -> (outputs, dict) with the per-pair (N,K) arrays the fixtures capture and the per-row
+    bounds below; "rows" -> the per-row entries only (what a 10^6-row comparison can afford):
+      G_abs_terms (N,3)          sum_k |term_k| of the pressure sum of nsc:615 (before the division by rho)
+      visc_abs_terms (N,3)       sum_k |B_ik|
+      visc_heat_abs_terms (N,)   sum_k |B_ik . dv| |m_i| / 2
     """
+    if visc_mode not in ("ref_axis0", "pairwise", "axis0_restated"):
+        raise ValueError("visc_mode must be 'ref_axis0', 'pairwise' or 'axis0_restated', not %r" % (visc_mode,))
+    per_pair = return_intermediates is True
     nb = np.asarray(neighbor).astype(np.int64)
     pts = np.asarray(points, dtype=np.float64)
     vel = np.asarray(velocities, dtype=np.float64)
@@ -167,7 +183,7 @@ def hydro_update(neighbor, points, mass, sizes, f_un, particle_type, T, mu_array
         wN = np.where(valid, Nw[j], 0.) * W
         for s in range(S):
             F[s, lo:hi] = np.sum(wN * fu[j, s], axis=1)                      # nsc:626
-        if return_intermediates:
+        if per_pair:
             inter.setdefault("W6_kernel", []).append(W)
             inter.setdefault("distances", []).append(np.sqrt(r2))
             inter.setdefault("neigh_sizes", []).append(hj)
@@ -190,7 +206,8 @@ def hydro_update(neighbor, points, mass, sizes, f_un, particle_type, T, mu_array
             pi = -1. / 2. * (c_ab * 2 - 3 * w) * w / rho_ab                  # nsc:649
         pi = np.where(valid, pi, 0.)
         Pi[lo:hi] = np.sum(pi, axis=1)
-        if return_intermediates:
+        if per_pair:
+            inter.setdefault("pi", []).append(pi)
             inter.setdefault("w_ab", []).append(w)
             inter.setdefault("rho_avg_ab", []).append(rho_ab)
             inter.setdefault("c_sound_ab", []).append(c_ab)
@@ -200,15 +217,33 @@ def hydro_update(neighbor, points, mass, sizes, f_un, particle_type, T, mu_array
     Bj_own = Bj
     if Bj_in is not None:
         Bj = np.asarray(Bj_in, dtype=np.float64)
+    mg_all = m * (pt == 0.)
     for lo in range(0, n, chunk):
         hi = min(n, lo + chunk)
         j, valid, dx, dv, r2, hj, W, cb, ca = _pair_geometry(nb, pts, vel, h, lo, hi, clip_grad)
-        B = ((np.where(valid, Bj[j], 0.) * cb)[..., None] * dx
-             + (Bj_own[lo:hi][:, None] * ca)[..., None] * dx) / 2.
-        visc_accel[lo:hi] = -np.sum(B, axis=1)                                # nsc:651-652
-        if return_intermediates:
-            inter.setdefault("visc_abs_terms", []).append(np.sum(np.abs(B), axis=1))
-        visc_heat[lo:hi] = np.sum(B * dv, axis=(1, 2)) * m[lo:hi] / 2.        # nsc:653-654
+        if visc_mode == "ref_axis0":
+            B = ((np.where(valid, Bj[j], 0.) * cb)[..., None] * dx
+                 + (Bj_own[lo:hi][:, None] * ca)[..., None] * dx) / 2.
+        else:
+            with np.errstate(all="ignore"):
+                if visc_mode == "pairwise":                                   # the pair's own pi_ik, as in the Pi pass
+                    w = np.sum(dv * dx, axis=2) / np.sqrt(r2 + 0.01 * hj ** 2)
+                    w = np.where(w > 0., 0., w)
+                    rho_ab = (np.where(valid, rho[j], 0.) + rho[lo:hi][:, None]) / 2.
+                    c_ab = 0.5 * (np.where(valid, cs[j], 0.) + cs_i[lo:hi][:, None])
+                    p_nb = p_own = np.where(valid, -1. / 2. * (c_ab * 2 - 3 * w) * w / rho_ab, 0.)
+                else:
+                    p_nb, p_own = Pi[j], np.broadcast_to(Pi[lo:hi][:, None], j.shape)
+                B = ((np.where(valid, mg_all[j], 0.) * p_nb * cb)[..., None] * dx
+                     + (mg_all[lo:hi][:, None] * p_own * ca)[..., None] * dx) / 2.
+                B = np.where(valid[..., None], B, 0.)
+        with np.errstate(all="ignore"):
+            visc_accel[lo:hi] = -np.sum(B, axis=1)                            # nsc:651-652
+            Bdv = np.sum(B * dv, axis=2)
+            visc_heat[lo:hi] = np.sum(B * dv, axis=(1, 2)) * m[lo:hi] / 2.    # nsc:653-654
+            if return_intermediates:
+                inter.setdefault("visc_abs_terms", []).append(np.sum(np.abs(B), axis=1))
+                inter.setdefault("visc_heat_abs_terms", []).append(np.sum(np.abs(Bdv), axis=1) * np.abs(m[lo:hi]) / 2.)
     out = (hydro_accel, visc_accel, visc_heat, rho_out, nden, F, rho_d)
     if return_intermediates:
         inter = {k_: np.concatenate(v, axis=0) for k_, v in inter.items()}
@@ -222,12 +257,33 @@ def hydro_update(neighbor, points, mass, sizes, f_un, particle_type, T, mu_array
 # ==========================================================================================
 # loop forms                                                                 nsc:673-816
 # ==========================================================================================
+LOOP_CHUNK = 32768      # rows per pass of the loop forms: their (chunk, K, 3) temporaries stay small at any N
+
+
+def _row_chunks(n, chunk):
+    """Row ranges of at most `chunk` rows (None: all rows at once).  Rows are independent, so the loop forms
+    return the same bits for every chunk size."""
+    step = n if not chunk else int(chunk)
+    return [(lo, min(n, lo + step)) for lo in range(0, n, max(step, 1))]
+
+
 def _loop_geometry(points, neighbor):
-    pts = np.asarray(points, dtype=np.float64)
-    nb = np.asarray(neighbor).astype(np.int64)
-    dx = pts[nb] - pts[:, None, :]                     # relative to particle i itself
-    r2 = np.sum(dx ** 2, axis=2)
+    """All rows at once, every entry a particle -> (pts, nb, dx, r2)."""
+    pts, nb, valid, dx, r2 = _loop_rows(points, neighbor, 0, None)
     return pts, nb, dx, r2
+
+
+def _loop_rows(points, neighbor, lo, hi):
+    """Rows lo:hi -> (pts, nb (c,K) with missing entries pointed at particle 0, valid (c,K), dx, r2).  An entry
+    idx == N is a missing neighbour (nsc:545-548): the reference would raise on it, here - as in
+    hydro_update - it contributes zero to every sum."""
+    pts = np.asarray(points, dtype=np.float64)
+    nb = np.asarray(neighbor)[lo:hi].astype(np.int64)
+    valid = nb < len(pts)
+    nb = np.where(valid, nb, 0)
+    dx = pts[nb] - pts[lo:hi][:, None, :]              # relative to particle i itself
+    r2 = np.sum(dx ** 2, axis=2)
+    return pts, nb, valid, dx, r2
 
 
 def _weigh2(r2, m, d):
@@ -247,48 +303,69 @@ def _grad_weight(dx, r2, m, d, ptype_nb):
     return np.nan_to_num((c * (q > 0))[..., None] * dx)
 
 
-def density(points, mass, particle_type, neighbor, d):
+def density(points, mass, particle_type, neighbor, d, chunk=LOOP_CHUNK):
     """nsc:693-702."""
-    pts, nb, dx, r2 = _loop_geometry(points, neighbor)
-    m = np.asarray(mass, dtype=np.float64)[nb]
-    rho = _weigh2(r2, m, d) * (np.asarray(particle_type)[nb] == 0)
-    return np.sum(np.where(rho > 0, rho, 0.), axis=1)
+    n = len(points)
+    out = np.zeros(n)
+    for lo, hi in _row_chunks(n, chunk):
+        pts, nb, valid, dx, r2 = _loop_rows(points, neighbor, lo, hi)
+        m = np.asarray(mass, dtype=np.float64)[nb]
+        rho = _weigh2(r2, m, d) * (np.asarray(particle_type)[nb] == 0)
+        out[lo:hi] = np.sum(np.where(valid & (rho > 0), rho, 0.), axis=1)
+    return out
 
 
-def dust_density(points, mass, neighbor, particle_type, sizes, d=None):
+def dust_density(points, mass, neighbor, particle_type, sizes, d=None, chunk=LOOP_CHUNK):
     """nsc:704-717."""
-    pts, nb, dx, r2 = _loop_geometry(points, neighbor)
-    m = np.asarray(mass, dtype=np.float64)[nb]
-    ds = np.asarray(sizes, dtype=np.float64)[nb]
-    with np.errstate(all="ignore"):
-        rho = _weigh2_dust(r2, m, ds) * (np.asarray(particle_type)[nb] == 2)
-    return np.sum(np.where(rho > 0, rho, 0.), axis=1)
+    n = len(points)
+    out = np.zeros(n)
+    for lo, hi in _row_chunks(n, chunk):
+        pts, nb, valid, dx, r2 = _loop_rows(points, neighbor, lo, hi)
+        m = np.asarray(mass, dtype=np.float64)[nb]
+        ds = np.asarray(sizes, dtype=np.float64)[nb]
+        with np.errstate(all="ignore"):
+            rho = _weigh2_dust(r2, m, ds) * (np.asarray(particle_type)[nb] == 2)
+        out[lo:hi] = np.sum(np.where(valid & (rho > 0), rho, 0.), axis=1)
+    return out
 
 
-def num_dens(mass, points, mu_array, neighbor, d):
+def num_dens(mass, points, mu_array, neighbor, d, chunk=LOOP_CHUNK):
     """nsc:744-753 (no type mask; m_h, not amu)."""
-    pts, nb, dx, r2 = _loop_geometry(points, neighbor)
-    m = np.asarray(mass, dtype=np.float64)[nb]
-    nd = _weigh2(r2, m, d) / (np.asarray(mu_array, dtype=np.float64)[nb] * M_H)
-    return np.sum(np.where(nd > 0, nd, 0.), axis=1)
+    n = len(points)
+    out = np.zeros(n)
+    for lo, hi in _row_chunks(n, chunk):
+        pts, nb, valid, dx, r2 = _loop_rows(points, neighbor, lo, hi)
+        m = np.asarray(mass, dtype=np.float64)[nb]
+        nd = _weigh2(r2, m, d) / (np.asarray(mu_array, dtype=np.float64)[nb] * M_H)
+        out[lo:hi] = np.sum(np.where(valid & (nd > 0), nd, 0.), axis=1)
+    return out
 
 
-def del_pressure(points, mass, particle_type, neighbor, E_internal, gamma_array, d):
-    """nsc:755-774."""
-    pts, nb, dx, r2 = _loop_geometry(points, neighbor)
+def del_pressure(points, mass, particle_type, neighbor, E_internal, gamma_array, d, chunk=LOOP_CHUNK,
+                 return_abs_terms=False):
+    """nsc:755-774.  return_abs_terms: -> (sum, sum_k |term_k| per row and component)."""
+    n = len(points)
     pt = np.asarray(particle_type)
-    m = np.asarray(mass, dtype=np.float64)[nb]
     E = np.asarray(E_internal, dtype=np.float64)
-    gw = _grad_weight(dx, r2, m, d, pt[nb])
-    fac = 0.5 * (E[nb] + E[:, None]) / np.asarray(gamma_array, dtype=np.float64)[nb]
-    out = np.sum(gw * fac[..., None], axis=1)
-    return out * (pt == 0)[:, None]
+    out = np.zeros((n, 3)); out_abs = np.zeros((n, 3))
+    for lo, hi in _row_chunks(n, chunk):
+        pts, nb, valid, dx, r2 = _loop_rows(points, neighbor, lo, hi)
+        m = np.asarray(mass, dtype=np.float64)[nb]
+        gw = _grad_weight(dx, r2, m, d, pt[nb])
+        fac = 0.5 * (E[nb] + E[lo:hi][:, None]) / np.asarray(gamma_array, dtype=np.float64)[nb]
+        term = np.where(valid[..., None], gw * fac[..., None], 0.)
+        gas_i = (pt[lo:hi] == 0)[:, None]
+        out[lo:hi] = np.sum(term, axis=1) * gas_i
+        if return_abs_terms:
+            out_abs[lo:hi] = np.sum(np.abs(term), axis=1) * gas_i
+    return (out, out_abs) if return_abs_terms else out
 
 
 def artificial_viscosity(neighbor, points, particle_type, sizes, mass, densities, velocities, T,
-                         gamma_array, mu_array, d):
-    """nsc:788-816."""
-    pts, nb, dx, r2 = _loop_geometry(points, neighbor)
+                         gamma_array, mu_array, d, chunk=LOOP_CHUNK, return_abs_terms=False):
+    """nsc:788-816 -> (accel (N,3), heat (N,)).  return_abs_terms: two more, sum_k |accel term_k| (N,3) and
+    sum_k |heat term_k| (N,)."""
+    n = len(points)
     pt = np.asarray(particle_type)
     m = np.asarray(mass, dtype=np.float64)
     vel = np.asarray(velocities, dtype=np.float64)
@@ -296,29 +373,45 @@ def artificial_viscosity(neighbor, points, particle_type, sizes, mass, densities
     with np.errstate(all="ignore"):
         css = np.nan_to_num((np.asarray(gamma_array) * K_B * np.asarray(T)
                              / (np.asarray(mu_array) * AMU)) ** 0.5)
-        dv = vel[nb] - vel[:, None, :]
-        w = np.sum(dv * dx, axis=2) / r2 ** 0.5
-        w = np.where(w > 0, 0., w)
-        w = np.nan_to_num(w)
-        vsig = css[nb] + css[:, None] - 3 * w
-        rho_ij = (rho[nb] + rho[:, None]) / 2.
-        PI = -1. / 2. * vsig * w / rho_ij
-        gw = _grad_weight(dx, r2, m[:, None], d, pt[nb])
-        mbar = (m[nb] + m[:, None]) / 2.
-        accel_ij = (mbar * PI)[..., None] * gw
-        heat_ij = 0.5 * mbar * PI * np.sum(dv * gw, axis=2)
-    gasnb = pt[nb] == 0
-    accel = np.sum(np.where(gasnb[..., None], accel_ij, 0.), axis=1)
-    heat = np.sum(np.where(gasnb, heat_ij, 0.), axis=1)
-    act = (pt == 0) & (np.sum(gasnb, axis=1) > 0)
-    return accel * act[:, None], heat * act
+    accel = np.zeros((n, 3)); heat = np.zeros(n)
+    accel_abs = np.zeros((n, 3)); heat_abs = np.zeros(n)
+    for lo, hi in _row_chunks(n, chunk):
+        pts, nb, valid, dx, r2 = _loop_rows(points, neighbor, lo, hi)
+        with np.errstate(all="ignore"):
+            dv = vel[nb] - vel[lo:hi][:, None, :]
+            w = np.sum(dv * dx, axis=2) / r2 ** 0.5
+            w = np.where(w > 0, 0., w)
+            w = np.nan_to_num(w)
+            vsig = css[nb] + css[lo:hi][:, None] - 3 * w
+            rho_ij = (rho[nb] + rho[lo:hi][:, None]) / 2.
+            PI = -1. / 2. * vsig * w / rho_ij
+            gw = _grad_weight(dx, r2, m[lo:hi][:, None], d, pt[nb])
+            mbar = (m[nb] + m[lo:hi][:, None]) / 2.
+            accel_ij = (mbar * PI)[..., None] * gw
+            heat_ij = 0.5 * mbar * PI * np.sum(dv * gw, axis=2)
+        gasnb = valid & (pt[nb] == 0)
+        accel_ij = np.where(gasnb[..., None], accel_ij, 0.)
+        heat_ij = np.where(gasnb, heat_ij, 0.)
+        act = (pt[lo:hi] == 0) & (np.sum(gasnb, axis=1) > 0)
+        accel[lo:hi] = np.sum(accel_ij, axis=1) * act[:, None]
+        heat[lo:hi] = np.sum(heat_ij, axis=1) * act
+        if return_abs_terms:
+            with np.errstate(all="ignore"):
+                accel_abs[lo:hi] = np.sum(np.abs(accel_ij), axis=1) * act[:, None]
+                heat_abs[lo:hi] = np.sum(np.abs(heat_ij), axis=1) * act
+    return (accel, heat, accel_abs, heat_abs) if return_abs_terms else (accel, heat)
 
 
-def crossing_time(neighbor, velocities, sizes, particle_type, dt_0=DT_0):
+def crossing_time(neighbor, velocities, sizes, particle_type, dt_0=DT_0, chunk=LOOP_CHUNK):
     """nsc:776-786."""
-    nb = np.asarray(neighbor).astype(np.int64)
     vel = np.asarray(velocities, dtype=np.float64)
-    rel = np.max(np.sum((vel[nb] - vel[:, None, :]) ** 2, axis=2), axis=1) ** 0.5
+    n = len(vel)
+    rel = np.zeros(n)
+    for lo, hi in _row_chunks(n, chunk):
+        nb = np.asarray(neighbor)[lo:hi].astype(np.int64)
+        valid = nb < n
+        dv2 = np.sum((vel[np.where(valid, nb, 0)] - vel[lo:hi][:, None, :]) ** 2, axis=2)
+        rel[lo:hi] = np.max(np.where(valid, dv2, 0.), axis=1) ** 0.5
     with np.errstate(all="ignore"):
         ct = np.nan_to_num(np.asarray(sizes, dtype=np.float64) / rel) * (np.asarray(particle_type) == 0)
     nz = ct[ct != 0]
@@ -341,26 +434,37 @@ def sigma_effective():
         * -(a[1] ** -0.5 - a[0] ** -0.5) / (a[1] ** 0.5 - a[0] ** 0.5)
 
 
-def net_impulse(points, mass, sizes, velocities, particle_type, neighbor, f_un, d=None):
-    """nsc:719-742: dust -> gas drag with scatter-added reaction."""
-    pts, nb, dx, r2 = _loop_geometry(points, neighbor)
-    n = len(pts)
+def net_impulse(points, mass, sizes, velocities, particle_type, neighbor, f_un, d=None, chunk=LOOP_CHUNK,
+                return_abs_terms=False):
+    """nsc:719-742: dust -> gas drag with scatter-added reaction -> (onto (N,3), reaction (N,3)).
+    return_abs_terms: two more, the sums of the absolute values of the terms each of the two gathers / receives."""
+    n = len(points)
     pt = np.asarray(particle_type)
     fu = np.asarray(f_un, dtype=np.float64)
     vel = np.asarray(velocities, dtype=np.float64)
     meff, seff = grain_mass(), sigma_effective()
     mgm = fu @ meff
     mcs = fu @ seff
-    dv = vel[nb] - vel[:, None, :]
-    with np.errstate(all="ignore"):
-        wf = _weigh2_dust(r2, np.asarray(mass, dtype=np.float64)[nb], np.asarray(sizes, dtype=np.float64)[nb])
-        coef = wf / mgm[nb] * mcs[nb] * np.sum(dv ** 2, axis=2) ** 0.5 * (pt[nb] == 2) * (wf > 0)
-        acc = coef[..., None] * dv
-    onto = np.sum(acc, axis=1)
-    react = np.zeros((n, 3))
-    notself = (nb != np.arange(n)[:, None])
-    np.add.at(react, nb.ravel(), (-(acc * notself[..., None])).reshape(-1, 3))
-    return onto, react
+    onto = np.zeros((n, 3)); react = np.zeros((n, 3))
+    onto_abs = np.zeros((n, 3)); react_abs = np.zeros((n, 3))
+    for lo, hi in _row_chunks(n, chunk):
+        pts, nb, valid, dx, r2 = _loop_rows(points, neighbor, lo, hi)
+        dv = vel[nb] - vel[lo:hi][:, None, :]
+        with np.errstate(all="ignore"):
+            wf = _weigh2_dust(r2, np.asarray(mass, dtype=np.float64)[nb], np.asarray(sizes, dtype=np.float64)[nb])
+            coef = wf / mgm[nb] * mcs[nb] * np.sum(dv ** 2, axis=2) ** 0.5 * (pt[nb] == 2) * (wf > 0)
+            acc = np.where(valid[..., None], coef[..., None] * dv, 0.)
+        onto[lo:hi] = np.sum(acc, axis=1)
+        notself = (nb != np.arange(lo, hi)[:, None])
+        back = (-(acc * notself[..., None])).reshape(-1, 3)
+        # the scatter in np.add.at's order (row by row, neighbour by neighbour).  Terms that are exactly zero - every gas
+        # neighbour's - are left out: the sums start at +0.0, and adding +-0.0 changes no bit of them
+        sel = np.any(back != 0, axis=1)
+        np.add.at(react, nb.ravel()[sel], back[sel])
+        if return_abs_terms:
+            onto_abs[lo:hi] = np.sum(np.abs(acc), axis=1)
+            np.add.at(react_abs, nb.ravel()[sel], np.abs(back[sel]))
+    return (onto, react, onto_abs, react_abs) if return_abs_terms else (onto, react)
 
 
 # ==========================================================================================

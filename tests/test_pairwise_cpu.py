@@ -19,33 +19,17 @@ def pair_pi(w, rho_ab, c_ab):
         return -1. / 2. * (c_ab * 2 - 3 * w) * w / rho_ab
 
 
-def viscosity_sums(args, clip_grad=False, mode="pairwise"):
+def viscosity_sums(args, clip_grad=False, mode="pairwise", chunk=32768, per_pair=True):
     """-> (oracle outputs with visc_accel, visc_heat replaced by the `mode` sums, per-pair pi (N,K)).
-    mode "axis0": the same code with pi_ik replaced by Pi_j (neighbour term) and Pi_i (own term)."""
-    nb, pts, m, h, fu, pt, T, mu, gam, vel = args
-    nb = np.asarray(nb).astype(np.int64)
-    n = len(nb)
+    mode "axis0": the same code with pi_ik replaced by Pi_j (neighbour term) and Pi_i (own term).
+    The sums are the oracle's (hydro_update visc_mode="pairwise" / "axis0_restated"), formed `chunk` rows at a time;
+    per_pair=False returns, in place of pi, the per-row bounds alone (visc_abs_terms = sum_k |B_ik|,
+    visc_heat_abs_terms = sum_k |B_ik . dv| m_i / 2, G_abs_terms) - nothing of size (N, K) is kept."""
+    visc_mode = {"pairwise": "pairwise", "axis0": "axis0_restated"}[mode]
     with np.errstate(all="ignore"):
-        out, inter = orc.hydro_update(*args, return_intermediates=True, clip_grad=clip_grad)
-    j, valid, dx, dv, r2, hj, W, cb, ca = orc._pair_geometry(nb, np.asarray(pts, np.float64),
-                                                             np.asarray(vel, np.float64), np.asarray(h, np.float64),
-                                                             0, n, clip_grad)
-    pi = np.where(valid, pair_pi(inter["w_ab"], inter["rho_avg_ab"], inter["c_sound_ab"]), 0.)
-    mg = np.asarray(m, np.float64) * (np.asarray(pt) == 0.)
-    if mode == "pairwise":
-        p_nb, p_own = pi, pi
-    else:
-        Pi = pi.sum(axis=1)
-        p_nb, p_own = Pi[j], np.broadcast_to(Pi[:, None], pi.shape)
-    with np.errstate(all="ignore"):
-        B = ((np.where(valid, mg[j], 0.) * p_nb * cb)[..., None] * dx
-             + (mg[:, None] * p_own * ca)[..., None] * dx) / 2.
-        B = np.where(valid[..., None], B, 0.)
-        va = -np.sum(B, axis=1)
-        vh = np.sum(B * dv, axis=(1, 2)) * np.asarray(m, np.float64) / 2.
-    out = list(out)
-    out[1], out[2] = va, vh
-    return tuple(out), pi
+        out, inter = orc.hydro_update(*args, return_intermediates=True if per_pair else "rows", clip_grad=clip_grad,
+                                      visc_mode=visc_mode, chunk=chunk)
+    return out, (inter["pi"] if per_pair else inter)
 
 
 def signed_close(x, ref, what, tol=1e-10):
