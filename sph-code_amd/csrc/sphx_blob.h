@@ -3,6 +3,7 @@
 // layout, staging, slot-list access and the lanes-per-particle reductions.
 #pragma once
 #include "sphx_internal.h"
+#include "sphx_pair.h"          // Q4, gload4; the pair terms the LDS kernels share with the gather kernels
 
 #ifndef BLOB_P
 #define BLOB_P 128                  // particles per workgroup
@@ -34,12 +35,6 @@ __device__ __forceinline__ unsigned slot_hash(int j) {
 }
 
 // ---- helpers -----------------------------------------------------------------------------------
-struct Q4 { double a, b, c, d; };
-__device__ __forceinline__ Q4 gload4(const double* p) {
-    const double2 lo = *reinterpret_cast<const double2*>(p);
-    const double2 hi = *reinterpret_cast<const double2*>(p + 2);
-    return Q4{lo.x, lo.y, hi.x, hi.y};
-}
 // chunks 2c, 2c+1 of slot s
 __device__ __forceinline__ Q4 lload4(const double2* img, int s, int c2) {
     const double2 lo = img[(2 * c2) * BLOB_S + s];
@@ -65,6 +60,7 @@ __device__ __forceinline__ double sqrt_mid(double x) {
     g = __builtin_fma(d1, h, g);
     return x > 0.0 ? g : 0.0;
 }
+struct SqrtMid { __device__ __forceinline__ double operator()(double x) const { return sqrt_mid(x); } };   // the terms of sphx_pair.h
 
 // the value held by the other lane of the pair (lane ^ 1), moved inside the VALU
 __device__ __forceinline__ double pair_swap(double v) {
@@ -181,3 +177,5 @@ __device__ __forceinline__ int blob_sel_at(const BlobSel& s, int bi, int count) 
 BlobSel sphx_blob_sel(sphx_ctx* ctx, int part);
 
 int sphx_blob_grid(sphx_ctx* ctx, int nblk);       // persistent grid of the LDS passes (2 workgroups per CU)
+// allow `kernel` up to `bytes` of dynamic LDS on the context's device (once per kernel: sphx_ctx::lds_raised)
+int sphx_lds_opt_in(sphx_ctx* ctx, const void* kernel, size_t bytes);

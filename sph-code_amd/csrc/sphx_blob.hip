@@ -21,9 +21,12 @@
 // A reference that found no free entry within BLOB_PROBES probes (blobs with more than ~900
 // distinct neighbours; the most seen at BLOB_P = 128 is ~800) keeps the 0xFFFE marker and is
 // fetched from global memory through the int32 list.
+//
+// What is computed for a neighbour is not written here: every *_batch function loads its records (LDS, or global
+// memory for an unstaged one) and hands them to the term functions of sphx_pair.h, which the gather kernels call too.
 #include "sphx_blob.h"
 #include "sphx_wave.h"
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)            // (as sphx_pair.h: NumPy never fuses a multiply into an add)
 #include <float.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -234,13 +237,13 @@ int sphx_blob_translate(sphx_ctx* ctx, int64_t n, int k) {
 // A batch of NB list positions of this lane.  FAST: every lane of the wave has a staged neighbour at
 // each of them (the usual case): straight-line LDS reads and arithmetic, nothing to branch on.
 // Otherwise a position may be empty (skipped) or unstaged (fetched through the int32 list).
-struct DensAcc { double rho, rd, n, gx, gy, gz; };
-// WOUT: the batch's species weights Nw_j W_ij (nsc:626) are handed back as well (0 where the list has no neighbour)
-template <bool FAST, bool CLIP, bool WOUT = false>
-__device__ __forceinline__ void density_batch(DensAcc& a, const unsigned (&sl)[NB], const double2* img,
+// wout: the batch's species weights Nw_j W_ij (nsc:626; 0 where the list has no neighbour), for the kernel that goes on to
+// the composition sweeps
+template <bool FAST, bool CLIP>
+__device__ __forceinline__ void density_batch(DensAcc& a, double (&wout)[NB], const unsigned (&sl)[NB], const double2* img,
                                               const RecA* __restrict__ rec, const int* __restrict__ nbr,
                                               size_t col0, size_t colstep, double xr, double yr, double zr,
-                                              double hi2, double ci, double Ai, double* wout = nullptr) {
+                                              double hi2, double ci, double Ai) {
     Q4 q0b[NB], q1b[NB];
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
@@ -253,40 +256,18 @@ __device__ __forceinline__ void density_batch(DensAcc& a, const unsigned (&sl)[N
     if (FAST) __builtin_amdgcn_sched_barrier(0);       // all of the batch's LDS reads are issued before its arithmetic
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
-        if (WOUT) wout[u] = 0.0;
+        wout[u] = 0.0;
         if (!FAST && sl[u] == SLOT_NONE) continue;
-        const Q4 q0 = q0b[u], q1 = q1b[u];
-        const double dx = q0.a - xr, dy = q0.b - yr, dz = q0.c - zr;
-        const double r = sqrt_mid(dx * dx + dy * dy + dz * dz);   // nsc:586
-        const double r2 = r * r;                              // nsc:588 squares the rounded distance
-        const double qj = q0.d - r2;
-        const double c1 = q1.a, ms = q1.b, Aj = q1.c, Nw = q1.d;
-        double W = c1 * (qj * qj * qj);                       // nsc:588
-        W = (W < 0.0) ? 0.0 : W;                              // nsc:589
-        const double cb = (CLIP && !(qj > 0.0)) ? 0.0 : -6.0 * c1 * (qj * qj);   // nsc:591 (not clipped; CLIP: nsc:689)
-        const double qi = hi2 - r2;
-        const double ca = ci * (qi * qi);                     // nsc:592
-        a.rho += fmax(ms, 0.0) * W;                           // nsc:605
-        a.rd += fmax(-ms, 0.0) * W;                           // nsc:606
-        const double nww = Nw * W;
-        a.n += nww;                                           // nsc:607
-        if (WOUT) wout[u] = nww;                              // nsc:626
-        // nsc:615, the pair's common factor taken out of the three components: (A_j g_b + A_i g_a) / 2 = t (dx, dy, dz) with
-        // t = (A_j c_b + A_i c_a) / 2 - 10 fp64 operations instead of 21, each a 4-cycle issue; a regrouping of
-        // the reference's products (a few ulp per term against a bound of 1e-12 x sum|term|), the same in every variant
-        const double tg = (Aj * cb + Ai * ca) * 0.5;
-        a.gx += tg * dx;
-        a.gy += tg * dy;
-        a.gz += tg * dz;
+        wout[u] = density_term<SqrtMid>(a, q0b[u], q1b[u], xr, yr, zr, hi2, ci, Ai, CLIP);
     }
 }
 
 // ---- pass 1: rho, rho_dust, n, grad P        nsc:588-619 --------------------------------------
-__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_kernel(int n, int npad, int k, int nblk, int clip,
+__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_kernel(int n, int npad, int k, int nblk,
                                                               const int* __restrict__ nbr,
                                                               const u16* __restrict__ slot16,
                                                               const int* __restrict__ uniq,
-                                                              const int* __restrict__ qorder,
+                                                              const int* __restrict__ qorder, int clip,
                                                               const int* __restrict__ omap, int n_active,
                                                               const RecA* __restrict__ rec, double* rho_s,
                                                               double* rho, double* rhod, double* nden, double* G,
@@ -325,10 +306,11 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_kernel(int n, 
                 if (m0 + NB < nm) load_slots(sl, tile, m0 + NB, half, t);    // next batch's slots, behind this one's reads
                 const size_t col0 = (size_t)(LPP * m0 + half) * npad + p;
                 const bool fast = all_staged(cur);
-                if (fast && !clip) density_batch<true, false>(a, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
-                else if (fast) density_batch<true, true>(a, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
-                else if (!clip) density_batch<false, false>(a, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
-                else density_batch<false, true>(a, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
+                double wo[NB];                                 // (the species weights: not wanted here)
+                if (fast && !clip) density_batch<true, false>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
+                else if (fast) density_batch<true, true>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
+                else if (!clip) density_batch<false, false>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
+                else density_batch<false, true>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
             }
             const double s_rho = group_total(a.rho), s_rd = group_total(a.rd), s_n = group_total(a.n);
             const double gx = group_total(a.gx), gy = group_total(a.gy), gz = group_total(a.gz);
@@ -369,18 +351,9 @@ __device__ __forceinline__ void pi_batch(double& s_pi, double& maxrel, const uns
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
         if (!FAST && sl[u] == SLOT_NONE) continue;
-        const Q4 q0 = q0b[u], qv = qvb[u];
-        const double rho_j = rhob[u];
-        const double dx = q0.a - r0.a, dy = q0.b - r0.b, dz = q0.c - r0.c;
-        const double dvx = qv.a - rv.a, dvy = qv.b - rv.b, dvz = qv.c - rv.c;
-        const double r2 = dx * dx + dy * dy + dz * dz;
-        const double dot = dvx * dx + dvy * dy + dvz * dz;
-        double w = dot / sqrt_mid(r2 + 0.01 * q0.d);                    // nsc:643
-        w = (w > 0.0) ? 0.0 : w;                                        // nsc:644
-        const double rho_ab = (rho_j + rho_i) / 2.0;                    // nsc:646
-        const double c_ab = 0.5 * (qv.d + cs_i);                        // nsc:647
-        s_pi += -0.5 * (c_ab * 2.0 - 3.0 * w) * w / rho_ab;             // nsc:649
-        maxrel = fmax(maxrel, dvx * dvx + dvy * dvy + dvz * dvz);       // nsc:780
+        const PiPair t = pi_term<SqrtMid>(q0b[u], qvb[u], rhob[u], r0, rv, rho_i, cs_i);
+        s_pi += t.pi;
+        maxrel = fmax(maxrel, t.rel);
     }
 }
 
@@ -395,11 +368,10 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_pi_kernel(int n, int n
                                                          const RecSelf* __restrict__ selfr, RecBC* bc, double* Pi,
                                                          double* BwOut, u64* ct_bits, BlobSel sel) {
     extern __shared__ double2 img[];                       // 4 * BLOB_S chunks, BLOB_S doubles, slot tile
-    __shared__ u64 sm[PASS_T / 64];
     double* lrho = reinterpret_cast<double*>(img + 4 * BLOB_S);
     u16* tile = reinterpret_cast<u16*>(lrho + BLOB_S);
     const int t = threadIdx.x / LPP, half = threadIdx.x & (LPP - 1);     // half: which partial sum
-    u64 my_ct = 0x7FF0000000000000ull;       // +inf: "no crossing time"
+    u64 my_ct = SPHX_CT_NONE;
     const int nsel = blob_sel_count(sel, nblk);
     for (int bi = blockIdx.x; bi < nsel; bi += gridDim.x) {
         const int b = blob_sel_at(sel, bi, nsel);
@@ -446,31 +418,17 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_pi_kernel(int n, int n
                 bc[i].Bw = bw;
                 if (BwOut) BwOut[o] = bw;
                 if (ms_i > 0.0) {                                               // gas only     nsc:782
-                    double ct = h_i / sqrt(maxrel);
-                    if (ct != ct) ct = 0.0;                                     // nan_to_num
-                    if (ct > DBL_MAX) ct = DBL_MAX;
-                    if (ct > 0.0) { const u64 cb = (u64)__double_as_longlong(ct); my_ct = cb < my_ct ? cb : my_ct; }
+                    const u64 cb = ct_vote_bits(h_i, maxrel);
+                    my_ct = cb < my_ct ? cb : my_ct;
                 }
             }
         }
         __syncthreads();
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 q = __shfl_xor(my_ct, o, 64);
-        my_ct = q < my_ct ? q : my_ct;
-    }
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = my_ct;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 r = sm[0];
-        for (int w = 1; w < PASS_T / 64; ++w) r = sm[w] < r ? sm[w] : r;
-        if (r != 0x7FF0000000000000ull) atomicMin(ct_bits, r);
-    }
+    block_min_vote<PASS_T>(my_ct, ct_bits);
 }
 
 // ---- pass 3: viscous acceleration + heat      nsc:651-654 --------------------------------------
-struct ViscAcc { double x, y, z, h; };
 template <bool FAST, bool CLIP>
 __device__ __forceinline__ void visc_batch(ViscAcc& a, const unsigned (&sl)[NB], const double2* img,
                                            const double* lc1, const RecB* __restrict__ recb,
@@ -496,26 +454,15 @@ __device__ __forceinline__ void visc_batch(ViscAcc& a, const unsigned (&sl)[NB],
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
         if (!FAST && sl[u] == SLOT_NONE) continue;
-        const Q4 q0 = q0b[u], qv = qvb[u];
-        const double c1 = c1b[u], Bj = qv.d;
-        const double dx = q0.a - r0.a, dy = q0.b - r0.b, dz = q0.c - r0.c;
-        const double r = sqrt_mid(dx * dx + dy * dy + dz * dz);
-        const double r2 = r * r;
-        const double qj = q0.d - r2, qi = hi2 - r2;
-        const double cb = (CLIP && !(qj > 0.0)) ? 0.0 : -6.0 * c1 * (qj * qj);
-        const double ca = ci * (qi * qi);
-        const double tb = (Bj * cb + Bi * ca) / 2.0;                          // nsc:651, the common factor taken out (see pass 1)
-        const double bx = tb * dx, by = tb * dy, bz = tb * dz;
-        a.x += bx; a.y += by; a.z += bz;
-        a.h += bx * (qv.a - rv.a) + by * (qv.b - rv.b) + bz * (qv.c - rv.c);   // nsc:653
+        visc_term<SqrtMid>(a, q0b[u], qvb[u], qvb[u].d, c1b[u], r0, rv, hi2, ci, Bi, CLIP);
     }
 }
 
-__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_visc_kernel(int n, int npad, int k, int nblk, int clip,
+__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_visc_kernel(int n, int npad, int k, int nblk,
                                                            const int* __restrict__ nbr,
                                                            const u16* __restrict__ slot16,
                                                            const int* __restrict__ uniq,
-                                                           const int* __restrict__ qorder,
+                                                           const int* __restrict__ qorder, int clip,
                                                            const int* __restrict__ omap, int n_active,
                                                            const RecB* __restrict__ recb,
                                                            const RecBC* __restrict__ bc,
@@ -605,33 +552,15 @@ __device__ __forceinline__ void visc_pw_batch(ViscAcc& a, double& maxrel, const 
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
         if (!FAST && sl[u] == SLOT_NONE) continue;
-        const Q4 q0 = q0b[u], qv = qvb[u];
-        const double dx = q0.a - r0.a, dy = q0.b - r0.b, dz = q0.c - r0.c;
-        const double dvx = qv.a - rv.a, dvy = qv.b - rv.b, dvz = qv.c - rv.c;
-        const double rr = dx * dx + dy * dy + dz * dz;
-        const double dot = dvx * dx + dvy * dy + dvz * dz;
-        double w = dot / sqrt_mid(rr + 0.01 * q0.d);                    // nsc:643
-        w = (w > 0.0) ? 0.0 : w;                                        // nsc:644
-        const double rho_ab = (rhob[u] + rho_i) / 2.0;                  // nsc:646
-        const double c_ab = 0.5 * (qv.d + cs_i);                        // nsc:647
-        const double pi = -0.5 * (c_ab * 2.0 - 3.0 * w) * w / rho_ab;   // nsc:649, per pair
-        maxrel = fmax(maxrel, dvx * dvx + dvy * dvy + dvz * dvz);       // nsc:780
-        const double r = sqrt_mid(rr);
-        const double r2 = r * r;
-        const double qj = q0.d - r2, qi = hi2 - r2;
-        const double cb = (CLIP && !(qj > 0.0)) ? 0.0 : -6.0 * mcb[u] * (qj * qj);
-        const double ca = ci * (qi * qi);
-        const double tb = pi * (cb + ca) / 2.0;
-        a.x += tb * dx; a.y += tb * dy; a.z += tb * dz;
-        a.h += tb * dot;                                                // nsc:653
+        maxrel = fmax(maxrel, visc_pw_term<SqrtMid>(a, q0b[u], qvb[u], rhob[u], mcb[u], r0, rv, rho_i, cs_i, hi2, ci, CLIP));
     }
 }
 
-__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_visc_pw_kernel(int n, int npad, int k, int nblk, int clip,
+__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_visc_pw_kernel(int n, int npad, int k, int nblk,
                                                               const int* __restrict__ nbr,
                                                               const u16* __restrict__ slot16,
                                                               const int* __restrict__ uniq,
-                                                              const int* __restrict__ qorder,
+                                                              const int* __restrict__ qorder, int clip,
                                                               const int* __restrict__ omap, int n_active,
                                                               const RecB* __restrict__ recb,
                                                               const double* __restrict__ rho_s,
@@ -640,11 +569,10 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_visc_pw_kernel(int n, 
                                                               const double* __restrict__ m, double* va, double* vh,
                                                               u64* ct_bits, BlobSel sel) {
     extern __shared__ double2 img[];                       // 4 * BLOB_S chunks, BLOB_S rho_j, slot tile
-    __shared__ u64 sm[PASS_T / 64];
     double* lrho = reinterpret_cast<double*>(img + 4 * BLOB_S);
     u16* tile = reinterpret_cast<u16*>(lrho + BLOB_S);
     const int t = threadIdx.x / LPP, half = threadIdx.x & (LPP - 1);     // half: which partial sum
-    u64 my_ct = 0x7FF0000000000000ull;       // +inf: "no crossing time"
+    u64 my_ct = SPHX_CT_NONE;
     const int nsel = blob_sel_count(sel, nblk);
     for (int bi = blockIdx.x; bi < nsel; bi += gridDim.x) {
         const int b = blob_sel_at(sel, bi, nsel);
@@ -692,26 +620,99 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_visc_pw_kernel(int n, 
                 va[3 * (size_t)o + 0] = -ax; va[3 * (size_t)o + 1] = -ay; va[3 * (size_t)o + 2] = -az;
                 vh[o] = heat * mi / 2.0;                                        // nsc:654
                 if (sf.mg > 0.0) {                                              // gas only     nsc:782
-                    double ct = h_i / sqrt(maxrel);
-                    if (ct != ct) ct = 0.0;                                     // nan_to_num
-                    if (ct > DBL_MAX) ct = DBL_MAX;
-                    if (ct > 0.0) { const u64 cb = (u64)__double_as_longlong(ct); my_ct = cb < my_ct ? cb : my_ct; }
+                    const u64 cb = ct_vote_bits(h_i, maxrel);
+                    my_ct = cb < my_ct ? cb : my_ct;
                 }
             }
         }
         __syncthreads();
     }
+    block_min_vote<PASS_T>(my_ct, ct_bits);
+}
+
+// ---- sweeps (2), (3) of the species pass (blob_species_kernel) and its epilogue -------------------------------------
+// w: the weights Nw_j W_ij of this lane's list positions, in registers (every index a compile-time constant).  The image
+// is refilled with the lower, then the upper 64 bytes of the distinct neighbours' composition rows; the lane accumulates
+// weight x row, the group's totals are F[s, i]; then Z_i (drv:663) and the AGB yields at (Z_i, m_i).  Every thread of the
+// workgroup calls (barriers inside); the caller synchronises before the image is written again.
+template <int SPEC_MAXM>
+__device__ __forceinline__ void species_sweeps(const double (&w)[SPEC_MAXM], double2* img, const u16* tile,
+                                               const int* __restrict__ uq, const int* __restrict__ nbr, int n, int npad,
+                                               int nm, int p, int i, int t, int half, bool live, int S,
+                                               const double* __restrict__ fun, const int* __restrict__ row_of,
+                                               const double* __restrict__ m, const AgbTable& agb, int agb_on, double* F,
+                                               double* Zout, double* agb_out) {
+    double tot[16];
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 q = __shfl_xor(my_ct, o, 64);
-        my_ct = q < my_ct ? q : my_ct;
+    for (int hh = 0; hh < 2; ++hh) {
+        __syncthreads();                                   // everybody is done with the previous image
+        // this half of the distinct neighbours' composition rows into the image
+        {
+            int ju[NSTAGE];
+#pragma unroll
+            for (int r = 0; r < NSTAGE; ++r) {
+                const int s = threadIdx.x + r * PASS_T;
+                ju[r] = (s < BLOB_S) ? uq[s] : -1;
+            }
+            double2 c[NSTAGE][4];
+#pragma unroll
+            for (int r = 0; r < NSTAGE; ++r) {
+                const int jr = ju[r] < 0 ? 0 : ju[r];
+                const double2* g = reinterpret_cast<const double2*>(fun + (size_t)(row_of ? row_of[jr] : jr) * 16) + 4 * hh;
+                c[r][0] = g[0]; c[r][1] = g[1]; c[r][2] = g[2]; c[r][3] = g[3];
+            }
+#pragma unroll
+            for (int r = 0; r < NSTAGE; ++r) {
+                const int s = threadIdx.x + r * PASS_T;
+                if (ju[r] >= 0) {
+                    img[0 * BLOB_S + s] = c[r][0]; img[1 * BLOB_S + s] = c[r][1];
+                    img[2 * BLOB_S + s] = c[r][2]; img[3 * BLOB_S + s] = c[r][3];
+                }
+            }
+        }
+        __syncthreads();
+        double acc[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[q] = 0.0;
+#pragma unroll
+        for (int mm = 0; mm < SPEC_MAXM; ++mm) {
+            if (mm < nm) {
+                const unsigned sl = tile[(LPP * mm + half) * BLOB_P + t];
+                if (sl != SLOT_NONE && live) {
+                    Q4 f0, f1;
+                    if (sl < SLOT_OVER) { f0 = lload4(img, (int)sl, 0); f1 = lload4(img, (int)sl, 1); }
+                    else {
+                        const int jo = nbr[(size_t)(LPP * mm + half) * npad + p];
+                        const double* q = fun + (size_t)(row_of ? row_of[jo] : jo) * 16 + 8 * hh;
+                        f0 = gload4(q); f1 = gload4(q + 4);
+                    }
+                    const double wm = w[mm];
+                    acc[0] += wm * f0.a; acc[1] += wm * f0.b; acc[2] += wm * f0.c; acc[3] += wm * f0.d;
+                    acc[4] += wm * f1.a; acc[5] += wm * f1.b; acc[6] += wm * f1.c; acc[7] += wm * f1.d;
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) tot[8 * hh + q] = group_total(acc[q]);
     }
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = my_ct;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 r = sm[0];
-        for (int w = 1; w < PASS_T / 64; ++w) r = sm[w] < r ? sm[w] : r;
-        if (r != 0x7FF0000000000000ull) atomicMin(ct_bits, r);
+    if (live && !half) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if (q < S) F[(size_t)q * n + i] = tot[q];
+    }
+    if (live && agb_on) {
+        // every lane of the group holds the totals: the metallicity in all four, the splines dealt over them
+        const double Z = species_metallicity(agb, tot, S);
+        if (!half) Zout[i] = Z;
+        const double Mi = m[i];
+        double* row = agb_out + (size_t)i * S;
+        for (int q = half; q < S; q += LPP)
+            if (!((agb.covered >> q) & 1u)) row[q] = 0.0;  // species no spline writes
+        for (int o = half; o < agb.nspl; o += LPP) {
+            double val;
+            const int target = agb_one_spline(agb, o, Mi, Z, val);
+            if (target >= 0) row[target] = val;
+        }
     }
 }
 
@@ -721,9 +722,9 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_visc_pw_kernel(int n, 
 // set of kernel evaluations fewer per blob (with-species step 1.65 -> see DESIGN 6.1).  Same expressions in the same
 // order as the two kernels run one after the other: bit-identical outputs.
 template <int SPEC_MAXM>
-__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_species_kernel(int n, int npad, int k, int nblk, int clip,
+__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_species_kernel(int n, int npad, int k, int nblk,
         const int* __restrict__ nbr, const u16* __restrict__ slot16, const int* __restrict__ uniq,
-        const int* __restrict__ qorder, const RecA* __restrict__ rec, double* rho_s, double* rho, double* rhod,
+        const int* __restrict__ qorder, int clip, const RecA* __restrict__ rec, double* rho_s, double* rho, double* rhod,
         double* nden, double* G, double* ha,
         int S, const double* __restrict__ fun, const int* __restrict__ row_of, const double* __restrict__ m, AgbTable agb,
         int agb_on, double* F, double* Zout, double* agb_out) {
@@ -761,10 +762,10 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_species_kernel
                     const size_t col0 = (size_t)(LPP * m0 + half) * npad + p;
                     const bool fast = all_staged(cur);
                     double wo[NB];
-                    if (fast && !clip) density_batch<true, false, true>(a, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai, wo);
-                    else if (fast) density_batch<true, true, true>(a, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai, wo);
-                    else if (!clip) density_batch<false, false, true>(a, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai, wo);
-                    else density_batch<false, true, true>(a, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai, wo);
+                    if (fast && !clip) density_batch<true, false>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
+                    else if (fast) density_batch<true, true>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
+                    else if (!clip) density_batch<false, false>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
+                    else density_batch<false, true>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
 #pragma unroll
                     for (int u = 0; u < NB; ++u) if (m0 + u < SPEC_MAXM) w[m0 + u] = wo[u];
                 }
@@ -780,113 +781,12 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_species_kernel
                 ha[3 * (size_t)i + 2] = -gz / s_rho;
             }
         }
-        // ---- the composition sweeps of blob_species_kernel, on the weights in hand
-        double tot[16];
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            __syncthreads();                                   // everybody is done with the previous image
-            {
-                int ju[NSTAGE];
-#pragma unroll
-                for (int r = 0; r < NSTAGE; ++r) {
-                    const int s = threadIdx.x + r * PASS_T;
-                    ju[r] = (s < BLOB_S) ? uq[s] : -1;
-                }
-                double2 c[NSTAGE][4];
-#pragma unroll
-                for (int r = 0; r < NSTAGE; ++r) {
-                    const int jr = ju[r] < 0 ? 0 : ju[r];
-                    const double2* g = reinterpret_cast<const double2*>(fun + (size_t)(row_of ? row_of[jr] : jr) * 16) + 4 * hh;
-                    c[r][0] = g[0]; c[r][1] = g[1]; c[r][2] = g[2]; c[r][3] = g[3];
-                }
-#pragma unroll
-                for (int r = 0; r < NSTAGE; ++r) {
-                    const int s = threadIdx.x + r * PASS_T;
-                    if (ju[r] >= 0) {
-                        img[0 * BLOB_S + s] = c[r][0]; img[1 * BLOB_S + s] = c[r][1];
-                        img[2 * BLOB_S + s] = c[r][2]; img[3 * BLOB_S + s] = c[r][3];
-                    }
-                }
-            }
-            __syncthreads();
-            double acc[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc[q] = 0.0;
-#pragma unroll
-            for (int mm = 0; mm < SPEC_MAXM; ++mm) {
-                if (mm < nm) {
-                    const unsigned sl = tile[(LPP * mm + half) * BLOB_P + t];
-                    if (sl != SLOT_NONE && live) {
-                        Q4 f0, f1;
-                        if (sl < SLOT_OVER) { f0 = lload4(img, (int)sl, 0); f1 = lload4(img, (int)sl, 1); }
-                        else {
-                            const int jo = nbr[(size_t)(LPP * mm + half) * npad + p];
-                            const double* q = fun + (size_t)(row_of ? row_of[jo] : jo) * 16 + 8 * hh;
-                            f0 = gload4(q); f1 = gload4(q + 4);
-                        }
-                        const double wm = w[mm];
-                        acc[0] += wm * f0.a; acc[1] += wm * f0.b; acc[2] += wm * f0.c; acc[3] += wm * f0.d;
-                        acc[4] += wm * f1.a; acc[5] += wm * f1.b; acc[6] += wm * f1.c; acc[7] += wm * f1.d;
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) tot[8 * hh + q] = group_total(acc[q]);
-        }
-        if (live && !half) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                if (q < S) F[(size_t)q * n + i] = tot[q];
-        }
-        if (live && agb_on) {
-            double heavy = 0.0, all = 0.0;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                if (q < S) {
-                    const double ww = tot[q] * agb.mu[q];
-                    all += ww;
-                    if (q >= 6) heavy += ww;
-                }
-            }
-            const double Z = heavy / all;                      // drv:663
-            if (!half) Zout[i] = Z;
-            const double Mi = m[i];
-            double* row = agb_out + (size_t)i * S;
-            for (int q = half; q < S; q += LPP)
-                if (!((agb.covered >> q) & 1u)) row[q] = 0.0;
-            for (int o = half; o < agb.nspl; o += LPP) {
-                double val;
-                const int target = agb_one_spline(agb, o, Mi, Z, val);
-                if (target >= 0) row[target] = val;
-            }
-        }
+        // ---- the composition sweeps of the species pass, on the weights in hand
+        species_sweeps(w, img, tile, uq, nbr, n, npad, nm, p, i, t, half, live, S, fun, row_of, m, agb, agb_on, F, Zout, agb_out);
         __syncthreads();                                       // the image is rewritten by the next blob
     }
 }
 
-int sphx_blob_density_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted,
-                              double* F, double* Z, double* agb, int agb_on) {
-    const int64_t npad = sphx_pad64(n);
-    const int nblk = (int)((npad + BLOB_P - 1) / BLOB_P);
-    static bool attr = false;
-    if (!attr) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_density_species_kernel<10>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(64, SPHX_MAX_K)));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_density_species_kernel<16>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(64, SPHX_MAX_K)));
-        attr = true;
-    }
-#define DS_ARGS (int)n, (int)npad, k, nblk, ctx->clip_grad, ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(), ctx->qorder, \
-                ctx->rec1.as<RecA>(), ctx->rho_s.as<double>(), ctx->rho.as<double>(), ctx->rhod.as<double>(), ctx->nden.as<double>(), \
-                ctx->lean_outputs ? nullptr : ctx->G.as<double>(), ctx->ha.as<double>(), S, fun, row_of, m_sorted, ctx->agb, agb_on, F, Z, agb
-    if (KPAD(k) / LPP <= 10)
-        hipLaunchKernelGGL(blob_density_species_kernel<10>, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(64, k), ctx->stream, DS_ARGS);
-    else
-        hipLaunchKernelGGL(blob_density_species_kernel<16>, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(64, k), ctx->stream, DS_ARGS);
-#undef DS_ARGS
-    HIPCHK(hipGetLastError());
-    return SPHX_OK;
-}
 
 // ---- species pass (nsc:624-627) out of LDS, + metallicity and AGB yields ---------------------------
 // F[s,i] = sum_k Nw_j W_ij f_un[j,s] needs, per neighbour, the 64-B record (for W) AND the 128-B composition row: 184 KB
@@ -898,11 +798,11 @@ int sphx_blob_density_species(sphx_ctx* ctx, int64_t n, int k, int S, const doub
 // Sums: the lane's positions k = q mod 4 in ascending k, then (p0 + p1) + (p2 + p3) as in the other LDS passes.
 // SPEC_MAXM: list positions per lane the registers are sized for (K <= 40: 10; else 16)
 template <int SPEC_MAXM>
-__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_species_kernel(int n, int npad, int k, int nblk, int S,
+__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_species_kernel(int n, int npad, int k, int nblk,
                                                               const int* __restrict__ nbr,
                                                               const u16* __restrict__ slot16,
                                                               const int* __restrict__ uniq,
-                                                              const int* __restrict__ qorder,
+                                                              const int* __restrict__ qorder, int S,
                                                               const RecA* __restrict__ rec,
                                                               const double* __restrict__ fun,       // rows of 16 doubles
                                                               const int* __restrict__ row_of,       // (nullable) row of particle j
@@ -942,127 +842,17 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_species_kernel(int n, 
                             const double* q = reinterpret_cast<const double*>(&rec[nbr[(size_t)(LPP * mm + half) * npad + p]]);
                             q0 = gload4(q); q1 = gload4(q + 4);
                         }
-                        const double dx = q0.a - xr, dy = q0.b - yr, dz = q0.c - zr;
-                        const double r = sqrt_mid(dx * dx + dy * dy + dz * dz);
-                        const double qj = q0.d - r * r;
-                        double W = q1.a * (qj * qj * qj);
-                        W = (W < 0.0) ? 0.0 : W;
-                        w[mm] = q1.d * W;
+                        w[mm] = species_weight<SqrtMid>(q0, q1.a, q1.d, xr, yr, zr);
                     }
                 }
             }
         }
-        double tot[16];
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            __syncthreads();                                   // everybody is done with the previous image
-            // ---- (2), (3): this half of the distinct neighbours' composition rows into the image
-            {
-                int ju[NSTAGE];
-#pragma unroll
-                for (int r = 0; r < NSTAGE; ++r) {
-                    const int s = threadIdx.x + r * PASS_T;
-                    ju[r] = (s < BLOB_S) ? uq[s] : -1;
-                }
-                double2 c[NSTAGE][4];
-#pragma unroll
-                for (int r = 0; r < NSTAGE; ++r) {
-                    const int jr = ju[r] < 0 ? 0 : ju[r];
-                    const double2* g = reinterpret_cast<const double2*>(fun + (size_t)(row_of ? row_of[jr] : jr) * 16) + 4 * hh;
-                    c[r][0] = g[0]; c[r][1] = g[1]; c[r][2] = g[2]; c[r][3] = g[3];
-                }
-#pragma unroll
-                for (int r = 0; r < NSTAGE; ++r) {
-                    const int s = threadIdx.x + r * PASS_T;
-                    if (ju[r] >= 0) {
-                        img[0 * BLOB_S + s] = c[r][0]; img[1 * BLOB_S + s] = c[r][1];
-                        img[2 * BLOB_S + s] = c[r][2]; img[3 * BLOB_S + s] = c[r][3];
-                    }
-                }
-            }
-            __syncthreads();
-            double acc[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc[q] = 0.0;
-#pragma unroll
-            for (int mm = 0; mm < SPEC_MAXM; ++mm) {
-                if (mm < nm) {
-                    const unsigned sl = tile[(LPP * mm + half) * BLOB_P + t];
-                    if (sl != SLOT_NONE && live) {
-                        Q4 f0, f1;
-                        if (sl < SLOT_OVER) { f0 = lload4(img, (int)sl, 0); f1 = lload4(img, (int)sl, 1); }
-                        else {
-                            const int jo = nbr[(size_t)(LPP * mm + half) * npad + p];
-                            const double* q = fun + (size_t)(row_of ? row_of[jo] : jo) * 16 + 8 * hh;
-                            f0 = gload4(q); f1 = gload4(q + 4);
-                        }
-                        const double wm = w[mm];
-                        acc[0] += wm * f0.a; acc[1] += wm * f0.b; acc[2] += wm * f0.c; acc[3] += wm * f0.d;
-                        acc[4] += wm * f1.a; acc[5] += wm * f1.b; acc[6] += wm * f1.c; acc[7] += wm * f1.d;
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) tot[8 * hh + q] = group_total(acc[q]);
-        }
-        if (live && !half) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                if (q < S) F[(size_t)q * n + i] = tot[q];
-        }
-        if (live && agb_on) {
-            // every lane of the group holds the totals: the metallicity in all four, the splines dealt over them
-            double heavy = 0.0, all = 0.0;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                if (q < S) {
-                    const double ww = tot[q] * agb.mu[q];
-                    all += ww;
-                    if (q >= 6) heavy += ww;
-                }
-            }
-            const double Z = heavy / all;                      // drv:663
-            if (!half) Zout[i] = Z;
-            const double Mi = m[i];
-            double* row = agb_out + (size_t)i * S;
-            for (int q = half; q < S; q += LPP)
-                if (!((agb.covered >> q) & 1u)) row[q] = 0.0;  // species no spline writes
-            for (int o = half; o < agb.nspl; o += LPP) {
-                double val;
-                const int target = agb_one_spline(agb, o, Mi, Z, val);
-                if (target >= 0) row[target] = val;
-            }
-        }
+        // ---- (2), (3)
+        species_sweeps(w, img, tile, uq, nbr, n, npad, nm, p, i, t, half, live, S, fun, row_of, m, agb, agb_on, F, Zout, agb_out);
         __syncthreads();                                       // the image is rewritten by the next blob
     }
 }
 
-int sphx_blob_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted, double* F,
-                      double* Z, double* agb, int agb_on) {
-    const int64_t npad = sphx_pad64(n);
-    const int nblk = (int)((npad + BLOB_P - 1) / BLOB_P);
-    static bool attr = false;
-    if (!attr) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_species_kernel<10>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(64, SPHX_MAX_K)));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_species_kernel<16>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(64, SPHX_MAX_K)));
-        attr = true;
-    }
-    if (KPAD(k) / LPP <= 10)
-        hipLaunchKernelGGL(blob_species_kernel<10>, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(64, k), ctx->stream, (int)n,
-                           (int)npad, k, nblk, S, ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(), ctx->qorder,
-                           ctx->rec1.as<RecA>(), fun, row_of, m_sorted, ctx->agb, agb_on, F, Z, agb);
-    else
-        hipLaunchKernelGGL(blob_species_kernel<16>, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(64, k), ctx->stream, (int)n,
-                           (int)npad, k, nblk, S, ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(), ctx->qorder,
-                           ctx->rec1.as<RecA>(), fun, row_of, m_sorted, ctx->agb, agb_on, F, Z, agb);
-    HIPCHK(hipGetLastError());
-    return SPHX_OK;
-}
-
-// ---- launchers (buffers are sized by the callers in sphx_sums.hip) -----------------------------
-// persistent grid: two workgroups per CU (what the LDS image allows), a multiple of the 8 XCDs
 // ---- gas-dust drag out of LDS                 nsc:719-742 (net_impulse; gather form: sphx_sums.hip) ---------------------
 // Only dust neighbours count (a tenth of the references in the two-phase cloud), and every one of them costs the
 // gather form a chain of gathers (type, record, m, grain mass, cross-section) and an atomic with return for its place
@@ -1174,22 +964,11 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_drag_kernel(int n, int
                     const double* qb = reinterpret_cast<const double*>(&recb[j]);
                     q0 = gload4(qb); qv = gload4(qb + 4);
                 }
-                const double dx = q0.a - r0.a, dy = q0.b - r0.b, dz = q0.c - r0.c;
-                const double ds2 = q0.d, ds = sqrt(ds2);
-                const double q = ds2 - (dx * dx + dy * dy + dz * dz);
-                const double ds4 = ds2 * ds2;
-                const double wf = m[j] * 315.0 * (q * q * q) / (201.06192982974676 * (ds4 * ds4 * ds));   // nsc:678-681
-                double fx = 0.0, fy = 0.0, fz = 0.0;
-                if (wf > 0.0) {
-                    const double dvx = qv.a - rv.a, dvy = qv.b - rv.b, dvz = qv.c - rv.c;
-                    const double coef = wf / mgm[j] * mcs[j] * sqrt(dvx * dvx + dvy * dvy + dvz * dvz);
-                    fx = coef * dvx; fy = coef * dvy; fz = coef * dvz;
-                    ox += fx; oy += fy; oz += fz;
-                }
+                const Vec3 f = drag_term(ox, oy, oz, q0, qv, r0, rv, j, m, mgm, mcs);
                 if (j != i) {                                              // nsc:741
                     const int slot = (sl < SLOT_OVER) ? baseL[sl] + atomicAdd(&cntL[sl], 1)
                                                       : sc.start[j] + atomicSub(&sc.cnt[j], 1) - 1;
-                    sphx_drag_put(sc, slot, ((u64)(unsigned)id[i] << 8) | (u64)kk, -fx, -fy, -fz);
+                    sphx_drag_put(sc, slot, ((u64)(unsigned)id[i] << 8) | (u64)kk, -f.x, -f.y, -f.z);
                 }
             }
         }
@@ -1199,35 +978,14 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_drag_kernel(int n, int
     }
 }
 
-// counting pass of the scatter plan (true) / the pass itself (false -> fill) on the blob lists
-int sphx_blob_drag(sphx_ctx* ctx, int64_t n, int k, bool count_only, const double* m, const double* ptype, const double* mgm,
-                   const double* mcs, const int* id, double* onto, const DragScatter& sc) {
-    const int64_t npad = sphx_pad64(n);
-    const int nblk = (int)((npad + BLOB_P - 1) / BLOB_P);
-    if (!ctx->drag_attr_set) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_drag_kernel<true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(IMG_BYTES(64, SPHX_MAX_K) + DRAG_XLDS)));
-        ctx->drag_attr_set = true;
-    }
-    if (count_only)
-        hipLaunchKernelGGL(blob_drag_kernel<false>, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T),
-                           (size_t)KPAD(k) * BLOB_P * sizeof(u16) + DRAG_XLDS, ctx->stream, (int)n, (int)npad, k, nblk,
-                           ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(), ctx->qorder, nullptr, m, ptype, mgm, mcs,
-                           id, onto, sc);
-    else
-        hipLaunchKernelGGL(blob_drag_kernel<true>, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(64, k) + DRAG_XLDS,
-                           ctx->stream, (int)n, (int)npad, k, nblk, ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(),
-                           ctx->qorder, ctx->recv.as<RecB>(), m, ptype, mgm, mcs, id, onto, sc);
-    HIPCHK(hipGetLastError());
-    return SPHX_OK;
-}
-
+// ---- launchers (buffers are sized by the callers in sphx_sums.hip) -----------------------------
 BlobSel sphx_blob_sel(sphx_ctx* ctx, int part) {
     if (!ctx->blob_split_valid) return BlobSel{nullptr, nullptr, 0};
     const int* list = ctx->blob_split.as<int>();
     return BlobSel{list, list + (size_t)ctx->blob_split_nblk, part == 0 ? 3 : part};
 }
 
+// persistent grid: two workgroups per CU (what the LDS image allows), a multiple of the 8 XCDs
 int sphx_blob_grid(sphx_ctx* ctx, int nblk) {
     if (ctx->blob_grid <= 0) {
         int cus = 256;
@@ -1237,69 +995,76 @@ int sphx_blob_grid(sphx_ctx* ctx, int nblk) {
     return nblk < ctx->blob_grid ? nblk : ctx->blob_grid;
 }
 
-static int blob_attr_once(sphx_ctx* ctx) {
-    if (ctx->blob_attr_set) return SPHX_OK;
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_density_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(64, SPHX_MAX_K)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_pi_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(72, SPHX_MAX_K)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_visc_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(72, SPHX_MAX_K)));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_visc_pw_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(72, SPHX_MAX_K)));
-    ctx->blob_attr_set = true;
+int sphx_lds_opt_in(sphx_ctx* ctx, const void* kernel, size_t bytes) {
+    for (int q = 0; q < ctx->n_lds_raised; ++q)
+        if (ctx->lds_raised[q] == kernel) return SPHX_OK;
+    if (ctx->n_lds_raised == SPHX_LDS_KERNELS)
+        return sphx_set_err(ctx, SPHX_E_HIP, "sphx_lds_opt_in: more than %d kernels", SPHX_LDS_KERNELS);
+    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    ctx->lds_raised[ctx->n_lds_raised++] = kernel;
     return SPHX_OK;
 }
 
-int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k) {
-    SPHX_TRY(blob_attr_once(ctx));
+// One launch on the persistent grid.  Every LDS kernel of this file begins with (n, npad, k, nblk, nbr, slot16, uniq,
+// qorder); `rest` are the arguments behind them.  Dynamic LDS: per_slot bytes of image per slot (0: no image) and the
+// slot tile, + extra.
+template <class Kern, class... Rest>
+static int blob_launch(sphx_ctx* ctx, Kern kern, int per_slot, size_t extra, int64_t n, int k, Rest... rest) {
     const int64_t npad = sphx_pad64(n);
     const int nblk = (int)((npad + BLOB_P - 1) / BLOB_P);
-    hipLaunchKernelGGL(blob_density_kernel, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(64, k), ctx->stream, (int)n, (int)npad, k, nblk, ctx->clip_grad,
-                       ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(),
-                       ctx->qorder, ctx->map_perm, ctx->map_perm ? ctx->map_nactive : (int)n, ctx->rec1.as<RecA>(),
-                       ctx->rho_s.as<double>(), ctx->rho.as<double>(),
-                       ctx->rhod.as<double>(), ctx->nden.as<double>(), ctx->lean_outputs ? nullptr : ctx->G.as<double>(), ctx->ha.as<double>(),
-                       sphx_blob_sel(ctx, ctx->pass_part));
+    SPHX_TRY(sphx_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), IMG_BYTES(per_slot, SPHX_MAX_K) + extra));
+    hipLaunchKernelGGL(kern, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(per_slot, k) + extra, ctx->stream, (int)n,
+                       (int)npad, k, nblk, ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(), ctx->qorder, rest...);
     HIPCHK(hipGetLastError());
     return SPHX_OK;
+}
+// callers' particles that are computed (device API: the owned ones; ghosts, o >= n_active, are candidates only)
+static int blob_n_active(const sphx_ctx* ctx, int64_t n) { return ctx->map_perm ? ctx->map_nactive : (int)n; }
+
+int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k) {
+    return blob_launch(ctx, blob_density_kernel, 64, 0, n, k, ctx->clip_grad, ctx->map_perm, blob_n_active(ctx, n),
+                       ctx->rec1.as<RecA>(), ctx->rho_s.as<double>(), ctx->rho.as<double>(), ctx->rhod.as<double>(),
+                       ctx->nden.as<double>(), ctx->lean_outputs ? nullptr : ctx->G.as<double>(), ctx->ha.as<double>(),
+                       sphx_blob_sel(ctx, ctx->pass_part));
 }
 
 int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits) {
-    SPHX_TRY(blob_attr_once(ctx));
-    const int64_t npad = sphx_pad64(n);
-    const int nblk = (int)((npad + BLOB_P - 1) / BLOB_P);
-    hipLaunchKernelGGL(blob_pi_kernel, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(72, k), ctx->stream, (int)n, (int)npad, k, nblk,
-                       ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(),
-                       ctx->qorder, ctx->map_perm, ctx->map_perm ? ctx->map_nactive : (int)n, ctx->recv.as<RecB>(),
+    return blob_launch(ctx, blob_pi_kernel, 72, 0, n, k, ctx->map_perm, blob_n_active(ctx, n), ctx->recv.as<RecB>(),
                        ctx->rho_s.as<double>(), ctx->self_s.as<RecSelf>(), ctx->bc_s.as<RecBC>(), ctx->Pi.as<double>(),
                        ctx->map_perm ? ctx->Bw.as<double>() : nullptr, ct_bits, sphx_blob_sel(ctx, ctx->pass_part));
-    HIPCHK(hipGetLastError());
-    return SPHX_OK;
 }
 
 int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m) {
-    SPHX_TRY(blob_attr_once(ctx));
-    const int64_t npad = sphx_pad64(n);
-    const int nblk = (int)((npad + BLOB_P - 1) / BLOB_P);
-    hipLaunchKernelGGL(blob_visc_kernel, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(72, k), ctx->stream, (int)n, (int)npad, k, nblk, ctx->clip_grad,
-                       ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(),
-                       ctx->qorder, ctx->map_perm, ctx->map_perm ? ctx->map_nactive : (int)n, ctx->recv.as<RecB>(),
-                       ctx->bc_s.as<RecBC>(), m, ctx->va.as<double>(),
-                       ctx->vh.as<double>(), sphx_blob_sel(ctx, ctx->pass_part));
-    HIPCHK(hipGetLastError());
-    return SPHX_OK;
+    return blob_launch(ctx, blob_visc_kernel, 72, 0, n, k, ctx->clip_grad, ctx->map_perm, blob_n_active(ctx, n),
+                       ctx->recv.as<RecB>(), ctx->bc_s.as<RecBC>(), m, ctx->va.as<double>(), ctx->vh.as<double>(),
+                       sphx_blob_sel(ctx, ctx->pass_part));
 }
 
 int sphx_blob_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m, u64* ct_bits) {
-    SPHX_TRY(blob_attr_once(ctx));
-    const int64_t npad = sphx_pad64(n);
-    const int nblk = (int)((npad + BLOB_P - 1) / BLOB_P);
-    hipLaunchKernelGGL(blob_visc_pw_kernel, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(72, k), ctx->stream, (int)n, (int)npad, k, nblk, ctx->clip_grad,
-                       ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(),
-                       ctx->qorder, ctx->map_perm, ctx->map_perm ? ctx->map_nactive : (int)n, ctx->recv.as<RecB>(),
-                       ctx->rho_s.as<double>(), ctx->bc_s.as<RecBC>(), ctx->self_s.as<RecSelf>(), m, ctx->va.as<double>(),
-                       ctx->vh.as<double>(), ct_bits, sphx_blob_sel(ctx, ctx->pass_part));
-    HIPCHK(hipGetLastError());
-    return SPHX_OK;
+    return blob_launch(ctx, blob_visc_pw_kernel, 72, 0, n, k, ctx->clip_grad, ctx->map_perm, blob_n_active(ctx, n),
+                       ctx->recv.as<RecB>(), ctx->rho_s.as<double>(), ctx->bc_s.as<RecBC>(), ctx->self_s.as<RecSelf>(), m,
+                       ctx->va.as<double>(), ctx->vh.as<double>(), ct_bits, sphx_blob_sel(ctx, ctx->pass_part));
+}
+
+// (the weights' registers are sized for K <= 40, else for SPHX_MAX_K: SPEC_MAXM)
+int sphx_blob_density_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted,
+                              double* F, double* Z, double* agb, int agb_on) {
+    const auto kern = (KPAD(k) / LPP <= 10) ? blob_density_species_kernel<10> : blob_density_species_kernel<16>;
+    return blob_launch(ctx, kern, 64, 0, n, k, ctx->clip_grad, ctx->rec1.as<RecA>(), ctx->rho_s.as<double>(), ctx->rho.as<double>(),
+                       ctx->rhod.as<double>(), ctx->nden.as<double>(), ctx->lean_outputs ? nullptr : ctx->G.as<double>(),
+                       ctx->ha.as<double>(), S, fun, row_of, m_sorted, ctx->agb, agb_on, F, Z, agb);
+}
+
+int sphx_blob_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted, double* F,
+                      double* Z, double* agb, int agb_on) {
+    const auto kern = (KPAD(k) / LPP <= 10) ? blob_species_kernel<10> : blob_species_kernel<16>;
+    return blob_launch(ctx, kern, 64, 0, n, k, S, ctx->rec1.as<RecA>(), fun, row_of, m_sorted, ctx->agb, agb_on, F, Z, agb);
+}
+
+// counting pass of the scatter plan (true) / the pass itself (false -> fill) on the blob lists
+int sphx_blob_drag(sphx_ctx* ctx, int64_t n, int k, bool count_only, const double* m, const double* ptype, const double* mgm,
+                   const double* mcs, const int* id, double* onto, const DragScatter& sc) {
+    if (count_only)
+        return blob_launch(ctx, blob_drag_kernel<false>, 0, DRAG_XLDS, n, k, nullptr, m, ptype, mgm, mcs, id, onto, sc);
+    return blob_launch(ctx, blob_drag_kernel<true>, 64, DRAG_XLDS, n, k, ctx->recv.as<RecB>(), m, ptype, mgm, mcs, id, onto, sc);
 }

@@ -174,12 +174,6 @@ struct FusedCountArgs {
     int* zero_int;                          // the search's fail-list counter, zeroed here instead of by a launch of its own (nullable)
     int* rank;                              // (nullable) the particle's arrival number in its cell: cell_scatter then needs no atomic
 };
-__device__ __forceinline__ double nan_to_num_g(double v) {
-    if (v != v) return 0.0;
-    if (v > DBL_MAX) return DBL_MAX;
-    if (v < -DBL_MAX) return -DBL_MAX;
-    return v;
-}
 __global__ __launch_bounds__(RED_BLOCK) void grid_count_fused(FusedCountArgs a) {
     __shared__ double sm[RED_BLOCK / 64][BB_W];
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -196,7 +190,7 @@ __global__ __launch_bounds__(RED_BLOCK) void grid_count_fused(FusedCountArgs a) 
                 double q = v[c];
                 q = (q > a.lim) ? a.lim : q;
                 q = (q < -a.lim) ? -a.lim : q;
-                v[c] = nan_to_num_g(q);
+                v[c] = sphx_nan_to_num(q);
             }
             // (written back only where the guard changed something - bit patterns compared, NaN included: in a sane state
             //  that is nowhere, and 48 MB of stores per step at 1e6 particles stay undone)
@@ -204,7 +198,7 @@ __global__ __launch_bounds__(RED_BLOCK) void grid_count_fused(FusedCountArgs a) 
             if (__double_as_longlong(v[1]) != __double_as_longlong(o1)) a.y[i] = v[1];
             if (__double_as_longlong(v[2]) != __double_as_longlong(o2)) a.z[i] = v[2];
             const double w0 = a.vx[i], w1 = a.vy[i], w2 = a.vz[i];
-            const double u0 = nan_to_num_g(w0), u1 = nan_to_num_g(w1), u2 = nan_to_num_g(w2);
+            const double u0 = sphx_nan_to_num(w0), u1 = sphx_nan_to_num(w1), u2 = sphx_nan_to_num(w2);
             if (__double_as_longlong(u0) != __double_as_longlong(w0)) a.vx[i] = u0;
             if (__double_as_longlong(u1) != __double_as_longlong(w1)) a.vy[i] = u1;
             if (__double_as_longlong(u2) != __double_as_longlong(w2)) a.vz[i] = u2;

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <math.h>
+#include <float.h>
 #include "../../include/sphx.h"
 #include "sphx_agb.h"
 
@@ -134,6 +135,8 @@ struct StateArrays {
     DevBuf mgm, mcs;                             // mean grain mass / cross-section (drag, optional)
 };
 
+#define SPHX_LDS_KERNELS 16           // room in sphx_ctx::lds_raised (the LDS kernels of sphx_blob.hip and sphx_loopforms.hip: 11)
+
 struct sphx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;       // stream every launch goes to (own_stream or the caller's)
@@ -169,7 +172,6 @@ struct sphx_ctx {
     int loop_forms = 0;           // step mode: the loop forms of the reference's time loop (sphx_state_set_loop_forms)
     double loop_d = 0.0;          // their global d (drv:68)
     DevBuf lrec_a, lrec_v;        // loop-form records (sphx_loopforms.hip)
-    bool loop_attr_set = false;
     int clip_grad = 0;            // physics option: neighbour-side gradient clipped beyond h_j (sphx_set_clip_grad)
     int visc_mode = 0;            // hydro_update-mode viscosity of sphx_step and the sphx_dev_* passes (sphx_set_visc_mode)
     bool visc_pw = false;         // the records being built feed the pairwise viscous pass (sphx_prep: RecBC.Bw)
@@ -263,11 +265,13 @@ struct sphx_ctx {
     bool blob_split_on = true, blob_split_valid = false;
     int blob_split_nblk = 0;
     bool loop2_interior_done = false;
-    bool drag_attr_set = false, drag_lds = true;
+    bool drag_lds = true;
     int64_t max_cells = 0;          // SPHX_MAX_CELLS: > 0 lowers the limit on grid cells
     double reach_cap = 0.0;         // sphx_dev_set_reach_cap: head-room of a claimed reach limited to this length (0: not)
     int pass_part = 0;              // which blobs hydro_update's passes and the record build take: 0 all, 1 interior, 2 boundary
-    bool blob_attr_set = false;
+    // the kernels whose dynamic-LDS limit has been raised on this context's device (sphx_blob.hip: sphx_lds_opt_in)
+    const void* lds_raised[SPHX_LDS_KERNELS] = {nullptr};
+    int n_lds_raised = 0;
     int blob_grid = 0;              // persistent workgroups of the LDS passes (0: not yet derived)
     int blob_slots = 1 << 20;       // distinct neighbours staged per workgroup (clamped to the image size)
     int map_nactive = 0;            // device API: callers' particles below this are computed
@@ -362,8 +366,17 @@ __device__ __forceinline__ int xcd_block(int b, int nb) {
 // lanes-per-particle split of the LDS kernels (sphx_blob.hip), so all variants agree bit for bit.
 #ifndef SPHX_SUM_PARTS
 #define SPHX_SUM_PARTS 4
-#define LAG_OFF 1024                 // byte offset of the lag slots in ctx->pinned: slot s at LAG_OFF + 512 s (box), + 256 (h sums)
 #endif
+
+#define LAG_OFF 1024                 // byte offset of the lag slots in ctx->pinned: slot s at LAG_OFF + 512 s (box), + 256 (h sums)
+
+// np.nan_to_num of one value (drv:233-238, 460-463, 490-491; nsc:783)
+__device__ __forceinline__ double sphx_nan_to_num(double v) {
+    if (v != v) return 0.0;
+    if (v > DBL_MAX) return DBL_MAX;
+    if (v < -DBL_MAX) return -DBL_MAX;
+    return v;
+}
 
 // "no gas particle has voted a crossing time yet": the bits of +inf.  Votes are nan_to_num'ed
 // (at most DBL_MAX = 0x7FEF...), so no vote can produce it and atomicMin on the bits keeps any vote.

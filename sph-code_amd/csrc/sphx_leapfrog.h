@@ -8,13 +8,6 @@
 #pragma once
 #include <float.h>
 
-__device__ __forceinline__ double sphx_nan_to_num(double v) {
-    if (v != v) return 0.0;
-    if (v > DBL_MAX) return DBL_MAX;
-    if (v < -DBL_MAX) return -DBL_MAX;
-    return v;
-}
-
 // drv:223-229.  ct = nsc.crossing_time's return value (nsc:783-786).
 __device__ __forceinline__ double sphx_dt_rule(double ct, int first, double dt_0, double max_age) {
     double dt = first ? dt_0 / 10.0 : fmax(dt_0 / 5.0, fmin(dt_0 * 2.0, ct));   // drv:223-226

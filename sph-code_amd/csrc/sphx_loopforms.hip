@@ -3,6 +3,7 @@
 // driver-injected global d, clipped gradients, physical sign.  One thread per particle over
 // the K-major neighbour list; deltas are relative to the particle itself.
 #include "sphx_internal.h"
+#include "sphx_pair.h"             // parts_total, the crossing-time vote and its workgroup minimum
 // NumPy never fuses a multiply into an add: keep every operation separately rounded so that
 // cancellations such as h_j^2 - r^2 at the kernel edge reproduce the reference bit for bit.
 #pragma clang fp contract(off)
@@ -10,12 +11,6 @@
 
 #define PI64 201.06192982974676      /* 64 pi */
 
-__device__ __forceinline__ double nan_to_num_d(double v) {
-    if (v != v) return 0.0;
-    if (v > DBL_MAX) return DBL_MAX;
-    if (v < -DBL_MAX) return -DBL_MAX;
-    return v;
-}
 __device__ __forceinline__ double pow9(double d) {
     double d2 = d * d, d4 = d2 * d2;
     return d4 * d4 * d;
@@ -88,9 +83,9 @@ __global__ __launch_bounds__(256) void loop_del_pressure_kernel(LoopArgs a) {
             const double r2 = dx * dx + dy * dy + dz * dz;
             const double c = grad_coef(r2, a.m[j], a.d, a.m0, d9, a.pt[j]);
             const double f = (a.E[j] + Ei) / a.gam[j];
-            gx += 0.5 * nan_to_num_d(c * dx) * f;
-            gy += 0.5 * nan_to_num_d(c * dy) * f;
-            gz += 0.5 * nan_to_num_d(c * dz) * f;
+            gx += 0.5 * sphx_nan_to_num(c * dx) * f;
+            gy += 0.5 * sphx_nan_to_num(c * dy) * f;
+            gz += 0.5 * sphx_nan_to_num(c * dz) * f;
         }
     }
     a.out3[3 * (size_t)i] = gx; a.out3[3 * (size_t)i + 1] = gy; a.out3[3 * (size_t)i + 2] = gz;
@@ -105,7 +100,7 @@ __global__ __launch_bounds__(256) void loop_av_kernel(LoopArgs a) {
         const double xi = a.pos[3 * (size_t)i], yi = a.pos[3 * (size_t)i + 1], zi = a.pos[3 * (size_t)i + 2];
         const double vxi = a.vel[3 * (size_t)i], vyi = a.vel[3 * (size_t)i + 1], vzi = a.vel[3 * (size_t)i + 2];
         const double d9 = pow9(a.d), mi = a.m[i], rhoi = a.rho[i];
-        const double csi = nan_to_num_d(sqrt(a.gam[i] * a.kB * a.T[i] / (a.mu[i] * a.amu)));
+        const double csi = sphx_nan_to_num(sqrt(a.gam[i] * a.kB * a.T[i] / (a.mu[i] * a.amu)));
         for (int kk = 0; kk < a.k; ++kk) {
             int j = a.nbr[(size_t)kk * a.npad + i];
             if (j < 0 || a.pt[j] != 0.0) continue;            // sums run over gas neighbours only
@@ -116,13 +111,13 @@ __global__ __launch_bounds__(256) void loop_av_kernel(LoopArgs a) {
             const double r2 = dx * dx + dy * dy + dz * dz;
             double w = (dvx * dx + dvy * dy + dvz * dz) / sqrt(r2);
             w = (w > 0.0) ? 0.0 : w;
-            w = nan_to_num_d(w);                              // self pair: 0/0
-            const double csj = nan_to_num_d(sqrt(a.gam[j] * a.kB * a.T[j] / (a.mu[j] * a.amu)));
+            w = sphx_nan_to_num(w);                              // self pair: 0/0
+            const double csj = sphx_nan_to_num(sqrt(a.gam[j] * a.kB * a.T[j] / (a.mu[j] * a.amu)));
             const double vsig = csj + csi - 3.0 * w;
             const double rho_ij = (a.rho[j] + rhoi) / 2.0;
             const double PI = -0.5 * vsig * w / rho_ij;
             const double c = grad_coef(r2, mi, a.d, a.m0, d9, a.pt[j]);     // h(m_i)  nsc:805
-            const double gwx = nan_to_num_d(c * dx), gwy = nan_to_num_d(c * dy), gwz = nan_to_num_d(c * dz);
+            const double gwx = sphx_nan_to_num(c * dx), gwy = sphx_nan_to_num(c * dy), gwz = sphx_nan_to_num(c * dz);
             const double mb = (a.m[j] + mi) / 2.0;
             ax += mb * PI * gwx; ay += mb * PI * gwy; az += mb * PI * gwz;
             heat += 0.5 * mb * PI * (dvx * gwx + dvy * gwy + dvz * gwz);
@@ -134,9 +129,8 @@ __global__ __launch_bounds__(256) void loop_av_kernel(LoopArgs a) {
 
 // nsc:776-786
 __global__ __launch_bounds__(256) void loop_ct_kernel(LoopArgs a) {
-    __shared__ u64 sm[4];
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    u64 mine = 0x7FF0000000000000ull;
+    u64 mine = SPHX_CT_NONE;
     if (i < a.n && a.pt[i] == 0.0) {
         const double vxi = a.vel[3 * (size_t)i], vyi = a.vel[3 * (size_t)i + 1], vzi = a.vel[3 * (size_t)i + 2];
         double mx = 0.0;
@@ -147,21 +141,9 @@ __global__ __launch_bounds__(256) void loop_ct_kernel(LoopArgs a) {
                          dvz = a.vel[3 * (size_t)j + 2] - vzi;
             mx = fmax(mx, dvx * dvx + dvy * dvy + dvz * dvz);
         }
-        double ct = nan_to_num_d(a.h[i] / sqrt(mx));
-        if (ct > 0.0) mine = (u64)__double_as_longlong(ct);
+        mine = ct_vote_bits(a.h[i], mx);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        u64 p = __shfl_xor(mine, o, 64);
-        mine = p < mine ? p : mine;
-    }
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 r = sm[0];
-        for (int w = 1; w < 4; ++w) r = sm[w] < r ? sm[w] : r;
-        if (r != 0x7FF0000000000000ull) atomicMin(a.ct_bits, r);
-    }
+    block_min_vote<256>(mine, a.ct_bits);
 }
 
 // nsc:719-742; the reaction as an ordered scatter (DragScatter, sphx_internal.h): np.add.at's order, the same bits every run
@@ -415,16 +397,11 @@ __global__ __launch_bounds__(256) void loop_prep_kernel(LoopPrepArgs a) {
     a.p1[i] = r;
     RecP2 v;
     v.x = r.x; v.y = r.y; v.z = r.z;
-    const double cs = nan_to_num_d(sqrt(a.gam[i] * a.kB * a.T[i] / (a.mu[i] * a.amu)));     // nsc:792
+    const double cs = sphx_nan_to_num(sqrt(a.gam[i] * a.kB * a.T[i] / (a.mu[i] * a.amu)));     // nsc:792
     v.css = gas ? cs : -(cs + 1.0);
     v.vx = a.vx[i]; v.vy = a.vy[i]; v.vz = a.vz[i];
     v.rho = 0.0;                                                 // pass 1 fills it in
     a.p2[i] = v;
-}
-
-__device__ __forceinline__ double parts_total_l(const double (&a)[SPHX_SUM_PARTS]) {
-    if (SPHX_SUM_PARTS == 4) return (a[0] + a[1]) + (a[2] + a[3]);
-    return a[0] + a[SPHX_SUM_PARTS - 1];
 }
 
 // ---- terms of one neighbour (shared by the gather and the LDS kernels) -------------------------------
@@ -449,9 +426,9 @@ __device__ __forceinline__ void loop1_term(L1Acc& a, const Q4& q0, const Q4& q1,
         double c = q1.b * (q * q) * (gas_j ? 1.0 : 0.0);
         c = (q > 0.0) ? c : 0.0;
         const double f = (q1.d + Ei) / gam_j;
-        a.gx += 0.5 * nan_to_num_d(c * dx) * f;
-        a.gy += 0.5 * nan_to_num_d(c * dy) * f;
-        a.gz += 0.5 * nan_to_num_d(c * dz) * f;
+        a.gx += 0.5 * sphx_nan_to_num(c * dx) * f;
+        a.gy += 0.5 * sphx_nan_to_num(c * dy) * f;
+        a.gz += 0.5 * sphx_nan_to_num(c * dz) * f;
     }
 }
 struct L2Acc { double ax, ay, az, heat; };
@@ -465,14 +442,14 @@ __device__ __forceinline__ double loop2_term(L2Acc& a, const Q4& q0, const Q4& q
     const double r2 = dx * dx + dy * dy + dz * dz;
     double w = (dvx * dx + dvy * dy + dvz * dz) / sqrt_mid(r2);                   // (sqrt's bits on this range: sphx_blob.h)
     w = (w > 0.0) ? 0.0 : w;
-    w = nan_to_num_d(w);                                                          // self pair: 0/0
+    w = sphx_nan_to_num(w);                                                          // self pair: 0/0
     const double vsig = q0.d + s0.d - 3.0 * w;
     const double rho_ij = (qv.d + rho_i) / 2.0;
     const double PI = -0.5 * vsig * w / rho_ij;
     const double q = hq_i - r2;                                                   // h(m_i), nsc:805
     double c = g1_i * (q * q) * 1.0;
     c = (q > 0.0) ? c : 0.0;
-    const double gwx = nan_to_num_d(c * dx), gwy = nan_to_num_d(c * dy), gwz = nan_to_num_d(c * dz);
+    const double gwx = sphx_nan_to_num(c * dx), gwy = sphx_nan_to_num(c * dy), gwz = sphx_nan_to_num(c * dz);
     const double mb = (m_j + m_i) / 2.0;
     a.ax += mb * PI * gwx; a.ay += mb * PI * gwy; a.az += mb * PI * gwz;
     a.heat += 0.5 * mb * PI * (dvx * gwx + dvy * gwy + dvz * gwz);
@@ -518,15 +495,10 @@ __global__ __launch_bounds__(256) void loop_pass1_kernel(int n, int npad, int k,
             loop1_term(acc[u & (SPHX_SUM_PARTS - 1)], q0b[u], q1b[u], gb[u], dm, dh, s0.a, s0.b, s0.c, s1.d, gas_i, d9);
         }
     }
-    double t_rho[SPHX_SUM_PARTS], t_rd[SPHX_SUM_PARTS], t_n[SPHX_SUM_PARTS], t_x[SPHX_SUM_PARTS], t_y[SPHX_SUM_PARTS],
-        t_z[SPHX_SUM_PARTS];
-#pragma unroll
-    for (int q = 0; q < SPHX_SUM_PARTS; ++q) {
-        t_rho[q] = acc[q].rho; t_rd[q] = acc[q].rd; t_n[q] = acc[q].n; t_x[q] = acc[q].gx; t_y[q] = acc[q].gy; t_z[q] = acc[q].gz;
-    }
-    const double s_rho = parts_total_l(t_rho);
-    rho[i] = s_rho; rhod[i] = parts_total_l(t_rd); nden[i] = parts_total_l(t_n);
-    G[3 * (size_t)i] = parts_total_l(t_x); G[3 * (size_t)i + 1] = parts_total_l(t_y); G[3 * (size_t)i + 2] = parts_total_l(t_z);
+    const double s_rho = parts_total(acc, &L1Acc::rho);
+    rho[i] = s_rho; rhod[i] = parts_total(acc, &L1Acc::rd); nden[i] = parts_total(acc, &L1Acc::n);
+    G[3 * (size_t)i] = parts_total(acc, &L1Acc::gx); G[3 * (size_t)i + 1] = parts_total(acc, &L1Acc::gy);
+    G[3 * (size_t)i + 2] = parts_total(acc, &L1Acc::gz);
     p2[i].rho = s_rho;
 }
 
@@ -537,9 +509,8 @@ __global__ __launch_bounds__(256) void loop_pass2_kernel(int n, int npad, int k,
                                                          const double* __restrict__ m, const double* __restrict__ h,
                                                          const int* __restrict__ qorder, double* va, double* vh,
                                                          u64* ct_bits) {
-    __shared__ u64 sm[4];
     const int p = xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
-    u64 mine = 0x7FF0000000000000ull;
+    u64 mine = SPHX_CT_NONE;
     if (p < n) {
         const int i = qorder ? qorder[p] : p;
         const double* sp = reinterpret_cast<const double*>(&p2[i]);
@@ -569,28 +540,14 @@ __global__ __launch_bounds__(256) void loop_pass2_kernel(int n, int npad, int k,
                                              g1_i));
                 }
             }
-            double t_x[SPHX_SUM_PARTS], t_y[SPHX_SUM_PARTS], t_z[SPHX_SUM_PARTS], t_h[SPHX_SUM_PARTS];
-#pragma unroll
-            for (int q = 0; q < SPHX_SUM_PARTS; ++q) { t_x[q] = acc[q].ax; t_y[q] = acc[q].ay; t_z[q] = acc[q].az; t_h[q] = acc[q].heat; }
-            ax = parts_total_l(t_x); ay = parts_total_l(t_y); az = parts_total_l(t_z); heat = parts_total_l(t_h);
-            const double ct = nan_to_num_d(h[i] / sqrt(mx));
-            if (ct > 0.0) mine = (u64)__double_as_longlong(ct);
+            ax = parts_total(acc, &L2Acc::ax); ay = parts_total(acc, &L2Acc::ay); az = parts_total(acc, &L2Acc::az);
+            heat = parts_total(acc, &L2Acc::heat);
+            mine = ct_vote_bits(h[i], mx);
         }
         va[3 * (size_t)i] = ax; va[3 * (size_t)i + 1] = ay; va[3 * (size_t)i + 2] = az;
         vh[i] = heat;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 q = __shfl_xor(mine, o, 64);
-        mine = q < mine ? q : mine;
-    }
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 r = sm[0];
-        for (int w = 1; w < 4; ++w) r = sm[w] < r ? sm[w] : r;
-        if (r != 0x7FF0000000000000ull) atomicMin(ct_bits, r);
-    }
+    block_min_vote<256>(mine, ct_bits);
 }
 
 // ---- LDS form (sphx_blob.h: blob image, LPP lanes per particle, persistent workgroups) ------------------
@@ -678,11 +635,10 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_loop2_kernel(int n, in
                                                                           const double* __restrict__ h, double* va,
                                                                           double* vh, u64* ct_bits, BlobSel sel) {
     extern __shared__ double2 img[];                       // 4 * BLOB_S chunks, m, slot tile
-    __shared__ u64 sm[PASS_T / 64];
     double* lm = reinterpret_cast<double*>(img + 4 * BLOB_S);
     u16* tile = reinterpret_cast<u16*>(lm + BLOB_S);
     const int t = threadIdx.x / LPP, part = threadIdx.x & (LPP - 1);
-    u64 mine = 0x7FF0000000000000ull;
+    u64 mine = SPHX_CT_NONE;
     const int nsel = blob_sel_count(sel, nblk);
     for (int bi = blockIdx.x; bi < nsel; bi += gridDim.x) {
         const int b = blob_sel_at(sel, bi, nsel);
@@ -733,25 +689,14 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_loop2_kernel(int n, in
                 va[3 * (size_t)i] = ax; va[3 * (size_t)i + 1] = ay; va[3 * (size_t)i + 2] = az;
                 vh[i] = heat;
                 if (s0.d >= 0.0) {
-                    const double ct = nan_to_num_d(h_i / sqrt(mx));
-                    if (ct > 0.0) { const u64 cb = (u64)__double_as_longlong(ct); mine = cb < mine ? cb : mine; }
+                    const u64 cb = ct_vote_bits(h_i, mx);
+                    mine = cb < mine ? cb : mine;
                 }
             }
         }
         __syncthreads();
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 q = __shfl_xor(mine, o, 64);
-        mine = q < mine ? q : mine;
-    }
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 r = sm[0];
-        for (int w = 1; w < PASS_T / 64; ++w) r = sm[w] < r ? sm[w] : r;
-        if (r != 0x7FF0000000000000ull) atomicMin(ct_bits, r);
-    }
+    block_min_vote<PASS_T>(mine, ct_bits);
 }
 
 // The three launches of the loop-form sums on a set of SORTED state arrays `st` (the fused loop: the resident
@@ -776,16 +721,6 @@ static int loop_prep_launch(sphx_ctx* ctx, int64_t n, double d, StateArrays& st)
     HIPCHK(hipGetLastError());
     return SPHX_OK;
 }
-static int loop_attr(sphx_ctx* ctx) {
-    if (!ctx->loop_attr_set) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_loop1_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(72, SPHX_MAX_K)));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(blob_loop2_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)IMG_BYTES(72, SPHX_MAX_K)));
-        ctx->loop_attr_set = true;
-    }
-    return SPHX_OK;
-}
 // The LDS form's per-neighbour side value: gamma of a gas particle (del_pressure, nsc:755); for a dust particle its mass,
 // with its size (this step's kNN radius, Weigh2_dust nsc:678) put where the record keeps g1 - a factor that the type
 // mask zeroes for every neighbour that is not gas; -1 for a star.  (The gather form reads type, mass and size directly.)
@@ -805,7 +740,7 @@ static int loop_pass1_launch(sphx_ctx* ctx, int64_t n, int k, double d, StateArr
     const int npad = (int)sphx_pad64(n);
     RecP1* p1 = ctx->lrec_a.as<RecP1>(); RecP2* p2 = ctx->lrec_v.as<RecP2>();
     if (ctx->qorder && ctx->blob_lists) {
-        SPHX_TRY(loop_attr(ctx));
+        SPHX_TRY(sphx_lds_opt_in(ctx, reinterpret_cast<const void*>(blob_loop1_kernel), IMG_BYTES(72, SPHX_MAX_K)));
         const int nblk = (npad + BLOB_P - 1) / BLOB_P;
         const int g = sphx_blob_grid(ctx, nblk);
         SPHX_TRY(sphx_ensure(ctx, ctx->loop_side, (size_t)n * sizeof(double)));
@@ -830,7 +765,7 @@ static int loop_pass2_launch(sphx_ctx* ctx, int64_t n, int k, StateArrays& st, c
     const int npad = (int)sphx_pad64(n);
     RecP1* p1 = ctx->lrec_a.as<RecP1>(); RecP2* p2 = ctx->lrec_v.as<RecP2>();
     if (ctx->qorder && ctx->blob_lists) {
-        SPHX_TRY(loop_attr(ctx));
+        SPHX_TRY(sphx_lds_opt_in(ctx, reinterpret_cast<const void*>(blob_loop2_kernel), IMG_BYTES(72, SPHX_MAX_K)));
         const int nblk = (npad + BLOB_P - 1) / BLOB_P;
         const int g = sphx_blob_grid(ctx, nblk);
         hipLaunchKernelGGL(blob_loop2_kernel, dim3(g), dim3(PASS_T), IMG_BYTES(72, k), ctx->stream, (int)n, npad, k, nblk,

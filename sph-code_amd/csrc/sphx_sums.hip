@@ -10,10 +10,12 @@
 // order shared with the lanes-per-particle split of the LDS kernels of sphx_blob.hip, so all
 // variants agree bit for bit.  In registers, no atomics: results are bitwise reproducible.
 // Deltas are taken relative to nbr[0][i] (the reference subtracts neighbour 0, nsc:580-581).
+// The kernels here are the gather form: they fetch indices, then records, and hand every neighbour to the term
+// functions of sphx_pair.h, where the arithmetic of a pair is written once for this form and the LDS form.
 #include "sphx_internal.h"
 #include "sphx_wave.h"
-// NumPy never fuses a multiply into an add: keep every operation separately rounded so that
-// cancellations such as h_j^2 - r^2 at the kernel edge reproduce the reference bit for bit.
+#include "sphx_pair.h"
+// NumPy never fuses a multiply into an add (sphx_pair.h)
 #pragma clang fp contract(off)
 #include <float.h>
 #include <stdlib.h>
@@ -119,24 +121,11 @@ int sphx_transpose_nbr(sphx_ctx* ctx, int64_t n, int k, const int64_t* nb_dev) {
 struct OutMap { const int* perm; int n_active; };
 __device__ __forceinline__ int out_index(const OutMap& m, int i) { return m.perm ? m.perm[i] : i; }
 
-// 32-B pieces of a record, loaded as two 16-B vectors each
-struct Q4 { double a, b, c, d; };
-__device__ __forceinline__ Q4 load4(const double* p) {
-    const double2 lo = *reinterpret_cast<const double2*>(p);
-    const double2 hi = *reinterpret_cast<const double2*>(p + 2);
-    return Q4{lo.x, lo.y, hi.x, hi.y};
-}
-
 // The neighbour loops run in chunks of NBATCH: all NBATCH indices are fetched first, then all
 // NBATCH records, so several independent gathers are in flight per lane before the first use
-// (the passes are bound by gather latency, not arithmetic); the sums still accumulate in list order.
+// (the passes are bound by gather latency, not arithmetic); the sums still accumulate in list order,
+// one partial sum per list position k mod SPHX_SUM_PARTS (parts_total, sphx_pair.h).
 #define NBATCH 4
-
-// (p0 + p1) [+ (p2 + p3)]: the order the lane groups of sphx_blob.hip combine their partial sums in
-__device__ __forceinline__ double parts_total(const double (&a)[SPHX_SUM_PARTS]) {
-    if (SPHX_SUM_PARTS == 4) return (a[0] + a[1]) + (a[2] + a[3]);
-    return a[0] + a[SPHX_SUM_PARTS - 1];
-}
 
 // ---- pass 1 ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pass_density_kernel(int n, int npad, int k, int clip,
@@ -151,13 +140,12 @@ __global__ __launch_bounds__(256) void pass_density_kernel(int n, int npad, int 
     const int o = out_index(om, i);
     if (o >= om.n_active) return;
     const double* self = reinterpret_cast<const double*>(&rec[i]);
-    const Q4 s0 = load4(self), s1 = load4(self + 4);          // x y z h2 | c1 ms A Nw
+    const Q4 s0 = gload4(self), s1 = gload4(self + 4);          // x y z h2 | c1 ms A Nw
     int j0 = nbr[p];
     double xr = s0.a, yr = s0.b, zr = s0.c;
     if (j0 >= 0 && j0 != i) { xr = rec[j0].x; yr = rec[j0].y; zr = rec[j0].z; }
     const double hi2 = s0.d, ci = -6.0 * s1.a, Ai = s1.c;
-    double a_rho[SPHX_SUM_PARTS] = {}, a_rd[SPHX_SUM_PARTS] = {}, a_n[SPHX_SUM_PARTS] = {};
-    double a_gx[SPHX_SUM_PARTS] = {}, a_gy[SPHX_SUM_PARTS] = {}, a_gz[SPHX_SUM_PARTS] = {};
+    DensAcc acc[SPHX_SUM_PARTS] = {};
     for (int kk0 = 0; kk0 < k; kk0 += NBATCH) {
       int jb[NBATCH];
       Q4 q0b[NBATCH], q1b[NBATCH];
@@ -166,33 +154,16 @@ __global__ __launch_bounds__(256) void pass_density_kernel(int n, int npad, int 
 #pragma unroll
       for (int u = 0; u < NBATCH; ++u) {
           const double* q = reinterpret_cast<const double*>(&rec[jb[u] < 0 ? i : jb[u]]);
-          q0b[u] = load4(q); q1b[u] = load4(q + 4);
+          q0b[u] = gload4(q); q1b[u] = gload4(q + 4);
       }
 #pragma unroll
       for (int u = 0; u < NBATCH; ++u) {
         if (jb[u] < 0) continue;
-        const Q4 q0 = q0b[u], q1 = q1b[u];
-        const double dx = q0.a - xr, dy = q0.b - yr, dz = q0.c - zr;
-        const double r = sqrt(dx * dx + dy * dy + dz * dz);   // nsc:586
-        const double r2 = r * r;                              // nsc:588 squares the rounded distance
-        const double qj = q0.d - r2;
-        const double c1 = q1.a, ms = q1.b, Aj = q1.c, Nw = q1.d;
-        double W = c1 * (qj * qj * qj);                       // nsc:588
-        W = (W < 0.0) ? 0.0 : W;                              // nsc:589
-        const double cb = (clip && !(qj > 0.0)) ? 0.0 : -6.0 * c1 * (qj * qj);   // nsc:591 (not clipped; clip: nsc:689)
-        const double qi = hi2 - r2;
-        const double ca = ci * (qi * qi);                     // nsc:592
-        a_rho[u & (SPHX_SUM_PARTS - 1)] += fmax(ms, 0.0) * W;                    // nsc:605
-        a_rd[u & (SPHX_SUM_PARTS - 1)] += fmax(-ms, 0.0) * W;                    // nsc:606
-        a_n[u & (SPHX_SUM_PARTS - 1)] += Nw * W;                                 // nsc:607
-        const double tg = (Aj * cb + Ai * ca) * 0.5;                                 // nsc:615 (as sphx_blob.hip density_batch)
-        a_gx[u & (SPHX_SUM_PARTS - 1)] += tg * dx;
-        a_gy[u & (SPHX_SUM_PARTS - 1)] += tg * dy;
-        a_gz[u & (SPHX_SUM_PARTS - 1)] += tg * dz;
+        density_term<SqrtLib>(acc[u & (SPHX_SUM_PARTS - 1)], q0b[u], q1b[u], xr, yr, zr, hi2, ci, Ai, clip != 0);
       }
     }
-    const double s_rho = parts_total(a_rho), s_rd = parts_total(a_rd), s_n = parts_total(a_n);
-    const double gx = parts_total(a_gx), gy = parts_total(a_gy), gz = parts_total(a_gz);
+    const double s_rho = parts_total(acc, &DensAcc::rho), s_rd = parts_total(acc, &DensAcc::rd), s_n = parts_total(acc, &DensAcc::n);
+    const double gx = parts_total(acc, &DensAcc::gx), gy = parts_total(acc, &DensAcc::gy), gz = parts_total(acc, &DensAcc::gz);
     rho[o] = s_rho; rhod[o] = s_rd; nden[o] = s_n;
     rho_s[i] = s_rho;                                         // sorted order: gathered by pass 2
     if (G) { G[3 * (size_t)o + 0] = -gx; G[3 * (size_t)o + 1] = -gy; G[3 * (size_t)o + 2] = -gz; }
@@ -218,20 +189,6 @@ int sphx_pass_density(sphx_ctx* ctx, int64_t n, int k) {
 }
 
 // ---- pass 2 ---------------------------------------------------------------------------------
-__device__ __forceinline__ u64 block_min_u64(u64 v) {
-    __shared__ u64 sm[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        u64 p = __shfl_xor(v, o, 64);
-        v = p < v ? p : v;
-    }
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 r = sm[0];
-    for (int w = 1; w < 4; ++w) r = sm[w] < r ? sm[w] : r;
-    return r;
-}
-
 __global__ __launch_bounds__(256) void pass_pi_kernel(int n, int npad, int k, const int* __restrict__ nbr,
                                                       const RecB* __restrict__ recb,
                                                       const double* __restrict__ rho_s,
@@ -239,14 +196,14 @@ __global__ __launch_bounds__(256) void pass_pi_kernel(int n, int npad, int k, co
                                                       const int* __restrict__ qorder, OutMap om, double* Pi, double* BwOut,
                                                       u64* ct_bits) {
     const int p = xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
-    u64 my_ct = 0x7FF0000000000000ull;       // +inf: "no crossing time"
+    u64 my_ct = SPHX_CT_NONE;
     const int i = (p < n) ? (qorder ? qorder[p] : p) : n;
     const int o = (i < n) ? out_index(om, i) : 0x7FFFFFFF;
     if (i < n && o < om.n_active) {
         int j0 = nbr[p];
         if (j0 < 0) j0 = i;
         const double* rq = reinterpret_cast<const double*>(&recb[j0]);
-        const Q4 r0 = load4(rq), rv = load4(rq + 4);                         // x y z h2 | vx vy vz cs
+        const Q4 r0 = gload4(rq), rv = gload4(rq + 4);                         // x y z h2 | vx vy vz cs
         const RecSelf sf = selfr[i];
         const double rho_i = rho_s[i], cs_i = sf.csi, ms_i = sf.mg, h_i = sf.h;
         double a_pi[SPHX_SUM_PARTS] = {}, maxrel = 0.0;
@@ -260,24 +217,15 @@ __global__ __launch_bounds__(256) void pass_pi_kernel(int n, int npad, int k, co
           for (int u = 0; u < NBATCH; ++u) {
               const int jj = jb[u] < 0 ? i : jb[u];
               const double* qb = reinterpret_cast<const double*>(&recb[jj]);
-              q0b[u] = load4(qb); qvb[u] = load4(qb + 4);
+              q0b[u] = gload4(qb); qvb[u] = gload4(qb + 4);
               rhob[u] = rho_s[jj];
           }
 #pragma unroll
           for (int u = 0; u < NBATCH; ++u) {
             if (jb[u] < 0) continue;
-            const Q4 q0 = q0b[u], qv = qvb[u];
-            const double rho_j = rhob[u];
-            const double dx = q0.a - r0.a, dy = q0.b - r0.b, dz = q0.c - r0.c;
-            const double dvx = qv.a - rv.a, dvy = qv.b - rv.b, dvz = qv.c - rv.c;
-            const double r2 = dx * dx + dy * dy + dz * dz;
-            const double dot = dvx * dx + dvy * dy + dvz * dz;
-            double w = dot / sqrt(r2 + 0.01 * q0.d);                        // nsc:643
-            w = (w > 0.0) ? 0.0 : w;                                        // nsc:644
-            const double rho_ab = (rho_j + rho_i) / 2.0;                    // nsc:646
-            const double c_ab = 0.5 * (qv.d + cs_i);                        // nsc:647
-            a_pi[u & (SPHX_SUM_PARTS - 1)] += -0.5 * (c_ab * 2.0 - 3.0 * w) * w / rho_ab;      // nsc:649
-            maxrel = fmax(maxrel, dvx * dvx + dvy * dvy + dvz * dvz);       // nsc:780
+            const PiPair t = pi_term<SqrtLib>(q0b[u], qvb[u], rhob[u], r0, rv, rho_i, cs_i);
+            a_pi[u & (SPHX_SUM_PARTS - 1)] += t.pi;
+            maxrel = fmax(maxrel, t.rel);
           }
         }
         const double s_pi = parts_total(a_pi);
@@ -285,15 +233,9 @@ __global__ __launch_bounds__(256) void pass_pi_kernel(int n, int npad, int k, co
         const double bw = fmax(ms_i, 0.0) * s_pi;                           // m Pi [t==0]  nsc:651
         bc[i].Bw = bw;
         if (BwOut) BwOut[o] = bw;
-        if (ms_i > 0.0) {                                                   // gas only     nsc:782
-            double ct = h_i / sqrt(maxrel);
-            if (ct != ct) ct = 0.0;                                         // nan_to_num
-            if (ct > DBL_MAX) ct = DBL_MAX;
-            if (ct > 0.0) my_ct = (u64)__double_as_longlong(ct);
-        }
+        if (ms_i > 0.0) my_ct = ct_vote_bits(h_i, maxrel);                  // gas only     nsc:782
     }
-    u64 bm = block_min_u64(my_ct);
-    if (threadIdx.x == 0 && bm != 0x7FF0000000000000ull) atomicMin(ct_bits, bm);
+    block_min_vote<256>(my_ct, ct_bits);
 }
 
 int sphx_pass_pi(sphx_ctx* ctx, int64_t n, int k, const double* h, const double* ptype) {
@@ -330,10 +272,10 @@ __global__ __launch_bounds__(256) void pass_visc_kernel(int n, int npad, int k, 
     int j0 = nbr[p];
     if (j0 < 0) j0 = i;
     const double* rq = reinterpret_cast<const double*>(&recb[j0]);
-    const Q4 r0 = load4(rq), rv = load4(rq + 4);
+    const Q4 r0 = gload4(rq), rv = gload4(rq + 4);
     const double2 bci = *reinterpret_cast<const double2*>(&bc[i]);       // Bw, c1
     const double hi2 = recb[i].h2, ci = -6.0 * bci.y, Bi = bci.x;
-    double a_x[SPHX_SUM_PARTS] = {}, a_y[SPHX_SUM_PARTS] = {}, a_z[SPHX_SUM_PARTS] = {}, a_h[SPHX_SUM_PARTS] = {};
+    ViscAcc acc[SPHX_SUM_PARTS] = {};
     for (int kk0 = 0; kk0 < k; kk0 += NBATCH) {
       int jb[NBATCH];
       Q4 q0b[NBATCH], qvb[NBATCH];
@@ -344,28 +286,17 @@ __global__ __launch_bounds__(256) void pass_visc_kernel(int n, int npad, int k, 
       for (int u = 0; u < NBATCH; ++u) {
           const int jj = jb[u] < 0 ? i : jb[u];
           const double* qb = reinterpret_cast<const double*>(&recb[jj]);
-          q0b[u] = load4(qb); qvb[u] = load4(qb + 4);
+          q0b[u] = gload4(qb); qvb[u] = gload4(qb + 4);
           bcb[u] = *reinterpret_cast<const double2*>(&bc[jj]);
       }
 #pragma unroll
       for (int u = 0; u < NBATCH; ++u) {
         if (jb[u] < 0) continue;
-        const Q4 q0 = q0b[u], qv = qvb[u];
-        const double2 bcj = bcb[u];
-        const double c1 = bcj.y, Bj = bcj.x;
-        const double dx = q0.a - r0.a, dy = q0.b - r0.b, dz = q0.c - r0.c;
-        const double r = sqrt(dx * dx + dy * dy + dz * dz);
-        const double r2 = r * r;
-        const double qj = q0.d - r2, qi = hi2 - r2;
-        const double cb = (clip && !(qj > 0.0)) ? 0.0 : -6.0 * c1 * (qj * qj);
-        const double ca = ci * (qi * qi);
-        const double tb = (Bj * cb + Bi * ca) / 2.0;                          // nsc:651, the common factor taken out (see pass 1)
-        const double bx = tb * dx, by = tb * dy, bz = tb * dz;
-        a_x[u & (SPHX_SUM_PARTS - 1)] += bx; a_y[u & (SPHX_SUM_PARTS - 1)] += by; a_z[u & (SPHX_SUM_PARTS - 1)] += bz;
-        a_h[u & (SPHX_SUM_PARTS - 1)] += bx * (qv.a - rv.a) + by * (qv.b - rv.b) + bz * (qv.c - rv.c);   // nsc:653
+        visc_term<SqrtLib>(acc[u & (SPHX_SUM_PARTS - 1)], q0b[u], qvb[u], bcb[u].x, bcb[u].y, r0, rv, hi2, ci, Bi, clip != 0);
       }
     }
-    const double ax = parts_total(a_x), ay = parts_total(a_y), az = parts_total(a_z), heat = parts_total(a_h);
+    const double ax = parts_total(acc, &ViscAcc::x), ay = parts_total(acc, &ViscAcc::y), az = parts_total(acc, &ViscAcc::z);
+    const double heat = parts_total(acc, &ViscAcc::h);
     va[3 * (size_t)o + 0] = -ax; va[3 * (size_t)o + 1] = -ay; va[3 * (size_t)o + 2] = -az;
     vh[o] = heat * m[o] / 2.0;                                              // nsc:654  (m in output order)
 }
@@ -384,10 +315,8 @@ int sphx_pass_visc(sphx_ctx* ctx, int64_t n, int k, const double* m) {
 }
 
 // ---- passes 2 + 3 fused: the pairwise viscosity (visc_mode 1) ------------------------------------
-// pi_ik of nsc:649 stays inside the sum (the Monaghan form of the loop version, nsc:802-808):
-//   B_ik = pi_ik (M_j c_b + M_i c_a) / 2 (dx, dy, dz),  M = m [t==0] C/h^9 (RecBC.Bw, sphx_prep),  c_b, c_a as pass 3
-// nothing needs Pi_j, so pass 2 is not run; this pass casts its crossing-time vote instead.  The heat term is added
-// as t_b * (dv . dx) with the very dot product whose sign made pi_ik > 0 (w < 0): every term is >= 0 by construction.
+// pi_ik of nsc:649 stays inside the sum (visc_pw_term, sphx_pair.h): nothing needs Pi_j, so pass 2 is not run; this pass
+// casts its crossing-time vote instead.
 __global__ __launch_bounds__(256) void pass_visc_pw_kernel(int n, int npad, int k, int clip,
                                                            const int* __restrict__ nbr,
                                                            const RecB* __restrict__ recb,
@@ -398,18 +327,18 @@ __global__ __launch_bounds__(256) void pass_visc_pw_kernel(int n, int npad, int 
                                                            const double* __restrict__ m, double* va, double* vh,
                                                            u64* ct_bits) {
     const int p = xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
-    u64 my_ct = 0x7FF0000000000000ull;       // +inf: "no crossing time"
+    u64 my_ct = SPHX_CT_NONE;
     const int i = (p < n) ? (qorder ? qorder[p] : p) : n;
     const int o = (i < n) ? out_index(om, i) : 0x7FFFFFFF;
     if (i < n && o < om.n_active) {
         int j0 = nbr[p];
         if (j0 < 0) j0 = i;
         const double* rq = reinterpret_cast<const double*>(&recb[j0]);
-        const Q4 r0 = load4(rq), rv = load4(rq + 4);
+        const Q4 r0 = gload4(rq), rv = gload4(rq + 4);
         const RecSelf sf = selfr[i];
         const double rho_i = rho_s[i], cs_i = sf.csi, h_i = sf.h;
         const double hi2 = recb[i].h2, ci = -6.0 * bc[i].Bw;
-        double a_x[SPHX_SUM_PARTS] = {}, a_y[SPHX_SUM_PARTS] = {}, a_z[SPHX_SUM_PARTS] = {}, a_h[SPHX_SUM_PARTS] = {};
+        ViscAcc acc[SPHX_SUM_PARTS] = {};
         double maxrel = 0.0;
         for (int kk0 = 0; kk0 < k; kk0 += NBATCH) {
           int jb[NBATCH];
@@ -421,46 +350,24 @@ __global__ __launch_bounds__(256) void pass_visc_pw_kernel(int n, int npad, int 
           for (int u = 0; u < NBATCH; ++u) {
               const int jj = jb[u] < 0 ? i : jb[u];
               const double* qb = reinterpret_cast<const double*>(&recb[jj]);
-              q0b[u] = load4(qb); qvb[u] = load4(qb + 4);
+              q0b[u] = gload4(qb); qvb[u] = gload4(qb + 4);
               rhob[u] = rho_s[jj];
               mcb[u] = bc[jj].Bw;
           }
 #pragma unroll
           for (int u = 0; u < NBATCH; ++u) {
             if (jb[u] < 0) continue;
-            const Q4 q0 = q0b[u], qv = qvb[u];
-            const double dx = q0.a - r0.a, dy = q0.b - r0.b, dz = q0.c - r0.c;
-            const double dvx = qv.a - rv.a, dvy = qv.b - rv.b, dvz = qv.c - rv.c;
-            const double rr = dx * dx + dy * dy + dz * dz;
-            const double dot = dvx * dx + dvy * dy + dvz * dz;
-            double w = dot / sqrt(rr + 0.01 * q0.d);                        // nsc:643
-            w = (w > 0.0) ? 0.0 : w;                                        // nsc:644
-            const double rho_ab = (rhob[u] + rho_i) / 2.0;                  // nsc:646
-            const double c_ab = 0.5 * (qv.d + cs_i);                        // nsc:647
-            const double pi = -0.5 * (c_ab * 2.0 - 3.0 * w) * w / rho_ab;   // nsc:649, per pair
-            maxrel = fmax(maxrel, dvx * dvx + dvy * dvy + dvz * dvz);       // nsc:780
-            const double r = sqrt(rr);
-            const double r2 = r * r;
-            const double qj = q0.d - r2, qi = hi2 - r2;
-            const double cb = (clip && !(qj > 0.0)) ? 0.0 : -6.0 * mcb[u] * (qj * qj);
-            const double ca = ci * (qi * qi);
-            const double tb = pi * (cb + ca) / 2.0;
-            a_x[u & (SPHX_SUM_PARTS - 1)] += tb * dx; a_y[u & (SPHX_SUM_PARTS - 1)] += tb * dy; a_z[u & (SPHX_SUM_PARTS - 1)] += tb * dz;
-            a_h[u & (SPHX_SUM_PARTS - 1)] += tb * dot;                       // nsc:653
+            maxrel = fmax(maxrel, visc_pw_term<SqrtLib>(acc[u & (SPHX_SUM_PARTS - 1)], q0b[u], qvb[u], rhob[u], mcb[u], r0, rv,
+                                                         rho_i, cs_i, hi2, ci, clip != 0));
           }
         }
-        const double ax = parts_total(a_x), ay = parts_total(a_y), az = parts_total(a_z), heat = parts_total(a_h);
+        const double ax = parts_total(acc, &ViscAcc::x), ay = parts_total(acc, &ViscAcc::y), az = parts_total(acc, &ViscAcc::z);
+        const double heat = parts_total(acc, &ViscAcc::h);
         va[3 * (size_t)o + 0] = -ax; va[3 * (size_t)o + 1] = -ay; va[3 * (size_t)o + 2] = -az;
         vh[o] = heat * m[o] / 2.0;                                          // nsc:654
-        if (sf.mg > 0.0) {                                                  // gas only     nsc:782
-            double ct = h_i / sqrt(maxrel);
-            if (ct != ct) ct = 0.0;                                         // nan_to_num
-            if (ct > DBL_MAX) ct = DBL_MAX;
-            if (ct > 0.0) my_ct = (u64)__double_as_longlong(ct);
-        }
+        if (sf.mg > 0.0) my_ct = ct_vote_bits(h_i, maxrel);                 // gas only     nsc:782
     }
-    u64 bm = block_min_u64(my_ct);
-    if (threadIdx.x == 0 && bm != 0x7FF0000000000000ull) atomicMin(ct_bits, bm);
+    block_min_vote<256>(my_ct, ct_bits);
 }
 
 int sphx_pass_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m) {
@@ -638,7 +545,7 @@ __global__ __launch_bounds__(256) void pass_drag_kernel(int n, int npad, int k, 
     if (p >= n) return;
     const int i = qorder ? qorder[p] : p;
     const double* rq = reinterpret_cast<const double*>(&recb[i]);
-    const Q4 r0 = load4(rq), rv = load4(rq + 4);
+    const Q4 r0 = gload4(rq), rv = gload4(rq + 4);
     // (partial sums over the list positions k mod SPHX_SUM_PARTS, as every sum of the step: the LDS form, sphx_blob.hip
     //  blob_drag_kernel, keeps one per lane)
     double a_x[SPHX_SUM_PARTS] = {}, a_y[SPHX_SUM_PARTS] = {}, a_z[SPHX_SUM_PARTS] = {};
@@ -649,22 +556,11 @@ __global__ __launch_bounds__(256) void pass_drag_kernel(int n, int npad, int k, 
         double& oy = a_y[kk & (SPHX_SUM_PARTS - 1)];
         double& oz = a_z[kk & (SPHX_SUM_PARTS - 1)];
         const double* qb = reinterpret_cast<const double*>(&recb[j]);
-        const Q4 q0 = load4(qb), qv = load4(qb + 4);
-        const double dx = q0.a - r0.a, dy = q0.b - r0.b, dz = q0.c - r0.c;
-        const double ds2 = q0.d, ds = sqrt(ds2);
-        const double q = ds2 - (dx * dx + dy * dy + dz * dz);
-        const double ds4 = ds2 * ds2;
-        const double wf = m[j] * 315.0 * (q * q * q) / (201.06192982974676 * (ds4 * ds4 * ds));   // nsc:678-681
-        double fx = 0.0, fy = 0.0, fz = 0.0;
-        if (wf > 0.0) {
-            const double dvx = qv.a - rv.a, dvy = qv.b - rv.b, dvz = qv.c - rv.c;
-            const double coef = wf / mgm[j] * mcs[j] * sqrt(dvx * dvx + dvy * dvy + dvz * dvz);
-            fx = coef * dvx; fy = coef * dvy; fz = coef * dvz;
-            ox += fx; oy += fy; oz += fz;
-        }
+        const Q4 q0 = gload4(qb), qv = gload4(qb + 4);
+        const Vec3 f = drag_term(ox, oy, oz, q0, qv, r0, rv, j, m, mgm, mcs);
         if (j != i) {                                              // nsc:741 (a zero where the kernel vanishes: counted too)
             const int slot = sc.start[j] + atomicSub(&sc.cnt[j], 1) - 1;
-            sphx_drag_put(sc, slot, ((u64)(unsigned)id[i] << 8) | (u64)kk, -fx, -fy, -fz);
+            sphx_drag_put(sc, slot, ((u64)(unsigned)id[i] << 8) | (u64)kk, -f.x, -f.y, -f.z);
         }
     }
     onto[3 * (size_t)i] = parts_total(a_x); onto[3 * (size_t)i + 1] = parts_total(a_y); onto[3 * (size_t)i + 2] = parts_total(a_z);
@@ -712,14 +608,8 @@ __global__ __launch_bounds__(256) void pass_species_kernel(int n, int npad, int 
         int j = nbr[(size_t)kk * npad + p];
         if (j < 0) continue;
         const double* q = reinterpret_cast<const double*>(&rec[j]);
-        const Q4 q0 = load4(q);
-        const double c1 = q[4], Nw = q[7];
-        const double dx = q0.a - xr, dy = q0.b - yr, dz = q0.c - zr;
-        const double r = sqrt(dx * dx + dy * dy + dz * dz);
-        const double qj = q0.d - r * r;
-        double W = c1 * (qj * qj * qj);
-        W = (W < 0.0) ? 0.0 : W;
-        const double wN = Nw * W;
+        const Q4 q0 = gload4(q);
+        const double wN = species_weight<SqrtLib>(q0, q[4], q[7], xr, yr, zr);
         const double* f = fun + (size_t)j * S + s0;
 #pragma unroll
         for (int t = 0; t < SPEC_CHUNK; ++t)
@@ -772,14 +662,8 @@ __global__ __launch_bounds__(256) void step_species_kernel(int n, int npad, int 
         for (int u = 0; u < 4; ++u) {
             const int jj = jb[u] < 0 ? i : jb[u];
             const double* q = reinterpret_cast<const double*>(&rec[jj]);
-            const Q4 q0 = load4(q);
-            const double c1 = q[4], Nw = q[7];
-            const double dx = q0.a - xr, dy = q0.b - yr, dz = q0.c - zr;
-            const double r = sqrt(dx * dx + dy * dy + dz * dz);
-            const double qj = q0.d - r * r;
-            double W = c1 * (qj * qj * qj);
-            W = (W < 0.0) ? 0.0 : W;
-            wN[u] = jb[u] < 0 ? 0.0 : Nw * W;
+            const Q4 q0 = gload4(q);
+            wN[u] = jb[u] < 0 ? 0.0 : species_weight<SqrtLib>(q0, q[4], q[7], xr, yr, zr);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -800,16 +684,7 @@ __global__ __launch_bounds__(256) void step_species_kernel(int n, int npad, int 
     for (int t = 0; t < SMAX; ++t)
         if (t < S) F[(size_t)t * n + i] = acc[t];
     if (!agb_on) return;
-    double heavy = 0.0, all = 0.0;
-#pragma unroll
-    for (int t = 0; t < SMAX; ++t) {
-        if (t < S) {
-            const double w = acc[t] * agb.mu[t];
-            all += w;
-            if (t >= 6) heavy += w;
-        }
-    }
-    const double Z = heavy / all;                            // drv:663 (0/0 -> NaN for a particle without gas neighbours)
+    const double Z = species_metallicity(agb, acc, S);           // drv:663
     Zout[i] = Z;
     double dust[AGB_MAX_SPEC];
     agb_dust_yields(agb, m[i], Z, dust);
