@@ -15,15 +15,21 @@ int sphx_set_err(sphx_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-int sphx_ensure(sphx_ctx* ctx, DevBuf& b, size_t bytes) {
+void sphx_release(sphx_ctx* ctx, DevBuf& b) {
+    for (size_t q = 0; q < ctx->allocs.size(); ++q)
+        if (ctx->allocs[q] == b.p) { ctx->allocs[q] = ctx->allocs.back(); ctx->allocs.pop_back(); break; }
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+}
+
+int sphx_ensure(sphx_ctx* ctx, DevBuf& b, size_t bytes, hipStream_t in_use_on) {
     if (bytes == 0) bytes = 8;
     if (b.cap >= bytes) return SPHX_OK;
     if (b.p) {
         // buffers may still be referenced by queued work
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        HIPCHK(hipFree(b.p));
-        b.p = nullptr;
-        b.cap = 0;
+        HIPCHK(hipStreamSynchronize(in_use_on));
+        sphx_release(ctx, b);
     }
     size_t want = bytes + bytes / 8 + 256;
     hipError_t e = hipMalloc(&b.p, want);
@@ -32,6 +38,7 @@ int sphx_ensure(sphx_ctx* ctx, DevBuf& b, size_t bytes) {
         return sphx_set_err(ctx, SPHX_E_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
     }
     b.cap = want;
+    ctx->allocs.push_back(b.p);
     return SPHX_OK;
 }
 
@@ -160,33 +167,11 @@ extern "C" int sphx_create(sphx_ctx** out, int device) {
     return SPHX_OK;
 }
 
-static void free_buf(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
-static void free_state(StateArrays& s) {
-    DevBuf* all[] = {&s.x, &s.y, &s.z, &s.vx, &s.vy, &s.vz, &s.ax, &s.ay, &s.az, &s.m, &s.T,
-                     &s.mu, &s.gam, &s.E, &s.hprev, &s.ptype, &s.id, &s.fun, &s.mgm, &s.mcs};
-    for (DevBuf* b : all) free_buf(*b);
-}
-
 extern "C" void sphx_destroy(sphx_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    DevBuf* all[] = {&ctx->rec1, &ctx->recv, &ctx->nbr, &ctx->rho, &ctx->rhod, &ctx->nden, &ctx->G,
-                     &ctx->Pi, &ctx->Bw, &ctx->rho_s, &ctx->bc_s, &ctx->self_s, &ctx->drag_on, &ctx->drag_re, &ctx->grav, &ctx->grav_sort, &ctx->grav_tmp, &ctx->grav_pyr, &ctx->grav_cell, &ctx->lrec_a, &ctx->lrec_v, &ctx->porder, &ctx->mcount, &ctx->mstart, &ctx->slot16, &ctx->uniq, &ctx->list64, &ctx->dref, &ctx->pos0, &ctx->pos4, &ctx->va, &ctx->vh, &ctx->ha, &ctx->F,
-                     &ctx->scal, &ctx->cell_of, &ctx->cell_start, &ctx->cell_fill, &ctx->perm,
-                     &ctx->inv, &ctx->scan_tmp, &ctx->bbox_tmp, &ctx->in_a, &ctx->in_b, &ctx->in_c,
-                     &ctx->in_d, &ctx->in_e, &ctx->in_f, &ctx->in_g, &ctx->in_h, &ctx->in_i,
-                     &ctx->in_j, &ctx->out_a, &ctx->out_b, &ctx->out_c, &ctx->idx64, &ctx->dist_out,
-                     &ctx->nontriv, &ctx->h_api, &ctx->hsum_tmp, &ctx->grav_quad, &ctx->scal_tmp, &ctx->fail_list,
-                     &ctx->agb_knots, &ctx->Zmet, &ctx->agb_dust, &ctx->need_pyr, &ctx->ds_cnt, &ctx->ds_start, &ctx->ds_ent,
-                     &ctx->loop_side, &ctx->crowded, &ctx->fun_id, &ctx->olev_start, &ctx->olev_fill, &ctx->olev_list, &ctx->olev_key, &ctx->blob_class, &ctx->blob_split, &ctx->badc, &ctx->tie_list, &ctx->lbs_state[0], &ctx->lbs_state[1], &ctx->cell_rank};
-    for (DevBuf* b : all) free_buf(*b);
-    free_state(ctx->st);
-    free_state(ctx->alt);
+    for (void* p : ctx->allocs) (void)hipFree(p);
     for (int i = 0; i < 10; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
     for (int r = 0; r < 3; ++r)
@@ -248,10 +233,6 @@ static int download(sphx_ctx* ctx, void* host, const void* dev, size_t bytes) {
     HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
     return SPHX_OK;
 }
-#define NEED(p)                                                                              \
-    do {                                                                                     \
-        if (!(p)) return sphx_set_err(ctx, SPHX_E_ARG, "%s: argument %s is NULL", __func__, #p); \
-    } while (0)
 
 // =============================================================================================
 // nsc.neighbors                                                                nsc:541-552
@@ -289,8 +270,11 @@ extern "C" int sphx_neighbors(sphx_ctx* ctx, int64_t n, int k, const double* poi
     o.nbr = nullptr; o.h_sorted = nullptr;
     o.idx64 = ctx->idx64.as<int64_t>(); o.dist = ctx->dist_out.as<double>();
     o.nontriv = ctx->nontriv.as<int64_t>(); o.h_by_id = ctx->h_api.as<double>();
-    // sorted -> original index is the permutation itself
-    SPHX_TRY(sphx_knn(ctx, n, k, xs, ys, zs, ctx->perm.as<int>(), nullptr, nullptr, 1.0, dist, o));
+    KnnIn in;
+    in.xs = xs; in.ys = ys; in.zs = zs;
+    in.id = ctx->perm.as<int>();             // sorted -> original index is the permutation itself
+    in.rbound = dist;
+    SPHX_TRY(sphx_knn(ctx, n, k, in, o));
     SPHX_TRY(download(ctx, idx, o.idx64, (size_t)n * k * sizeof(int64_t)));
     SPHX_TRY(download(ctx, dist_out, o.dist, (size_t)n * k * sizeof(double)));
     SPHX_TRY(download(ctx, nontriv, o.nontriv, (size_t)n * sizeof(int64_t)));
@@ -338,11 +322,12 @@ extern "C" int sphx_hydro_update(sphx_ctx* ctx, int64_t n, int k, int s, const i
         SPHX_TRY(sphx_transpose_nbr(ctx, n, k, ctx->idx64.as<int64_t>()));
         ctx->nbr_api_valid = true; ctx->nbr_api_n = n; ctx->nbr_api_k = k;
     }
-    ctx->visc_pw = visc_mode == 1;          // (the call's own argument; the context's step mode plays no part)
-    SPHX_TRY(sphx_prep(ctx, n, nullptr, nullptr, nullptr, ctx->in_a.as<double>(), nullptr, nullptr,
-                       nullptr, ctx->in_b.as<double>(), ctx->in_c.as<double>(), ctx->in_d.as<double>(),
-                       ctx->in_e.as<double>(), ctx->in_f.as<double>(), ctx->in_g.as<double>(),
-                       ctx->in_h.as<double>()));
+    PrepIn pin;
+    pin.pos_aos(ctx->in_a.as<double>()); pin.vel_aos(ctx->in_b.as<double>());
+    pin.m = ctx->in_c.as<double>(); pin.h = ctx->in_d.as<double>(); pin.T = ctx->in_e.as<double>();
+    pin.mu = ctx->in_f.as<double>(); pin.gam = ctx->in_g.as<double>(); pin.ptype = ctx->in_h.as<double>();
+    // (pairwise: the call's own argument; the context's step mode plays no part)
+    SPHX_TRY(sphx_prep(ctx, n, pin, visc_mode == 1, ctx->stream));
     SPHX_TRY(sphx_pass_density(ctx, n, k));
     if (visc_mode == 1) {
         SPHX_TRY(sphx_pass_visc_pw(ctx, n, k, ctx->in_c.as<double>()));
@@ -501,6 +486,204 @@ extern "C" int sphx_state_set_gravity(sphx_ctx* ctx, int mode, double G) {
     return SPHX_OK;
 }
 
+// ---- one step of the fused loop, in three phases: grid + search, sums, gravity + update ----
+static PrepIn prep_in_of_state(const StateArrays& s) {
+    PrepIn in;
+    in.x = s.x.as<double>(); in.y = s.y.as<double>(); in.z = s.z.as<double>(); in.ps = 1;
+    in.vx = s.vx.as<double>(); in.vy = s.vy.as<double>(); in.vz = s.vz.as<double>(); in.vs = 1;
+    in.m = s.m.as<double>(); in.h = s.hprev.as<double>(); in.T = s.T.as<double>();
+    in.mu = s.mu.as<double>(); in.gam = s.gam.as<double>(); in.ptype = s.ptype.as<double>();
+    return in;
+}
+
+// cell size of the next grid from the previous step's mean h (read back together with the search's counters); 0: none yet
+static int step_cell_hint(sphx_ctx* ctx, int64_t n, double* cell_hint) {
+    *cell_hint = 0.0;
+    if (ctx->step_count == 0) return SPHX_OK;
+    const double* hs;                                                  // [0] sum ... [3] count
+    if (ctx->lag_hvalid[ctx->lag_hslot]) {
+        // copied out right after the previous step's search: no wait on that step's tail
+        HIPCHK(hipEventSynchronize(ctx->lag_halias[ctx->lag_hslot] ? ctx->lag_halias[ctx->lag_hslot]
+                                                                     : ctx->lag_hev[ctx->lag_hslot]));
+        hs = (const double*)((char*)ctx->pinned + LAG_OFF + 512 * ctx->lag_hslot + 256);
+        // the same copy carries the previous search's counters
+        const u64* sv = (const u64*)hs;           // slots SC_HSUM ..: [5] SC_NFAILQ [6] SC_SHORT [7] SC_FARQ [8] SC_BADHINT
+        for (int q = 0; q < 10; ++q) ctx->knn_lag[q] = sv[(SC_NFAILQ - SC_HSUM) + q];      // .. SC_KGDBG + 2
+        ctx->knn_lag_valid = true;
+    } else {
+        HIPCHK(hipMemcpyAsync((char*)ctx->pinned + 256, ctx->scal.as<double>() + SC_HSUM, 4 * sizeof(double),
+                              hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        hs = (const double*)((char*)ctx->pinned + 256);
+    }
+    const double hmean = hs[3] > 0.0 ? hs[0] / hs[3] : 0.0;
+    if (hmean > 0.0 && isfinite(hmean)) {
+        // SPHX_CELL_FEEDBACK: when a sizeable share of the particles lives in cells of >= DENSE_CELL members (a core
+        // much denser than the mean radius suggests: the 27 cells around a group overflow its tile and the search hands
+        // the group's queries on), the cells shrink, 3 % a step; they relax again, 1 % a step, once that share is small.
+        // (A property of the positions alone: every variant of the search sees the same grid.)
+        *cell_hint = ctx->cell_factor * sphx_cell_feedback(ctx, n) * hmean;
+        ctx->h_clip = ctx->h_clip_factor * hmean;
+    }
+    return SPHX_OK;
+}
+
+// Phase 1: the neighbour list of this step in ctx->nbr and the radii in st.hprev - refreshed from the Verlet lists, or by
+// grid build, blob order, permutation of the state and search.  Records ev[1] in front of the search.
+static int step_search(sphx_ctx* ctx, int k, double dist, hipEvent_t* ev) {
+    const int64_t n = ctx->n;
+    // drv:233-238: applied by the grid build's first pass over the particles (sphx_grid.hip); the Verlet path looks at
+    // the positions before any grid is built, so it clamps here
+    if (ctx->use_verlet) SPHX_TRY(sphx_clamp(ctx, n, ctx->st));
+    SPHX_TRY(sphx_ensure(ctx, ctx->nbr, (size_t)k * ctx->npad * sizeof(int)));
+    // ---- incremental exact kNN from the Verlet lists (sphx_refresh.hip) ---------------------
+    if (ctx->use_verlet && ctx->list_valid && ctx->list_n == n && ctx->list_k == k) {
+        StateArrays& r = ctx->st;
+        HIPCHK(hipEventRecord(ev[1], ctx->stream));
+        int64_t nfail = 0;
+        SPHX_TRY(sphx_knn_refresh(ctx, n, k, r.x.as<double>(), r.y.as<double>(), r.z.as<double>(),
+                                  ctx->nbr.as<int>(), r.hprev.as<double>(), &nfail));
+        if (nfail == 0) {
+            ctx->stats.refresh_steps++;
+            return SPHX_OK;
+        }
+        ctx->list_valid = false;         // some result could not be proven exact: rebuild
+    }
+    double cell_hint = 0.0;
+    SPHX_TRY(step_cell_hint(ctx, n, &cell_hint));
+    {
+        StateArrays& r = ctx->st;       // the box statistics are the previous step's when there are any
+        const bool blob = ctx->use_blob && !ctx->use_verlet;
+        GridBuildOpts g;
+        g.lagged = true;
+        g.alias_ev = ev[1];               // (recorded below, behind the state's permutation)
+        g.sort_cells_later = blob;        // the blob-order pass over the cells sorts their members too
+        if (!ctx->use_verlet) { g.clamp_vel[0] = r.vx.as<double>(); g.clamp_vel[1] = r.vy.as<double>(); g.clamp_vel[2] = r.vz.as<double>(); }
+        SPHX_TRY(sphx_build_grid(ctx, n, k, r.x.as<double>(), r.y.as<double>(), r.z.as<double>(), cell_hint, g));
+        // (the blob order needs cell_of / perm / cell_start only: before the state is permuted, so that the
+        //  deferred member sort has run when perm is used; its last scatter: in sphx_permute_state's kernel, right below)
+        if (blob) SPHX_TRY(sphx_build_blob_order(ctx, n, /*defer_scatter=*/true));
+    }
+    const bool split = ctx->side_stream && !ctx->use_verlet;
+    SPHX_TRY(sphx_permute_state(ctx, n, split, ev[1]));      // (records ev[1] behind the search's part)
+    StateArrays& r = ctx->st;
+    KnnIn in;
+    in.xs = r.x.as<double>(); in.ys = r.y.as<double>(); in.zs = r.z.as<double>();
+    in.id = r.id.as<int>(); in.inv = ctx->inv.as<int>();
+    in.rsearch = r.hprev.as<double>();
+    in.hinted = ctx->step_count > 0 && !ctx->use_verlet;     // hprev holds the previous step's radii
+    in.lag_external = true;              // (step_cell_hint has handed the previous search's counters over)
+    in.rscale = ctx->rscale;
+    in.rbound = dist;
+    KnnOut o;
+    o.nbr = ctx->nbr.as<int>();
+    o.h_sorted = r.hprev.as<double>();   // read as the search-radius hint, then overwritten
+    o.idx64 = nullptr; o.dist = nullptr; o.nontriv = nullptr; o.h_by_id = nullptr;
+    if (ctx->use_verlet) {
+        SPHX_TRY(sphx_ensure(ctx, ctx->list64, (size_t)n * 64 * sizeof(int)));
+        SPHX_TRY(sphx_ensure(ctx, ctx->dref, (size_t)n * sizeof(double)));
+        o.list64 = ctx->list64.as<int>();
+        o.dref = ctx->dref.as<double>();
+        in.rscale = ctx->rscale_build;   // wider: the list must hold 64 entries to earn its margin
+    }
+    SPHX_TRY(sphx_knn(ctx, n, k, in, o));
+    if (split) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_perm, 0));    // the rest of the state is in place
+    if (ctx->use_verlet) {
+        SPHX_TRY(sphx_save_list_positions(ctx, n, r.x.as<double>(), r.y.as<double>(), r.z.as<double>()));
+        ctx->list_valid = true;
+        ctx->list_n = n;
+        ctx->list_k = k;
+    }
+    ctx->stats.rebuild_steps++;
+    return SPHX_OK;
+}
+
+// the sum of h on `stream` and its copy to the host: the next step's cell size, read there when the next grid is sized;
+// the search's counters travel in the same copy (SC_HSUM .. SC_BADHINT are consecutive slots)
+static int step_h_sums_out(sphx_ctx* ctx, int64_t n, const double* h, hipStream_t stream) {
+    SPHX_TRY(sphx_hsum(ctx, n, h, stream));
+    const int hsl = ctx->lag_hslot ^ 1;
+    HIPCHK(hipMemcpyAsync((char*)ctx->pinned + LAG_OFF + 512 * hsl + 256, ctx->scal.as<double>() + SC_HSUM,
+                          (SC_KGDBG + 2 - SC_HSUM + 1) * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipEventRecord(ctx->lag_hev[hsl], stream));
+    ctx->lag_halias[hsl] = nullptr;
+    ctx->lag_hvalid[hsl] = true;
+    ctx->lag_hslot = hsl;
+    return SPHX_OK;
+}
+
+// Phase 2: the sums of hydro_update (or the loop forms) on the list of phase 1.  search_end: the event recorded behind the search.
+static int step_sums(sphx_ctx* ctx, int k, hipEvent_t* ev, hipEvent_t search_end, bool detail) {
+    const int64_t n = ctx->n;
+    StateArrays& s = ctx->st;
+    const bool pairwise = ctx->visc_mode == 1 && !ctx->loop_forms;     // (what sphx_prep builds RecBC.Bw for)
+    // the record build (bandwidth-bound) does not depend on the list dedup (latency-bound): side by side on the side
+    // stream - and behind it there the sum of h and its copy to the host (the passes wait for the records, not for
+    // those; nobody but the next step's host code reads the sums)
+    const bool fork = ctx->qorder && ctx->use_lds && !ctx->loop_forms && ctx->side_stream;
+    if (fork) HIPCHK(hipStreamWaitEvent(ctx->side_stream, search_end, 0));       // (the search's end event doubles as the fork)
+    else SPHX_TRY(step_h_sums_out(ctx, n, s.hprev.as<double>(), ctx->stream));
+    if (ctx->qorder && ctx->use_lds) SPHX_TRY(sphx_blob_translate(ctx, n, k));
+    const bool species = ctx->s > 0 && ctx->fun_id.p;      // nsc:624-627 on the step's list: the state carries f_un
+    if (ctx->loop_forms) {
+        // the reference's time loop (drv:451-458): loop forms on this step's neighbour list
+        if (ctx->drag || species)          // (the species pass reads hydro_update's records, RecA)
+            SPHX_TRY(sphx_prep(ctx, n, prep_in_of_state(s), pairwise, ctx->stream));
+        if (detail) HIPCHK(hipEventRecord(ev[3], ctx->stream));
+        SPHX_TRY(sphx_loop_step_sums(ctx, n, k, ctx->loop_d));
+        if (detail) HIPCHK(hipEventRecord(ev[9], ctx->stream));
+        if (species) SPHX_TRY(sphx_step_species(ctx, n, k));       // (+ metallicity, AGB yields)
+        if (detail) HIPCHK(hipEventRecord(ev[4], ctx->stream));
+        if (detail) HIPCHK(hipEventRecord(ev[5], ctx->stream));
+    } else {
+        // (forked: the side stream is behind the search's end event, and so behind everything that read the previous
+        //  records - also what sphx_prep waits for before it frees an outgrown record buffer)
+        SPHX_TRY(sphx_prep(ctx, n, prep_in_of_state(s), pairwise, fork ? ctx->side_stream : ctx->stream));
+        if (fork) {
+            HIPCHK(hipEventRecord(ctx->ev_join, ctx->side_stream));
+            HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+            SPHX_TRY(step_h_sums_out(ctx, n, s.hprev.as<double>(), ctx->side_stream));
+        }
+        if (detail) HIPCHK(hipEventRecord(ev[3], ctx->stream));
+        // Pass 1, lean: nothing in the step reads G (hydro_accel = G / rho is what the update takes).  The species pass
+        // (+ metallicity and AGB yields when a table is set) inside pass 1's kernel where both run out of LDS (their
+        // first sweeps are the same), else behind it
+        const bool sp_fused = species && ctx->species_fused && ctx->species_lds && ctx->use_lds && ctx->qorder && ctx->blob_lists &&
+                              !ctx->map_perm && ctx->sp == 16 && ctx->s <= 16 && k <= SPHX_MAX_K;
+        if (sp_fused) {
+            const int S = ctx->s;
+            SPHX_TRY(sphx_ensure(ctx, ctx->rho, (size_t)n * sizeof(double)));
+            SPHX_TRY(sphx_ensure(ctx, ctx->rhod, (size_t)n * sizeof(double)));
+            SPHX_TRY(sphx_ensure(ctx, ctx->nden, (size_t)n * sizeof(double)));
+            SPHX_TRY(sphx_ensure(ctx, ctx->G, (size_t)n * 3 * sizeof(double)));
+            SPHX_TRY(sphx_ensure(ctx, ctx->ha, (size_t)n * 3 * sizeof(double)));
+            SPHX_TRY(sphx_ensure(ctx, ctx->F, (size_t)n * S * sizeof(double)));
+            if (ctx->agb_on) {
+                SPHX_TRY(sphx_ensure(ctx, ctx->Zmet, (size_t)n * sizeof(double)));
+                SPHX_TRY(sphx_ensure(ctx, ctx->agb_dust, (size_t)n * S * sizeof(double)));
+            }
+            SPHX_TRY(sphx_blob_density_species(ctx, n, k, /*lean=*/true, S, ctx->fun_id.as<double>(), s.id.as<int>(),
+                                               s.m.as<double>(), ctx->F.as<double>(), ctx->Zmet.as<double>(),
+                                               ctx->agb_dust.as<double>(), (ctx->agb_on && ctx->Zmet.p && ctx->agb_dust.p) ? 1 : 0));
+        } else {
+            SPHX_TRY(sphx_pass_density(ctx, n, k, /*lean=*/true));
+        }
+        if (detail) HIPCHK(hipEventRecord(ev[9], ctx->stream));
+        if (species && !sp_fused) SPHX_TRY(sphx_step_species(ctx, n, k));
+        if (detail) HIPCHK(hipEventRecord(ev[4], ctx->stream));
+        if (ctx->visc_mode == 1) {                 // passes 2 + 3 in one (pairwise viscosity): ms_pi stays 0
+            SPHX_TRY(sphx_pass_visc_pw(ctx, n, k, s.m.as<double>()));
+        } else {
+            SPHX_TRY(sphx_pass_pi(ctx, n, k, s.hprev.as<double>(), s.ptype.as<double>()));
+            if (detail) HIPCHK(hipEventRecord(ev[5], ctx->stream));
+            SPHX_TRY(sphx_pass_visc(ctx, n, k, s.m.as<double>()));
+        }
+    }
+    if (ctx->drag)
+        SPHX_TRY(sphx_pass_drag(ctx, n, k, s.m.as<double>(), s.ptype.as<double>(), s.mgm.as<double>(), s.mcs.as<double>()));
+    return SPHX_OK;
+}
+
 // call_first / call_last: the first / last step of this sphx_step call (they carry the call's start and end events)
 static int one_step(sphx_ctx* ctx, int k, double dist, int first, double fixed_dt, bool call_first, bool call_last) {
     const int64_t n = ctx->n;
@@ -519,224 +702,14 @@ static int one_step(sphx_ctx* ctx, int k, double dist, int first, double fixed_d
     ctx->qorder = nullptr;
     ctx->blob_lists = false;
     ctx->blob_split_valid = false;
-    ctx->visc_pw = ctx->visc_mode == 1 && !ctx->loop_forms;     // (what sphx_prep builds RecBC.Bw for)
     ctx->pass_part = 0;
     ctx->nbr_api_valid = false;   // the step overwrites the K-major list (search or Verlet refresh)
     if (rec0) HIPCHK(hipEventRecord(ev[0], ctx->stream));
-    // drv:233-238: applied by the grid build's first pass over the particles (sphx_grid.hip); the Verlet path looks at
-    // the positions before any grid is built, so it clamps here
-    ctx->clamp_vx = nullptr;
-    if (ctx->use_verlet) {
-        SPHX_TRY(sphx_clamp(ctx, n, ctx->st));
-    } else {
-        ctx->clamp_vx = ctx->st.vx.as<double>(); ctx->clamp_vy = ctx->st.vy.as<double>(); ctx->clamp_vz = ctx->st.vz.as<double>();
-    }
-    SPHX_TRY(sphx_ensure(ctx, ctx->nbr, (size_t)k * ctx->npad * sizeof(int)));
-    // ---- incremental exact kNN from the Verlet lists (sphx_refresh.hip) ---------------------
-    bool searched = false;
-    if (ctx->use_verlet && ctx->list_valid && ctx->list_n == n && ctx->list_k == k) {
-        StateArrays& r = ctx->st;
-        HIPCHK(hipEventRecord(ev[1], ctx->stream));
-        int64_t nfail = 0;
-        SPHX_TRY(sphx_knn_refresh(ctx, n, k, r.x.as<double>(), r.y.as<double>(), r.z.as<double>(),
-                                  ctx->nbr.as<int>(), r.hprev.as<double>(), &nfail));
-        if (nfail == 0) {
-            searched = true;
-            ctx->stats.refresh_steps++;
-        } else {
-            ctx->list_valid = false;         // some result could not be proven exact: rebuild
-        }
-    }
-    if (!searched) {
-        // cell size from the previous step's mean h (read back together with the bounding box)
-        double cell_hint = 0.0;
-        if (ctx->step_count > 0) {
-            const double* hs;                                                  // [0] sum ... [3] count
-            if (ctx->lag_hvalid[ctx->lag_hslot]) {
-                // copied out right after the previous step's search: no wait on that step's tail
-                HIPCHK(hipEventSynchronize(ctx->lag_halias[ctx->lag_hslot] ? ctx->lag_halias[ctx->lag_hslot]
-                                                                             : ctx->lag_hev[ctx->lag_hslot]));
-                hs = (const double*)((char*)ctx->pinned + LAG_OFF + 512 * ctx->lag_hslot + 256);
-            } else {
-                HIPCHK(hipMemcpyAsync((char*)ctx->pinned + 256, ctx->scal.as<double>() + SC_HSUM, 4 * sizeof(double),
-                                      hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(hipStreamSynchronize(ctx->stream));
-                hs = (const double*)((char*)ctx->pinned + 256);
-            }
-            if (ctx->lag_hvalid[ctx->lag_hslot]) {       // the same copy carries the previous search's counters
-                const u64* sv = (const u64*)hs;           // slots SC_HSUM ..: [5] SC_NFAILQ [6] SC_SHORT [7] SC_FARQ [8] SC_BADHINT
-                for (int q = 0; q < 10; ++q) ctx->knn_lag[q] = sv[(SC_NFAILQ - SC_HSUM) + q];      // .. SC_KGDBG + 2
-                ctx->knn_lag_valid = true;
-            }
-            const double hmean = hs[3] > 0.0 ? hs[0] / hs[3] : 0.0;
-            if (hmean > 0.0 && isfinite(hmean)) {
-                // SPHX_CELL_FEEDBACK: when a sizeable share of the particles lives in cells of >= DENSE_CELL members (a core
-                // much denser than the mean radius suggests: the 27 cells around a group overflow its tile and the search hands
-                // the group's queries on), the cells shrink, 3 % a step; they relax again, 1 % a step, once that share is small.
-                // (A property of the positions alone: every variant of the search sees the same grid.)
-                cell_hint = ctx->cell_factor * sphx_cell_feedback(ctx, n) * hmean;
-                ctx->h_clip = ctx->h_clip_factor * hmean;
-            }
-        }
-        {
-            StateArrays& r = ctx->st;       // the box statistics are the previous step's when there are any
-            const bool blob = ctx->use_blob && !ctx->use_verlet;
-            ctx->lag_on = true;
-            ctx->step_ev1 = ev[1];            // (recorded below, behind the state's permutation)
-            ctx->defer_cell_sort = blob;      // the blob-order pass over the cells sorts their members too
-            const int rc_ = sphx_build_grid(ctx, n, k, r.x.as<double>(), r.y.as<double>(), r.z.as<double>(), cell_hint);
-            ctx->lag_on = false;
-            ctx->step_ev1 = nullptr;
-            ctx->defer_cell_sort = false;
-            ctx->clamp_vx = nullptr;
-            SPHX_TRY(rc_);
-            // (the blob order needs cell_of / perm / cell_start only: before the state is permuted, so that the
-            //  deferred member sort has run when perm is used)
-            if (blob) {
-                ctx->defer_blob_scatter = true;          // (its last scatter: in sphx_permute_state's kernel, right below)
-                const int rc_b = sphx_build_blob_order(ctx, n);
-                ctx->defer_blob_scatter = false;
-                SPHX_TRY(rc_b);
-            }
-        }
-        const bool split = ctx->side_stream && !ctx->use_verlet;
-        SPHX_TRY(sphx_permute_state(ctx, n, split, ev[1]));      // (records ev[1] behind the search's part)
-        StateArrays& r = ctx->st;
-        KnnOut o;
-        o.nbr = ctx->nbr.as<int>();
-        o.h_sorted = r.hprev.as<double>();   // read as the search-radius hint, then overwritten
-        o.idx64 = nullptr; o.dist = nullptr; o.nontriv = nullptr; o.h_by_id = nullptr;
-        double rs = ctx->rscale;
-        if (ctx->use_verlet) {
-            SPHX_TRY(sphx_ensure(ctx, ctx->list64, (size_t)n * 64 * sizeof(int)));
-            SPHX_TRY(sphx_ensure(ctx, ctx->dref, (size_t)n * sizeof(double)));
-            o.list64 = ctx->list64.as<int>();
-            o.dref = ctx->dref.as<double>();
-            rs = ctx->rscale_build;          // wider: the list must hold 64 entries to earn its margin
-        }
-        ctx->knn_hinted = ctx->step_count > 0 && !ctx->use_verlet;     // hprev holds the previous step's radii
-        ctx->knn_lag_external = true;
-        const int rc_knn = sphx_knn(ctx, n, k, r.x.as<double>(), r.y.as<double>(), r.z.as<double>(), r.id.as<int>(),
-                                    ctx->inv.as<int>(), r.hprev.as<double>(), rs, dist, o);
-        ctx->knn_hinted = false;
-        ctx->knn_lag_external = false;
-        SPHX_TRY(rc_knn);
-        if (split) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_perm, 0));    // the rest of the state is in place
-        if (ctx->use_verlet) {
-            SPHX_TRY(sphx_save_list_positions(ctx, n, r.x.as<double>(), r.y.as<double>(), r.z.as<double>()));
-            ctx->list_valid = true;
-            ctx->list_n = n;
-            ctx->list_k = k;
-        }
-        ctx->stats.rebuild_steps++;
-    }
-    StateArrays& s = ctx->st;
+    SPHX_TRY(step_search(ctx, k, dist, ev));
     HIPCHK(hipEventRecord(ev[2], ctx->stream));
-    // the record build (bandwidth-bound) does not depend on the list dedup (latency-bound): side by side - and with
-    // it the sum of h and its copy to the host (the next step's cell size, read there when the next grid is sized;
-    // the search's counters travel in the same copy: SC_HSUM .. SC_BADHINT are consecutive slots)
-    const bool fork = ctx->qorder && ctx->use_lds && !ctx->loop_forms && ctx->side_stream;
-    hipStream_t hs_stream = ctx->stream;
-    if (fork) {
-        HIPCHK(hipStreamWaitEvent(ctx->side_stream, ev[2], 0));       // (the search's end event doubles as the fork)
-        hs_stream = ctx->side_stream;
-    }
-    // (forked: BEHIND the record build on the side stream - the passes wait for that one, not for this; nobody but the
-    //  next step's host code reads the sums)
-    auto h_sums_out = [&]() -> int {
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = hs_stream;
-        const int rc_h = sphx_hsum(ctx, n, s.hprev.as<double>());
-        ctx->stream = main_stream;
-        SPHX_TRY(rc_h);
-        const int hsl = ctx->lag_hslot ^ 1;
-        HIPCHK(hipMemcpyAsync((char*)ctx->pinned + LAG_OFF + 512 * hsl + 256, ctx->scal.as<double>() + SC_HSUM,
-                              (SC_KGDBG + 2 - SC_HSUM + 1) * sizeof(double), hipMemcpyDeviceToHost, hs_stream));
-        HIPCHK(hipEventRecord(ctx->lag_hev[hsl], hs_stream));
-        ctx->lag_halias[hsl] = nullptr;
-        ctx->lag_hvalid[hsl] = true;
-        ctx->lag_hslot = hsl;
-        return SPHX_OK;
-    };
-    if (!fork) SPHX_TRY(h_sums_out());
-    if (ctx->qorder && ctx->use_lds) SPHX_TRY(sphx_blob_translate(ctx, n, k));
-    if (ctx->loop_forms) {
-        // the reference's time loop (drv:451-458): loop forms on this step's neighbour list
-        const bool species = ctx->s > 0 && ctx->fun_id.p;      // the species pass reads hydro_update's records (RecA)
-        if (ctx->drag || species)
-            SPHX_TRY(sphx_prep(ctx, n, s.x.as<double>(), s.y.as<double>(), s.z.as<double>(), nullptr,
-                               s.vx.as<double>(), s.vy.as<double>(), s.vz.as<double>(), nullptr, s.m.as<double>(),
-                               s.hprev.as<double>(), s.T.as<double>(), s.mu.as<double>(), s.gam.as<double>(),
-                               s.ptype.as<double>()));
-        if (detail) HIPCHK(hipEventRecord(ev[3], ctx->stream));
-        SPHX_TRY(sphx_loop_step_sums(ctx, n, k, ctx->loop_d));
-        if (detail) HIPCHK(hipEventRecord(ev[9], ctx->stream));
-        if (species) SPHX_TRY(sphx_step_species(ctx, n, k));       // nsc:624-627 (+ metallicity, AGB yields)
-        if (detail) HIPCHK(hipEventRecord(ev[4], ctx->stream));
-        if (detail) HIPCHK(hipEventRecord(ev[5], ctx->stream));
-        if (ctx->drag)
-            SPHX_TRY(sphx_pass_drag(ctx, n, k, s.m.as<double>(), s.ptype.as<double>(), s.mgm.as<double>(),
-                                    s.mcs.as<double>()));
-    } else {
-    {
-        hipStream_t main_stream = ctx->stream;
-        if (fork) ctx->stream = ctx->side_stream;          // (it is already behind the search: the h sums went there first)
-        const int rc_prep = sphx_prep(ctx, n, s.x.as<double>(), s.y.as<double>(), s.z.as<double>(), nullptr,
-                                      s.vx.as<double>(), s.vy.as<double>(), s.vz.as<double>(), nullptr,
-                                      s.m.as<double>(), s.hprev.as<double>(), s.T.as<double>(), s.mu.as<double>(),
-                                      s.gam.as<double>(), s.ptype.as<double>());
-        ctx->stream = main_stream;
-        if (rc_prep != SPHX_OK) return rc_prep;
-        if (fork) {
-            HIPCHK(hipEventRecord(ctx->ev_join, ctx->side_stream));
-            HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-            SPHX_TRY(h_sums_out());
-        }
-    }
-    if (detail) HIPCHK(hipEventRecord(ev[3], ctx->stream));
-    ctx->lean_outputs = true;          // (nothing in the step reads G: hydro_accel = G / rho is what the update takes)
-    // nsc:624-627 on the step's list (+ metallicity and AGB yields when a table is set): when the state carries f_un -
-    // inside pass 1's kernel where both run out of LDS (their first sweeps are the same), else behind it
-    const bool species = ctx->s > 0 && ctx->fun_id.p;
-    const bool sp_fused = species && ctx->species_fused && ctx->species_lds && ctx->use_lds && ctx->qorder && ctx->blob_lists &&
-                          !ctx->map_perm && ctx->sp == 16 && ctx->s <= 16 && k <= SPHX_MAX_K;
-    int rc_dens;
-    if (sp_fused) {
-        const int S = ctx->s;
-        rc_dens = sphx_ensure(ctx, ctx->rho, (size_t)n * sizeof(double));
-        if (rc_dens == SPHX_OK) rc_dens = sphx_ensure(ctx, ctx->rhod, (size_t)n * sizeof(double));
-        if (rc_dens == SPHX_OK) rc_dens = sphx_ensure(ctx, ctx->nden, (size_t)n * sizeof(double));
-        if (rc_dens == SPHX_OK) rc_dens = sphx_ensure(ctx, ctx->G, (size_t)n * 3 * sizeof(double));
-        if (rc_dens == SPHX_OK) rc_dens = sphx_ensure(ctx, ctx->ha, (size_t)n * 3 * sizeof(double));
-        if (rc_dens == SPHX_OK) rc_dens = sphx_ensure(ctx, ctx->F, (size_t)n * S * sizeof(double));
-        if (rc_dens == SPHX_OK && ctx->agb_on) {
-            rc_dens = sphx_ensure(ctx, ctx->Zmet, (size_t)n * sizeof(double));
-            if (rc_dens == SPHX_OK) rc_dens = sphx_ensure(ctx, ctx->agb_dust, (size_t)n * S * sizeof(double));
-        }
-        if (rc_dens == SPHX_OK)
-            rc_dens = sphx_blob_density_species(ctx, n, k, S, ctx->fun_id.as<double>(), ctx->st.id.as<int>(), ctx->st.m.as<double>(),
-                                                ctx->F.as<double>(), ctx->Zmet.as<double>(), ctx->agb_dust.as<double>(),
-                                                (ctx->agb_on && ctx->Zmet.p && ctx->agb_dust.p) ? 1 : 0);
-    } else {
-        rc_dens = sphx_pass_density(ctx, n, k);
-    }
-    ctx->lean_outputs = false;
-    SPHX_TRY(rc_dens);
-    if (detail) HIPCHK(hipEventRecord(ev[9], ctx->stream));
-    if (species && !sp_fused) SPHX_TRY(sphx_step_species(ctx, n, k));
-    if (detail) HIPCHK(hipEventRecord(ev[4], ctx->stream));
-    if (ctx->visc_mode == 1) {                 // passes 2 + 3 in one (pairwise viscosity): ms_pi stays 0
-        SPHX_TRY(sphx_pass_visc_pw(ctx, n, k, s.m.as<double>()));
-    } else {
-        SPHX_TRY(sphx_pass_pi(ctx, n, k, s.hprev.as<double>(), s.ptype.as<double>()));
-        if (detail) HIPCHK(hipEventRecord(ev[5], ctx->stream));
-        SPHX_TRY(sphx_pass_visc(ctx, n, k, s.m.as<double>()));
-    }
-    if (ctx->drag)
-        SPHX_TRY(sphx_pass_drag(ctx, n, k, s.m.as<double>(), s.ptype.as<double>(), s.mgm.as<double>(),
-                                s.mcs.as<double>()));
-    }
+    SPHX_TRY(step_sums(ctx, k, ev, ev[2], detail));
     if (detail) HIPCHK(hipEventRecord(ev[6], ctx->stream));
+    StateArrays& s = ctx->st;
     if (ctx->gravity) {                          // drv:448-449; softening = median(h), nsc:358
         SPHX_TRY(sphx_ensure(ctx, ctx->grav, (size_t)n * 3 * sizeof(double)));
         double* eps = ctx->scal.as<double>() + SC_GRAV_EPS;

@@ -1021,10 +1021,10 @@ static int blob_launch(sphx_ctx* ctx, Kern kern, int per_slot, size_t extra, int
 // callers' particles that are computed (device API: the owned ones; ghosts, o >= n_active, are candidates only)
 static int blob_n_active(const sphx_ctx* ctx, int64_t n) { return ctx->map_perm ? ctx->map_nactive : (int)n; }
 
-int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k) {
+int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k, bool lean) {
     return blob_launch(ctx, blob_density_kernel, 64, 0, n, k, ctx->clip_grad, ctx->map_perm, blob_n_active(ctx, n),
                        ctx->rec1.as<RecA>(), ctx->rho_s.as<double>(), ctx->rho.as<double>(), ctx->rhod.as<double>(),
-                       ctx->nden.as<double>(), ctx->lean_outputs ? nullptr : ctx->G.as<double>(), ctx->ha.as<double>(),
+                       ctx->nden.as<double>(), lean ? nullptr : ctx->G.as<double>(), ctx->ha.as<double>(),
                        sphx_blob_sel(ctx, ctx->pass_part));
 }
 
@@ -1047,11 +1047,11 @@ int sphx_blob_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m, u64* ct_
 }
 
 // (the weights' registers are sized for K <= 40, else for SPHX_MAX_K: SPEC_MAXM)
-int sphx_blob_density_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted,
-                              double* F, double* Z, double* agb, int agb_on) {
+int sphx_blob_density_species(sphx_ctx* ctx, int64_t n, int k, bool lean, int S, const double* fun, const int* row_of,
+                              const double* m_sorted, double* F, double* Z, double* agb, int agb_on) {
     const auto kern = (KPAD(k) / LPP <= 10) ? blob_density_species_kernel<10> : blob_density_species_kernel<16>;
     return blob_launch(ctx, kern, 64, 0, n, k, ctx->clip_grad, ctx->rec1.as<RecA>(), ctx->rho_s.as<double>(), ctx->rho.as<double>(),
-                       ctx->rhod.as<double>(), ctx->nden.as<double>(), ctx->lean_outputs ? nullptr : ctx->G.as<double>(),
+                       ctx->rhod.as<double>(), ctx->nden.as<double>(), lean ? nullptr : ctx->G.as<double>(),
                        ctx->ha.as<double>(), S, fun, row_of, m_sorted, ctx->agb, agb_on, F, Z, agb);
 }
 

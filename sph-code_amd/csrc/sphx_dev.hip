@@ -46,11 +46,6 @@ __global__ __launch_bounds__(256) void inject_field_kernel(int n, const int* per
     dst[(size_t)t * stride] = src[perm[t]];
 }
 
-#define NEED(p)                                                                              \
-    do {                                                                                     \
-        if (!(p)) return sphx_set_err(ctx, SPHX_E_ARG, "%s: argument %s is NULL", __func__, #p); \
-    } while (0)
-
 // fold the kNN launch time of the last sphx_dev_search into the statistics (events on the library's stream)
 int sphx_dev_collect(sphx_ctx* ctx) {
     if (!ctx->dev_ev_pending) return SPHX_OK;
@@ -88,10 +83,9 @@ extern "C" int sphx_dev_search(sphx_ctx* ctx, int64_t n_total, int64_t n_owned, 
     if (ctx->dev_hmean > 0.0) cell_hint = ctx->cell_factor * sphx_cell_feedback(ctx, n) * ctx->dev_hmean;
     // grid sized from the previous search's box statistics (sphx_grid.hip): the decomposed driver's step
     // then has ONE host wait - its end-of-step scalars - and the host queues the whole step ahead of the GPU
-    ctx->lag_on = true;
-    const int rc_grid = sphx_build_grid(ctx, n, k, x, y, z, cell_hint);
-    ctx->lag_on = false;
-    SPHX_TRY(rc_grid);
+    GridBuildOpts gopts;
+    gopts.lagged = true;
+    SPHX_TRY(sphx_build_grid(ctx, n, k, x, y, z, cell_hint, gopts));
     hipLaunchKernelGGL(gather3_aos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
                        (int)n, ctx->perm.as<int>(), pos, xs, ys, zs, (int*)nullptr);
     HIPCHK(hipGetLastError());
@@ -110,13 +104,15 @@ extern "C" int sphx_dev_search(sphx_ctx* ctx, int64_t n_total, int64_t n_owned, 
     o.nbr = ctx->nbr.as<int>();
     o.h_sorted = nullptr; o.idx64 = nullptr; o.dist = nullptr; o.nontriv = nullptr;
     o.h_by_id = h_out;
-    ctx->knn_hint_by_id = (hint != nullptr);
-    ctx->knn_hinted = (hint != nullptr);
+    KnnIn in;
+    in.xs = xs; in.ys = ys; in.zs = zs;
+    in.id = ctx->perm.as<int>(); in.inv = ctx->inv.as<int>();
+    in.rsearch = hint;                       // (the previous radii, in caller order)
+    in.hinted = in.hint_by_id = (hint != nullptr);
+    in.rscale = rscale > 0.0 ? rscale : ctx->rscale;
+    in.rbound = dist;
     HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
-    int rc = sphx_knn(ctx, n, k, xs, ys, zs, ctx->perm.as<int>(), ctx->inv.as<int>(), hint,
-                      rscale > 0.0 ? rscale : ctx->rscale, dist, o);
-    ctx->knn_hint_by_id = false;
-    ctx->knn_hinted = false;
+    int rc = sphx_knn(ctx, n, k, in, o);
     HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
     ctx->dev_ev_pending = (rc == SPHX_OK);
     if (rc == SPHX_OK && ctx->qorder && ctx->use_lds) rc = sphx_blob_translate(ctx, n, k);
@@ -168,9 +164,10 @@ extern "C" int sphx_dev_prep(sphx_ctx* ctx, const double* pos, const double* vel
     NEED(pos); NEED(vel); NEED(mass); NEED(h); NEED(T); NEED(mu); NEED(gamma); NEED(ptype);
     if (!ctx->map_perm) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_dev_prep before sphx_dev_search");
     HIPCHK(hipSetDevice(ctx->device));
-    ctx->visc_pw = ctx->visc_mode == 1;
-    return sphx_prep(ctx, ctx->n, nullptr, nullptr, nullptr, pos, nullptr, nullptr, nullptr, vel, mass, h, T,
-                     mu, gamma, ptype);
+    PrepIn in;
+    in.pos_aos(pos); in.vel_aos(vel);
+    in.m = mass; in.h = h; in.T = T; in.mu = mu; in.gam = gamma; in.ptype = ptype;
+    return sphx_prep(ctx, ctx->n, in, ctx->visc_mode == 1, ctx->stream);
 }
 
 // A pass writes its results (already in the caller's order, through the OutMap) into context buffers; for
@@ -342,10 +339,29 @@ __global__ __launch_bounds__(256) void dev_integrate_kernel(DevIntegArgs a) {
         sphx_count_bad(a.counters, BAD_STATE, bad_st);
     }
 }
-// the drag terms handed over by sphx_dev_set_drag_terms are consumed by the next update
-static void take_drag_terms(sphx_ctx* ctx, DevIntegArgs& a) {
+// What the three updates below share: the state arrays, the viscous terms, the constants, dt as given (no verdict on the
+// device) and hydro_update's pressure term; each entry point then sets what differs.  The drag terms handed over by
+// sphx_dev_set_drag_terms are consumed.
+static DevIntegArgs dev_integ_args(sphx_ctx* ctx, int64_t n_owned, double* pos, double* vel, double* accel_old, double* E_internal,
+                                   double* T, const double* mass, const double* mu, const double* gamma, const double* ptype,
+                                   const double* ha, const double* va, const double* vh, double dt) {
+    DevIntegArgs a;
+    a.n = (int)n_owned;
+    a.pos = pos; a.vel = vel; a.acc = accel_old; a.E = E_internal; a.T = T;
+    a.m = mass; a.mu = mu; a.gam = gamma; a.ptype = ptype;
+    a.ha = ha; a.va = va; a.vh = vh;
+    a.G = nullptr; a.rho = nullptr;
     a.drag_on = ctx->dev_drag_on; a.drag_re = ctx->dev_drag_re; a.drho = ctx->dev_drag_rho; a.drhod = ctx->dev_drag_rhod;
     ctx->dev_drag_on = ctx->dev_drag_re = ctx->dev_drag_rho = ctx->dev_drag_rhod = nullptr;
+    a.dt = dt; a.m_h = ctx->cst.m_h; a.kB = ctx->cst.k_B; a.lim = ctx->cst.pos_clamp;
+    a.red2 = nullptr; a.dt_out = nullptr; a.first = 0; a.fixed_dt = 0.0; a.dt_0 = ctx->cst.dt_0; a.max_age = ctx->cst.max_age;
+    a.counters = ctx->badc.as<u64>();
+    return a;
+}
+static int dev_integ_launch(sphx_ctx* ctx, const DevIntegArgs& a) {
+    hipLaunchKernelGGL(dev_integrate_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
 }
 // drv:233-238 on (n,3) arrays
 __global__ __launch_bounds__(256) void dev_clamp_kernel(int n3, double lim, double* pos, double* vel) {
@@ -375,19 +391,8 @@ extern "C" int sphx_dev_integrate(sphx_ctx* ctx, int64_t n_owned, double* pos, d
     NEED(ptype); NEED(hydro_accel); NEED(visc_accel); NEED(visc_heat);
     HIPCHK(hipSetDevice(ctx->device));
     if (n_owned < 1) return SPHX_OK;
-    DevIntegArgs a;
-    a.n = (int)n_owned;
-    a.pos = pos; a.vel = vel; a.acc = accel_old; a.E = E_internal; a.T = T;
-    a.m = mass; a.mu = mu; a.gam = gamma; a.ptype = ptype;
-    a.ha = hydro_accel; a.va = visc_accel; a.vh = visc_heat;
-    a.G = nullptr; a.rho = nullptr;
-    take_drag_terms(ctx, a);
-    a.dt = dt; a.m_h = ctx->cst.m_h; a.kB = ctx->cst.k_B; a.lim = ctx->cst.pos_clamp;
-    a.red2 = nullptr; a.dt_out = nullptr; a.first = 0; a.fixed_dt = 0.0; a.dt_0 = ctx->cst.dt_0; a.max_age = ctx->cst.max_age;
-    a.counters = ctx->badc.as<u64>();
-    hipLaunchKernelGGL(dev_integrate_kernel, dim3((unsigned)((n_owned + 255) / 256)), dim3(256), 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    return SPHX_OK;
+    return dev_integ_launch(ctx, dev_integ_args(ctx, n_owned, pos, vel, accel_old, E_internal, T, mass, mu, gamma, ptype,
+                                                hydro_accel, visc_accel, visc_heat, dt));
 }
 
 // The same update with the step's verdict and dt taken on the device: red2 (device) = {1 if some rank's halo
@@ -404,20 +409,10 @@ extern "C" int sphx_dev_integrate_auto(sphx_ctx* ctx, int64_t n_owned, double* p
     NEED(ptype); NEED(hydro_accel); NEED(visc_accel); NEED(visc_heat); NEED(red2); NEED(dt_out);
     HIPCHK(hipSetDevice(ctx->device));
     if (n_owned < 1) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_integrate_auto: n_owned=%lld", (long long)n_owned);
-    DevIntegArgs a;
-    a.n = (int)n_owned;
-    a.pos = pos; a.vel = vel; a.acc = accel_old; a.E = E_internal; a.T = T;
-    a.m = mass; a.mu = mu; a.gam = gamma; a.ptype = ptype;
-    a.ha = hydro_accel; a.va = visc_accel; a.vh = visc_heat;
-    a.G = nullptr; a.rho = nullptr;
-    take_drag_terms(ctx, a);
-    a.dt = 0.0; a.m_h = ctx->cst.m_h; a.kB = ctx->cst.k_B; a.lim = ctx->cst.pos_clamp;
+    DevIntegArgs a = dev_integ_args(ctx, n_owned, pos, vel, accel_old, E_internal, T, mass, mu, gamma, ptype, hydro_accel,
+                                    visc_accel, visc_heat, 0.0);
     a.red2 = red2; a.dt_out = dt_out; a.first = first; a.fixed_dt = fixed_dt;
-    a.dt_0 = ctx->cst.dt_0; a.max_age = ctx->cst.max_age;
-    a.counters = ctx->badc.as<u64>();
-    hipLaunchKernelGGL(dev_integrate_kernel, dim3((unsigned)((n_owned + 255) / 256)), dim3(256), 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    return SPHX_OK;
+    return dev_integ_launch(ctx, a);
 }
 
 // drv:460-491 on the loop forms' outputs (multigpu.py, forms = "loop"): pressure_accel = delp / rho [gas],
@@ -433,20 +428,11 @@ extern "C" int sphx_dev_integrate_loop(sphx_ctx* ctx, int64_t n_owned, double* p
     if (red2 && !dt_out) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_integrate_loop: red2 without dt_out");
     HIPCHK(hipSetDevice(ctx->device));
     if (n_owned < 1) return SPHX_OK;
-    DevIntegArgs a;
-    a.n = (int)n_owned;
-    a.pos = pos; a.vel = vel; a.acc = accel_old; a.E = E_internal; a.T = T;
-    a.m = mass; a.mu = mu; a.gam = gamma; a.ptype = ptype;
-    a.ha = nullptr; a.va = av_accel; a.vh = av_heat;
-    a.G = delp; a.rho = rho;
-    take_drag_terms(ctx, a);
-    a.dt = dt; a.m_h = ctx->cst.m_h; a.kB = ctx->cst.k_B; a.lim = ctx->cst.pos_clamp;
+    DevIntegArgs a = dev_integ_args(ctx, n_owned, pos, vel, accel_old, E_internal, T, mass, mu, gamma, ptype, nullptr, av_accel,
+                                    av_heat, dt);
+    a.G = delp; a.rho = rho;              // (loop-form mode: pressure = delp / rho, ha unused)
     a.red2 = red2; a.dt_out = dt_out; a.first = first; a.fixed_dt = fixed_dt;
-    a.dt_0 = ctx->cst.dt_0; a.max_age = ctx->cst.max_age;
-    a.counters = ctx->badc.as<u64>();
-    hipLaunchKernelGGL(dev_integrate_kernel, dim3((unsigned)((n_owned + 255) / 256)), dim3(256), 0, ctx->stream, a);
-    HIPCHK(hipGetLastError());
-    return SPHX_OK;
+    return dev_integ_launch(ctx, a);
 }
 
 // ---- gas-dust drag (nsc:719-742) on owned + ghost arrays --------------------------------------------------------------

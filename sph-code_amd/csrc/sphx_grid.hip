@@ -426,10 +426,7 @@ extern "C" int sphx_selftest_scan(sphx_ctx* ctx, int n, unsigned seed, long long
         if (single_launch) *single_launch = ((n + 1 + LBS_TILE - 1) / LBS_TILE <= LBS_MAXTILES) ? 1 : 0;
     } while (false);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (in.p) (void)hipFree(in.p);
-    if (o1.p) (void)hipFree(o1.p);
-    if (o2.p) (void)hipFree(o2.p);
-    if (bad.p) (void)hipFree(bad.p);
+    for (DevBuf* b : {&in, &o1, &o2, &bad}) sphx_release(ctx, *b);
     return rc;
 }
 
@@ -582,16 +579,24 @@ __global__ __launch_bounds__(256) void cell_sort_members(int ncells, const int* 
 
 #define SPHX_MAX_CELLS (SCAN_TILE * 4096)
 
-int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const double* y,
-                    const double* z, double cell_hint) {
+int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const double* y, const double* z, double cell_hint,
+                    const GridBuildOpts& opts) {
     double bb[13];
+    // drv:233-238 when the caller asked for it: inside the fused count kernel, or by a launch of its own before any
+    // other kernel of this build reads the positions
+    bool clamp_pending = opts.clamp_vel[0] != nullptr;
+    auto clamp_now = [&]() -> int {
+        if (!clamp_pending) return SPHX_OK;
+        clamp_pending = false;
+        return sphx_clamp(ctx, n, ctx->st);
+    };
     // the statistics window of the robust box as the previous build left it (this build moves it)
     ClipBox clip0;
     clip0.on = ctx->clip_valid ? 1 : 0;
     for (int c = 0; c < 3; ++c) { clip0.lo[c] = ctx->clip_lo[c]; clip0.hi[c] = ctx->clip_hi[c]; }
     bool fused = false;           // this step's statistics come out of the cell-count kernel itself
     int lag_cur = 0;
-    if (ctx->lag_on) {
+    if (opts.lagged) {
         // Fused step loop: this step's statistics are launched and copied out, the grid is sized from
         // the previous step's (already on the host) - the loop never waits for the step it launches.
         // One step of motion makes the box slightly stale, which only steers performance: particles
@@ -606,7 +611,7 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         lag_cur = cur;
         fused = use == prev;
         if (!fused) {
-            if (ctx->clamp_vx) { SPHX_TRY(sphx_clamp(ctx, n, ctx->st)); ctx->clamp_vx = nullptr; }
+            SPHX_TRY(clamp_now());
             SPHX_TRY(bbox_launch(ctx, n, x, y, z, true, slot + 512 * cur));
             HIPCHK(hipEventRecord(ctx->lag_bev[cur], ctx->stream));
             ctx->lag_balias[cur] = nullptr;
@@ -617,11 +622,11 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         ctx->lag_bn[cur] = n;
         ctx->lag_bslot = cur;
     } else {
-        if (ctx->clamp_vx) { SPHX_TRY(sphx_clamp(ctx, n, ctx->st)); ctx->clamp_vx = nullptr; }
+        SPHX_TRY(clamp_now());
         SPHX_TRY(sphx_bbox(ctx, n, x, y, z, bb, true));
     }
     if (ctx->clip_valid && bb[12] < 0.5 * (double)n) {     // the clip box lost the cloud: re-anchor
-        if (ctx->clamp_vx) { SPHX_TRY(sphx_clamp(ctx, n, ctx->st)); ctx->clamp_vx = nullptr; }
+        SPHX_TRY(clamp_now());
         SPHX_TRY(sphx_bbox(ctx, n, x, y, z, bb, false));
     }
     double tmin[3], tmax[3];
@@ -723,7 +728,9 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         FusedCountArgs fa;
         fa.n = (int)n;
         fa.x = const_cast<double*>(x); fa.y = const_cast<double*>(y); fa.z = const_cast<double*>(z);
-        fa.vx = ctx->clamp_vx; fa.vy = ctx->clamp_vy; fa.vz = ctx->clamp_vz;
+        fa.vx = fa.vy = fa.vz = nullptr;
+        if (clamp_pending) { fa.vx = opts.clamp_vel[0]; fa.vy = opts.clamp_vel[1]; fa.vz = opts.clamp_vel[2]; }
+        clamp_pending = false;
         fa.lim = ctx->cst.pos_clamp;
         fa.clip = clip0;
         fa.g = g;
@@ -744,7 +751,6 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         int fb = pb < FUSED_MAXBLOCKS ? pb : FUSED_MAXBLOCKS;
         hipLaunchKernelGGL(grid_count_fused, dim3(fb), dim3(RED_BLOCK), 0, ctx->stream, fa);
         HIPCHK(hipGetLastError());
-        ctx->clamp_vx = nullptr;
         if (pb >= BB_W) {
             bb_fold_blocks = fb; bb_fold_part = part; bb_fold_out = fin;   // folded by cell_scatter's first blocks, copied out there
         } else {
@@ -768,17 +774,15 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         char* slot = (char*)ctx->pinned + LAG_OFF;
         if (!to_host)
             HIPCHK(hipMemcpyAsync(slot + 512 * lag_cur, bb_fold_out, BB_W * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        if (ctx->step_ev1) {
-            ctx->lag_balias[lag_cur] = ctx->step_ev1;          // recorded by the caller a few launches on, before the search
+        if (opts.alias_ev) {
+            ctx->lag_balias[lag_cur] = opts.alias_ev;          // recorded by the caller a few launches on, before the search
         } else {
             HIPCHK(hipEventRecord(ctx->lag_bev[lag_cur], ctx->stream));
             ctx->lag_balias[lag_cur] = nullptr;
         }
     }
-    ctx->cells_unsorted = false;
-    if (ctx->defer_cell_sort) {
-        ctx->cells_unsorted = true;          // sphx_build_blob_order's per-cell pass sorts the members too
-    } else {
+    ctx->cells_unsorted = opts.sort_cells_later;          // (sphx_build_blob_order's per-cell pass sorts the members too)
+    if (!opts.sort_cells_later) {
         hipLaunchKernelGGL(cell_sort_members, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, ctx->stream, nc, start,
                            ctx->perm.as<int>());
     }
@@ -936,7 +940,7 @@ __global__ __launch_bounds__(256) void blob_scatter(int n, GridParams g, BlobBit
 
 // porder[p] = storage index of the p-th particle in blob order; ctx->qorder points at it on success
 // (left nullptr = identity when the code space would be unreasonably large).
-int sphx_build_blob_order(sphx_ctx* ctx, int64_t n) {
+int sphx_build_blob_order(sphx_ctx* ctx, int64_t n, bool defer_scatter) {
     const GridParams g = ctx->grid;
     BlobBits b{0, 0, 0, 0};
     while ((1 << b.bx) < g.nx) ++b.bx;
@@ -986,7 +990,7 @@ int sphx_build_blob_order(sphx_ctx* ctx, int64_t n) {
                            ctx->perm.as<int>());
     ctx->cells_unsorted = false;
     SPHX_TRY(excl_scan_plus_total(ctx, mc, ms, M));
-    if (ctx->defer_blob_scatter) {
+    if (defer_scatter) {
         // the fused loop: the scatter rides in the kernel that permutes the state next (sphx_permute_state), one
         // thread per stored particle there as here
         ctx->blob_scatter_pending = true;

@@ -183,17 +183,17 @@ __global__ __launch_bounds__(256) void hsum_kernel(int n, const double* h, doubl
     }
 }
 #define HSUM_BLOCKS 512
-int sphx_hsum(sphx_ctx* ctx, int64_t n, const double* h) {
+int sphx_hsum(sphx_ctx* ctx, int64_t n, const double* h, hipStream_t stream) {
     double* out = ctx->scal.as<double>() + SC_HSUM;
     double* cnt = ctx->scal.as<double>() + SC_HCNT;
     const bool fresh = ctx->hsum_tmp.p == nullptr;
-    SPHX_TRY(sphx_ensure(ctx, ctx->hsum_tmp, (size_t)(2 * HSUM_BLOCKS + 2) * sizeof(double)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->hsum_tmp, (size_t)(2 * HSUM_BLOCKS + 2) * sizeof(double), stream));
     double* partial = ctx->hsum_tmp.as<double>();
     unsigned* ticket = reinterpret_cast<unsigned*>(partial + 2 * HSUM_BLOCKS);
-    if (fresh) HIPCHK(hipMemsetAsync(ticket, 0, sizeof(double), ctx->stream));
+    if (fresh) HIPCHK(hipMemsetAsync(ticket, 0, sizeof(double), stream));
     int blocks = (int)((n + 255) / 256);
     if (blocks > HSUM_BLOCKS) blocks = HSUM_BLOCKS;
-    hipLaunchKernelGGL(hsum_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (int)n, h, ctx->h_clip, partial, ticket,
+    hipLaunchKernelGGL(hsum_kernel, dim3(blocks), dim3(256), 0, stream, (int)n, h, ctx->h_clip, partial, ticket,
                        out, cnt, ctx->badc.as<u64>());
     HIPCHK(hipGetLastError());
     return SPHX_OK;
@@ -381,11 +381,10 @@ static int up_(sphx_ctx* ctx, DevBuf& b, const void* host, size_t bytes) {
     HIPCHK(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
     return SPHX_OK;
 }
-#define NEEDP(p) do { if (!(p)) return sphx_set_err(ctx, SPHX_E_ARG, "%s: argument %s is NULL", __func__, #p); } while (0)
 
 extern "C" int sphx_dt_rule(sphx_ctx* ctx, int64_t n, const double* ct, const int32_t* first, double* dt) {
     if (!ctx) return SPHX_E_ARG;
-    NEEDP(ct); NEEDP(first); NEEDP(dt);
+    NEED(ct); NEED(first); NEED(dt);
     if (n < 1) return SPHX_OK;
     HIPCHK(hipSetDevice(ctx->device));
     SPHX_TRY(up_(ctx, ctx->in_a, ct, (size_t)n * 8));
@@ -407,7 +406,7 @@ __global__ __launch_bounds__(256) void clamp_aos_kernel(int n3, double lim, doub
 }
 extern "C" int sphx_clamp_arrays(sphx_ctx* ctx, int64_t n, double* points, double* velocities) {
     if (!ctx) return SPHX_E_ARG;
-    NEEDP(points); NEEDP(velocities);
+    NEED(points); NEED(velocities);
     if (n < 1) return SPHX_OK;
     HIPCHK(hipSetDevice(ctx->device));
     const size_t nb3 = (size_t)n * 24;
@@ -431,8 +430,8 @@ extern "C" int sphx_leapfrog(sphx_ctx* ctx, int64_t n, double* points, double* v
                              const double* drag_on_gas, const double* drag_reaction, const double* av_accel,
                              const double* av_heat, double dt) {
     if (!ctx) return SPHX_E_ARG;
-    NEEDP(points); NEEDP(velocities); NEEDP(total_accel); NEEDP(E_internal); NEEDP(T); NEEDP(mass); NEEDP(mu);
-    NEEDP(gamma); NEEDP(ptype); NEEDP(delp); NEEDP(densities); NEEDP(av_accel); NEEDP(av_heat);
+    NEED(points); NEED(velocities); NEED(total_accel); NEED(E_internal); NEED(T); NEED(mass); NEED(mu);
+    NEED(gamma); NEED(ptype); NEED(delp); NEED(densities); NEED(av_accel); NEED(av_heat);
     if ((drag_on_gas != nullptr) != (drag_reaction != nullptr) || (drag_on_gas && !dust_densities))
         return sphx_set_err(ctx, SPHX_E_ARG, "sphx_leapfrog: drag needs drag_on_gas, drag_reaction and dust_densities");
     if (n < 1) return SPHX_OK;

@@ -6,6 +6,7 @@
 #include <string.h>
 #include <math.h>
 #include <float.h>
+#include <vector>
 #include "../../include/sphx.h"
 #include "sphx_agb.h"
 
@@ -138,23 +139,158 @@ struct StateArrays {
 #define SPHX_LDS_KERNELS 16           // room in sphx_ctx::lds_raised (the LDS kernels of sphx_blob.hip and sphx_loopforms.hip: 11)
 
 struct sphx_ctx {
+    // ======== configuration: read from the environment by sphx_create, or set by sphx_set_* / sphx_state_set_* ========
     int device = 0;
-    hipStream_t stream = nullptr;       // stream every launch goes to (own_stream or the caller's)
+    hipStream_t stream = nullptr;       // stream every launch goes to (own_stream or the caller's: sphx_set_stream)
     hipStream_t own_stream = nullptr;
     hipStream_t side_stream = nullptr;  // independent work beside the main chain (record build while the lists are deduplicated)
-    hipEvent_t ev_join = nullptr;
-    hipEvent_t ev_perm = nullptr;       // the state's permutation split over the two streams (sphx_permute_state)
-    double dev_hmean = 0.0;             // device API: mean h of the previous search (cell size)
-    bool knn_hint_by_id = false;        // device API: search-radius hints are in caller order
-    char err[512] = {0};
     sphx_constants cst;
+    char tunables[1024] = {0};          // "NAME=value ..." of every SPHX_* variable sphx_create read (sphx_tunables)
     double rscale = 1.08, cell_factor = 0.55;    // search tuning (sphx_set_tuning)
-    sphx_stats stats;
+    double rscale_build = 1.3;          // search radius factor on list-building steps
+    bool use_verlet = false;            // opt-in (sphx_set_incremental): pays only for slow drift
+    bool use_blob = true;
+    int blob_curve = 0;                 // 0: Hilbert where its code space fits, 1: Morton always (SPHX_BLOB_CURVE)
+    bool use_group = true;              // hinted searches by the lane-per-query grouped kernel (SPHX_KNN_GROUP=0: off)
+    bool use_lds = true;                // run the step loop's passes out of LDS (needs blob order)
+    bool drag_lds = true;
+    bool blob_split_on = true;
+    bool species_lds = true;            // SPHX_SPECIES_LDS=0: the species pass by gathers (sphx_sums.hip) also when blob lists exist
+    bool species_fused = true;          // the step's species pass inside pass 1's kernel (SPHX_SPECIES_FUSED=0: a kernel of its own)
+    int blob_grid = 0;                  // persistent workgroups of the LDS passes (0: not yet derived)
+    int blob_slots = 1 << 20;           // distinct neighbours staged per workgroup (clamped to the image size)
+    int olev_mode = 2;                  // SPHX_OUTLIER_LEVELS: 0 never, 1 whenever a particle lies outside the box, 2 auto
+    // hint distrust (an experiment kept as an option, off by default): skip the grouped kernel and seed every radius
+    // from the local cell counts.  Auto mode enters when the previous hinted search left more than a quarter of its
+    // queries to the general kernel (a diverging run: particles move by several h per step) and leaves once fewer than
+    // 5 % of the radii found lie beyond [0.5, 1.5] x hint.  Measured on the diverged cube: no faster than the grouped
+    // kernel certifying what it can and the list-mode kernel re-seeding the stale hints it meets (DESIGN 5.2c).
+    int distrust_mode = 0;              // SPHX_HINT_DISTRUST: 0 never, 1 always, 2 auto
+    bool cell_feedback = true;          // SPHX_CELL_FEEDBACK=0 switches it off: cells shrink while groups' tiles overflow (sphx_api.hip)
+    double cell_fb_hi = 0.30, cell_fb_lo = 0.10;     // (SPHX_CELL_FB_HI / _LO)
+    int64_t max_cells = 0;              // SPHX_MAX_CELLS: > 0 lowers the limit on grid cells
+    double box_sigmas = 3.0;            // the grid covers mean +- this many standard deviations of the positions (SPHX_BOX_SIGMAS)
+    double h_clip_factor = 8.0;         // h above this many times the previous mean is left out of the mean that sizes the cells (SPHX_HCLIP)
+    double reach_cap = 0.0;             // sphx_dev_set_reach_cap: head-room of a claimed reach limited to this length (0: not)
+    bool timing_detail = false;         // per-pass timing events in sphx_step (sphx_set_timing_detail)
+    int clip_grad = 0;                  // physics option: neighbour-side gradient clipped beyond h_j (sphx_set_clip_grad)
+    int visc_mode = 0;                  // hydro_update-mode viscosity of sphx_step and the sphx_dev_* passes (sphx_set_visc_mode)
+    bool drag = false;                  // gas-dust drag enabled in the step loop (sphx_state_set_drag)
+    int loop_forms = 0;                 // step mode: the loop forms of the reference's time loop (sphx_state_set_loop_forms)
+    double loop_d = 0.0;                // their global d (drv:68)
+    int gravity = 0;                    // 1: direct-sum self-gravity each step (sphx_state_set_gravity)
+    double grav_G = 0.0;
+    int grav_order = 2;                 // multipole order of the tree's cells: 1 monopoles, 2 + second moments (sphx_set_gravity_order)
+    bool grav_per_thread = false;       // SPHX_GRAV_KERNEL=0: tree walk per thread instead of per wave through LDS
+    int grav_ws = 1;                    // well-separatedness of the tree form (cells)
+    // species pass inside the step (nsc:624-627) + per-particle metallicity + fused AGB yields (sphx_state_set_agb)
+    bool agb_on = false;
+    AgbTable agb;
+    double dev_hmean = 0.0;             // device API: mean h of the previous search (cell size; sphx_dev_set_mean_h)
 
+    // ======== state that lives from one C-ABI call to the next ========
+    char err[512] = {0};
+    sphx_stats stats;
     // ---- working set (any particle order) ----
     int64_t n = 0, npad = 0;
     int k = 0, s = 0;
     int sp = 0;                   // doubles per particle of the resident composition rows: s padded to whole 128-B lines
+    bool has_state = false;
+    int64_t step_count = 0;
+    double dt_last = 0.0;
+    // The update writes the new temperatures into alt.T (dead once the state has been permuted) and swaps it with st.T:
+    // what is left in alt.T is T at the instant of the step's sums, in the step's sorted order like rho / nden - P_i = n_i
+    // k_B T_i of ONE instant at no cost to the step (sphx_state_download_pressure).  (st.T and alt.T are then the same two
+    // buffers at the start of every step; the other arrays of st / alt swap roles every step.)
+    bool tprev_valid = false;
+    bool ct_primed = false;             // SC_CT_BITS holds "none yet" (left so by dt_kernel)
+    bool recs_pw = false;         // the records sphx_prep built last feed the pairwise viscous pass (sphx_dev_visc_pairwise checks it)
+    // the K-major list in `nbr` is the caller-order list of the last array-API call with this shape
+    // (a later call may pass neighbor == NULL instead of uploading the same (N, K) int64 array again)
+    bool nbr_api_valid = false;
+    int64_t nbr_api_n = 0;
+    int nbr_api_k = 0;
+    // ---- Verlet refresh (sphx_refresh.hip) ----
+    bool list_valid = false;
+    int64_t list_n = 0;
+    int list_k = 0;
+    // ---- the order of the last search ----
+    const int* map_perm = nullptr;  // device API: sorted -> caller index (nullptr: identity)
+    int map_nactive = 0;            // device API: callers' particles below this are computed
+    // Processing order of the step loop: column p of the neighbour list / thread p of a pass works
+    // on the particle stored at qorder[p].  Storage stays x-fastest by cell (the search walks rows);
+    // the processing order follows the cells along a Morton curve, so a workgroup's particles form
+    // a compact blob and share most of their neighbours (sphx_grid.hip: sphx_build_blob_order).
+    const int* qorder = nullptr;    // nullptr: identity
+    bool blob_lists = false;        // slot lists valid for the current neighbour list
+    // decomposed runs: blobs by what they need from other ranks (sphx_blob.hip: blob_dedup_kernel's bclass)
+    bool blob_split_valid = false;
+    int blob_split_nblk = 0;
+    int pass_part = 0;              // which blobs hydro_update's passes and the record build take: 0 all, 1 interior, 2 boundary
+    bool loop2_interior_done = false;
+    bool dev_ev_pending = false;  // sphx_dev_search recorded ev[1]/ev[2] around its kNN launch: not yet read
+    // device-pointer API: drag terms handed to the next sphx_dev_integrate* call (sphx_dev_set_drag_terms)
+    const double *dev_drag_on = nullptr, *dev_drag_re = nullptr, *dev_drag_rho = nullptr, *dev_drag_rhod = nullptr;
+    // ---- grid ----
+    GridParams grid;
+    const double* tbox = nullptr;   // device: TRUE bounding box {min xyz, max xyz} of the last grid build
+    double tbox_h[6] = {0, 0, 0, 0, 0, 0};   // host copy of the true bounding box the last grid build knew (may lag a step)
+    double clip_lo[3] = {0, 0, 0}, clip_hi[3] = {0, 0, 0};   // statistics window of the robust grid box
+    bool clip_valid = false;
+    double h_clip = 0.0;            // h above this is left out of the mean that sizes the cells (0: none)
+    double cell_scale = 1.0;        // the factor cell_feedback has reached (sphx_cell_feedback)
+    // what a grid build or a blob order left for a later call to finish (outputs of sphx_build_grid / sphx_build_blob_order)
+    bool cells_unsorted = false;         // the per-cell member sort rides in the blob-order pass
+    bool blob_scatter_pending = false;   // the blob order's last scatter rides in the state's permutation
+    BlobBits blob_scatter_bits;
+    const int* blob_scatter_mstart = nullptr;
+    // allocations known to be all zero between uses (nullptr: memset first)
+    bool bbox_ticket_zeroed = false;
+    const void* cell_fill_zeroed = nullptr;   // the cell_fill allocation known to be all zero between grid builds
+    const void* mcount_zeroed = nullptr;   // the blob-count allocation known to be all zero (cleaned by the deferred scatter)
+    int mcount_zeroed_M = 0;
+    const void* fcount_zeroed = nullptr;   // the fail-list allocation whose counter the grid build has zeroed for this step
+    int64_t fcount_zeroed_n = 0;
+    const void* ds_cnt_zeroed = nullptr;
+    const void* olev_fill_zeroed = nullptr;
+    unsigned lbs_epoch[2] = {0u, 0u};
+    // the kernels whose dynamic-LDS limit has been raised on this context's device (sphx_blob.hip: sphx_lds_opt_in)
+    const void* lds_raised[SPHX_LDS_KERNELS] = {nullptr};
+    int n_lds_raised = 0;
+    // ---- what the previous search reported (read a step late) ----
+    // outlier levels (see OutLevels): built for a hinted search when the previous one met enough far queries
+    OutLevels olev;                 // olev.L == 0: not built for the current grid
+    bool olev_ev_valid = false;
+    u64 farq_seen = 0;              // SC_FARQ as last read (the counter only grows)
+    int64_t farq_last = 0;          // far queries met by the previous hinted search
+    int64_t list_len_last = 0;      // queries the previous hinted search left to the general kernel (sizes the list-mode grid)
+    bool knn_lag_valid = false;     // knn_lag holds slots the caller of sphx_knn copied out behind the previous search (KnnIn::lag_external)
+    u64 knn_lag[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // slots SC_NFAILQ .. SC_KGDBG + 2
+    u64 densep_seen = 0;            // SC_DENSEP as last read
+    int64_t densep_last = 0;        // particles in cells of >= DENSE_CELL members at the last grid build the host knows of
+    u64 crowded_seen = 0;           // SC_CROWDED as last read (the counter only grows)
+    int64_t crowded_last = 0;       // cells of 17 .. 512 members at the last grid build the host knows of
+    bool distrust = false;          // hint distrust is on for the next search (distrust_mode)
+    u64 badhint_seen = 0;
+    // ---- timing events of the step loop, and its lagged read-backs ----
+    // The fused step loop never waits for the step it is launching: its timing events live in a
+    // ring (collected two steps late), and the two host read-backs that size the grid - bounding
+    // box statistics and mean h - are taken from the PREVIOUS step's copies (slots in `pinned` at
+    // LAG_OFF; the grid box only steers performance: out-of-box particles are clamped into the
+    // boundary cells, which the search handles exactly).
+    bool ev_detail[3] = {false, false, false};
+    int ev_has07[3] = {0, 0, 0};        // bit 0 / 1: the slot's step recorded its start / end event
+    unsigned ev_pending = 0;            // bit s: ring slot s holds an uncollected step
+    // An event record costs the stream ~10 us: where the fused loop records one anyway right behind a read-back's copy
+    // (the search's start event behind the box statistics, the side stream's join event behind the h sums), the host
+    // waits on that one instead of a record of its own (the alias; nullptr: lag_bev / lag_hev were recorded).
+    hipEvent_t lag_balias[2] = {nullptr, nullptr}, lag_halias[2] = {nullptr, nullptr};
+    bool lag_bvalid[2] = {false, false}, lag_hvalid[2] = {false, false};
+    int64_t lag_bn[2] = {0, 0};
+    int lag_bslot = 0, lag_hslot = 0;
+
+    // ======== device resources: buffers (all from sphx_ensure), events, pinned host scratch ========
+    std::vector<void*> allocs;    // every live allocation of sphx_ensure: what sphx_destroy frees
     DevBuf rec1, recv;            // RecA[n], RecB[n]
     DevBuf rho_s, bc_s, self_s;   // sorted-order compact arrays: rho[n], RecBC[n], RecSelf[n]
     DevBuf drag_on, drag_re;      // (n,3) dust->gas drag and its scatter-added reaction (nsc:719-742)
@@ -166,176 +302,48 @@ struct sphx_ctx {
     DevBuf crowded;                              // cells of 17 .. 512 members, listed by blob_count for cell_sort_crowded
     DevBuf loop_side;                            // loop-form pass 1, LDS form: gamma | dust mass | -1 per particle
     DevBuf ds_cnt, ds_start, ds_ent;             // ordered scatter of the reaction (DragScatter)
-    const void* ds_cnt_zeroed = nullptr;
-    bool drag = false;            // gas-dust drag enabled in the step loop (sphx_state_set_drag)
-    bool dev_ev_pending = false;  // sphx_dev_search recorded ev[1]/ev[2] around its kNN launch: not yet read
-    int loop_forms = 0;           // step mode: the loop forms of the reference's time loop (sphx_state_set_loop_forms)
-    double loop_d = 0.0;          // their global d (drv:68)
     DevBuf lrec_a, lrec_v;        // loop-form records (sphx_loopforms.hip)
-    int clip_grad = 0;            // physics option: neighbour-side gradient clipped beyond h_j (sphx_set_clip_grad)
-    int visc_mode = 0;            // hydro_update-mode viscosity of sphx_step and the sphx_dev_* passes (sphx_set_visc_mode)
-    bool visc_pw = false;         // the records being built feed the pairwise viscous pass (sphx_prep: RecBC.Bw)
-    bool recs_pw = false;         // the records sphx_prep built last were built so (sphx_dev_visc_pairwise checks it)
-    int gravity = 0;              // 1: direct-sum self-gravity each step (sphx_state_set_gravity)
-    double grav_G = 0.0;
     DevBuf grav, grav_sort, grav_tmp;   // (n,3) accelerations, sorted h, radix-sort scratch
     DevBuf grav_pyr, grav_cell;         // cell pyramid (mass, centre of mass), fine cell of each sorted particle
-    int grav_order = 2;                 // multipole order of the tree's cells: 1 monopoles, 2 + second moments (sphx_set_gravity_order)
     DevBuf grav_quad;
-    bool grav_per_thread = false;       // SPHX_GRAV_KERNEL=0: tree walk per thread instead of per wave through LDS
-    int grav_ws = 1;                    // well-separatedness of the tree form (cells)
-    // ---- Verlet refresh (sphx_refresh.hip) ----
-    DevBuf list64, dref, pos0, pos4;   // int32[n][64], f64[n], f64[3n] positions at list build, f64[4n] packed current
-    bool list_valid = false, use_verlet = false;   // opt-in (sphx_set_incremental): pays only for slow drift
-    int64_t list_n = 0;
-    int list_k = 0;
-    double rscale_build = 1.3;          // search radius factor on list-building steps
+    DevBuf list64, dref, pos0, pos4;   // Verlet refresh: int32[n][64], f64[n], f64[3n] positions at list build, f64[4n] packed current
     DevBuf nbr;                   // int32 [k][npad], K-major, -1 = missing
-    const int* map_perm = nullptr;  // device API: sorted -> caller index (nullptr: identity)
-    // Processing order of the step loop: column p of the neighbour list / thread p of a pass works
-    // on the particle stored at qorder[p].  Storage stays x-fastest by cell (the search walks rows);
-    // the processing order follows the cells along a Morton curve, so a workgroup's particles form
-    // a compact blob and share most of their neighbours (sphx_grid.hip: sphx_build_blob_order).
-    const int* qorder = nullptr;    // nullptr: identity
-    DevBuf porder, mcount, mstart;
-    bool use_blob = true;
-    // device-pointer API: drag terms handed to the next sphx_dev_integrate* call (sphx_dev_set_drag_terms)
-    const double *dev_drag_on = nullptr, *dev_drag_re = nullptr, *dev_drag_rho = nullptr, *dev_drag_rhod = nullptr;
-    // species pass inside the step (nsc:624-627) + per-particle metallicity + fused AGB yields (sphx_state_set_agb)
-    bool agb_on = false;
-    AgbTable agb;
+    DevBuf porder, mcount, mstart;      // blob order (qorder points at porder)
     DevBuf agb_knots, Zmet, agb_dust;
-    // the fused loop's first pass (sphx_grid.hip grid_count_fused): clamp + box statistics + cell histogram in one kernel
-    double *clamp_vx = nullptr, *clamp_vy = nullptr, *clamp_vz = nullptr;   // set by the step: the grid build applies drv:233-238
-    bool bbox_ticket_zeroed = false;
-    bool defer_cell_sort = false, cells_unsorted = false;   // the per-cell member sort rides in the blob-order pass
-    bool defer_blob_scatter = false, blob_scatter_pending = false;   // the blob order's last scatter rides in the state's permutation
-    const void* mcount_zeroed = nullptr;   // the blob-count allocation known to be all zero (cleaned by the deferred scatter)
-    int mcount_zeroed_M = 0;
-    BlobBits blob_scatter_bits;
-    const int* blob_scatter_mstart = nullptr;
-    bool species_lds = true;        // SPHX_SPECIES_LDS=0: the species pass by gathers (sphx_sums.hip) also when blob lists exist
-    bool use_group = true;          // hinted searches by the lane-per-query grouped kernel (SPHX_KNN_GROUP=0: off)
-    bool knn_hinted = false;        // set by the callers of sphx_knn whose rsearch holds real previous radii
     DevBuf fail_list;               // queries the grouped kernel hands to the general one (+ their count)
-    // outlier levels (see OutLevels): built for a hinted search when the previous one met enough far queries
-    int olev_mode = 2;              // SPHX_OUTLIER_LEVELS: 0 never, 1 whenever a particle lies outside the box, 2 auto
-    OutLevels olev;                 // olev.L == 0: not built for the current grid
     DevBuf olev_start, olev_fill, olev_list, olev_key;
-    const void* olev_fill_zeroed = nullptr;
-    double tbox_h[6] = {0, 0, 0, 0, 0, 0};   // host copy of the true bounding box the last grid build knew (may lag a step)
-    hipEvent_t olev_ev = nullptr;   // recorded behind the copy of SC_FARQ to the host
-    bool olev_ev_valid = false;
-    u64 farq_seen = 0;              // SC_FARQ as last read (the counter only grows)
-    int64_t farq_last = 0;          // far queries met by the previous hinted search
     DevBuf lbs_state[2];                   // tile words of the look-back scan (sphx_grid.hip), per launching stream
-    unsigned lbs_epoch[2] = {0u, 0u};
-    bool species_fused = true;             // the step's species pass inside pass 1's kernel (SPHX_SPECIES_FUSED=0: a kernel of its own)
     DevBuf cell_rank;                       // the particles' arrival numbers in their cells (grid build)
     DevBuf tie_list;                       // int4 {query slot, rank, index a, index b}: near ties the grouped search leaves to the list-mode launch's tie blocks
-    const void* fcount_zeroed = nullptr;   // the fail-list allocation whose counter the grid build has zeroed for this step
-    int64_t fcount_zeroed_n = 0;
-    int64_t list_len_last = 0;      // queries the previous hinted search left to the general kernel (sizes the list-mode grid)
-    bool knn_lag_external = false;  // the caller copies SC_NFAILQ .. SC_BADHINT out behind the search and hands them back
-    bool knn_lag_valid = false;
-    u64 knn_lag[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // slots SC_NFAILQ .. SC_KGDBG + 2
-    u64 densep_seen = 0;            // SC_DENSEP as last read
-    int64_t densep_last = 0;        // particles in cells of >= DENSE_CELL members at the last grid build the host knows of
-    u64 crowded_seen = 0;           // SC_CROWDED as last read (the counter only grows)
-    bool lean_outputs = false;      // the step loop: the pressure term itself (G; hydro_update returns G / rho) is not stored
-    bool cell_feedback = true;      // SPHX_CELL_FEEDBACK=0 switches it off: cells shrink while groups' tiles overflow (sphx_api.hip)
-    double cell_scale = 1.0, cell_fb_hi = 0.30, cell_fb_lo = 0.10;     // (SPHX_CELL_FB_HI / _LO)
-    int64_t crowded_last = 0;       // cells of 17 .. 512 members at the last grid build the host knows of
-    // hint distrust (an experiment kept as an option, off by default): skip the grouped kernel and seed every radius
-    // from the local cell counts.  Auto mode enters when the previous hinted search left more than a quarter of its
-    // queries to the general kernel (a diverging run: particles move by several h per step) and leaves once fewer than
-    // 5 % of the radii found lie beyond [0.5, 1.5] x hint.  Measured on the diverged cube: no faster than the grouped
-    // kernel certifying what it can and the list-mode kernel re-seeding the stale hints it meets (DESIGN 5.2c).
-    bool distrust = false;
-    u64 badhint_seen = 0;
-    int distrust_mode = 0;          // SPHX_HINT_DISTRUST: 0 never, 1 always, 2 auto
-    int blob_curve = 0;             // 0: Hilbert where its code space fits, 1: Morton always (SPHX_BLOB_CURVE)
     // sphx_blob.hip: per-workgroup distinct-neighbour lists + 16-bit slot lists for the LDS passes
     DevBuf slot16, uniq;
-    bool use_lds = true;            // run the step loop's passes out of LDS (needs blob order)
-    bool blob_lists = false;        // slot lists valid for the current neighbour list
-    // decomposed runs: blobs by what they need from other ranks (sphx_blob.hip: blob_dedup_kernel's bclass).
     // blob_split: int list[nblk] (interior blobs, then boundary blobs), then cnt[3] {interior, boundary, idle}
     DevBuf blob_class, blob_split;
-    bool blob_split_on = true, blob_split_valid = false;
-    int blob_split_nblk = 0;
-    bool loop2_interior_done = false;
-    bool drag_lds = true;
-    int64_t max_cells = 0;          // SPHX_MAX_CELLS: > 0 lowers the limit on grid cells
-    double reach_cap = 0.0;         // sphx_dev_set_reach_cap: head-room of a claimed reach limited to this length (0: not)
-    int pass_part = 0;              // which blobs hydro_update's passes and the record build take: 0 all, 1 interior, 2 boundary
-    // the kernels whose dynamic-LDS limit has been raised on this context's device (sphx_blob.hip: sphx_lds_opt_in)
-    const void* lds_raised[SPHX_LDS_KERNELS] = {nullptr};
-    int n_lds_raised = 0;
-    int blob_grid = 0;              // persistent workgroups of the LDS passes (0: not yet derived)
-    int blob_slots = 1 << 20;       // distinct neighbours staged per workgroup (clamped to the image size)
-    int map_nactive = 0;            // device API: callers' particles below this are computed
     DevBuf rho, rhod, nden, G, Pi, Bw, va, vh, ha, F;
     DevBuf scal;                  // small device scalars: ct bits, dt, counters
-    // ---- grid ----
-    GridParams grid;
-    const double* tbox = nullptr;   // device: TRUE bounding box {min xyz, max xyz} of the last grid build
-    double clip_lo[3] = {0, 0, 0}, clip_hi[3] = {0, 0, 0};   // statistics window of the robust grid box
-    bool clip_valid = false;
-    double box_sigmas = 3.0;        // the grid covers mean +- this many standard deviations of the positions (SPHX_BOX_SIGMAS)
-    double h_clip = 0.0;            // h above this is left out of the mean that sizes the cells (0: none)
-    double h_clip_factor = 8.0;     // ... = this many times the previous mean (SPHX_HCLIP)
-    DevBuf cell_of, cell_start, cell_fill, perm, inv, scan_tmp, bbox_tmp;
-    // ---- host-API staging ----
+    DevBuf cell_of, cell_start, cell_fill, perm, inv, scan_tmp, bbox_tmp;      // grid
+    // host-API staging
     DevBuf in_a, in_b, in_c, in_d, in_e, in_f, in_g, in_h, in_i, in_j, out_a, out_b, out_c;
     DevBuf idx64, dist_out, nontriv, h_api;
-    // ---- simulation state ----
-    StateArrays st, alt;
-    // The update writes the new temperatures into alt.T (dead once the state has been permuted) and swaps it with st.T:
-    // what is left in alt.T is T at the instant of the step's sums, in the step's sorted order like rho / nden - P_i = n_i
-    // k_B T_i of ONE instant at no cost to the step (sphx_state_download_pressure).  (st.T and alt.T are then the same two
-    // buffers at the start of every step; the other arrays of st / alt swap roles every step.)
-    bool tprev_valid = false;
+    StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
-    bool has_state = false;
-    int64_t step_count = 0;
-    double dt_last = 0.0;
-    hipEvent_t ev[10] = {nullptr};
-    // The fused step loop never waits for the step it is launching: its timing events live in a
-    // ring (collected two steps late), and the two host read-backs that size the grid - bounding
-    // box statistics and mean h - are taken from the PREVIOUS step's copies (slots in `pinned` at
-    // LAG_OFF; the grid box only steers performance: out-of-box particles are clamped into the
-    // boundary cells, which the search handles exactly).
-    const void* cell_fill_zeroed = nullptr;   // the cell_fill allocation known to be all zero between grid builds
-    // the K-major list in `nbr` is the caller-order list of the last array-API call with this shape
-    // (a later call may pass neighbor == NULL instead of uploading the same (N, K) int64 array again)
-    bool nbr_api_valid = false;
-    int64_t nbr_api_n = 0;
-    int nbr_api_k = 0;
-    bool ct_primed = false;             // SC_CT_BITS holds "none yet" (left so by dt_kernel)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
     DevBuf hsum_tmp;                    // hsum_kernel's per-block partial sums + its ticket
-    char tunables[1024] = {0};          // "NAME=value ..." of every SPHX_* variable sphx_create read (sphx_tunables)
+    hipEvent_t ev_join = nullptr;
+    hipEvent_t ev_perm = nullptr;       // the state's permutation split over the two streams (sphx_permute_state)
+    hipEvent_t olev_ev = nullptr;   // recorded behind the copy of SC_FARQ to the host
+    hipEvent_t ev[10] = {nullptr};
     hipEvent_t evring[3][10] = {{nullptr}};
-    bool timing_detail = false;         // per-pass timing events in sphx_step (sphx_set_timing_detail)
-    bool ev_detail[3] = {false, false, false};
-    int ev_has07[3] = {0, 0, 0};        // bit 0 / 1: the slot's step recorded its start / end event
-    unsigned ev_pending = 0;            // bit s: ring slot s holds an uncollected step
     hipEvent_t lag_bev[2] = {nullptr, nullptr}, lag_hev[2] = {nullptr, nullptr};
-    // An event record costs the stream ~10 us: where the fused loop records one anyway right behind a read-back's copy
-    // (the search's start event behind the box statistics, the side stream's join event behind the h sums), the host
-    // waits on that one instead of a record of its own (the alias; nullptr: lag_bev / lag_hev were recorded).
-    hipEvent_t lag_balias[2] = {nullptr, nullptr}, lag_halias[2] = {nullptr, nullptr};
-    hipEvent_t step_ev1 = nullptr;      // set by the fused loop around its grid build: the event it records before the search
-    bool lag_on = false;                // set by the fused loop around its grid build
-    bool lag_bvalid[2] = {false, false}, lag_hvalid[2] = {false, false};
-    int64_t lag_bn[2] = {0, 0};
-    int lag_bslot = 0, lag_hslot = 0;
     void* pinned = nullptr;       // small pinned host scratch for scalar read-back
 };
 
 int sphx_set_err(sphx_ctx* ctx, int code, const char* fmt, ...);
-int sphx_ensure(sphx_ctx* ctx, DevBuf& b, size_t bytes);
+// Grow-only: at least `bytes` in b.  Every allocation is entered in ctx->allocs (sphx_destroy frees them all); before an
+// outgrown one is freed the host waits for `in_use_on`, the stream whose queued work may still read it.
+int sphx_ensure(sphx_ctx* ctx, DevBuf& b, size_t bytes, hipStream_t in_use_on);
+static inline int sphx_ensure(sphx_ctx* ctx, DevBuf& b, size_t bytes) { return sphx_ensure(ctx, b, bytes, ctx->stream); }
+void sphx_release(sphx_ctx* ctx, DevBuf& b);      // frees b's allocation now (the caller knows it idle)
 
 #define HIPCHK(expr)                                                                         \
     do {                                                                                     \
@@ -343,6 +351,10 @@ int sphx_ensure(sphx_ctx* ctx, DevBuf& b, size_t bytes);
         if (e_ != hipSuccess)                                                                \
             return sphx_set_err(ctx, SPHX_E_HIP, "%s:%d %s -> %s", __FILE__, __LINE__,       \
                                 #expr, hipGetErrorString(e_));                               \
+    } while (0)
+#define NEED(p)                                                                              \
+    do {                                                                                     \
+        if (!(p)) return sphx_set_err(ctx, SPHX_E_ARG, "%s: argument %s is NULL", __func__, #p); \
     } while (0)
 #define SPHX_TRY(expr)                                                                       \
     do {                                                                                     \
@@ -431,7 +443,9 @@ int sphx_gravity_tree_launch(sphx_ctx* ctx, int64_t n, const double* x, const do
                              double* acc);
 int sphx_dev_collect(sphx_ctx* ctx);
 int sphx_loop_step_sums(sphx_ctx* ctx, int64_t n, int k, double d);
-int sphx_build_blob_order(sphx_ctx* ctx, int64_t n);
+// defer_scatter: the order's last scatter is left to the kernel that permutes the state next (sphx_permute_state finds
+// it in ctx->blob_scatter_pending / _bits / _mstart)
+int sphx_build_blob_order(sphx_ctx* ctx, int64_t n, bool defer_scatter = false);
 // the factor on the cell size for the next grid over n particles (cell_scale, moved one step by the last known dense share)
 static inline double sphx_cell_feedback(sphx_ctx* ctx, int64_t n) {
     if (ctx->cell_feedback && n > 0) {
@@ -442,16 +456,29 @@ static inline double sphx_cell_feedback(sphx_ctx* ctx, int64_t n) {
     return ctx->cell_scale;
 }
 int sphx_blob_translate(sphx_ctx* ctx, int64_t n, int k);
-int sphx_blob_density_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted,
-                              double* F, double* Z, double* agb, int agb_on);
-int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k);
+// lean: the pressure term itself (G; hydro_update returns G / rho in ha) is not stored
+int sphx_blob_density_species(sphx_ctx* ctx, int64_t n, int k, bool lean, int S, const double* fun, const int* row_of,
+                              const double* m_sorted, double* F, double* Z, double* agb, int agb_on);
+int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k, bool lean);
 int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits);
 int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m);
 int sphx_blob_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m, u64* ct_bits);
 int sphx_blob_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted, double* F,
                       double* Z, double* agb, int agb_on);
-int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const double* y,
-                    const double* z, double cell_hint);   // fills grid, cell_start, perm
+struct GridBuildOpts {
+    // the grid is sized from the previous build's box statistics, already on the host; this build's are copied out for
+    // the next one (the fused loop, sphx_dev_search): the host never waits for the step it launches
+    bool lagged = false;
+    // lagged: an event the caller records on the stream a few launches on (before the search); the host then waits on it
+    // for this build's statistics instead of on a record of the build's own (nullptr: the build records lag_bev)
+    hipEvent_t alias_ev = nullptr;
+    // the per-cell member sort is left to sphx_build_blob_order, which the caller runs next (ctx->cells_unsorted says so)
+    bool sort_cells_later = false;
+    // set (all three, vx vy vz): drv:233-238 is applied to ctx->st - positions and these velocities - by the build's first pass
+    double* clamp_vel[3] = {nullptr, nullptr, nullptr};
+};
+int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const double* y, const double* z, double cell_hint,
+                    const GridBuildOpts& opts = GridBuildOpts());   // fills grid, cell_start, perm
 int sphx_excl_scan_int(sphx_ctx* ctx, const int* in, int* out, int n);   // out[0..n] = exclusive prefix sums, out[n] = total (in[n] must be 0)
 // The drag reaction (nsc:741: every particle adds -f to each of its dust neighbours) as an ORDERED scatter: the
 // contributions to a particle are first laid side by side (slices from a count + scan), then added in the order the
@@ -474,6 +501,17 @@ int sphx_blob_drag(sphx_ctx* ctx, int64_t n, int k, bool count_only, const doubl
                    const double* mcs, const int* id, double* onto, const DragScatter& sc);
 int sphx_build_outlier_levels(sphx_ctx* ctx, int64_t n, const double* xs, const double* ys, const double* zs);   // (sorted order)
 // knn
+struct KnnIn {
+    const double *xs, *ys, *zs;          // positions in cell-sorted order
+    const int32_t* id;                   // sorted -> caller index
+    const int32_t* inv = nullptr;
+    const double* rsearch = nullptr;     // search-radius hints (nullable)
+    double rscale = 1.0, rbound = 0.0;
+    bool hinted = false;                 // rsearch holds real previous radii: the grouped kernel may trust them
+    bool hint_by_id = false;             // rsearch is in caller order
+    // the caller copies SC_NFAILQ .. SC_BADHINT out behind the search and hands them back (ctx->knn_lag, knn_lag_valid)
+    bool lag_external = false;
+};
 struct KnnOut {
     int32_t* nbr;       // [k][npad] sorted indices (nullable)
     int32_t* list64 = nullptr;   // [n][64] Verlet candidate list (nullable)
@@ -484,15 +522,18 @@ struct KnnOut {
     int64_t* nontriv;   // (n,) by id (nullable)
     double* h_by_id;    // (n,) by id (nullable)
 };
-int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const double* xs, const double* ys,
-             const double* zs, const int32_t* id, const int32_t* inv, const double* rsearch,
-             double rscale, double rbound, const KnnOut& out);
+int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const KnnIn& in, const KnnOut& out);
 // sums
-int sphx_prep(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z,
-              const double* pos_aos, const double* vx, const double* vy, const double* vz,
-              const double* vel_aos, const double* m, const double* h, const double* T,
-              const double* mu, const double* gam, const double* ptype);
-int sphx_pass_density(sphx_ctx* ctx, int64_t n, int k);
+struct PrepIn {
+    const double *x, *y, *z; int ps;       // position pointers + element stride (1 SoA, 3 AoS)
+    const double *vx, *vy, *vz; int vs;
+    const double *m, *h, *T, *mu, *gam, *ptype;
+    void pos_aos(const double* p) { x = p; y = p + 1; z = p + 2; ps = 3; }
+    void vel_aos(const double* v) { vx = v; vy = v + 1; vz = v + 2; vs = 3; }
+};
+// the records of every pass from `in`, launched on `stream`; pairwise: they feed the pairwise viscous pass (RecBC.Bw)
+int sphx_prep(sphx_ctx* ctx, int64_t n, const PrepIn& in, bool pairwise, hipStream_t stream);
+int sphx_pass_density(sphx_ctx* ctx, int64_t n, int k, bool lean = false);      // lean: G is not stored
 int sphx_pass_pi(sphx_ctx* ctx, int64_t n, int k, const double* h, const double* ptype);
 int sphx_pass_visc(sphx_ctx* ctx, int64_t n, int k, const double* m);
 int sphx_pass_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m);   // passes 2 + 3 fused, visc_mode 1
@@ -508,7 +549,7 @@ int sphx_transpose_nbr(sphx_ctx* ctx, int64_t n, int k, const int64_t* nb_rowmaj
 // integrate / layout helpers (sphx_integrate.hip)
 int sphx_clamp(sphx_ctx* ctx, int64_t n, StateArrays& s);
 int sphx_permute_state(sphx_ctx* ctx, int64_t n, bool split, hipEvent_t after_first);
-int sphx_hsum(sphx_ctx* ctx, int64_t n, const double* h);
+int sphx_hsum(sphx_ctx* ctx, int64_t n, const double* h, hipStream_t stream);
 int sphx_compute_dt(sphx_ctx* ctx, int first, double fixed_dt);
 int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt = 0, int first = 0, double fixed_dt = 0.0);
 int sphx_pass_drag(sphx_ctx* ctx, int64_t n, int k, const double* m, const double* ptype, const double* mgm,

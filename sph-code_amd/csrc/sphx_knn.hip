@@ -751,9 +751,8 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
     }
 }
 
-int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const double* xs, const double* ys,
-             const double* zs, const int32_t* id, const int32_t* inv, const double* rsearch,
-             double rscale, double rbound, const KnnOut& out) {
+int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const KnnIn& in, const KnnOut& out) {
+    const double *xs = in.xs, *ys = in.ys, *zs = in.zs, *rsearch = in.rsearch;
     if (k < 1 || k > SPHX_MAX_K) return sphx_set_err(ctx, SPHX_E_ARG, "k=%d not in 1..%d", k, SPHX_MAX_K);
     if (n < 1 || n > (1ll << 29)) return sphx_set_err(ctx, SPHX_E_ARG, "n=%lld out of range (1..2^29)", (long long)n);
     ctx->nbr_api_valid = false;          // the K-major list is about to be overwritten
@@ -763,16 +762,16 @@ int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const double* xs, const double* ys
     a.npad = (int)sphx_pad64(n);
     a.n_active = ctx->map_perm ? ctx->map_nactive : 0x7FFFFFFF;
     a.x = xs; a.y = ys; a.z = zs;
-    a.id = id; a.inv = inv;
+    a.id = in.id; a.inv = in.inv;
     a.qorder = ctx->qorder;
     a.cell_start = ctx->cell_start.as<int>();
     a.g = ctx->grid;
     a.tbox = ctx->tbox;
     a.rsearch = rsearch;
-    a.hint_by_id = ctx->knn_hint_by_id ? 1 : 0;
-    a.rscale = rscale;
+    a.hint_by_id = in.hint_by_id ? 1 : 0;
+    a.rscale = in.rscale;
     a.tie_list = nullptr; a.tie_count = nullptr; a.tie_cap = 0; a.list_blocks = 0;
-    a.rbound = (rbound > 0.0) ? rbound : INFINITY;
+    a.rbound = (in.rbound > 0.0) ? in.rbound : INFINITY;
     a.nbr = out.nbr;
     a.list64 = out.list64;
     a.dref = out.dref;
@@ -792,13 +791,13 @@ int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const double* xs, const double* ys
                        a.counters;
     // Hinted searches of the step loop and of the device API: the lane-per-query grouped kernel first, then this
     // kernel in list mode for whatever it could not certify (sphx_knn_group.hip).
-    if ((lean || lean2) && ctx->use_group && ctx->knn_hinted && rsearch) {
+    if ((lean || lean2) && ctx->use_group && in.hinted && rsearch) {
         const size_t tile_bytes = (size_t)k * (KNN_PPB + 1) * sizeof(int);
         // What the previous hinted search reported (copied out behind it, on the host long since: no wait): queries it
         // left to the general kernel, far queries (outside the grid box, wide spheres), radii that contradicted their hints
-        // (the fused loop copies these slots out together with its mean-h read-back and hands them over: knn_lag_*)
+        // (the fused loop copies these slots out together with its mean-h read-back and hands them over: in.lag_external)
         const bool lagged = ctx->olev_mode == 2 || ctx->distrust_mode == 2;
-        const bool ext = ctx->knn_lag_external;
+        const bool ext = in.lag_external;
         if (lagged && (ext ? ctx->knn_lag_valid : ctx->olev_ev_valid)) {
             if (!ext) HIPCHK(hipEventSynchronize(ctx->olev_ev));
             const u64* v = ext ? ctx->knn_lag : (const u64*)((const char*)ctx->pinned + 3072);   // slots SC_NFAILQ .. SC_BADHINT

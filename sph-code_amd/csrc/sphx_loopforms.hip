@@ -181,10 +181,6 @@ static int up(sphx_ctx* ctx, DevBuf& b, const void* host, size_t bytes) {
     HIPCHK(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
     return SPHX_OK;
 }
-#define NEED(p)                                                                              \
-    do {                                                                                     \
-        if (!(p)) return sphx_set_err(ctx, SPHX_E_ARG, "%s: argument %s is NULL", __func__, #p); \
-    } while (0)
 
 static int loop_begin(sphx_ctx* ctx, int64_t n, int k, const int64_t* neighbor, LoopArgs* a) {
     if (n < 1 || n > 0x7FFFFFF0ll) return sphx_set_err(ctx, SPHX_E_ARG, "n=%lld out of range", (long long)n);
@@ -831,13 +827,12 @@ __global__ __launch_bounds__(256) void dev_to_caller_kernel(int n, const int* pe
     if (c >= n_active) return;
     for (int q = 0; q < w; ++q) dst[(size_t)c * w + q] = src[(size_t)s * w + q];
 }
-#define NEEDD(p) do { if (!(p)) return sphx_set_err(ctx, SPHX_E_ARG, "%s: argument %s is NULL", __func__, #p); } while (0)
 
 extern "C" int sphx_dev_loop_prep(sphx_ctx* ctx, const double* pos, const double* vel, const double* mass,
                                   const double* T, const double* mu, const double* gamma, const double* ptype,
                                   const double* E_internal, double d) {
     if (!ctx) return SPHX_E_ARG;
-    NEEDD(pos); NEEDD(vel); NEEDD(mass); NEEDD(T); NEEDD(mu); NEEDD(gamma); NEEDD(ptype); NEEDD(E_internal);
+    NEED(pos); NEED(vel); NEED(mass); NEED(T); NEED(mu); NEED(gamma); NEED(ptype); NEED(E_internal);
     if (!ctx->map_perm) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_dev_loop_prep before sphx_dev_search");
     if (!(d > 0.0)) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_loop_prep: d must be positive");
     HIPCHK(hipSetDevice(ctx->device));
@@ -862,7 +857,7 @@ extern "C" int sphx_dev_loop_prep(sphx_ctx* ctx, const double* pos, const double
 extern "C" int sphx_dev_loop_pass1(sphx_ctx* ctx, const double* h_complete, double* rho, double* rho_dust, double* nden,
                                    double* delp) {
     if (!ctx) return SPHX_E_ARG;
-    NEEDD(h_complete);
+    NEED(h_complete);
     if (!ctx->map_perm || !(ctx->loop_d > 0.0)) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_dev_loop_pass1 before sphx_dev_loop_prep");
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t n = ctx->n;
@@ -905,7 +900,7 @@ extern "C" int sphx_dev_loop_pass2_interior(sphx_ctx* ctx) {
 extern "C" int sphx_dev_loop_pass2(sphx_ctx* ctx, const double* rho_complete, double* visc_accel, double* visc_heat,
                                    double* ct_out) {
     if (!ctx) return SPHX_E_ARG;
-    NEEDD(rho_complete);
+    NEED(rho_complete);
     if (!ctx->map_perm || !(ctx->loop_d > 0.0)) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_dev_loop_pass2 before sphx_dev_loop_prep");
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t n = ctx->n;

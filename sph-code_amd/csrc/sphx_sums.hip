@@ -61,22 +61,18 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     a.self[t] = sf;
 }
 
-int sphx_prep(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z,
-              const double* pos_aos, const double* vx, const double* vy, const double* vz,
-              const double* vel_aos, const double* m, const double* h, const double* T,
-              const double* mu, const double* gam, const double* ptype) {
-    SPHX_TRY(sphx_ensure(ctx, ctx->rec1, (size_t)n * sizeof(RecA)));
-    SPHX_TRY(sphx_ensure(ctx, ctx->recv, (size_t)n * sizeof(RecB)));
-    SPHX_TRY(sphx_ensure(ctx, ctx->rho_s, (size_t)n * sizeof(double)));
-    SPHX_TRY(sphx_ensure(ctx, ctx->bc_s, (size_t)n * sizeof(RecBC)));
-    SPHX_TRY(sphx_ensure(ctx, ctx->self_s, (size_t)n * sizeof(RecSelf)));
+int sphx_prep(sphx_ctx* ctx, int64_t n, const PrepIn& in, bool pairwise, hipStream_t stream) {
+    // (`stream` is also what the host waits for before an outgrown record buffer is freed)
+    SPHX_TRY(sphx_ensure(ctx, ctx->rec1, (size_t)n * sizeof(RecA), stream));
+    SPHX_TRY(sphx_ensure(ctx, ctx->recv, (size_t)n * sizeof(RecB), stream));
+    SPHX_TRY(sphx_ensure(ctx, ctx->rho_s, (size_t)n * sizeof(double), stream));
+    SPHX_TRY(sphx_ensure(ctx, ctx->bc_s, (size_t)n * sizeof(RecBC), stream));
+    SPHX_TRY(sphx_ensure(ctx, ctx->self_s, (size_t)n * sizeof(RecSelf), stream));
     PrepArgs a;
     a.n = (int)n;
-    if (pos_aos) { a.x = pos_aos; a.y = pos_aos + 1; a.z = pos_aos + 2; a.ps = 3; }
-    else { a.x = x; a.y = y; a.z = z; a.ps = 1; }
-    if (vel_aos) { a.vx = vel_aos; a.vy = vel_aos + 1; a.vz = vel_aos + 2; a.vs = 3; }
-    else { a.vx = vx; a.vy = vy; a.vz = vz; a.vs = 1; }
-    a.m = m; a.h = h; a.T = T; a.mu = mu; a.gam = gam; a.ptype = ptype;
+    a.x = in.x; a.y = in.y; a.z = in.z; a.ps = in.ps;
+    a.vx = in.vx; a.vy = in.vy; a.vz = in.vz; a.vs = in.vs;
+    a.m = in.m; a.h = in.h; a.T = in.T; a.mu = in.mu; a.gam = in.gam; a.ptype = in.ptype;
     a.kB = ctx->cst.k_B; a.amu = ctx->cst.amu;
     a.ra = ctx->rec1.as<RecA>();
     a.rb = ctx->recv.as<RecB>();
@@ -85,9 +81,9 @@ int sphx_prep(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const 
     a.perm = ctx->map_perm;
     a.which = ctx->map_perm ? ctx->pass_part : 0;
     a.n_active = ctx->map_nactive;
-    a.pairwise = ctx->visc_pw ? 1 : 0;
-    ctx->recs_pw = ctx->visc_pw;
-    hipLaunchKernelGGL(prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    a.pairwise = pairwise ? 1 : 0;
+    ctx->recs_pw = pairwise;
+    hipLaunchKernelGGL(prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
     HIPCHK(hipGetLastError());
     return SPHX_OK;
 }
@@ -172,18 +168,18 @@ __global__ __launch_bounds__(256) void pass_density_kernel(int n, int npad, int 
     ha[3 * (size_t)o + 2] = -gz / s_rho;
 }
 
-int sphx_pass_density(sphx_ctx* ctx, int64_t n, int k) {
+int sphx_pass_density(sphx_ctx* ctx, int64_t n, int k, bool lean) {
     SPHX_TRY(sphx_ensure(ctx, ctx->rho, (size_t)n * sizeof(double)));
     SPHX_TRY(sphx_ensure(ctx, ctx->rhod, (size_t)n * sizeof(double)));
     SPHX_TRY(sphx_ensure(ctx, ctx->nden, (size_t)n * sizeof(double)));
     SPHX_TRY(sphx_ensure(ctx, ctx->G, (size_t)n * 3 * sizeof(double)));
     SPHX_TRY(sphx_ensure(ctx, ctx->ha, (size_t)n * 3 * sizeof(double)));
-    if (ctx->qorder && ctx->blob_lists) return sphx_blob_density(ctx, n, k);
+    if (ctx->qorder && ctx->blob_lists) return sphx_blob_density(ctx, n, k, lean);
     hipLaunchKernelGGL(pass_density_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
                        (int)n, (int)sphx_pad64(n), k, ctx->clip_grad, ctx->nbr.as<int>(), ctx->rec1.as<RecA>(),
                        ctx->rho_s.as<double>(), ctx->qorder, OutMap{ctx->map_perm, ctx->map_perm ? ctx->map_nactive : (int)n},
                        ctx->rho.as<double>(), ctx->rhod.as<double>(), ctx->nden.as<double>(),
-                       ctx->lean_outputs ? nullptr : ctx->G.as<double>(), ctx->ha.as<double>());
+                       lean ? nullptr : ctx->G.as<double>(), ctx->ha.as<double>());
     HIPCHK(hipGetLastError());
     return SPHX_OK;
 }
