@@ -338,6 +338,64 @@ int sphx_state_download(sphx_ctx* ctx, double* pos, double* vel, double* accel,
  * T of sphx_state_download is the UPDATED temperature, drv:491; the one the sums read is kept by the update at no cost.)
  * Zeros before the first step.  Same caveat as rho / nden above about array calls on the same context.            */
 int sphx_state_download_pressure(sphx_ctx* ctx, double* pressure);
+/* ---- fields at arbitrary points: nsc.neighbors_arb, density_arb, dust_density_arb, temperature_arb,
+ *      dust_temperature_arb, photoionization_arb                                nsc:1422-1527 ----- *
+ * With C = 315/(64 pi), h(m) = (m/m_0)^(1/3) d, r = |x_k - x_0| for query point x_0 and particle k:
+ *   Wg_k = m_k C h(m_k)^-9 (h(m_k)^2 - r^2)^3 (nsc:673-676),  Wd_k = the same with s_k = sizes[k] (nsc:678-681),
+ *   g_k = [type_k == 0], u_k = [type_k == 2]; neither weight is clipped, the "> 0" masks below do that.
+ * Over the members k of the point's ball (nsc:1422-1426), and 0 from every function when the ball has at most one
+ * member (nsc:1432):
+ *   density          sum of the positive Wg g                                            nsc:1428-1443
+ *   dust_density     sum of the positive Wd u                                            nsc:1445-1461
+ *   temperature      nan_to_num(sum a / sum b) over a = Wg g T > 0, b = Wg g             nsc:1463-1486
+ *   dust_temperature nan_to_num(sum Wd u T / sum Wd u) over Wd u > 0                     nsc:1488-1508
+ *   photoionization  sum w nan_to_num(value) / sum w over w = (1 - r^2/h^2)^3 g n_part > 0; 0/0 stays NaN  nsc:1510-1527
+ * sphx_arb_fields (nsc:1422-1527), grid form: the ball is the EXACT set |x_k - x_0| <= radius (the reference asks
+ * cKDTree for eps = 0.1, whose answer depends on the tree's traversal); radius <= 0: max(sizes).  points (n,3), mass,
+ * particle_type (n,); sizes, T, n_part, value (n,) may be NULL, which skips the outputs that need them (value = the
+ * reference's `photoionization` argument).  arb_points (m,3); a point with a NaN or inf coordinate gets count 0 and zeros.
+ * Outputs (m,), any may be NULL.  count: the ball's members; NULL: only min(count, 2) is formed.  *candidates: pair
+ * evaluations performed.  The same inputs give the same bits on every call, in whatever order the points are given.
+ * m = 0 writes nothing.  SPHX_E_ARG: m < 0, n < 1, a NULL required pointer, radius <= 0 without sizes.
+ * ball_id != 0 names the ball: the caller promises that every call with this id on this context is given the same points
+ * and arb_points.  The context keeps the last ball's geometry on the device - the particles' cell list and sorted
+ * positions, the query points and their sorted order - and a call that names it again neither uploads points and
+ * arb_points nor rebuilds any of that: only mass ... value go up and the records and sums are formed (the reference's
+ * five functions are called one after the other on one list, nsc:1428-1527).  Without any field output (count alone)
+ * no record and no sum is formed at all.  ball_id = 0: nothing is kept.  One ball is held at a time; sphx_arb_fields_list
+ * drops it, sphx_state_sample replaces it with an unnamed one.
+ * One reading differs from the list form: temperature and photoionization also demand a positive weight of their
+ * terms.  With T_k < 0 (n_part_k < 0) the reference's masks pass particles OUTSIDE their own support, anywhere in the
+ * ball; the grid form's cost follows the supports, so it leaves them out.  Nothing changes for T >= 0, n_part >= 0. */
+int sphx_arb_fields(sphx_ctx* ctx, int64_t n, const double* points, const double* mass,
+                    const double* particle_type, const double* sizes, const double* T, const double* n_part,
+                    const double* value, double d, int64_t m, const double* arb_points, double radius,
+                    double* density, double* dust_density, double* temperature, double* dust_temperature,
+                    double* photoionization, int64_t* count, int64_t* candidates, int64_t ball_id);
+/* sphx_arb_fields_list (nsc:1428-1527), list form: the balls are given, as CSR - row_start (m+1) int64, non-decreasing
+ * (else SPHX_E_ARG), members int64 particle ids; an id < 0 or >= n is skipped.  Each row is summed in list order, every
+ * listed particle counts (no radius), count = the row's length.  This honours a list made elsewhere exactly - the
+ * reference's own eps = 0.1 lists included.                                                                         */
+int sphx_arb_fields_list(sphx_ctx* ctx, int64_t n, const double* points, const double* mass,
+                         const double* particle_type, const double* sizes, const double* T, const double* n_part,
+                         const double* value, double d, int64_t m, const double* arb_points,
+                         const int64_t* row_start, const int64_t* members, double* density, double* dust_density,
+                         double* temperature, double* dust_temperature, double* photoionization, int64_t* count,
+                         int64_t* candidates);
+/* sphx_state_sample (nsc:1422-1527): sphx_arb_fields' grid form on the step loop's device-resident state - the positions,
+ * masses, types, T and sizes sphx_state_download would return at this moment; n_part, value (n,) in the caller's
+ * particle order, or NULL.  SPHX_E_STATE before the first sphx_step (sizes do not exist yet).  The loop is not disturbed:
+ * the next sphx_step gives the bits it would have given without this call.  Its work buffers are shared with the array
+ * entry points: the caveat at sphx_state_download (rho, nden, visc_heat) applies.                                    */
+int sphx_state_sample(sphx_ctx* ctx, double d, const double* n_part, const double* value, int64_t m,
+                      const double* arb_points, double radius, double* density, double* dust_density,
+                      double* temperature, double* dust_temperature, double* photoionization, int64_t* count,
+                      int64_t* candidates);
+/* Device time of the last of the three calls above on this context, from HIP events on its stream, in ms:
+ * ms[0] inputs going up, ms[1] reductions, grid build, query sort, records (host waits between them included),
+ * ms[2] the sum and gate kernels (list form: the row kernel), ms[3] outputs coming back.  Measurement aid for
+ * nsc:1422-1527's replacement; replaces nothing in the reference.                                                   */
+int sphx_arb_last_timing(sphx_ctx* ctx, double ms[4]);
 int sphx_get_stats(sphx_ctx* ctx, sphx_stats* out);
 int sphx_reset_stats(sphx_ctx* ctx);
 

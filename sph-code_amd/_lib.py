@@ -80,6 +80,10 @@ SIGNATURES = {
     "sphx_step": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double]),
     "sphx_state_download": (C.c_int, [_P] + [_D] * 10),
     "sphx_state_download_pressure": (C.c_int, [_P, _D]),
+    "sphx_arb_fields": (C.c_int, [_P, C.c_int64] + [_D] * 7 + [C.c_double, C.c_int64, _D, C.c_double] + [_D] * 5 + [_I, _I, C.c_int64]),
+    "sphx_arb_last_timing": (C.c_int, [_P, _D]),
+    "sphx_arb_fields_list": (C.c_int, [_P, C.c_int64] + [_D] * 7 + [C.c_double, C.c_int64, _D, _I, _I] + [_D] * 5 + [_I, _I]),
+    "sphx_state_sample": (C.c_int, [_P, C.c_double, _D, _D, C.c_int64, _D, C.c_double] + [_D] * 5 + [_I, _I]),
     "sphx_get_stats": (C.c_int, [_P, C.POINTER(SphxStats)]),
     "sphx_reset_stats": (C.c_int, [_P]),
     "sphx_set_stream": (C.c_int, [_P, C.c_void_p]),

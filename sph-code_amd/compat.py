@@ -28,6 +28,8 @@ Documented differences from the reference:
   * rows with missing neighbours (index == N) contribute zero instead of raising.
   * mass / f_un arrive as longdouble from the driver and are cast to float64.
 """
+import itertools
+
 import numpy as np
 
 from . import _lib
@@ -351,3 +353,169 @@ def leapfrog(points, velocities, total_accel, E_internal, mass, mu_array, gamma_
     c.check(c.lib.sphx_leapfrog(c.h, n, dp(p), dp(v), dp(tot), dp(old), dp(E), dp(T), dp(m), dp(mu), dp(gam), dp(pt),
                                 dp(gr), dp(G), dp(rho), dp(rd), dp(don), dp(dre), dp(ava), dp(avh), float(dt)))
     return p, v, tot, E, T
+
+
+# ==============================================================================================
+# Fields at arbitrary points (nsc:1418-1529): the "very high-resolution graphs for publication"
+# ==============================================================================================
+ARB_FIELDS = ("density", "dust_density", "temperature", "dust_temperature", "photoionization")
+
+
+class _ArbRow:
+    """handle[j]: stands for the j-th ball where only its length is asked for (nsc:1432: len(narb[j]) > 1)."""
+    __slots__ = ("n",)
+
+    def __init__(self, n):
+        self.n = int(n)
+
+    def __len__(self):
+        return self.n
+
+
+class ArbBall:
+    """What neighbors_arb returns instead of nsc:1422-1426's list of lists: the particle positions, the query points
+    and the ball radius R = max(sizes).  The ball itself is never stored - the *_arb functions given a handle evaluate
+    the exact (eps = 0) ball on the device's cell grid.  The first call on a handle builds the particles' cell list and
+    sorts the query points; the library keeps both on the device under the handle's id, so the calls that follow on the
+    same handle (the reference calls its five functions one after the other) upload the per-particle scalars alone and
+    go straight to the sums (include/sphx.h sphx_arb_fields, ball_id).  One handle is held at a time: alternating
+    between two handles rebuilds.  The handle is for the positions and points it was made with: the functions refuse
+    other ones, and arrays changed in place afterwards need a new handle.  (Pass the very arrays the handle was made
+    with: they are recognised by identity.  An equal copy is compared element by element, an O(N + M) pass over
+    host memory on every call.)
+    len(handle) == M; len(handle[j]) is the exact member count (counted for all points on first use, no sums formed).
+    Counting is a call of its own with its own cell size (it knows no masses), so it replaces the ball the library
+    holds: ask for the counts before or after the five field calls, not between them - or take "count" from
+    arb_fields(..., with_stats=True), which fills the handle's counts on the way."""
+    _ids = itertools.count(1)
+
+    def __init__(self, points, arb_points, radius):
+        self.points = f64(points)
+        self.arb_points = f64(arb_points).reshape(-1, 3)
+        self.radius = float(radius)
+        self.ball_id = next(ArbBall._ids)
+        self._counts = None
+
+    def __len__(self):
+        return self.arb_points.shape[0]
+
+    def _check(self, pts, q):
+        for mine, theirs, what in ((self.points, pts, "points"), (self.arb_points, q, "arb_points")):
+            if mine is not theirs and not (mine.shape == theirs.shape and np.array_equal(mine, theirs, equal_nan=True)):
+                raise ValueError("%s are not the ones this neighbors_arb handle was made for" % what)
+
+    @property
+    def counts(self):
+        if self._counts is None:
+            n, m = self.points.shape[0], len(self)
+            cnt = np.zeros(m, np.int64)
+            cand = np.zeros(1, np.int64)
+            ones, zeros = np.ones(n), np.zeros(n)          # (required arguments; only the cell size is drawn from them)
+            c = context()
+            c.check(c.lib.sphx_arb_fields(c.h, n, dp(self.points), dp(ones), dp(zeros), None, None, None, None,
+                                          self.radius / 2.0, m, dp(self.arb_points), self.radius, None, None, None, None,
+                                          None, ip(cnt), ip(cand), 0))
+            self._counts = cnt
+        return self._counts
+
+    def __getitem__(self, j):
+        return _ArbRow(self.counts[j])
+
+
+def neighbors_arb(points, arb_points, sizes):
+    """nsc:1422-1426 -> ArbBall (the exact ball of radius max(sizes); the reference asks cKDTree for eps = 0.1)."""
+    pts = f64(points)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("points must be (N, 3)")
+    return ArbBall(pts, arb_points, np.max(f64(sizes)))
+
+
+def _arb_csr(narb, m):
+    """any sequence of index sequences (what nsc.neighbors_arb returns) -> CSR (row_start (m+1), members) int64."""
+    if len(narb) != m:
+        raise ValueError("narb has %d rows for %d arb_points" % (len(narb), m))
+    lens = np.fromiter((len(r) for r in narb), dtype=np.int64, count=m)
+    row_start = np.zeros(m + 1, np.int64)
+    np.cumsum(lens, out=row_start[1:])
+    members = np.empty(int(row_start[-1]), np.int64)
+    for j, r in enumerate(narb):
+        members[row_start[j]:row_start[j + 1]] = r
+    return row_start, members
+
+
+def arb_fields(points, arb_points, mass, particle_type, narb, sizes=None, T=None, N_PART=None, photoionization=None,
+               d=None, fields=ARB_FIELDS, with_stats=False):
+    """Every requested field of nsc:1428-1527 in ONE pass over the balls -> dict of (M,) arrays (what the five *_arb
+    functions below call with one field each).  narb: an ArbBall (grid form, exact ball) or any sequence of index
+    sequences (list form, honoured as given).  A field whose inputs are missing raises ValueError.
+    with_stats: the dict also carries "count" (M,) int64 and "candidates" (pair evaluations)."""
+    pts = f64(points)
+    n = pts.shape[0]
+    q = f64(arb_points).reshape(-1, 3)
+    m = q.shape[0]
+    opt = lambda a: None if a is None else f64(a, (n,))
+    ms, pt, sz, Tt, npart, val = f64(mass, (n,)), f64(particle_type, (n,)), opt(sizes), opt(T), opt(N_PART), opt(photoionization)
+    need = {"density": (), "dust_density": (sz,), "temperature": (Tt,), "dust_temperature": (sz, Tt),
+            "photoionization": (npart, val)}
+    out = {}
+    for f in fields:
+        if f not in need:
+            raise ValueError("unknown field %r (one of %s)" % (f, ", ".join(ARB_FIELDS)))
+        if any(a is None for a in need[f]):
+            raise ValueError("field %r needs inputs that were not given" % f)
+        out[f] = np.zeros(m)
+    ptrs = [dp(out.get(f)) for f in ARB_FIELDS]
+    cnt = np.zeros(m, np.int64) if with_stats else None
+    cand = np.zeros(1, np.int64)
+    c = context()
+    if isinstance(narb, ArbBall):
+        narb._check(pts, q)
+        c.check(c.lib.sphx_arb_fields(c.h, n, dp(pts), dp(ms), dp(pt), dp(sz), dp(Tt), dp(npart), dp(val), _d(d), m, dp(q),
+                                      narb.radius, *ptrs, ip(cnt), ip(cand), narb.ball_id))
+        if with_stats and narb._counts is None:
+            narb._counts = cnt.copy()
+    else:
+        row_start, members = _arb_csr(narb, m)
+        c.check(c.lib.sphx_arb_fields_list(c.h, n, dp(pts), dp(ms), dp(pt), dp(sz), dp(Tt), dp(npart), dp(val), _d(d), m,
+                                           dp(q), ip(row_start), ip(members), *ptrs, ip(cnt), ip(cand)))
+    if with_stats:
+        out["count"] = cnt
+        out["candidates"] = int(cand[0])
+    return out
+
+
+def density_arb(points, arb_points, mass, particle_type, narb, d=None):
+    """nsc:1428-1443."""
+    return arb_fields(points, arb_points, mass, particle_type, narb, d=d, fields=("density",))["density"]
+
+
+def dust_density_arb(points, arb_points, mass, particle_type, sizes, narb, d=None):
+    """nsc:1445-1461."""
+    return arb_fields(points, arb_points, mass, particle_type, narb, sizes=sizes, d=d,
+                      fields=("dust_density",))["dust_density"]
+
+
+def temperature_arb(points, arb_points, mass, particle_type, T, narb, d=None):
+    """nsc:1463-1486."""
+    return arb_fields(points, arb_points, mass, particle_type, narb, T=T, d=d, fields=("temperature",))["temperature"]
+
+
+def dust_temperature_arb(points, arb_points, mass, particle_type, sizes, T, narb, d=None):
+    """nsc:1488-1508."""
+    return arb_fields(points, arb_points, mass, particle_type, narb, sizes=sizes, T=T, d=d,
+                      fields=("dust_temperature",))["dust_temperature"]
+
+
+def photoionization_arb(points, arb_points, mass, N_PART, photoionization, particle_type, narb, d=None):
+    """nsc:1510-1527."""
+    return arb_fields(points, arb_points, mass, particle_type, narb, N_PART=N_PART, photoionization=photoionization,
+                      d=d, fields=("photoionization",))["photoionization"]
+
+
+def arb_last_timing():
+    """Device time of the last *_arb / arb_fields call of this module, from HIP events (include/sphx.h
+    sphx_arb_last_timing) -> dict of ms: upload, build, kernels, download."""
+    out = np.zeros(4)
+    c = context()
+    c.check(c.lib.sphx_arb_last_timing(c.h, dp(out)))
+    return dict(zip(("upload", "build", "kernels", "download"), out.tolist()))

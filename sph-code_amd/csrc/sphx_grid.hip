@@ -579,6 +579,9 @@ __global__ __launch_bounds__(256) void cell_sort_members(int ncells, const int* 
 
 #define SPHX_MAX_CELLS (SCAN_TILE * 4096)
 
+// (sphx_state_sample, sphx_arb.hip, calls this between two steps and puts back every host-side field of the context this
+//  function writes - grid, tbox, tbox_h, clip_lo / clip_hi / clip_valid, olev.L, cells_unsorted, stats.cells / cell_size: a
+//  field added here belongs on that list too)
 int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const double* y, const double* z, double cell_hint,
                     const GridBuildOpts& opts) {
     double bb[13];

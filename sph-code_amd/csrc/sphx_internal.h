@@ -325,6 +325,18 @@ struct sphx_ctx {
     // host-API staging
     DevBuf in_a, in_b, in_c, in_d, in_e, in_f, in_g, in_h, in_i, in_j, out_a, out_b, out_c;
     DevBuf idx64, dist_out, nontriv, h_api;
+    // arbitrary-point sampling (sphx_arb.hip): records, wide records, wide flags + offsets, per-cell largest support,
+    // query points, their keys / order, sort scratch (list form: the members), per-point sums, outputs, small scalars
+    DevBuf arb_rec, arb_wrec, arb_flag, arb_cmax, arb_q, arb_key, arb_tmp, arb_acc, arb_out, arb_red;
+    // ... and the geometry of the last grid-form call, in buffers of its own (no other entry point writes them): sorted
+    // positions (SoA, 3n), cell_start, perm.  With arb_ball_id != 0 it is the ball of that id (sphx_arb_fields): a later
+    // call with the same id, n and m reuses it together with the query points in arb_q and their sorted order in arb_key.
+    DevBuf arb_pos, arb_cs, arb_perm;
+    int64_t arb_ball_id = 0, arb_ball_n = 0, arb_ball_m = 0;
+    GridParams arb_g;
+    double arb_tb[6] = {0, 0, 0, 0, 0, 0};
+    double arb_ms[4] = {0, 0, 0, 0};            // sphx_arb_last_timing
+    hipEvent_t arb_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket

@@ -203,3 +203,18 @@ def two_phase(n, seed=12351, dust_frac=0.10, **kw):
 
 WORKLOADS = {"two_phase": two_phase, "dusty_sphere": dusty_sphere, "uniform_sphere": uniform_sphere, "polytrope": polytrope_sphere, "sedov": sedov_sphere,
              "uniform_cube": uniform_cube}
+
+
+def slice_points(center, normal_axis, extent, shape):
+    """A regular planar grid of query points for Simulation.sample / compat.*_arb: the plane through `center` normal
+    to axis `normal_axis` (0, 1, 2), `extent` (one length or a pair) wide along the two remaining axes in ascending
+    order, sampled at shape = (H, W) points including both edges -> (H, W, 3); index [i, j] steps the first remaining
+    axis with i, the second with j."""
+    center = np.asarray(center, dtype=np.float64)
+    ext = np.broadcast_to(np.asarray(extent, dtype=np.float64), (2,))
+    ua, va = [a for a in range(3) if a != int(normal_axis)]
+    q = np.empty((int(shape[0]), int(shape[1]), 3))
+    q[...] = center
+    q[..., ua] = (center[ua] + np.linspace(-0.5, 0.5, int(shape[0])) * ext[0])[:, None]
+    q[..., va] = (center[va] + np.linspace(-0.5, 0.5, int(shape[1])) * ext[1])[None, :]
+    return q

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import dp, f64
-from .compat import visc_mode_code
+from .compat import ARB_FIELDS, visc_mode_code
 
 log = logging.getLogger("sph_code_amd")
 
@@ -126,6 +126,51 @@ class Simulation:
         out["pressure"] = np.empty(n)
         c.check(c.lib.sphx_state_download_pressure(c.h, dp(out["pressure"])))
         return out
+
+    SAMPLE_FIELDS = ARB_FIELDS
+
+    def sample(self, arb_points, d, fields=("density", "dust_density", "temperature", "dust_temperature"),
+               n_part=None, value=None, radius=0.0, with_stats=False):
+        """The fields of nsc:1428-1527 at arbitrary points, from the state as it is on the device (include/sphx.h
+        sphx_state_sample; after the first step).  arb_points (..., 3) -> dict of arrays of shape (...): a (H, W, 3)
+        slice gives images.  d: the driver's global d (drv:68).  "photoionization" needs n_part and value, (N,) in the
+        particle order of the uploaded state.  radius <= 0: the ball radius is max(sizes).  The step loop is not
+        disturbed.  with_stats: also "count" (...) int64 and "candidates".
+        "temperature" and "photoionization" count a particle only inside its own support (include/sphx.h
+        sphx_arb_fields): nothing else for T >= 0.  A particle with T < 0 drops out of "temperature" (the result
+        is the reference's formula on max(T, 0)) - and forms="hydro_update" leaves negative temperatures behind from the
+        second step on; forms="loop" keeps T positive."""
+        q = f64(arb_points)
+        if q.ndim < 1 or q.shape[-1] != 3:
+            raise ValueError("arb_points must be (..., 3)")
+        shape = q.shape[:-1]
+        q = np.ascontiguousarray(q.reshape(-1, 3))
+        m = q.shape[0]
+        for f in fields:
+            if f not in self.SAMPLE_FIELDS:
+                raise ValueError("unknown field %r (one of %s)" % (f, ", ".join(self.SAMPLE_FIELDS)))
+        if "photoionization" in fields and (n_part is None or value is None):
+            raise ValueError("field 'photoionization' needs n_part and value")
+        npart = None if n_part is None else f64(n_part, (self.n,))
+        val = None if value is None else f64(value, (self.n,))
+        out = {f: np.zeros(m) for f in fields}
+        cnt = np.zeros(m, np.int64) if with_stats else None
+        cand = np.zeros(1, np.int64)
+        c = self.ctx
+        c.check(c.lib.sphx_state_sample(c.h, float(d), dp(npart), dp(val), m, dp(q), float(radius),
+                                        *[dp(out.get(f)) for f in self.SAMPLE_FIELDS], _lib.ip(cnt), _lib.ip(cand)))
+        out = {f: a.reshape(shape) for f, a in out.items()}
+        if with_stats:
+            out["count"] = cnt.reshape(shape)
+            out["candidates"] = int(cand[0])
+        return out
+
+    def sample_timing(self):
+        """Device time of the last sample() from HIP events -> dict of ms: upload, build, kernels, download."""
+        ms = np.zeros(4)
+        c = self.ctx
+        c.check(c.lib.sphx_arb_last_timing(c.h, dp(ms)))
+        return dict(zip(("upload", "build", "kernels", "download"), ms.tolist()))
 
     def download_species(self):
         """-> dict: f_un_neighbor (S,N) as nsc.hydro_update returns it (nsc:671), and with an AGB table also
