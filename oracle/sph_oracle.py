@@ -568,20 +568,26 @@ def step_loop(state, d, n_neigh=40, dist=np.inf, eps=0.0, first=False, fixed_dt=
 G_NEWTON = 6.67430e-11        # scipy.constants.G (nsc:21)
 
 
-def gravity_direct(points, mass, softening, G=G_NEWTON, chunk=512):
+def gravity_direct(points, mass, softening, G=G_NEWTON, chunk=512, return_abs=False):
     """The sum the reference's tree gravity (nsc:252-415) approximates: every particle as its own
-    monopole, Plummer-softened as at nsc:385:  G m_j (x_j - x_i) / (|x_j - x_i|^2 + eps^2)^(3/2)."""
+    monopole, Plummer-softened as at nsc:385:  G m_j (x_j - x_i) / (|x_j - x_i|^2 + eps^2)^(3/2).
+    return_abs: also the sum of the terms' magnitudes, component by component - the scale a row's
+    round-off is measured against (the signed sum itself is computed as without it)."""
     p = np.asarray(points, dtype=np.float64)
     m = np.asarray(mass, dtype=np.float64)
     out = np.zeros_like(p)
+    out_abs = np.zeros_like(p) if return_abs else None
     e2 = float(softening) ** 2
     for a in range(0, len(p), chunk):
         d = p[None, :, :] - p[a:a + chunk, None, :]                    # (c, n, 3)
         r2 = np.sum(d * d, axis=2) + e2
         with np.errstate(all="ignore"):
             w = np.where(r2 > 0, m[None, :] / (r2 * np.sqrt(r2)), 0.0)
-        out[a:a + chunk] = G * np.sum(w[:, :, None] * d, axis=1)
-    return out
+        t = w[:, :, None] * d
+        out[a:a + chunk] = G * np.sum(t, axis=1)
+        if return_abs:
+            out_abs[a:a + chunk] = G * np.sum(np.abs(t), axis=1)
+    return (out, out_abs) if return_abs else out
 
 
 def step(state, n_neigh=40, dist=np.inf, eps=0.0, first=False, grav_accel=None, workers=1,

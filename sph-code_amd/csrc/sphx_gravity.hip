@@ -221,12 +221,14 @@ __global__ __launch_bounds__(256) void pyr_up_kernel(Pyr py, int l, double4* pyr
 // the Taylor expansion of the SOFTENED kernel 1 / sqrt(r^2 + eps^2) to second order, s^2 = r^2 + eps^2,
 //   a = (M / s^3 + 15/2 (r.S.r) / s^7 - 3/2 tr(S) / s^5) r - 3 (S.r) / s^5
 // (for eps = 0 this is the usual traceless-quadrupole term).  f = 1 for a cell of the lane's list, else 0.
-// Needs s2 > 0: softening, or a cell that is not the particle's own - a well-separated cell never is.
+// s2 = 0 (no softening, and the cell's centre exactly on the particle: the wave kernel also runs, with f = 0, over the
+// lane's own cell, and a lone particle's cell IS the particle) contributes nothing - as a coincident pair does in the
+// direct sum; without the guard that term is 0 * inf.
 __device__ __forceinline__ void grav_term_quad(double4 a4, double4 b4, double4 c4, double f, double xi, double yi,
                                                double zi, double e2, double& ax, double& ay, double& az) {
     const double dx = a4.y - xi, dy = a4.z - yi, dz = a4.w - zi;
     const double r2 = dx * dx + dy * dy + dz * dz + e2;
-    const double y0 = __builtin_amdgcn_rsq(r2);
+    const double y0 = r2 > 0.0 ? __builtin_amdgcn_rsq(r2) : 0.0;
     const double inv = y0 * __builtin_fma(-0.5 * r2 * y0, y0, 1.5);
     const double inv2 = inv * inv, inv3 = inv * inv2, inv5 = inv3 * inv2, inv7 = inv5 * inv2;
     const double srx = b4.x * dx + b4.w * dy + c4.x * dz;

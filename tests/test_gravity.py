@@ -62,6 +62,71 @@ def test_gpu_direct_sum_vs_oracle():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [255, 256, 257, 511, 512, 513, 3000])
+def test_gpu_direct_sum_rows_vs_oracle(n):
+    """Row by row around the source tile (256): every component within 1e-12 of the sum of its terms'
+    magnitudes - a global max|ref| hides a row whose terms cancel."""
+    from oracle import sph_oracle as orc
+    import sph_code_amd.compat as nsc
+    p, m, h = _cloud(n, seed=n)
+    got = nsc.grav_force_direct(m, p, h)
+    ref, scale = orc.gravity_direct(p, m, np.median(h), return_abs=True)
+    assert (np.abs(got - ref) <= 1e-12 * scale).all(), np.max(np.abs(got - ref) / scale)
+
+
+def _direct_c_abi(m, p, sizes, eps):
+    from sph_code_amd import _lib
+    dp = lambda a: None if a is None else np.ascontiguousarray(a).ctypes.data_as(_lib.c_double_p)
+    m, p = np.ascontiguousarray(m), np.ascontiguousarray(p)
+    sizes = None if sizes is None else np.ascontiguousarray(sizes)
+    c = _lib.Context()
+    out = np.full((len(m), 3), np.nan)
+    c.check(c.lib.sphx_gravity_direct(c.h, len(m), dp(m), dp(p), dp(sizes), float(eps), 6.67430e-11, dp(out)))
+    c.close()
+    return out
+
+
+@pytest.mark.gpu
+def test_gpu_direct_sum_unsoftened_coincident_pairs():
+    """eps = 0 by value (sizes = NULL) with 40 coincident pairs: a pair at zero distance contributes
+    nothing, and every row stays within 1e-12 of its scale."""
+    from oracle import sph_oracle as orc
+    p, m, _ = _cloud(600, seed=77)
+    p[40:80] = p[:40]
+    got = _direct_c_abi(m, p, None, 0.0)
+    ref, scale = orc.gravity_direct(p, m, 0.0, return_abs=True)
+    assert np.isfinite(got).all()
+    assert (np.abs(got - ref) <= 1e-12 * scale).all(), np.max(np.abs(got - ref) / scale)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [512, 513])
+def test_gpu_direct_sum_softening_is_the_median_of_sizes(n):
+    """sizes given: eps is their median as NumPy defines it (even n: the mean of the two middle values),
+    taken on the device - h spread over a factor 10^6, with ties, some of them at the middle."""
+    from oracle import sph_oracle as orc
+    p, m, _ = _cloud(n, seed=n)
+    rs = np.random.RandomState(n + 1)
+    h = 2e4 * AU * 10.0 ** rs.uniform(-3.0, 3.0, n)
+    h[::7] = h[3]
+    h[1], h[2] = 2e1 * AU, 2e7 * AU
+    order = np.argsort(h)
+    if n % 2:
+        h[order[[n // 2 - 1, n // 2 + 1]]] = h[order[n // 2]]               # ties at the middle value
+    else:
+        h[order[[n // 2 - 3, n // 2 - 2]]] = h[order[n // 2 - 1]]           # ties up to the lower middle value
+    srt = np.sort(h)
+    assert h.max() / h.min() == 1e6 and len(np.unique(h)) < n - 50
+    if n % 2:
+        assert srt[n // 2 - 1] == srt[n // 2] == srt[n // 2 + 1]
+    else:
+        assert srt[n // 2 - 3] == srt[n // 2 - 1] != srt[n // 2]
+    got = _direct_c_abi(m, p, h, 0.0)
+    ref, scale = orc.gravity_direct(p, m, np.median(h), return_abs=True)
+    assert (np.abs(got - ref) <= 1e-12 * scale).all(), np.max(np.abs(got - ref) / scale)
+
+
+@pytest.mark.gpu
 def test_gpu_step_with_gravity_vs_oracle():
     """6 leapfrog steps of a small polytrope with self-gravity on: rtol 1e-9 on x, v, a vs the oracle's step
     (gravity = direct sum, eps = median(h) of each step)."""
