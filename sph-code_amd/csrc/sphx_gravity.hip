@@ -132,7 +132,12 @@ extern "C" int sphx_gravity_direct(sphx_ctx* ctx, int64_t n, const double* mass,
 // reference.  ws = 1: ~1.5e3 terms per particle, ~1 % rms force error; ws = 2: ~7e3 terms, ~0.2 %.
 // One thread per particle in processing (blob) order, so the lanes of a wave walk the same cells
 // and their loads of a cell record coalesce into one request.
+// Centres of mass are held RELATIVE to a point inside the cloud (GravRef: the centre of the grid box), and the walks take cell - particle
+// differences in that frame: a centre sum m x / M of absolute coordinates carries ulp(|x|), which for a cloud of size D at
+// distance T from the origin is T / D times the round-off of the differences themselves (1e-7 of a row at T / D = 2^27).
+// The near field differences two particles directly and needs no frame.
 #define PYR_MAX 12
+struct GravRef { double x, y, z; };
 struct Pyr {
     int nlev;                                   // levels 1..nlev exist; level nlev is a single cell
     int nx[PYR_MAX + 1], ny[PYR_MAX + 1], nz[PYR_MAX + 1];
@@ -142,24 +147,30 @@ struct Pyr {
 __global__ __launch_bounds__(256) void pyr_level1_kernel(GridParams g, Pyr py, const int* __restrict__ cell_start,
                                                          const double* __restrict__ x, const double* __restrict__ y,
                                                          const double* __restrict__ z, const double* __restrict__ m,
-                                                         double4* pyr, double4* quad) {
+                                                         GravRef ref, double4* pyr, double4* quad) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     const int nx1 = py.nx[1], ny1 = py.ny[1], nz1 = py.nz[1];
     if (c >= nx1 * ny1 * nz1) return;
     const int X = c % nx1, Y = (c / nx1) % ny1, Z = c / (nx1 * ny1);
     const int fx0 = 2 * X, fx1 = min(2 * X + 2, g.nx);
-    double sm = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    // first moments about the cell's first member (p0), so that an axis on which all members agree gives that value
+    // back exactly (a line or a plane has no force across it, to the last bit)
+    double sm = 0.0, sx = 0.0, sy = 0.0, sz = 0.0, p0x = 0.0, p0y = 0.0, p0z = 0.0;
+    bool have = false;
     for (int fz = 2 * Z; fz < min(2 * Z + 2, g.nz); ++fz)
         for (int fy = 2 * Y; fy < min(2 * Y + 2, g.ny); ++fy) {
             const int row = (fz * g.ny + fy) * g.nx;
             const int s = cell_start[row + fx0], e = cell_start[row + fx1];
             for (int j = s; j < e; ++j) {
-                const double mj = m[j];
-                sm += mj; sx += mj * x[j]; sy += mj * y[j]; sz += mj * z[j];
+                const double mj = m[j], rx = x[j] - ref.x, ry = y[j] - ref.y, rz = z[j] - ref.z;
+                if (!have) { p0x = rx; p0y = ry; p0z = rz; have = true; }
+                sm += mj; sx += mj * (rx - p0x); sy += mj * (ry - p0y); sz += mj * (rz - p0z);
             }
         }
-    const double inv = sm > 0.0 ? 1.0 / sm : 0.0;
-    const double cxm = sx * inv, cym = sy * inv, czm = sz * inv;
+    const bool massive = sm > 0.0;
+    const double inv = massive ? 1.0 / sm : 0.0;
+    const double cxm = massive ? p0x + sx * inv : 0.0, cym = massive ? p0y + sy * inv : 0.0,
+                 czm = massive ? p0z + sz * inv : 0.0;
     pyr[py.off[1] + c] = make_double4(sm, cxm, cym, czm);
     if (quad) {
         // second moments about the centre of mass, S_ab = sum m d_a d_b (not made traceless: the
@@ -170,7 +181,7 @@ __global__ __launch_bounds__(256) void pyr_level1_kernel(GridParams g, Pyr py, c
                 const int row = (fz * g.ny + fy) * g.nx;
                 const int s = cell_start[row + fx0], e = cell_start[row + fx1];
                 for (int j = s; j < e; ++j) {
-                    const double mj = m[j], dx = x[j] - cxm, dy = y[j] - cym, dz = z[j] - czm;
+                    const double mj = m[j], dx = (x[j] - ref.x) - cxm, dy = (y[j] - ref.y) - cym, dz = (z[j] - ref.z) - czm;
                     qxx += mj * dx * dx; qyy += mj * dy * dy; qzz += mj * dz * dz;
                     qxy += mj * dx * dy; qxz += mj * dx * dz; qyz += mj * dy * dz;
                 }
@@ -187,15 +198,19 @@ __global__ __launch_bounds__(256) void pyr_up_kernel(Pyr py, int l, double4* pyr
     const int X = c % nxl, Y = (c / nxl) % nyl, Z = c / (nxl * nyl);
     const int cx = py.nx[l - 1], cy = py.ny[l - 1], cz = py.nz[l - 1];
     const double4* ch = pyr + py.off[l - 1];
-    double sm = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    double sm = 0.0, sx = 0.0, sy = 0.0, sz = 0.0, p0x = 0.0, p0y = 0.0, p0z = 0.0;     // (p0: the first massive child)
+    bool have = false;
     for (int k = 2 * Z; k < min(2 * Z + 2, cz); ++k)
         for (int j = 2 * Y; j < min(2 * Y + 2, cy); ++j)
             for (int i = 2 * X; i < min(2 * X + 2, cx); ++i) {
                 const double4 q = ch[((size_t)k * cy + j) * cx + i];
-                sm += q.x; sx += q.x * q.y; sy += q.x * q.z; sz += q.x * q.w;
+                sm += q.x;                                      // (every child's mass, so that a NaN still travels up)
+                if (!(q.x > 0.0)) continue;                     // a massless child has no centre to offer
+                if (!have) { p0x = q.y; p0y = q.z; p0z = q.w; have = true; }
+                sx += q.x * (q.y - p0x); sy += q.x * (q.z - p0y); sz += q.x * (q.w - p0z);
             }
     const double inv = sm > 0.0 ? 1.0 / sm : 0.0;
-    const double cxm = sx * inv, cym = sy * inv, czm = sz * inv;
+    const double cxm = p0x + sx * inv, cym = p0y + sy * inv, czm = p0z + sz * inv;          // (no massive child: 0)
     pyr[py.off[l] + c] = make_double4(sm, cxm, cym, czm);
     if (quad) {
         // S = sum over children of S_child + M_child s s^T, s = child's centre - this centre
@@ -319,7 +334,8 @@ __global__ __launch_bounds__(256) void gravity_tree_kernel(int n, GridParams g, 
                                                            const double* __restrict__ z, const double* __restrict__ m,
                                                            const double4* __restrict__ pyr,
                                                            const double4* __restrict__ quad, const double* eps_ptr,
-                                                           double eps_val, double G, const int* __restrict__ qorder,
+                                                           double eps_val, double G, GravRef ref,
+                                                           const int* __restrict__ qorder,
                                                            const int* __restrict__ omap, double* acc) {
     const int p = xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
     if (p >= n) return;
@@ -331,9 +347,10 @@ __global__ __launch_bounds__(256) void gravity_tree_kernel(int n, GridParams g, 
     const int fx = c0 % g.nx, fy = (c0 / g.nx) % g.ny, fz = c0 / (g.nx * g.ny);
     double ax = 0.0, ay = 0.0, az = 0.0;
     near_walk_lane(g, ws, fx, fy, fz, cell_start, x, y, z, m, xi, yi, zi, e2, ax, ay, az);
+    const double xr = xi - ref.x, yr = yi - ref.y, zr = zi - ref.z;          // the cells' frame
     for (int l = 1; l < py.nlev; ++l)
         far_walk_lane(ws, fx >> l, fy >> l, fz >> l, py.nx[l], py.ny[l], py.nz[l], pyr + py.off[l],
-                      quad ? quad + 2 * py.off[l] : nullptr, xi, yi, zi, e2, ax, ay, az);
+                      quad ? quad + 2 * py.off[l] : nullptr, xr, yr, zr, e2, ax, ay, az);
     const int o = omap ? omap[i] : i;
     acc[3 * (size_t)o] = G * ax; acc[3 * (size_t)o + 1] = G * ay; acc[3 * (size_t)o + 2] = G * az;
 }
@@ -381,7 +398,8 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
                                                                 const double* __restrict__ z, const double* __restrict__ m,
                                                                 const double4* __restrict__ pyr,
                                                                 const double4* __restrict__ quad, const double* eps_ptr,
-                                                                double eps_val, double G, const int* __restrict__ qorder,
+                                                                double eps_val, double G, GravRef ref,
+                                                                const int* __restrict__ qorder,
                                                                 const int* __restrict__ omap, double* acc) {
     constexpr int CB = QUAD ? GT_CB / 2 : GT_CB;      // cells staged at a time
     __shared__ double4 cbuf_all[4][QUAD ? 3 * (GT_CB / 2) : GT_CB];
@@ -440,7 +458,8 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
             }
         }
     }
-    // ---- far field: interaction lists, level by level ------------------------------------------------
+    // ---- far field: interaction lists, level by level (in the cells' frame) ---------------------------
+    const double xr = xi - ref.x, yr = yi - ref.y, zr = zi - ref.z;
     for (int l = 1; l < py.nlev; ++l) {
         const int X = fx >> l, Y = fy >> l, Z = fz >> l;
         const int PX = X >> 1, PY = Y >> 1, PZ = Z >> 1;
@@ -456,7 +475,7 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
         const int own = 4 * ws + 2 + GT_SLACK;
         if (W > 32 || W > own || uy1 - uy0 >= own || uz1 - uz0 >= own) {
             // a wave spread over more cells than neighbours would be: the per-lane walk
-            far_walk_lane(ws, X, Y, Z, nxl, nyl, nzl, lev, QUAD ? quad + 2 * py.off[l] : nullptr, xi, yi, zi, e2,
+            far_walk_lane(ws, X, Y, Z, nxl, nyl, nzl, lev, QUAD ? quad + 2 * py.off[l] : nullptr, xr, yr, zr, e2,
                           ax, ay, az);
             continue;
         }
@@ -486,7 +505,7 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
                         for (int t = 0; t < W; ++t) {
                             const double4 q = rowq[t];
                             if (!(q.x > 0.0)) continue;                           // (uniform: an empty cell)
-                            grav_term_quad(q, rowq[CB + t], rowq[2 * CB + t], ((bits >> t) & 1u) ? 1.0 : 0.0, xi, yi, zi,
+                            grav_term_quad(q, rowq[CB + t], rowq[2 * CB + t], ((bits >> t) & 1u) ? 1.0 : 0.0, xr, yr, zr,
                                            e2, ax, ay, az);
                         }
                     } else if (soft) {
@@ -494,18 +513,18 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
                         int t = 0;
                         for (; t + 1 < W; t += 2) {
                             const double4 q0 = rowq[t], q1 = rowq[t + 1];
-                            grav_term_soft(q0.y, q0.z, q0.w, ((bits >> t) & 1u) ? q0.x : 0.0, xi, yi, zi, e2, ax, ay, az);
-                            grav_term_soft(q1.y, q1.z, q1.w, ((bits >> (t + 1)) & 1u) ? q1.x : 0.0, xi, yi, zi, e2, ax, ay, az);
+                            grav_term_soft(q0.y, q0.z, q0.w, ((bits >> t) & 1u) ? q0.x : 0.0, xr, yr, zr, e2, ax, ay, az);
+                            grav_term_soft(q1.y, q1.z, q1.w, ((bits >> (t + 1)) & 1u) ? q1.x : 0.0, xr, yr, zr, e2, ax, ay, az);
                         }
                         if (t < W) {
                             const double4 q0 = rowq[t];
-                            grav_term_soft(q0.y, q0.z, q0.w, ((bits >> t) & 1u) ? q0.x : 0.0, xi, yi, zi, e2, ax, ay, az);
+                            grav_term_soft(q0.y, q0.z, q0.w, ((bits >> t) & 1u) ? q0.x : 0.0, xr, yr, zr, e2, ax, ay, az);
                         }
                     } else {
                         for (int t = 0; t < W; ++t) {
                             const double4 q = rowq[t];
                             if (!(q.x > 0.0)) continue;                           // (uniform: an empty cell)
-                            grav_term(q.y, q.z, q.w, ((bits >> t) & 1u) ? q.x : 0.0, xi, yi, zi, e2, ax, ay, az);
+                            grav_term(q.y, q.z, q.w, ((bits >> t) & 1u) ? q.x : 0.0, xr, yr, zr, e2, ax, ay, az);
                         }
                     }
                 }
@@ -555,9 +574,15 @@ int sphx_gravity_tree_launch(sphx_ctx* ctx, int64_t n, const double* x, const do
         SPHX_TRY(sphx_ensure(ctx, ctx->grav_quad, (size_t)tot * 2 * sizeof(double4)));
         quad = ctx->grav_quad.as<double4>();
     }
+    // the frame: the centre of the grid box, brought inside the true bounding box axis by axis - the box of a thin slab is
+    // padded to a cell's width, far more than the slab's thickness, whose round-off the cross-slab force needs
+    const double bc[3] = {g.xmin + 0.5 * g.nx * g.cell, g.ymin + 0.5 * g.ny * g.cell, g.zmin + 0.5 * g.nz * g.cell};
+    double rc[3];
+    for (int c = 0; c < 3; ++c) rc[c] = fmin(fmax(bc[c], ctx->tbox_h[c]), ctx->tbox_h[3 + c]);
+    const GravRef ref = {rc[0], rc[1], rc[2]};
     const int n1 = py.nx[1] * py.ny[1] * py.nz[1];
     hipLaunchKernelGGL(pyr_level1_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, ctx->stream, g, py,
-                       ctx->cell_start.as<int>(), x, y, z, m, pyr, quad);
+                       ctx->cell_start.as<int>(), x, y, z, m, ref, pyr, quad);
     for (int q = 2; q <= py.nlev; ++q) {
         const int nq = py.nx[q] * py.ny[q] * py.nz[q];
         hipLaunchKernelGGL(pyr_up_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, py, q, pyr, quad);
@@ -567,15 +592,15 @@ int sphx_gravity_tree_launch(sphx_ctx* ctx, int64_t n, const double* x, const do
     if (ctx->grav_per_thread)         // SPHX_GRAV_KERNEL=0: the per-thread walk (the wave kernel's reference)
         hipLaunchKernelGGL(gravity_tree_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n, g, py,
                            ws, ctx->grav_cell.as<int>(), ctx->cell_start.as<int>(), x, y, z, m, pyr, quad, eps_dev, eps, G,
-                           ctx->qorder, omap, acc);
+                           ref, ctx->qorder, omap, acc);
     else if (quad)
         hipLaunchKernelGGL(gravity_tree_wave_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
                            (int)n, g, py, ws, ctx->grav_cell.as<int>(), ctx->cell_start.as<int>(), x, y, z, m, pyr, quad,
-                           eps_dev, eps, G, ctx->qorder, omap, acc);
+                           eps_dev, eps, G, ref, ctx->qorder, omap, acc);
     else
         hipLaunchKernelGGL(gravity_tree_wave_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
                            (int)n, g, py, ws, ctx->grav_cell.as<int>(), ctx->cell_start.as<int>(), x, y, z, m, pyr, quad,
-                           eps_dev, eps, G, ctx->qorder, omap, acc);
+                           eps_dev, eps, G, ref, ctx->qorder, omap, acc);
     HIPCHK(hipGetLastError());
     return SPHX_OK;
 }

@@ -29,15 +29,36 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
-// partial[block][13] = {min xyz, max xyz, sum xyz, sum of squares xyz, count}; non-finite
-// coordinates are ignored
+// partial[block][13] = {min xyz, max xyz, sum of (x - p) xyz, sum of (x - p)^2 xyz, count}; non-finite
+// coordinates are ignored.  The moments are taken about a pivot p near the cloud, not about the origin: with raw
+// moments var = sq/cnt - mean^2 loses eps T^2 for a cloud at distance T, which is all of it from T = 1e8 cloud sizes on.
+// p: the clip window's centre when the window is valid, else the first particle (pivot_dev: read on the device - the
+// host has not seen a position yet); any p within a few cloud sizes of the cloud will do.
 #define BB_W 13
-struct ClipBox { double lo[3], hi[3]; int on; };
+#define BB_PIVOT 16                 // the finished statistics carry the pivot at [16..18] (13: the fused kernel's ticket word)
+#define BB_OUT 19
+struct ClipBox { double lo[3], hi[3]; int on; double pivot[3]; int pivot_dev; };
+static void clip_set_pivot(ClipBox& clip, const double* fallback) {
+    clip.pivot_dev = 0;
+    for (int c = 0; c < 3; ++c) clip.pivot[c] = clip.on ? 0.5 * (clip.lo[c] + clip.hi[c]) : (fallback ? fallback[c] : 0.0);
+    if (!clip.on && !fallback) clip.pivot_dev = 1;
+    for (int c = 0; c < 3; ++c) if (!isfinite(clip.pivot[c])) clip.pivot[c] = 0.0;
+}
+__device__ __forceinline__ void clip_pivot(const ClipBox& clip, int n, const double* x, const double* y, const double* z,
+                                           double p[3]) {
+    p[0] = clip.pivot[0]; p[1] = clip.pivot[1]; p[2] = clip.pivot[2];
+    if (clip.pivot_dev && n > 0) {
+        const double f[3] = {x[0], y[0], z[0]};
+        for (int c = 0; c < 3; ++c) p[c] = isfinite(f[c]) ? f[c] : 0.0;
+    }
+}
 __global__ __launch_bounds__(RED_BLOCK) void bbox_partial(int n, const double* x, const double* y,
                                                           const double* z, ClipBox clip, double* partial) {
     __shared__ double sm[RED_BLOCK / 64][BB_W];
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     double su[3] = {0.0, 0.0, 0.0}, sq[3] = {0.0, 0.0, 0.0}, cnt = 0.0;
+    double piv[3];
+    clip_pivot(clip, n, x, y, z, piv);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         double v[3] = {x[i], y[i], z[i]};
         if (isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2])) {
@@ -52,7 +73,7 @@ __global__ __launch_bounds__(RED_BLOCK) void bbox_partial(int n, const double* x
             if (in) {
                 cnt += 1.0;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { su[c] += v[c]; sq[c] += v[c] * v[c]; }
+                for (int c = 0; c < 3; ++c) { const double r = v[c] - piv[c]; su[c] += r; sq[c] += r * r; }
             }
         }
     }
@@ -78,9 +99,19 @@ __global__ __launch_bounds__(RED_BLOCK) void bbox_partial(int n, const double* x
     }
 }
 // one block per component: block c reduces partial[:, c] (four waves, then their four results in a fixed order)
-__global__ __launch_bounds__(256) void bbox_final(int nblocks, const double* partial, double* out) {
+// blocks BB_W .. BB_W + 2 (bbox_launch only): the pivot the partials were taken about, for the host
+__global__ __launch_bounds__(256) void bbox_final(int nblocks, const double* partial, double* out, int n, const double* x,
+                                                  const double* y, const double* z, ClipBox clip) {
     __shared__ double sw[4];
     const int c = blockIdx.x;
+    if (c >= BB_W) {
+        if (threadIdx.x == 0) {
+            double p[3];
+            clip_pivot(clip, n, x, y, z, p);
+            out[BB_PIVOT + c - BB_W] = p[c - BB_W];
+        }
+        return;
+    }
     double v = c < 3 ? INFINITY : (c < 6 ? -INFINITY : 0.0);
     for (int b = threadIdx.x; b < nblocks; b += 256) {
         const double p = partial[b * BB_W + c];
@@ -103,34 +134,43 @@ static int bbox_launch(sphx_ctx* ctx, int64_t n, const double* x, const double* 
     ClipBox clip;
     clip.on = (use_clip && ctx->clip_valid) ? 1 : 0;
     for (int c = 0; c < 3; ++c) { clip.lo[c] = ctx->clip_lo[c]; clip.hi[c] = ctx->clip_hi[c]; }
+    clip_set_pivot(clip, nullptr);
     int blocks = (int)((n + RED_BLOCK - 1) / RED_BLOCK);
     if (blocks > RED_MAXBLOCKS) blocks = RED_MAXBLOCKS;
     SPHX_TRY(sphx_ensure(ctx, ctx->bbox_tmp, (size_t)(RED_MAXBLOCKS + 2 + FUSED_MAXBLOCKS) * BB_W * sizeof(double)));
     double* part = ctx->bbox_tmp.as<double>();
     double* fin = part + (size_t)RED_MAXBLOCKS * BB_W;
     hipLaunchKernelGGL(bbox_partial, dim3(blocks), dim3(RED_BLOCK), 0, ctx->stream, (int)n, x, y, z, clip, part);
-    hipLaunchKernelGGL(bbox_final, dim3(BB_W), dim3(256), 0, ctx->stream, blocks, part, fin);
+    hipLaunchKernelGGL(bbox_final, dim3(BB_W + 3), dim3(256), 0, ctx->stream, blocks, part, fin, (int)n, x, y, z, clip);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host_dst, fin, BB_W * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(host_dst, fin, BB_OUT * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     return SPHX_OK;
 }
-// sums -> mean and standard deviation
-static void bbox_finish(const void* host_src, double out_minmax[13]) {
+// sums about the pivot (host_src[BB_PIVOT..]) -> mean and standard deviation; rel (nullable): {min, max, mean} - pivot,
+// for the caller that wants the box's extents free of the rounding of far-away absolute corners
+static void bbox_finish(const void* host_src, double out_minmax[13], double rel[9] = nullptr) {
     memcpy(out_minmax, host_src, BB_W * sizeof(double));
+    double piv[3];
+    memcpy(piv, (const double*)host_src + BB_PIVOT, sizeof(piv));
     const double cnt = out_minmax[12] > 0.0 ? out_minmax[12] : 1.0;
     for (int c = 0; c < 3; ++c) {
-        const double mean = out_minmax[6 + c] / cnt;
+        const double mean = out_minmax[6 + c] / cnt;           // of x - p
         double var = out_minmax[9 + c] / cnt - mean * mean;
-        out_minmax[6 + c] = mean;
+        if (rel) { rel[c] = out_minmax[c] - piv[c]; rel[3 + c] = out_minmax[3 + c] - piv[c]; rel[6 + c] = mean; }
+        out_minmax[6 + c] = piv[c] + mean;
         out_minmax[9 + c] = var > 0.0 ? sqrt(var) : 0.0;
     }
 }
-int sphx_bbox(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z,
-              double out_minmax[13], bool use_clip) {
+static int bbox_sync(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z,
+                     double out_minmax[13], bool use_clip, double rel[9]) {
     SPHX_TRY(bbox_launch(ctx, n, x, y, z, use_clip, ctx->pinned));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    bbox_finish(ctx->pinned, out_minmax);
+    bbox_finish(ctx->pinned, out_minmax, rel);
     return SPHX_OK;
+}
+int sphx_bbox(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z,
+              double out_minmax[13], bool use_clip) {
+    return bbox_sync(ctx, n, x, y, z, out_minmax, use_clip, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -179,6 +219,7 @@ __global__ __launch_bounds__(RED_BLOCK) void grid_count_fused(FusedCountArgs a) 
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     double su[3] = {0.0, 0.0, 0.0}, sq[3] = {0.0, 0.0, 0.0}, cnt = 0.0;
     const GridParams g = a.g;
+    const double piv[3] = {a.clip.pivot[0], a.clip.pivot[1], a.clip.pivot[2]};      // (host-side pivot always: sphx_build_grid)
     if (a.ct_reset && blockIdx.x == 0 && threadIdx.x == 0) *a.ct_reset = SPHX_CT_NONE;
     if (a.zero_int && blockIdx.x == 0 && threadIdx.x == 0) { a.zero_int[0] = 0; a.zero_int[1] = 0; }   // fail count, tie count
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gridDim.x * blockDim.x) {
@@ -213,7 +254,7 @@ __global__ __launch_bounds__(RED_BLOCK) void grid_count_fused(FusedCountArgs a) 
             if (in) {
                 cnt += 1.0;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { su[c] += v[c]; sq[c] += v[c] * v[c]; }
+                for (int c = 0; c < 3; ++c) { const double r = v[c] - piv[c]; su[c] += r; sq[c] += r * r; }
             }
         }
         const int cx = cell_coord_g(v[0], g.xmin, g.inv_cell, g.nx - 1);
@@ -584,7 +625,7 @@ __global__ __launch_bounds__(256) void cell_sort_members(int ncells, const int* 
 //  field added here belongs on that list too)
 int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const double* y, const double* z, double cell_hint,
                     const GridBuildOpts& opts) {
-    double bb[13];
+    double bb[13], rel[9];         // rel: the box and the mean measured from the statistics' pivot
     // drv:233-238 when the caller asked for it: inside the fused count kernel, or by a launch of its own before any
     // other kernel of this build reads the positions
     bool clamp_pending = opts.clamp_vel[0] != nullptr;
@@ -620,21 +661,21 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
             ctx->lag_balias[cur] = nullptr;
         }
         HIPCHK(hipEventSynchronize(ctx->lag_balias[use] ? ctx->lag_balias[use] : ctx->lag_bev[use]));
-        bbox_finish(slot + 512 * use, bb);
+        bbox_finish(slot + 512 * use, bb, rel);
         ctx->lag_bvalid[cur] = true;
         ctx->lag_bn[cur] = n;
         ctx->lag_bslot = cur;
     } else {
         SPHX_TRY(clamp_now());
-        SPHX_TRY(sphx_bbox(ctx, n, x, y, z, bb, true));
+        SPHX_TRY(bbox_sync(ctx, n, x, y, z, bb, true, rel));
     }
     if (ctx->clip_valid && bb[12] < 0.5 * (double)n) {     // the clip box lost the cloud: re-anchor
         SPHX_TRY(clamp_now());
-        SPHX_TRY(sphx_bbox(ctx, n, x, y, z, bb, false));
+        SPHX_TRY(bbox_sync(ctx, n, x, y, z, bb, false, rel));
     }
-    double tmin[3], tmax[3];
+    double tmin[3], tmax[3], L[3];
     for (int c = 0; c < 3; ++c) {
-        if (!(bb[3 + c] >= bb[c])) { bb[c] = 0.0; bb[3 + c] = 0.0; }   // no finite coordinate
+        if (!(bb[3 + c] >= bb[c])) { bb[c] = 0.0; bb[3 + c] = 0.0; rel[c] = rel[3 + c] = 0.0; }   // no finite coordinate
         tmin[c] = bb[c]; tmax[c] = bb[3 + c];
         // Robust box: a few escaped particles (the reference lets them reach 1e11 AU, drv:233) must
         // not stretch the grid over empty space.  The grid covers mean +- 3 sigma (box_sigmas: a
@@ -643,15 +684,20 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         // exactly (half-infinite boundary cells).  With 8 sigma a freely expanding 1e6 polytrope
         // went from 2.25 to 3.74 ms/step in 400 steps (cells at the cap, 100-cell-wide halo
         // searches); with 3 it goes from 2.10 to 2.42.
-        const double lo = bb[6 + c] - ctx->box_sigmas * bb[9 + c], hi = bb[6 + c] + ctx->box_sigmas * bb[9 + c];
+        // The clip and the extent L are worked out on coordinates measured from the pivot: far from the origin the corners
+        // themselves carry ulp(|x|) each, 1e-8 of the extent at 2^27 cloud sizes, which must not reach the cell size.
+        const double piv = bb[6 + c] - rel[6 + c];
+        double lo_r = rel[c], hi_r = rel[3 + c];
+        const double lo = rel[6 + c] - ctx->box_sigmas * bb[9 + c], hi = rel[6 + c] + ctx->box_sigmas * bb[9 + c];
         if (bb[9 + c] > 0.0 && hi > lo) {
-            if (bb[c] < lo) bb[c] = lo;
-            if (bb[3 + c] > hi) bb[3 + c] = hi;
+            if (lo_r < lo) { lo_r = lo; bb[c] = piv + lo; }
+            if (hi_r > hi) { hi_r = hi; bb[3 + c] = piv + hi; }
         }
+        L[c] = hi_r - lo_r;
+        if (!(L[c] >= 0.0) || !isfinite(L[c])) L[c] = bb[3 + c] - bb[c];
     }
-    double L[3];
     double Lmax = 0.0;
-    for (int c = 0; c < 3; ++c) { L[c] = bb[3 + c] - bb[c]; if (L[c] > Lmax) Lmax = L[c]; }
+    for (int c = 0; c < 3; ++c) if (L[c] > Lmax) Lmax = L[c];
     // next time, statistics are taken over this box doubled about its centre
     for (int c = 0; c < 3; ++c) {
         const double mid = 0.5 * (bb[c] + bb[3 + c]), half = (L[c] > 0.0 ? L[c] : Lmax);
@@ -736,6 +782,10 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         clamp_pending = false;
         fa.lim = ctx->cst.pos_clamp;
         fa.clip = clip0;
+        // (no valid window: every particle of the previous build coincided - its box, the corner tbox_h, is that point)
+        clip_set_pivot(fa.clip, ctx->tbox_h);
+        // the pivot travels with the statistics: written here, by the host, next to where the device puts the sums
+        memcpy((char*)ctx->pinned + LAG_OFF + 512 * lag_cur + BB_PIVOT * sizeof(double), fa.clip.pivot, 3 * sizeof(double));
         fa.g = g;
         fa.cell_of = ctx->cell_of.as<int>();
         fa.hist = fill;
@@ -757,7 +807,8 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         if (pb >= BB_W) {
             bb_fold_blocks = fb; bb_fold_part = part; bb_fold_out = fin;   // folded by cell_scatter's first blocks, copied out there
         } else {
-            hipLaunchKernelGGL(bbox_final, dim3(BB_W), dim3(256), 0, ctx->stream, fb, part, fin);
+            hipLaunchKernelGGL(bbox_final, dim3(BB_W), dim3(256), 0, ctx->stream, fb, part, fin, 0,
+                               (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, fa.clip);
             bb_fold_out = fin;                                             // (a handful of particles: its own launch, copied out below)
         }
     } else {
