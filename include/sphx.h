@@ -51,6 +51,8 @@ typedef struct sphx_constants {
     double dt_0;     /* nsc:38  250000 yr                                  */
     double max_age;  /* drv:79  3e7 yr                                     */
     double pos_clamp;/* drv:233 1e11 AU                                    */
+    double solar_luminosity; /* nsc:31 3.846e26 W                          */
+    double c;        /* nsc:27  scipy.constants.c                          */
 } sphx_constants;
 
 /* Per-pass timing / traffic model of the last sphx_step call. */
@@ -396,6 +398,69 @@ int sphx_state_sample(sphx_ctx* ctx, double d, const double* n_part, const doubl
  * ms[2] the sum and gate kernels (list form: the row kernel), ms[3] outputs coming back.  Measurement aid for
  * nsc:1422-1527's replacement; replaces nothing in the reference.                                                   */
 int sphx_arb_last_timing(sphx_ctx* ctx, double ms[4]);
+/* ---- radiative transfer: the geometry and the deposition of nsc.rad_heating              nsc:922-965 ----- *
+ * rad_heating's star selection and luminosities (nsc:897-921) and its composition chemistry (nsc:967-1017) stay with the
+ * caller; these entry points take the selected sources a_s (n_src,3) with their `luminosities`, the sampled targets b_q
+ * (n_dst,3), and return what nsc:922-965 form.  With C2 = 3 pi / 80 (the reference's W6_constant, nsc:48 - not the
+ * 315/(64 pi) of the sums), particles p of EVERY type at x_p with h_p = sizes, m_p, mu_p, sigma_p = cross_array:
+ *   w_p = C2 h_p^-2 sigma_p m_p / (mu_p amu)                                                       nsc:928
+ *   ray (s,q), u = b_q - a_s:  d2_p = |(x_p - a_s) x u|^2 / |u|^2                                  nsc:927
+ *   blocked[s,q] = sum_p [d2_p < h_p^2] w_p,   star_distance[s,q] = |u|                            nsc:928-931
+ *     - the whole infinite line, matter behind the star included, as the reference has it.
+ *   over the particles g with ptypes != 1, in the caller's order (G of them):
+ *   gd[q,g] = |x_g - b_q|,  sd2[s,g] = |x_g - a_s|                                                 nsc:941-944
+ *   lum_factor[s,g] = nan_to_num(sd2 sum_q((gd + 1.)^-2 / star_distance[s,q] blocked[s,q]) / sum_q (gd + 1.)^-2)
+ *     - the 1. is one metre, as written in the reference                                           nsc:949
+ *   extinction[g] = w_g,  a_int = pi h_g^2,  df[s,g] = (nan_to_num(sd2)^2 + min(sizes over ptypes == 0)^2) 4 pi
+ *   l[s,g] = nan_to_num(exp(-nan_to_num(lum_factor)) / df L_s a_int extinction)                    nsc:954-961
+ *   lf2[g] = sum_s l dt solar_luminosity,   momentum[g] = sum_s (x_g - a_s)/sd2 l / m_g dt / c     nsc:963-965
+ * nan_to_num is NumPy's; everything else plain IEEE: a degenerate ray (a_s == b_q) has column 0 and distance 0, and its
+ * 0/0 zeroes lum_factor[s,:]; n_dst = 0 gives lum_factor = 0; n_src = 0 gives lf2 = momentum = 0.  The kernel compares
+ * |(x_p - a) x u|^2 with h_p^2 |u|^2 instead of dividing: the column is a top-hat, and a pair within rounding of its
+ * edge may fall on either side (of either evaluation).  The sums over p run in chunks of the particle range fixed by
+ * (n, n_src n_dst) alone and are added in chunk order, without atomics: the same inputs give the same bits on every
+ * call.  solar_luminosity, c, amu: sphx_constants.
+ * mode SPHX_RAD_LINE: the above.  SPHX_RAD_SEGMENT, an extension the reference does not have (parity unpinned, like
+ * clip_grad and visc_mode 1): only particles whose foot point lies between source and target block the ray,
+ * 0 <= (x_p - a).u < |u|^2, half-open - a particle AT the source counts, one AT the target does not; lum_factor and
+ * everything after it use the column the mode produced.
+ * SPHX_E_ARG: a negative count, a NULL required pointer, an unknown mode.
+ * Layout constants a test of the kernels' seams reads: the column kernel stages SPHX_RAD_TILE particles at a time, a
+ * workgroup holds SPHX_RAD_WG_RAYS rays, the particle range is split into up to ceil(2048 / ray tiles) chunks of whole
+ * tiles; the deposit kernel takes SPHX_RAD_SRC_CHUNK sources at a time.                                              */
+#define SPHX_RAD_LINE        0
+#define SPHX_RAD_SEGMENT     1
+#define SPHX_RAD_TILE        256
+#define SPHX_RAD_WG_RAYS     256
+#define SPHX_RAD_SRC_CHUNK   16
+/* sphx_rad_columns (nsc:922-931): the columns alone - the optical depth between any two point sets.  points (n,3);
+ * sizes, mass, mu, cross (n,); blocked (n_src,n_dst); star_distance (n_src,n_dst) or NULL.  n = 0 gives zero columns;
+ * n_src n_dst = 0 writes nothing and returns 0.                                                                    */
+int sphx_rad_columns(sphx_ctx* ctx, int64_t n, const double* points, const double* sizes, const double* mass,
+                     const double* mu, const double* cross, int64_t n_src, const double* src, int64_t n_dst,
+                     const double* dst, int mode, double* blocked /* (n_src,n_dst) */, double* star_distance /* may be NULL */);
+/* sphx_rad_transfer (nsc:922-965): all of the above.  ptypes (n,) f64 0/1/2; luminosities (n_src,).  Outputs in the
+ * reference's order over the G non-star particles - lf2 (G,), momentum (G,3), extinction (G,) - then blocked,
+ * star_distance (n_src,n_dst) and lum_factor (n_src,G); any may be NULL.  SPHX_E_ARG when no particle has ptypes == 0
+ * (the reference raises on the empty min of nsc:957), n = 0 included.                                              */
+int sphx_rad_transfer(sphx_ctx* ctx, int64_t n, const double* points, const double* ptypes, const double* mass,
+                      const double* sizes, const double* cross, const double* mu, int64_t n_src, const double* src,
+                      const double* luminosities, int64_t n_dst, const double* dst, double dt, int mode, double* lf2,
+                      double* momentum, double* extinction, double* blocked, double* star_distance, double* lum_factor);
+/* sphx_state_rad_transfer (nsc:922-965): sphx_rad_transfer on the step loop's device-resident state - the positions,
+ * masses, types, mu and sizes sphx_state_download would return at this moment; cross (n,) in the caller's particle order
+ * (as sphx_state_sample takes n_part).  The sums run in the caller's order: the bits are those of sphx_rad_transfer on
+ * the downloaded state.  SPHX_E_STATE before the first sphx_step (sizes do not exist yet).  It works in buffers of its
+ * own: the next sphx_step gives the bits it would have given without this call.                                    */
+int sphx_state_rad_transfer(sphx_ctx* ctx, const double* cross, int64_t n_src, const double* src,
+                            const double* luminosities, int64_t n_dst, const double* dst, double dt, int mode, double* lf2,
+                            double* momentum, double* extinction, double* blocked, double* star_distance,
+                            double* lum_factor);
+/* Device time of the last of the three calls above on this context, from HIP events on its stream, in ms: ms[0] inputs
+ * going up and prepared (w_p, h_p^2, the non-star list, min(sizes); one host wait), ms[1] the column kernel and the sum
+ * of its chunks, ms[2] spread and deposit, ms[3] outputs coming back.  Measurement aid for nsc:922-965's replacement;
+ * replaces nothing in the reference.                                                                               */
+int sphx_rad_last_timing(sphx_ctx* ctx, double ms[4]);
 int sphx_get_stats(sphx_ctx* ctx, sphx_stats* out);
 int sphx_reset_stats(sphx_ctx* ctx);
 

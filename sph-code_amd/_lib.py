@@ -14,7 +14,8 @@ c_int64_p = C.POINTER(C.c_int64)
 
 
 class SphxConstants(C.Structure):
-    _fields_ = [(n, C.c_double) for n in ("k_B", "amu", "m_h", "m_0", "dt_0", "max_age", "pos_clamp")]
+    _fields_ = [(n, C.c_double) for n in ("k_B", "amu", "m_h", "m_0", "dt_0", "max_age", "pos_clamp", "solar_luminosity",
+                                          "c")]
 
 
 class SphxStats(C.Structure):
@@ -84,6 +85,10 @@ SIGNATURES = {
     "sphx_arb_last_timing": (C.c_int, [_P, _D]),
     "sphx_arb_fields_list": (C.c_int, [_P, C.c_int64] + [_D] * 7 + [C.c_double, C.c_int64, _D, _I, _I] + [_D] * 5 + [_I, _I]),
     "sphx_state_sample": (C.c_int, [_P, C.c_double, _D, _D, C.c_int64, _D, C.c_double] + [_D] * 5 + [_I, _I]),
+    "sphx_rad_columns": (C.c_int, [_P, C.c_int64] + [_D] * 5 + [C.c_int64, _D, C.c_int64, _D, C.c_int, _D, _D]),
+    "sphx_rad_transfer": (C.c_int, [_P, C.c_int64] + [_D] * 6 + [C.c_int64, _D, _D, C.c_int64, _D, C.c_double, C.c_int] + [_D] * 6),
+    "sphx_state_rad_transfer": (C.c_int, [_P, _D, C.c_int64, _D, _D, C.c_int64, _D, C.c_double, C.c_int] + [_D] * 6),
+    "sphx_rad_last_timing": (C.c_int, [_P, _D]),
     "sphx_get_stats": (C.c_int, [_P, C.POINTER(SphxStats)]),
     "sphx_reset_stats": (C.c_int, [_P]),
     "sphx_set_stream": (C.c_int, [_P, C.c_void_p]),

@@ -41,6 +41,8 @@ amu = 1.66053906892e-27
 AU = 149597870700.0
 m_h = 1.0008 * amu
 solar_mass = 1.989e30
+solar_luminosity = 3.846e26
+c = 299792458.0
 m_0 = 10 ** 1.5 * solar_mass
 year = 60. * 60. * 24. * 365.
 dt_0 = year * 250000.
@@ -65,7 +67,7 @@ def context():
     global _ctx
     if _ctx is None:
         _ctx = _lib.Context()
-        _ctx.set_constants(k_B=k, amu=amu, m_h=m_h, m_0=m_0, dt_0=dt_0)
+        _ctx.set_constants(k_B=k, amu=amu, m_h=m_h, m_0=m_0, dt_0=dt_0, solar_luminosity=solar_luminosity, c=c)
     return _ctx
 
 
@@ -519,3 +521,84 @@ def arb_last_timing():
     c = context()
     c.check(c.lib.sphx_arb_last_timing(c.h, dp(out)))
     return dict(zip(("upload", "build", "kernels", "download"), out.tolist()))
+
+
+# ==============================================================================================
+# Radiative transfer: the geometry and the deposition of rad_heating (nsc:922-965)
+# ==============================================================================================
+RAD_MODES = {"line": 0, "segment": 1}
+
+
+def rad_mode_code(mode):
+    """"line" -> 0, "segment" -> 1 (include/sphx.h SPHX_RAD_LINE / SPHX_RAD_SEGMENT); anything else: ValueError."""
+    if not isinstance(mode, str) or mode not in RAD_MODES:
+        raise ValueError("mode must be 'line' or 'segment', not %r" % (mode,))
+    return RAD_MODES[mode]
+
+
+def _pts3(a, what):
+    out = f64(a)
+    if out.size == 0:
+        return np.zeros((0, 3))
+    if out.ndim != 2 or out.shape[1] != 3:
+        raise ValueError("%s must be (M, 3)" % what)
+    return out
+
+
+def rad_columns(positions, sizes, masses, mu_array, cross_array, sources, targets, mode="line"):
+    """The columns of nsc:922-931 between any two point sets -> (blocked, star_distance), each (n_src, n_dst):
+    blocked[s,q] = sum over the particles within their own h of the line through sources[s] and targets[q] of
+    C2 h^-2 cross m / (mu amu), C2 = 3 pi / 80; star_distance[s,q] = |targets[q] - sources[s]|.  mode="segment" (not the
+    reference's reading) counts only particles whose foot point lies between the two (include/sphx.h)."""
+    code = rad_mode_code(mode)
+    pts = _pts3(positions, "positions")
+    n = pts.shape[0]
+    src, dst = _pts3(sources, "sources"), _pts3(targets, "targets")
+    h, m, mu, cr = f64(sizes, (n,)), f64(masses, (n,)), f64(mu_array, (n,)), f64(cross_array, (n,))
+    blocked = np.zeros((src.shape[0], dst.shape[0])); sd = np.zeros((src.shape[0], dst.shape[0]))
+    c_ = context()
+    c_.check(c_.lib.sphx_rad_columns(c_.h, n, dp(pts), dp(h), dp(m), dp(mu), dp(cr), src.shape[0], dp(src), dst.shape[0],
+                                     dp(dst), code, dp(blocked), dp(sd)))
+    return blocked, sd
+
+
+def _rad_outputs(n_gas, n_src, n_dst, full):
+    lf2 = np.zeros(n_gas); mom = np.zeros((n_gas, 3)); ext = np.zeros(n_gas)
+    if not full:
+        return [lf2, mom, ext], [None, None, None]
+    return [lf2, mom, ext], [np.zeros((n_src, n_dst)), np.zeros((n_src, n_dst)), np.zeros((n_src, n_gas))]
+
+
+def rad_transfer(positions, ptypes, masses, sizes, cross_array, mu_array, sources, luminosities, targets, dt, mode="line",
+                 full=False):
+    """Lines 922-965 of nsc.rad_heating (nsc:893), with its argument names: the columns between the selected stars and
+    the sampled gas particles, their spread over every non-star particle, and the energy and momentum deposited
+    -> (lf2 (G,), momentum (G,3), extinction (G,)) over the G particles with ptypes != 1, as rad_heating returns them;
+    full=True: also blocked, star_distance (n_src, n_dst) and lum_factor (n_src, G).
+    What stays with the caller: the star selection and `luminosities` of nsc:897-921 (sources = the reference's rs2,
+    targets = its rg2) and the composition chemistry of nsc:967-1017.  ValueError when no particle has ptypes == 0
+    (the reference raises there too).  mode="segment": include/sphx.h, not the reference's reading."""
+    code = rad_mode_code(mode)
+    pts = _pts3(positions, "positions")
+    n = pts.shape[0]
+    src, dst = _pts3(sources, "sources"), _pts3(targets, "targets")
+    pt, m, h = f64(ptypes, (n,)), f64(masses, (n,)), f64(sizes, (n,))
+    cr, mu = f64(cross_array, (n,)), f64(mu_array, (n,))
+    L = f64(luminosities).reshape(-1)
+    if L.shape[0] != src.shape[0]:
+        raise ValueError("luminosities must have one entry per source")
+    main, extra = _rad_outputs(int(np.count_nonzero(pt != 1)), src.shape[0], dst.shape[0], full)
+    c_ = context()
+    c_.set_constants(amu=amu, solar_luminosity=solar_luminosity, c=c)
+    c_.check(c_.lib.sphx_rad_transfer(c_.h, n, dp(pts), dp(pt), dp(m), dp(h), dp(cr), dp(mu), src.shape[0], dp(src), dp(L),
+                                      dst.shape[0], dp(dst), float(dt), code, *[dp(a) for a in main + extra]))
+    return tuple(main + extra) if full else tuple(main)
+
+
+def rad_last_timing():
+    """Device time of the last rad_columns / rad_transfer call of this module, from HIP events (include/sphx.h
+    sphx_rad_last_timing) -> dict of ms: upload, columns, deposit, download."""
+    out = np.zeros(4)
+    c_ = context()
+    c_.check(c_.lib.sphx_rad_last_timing(c_.h, dp(out)))
+    return dict(zip(("upload", "columns", "deposit", "download"), out.tolist()))

@@ -50,6 +50,8 @@ static void default_constants(sphx_constants* c) {
     c->dt_0 = 60. * 60. * 24. * 365. * 250000.;
     c->max_age = 3e7 * 60. * 60. * 24. * 365.;
     c->pos_clamp = 1e11 * 149597870700.0;
+    c->solar_luminosity = 3.846e26;
+    c->c = 299792458.0;
 }
 
 extern "C" int sphx_version(void) { return 100; }
@@ -176,6 +178,8 @@ extern "C" void sphx_destroy(sphx_ctx* ctx) {
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
     for (int i = 0; i < 5; ++i)
         if (ctx->arb_ev[i]) (void)hipEventDestroy(ctx->arb_ev[i]);
+    for (int i = 0; i < 5; ++i)
+        if (ctx->rad_ev[i]) (void)hipEventDestroy(ctx->rad_ev[i]);
     for (int r = 0; r < 3; ++r)
         for (int i = 0; i < 10; ++i)
             if (ctx->evring[r][i]) (void)hipEventDestroy(ctx->evring[r][i]);

@@ -337,6 +337,12 @@ struct sphx_ctx {
     double arb_tb[6] = {0, 0, 0, 0, 0, 0};
     double arb_ms[4] = {0, 0, 0, 0};            // sphx_arb_last_timing
     hipEvent_t arb_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
+    // radiative transfer (sphx_rad.hip), buffers of its own - a call on the resident state touches nothing the step owns:
+    // staged inputs, SoA particles, rays + their outputs, the chunks' partial columns, non-star flags / offsets / list +
+    // small reductions, per-particle outputs, scan scratch
+    DevBuf rad_in, rad_soa, rad_ray, rad_part, rad_gas, rad_out, rad_tmp;
+    double rad_ms[4] = {0, 0, 0, 0};            // sphx_rad_last_timing
+    hipEvent_t rad_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket

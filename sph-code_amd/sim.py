@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import dp, f64
-from .compat import ARB_FIELDS, visc_mode_code
+from .compat import ARB_FIELDS, rad_mode_code, visc_mode_code
 
 log = logging.getLogger("sph_code_amd")
 
@@ -38,6 +38,7 @@ class Simulation:
         pts = f64(state["points"])
         n = pts.shape[0]
         self.n = n
+        self._ptype = f64(state["particle_type"], (n,)).copy()
         vel = f64(state["velocities"], (n, 3))
         fu = f64(state["f_un"]) if (with_species and state.get("f_un") is not None) else None
         acc = state.get("total_accel")
@@ -171,6 +172,37 @@ class Simulation:
         c = self.ctx
         c.check(c.lib.sphx_arb_last_timing(c.h, dp(ms)))
         return dict(zip(("upload", "build", "kernels", "download"), ms.tolist()))
+
+    def rad_transfer(self, sources, luminosities, targets, cross_array, dt, mode="line", full=False):
+        """Lines 922-965 of nsc.rad_heating on the state as it is on the device (include/sphx.h
+        sphx_state_rad_transfer; after the first step) -> (lf2 (G,), momentum (G,3), extinction (G,)) over the G non-star
+        particles in the order of the uploaded state; full=True: also blocked, star_distance, lum_factor.  The bits are
+        those of compat.rad_transfer on the downloaded state.  cross_array (N,) in the particle order of the uploaded
+        state.  The step loop is not disturbed."""
+        code = rad_mode_code(mode)
+        src = np.ascontiguousarray(f64(sources).reshape(-1, 3))
+        dst = np.ascontiguousarray(f64(targets).reshape(-1, 3))
+        L = f64(luminosities).reshape(-1)
+        if L.shape[0] != src.shape[0]:
+            raise ValueError("luminosities must have one entry per source")
+        cr = f64(cross_array, (self.n,))
+        if not hasattr(self, "_n_gas"):
+            self._n_gas = int(np.count_nonzero(self._ptype != 1))
+        G = self._n_gas
+        out = [np.zeros(G), np.zeros((G, 3)), np.zeros(G)]
+        extra = [np.zeros((src.shape[0], dst.shape[0])), np.zeros((src.shape[0], dst.shape[0])),
+                 np.zeros((src.shape[0], G))] if full else [None, None, None]
+        c = self.ctx
+        c.check(c.lib.sphx_state_rad_transfer(c.h, dp(cr), src.shape[0], dp(src), dp(L), dst.shape[0], dp(dst), float(dt), code,
+                                              *[dp(a) for a in out + extra]))
+        return tuple(out + extra) if full else tuple(out)
+
+    def rad_timing(self):
+        """Device time of the last rad_transfer() from HIP events -> dict of ms: upload, columns, deposit, download."""
+        ms = np.zeros(4)
+        c = self.ctx
+        c.check(c.lib.sphx_rad_last_timing(c.h, dp(ms)))
+        return dict(zip(("upload", "columns", "deposit", "download"), ms.tolist()))
 
     def download_species(self):
         """-> dict: f_un_neighbor (S,N) as nsc.hydro_update returns it (nsc:671), and with an AGB table also
