@@ -461,6 +461,56 @@ int sphx_state_rad_transfer(sphx_ctx* ctx, const double* cross, int64_t n_src, c
  * of its chunks, ms[2] spread and deposit, ms[3] outputs coming back.  Measurement aid for nsc:922-965's replacement;
  * replaces nothing in the reference.                                                                               */
 int sphx_rad_last_timing(sphx_ctx* ctx, double ms[4]);
+/* ---- nsc.rad_cooling(positions, particle_type, masses, sizes, cross_array, f_un, neighbor, mu_array, T, dt)
+ *                                                                                         nsc:1019-1176 ----- *
+ * Recombination and its cooling on the list `neighbors` returned (drv:276).  sizes and cross_array are accepted by the
+ * reference and never read: they are not arguments here.  Species columns of f_un (n,s), s >= 6: 0 H2, 1 He, 2 H, 3 H+,
+ * 4 He+, 5 e-.  With W(p,j) = Weigh2(x_p, x_j, m_p, d) (nsc:673-676, h(m) = (m/m_0)^(1/3) d), g_p = [type_p == 0],
+ * t4 = T_p / 1e4, for every gas row j with a gas neighbour and every p = neighbor[j,k]:
+ *   base = W / (mu_p m_h) g_p (m_h, not amu);  n_e, n_H+, n_He+, n_H0 = base f_p[5], f_p[3], f_p[4], f_p[2], each kept
+ *   where > 0;  rel_w = W g [W g > 0] / Weigh2(x_p, x_p, m_p, d)                           nsc:1044-1057
+ *   H_eff = 4.13e-19 t4^(-0.7131 - 0.0115 ln t4), He_eff = 2.72e-19 t4^-0.789, H2_eff = 7.3e-23 0.5 (T_p/100)^(1/2),
+ *   e_H = (0.684 - 0.0416 ln t4 + 0.54 t4^0.37) k T_p, e_He = (0.684 - 0.0416 ln(t4/4)) k T_p       nsc:1060-1067
+ *   over the entries with n_e > 0: num_e = sum n_e, A = sum H_eff n_e, B = sum He_eff n_e; num_H+ = sum n_H+,
+ *   num_He+ = sum n_He+; Cn = sum H2_eff n_H0 over n_H0 > 0                                 nsc:1075-1084
+ *   f_e = min((A num_H+ + B num_He+) / num_e dt, 0.9999), s_H = nan_to_num(A/(A+B)), s_He = nan_to_num(B/(A+B)),
+ *   f_H = f_e s_H, f_He = f_e s_He, f_Hn = min(Cn dt, 0.9999),
+ *   E_H = sum H_eff n_e e_H s_H dt, E_He = sum He_eff n_e e_He s_He dt (n_e > 0)             nsc:1088-1097
+ *   into every neighbour p: energy[3] += E_H rel_w, energy[4] += E_He rel_w, rec[2] += f_Hn [n_H0 > 0] rel_w,
+ *   rec[3], rec[4], rec[5] += f_H, f_He, f_e [n_e > 0] rel_w, rel += rel_w                   nsc:1102-1110
+ * then per particle (nsc:1112-1176): rec, energy /= rel + 1e-90; H+_frac, He+_frac, e_frac = f[5] rec[3,4,5];
+ * mult_factor; f[1] += He+_frac mult, f[2] += H+_frac mult, f[3,4,5] -= ...; rec[2] capped at 0.9999,
+ * f[0] += f[2] rec[2] / 2, f[2] -= f[2] rec[2]; energy = energy[3] f[3] + energy[4] f[4] (f before the transfers);
+ * every particle's s species - stars and dust included - divided by their sum.  f is nan_to_num(f_un) throughout.
+ * Quirks of the reference kept on purpose:
+ *   1. np.maximum(a, b, c) at nsc:1122 has three positional arguments and the third is `out`:
+ *      mult_factor = max(H+ ratio, He+ ratio); the electron ratio never enters.
+ *   2. nsc:1124-1125 test mf2 > 0.9999 and mf2 < 0.9999: mf2 == 0.9999 exactly keeps its value.
+ *   3. nan_to_num maps +-inf to +-DBL_MAX, not to 0; the x/0 ratios of nsc:1122 rely on it.
+ *   4. The two mass-budget prints (nsc:1027, 1172) are not reproduced.
+ *   5. Only rows 2-5 of rec_array and rows 3-4 of the energy accumulator are ever non-zero.
+ *   A row with num_e = 0 is NaN inside and contributes exactly zero through nan_to_num and the pair masks.
+ * Two repairs: np.min(x, 0.9999) at nsc:1089 and nsc:1094 passes 0.9999 as `axis` and raises
+ * TypeError; the reading implemented - and pinned by tests/golden/cool_*.npz - is np.minimum.
+ * Ours: a list entry outside [0, n) (the missing-neighbour value n) contributes nothing; the coefficients of a neighbour
+ * whose T is not in (0, inf) are zero.  A row is taken to hold distinct indices, as `neighbors` returns them; a repeated
+ * index is added once per occurrence (the reference's fancy-indexed += adds it once).
+ * The sums over K run in list order; a particle adds the rows that hold it in ascending row index, the order of the
+ * reference's loop, from a reverse list (4 bytes per pair) sorted per particle: no floating-point atomic, the same inputs
+ * give the same bits on every call.  m_0, m_h, k_B: sphx_constants.
+ * Outputs: final_comp (n,s), energy (n,), rec_array (s,n); row_table (n,6) or NULL: per row f_Hn, f_H, f_He, f_e (each
+ * nan_to_num'ed, as the scatter reads them), E_H, E_He; zeros for a row that does not contribute.
+ * SPHX_E_ARG: a NULL required pointer, n < 1, k < 1, s < 6, non-finite dt or d, n k beyond 2^31.
+ * SPHX_COOL_WG: lanes (rows, particles) of a workgroup of its kernels - a layout constant the tests' sizes straddle. */
+#define SPHX_COOL_WG         256
+int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const double* ptype,
+                     const double* mass, const double* f_un, const int64_t* neighbor, const double* mu, const double* T,
+                     double dt, double d, double* final_comp, double* energy, double* rec_array,
+                     double* row_table /* may be NULL: (n,6) */);
+/* Device time of the last sphx_rad_cooling call on this context, from HIP events on its stream, in ms: ms[0] inputs going
+ * up, records and the K-major list, ms[1] the row pass, ms[2] reverse list (scan, one host wait, fill, sort), gather and
+ * epilogue, ms[3] outputs coming back.  Measurement aid; replaces nothing in the reference.                          */
+int sphx_cool_last_timing(sphx_ctx* ctx, double ms[4]);
 int sphx_get_stats(sphx_ctx* ctx, sphx_stats* out);
 int sphx_reset_stats(sphx_ctx* ctx);
 

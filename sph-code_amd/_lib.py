@@ -89,6 +89,8 @@ SIGNATURES = {
     "sphx_rad_transfer": (C.c_int, [_P, C.c_int64] + [_D] * 6 + [C.c_int64, _D, _D, C.c_int64, _D, C.c_double, C.c_int] + [_D] * 6),
     "sphx_state_rad_transfer": (C.c_int, [_P, _D, C.c_int64, _D, _D, C.c_int64, _D, C.c_double, C.c_int] + [_D] * 6),
     "sphx_rad_last_timing": (C.c_int, [_P, _D]),
+    "sphx_rad_cooling": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int] + [_D] * 4 + [_I, _D, _D, C.c_double, C.c_double] + [_D] * 4),
+    "sphx_cool_last_timing": (C.c_int, [_P, _D]),
     "sphx_get_stats": (C.c_int, [_P, C.POINTER(SphxStats)]),
     "sphx_reset_stats": (C.c_int, [_P]),
     "sphx_set_stream": (C.c_int, [_P, C.c_void_p]),

@@ -14,6 +14,7 @@ for the functions the driver sph/code_running.py ("drv") calls on the SPH inner 
     del_pressure           nsc:755-774      drv:456
     artificial_viscosity   nsc:788-816      drv:458
     crossing_time          nsc:776-786      drv:222
+    rad_cooling            nsc:1019-1176    drv:276
 
 Hidden inputs are honoured the way the driver uses them: it assigns `nsc.d`, `nsc.d_0`,
 `nsc.dt`, `nsc.dt_0` (drv:68-75,231) and the functions read the module attribute at call
@@ -602,3 +603,36 @@ def rad_last_timing():
     c_ = context()
     c_.check(c_.lib.sphx_rad_last_timing(c_.h, dp(out)))
     return dict(zip(("upload", "columns", "deposit", "download"), out.tolist()))
+
+
+# ==============================================================================================
+# Radiative cooling: rad_cooling (nsc:1019-1176)
+# ==============================================================================================
+def rad_cooling(positions, particle_type, masses, sizes, cross_array, f_un, neighbor, mu_array, T, dt, d=None, full=False):
+    """nsc:1019-1176 -> (final_comp (N,S), energy (N,), rec_array (S,N)); full=True appends the (N,6) table of the rows'
+    scalars (f_Hn, f_H, f_He, f_e, E_H, E_He).  sizes and cross_array are accepted and never read, as in the reference.
+    The two np.min calls of nsc:1089, 1094 (a TypeError as committed) are read as np.minimum; the other quirks are kept
+    (include/sphx.h, sphx_rad_cooling).  f_un passes through nan_to_num on ingest, as nsc:1023 does."""
+    nb, n, K = _nk(neighbor)
+    pts, pt, m = f64(positions, (n, 3)), f64(particle_type, (n,)), f64(masses, (n,))
+    mu, temp, dd = f64(mu_array, (n,)), f64(T, (n,)), _d(d)
+    fun = np.nan_to_num(f64(f_un))
+    if fun.ndim != 2 or fun.shape[0] != n:
+        raise ValueError("f_un must be (N, S)")
+    S = fun.shape[1]
+    final = np.empty((n, S)); energy = np.empty(n); rec = np.empty((S, n))
+    table = np.empty((n, 6)) if full else None
+    c_ = context()
+    c_.set_constants(k_B=k, m_h=m_h, m_0=m_0)
+    c_.check(c_.lib.sphx_rad_cooling(c_.h, n, K, S, dp(pts), dp(pt), dp(m), dp(fun), ip(nb), dp(mu), dp(temp), float(dt), dd,
+                                     dp(final), dp(energy), dp(rec), dp(table)))
+    return (final, energy, rec, table) if full else (final, energy, rec)
+
+
+def cool_last_timing():
+    """Device time of the last rad_cooling call of this module, from HIP events (include/sphx.h sphx_cool_last_timing)
+    -> dict of ms: upload, rows, gather, download."""
+    out = np.zeros(4)
+    c_ = context()
+    c_.check(c_.lib.sphx_cool_last_timing(c_.h, dp(out)))
+    return dict(zip(("upload", "rows", "gather", "download"), out.tolist()))

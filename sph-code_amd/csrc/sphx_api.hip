@@ -180,6 +180,8 @@ extern "C" void sphx_destroy(sphx_ctx* ctx) {
         if (ctx->arb_ev[i]) (void)hipEventDestroy(ctx->arb_ev[i]);
     for (int i = 0; i < 5; ++i)
         if (ctx->rad_ev[i]) (void)hipEventDestroy(ctx->rad_ev[i]);
+    for (int i = 0; i < 5; ++i)
+        if (ctx->cool_ev[i]) (void)hipEventDestroy(ctx->cool_ev[i]);
     for (int r = 0; r < 3; ++r)
         for (int i = 0; i < 10; ++i)
             if (ctx->evring[r][i]) (void)hipEventDestroy(ctx->evring[r][i]);

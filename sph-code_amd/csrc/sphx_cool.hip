@@ -1,0 +1,299 @@
+// sphx_cool.hip - rad_cooling (nsc:1019-1176): recombination and its cooling by the linearised Draine model, on the
+// neighbour list `neighbors` returned.
+//
+// The reference loops over the gas rows j; each row forms seven sums over its K neighbours, six row scalars from them,
+// and scatter-adds seven values into its neighbours' rows.  Here:
+//   prep      one lane per particle: a 128-byte record of everything a pair needs from the neighbour (CoolRec,
+//             sphx_cool_pair.h) - the five temperature coefficients are formed N times, not N K times.
+//   list      one lane per list entry: the (n,k) int64 list becomes the K-major int32 list the row pass reads
+//             coalesced (an entry outside [0, n) becomes -1 and contributes nothing), the rows that contribute are
+//             flagged (a gas row with a gas neighbour, nsc:1028-1030) and the gas-gas pairs are counted per neighbour.
+//   rows      one lane per row: the sums over K in list order, the six row scalars -> table (n,6).
+//   reverse   the scatter is turned round: for each particle p the rows j that hold it - count (above), exclusive scan,
+//             fill, then each slice sorted, so that p adds its contributions in ascending j, the order the reference's
+//             loop adds them in.  An entry is a 4-byte row index.  The fill's order is whatever the atomics give; the
+//             sort removes it: the same inputs give the same bits on every call.  No floating-point atomic anywhere.
+//   gather    one lane per particle p: walks its slice (of any length: a hub particle sits in many rows), recomputes
+//             the pair's weight and masks from its own record and x_j - cool_pair on the same r^2 the row pass used -
+//             reads row j's six scalars, and then runs the elementwise epilogue (nsc:1112-1176) on what it holds.
+// Vector stores from plain C++ only.  Every operation separately rounded, as NumPy's are.
+#include "sphx_internal.h"
+#include "sphx_cool_pair.h"
+#include <rocprim/rocprim.hpp>
+#pragma clang fp contract(off)
+
+#define COOL_WG SPHX_COOL_WG
+
+// np.minimum(x, 0.9999): a NaN stays a NaN (nsc:1089, 1094 in their repaired reading)
+__device__ __forceinline__ double cool_cap(double x) { return x < 0.9999 ? x : (x != x ? x : 0.9999); }
+
+struct CoolPrep {
+    int n, s;
+    const double *pos, *ptype, *m, *mu, *T, *fun;      // (n,3), (n,) x 4, (n,s)
+    double d, m0, m_h, kB;
+    CoolRec* rec;
+};
+__global__ __launch_bounds__(COOL_WG) void cool_prep_kernel(CoolPrep a) {
+    const int i = blockIdx.x * COOL_WG + threadIdx.x;
+    if (i >= a.n) return;
+    CoolRec r;
+    r.x = a.pos[3 * (size_t)i]; r.y = a.pos[3 * (size_t)i + 1]; r.z = a.pos[3 * (size_t)i + 2];
+    const double m = a.m[i], d9 = pow9(a.d);
+    const bool gas = a.ptype[i] == 0.0;
+    const double c = weigh2_c(m, a.m0);
+    r.h2 = weigh2_h2(m, a.d, a.m0);
+    r.cg = gas ? c : 0.0;
+    r.winv = 1.0 / weigh2_w(c, r.h2 - 0.0, d9);
+    r.mm = a.mu[i] * a.m_h;
+    const double* f = a.fun + (size_t)i * a.s;
+    r.f2 = sphx_nan_to_num(f[2]); r.f3 = sphx_nan_to_num(f[3]); r.f4 = sphx_nan_to_num(f[4]); r.f5 = sphx_nan_to_num(f[5]);
+    cool_coeffs(gas ? a.T[i] : 0.0, a.kB, r);
+    a.rec[i] = r;
+}
+
+// entry e = (j, kk) of the (n,k) list
+__global__ __launch_bounds__(COOL_WG) void cool_list_kernel(int n, int npad, int k, const long long* __restrict__ nb,
+                                                            const double* __restrict__ ptype, int* __restrict__ nbr,
+                                                            int* cnt, int* flag) {
+    const long long e = (long long)blockIdx.x * COOL_WG + threadIdx.x;
+    if (e >= (long long)n * k) return;
+    const int j = (int)(e / k), kk = (int)(e - (long long)j * k);
+    const long long q = nb[e];
+    const int p = (q >= 0 && q < n) ? (int)q : -1;
+    nbr[(size_t)kk * npad + j] = p;
+    if (p >= 0 && ptype[j] == 0.0 && ptype[p] == 0.0) {
+        atomicAdd(&cnt[p], 1);
+        flag[j] = 1;
+    }
+}
+// slice of p: the rows that hold it, in the order the atomics hand out (sorted afterwards)
+__global__ __launch_bounds__(COOL_WG) void cool_fill_kernel(int n, int npad, int k, const int* __restrict__ nbr,
+                                                            const double* __restrict__ ptype, const int* __restrict__ start,
+                                                            int* cur, int* __restrict__ rev) {
+    const long long e = (long long)blockIdx.x * COOL_WG + threadIdx.x;
+    if (e >= (long long)npad * k) return;
+    const int kk = (int)(e / npad), j = (int)(e - (long long)kk * npad);
+    if (j >= n) return;
+    const int p = nbr[e];
+    if (p >= 0 && ptype[j] == 0.0 && ptype[p] == 0.0) rev[start[p] + atomicAdd(&cur[p], 1)] = j;
+}
+
+struct CoolRows {
+    int n, npad, k;
+    const int* nbr;
+    const int* flag;
+    const CoolRec* rec;
+    double dt, d;
+    double* tab;                                        // (n,6): f_Hn, f_H, f_He, f_e, E_H, E_He
+};
+__global__ __launch_bounds__(COOL_WG) void cool_row_kernel(CoolRows a) {
+    const int j = blockIdx.x * COOL_WG + threadIdx.x;
+    if (j >= a.n) return;
+    double* t = a.tab + 6 * (size_t)j;
+    if (!a.flag[j]) {
+        t[0] = t[1] = t[2] = t[3] = t[4] = t[5] = 0.0;
+        return;
+    }
+    const double xj = a.rec[j].x, yj = a.rec[j].y, zj = a.rec[j].z, d9 = pow9(a.d);
+    double num_e = 0.0, A = 0.0, B = 0.0, SH = 0.0, SHe = 0.0, nHp = 0.0, nHep = 0.0, Cn = 0.0;
+    for (int kk = 0; kk < a.k; ++kk) {
+        const int p = a.nbr[(size_t)kk * a.npad + j];
+        if (p < 0) continue;
+        const CoolRec r = a.rec[p];
+        const double dx = r.x - xj, dy = r.y - yj, dz = r.z - zj;
+        const CoolPair pr = cool_pair(r, dx * dx + dy * dy + dz * dz, d9);
+        if (pr.ne > 0.0) {                                               // the [n_e > 0] selections of nsc:1075-1097
+            const double th = r.Hf * pr.ne, the = r.Hef * pr.ne;
+            num_e += pr.ne; A += th; B += the;
+            SH += th * r.eH; SHe += the * r.eHe;
+        }
+        nHp += pr.nHp; nHep += pr.nHep;                                  // (zero where not positive)
+        if (pr.nH0 > 0.0) Cn += r.H2f * pr.nH0;
+    }
+    const double fe = cool_cap((A * nHp + B * nHep) / num_e * a.dt);     // nsc:1088-1089; num_e = 0: NaN
+    const double sH = sphx_nan_to_num(A / (A + B)), sHe = sphx_nan_to_num(B / (A + B));     // nsc:1091-1092
+    t[0] = sphx_nan_to_num(cool_cap(Cn * a.dt));                         // nsc:1094, 1105
+    t[1] = sphx_nan_to_num(fe * sH);                                     // nsc:1091, 1106
+    t[2] = sphx_nan_to_num(fe * sHe);
+    t[3] = sphx_nan_to_num(fe);
+    t[4] = SH * sH * a.dt;                                               // nsc:1096-1097
+    t[5] = SHe * sHe * a.dt;
+}
+
+struct CoolGather {
+    int n, s;
+    const int *start, *rev;
+    const CoolRec* rec;
+    const double* tab;
+    const double* fun;                                  // (n,s)
+    double d;
+    double *final_comp, *energy, *rec_array;            // (n,s), (n,), (s,n)
+};
+__global__ __launch_bounds__(COOL_WG) void cool_gather_kernel(CoolGather a) {
+    const int p = blockIdx.x * COOL_WG + threadIdx.x;
+    if (p >= a.n) return;
+    const CoolRec me = a.rec[p];
+    const double d9 = pow9(a.d);
+    double e3 = 0.0, e4 = 0.0, r2 = 0.0, r3 = 0.0, r4 = 0.0, r5 = 0.0, rel = 0.0;
+    const int t1 = a.start[p + 1];
+    for (int t = a.start[p]; t < t1; ++t) {                              // ascending j: the reference's loop order
+        const int j = a.rev[t];
+        const double dx = me.x - a.rec[j].x, dy = me.y - a.rec[j].y, dz = me.z - a.rec[j].z;
+        const CoolPair pr = cool_pair(me, dx * dx + dy * dy + dz * dz, d9);
+        const double* row = a.tab + 6 * (size_t)j;
+        const double w = pr.relw;
+        e3 += sphx_nan_to_num(row[4] * w);                               // nsc:1102-1103
+        e4 += sphx_nan_to_num(row[5] * w);
+        if (pr.nH0 > 0.0) r2 += row[0] * w;                              // nsc:1105-1108
+        if (pr.ne > 0.0) { r3 += row[1] * w; r4 += row[2] * w; r5 += row[3] * w; }
+        rel += w;                                                        // nsc:1110
+    }
+    // ---- epilogue, nsc:1112-1176 ----
+    const double den = rel + 1e-90;
+    r2 = sphx_nan_to_num(r2 / den); r3 = sphx_nan_to_num(r3 / den); r4 = sphx_nan_to_num(r4 / den); r5 = sphx_nan_to_num(r5 / den);
+    e3 = e3 / den; e4 = e4 / den;
+    const double* fin = a.fun + (size_t)p * a.s;
+    double f0 = sphx_nan_to_num(fin[0]), f1 = sphx_nan_to_num(fin[1]);
+    double f2 = me.f2, f3 = me.f3, f4 = me.f4, f5 = me.f5;
+    const double Hp = f5 * r3, Hep = f5 * r4, el = f5 * r5;              // nsc:1118-1120
+    const double qa = sphx_nan_to_num(Hp / f3), qb = sphx_nan_to_num(Hep / f4);
+    const double mf2 = qa > qb ? qa : qb;                                // nsc:1122: the third argument is `out`
+    double mult = mf2;
+    if (mf2 > 0.9999) mult = 0.9999 / mf2;                               // nsc:1124-1126; mf2 == 0.9999 keeps its value
+    if (mf2 < 0.9999) mult = 1.0;
+    if (f5 < 1e-10) mult = 0.0;
+    a.energy[p] = e3 * f3 + e4 * f4;                                     // nsc:1138
+    f1 += Hep * mult; f2 += Hp * mult;                                   // nsc:1148-1153
+    f3 -= Hp * mult; f4 -= Hep * mult; f5 -= el * mult;
+    r2 = r2 < 0.9999 ? r2 : 0.9999;                                      // nsc:1155 (r2 is no NaN here)
+    const double H2 = f2 * r2;
+    f0 += H2 / 2.0; f2 -= H2;                                            // nsc:1158-1159
+    double sum = ((((f0 + f1) + f2) + f3) + f4) + f5;                    // nsc:1174: over all S species, in their order
+    for (int c = 6; c < a.s; ++c) sum += sphx_nan_to_num(fin[c]);
+    double* fo = a.final_comp + (size_t)p * a.s;
+    fo[0] = f0 / sum; fo[1] = f1 / sum; fo[2] = f2 / sum; fo[3] = f3 / sum; fo[4] = f4 / sum; fo[5] = f5 / sum;
+    for (int c = 6; c < a.s; ++c) fo[c] = sphx_nan_to_num(fin[c]) / sum;
+    const size_t n = (size_t)a.n;
+    a.rec_array[p] = 0.0; a.rec_array[n + p] = 0.0;
+    a.rec_array[2 * n + p] = r2; a.rec_array[3 * n + p] = r3; a.rec_array[4 * n + p] = r4; a.rec_array[5 * n + p] = r5;
+    for (int c = 6; c < a.s; ++c) a.rec_array[(size_t)c * n + p] = 0.0;
+}
+
+// =====================================================================================================================
+// host side
+// =====================================================================================================================
+// events of a call: [0] start, [1] inputs on the device, records and list built, [2] rows done, [3] reverse list, gather
+// and epilogue done, [4] outputs on the host
+static int cool_end(sphx_ctx* ctx) {                    // (after the call's last synchronise)
+    for (int i = 0; i < 4; ++i) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, ctx->cool_ev[i], ctx->cool_ev[i + 1]));
+        ctx->cool_ms[i] = ms;
+    }
+    return SPHX_OK;
+}
+
+extern "C" int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const double* ptype,
+                                const double* mass, const double* f_un, const int64_t* neighbor, const double* mu,
+                                const double* T, double dt, double d, double* final_comp, double* energy, double* rec_array,
+                                double* row_table) {
+    if (!ctx) return SPHX_E_ARG;
+    if (n < 1 || k < 1 || s < 6)
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_rad_cooling: n=%lld, k=%d, s=%d (need n >= 1, k >= 1, s >= 6)", (long long)n, k, s);
+    if (n > 0x7FFFFFF0ll || sphx_pad64(n) * (int64_t)k > 0x7FFFFFF0ll || n * (int64_t)s > (1ll << 40))
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_rad_cooling: n=%lld x k=%d (or x s=%d) out of range", (long long)n, k, s);
+    if (!(dt - dt == 0.0) || !(d - d == 0.0))
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_rad_cooling: dt=%g, d=%g must be finite", dt, d);
+    NEED(points); NEED(ptype); NEED(mass); NEED(f_un); NEED(neighbor); NEED(mu); NEED(T);
+    NEED(final_comp); NEED(energy); NEED(rec_array);
+    HIPCHK(hipSetDevice(ctx->device));
+    for (int i = 0; i < 5; ++i)
+        if (!ctx->cool_ev[i]) HIPCHK(hipEventCreate(&ctx->cool_ev[i]));
+    for (int i = 0; i < 4; ++i) ctx->cool_ms[i] = 0.0;
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipEventRecord(ctx->cool_ev[0], st));
+    const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), ns = nn * (size_t)s, nk = nn * (size_t)k;
+    // ---- inputs: points (3n) | ptype | mass | mu | T (n each) | f_un (n s); the list as given ----
+    SPHX_TRY(sphx_ensure(ctx, ctx->cool_in, (7 * nn + ns) * sizeof(double)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->cool_nb, nk * sizeof(int64_t)));
+    double* in = ctx->cool_in.as<double>();
+    double *d_pos = in, *d_pt = in + 3 * nn, *d_m = in + 4 * nn, *d_mu = in + 5 * nn, *d_T = in + 6 * nn, *d_fun = in + 7 * nn;
+    HIPCHK(hipMemcpyAsync(d_pos, points, 3 * nn * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_pt, ptype, nn * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_m, mass, nn * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_mu, mu, nn * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_T, T, nn * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_fun, f_un, ns * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctx->cool_nb.p, neighbor, nk * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    // ---- records; the K-major list, the rows' flags, the counts ----
+    SPHX_TRY(sphx_ensure(ctx, ctx->cool_rec, nn * sizeof(CoolRec)));
+    // ints: nbr (k npad) | cnt (n + 1) | cur (n + 1) | flag (n + 1) | start (n + 1), each part a multiple of four
+    const size_t n1 = (nn + 4) & ~size_t(3);
+    SPHX_TRY(sphx_ensure(ctx, ctx->cool_int, ((size_t)k * npad + 4 * n1) * sizeof(int)));
+    int* nbr = ctx->cool_int.as<int>();
+    int *cnt = nbr + (size_t)k * npad, *cur = cnt + n1, *flag = cur + n1, *start = flag + n1;
+    HIPCHK(hipMemsetAsync(cnt, 0, 3 * n1 * sizeof(int), st));
+    CoolPrep pa;
+    pa.n = (int)n; pa.s = s; pa.pos = d_pos; pa.ptype = d_pt; pa.m = d_m; pa.mu = d_mu; pa.T = d_T; pa.fun = d_fun;
+    pa.d = d; pa.m0 = ctx->cst.m_0; pa.m_h = ctx->cst.m_h; pa.kB = ctx->cst.k_B;
+    pa.rec = ctx->cool_rec.as<CoolRec>();
+    const unsigned nblk = (unsigned)((nn + COOL_WG - 1) / COOL_WG);
+    hipLaunchKernelGGL(cool_prep_kernel, dim3(nblk), dim3(COOL_WG), 0, st, pa);
+    hipLaunchKernelGGL(cool_list_kernel, dim3((unsigned)((nk + COOL_WG - 1) / COOL_WG)), dim3(COOL_WG), 0, st, (int)n, (int)npad, k,
+                       (const long long*)ctx->cool_nb.p, d_pt, nbr, cnt, flag);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->cool_ev[1], st));
+    // ---- rows ----
+    SPHX_TRY(sphx_ensure(ctx, ctx->cool_tab, 6 * nn * sizeof(double)));
+    CoolRows ra;
+    ra.n = (int)n; ra.npad = (int)npad; ra.k = k; ra.nbr = nbr; ra.flag = flag; ra.rec = pa.rec; ra.dt = dt; ra.d = d;
+    ra.tab = ctx->cool_tab.as<double>();
+    hipLaunchKernelGGL(cool_row_kernel, dim3(nblk), dim3(COOL_WG), 0, st, ra);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->cool_ev[2], st));
+    // ---- the reverse list: scan, fill, sort each slice ----
+    size_t scan_bytes = 0;
+    HIPCHK(rocprim::exclusive_scan(nullptr, scan_bytes, cnt, start, 0, nn + 1, rocprim::plus<int>(), st));
+    SPHX_TRY(sphx_ensure(ctx, ctx->cool_tmp, scan_bytes + 64));
+    HIPCHK(rocprim::exclusive_scan(ctx->cool_tmp.p, scan_bytes, cnt, start, 0, nn + 1, rocprim::plus<int>(), st));
+    HIPCHK(hipMemcpyAsync(ctx->pinned, start + n, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const size_t M = (size_t)*(const int*)ctx->pinned;
+    if (M > nk) return sphx_set_err(ctx, SPHX_E_HIP, "sphx_rad_cooling: reverse list of %zu entries from %zu pairs", M, nk);
+    SPHX_TRY(sphx_ensure(ctx, ctx->cool_rev, 2 * (M + 4) * sizeof(int)));
+    int* rev_raw = ctx->cool_rev.as<int>();
+    int* rev = rev_raw + M + 4;
+    if (M > 0) {
+        hipLaunchKernelGGL(cool_fill_kernel, dim3((unsigned)(((size_t)k * npad + COOL_WG - 1) / COOL_WG)), dim3(COOL_WG), 0, st, (int)n,
+                           (int)npad, k, nbr, d_pt, start, cur, rev_raw);
+        HIPCHK(hipGetLastError());
+        unsigned bits = 1;
+        while (bits < 32 && (1ull << bits) < (unsigned long long)n) ++bits;
+        size_t sort_bytes = 0;
+        HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
+        SPHX_TRY(sphx_ensure(ctx, ctx->cool_tmp, sort_bytes + 64));
+        HIPCHK(rocprim::segmented_radix_sort_keys(ctx->cool_tmp.p, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
+    }
+    // ---- gather and epilogue: final_comp (n s) | energy (n) | rec_array (s n) ----
+    SPHX_TRY(sphx_ensure(ctx, ctx->cool_out, (2 * ns + nn) * sizeof(double)));
+    CoolGather ga;
+    ga.n = (int)n; ga.s = s; ga.start = start; ga.rev = rev; ga.rec = pa.rec; ga.tab = ra.tab; ga.fun = d_fun; ga.d = d;
+    ga.final_comp = ctx->cool_out.as<double>(); ga.energy = ga.final_comp + ns; ga.rec_array = ga.energy + nn;
+    hipLaunchKernelGGL(cool_gather_kernel, dim3(nblk), dim3(COOL_WG), 0, st, ga);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->cool_ev[3], st));
+    HIPCHK(hipMemcpyAsync(final_comp, ga.final_comp, ns * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(energy, ga.energy, nn * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rec_array, ga.rec_array, ns * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (row_table) HIPCHK(hipMemcpyAsync(row_table, ra.tab, 6 * nn * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(ctx->cool_ev[4], st));
+    HIPCHK(hipStreamSynchronize(st));
+    return cool_end(ctx);
+}
+
+// Device time of the last sphx_rad_cooling call on this context, from HIP events on its stream.
+extern "C" int sphx_cool_last_timing(sphx_ctx* ctx, double ms[4]) {
+    if (!ctx || !ms) return SPHX_E_ARG;
+    for (int i = 0; i < 4; ++i) ms[i] = ctx->cool_ms[i];
+    return SPHX_OK;
+}

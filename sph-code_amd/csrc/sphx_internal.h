@@ -343,6 +343,12 @@ struct sphx_ctx {
     DevBuf rad_in, rad_soa, rad_ray, rad_part, rad_gas, rad_out, rad_tmp;
     double rad_ms[4] = {0, 0, 0, 0};            // sphx_rad_last_timing
     hipEvent_t rad_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
+    // rad_cooling (sphx_cool.hip), buffers of its own: staged inputs, the list as given, the particles' records, ints (the
+    // K-major list, counts, cursors, flags, slice starts), the reverse list (as filled | sorted), the rows' table, outputs,
+    // scan / sort scratch
+    DevBuf cool_in, cool_nb, cool_rec, cool_int, cool_rev, cool_tab, cool_out, cool_tmp;
+    double cool_ms[4] = {0, 0, 0, 0};           // sphx_cool_last_timing
+    hipEvent_t cool_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket

@@ -8,19 +8,8 @@
 // cancellations such as h_j^2 - r^2 at the kernel edge reproduce the reference bit for bit.
 #pragma clang fp contract(off)
 #include <float.h>
+#include "sphx_weigh2.h"           // PI64, pow9, weigh2 (nsc:673-676)
 
-#define PI64 201.06192982974676      /* 64 pi */
-
-__device__ __forceinline__ double pow9(double d) {
-    double d2 = d * d, d4 = d2 * d2;
-    return d4 * d4 * d;
-}
-// nsc:673-676  m*315*(m_0/m)^3*((m/m_0)^(2/3) d^2 - r^2)^3/(64 pi d^9)
-__device__ __forceinline__ double weigh2(double r2, double m, double d, double m0, double d9) {
-    const double a = m0 / m;
-    const double q = pow(m / m0, 2.0 / 3.0) * (d * d) - r2;
-    return m * 315.0 * (a * a * a) * (q * q * q) / (PI64 * d9);
-}
 // nsc:678-681
 __device__ __forceinline__ double weigh2_dust(double r2, double m, double ds) {
     const double q = ds * ds - r2;
