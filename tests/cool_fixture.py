@@ -56,10 +56,22 @@ def _knn(n, seed):
     return pos, order, np.sqrt(np.maximum(np.take_along_axis(d2, order, axis=1), 0.0))
 
 
-def cloud(n, K, seed, dust=0.1, stars=0.02, neutral=False):
+@functools.lru_cache(maxsize=None)
+def _knn_tree(n, seed):
+    """_knn's positions and lists from a k-d tree (scipy.spatial.cKDTree): no (n, n) matrix, so n may be tens of thousands.
+    Column 0 = self; an exact tie may come in another order than _knn's stable sort gives (the list is an input)."""
+    from scipy.spatial import cKDTree
+    pos = np.random.RandomState(seed).rand(n, 3) * 3e16
+    dist, order = cKDTree(pos).query(pos, k=min(65, n))
+    dist, order = dist.reshape(n, -1), order.reshape(n, -1).astype(np.int64)
+    assert np.array_equal(order[:, 0], np.arange(n))            # (no two seeded positions coincide)
+    return pos, order, dist
+
+
+def cloud(n, K, seed, dust=0.1, stars=0.02, neutral=False, tree=False):
     """A small seeded cloud with an exact kNN list (column 0 = self; entries equal to n where n <= K) and an ionised
-    composition -> dict of compat.rad_cooling's arguments by name, and d."""
-    pos, order, dist = _knn(n, seed)
+    composition -> dict of compat.rad_cooling's arguments by name, and d.  tree=True: the list from _knn_tree (any n)."""
+    pos, order, dist = _knn_tree(n, seed) if tree else _knn(n, seed)
     rs = np.random.RandomState(seed + 1000)
     pt = np.zeros(n)
     u = rs.rand(n)
