@@ -515,13 +515,18 @@ def photoionization_arb(points, arb_points, mass, N_PART, photoionization, parti
                       d=d, fields=("photoionization",))["photoionization"]
 
 
+def _last_timing(getter, names):
+    """The four stage times (ms) a family's sphx_*_last_timing reports for the module context, under `names`."""
+    out = np.zeros(4)
+    c = context()
+    c.check(getattr(c.lib, getter)(c.h, dp(out)))
+    return dict(zip(names, out.tolist()))
+
+
 def arb_last_timing():
     """Device time of the last *_arb / arb_fields call of this module, from HIP events (include/sphx.h
     sphx_arb_last_timing) -> dict of ms: upload, build, kernels, download."""
-    out = np.zeros(4)
-    c = context()
-    c.check(c.lib.sphx_arb_last_timing(c.h, dp(out)))
-    return dict(zip(("upload", "build", "kernels", "download"), out.tolist()))
+    return _last_timing("sphx_arb_last_timing", ("upload", "build", "kernels", "download"))
 
 
 # ==============================================================================================
@@ -599,10 +604,7 @@ def rad_transfer(positions, ptypes, masses, sizes, cross_array, mu_array, source
 def rad_last_timing():
     """Device time of the last rad_columns / rad_transfer call of this module, from HIP events (include/sphx.h
     sphx_rad_last_timing) -> dict of ms: upload, columns, deposit, download."""
-    out = np.zeros(4)
-    c_ = context()
-    c_.check(c_.lib.sphx_rad_last_timing(c_.h, dp(out)))
-    return dict(zip(("upload", "columns", "deposit", "download"), out.tolist()))
+    return _last_timing("sphx_rad_last_timing", ("upload", "columns", "deposit", "download"))
 
 
 # ==============================================================================================
@@ -632,7 +634,4 @@ def rad_cooling(positions, particle_type, masses, sizes, cross_array, f_un, neig
 def cool_last_timing():
     """Device time of the last rad_cooling call of this module, from HIP events (include/sphx.h sphx_cool_last_timing)
     -> dict of ms: upload, rows, gather, download."""
-    out = np.zeros(4)
-    c_ = context()
-    c_.check(c_.lib.sphx_cool_last_timing(c_.h, dp(out)))
-    return dict(zip(("upload", "rows", "gather", "download"), out.tolist()))
+    return _last_timing("sphx_cool_last_timing", ("upload", "rows", "gather", "download"))

@@ -145,7 +145,7 @@ extern "C" int sphx_create(sphx_ctx** out, int device) {
     }
     bool ok = hipSetDevice(device) == hipSuccess &&
               sphx_stream_create(&ctx->stream, 0) == hipSuccess &&
-              hipHostMalloc(&ctx->pinned, 16384, hipHostMallocDefault) == hipSuccess;
+              hipHostMalloc((void**)&ctx->pinned, sizeof(PinnedLayout), hipHostMallocDefault) == hipSuccess;
     ctx->own_stream = ctx->stream;
     for (int i = 0; ok && i < 10; ++i) ok = hipEventCreate(&ctx->ev[i]) == hipSuccess;
     for (int r = 0; ok && r < 3; ++r)
@@ -176,12 +176,9 @@ extern "C" void sphx_destroy(sphx_ctx* ctx) {
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (int i = 0; i < 10; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    for (int i = 0; i < 5; ++i)
-        if (ctx->arb_ev[i]) (void)hipEventDestroy(ctx->arb_ev[i]);
-    for (int i = 0; i < 5; ++i)
-        if (ctx->rad_ev[i]) (void)hipEventDestroy(ctx->rad_ev[i]);
-    for (int i = 0; i < 5; ++i)
-        if (ctx->cool_ev[i]) (void)hipEventDestroy(ctx->cool_ev[i]);
+    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t})
+        for (int i = 0; i < 5; ++i)
+            if (t->ev[i]) (void)hipEventDestroy(t->ev[i]);
     for (int r = 0; r < 3; ++r)
         for (int i = 0; i < 10; ++i)
             if (ctx->evring[r][i]) (void)hipEventDestroy(ctx->evring[r][i]);
@@ -241,6 +238,47 @@ static int download(sphx_ctx* ctx, void* host, const void* dev, size_t bytes) {
     HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
     return SPHX_OK;
 }
+int sphx_upload_f64(sphx_ctx* ctx, const CopyF64* t, int nt) {
+    for (int i = 0; i < nt; ++i)
+        if (t[i].host)
+            HIPCHK(hipMemcpyAsync(const_cast<void*>(t[i].dev), t[i].host, t[i].count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    return SPHX_OK;
+}
+int sphx_download_f64(sphx_ctx* ctx, const CopyF64* t, int nt) {
+    for (int i = 0; i < nt; ++i)
+        if (t[i].host && t[i].dev && t[i].count > 0)
+            HIPCHK(hipMemcpyAsync(const_cast<void*>(t[i].host), t[i].dev, t[i].count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    return SPHX_OK;
+}
+
+// ---- the side calls' stage timer ----------------------------------------------------------------
+int StageTimer::begin(sphx_ctx* ctx) {
+    for (int i = 0; i < 5; ++i)
+        if (!ev[i]) HIPCHK(hipEventCreate(&ev[i]));
+    for (int i = 0; i < 4; ++i) ms[i] = 0.0;
+    return mark(ctx, 0);
+}
+int StageTimer::mark(sphx_ctx* ctx, int i) {
+    HIPCHK(hipEventRecord(ev[i], ctx->stream));
+    return SPHX_OK;
+}
+int StageTimer::end(sphx_ctx* ctx) {
+    for (int i = 0; i < 4; ++i) {
+        float t = 0.f;
+        HIPCHK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+        ms[i] = t;
+    }
+    return SPHX_OK;
+}
+// Device time of the four stages of the family's last call on this context, from HIP events on its stream.
+static int last_timing(sphx_ctx* ctx, StageTimer sphx_ctx::*t, double ms[4]) {
+    if (!ctx || !ms) return SPHX_E_ARG;
+    for (int i = 0; i < 4; ++i) ms[i] = (ctx->*t).ms[i];
+    return SPHX_OK;
+}
+extern "C" int sphx_arb_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::arb_t, ms); }
+extern "C" int sphx_rad_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::rad_t, ms); }
+extern "C" int sphx_cool_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::cool_t, ms); }
 
 // =============================================================================================
 // nsc.neighbors                                                                nsc:541-552
@@ -513,16 +551,16 @@ static int step_cell_hint(sphx_ctx* ctx, int64_t n, double* cell_hint) {
         // copied out right after the previous step's search: no wait on that step's tail
         HIPCHK(hipEventSynchronize(ctx->lag_halias[ctx->lag_hslot] ? ctx->lag_halias[ctx->lag_hslot]
                                                                      : ctx->lag_hev[ctx->lag_hslot]));
-        hs = (const double*)((char*)ctx->pinned + LAG_OFF + 512 * ctx->lag_hslot + 256);
+        hs = ctx->pinned->lag[ctx->lag_hslot].hs;
         // the same copy carries the previous search's counters
         const u64* sv = (const u64*)hs;           // slots SC_HSUM ..: [5] SC_NFAILQ [6] SC_SHORT [7] SC_FARQ [8] SC_BADHINT
         for (int q = 0; q < 10; ++q) ctx->knn_lag[q] = sv[(SC_NFAILQ - SC_HSUM) + q];      // .. SC_KGDBG + 2
         ctx->knn_lag_valid = true;
     } else {
-        HIPCHK(hipMemcpyAsync((char*)ctx->pinned + 256, ctx->scal.as<double>() + SC_HSUM, 4 * sizeof(double),
+        HIPCHK(hipMemcpyAsync(ctx->pinned->hsum, ctx->scal.as<double>() + SC_HSUM, sizeof(ctx->pinned->hsum),
                               hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        hs = (const double*)((char*)ctx->pinned + 256);
+        hs = ctx->pinned->hsum;
     }
     const double hmean = hs[3] > 0.0 ? hs[0] / hs[3] : 0.0;
     if (hmean > 0.0 && isfinite(hmean)) {
@@ -611,7 +649,7 @@ static int step_search(sphx_ctx* ctx, int k, double dist, hipEvent_t* ev) {
 static int step_h_sums_out(sphx_ctx* ctx, int64_t n, const double* h, hipStream_t stream) {
     SPHX_TRY(sphx_hsum(ctx, n, h, stream));
     const int hsl = ctx->lag_hslot ^ 1;
-    HIPCHK(hipMemcpyAsync((char*)ctx->pinned + LAG_OFF + 512 * hsl + 256, ctx->scal.as<double>() + SC_HSUM,
+    HIPCHK(hipMemcpyAsync(ctx->pinned->lag[hsl].hs, ctx->scal.as<double>() + SC_HSUM,
                           (SC_KGDBG + 2 - SC_HSUM + 1) * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipEventRecord(ctx->lag_hev[hsl], stream));
     ctx->lag_halias[hsl] = nullptr;
@@ -800,7 +838,7 @@ extern "C" int sphx_step(sphx_ctx* ctx, int nsteps, int k, double dist, int firs
         SPHX_TRY(collect_stats(ctx, (ring + 1) % 3));  // two steps ago: finished long since, no wait
     }
     if (per_call) HIPCHK(hipEventRecord(ctx->ev[9], ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->pinned, ctx->scal.p, SC_NSLOTS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->pinned->scal, ctx->scal.p, SC_NSLOTS * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     for (int r = 0; r < 3; ++r) SPHX_TRY(collect_stats(ctx, (int)((ctx->step_count + r) % 3)));   // oldest first
     if (per_call) {                                        // the call's wall time on the stream, over all its steps
@@ -808,8 +846,8 @@ extern "C" int sphx_step(sphx_ctx* ctx, int nsteps, int k, double dist, int firs
         HIPCHK(hipEventElapsedTime(&tot, ctx->ev[8], ctx->ev[9]));
         ctx->stats.ms_total += tot;
     }
-    const u64* sc = (const u64*)ctx->pinned;
-    ctx->dt_last = ((const double*)ctx->pinned)[SC_DT];
+    const u64* sc = ctx->pinned->scal;
+    memcpy(&ctx->dt_last, &sc[SC_DT], sizeof(double));
     ctx->stats.candidates = (int64_t)sc[SC_CAND];
     ctx->stats.retries = (int64_t)sc[SC_RETRY];
     ctx->stats.fallback_queries = (int64_t)(u32)sc[SC_NFAILQ];
@@ -960,7 +998,7 @@ extern "C" int sphx_state_download_species(sphx_ctx* ctx, double* F, double* Z, 
 }
 
 int sphx_badc_read(sphx_ctx* ctx) {
-    u64* hb = (u64*)((char*)ctx->pinned + 8192);
+    u64* hb = ctx->pinned->badc;
     HIPCHK(hipMemcpyAsync(hb, ctx->badc.p, (size_t)BADC_BUCKETS * BADC_STRIDE * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     u64 tot[4] = {0, 0, 0, 0};

@@ -20,7 +20,7 @@
 // member by member.  R may be the whole cloud; the sums never depend on it.
 //
 // List form: one lane per CSR row, in list order (arb_list_kernel) - what pins the arithmetic to the reference.
-#include "sphx_internal.h"
+#include "sphx_wave.h"
 #include "sphx_arb_pair.h"
 #include <rocprim/rocprim.hpp>
 
@@ -65,22 +65,6 @@ __device__ __forceinline__ void arb_store_rec(ArbRec* dst, const ArbRec& r) {
     q[4] = make_double2(r.T, r.pw);  q[5] = make_double2(r.val, r.pad);
 }
 
-__device__ __forceinline__ double arb_wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double arb_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double arb_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // {max sizes, max support, sum of supports, particles with a support} -> part[block][4], then out[4]
 #define ARB_RED_BLOCKS 256
 __global__ __launch_bounds__(256) void arb_reduce_kernel(int n, ArbPartIn in, double* part) {
@@ -96,7 +80,7 @@ __global__ __launch_bounds__(256) void arb_reduce_kernel(int n, ArbPartIn in, do
         if (in.sizes && t == 2.0 && s > sup) sup = s;
         if (sup > 0.0 && sup <= DBL_MAX) { mxu = fmax(mxu, sup); su += sup; cn += 1.0; }
     }
-    mxs = arb_wave_max(mxs); mxu = arb_wave_max(mxu); su = arb_wave_sum(su); cn = arb_wave_sum(cn);
+    mxs = wave_max_f64(mxs); mxu = wave_max_f64(mxu); su = wave_sum_f64(su); cn = wave_sum_f64(cn);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { sm[w][0] = mxs; sm[w][1] = mxu; sm[w][2] = su; sm[w][3] = cn; }
     __syncthreads();
@@ -113,7 +97,7 @@ __global__ __launch_bounds__(64) void arb_reduce_final(int nb, const double* par
     for (int b = threadIdx.x; b < nb; b += 64) {
         mxs = fmax(mxs, part[4 * b]); mxu = fmax(mxu, part[4 * b + 1]); su += part[4 * b + 2]; cn += part[4 * b + 3];
     }
-    mxs = arb_wave_max(mxs); mxu = arb_wave_max(mxu); su = arb_wave_sum(su); cn = arb_wave_sum(cn);
+    mxs = wave_max_f64(mxs); mxu = wave_max_f64(mxu); su = wave_sum_f64(su); cn = wave_sum_f64(cn);
     if (threadIdx.x == 0) { out[0] = mxs; out[1] = mxu; out[2] = su; out[3] = cn; }
 }
 
@@ -224,9 +208,9 @@ __global__ __launch_bounds__(64) void arb_grid_kernel(ArbGridArgs a) {
     if (live) {
         const GridParams g = a.g;
         // the wave's box, in space and in cell units
-        const double lox = arb_wave_min(act ? qx : INFINITY), hix = arb_wave_max(act ? qx : -INFINITY);
-        const double loy = arb_wave_min(act ? qy : INFINITY), hiy = arb_wave_max(act ? qy : -INFINITY);
-        const double loz = arb_wave_min(act ? qz : INFINITY), hiz = arb_wave_max(act ? qz : -INFINITY);
+        const double lox = wave_min_f64(act ? qx : INFINITY), hix = wave_max_f64(act ? qx : -INFINITY);
+        const double loy = wave_min_f64(act ? qy : INFINITY), hiy = wave_max_f64(act ? qy : -INFINITY);
+        const double loz = wave_min_f64(act ? qz : INFINITY), hiz = wave_max_f64(act ? qz : -INFINITY);
         const double tlx = (lox - g.xmin) * g.inv_cell, thx = (hix - g.xmin) * g.inv_cell;
         const double tly = (loy - g.ymin) * g.inv_cell, thy = (hiy - g.ymin) * g.inv_cell;
         const double tlz = (loz - g.zmin) * g.inv_cell, thz = (hiz - g.zmin) * g.inv_cell;
@@ -434,7 +418,6 @@ __global__ __launch_bounds__(64) void arb_list_kernel(int m, int n, const double
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-static int arb_end(sphx_ctx* ctx);
 struct ArbHostOut { double *density, *dust_density, *temperature, *dust_temperature, *photoionization; int64_t* count; };
 
 // device output block [6][m] in ctx->arb_out, pointers only for what the caller wants and the inputs allow
@@ -450,17 +433,17 @@ static int arb_out_ptrs(sphx_ctx* ctx, int64_t m, const ArbHostOut& h, bool has_
     return SPHX_OK;
 }
 static int arb_out_download(sphx_ctx* ctx, int64_t m, const ArbHostOut& h, const ArbOutPtrs& o, int64_t* candidates) {
-    const size_t mb = (size_t)m * sizeof(double);
-    struct P { void* host; const void* dev; };
-    P ps[] = {{h.density, o.density}, {h.dust_density, o.dust_density}, {h.temperature, o.temperature},
-              {h.dust_temperature, o.dust_temperature}, {h.photoionization, o.photoionization}, {h.count, o.count}};
-    for (const P& p : ps)
-        if (p.host && p.dev && m > 0) HIPCHK(hipMemcpyAsync(p.host, p.dev, mb, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync((char*)ctx->pinned + 64, ctx->arb_red.as<double>() + 8, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipEventRecord(ctx->arb_ev[4], ctx->stream));
+    const size_t md = (size_t)m;                           // (count: int64, the width of a double)
+    const CopyF64 ps[] = {{h.density, o.density, md}, {h.dust_density, o.dust_density, md}, {h.temperature, o.temperature, md},
+                          {h.dust_temperature, o.dust_temperature, md}, {h.photoionization, o.photoionization, md},
+                          {h.count, o.count, md}};
+    SPHX_TRY(sphx_download_f64(ctx, ps, 6));
+    u64* cand = &ctx->pinned->side.cand;
+    HIPCHK(hipMemcpyAsync(cand, ctx->arb_red.as<double>() + 8, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    SPHX_TRY(ctx->arb_t.mark(ctx, 4));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (candidates) *candidates = (int64_t) * (const u64*)((const char*)ctx->pinned + 64);
-    return arb_end(ctx);
+    if (candidates) *candidates = (int64_t)*cand;
+    return ctx->arb_t.end(ctx);
 }
 // ctx->arb_red: [0..3] the reduction's result, [8] the candidates counter (u64), [16 ..] block partials
 static int arb_red_prepare(sphx_ctx* ctx) {
@@ -469,23 +452,6 @@ static int arb_red_prepare(sphx_ctx* ctx) {
     return SPHX_OK;
 }
 
-// events of a call: [0] start, [1] inputs on the device, [2] geometry and records built, [3] sums and gate done, [4]
-// outputs on the host
-static int arb_begin(sphx_ctx* ctx) {
-    for (int i = 0; i < 5; ++i)
-        if (!ctx->arb_ev[i]) HIPCHK(hipEventCreate(&ctx->arb_ev[i]));
-    for (int i = 0; i < 4; ++i) ctx->arb_ms[i] = 0.0;
-    HIPCHK(hipEventRecord(ctx->arb_ev[0], ctx->stream));
-    return SPHX_OK;
-}
-static int arb_end(sphx_ctx* ctx) {                     // (after the call's last synchronise)
-    for (int i = 0; i < 4; ++i) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->arb_ev[i], ctx->arb_ev[i + 1]));
-        ctx->arb_ms[i] = ms;
-    }
-    return SPHX_OK;
-}
 static bool arb_ball_hit(const sphx_ctx* ctx, int64_t ball_id, int64_t n, int64_t m) {
     return ball_id != 0 && ctx->arb_ball_id == ball_id && ctx->arb_ball_n == n && ctx->arb_ball_m == m;
 }
@@ -511,7 +477,7 @@ static int arb_run_grid(sphx_ctx* ctx, int64_t n, const ArbPartIn& in, int64_t m
         HIPCHK(hipMemcpyAsync(ctx->arb_q.p, arb_points, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     }
     SPHX_TRY(sphx_ensure(ctx, ctx->arb_acc, (size_t)mpad * (ARB_NACC * sizeof(double) + sizeof(int))));
-    HIPCHK(hipEventRecord(ctx->arb_ev[1], ctx->stream));
+    SPHX_TRY(ctx->arb_t.mark(ctx, 1));
     // supports: the ball's radius and, for a new geometry, the cell size
     double R = radius, cell_hint = 0.0;
     if (!hit || !(radius > 0.0)) {
@@ -520,10 +486,9 @@ static int arb_run_grid(sphx_ctx* ctx, int64_t n, const ArbPartIn& in, int64_t m
         hipLaunchKernelGGL(arb_reduce_kernel, dim3(rb), dim3(256), 0, ctx->stream, (int)n, in, red + 16);
         hipLaunchKernelGGL(arb_reduce_final, dim3(1), dim3(64), 0, ctx->stream, rb, red + 16, red);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(ctx->pinned, red, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        const double* rd = ctx->pinned->side.red;
+        HIPCHK(hipMemcpyAsync(ctx->pinned->side.red, red, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        double rd[4];
-        memcpy(rd, ctx->pinned, sizeof(rd));
         if (!(radius > 0.0)) R = rd[0];
         cell_hint = rd[3] > 0.0 ? rd[2] / rd[3] : 0.0;     // the mean support
     }
@@ -577,17 +542,17 @@ static int arb_run_grid(sphx_ctx* ctx, int64_t n, const ArbPartIn& in, int64_t m
                            wcut, rec, wide);
         HIPCHK(hipGetLastError());
         SPHX_TRY(sphx_excl_scan_int(ctx, wide, woff, (int)n));
-        HIPCHK(hipMemcpyAsync((char*)ctx->pinned + 32, woff + n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(&ctx->pinned->side.count, woff + n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         hipLaunchKernelGGL(arb_cell_max, dim3((unsigned)((g.ncells + 255) / 256)), dim3(256), 0, ctx->stream, g.ncells,
                            cell_start, rec, ctx->arb_cmax.as<double>());
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        nwide = *(const int*)((const char*)ctx->pinned + 32);
+        nwide = ctx->pinned->side.count;
         SPHX_TRY(sphx_ensure(ctx, ctx->arb_wrec, (size_t)(nwide > 0 ? nwide : 1) * sizeof(ArbRec)));
         if (nwide > 0)
             hipLaunchKernelGGL(arb_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n, in, perm, sp,
                                wide, woff, ctx->arb_wrec.as<ArbRec>());
     }
-    HIPCHK(hipEventRecord(ctx->arb_ev[2], ctx->stream));
+    SPHX_TRY(ctx->arb_t.mark(ctx, 2));
     ArbGridArgs a;
     a.m = (int)m;
     a.q = ctx->arb_q.as<double>();
@@ -611,7 +576,7 @@ static int arb_run_grid(sphx_ctx* ctx, int64_t n, const ArbPartIn& in, int64_t m
     else HIPCHK(hipMemsetAsync(a.acc, 0, (size_t)mpad * (ARB_NACC * sizeof(double) + sizeof(int)), ctx->stream));
     hipLaunchKernelGGL(arb_gate_kernel, dim3(nb), dim3(64), 0, ctx->stream, a, hout.count ? 1 : 0, o);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->arb_ev[3], ctx->stream));
+    SPHX_TRY(ctx->arb_t.mark(ctx, 3));
     return arb_out_download(ctx, m, hout, o, candidates);
 }
 
@@ -636,16 +601,14 @@ static int arb_stage_particles(sphx_ctx* ctx, int64_t n, const double* points, c
         x = ctx->in_b.as<double>(); y = ctx->in_c.as<double>(); z = ctx->in_d.as<double>();
         SPHX_TRY(sphx_aos_to_soa3(ctx, n, ctx->in_a.as<double>(), x, y, z));
     }
-    struct U { const double* host; DevBuf* dev; const double** slot; };
     in->x = x; in->y = y; in->z = z;
-    in->m = in->ptype = in->sizes = in->T = in->npart = in->value = nullptr;
-    U us[] = {{mass, &ctx->in_e, &in->m}, {ptype, &ctx->in_f, &in->ptype}, {sizes, &ctx->in_g, &in->sizes},
-              {T, &ctx->in_h, &in->T}, {n_part, &ctx->in_i, &in->npart}, {value, &ctx->in_j, &in->value}};
-    for (const U& u : us) {
-        if (!u.host) continue;
-        HIPCHK(hipMemcpyAsync(u.dev->p, u.host, nb, hipMemcpyHostToDevice, ctx->stream));
-        *u.slot = u.dev->as<double>();
-    }
+    const size_t nd = (size_t)n;
+    const CopyF64 us[] = {{mass, ctx->in_e.p, nd}, {ptype, ctx->in_f.p, nd}, {sizes, ctx->in_g.p, nd},
+                          {T, ctx->in_h.p, nd}, {n_part, ctx->in_i.p, nd}, {value, ctx->in_j.p, nd}};
+    SPHX_TRY(sphx_upload_f64(ctx, us, 6));
+    auto given = [](const double* host, const DevBuf& b) { return host ? b.as<double>() : nullptr; };
+    in->m = given(mass, ctx->in_e); in->ptype = given(ptype, ctx->in_f); in->sizes = given(sizes, ctx->in_g);
+    in->T = given(T, ctx->in_h); in->npart = given(n_part, ctx->in_i); in->value = given(value, ctx->in_j);
     in->aux_id = nullptr;
     in->d = d;
     in->m0 = ctx->cst.m_0;
@@ -663,7 +626,7 @@ extern "C" int sphx_arb_fields(sphx_ctx* ctx, int64_t n, const double* points, c
     if (!sizes && !(radius > 0.0))
         return sphx_set_err(ctx, SPHX_E_ARG, "sphx_arb_fields: radius <= 0 means max(sizes), but sizes is NULL");
     HIPCHK(hipSetDevice(ctx->device));
-    SPHX_TRY(arb_begin(ctx));
+    SPHX_TRY(ctx->arb_t.begin(ctx));
     const bool hit = arb_ball_hit(ctx, ball_id, n, m);
     ArbPartIn in;
     SPHX_TRY(arb_stage_particles(ctx, n, hit ? nullptr : points, mass, particle_type, sizes, T, n_part, value, d, &in));
@@ -688,7 +651,7 @@ extern "C" int sphx_arb_fields_list(sphx_ctx* ctx, int64_t n, const double* poin
     const int64_t nnz = row_start[m];
     if (nnz > row_start[0] && !members) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_arb_fields_list: argument members is NULL");
     HIPCHK(hipSetDevice(ctx->device));
-    SPHX_TRY(arb_begin(ctx));
+    SPHX_TRY(ctx->arb_t.begin(ctx));
     ctx->arb_ball_id = 0;                                  // (the query buffers of a held ball are overwritten below)
     ArbPartIn in;
     SPHX_TRY(arb_stage_particles(ctx, n, points, mass, particle_type, sizes, T, n_part, value, d, &in));
@@ -704,16 +667,16 @@ extern "C" int sphx_arb_fields_list(sphx_ctx* ctx, int64_t n, const double* poin
     HIPCHK(hipMemcpyAsync(ctx->arb_q.p, arb_points, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->arb_key.p, row_start, ((size_t)m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     if (nnz > 0) HIPCHK(hipMemcpyAsync(ctx->arb_tmp.p, members, (size_t)nnz * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipEventRecord(ctx->arb_ev[1], ctx->stream));
+    SPHX_TRY(ctx->arb_t.mark(ctx, 1));
     hipLaunchKernelGGL(arb_record_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, ctx->stream, (int)n, in,
                        (const int*)nullptr, (const double*)nullptr, 0.0, ctx->arb_rec.as<ArbRec>(), (int*)nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->arb_ev[2], ctx->stream));
+    SPHX_TRY(ctx->arb_t.mark(ctx, 2));
     hipLaunchKernelGGL(arb_list_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, (int)m, (int)n,
                        ctx->arb_q.as<double>(), ctx->arb_key.as<long long>(), ctx->arb_tmp.as<long long>(),
                        ctx->arb_rec.as<ArbRec>(), o, reinterpret_cast<u64*>(ctx->arb_red.as<double>() + 8));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->arb_ev[3], ctx->stream));
+    SPHX_TRY(ctx->arb_t.mark(ctx, 3));
     return arb_out_download(ctx, m, hout, o, candidates);
 }
 
@@ -731,7 +694,7 @@ extern "C" int sphx_state_sample(sphx_ctx* ctx, double d, const double* n_part, 
     const int64_t n = ctx->n;
     SPHX_TRY(arb_check_common(ctx, "sphx_state_sample", n, m, arb_points));
     HIPCHK(hipSetDevice(ctx->device));
-    SPHX_TRY(arb_begin(ctx));
+    SPHX_TRY(ctx->arb_t.begin(ctx));
     const size_t nb = (size_t)n * sizeof(double);
     StateArrays& s = ctx->st;
     ArbPartIn in;
@@ -748,33 +711,9 @@ extern "C" int sphx_state_sample(sphx_ctx* ctx, double d, const double* n_part, 
     }
     in.d = d;
     in.m0 = ctx->cst.m_0;
-    // what sphx_build_grid changes on the host side of the context
-    const GridParams g0 = ctx->grid;
-    const double* tbox0 = ctx->tbox;
-    double tb0[6], cl0[3], ch0[3];
-    memcpy(tb0, ctx->tbox_h, sizeof(tb0)); memcpy(cl0, ctx->clip_lo, sizeof(cl0)); memcpy(ch0, ctx->clip_hi, sizeof(ch0));
-    const bool cv0 = ctx->clip_valid, cu0 = ctx->cells_unsorted;
-    const int olev0 = ctx->olev.L;
-    const int64_t cells0 = ctx->stats.cells;
-    const double cs0 = ctx->stats.cell_size;
-    const int* mp0 = ctx->map_perm;
-    const int* qo0 = ctx->qorder;
     const ArbHostOut hout{density, dust_density, temperature, dust_temperature, photoionization, count};
+    const GridHostState saved = sphx_grid_host_save(ctx);
     const int rc = arb_run_grid(ctx, n, in, m, arb_points, radius, hout, candidates, 0, false);
-    ctx->grid = g0;
-    ctx->tbox = tbox0;
-    memcpy(ctx->tbox_h, tb0, sizeof(tb0)); memcpy(ctx->clip_lo, cl0, sizeof(cl0)); memcpy(ctx->clip_hi, ch0, sizeof(ch0));
-    ctx->clip_valid = cv0; ctx->cells_unsorted = cu0;
-    ctx->olev.L = olev0;
-    ctx->stats.cells = cells0; ctx->stats.cell_size = cs0;
-    ctx->map_perm = mp0; ctx->qorder = qo0;
+    sphx_grid_host_restore(ctx, saved);
     return rc;
-}
-
-// Device time of the last sphx_arb_fields / sphx_arb_fields_list / sphx_state_sample call on this context, from HIP events
-// on its stream.
-extern "C" int sphx_arb_last_timing(sphx_ctx* ctx, double ms[4]) {
-    if (!ctx || !ms) return SPHX_E_ARG;
-    for (int i = 0; i < 4; ++i) ms[i] = ctx->arb_ms[i];
-    return SPHX_OK;
 }

@@ -182,17 +182,6 @@ __global__ __launch_bounds__(COOL_WG) void cool_gather_kernel(CoolGather a) {
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-// events of a call: [0] start, [1] inputs on the device, records and list built, [2] rows done, [3] reverse list, gather
-// and epilogue done, [4] outputs on the host
-static int cool_end(sphx_ctx* ctx) {                    // (after the call's last synchronise)
-    for (int i = 0; i < 4; ++i) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->cool_ev[i], ctx->cool_ev[i + 1]));
-        ctx->cool_ms[i] = ms;
-    }
-    return SPHX_OK;
-}
-
 extern "C" int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const double* ptype,
                                 const double* mass, const double* f_un, const int64_t* neighbor, const double* mu,
                                 const double* T, double dt, double d, double* final_comp, double* energy, double* rec_array,
@@ -207,23 +196,16 @@ extern "C" int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const do
     NEED(points); NEED(ptype); NEED(mass); NEED(f_un); NEED(neighbor); NEED(mu); NEED(T);
     NEED(final_comp); NEED(energy); NEED(rec_array);
     HIPCHK(hipSetDevice(ctx->device));
-    for (int i = 0; i < 5; ++i)
-        if (!ctx->cool_ev[i]) HIPCHK(hipEventCreate(&ctx->cool_ev[i]));
-    for (int i = 0; i < 4; ++i) ctx->cool_ms[i] = 0.0;
+    SPHX_TRY(ctx->cool_t.begin(ctx));
     hipStream_t st = ctx->stream;
-    HIPCHK(hipEventRecord(ctx->cool_ev[0], st));
     const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), ns = nn * (size_t)s, nk = nn * (size_t)k;
     // ---- inputs: points (3n) | ptype | mass | mu | T (n each) | f_un (n s); the list as given ----
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_in, (7 * nn + ns) * sizeof(double)));
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_nb, nk * sizeof(int64_t)));
     double* in = ctx->cool_in.as<double>();
     double *d_pos = in, *d_pt = in + 3 * nn, *d_m = in + 4 * nn, *d_mu = in + 5 * nn, *d_T = in + 6 * nn, *d_fun = in + 7 * nn;
-    HIPCHK(hipMemcpyAsync(d_pos, points, 3 * nn * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_pt, ptype, nn * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_m, mass, nn * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_mu, mu, nn * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_T, T, nn * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_fun, f_un, ns * sizeof(double), hipMemcpyHostToDevice, st));
+    const CopyF64 us[] = {{points, d_pos, 3 * nn}, {ptype, d_pt, nn}, {mass, d_m, nn}, {mu, d_mu, nn}, {T, d_T, nn}, {f_un, d_fun, ns}};
+    SPHX_TRY(sphx_upload_f64(ctx, us, 6));
     HIPCHK(hipMemcpyAsync(ctx->cool_nb.p, neighbor, nk * sizeof(int64_t), hipMemcpyHostToDevice, st));
     // ---- records; the K-major list, the rows' flags, the counts ----
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_rec, nn * sizeof(CoolRec)));
@@ -242,7 +224,7 @@ extern "C" int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const do
     hipLaunchKernelGGL(cool_list_kernel, dim3((unsigned)((nk + COOL_WG - 1) / COOL_WG)), dim3(COOL_WG), 0, st, (int)n, (int)npad, k,
                        (const long long*)ctx->cool_nb.p, d_pt, nbr, cnt, flag);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->cool_ev[1], st));
+    SPHX_TRY(ctx->cool_t.mark(ctx, 1));
     // ---- rows ----
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_tab, 6 * nn * sizeof(double)));
     CoolRows ra;
@@ -250,15 +232,12 @@ extern "C" int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const do
     ra.tab = ctx->cool_tab.as<double>();
     hipLaunchKernelGGL(cool_row_kernel, dim3(nblk), dim3(COOL_WG), 0, st, ra);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->cool_ev[2], st));
+    SPHX_TRY(ctx->cool_t.mark(ctx, 2));
     // ---- the reverse list: scan, fill, sort each slice ----
-    size_t scan_bytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, scan_bytes, cnt, start, 0, nn + 1, rocprim::plus<int>(), st));
-    SPHX_TRY(sphx_ensure(ctx, ctx->cool_tmp, scan_bytes + 64));
-    HIPCHK(rocprim::exclusive_scan(ctx->cool_tmp.p, scan_bytes, cnt, start, 0, nn + 1, rocprim::plus<int>(), st));
-    HIPCHK(hipMemcpyAsync(ctx->pinned, start + n, sizeof(int), hipMemcpyDeviceToHost, st));
+    SPHX_TRY(sphx_excl_scan_int(ctx, cnt, start, (int)n));             // (cnt[n] = 0: the memset above; both start on 16-byte boundaries)
+    HIPCHK(hipMemcpyAsync(&ctx->pinned->side.count, start + n, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    const size_t M = (size_t)*(const int*)ctx->pinned;
+    const size_t M = (size_t)ctx->pinned->side.count;
     if (M > nk) return sphx_set_err(ctx, SPHX_E_HIP, "sphx_rad_cooling: reverse list of %zu entries from %zu pairs", M, nk);
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_rev, 2 * (M + 4) * sizeof(int)));
     int* rev_raw = ctx->cool_rev.as<int>();
@@ -281,19 +260,10 @@ extern "C" int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const do
     ga.final_comp = ctx->cool_out.as<double>(); ga.energy = ga.final_comp + ns; ga.rec_array = ga.energy + nn;
     hipLaunchKernelGGL(cool_gather_kernel, dim3(nblk), dim3(COOL_WG), 0, st, ga);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->cool_ev[3], st));
-    HIPCHK(hipMemcpyAsync(final_comp, ga.final_comp, ns * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(energy, ga.energy, nn * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(rec_array, ga.rec_array, ns * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (row_table) HIPCHK(hipMemcpyAsync(row_table, ra.tab, 6 * nn * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(ctx->cool_ev[4], st));
+    SPHX_TRY(ctx->cool_t.mark(ctx, 3));
+    const CopyF64 ds[] = {{final_comp, ga.final_comp, ns}, {energy, ga.energy, nn}, {rec_array, ga.rec_array, ns}, {row_table, ra.tab, 6 * nn}};
+    SPHX_TRY(sphx_download_f64(ctx, ds, 4));
+    SPHX_TRY(ctx->cool_t.mark(ctx, 4));
     HIPCHK(hipStreamSynchronize(st));
-    return cool_end(ctx);
-}
-
-// Device time of the last sphx_rad_cooling call on this context, from HIP events on its stream.
-extern "C" int sphx_cool_last_timing(sphx_ctx* ctx, double ms[4]) {
-    if (!ctx || !ms) return SPHX_E_ARG;
-    for (int i = 0; i < 4; ++i) ms[i] = ctx->cool_ms[i];
-    return SPHX_OK;
+    return ctx->cool_t.end(ctx);
 }

@@ -4,30 +4,13 @@
 // (cy,cz) is one contiguous range of the sorted particle arrays (what sphx_knn.hip streams).
 // Coordinates outside the box are clamped into the boundary cells by the same monotone map
 // the search uses for its range ends, so clamping never loses a neighbour.
-#include "sphx_internal.h"
+#include "sphx_wave.h"
 #include <rocprim/rocprim.hpp>
 #include <float.h>
 
 #define RED_BLOCK 256
 #define RED_MAXBLOCKS 1024
 #define FUSED_MAXBLOCKS 4096        // grid_count_fused: one particle per thread up to 1e6 (histogram atomics want threads in flight)
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // partial[block][13] = {min xyz, max xyz, sum of (x - p) xyz, sum of (x - p)^2 xyz, count}; non-finite
 // coordinates are ignored.  The moments are taken about a pivot p near the cloud, not about the origin: with raw
@@ -37,6 +20,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 #define BB_W 13
 #define BB_PIVOT 16                 // the finished statistics carry the pivot at [16..18] (13: the fused kernel's ticket word)
 #define BB_OUT 19
+static_assert(BB_OUT * sizeof(double) <= sizeof(PinnedLag::box) && BB_OUT <= SC_NSLOTS, "the statistics fit their pinned slots");
 struct ClipBox { double lo[3], hi[3]; int on; double pivot[3]; int pivot_dev; };
 static void clip_set_pivot(ClipBox& clip, const double* fallback) {
     clip.pivot_dev = 0;
@@ -80,9 +64,9 @@ __global__ __launch_bounds__(RED_BLOCK) void bbox_partial(int n, const double* x
     int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        mn[c] = wave_min(mn[c]); mx[c] = wave_max(mx[c]); su[c] = wave_sum(su[c]); sq[c] = wave_sum(sq[c]);
+        mn[c] = wave_min_f64(mn[c]); mx[c] = wave_max_f64(mx[c]); su[c] = wave_sum_f64(su[c]); sq[c] = wave_sum_f64(sq[c]);
     }
-    cnt = wave_sum(cnt);
+    cnt = wave_sum_f64(cnt);
     if (lane == 0) {
         for (int c = 0; c < 3; ++c) {
             sm[wave][c] = mn[c]; sm[wave][3 + c] = mx[c]; sm[wave][6 + c] = su[c]; sm[wave][9 + c] = sq[c];
@@ -117,7 +101,7 @@ __global__ __launch_bounds__(256) void bbox_final(int nblocks, const double* par
         const double p = partial[b * BB_W + c];
         v = c < 3 ? fmin(v, p) : (c < 6 ? fmax(v, p) : v + p);
     }
-    v = c < 3 ? wave_min(v) : (c < 6 ? wave_max(v) : wave_sum(v));
+    v = c < 3 ? wave_min_f64(v) : (c < 6 ? wave_max_f64(v) : wave_sum_f64(v));
     if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -163,9 +147,9 @@ static void bbox_finish(const void* host_src, double out_minmax[13], double rel[
 }
 static int bbox_sync(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z,
                      double out_minmax[13], bool use_clip, double rel[9]) {
-    SPHX_TRY(bbox_launch(ctx, n, x, y, z, use_clip, ctx->pinned));
+    SPHX_TRY(bbox_launch(ctx, n, x, y, z, use_clip, ctx->pinned->scal));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    bbox_finish(ctx->pinned, out_minmax, rel);
+    bbox_finish(ctx->pinned->scal, out_minmax, rel);
     return SPHX_OK;
 }
 int sphx_bbox(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z,
@@ -268,9 +252,9 @@ __global__ __launch_bounds__(RED_BLOCK) void grid_count_fused(FusedCountArgs a) 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        mn[c] = wave_min(mn[c]); mx[c] = wave_max(mx[c]); su[c] = wave_sum(su[c]); sq[c] = wave_sum(sq[c]);
+        mn[c] = wave_min_f64(mn[c]); mx[c] = wave_max_f64(mx[c]); su[c] = wave_sum_f64(su[c]); sq[c] = wave_sum_f64(sq[c]);
     }
-    cnt = wave_sum(cnt);
+    cnt = wave_sum_f64(cnt);
     if (lane == 0) {
         for (int c = 0; c < 3; ++c) {
             sm[wave][c] = mn[c]; sm[wave][3 + c] = mx[c]; sm[wave][6 + c] = su[c]; sm[wave][9 + c] = sq[c];
@@ -372,7 +356,7 @@ __global__ __launch_bounds__(256) void lookback_scan_kernel(int n_items, int* __
             __builtin_amdgcn_s_sleep(1);
         }
     }
-    part = wave_sum(part);
+    part = wave_sum_f64(part);            // (through doubles: exact, the sums stay below 2^31)
     __shared__ int s_part[4];
     if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = part;
     __syncthreads();
@@ -537,7 +521,7 @@ __global__ __launch_bounds__(256) void cell_scatter(int n, const int* cell_of, c
             const double p = bb_part[b * BB_W + c];
             v = c < 3 ? fmin(v, p) : (c < 6 ? fmax(v, p) : v + p);
         }
-        v = c < 3 ? wave_min(v) : (c < 6 ? wave_max(v) : wave_sum(v));
+        v = c < 3 ? wave_min_f64(v) : (c < 6 ? wave_max_f64(v) : wave_sum_f64(v));
         if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = v;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -620,9 +604,24 @@ __global__ __launch_bounds__(256) void cell_sort_members(int ncells, const int* 
 
 #define SPHX_MAX_CELLS (SCAN_TILE * 4096)
 
-// (sphx_state_sample, sphx_arb.hip, calls this between two steps and puts back every host-side field of the context this
-//  function writes - grid, tbox, tbox_h, clip_lo / clip_hi / clip_valid, olev.L, cells_unsorted, stats.cells / cell_size: a
-//  field added here belongs on that list too)
+// The host-side fields of the context a grid build between two steps must leave as it found them (GridHostState,
+// sphx_internal.h): a field sphx_build_grid comes to write, and the next step reads, belongs in these two functions too.
+GridHostState sphx_grid_host_save(const sphx_ctx* ctx) {
+    GridHostState s;
+    s.grid = ctx->grid; s.tbox = ctx->tbox;
+    memcpy(s.tbox_h, ctx->tbox_h, sizeof(s.tbox_h)); memcpy(s.clip_lo, ctx->clip_lo, sizeof(s.clip_lo)); memcpy(s.clip_hi, ctx->clip_hi, sizeof(s.clip_hi));
+    s.clip_valid = ctx->clip_valid; s.cells_unsorted = ctx->cells_unsorted; s.olev_L = ctx->olev.L;
+    s.cells = ctx->stats.cells; s.cell_size = ctx->stats.cell_size;
+    s.map_perm = ctx->map_perm; s.qorder = ctx->qorder;
+    return s;
+}
+void sphx_grid_host_restore(sphx_ctx* ctx, const GridHostState& s) {
+    ctx->grid = s.grid; ctx->tbox = s.tbox;
+    memcpy(ctx->tbox_h, s.tbox_h, sizeof(s.tbox_h)); memcpy(ctx->clip_lo, s.clip_lo, sizeof(s.clip_lo)); memcpy(ctx->clip_hi, s.clip_hi, sizeof(s.clip_hi));
+    ctx->clip_valid = s.clip_valid; ctx->cells_unsorted = s.cells_unsorted; ctx->olev.L = s.olev_L;
+    ctx->stats.cells = s.cells; ctx->stats.cell_size = s.cell_size;
+    ctx->map_perm = s.map_perm; ctx->qorder = s.qorder;
+}
 int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const double* y, const double* z, double cell_hint,
                     const GridBuildOpts& opts) {
     double bb[13], rel[9];         // rel: the box and the mean measured from the statistics' pivot
@@ -647,7 +646,7 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         // outside it are clamped into the boundary cells.  (tbox, the device-side true bounding box
         // the search reads, is this step's.)
         const int prev = ctx->lag_bslot, cur = prev ^ 1;
-        char* slot = (char*)ctx->pinned + LAG_OFF;
+        PinnedLag* slot = ctx->pinned->lag;
         // (the previous statistics describe this cloud if they were taken over about as many particles: the
         //  fused loop's n is constant, the decomposed driver's owned + ghost count wobbles by a few per cent)
         const int64_t pn = ctx->lag_bn[prev];
@@ -656,12 +655,12 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         fused = use == prev;
         if (!fused) {
             SPHX_TRY(clamp_now());
-            SPHX_TRY(bbox_launch(ctx, n, x, y, z, true, slot + 512 * cur));
+            SPHX_TRY(bbox_launch(ctx, n, x, y, z, true, slot[cur].box));
             HIPCHK(hipEventRecord(ctx->lag_bev[cur], ctx->stream));
             ctx->lag_balias[cur] = nullptr;
         }
         HIPCHK(hipEventSynchronize(ctx->lag_balias[use] ? ctx->lag_balias[use] : ctx->lag_bev[use]));
-        bbox_finish(slot + 512 * use, bb, rel);
+        bbox_finish(slot[use].box, bb, rel);
         ctx->lag_bvalid[cur] = true;
         ctx->lag_bn[cur] = n;
         ctx->lag_bslot = cur;
@@ -785,7 +784,7 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
         // (no valid window: every particle of the previous build coincided - its box, the corner tbox_h, is that point)
         clip_set_pivot(fa.clip, ctx->tbox_h);
         // the pivot travels with the statistics: written here, by the host, next to where the device puts the sums
-        memcpy((char*)ctx->pinned + LAG_OFF + 512 * lag_cur + BB_PIVOT * sizeof(double), fa.clip.pivot, 3 * sizeof(double));
+        memcpy(ctx->pinned->lag[lag_cur].box + BB_PIVOT, fa.clip.pivot, 3 * sizeof(double));
         fa.g = g;
         fa.cell_of = ctx->cell_of.as<int>();
         fa.hist = fill;
@@ -820,14 +819,13 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
     // (the statistics folded by the scatter's first blocks go straight to the pinned slot the next step's host code reads:
     //  the 104-byte copy that followed was a launch of its own on the step's stream, 5 us + its gaps)
     const bool to_host = bb_fold_part != nullptr && bb_fold_out && pb >= BB_W;
-    double* bb_host = to_host ? reinterpret_cast<double*>((char*)ctx->pinned + LAG_OFF + 512 * lag_cur) : nullptr;
+    double* bb_host = to_host ? ctx->pinned->lag[lag_cur].box : nullptr;
     hipLaunchKernelGGL(cell_scatter, dim3(pb), dim3(256), 0, ctx->stream, (int)n,
                        ctx->cell_of.as<int>(), start, fill, ctx->perm.as<int>(), bb_fold_blocks, bb_fold_part, bb_fold_out, bb_host, rank_dev);
     if (rank_dev && !hist_zeroed) HIPCHK(hipMemsetAsync(fill, 0, ((size_t)nc + 1) * sizeof(int), ctx->stream));     // (rocPRIM's scan left the counts in place)
     if (bb_fold_out) {
-        char* slot = (char*)ctx->pinned + LAG_OFF;
         if (!to_host)
-            HIPCHK(hipMemcpyAsync(slot + 512 * lag_cur, bb_fold_out, BB_W * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(ctx->pinned->lag[lag_cur].box, bb_fold_out, BB_W * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         if (opts.alias_ev) {
             ctx->lag_balias[lag_cur] = opts.alias_ev;          // recorded by the caller a few launches on, before the search
         } else {

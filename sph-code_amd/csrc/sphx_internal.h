@@ -15,6 +15,7 @@
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
+struct PinnedLayout;
 
 // ------------------------------------------------------------------------------------------
 // device buffer with grow-only capacity
@@ -134,6 +135,16 @@ struct StateArrays {
     DevBuf id;                                   // int32 persistent particle id
     DevBuf fun;                                  // (n,s) f64 composition (optional)
     DevBuf mgm, mcs;                             // mean grain mass / cross-section (drag, optional)
+};
+
+// The stage timer of a side call (the arb, rad and cool entry points): five events on ctx->stream around its four stages.
+// (sphx_api.hip; a call that returns between begin and end leaves ms zeroed)
+struct StageTimer {
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
+    double ms[4] = {0, 0, 0, 0};
+    int begin(sphx_ctx* ctx);           // creates the events, zeroes ms, records ev[0]
+    int mark(sphx_ctx* ctx, int i);     // records ev[i]
+    int end(sphx_ctx* ctx);             // ms[i] = ev[i] .. ev[i + 1]; after the call's last synchronise
 };
 
 #define SPHX_LDS_KERNELS 16           // room in sphx_ctx::lds_raised (the LDS kernels of sphx_blob.hip and sphx_loopforms.hip: 11)
@@ -275,9 +286,9 @@ struct sphx_ctx {
     // ---- timing events of the step loop, and its lagged read-backs ----
     // The fused step loop never waits for the step it is launching: its timing events live in a
     // ring (collected two steps late), and the two host read-backs that size the grid - bounding
-    // box statistics and mean h - are taken from the PREVIOUS step's copies (slots in `pinned` at
-    // LAG_OFF; the grid box only steers performance: out-of-box particles are clamped into the
-    // boundary cells, which the search handles exactly).
+    // box statistics and mean h - are taken from the PREVIOUS step's copies (pinned->lag; the grid
+    // box only steers performance: out-of-box particles are clamped into the boundary cells, which
+    // the search handles exactly).
     bool ev_detail[3] = {false, false, false};
     int ev_has07[3] = {0, 0, 0};        // bit 0 / 1: the slot's step recorded its start / end event
     unsigned ev_pending = 0;            // bit s: ring slot s holds an uncollected step
@@ -335,20 +346,23 @@ struct sphx_ctx {
     int64_t arb_ball_id = 0, arb_ball_n = 0, arb_ball_m = 0;
     GridParams arb_g;
     double arb_tb[6] = {0, 0, 0, 0, 0, 0};
-    double arb_ms[4] = {0, 0, 0, 0};            // sphx_arb_last_timing
-    hipEvent_t arb_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
+    // events of a call: [0] start, [1] inputs on the device, [2] geometry and records built, [3] sums and gate done, [4]
+    // outputs on the host (sphx_arb_last_timing)
+    StageTimer arb_t;
     // radiative transfer (sphx_rad.hip), buffers of its own - a call on the resident state touches nothing the step owns:
     // staged inputs, SoA particles, rays + their outputs, the chunks' partial columns, non-star flags / offsets / list +
-    // small reductions, per-particle outputs, scan scratch
-    DevBuf rad_in, rad_soa, rad_ray, rad_part, rad_gas, rad_out, rad_tmp;
-    double rad_ms[4] = {0, 0, 0, 0};            // sphx_rad_last_timing
-    hipEvent_t rad_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
+    // small reductions, per-particle outputs (the flags are scanned by sphx_excl_scan_int, in the grid's scratch)
+    DevBuf rad_in, rad_soa, rad_ray, rad_part, rad_gas, rad_out;
+    // events of a call: [0] start, [1] inputs on the device and prepared, [2] columns done, [3] spread and deposit done,
+    // [4] outputs on the host (sphx_rad_last_timing)
+    StageTimer rad_t;
     // rad_cooling (sphx_cool.hip), buffers of its own: staged inputs, the list as given, the particles' records, ints (the
     // K-major list, counts, cursors, flags, slice starts), the reverse list (as filled | sorted), the rows' table, outputs,
-    // scan / sort scratch
+    // scratch of the segmented sort (the counts are scanned by sphx_excl_scan_int)
     DevBuf cool_in, cool_nb, cool_rec, cool_int, cool_rev, cool_tab, cool_out, cool_tmp;
-    double cool_ms[4] = {0, 0, 0, 0};           // sphx_cool_last_timing
-    hipEvent_t cool_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
+    // events of a call: [0] start, [1] inputs on the device, records and list built, [2] rows done, [3] reverse list, gather
+    // and epilogue done, [4] outputs on the host (sphx_cool_last_timing)
+    StageTimer cool_t;
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
@@ -359,7 +373,7 @@ struct sphx_ctx {
     hipEvent_t ev[10] = {nullptr};
     hipEvent_t evring[3][10] = {{nullptr}};
     hipEvent_t lag_bev[2] = {nullptr, nullptr}, lag_hev[2] = {nullptr, nullptr};
-    void* pinned = nullptr;       // small pinned host scratch for scalar read-back
+    PinnedLayout* pinned = nullptr;     // small pinned host scratch for scalar read-back
 };
 
 int sphx_set_err(sphx_ctx* ctx, int code, const char* fmt, ...);
@@ -403,8 +417,6 @@ __device__ __forceinline__ int xcd_block(int b, int nb) {
 #ifndef SPHX_SUM_PARTS
 #define SPHX_SUM_PARTS 4
 #endif
-
-#define LAG_OFF 1024                 // byte offset of the lag slots in ctx->pinned: slot s at LAG_OFF + 512 s (box), + 256 (h sums)
 
 // np.nan_to_num of one value (drv:233-238, 460-463, 490-491; nsc:783)
 __device__ __forceinline__ double sphx_nan_to_num(double v) {
@@ -453,6 +465,49 @@ enum {
     BADC_BUCKETS = 64, BADC_STRIDE = 16
 };
 int sphx_badc_read(sphx_ctx* ctx);          // sums the buckets into ctx->stats.bad_* (waits for the stream)
+
+// ---- ctx->pinned: who reads back what, and where (host code only) ------------------------------------
+// What a side call (arb / rad / cool) reads back beside its reduction: the reduction's 32 bytes, a 4-byte count, arb's
+// candidate counter.
+struct PinnedSide { double red[4]; int count; int pad_[7]; u64 cand; };
+struct PinnedLag {
+    double box[32];           // a grid build's box statistics (sphx_grid.hip: BB_OUT doubles)
+    double hs[32];            // SC_HSUM .. SC_KGDBG + 2: the h sums and the search's counters behind them
+};
+struct PinnedLayout {
+    // Read-backs the launching call itself waits for: sphx_step's scalar slots, a synchronous box reduction, the Verlet
+    // refresh's and rad_cooling's counts (scal), the side calls' tuples (side).  side.count and side.cand lie INSIDE the
+    // scalar block's bytes.  That is safe only because a step call and a side call never have copies in flight together:
+    // each waits for its own copies before it returns, and a context serves one call at a time.
+    union {
+        u64 scal[SC_NSLOTS];
+        PinnedSide side;
+    };
+    char pad0_[256 - SC_NSLOTS * 8];
+    double hsum[4];           // SC_HSUM .. of a step that has no lagged copy to size its cells from
+    char pad1_[1024 - 256 - 4 * 8];
+    PinnedLag lag[2];         // the fused loop's lagged read-backs (lag_bslot / lag_hslot say which is current)
+    char pad2_[3072 - 1024 - 2 * 512];
+    u64 knn_lag[10];          // SC_NFAILQ .. SC_KGDBG + 2, copied out behind a hinted search (sphx_knn.hip)
+    char pad3_[8192 - 3072 - 10 * 8];
+    u64 badc[BADC_BUCKETS * BADC_STRIDE];      // the failure buckets (sphx_badc_read)
+};
+static_assert(sizeof(PinnedLayout) == 16384, "ctx->pinned is 16 KiB");
+static_assert(offsetof(PinnedLayout, side) == 0 && offsetof(PinnedSide, count) == 32 && offsetof(PinnedSide, cand) == 64 &&
+                  offsetof(PinnedLayout, hsum) == 256 && offsetof(PinnedLayout, lag) == 1024 && sizeof(PinnedLag) == 512 &&
+                  offsetof(PinnedLag, hs) == 256 && offsetof(PinnedLayout, knn_lag) == 3072 && offsetof(PinnedLayout, badc) == 8192,
+              "the offsets in use since the members were byte counts");
+#define SPHX_PIN_APART(a, b) \
+    static_assert(offsetof(PinnedLayout, a) + sizeof(PinnedLayout::a) <= offsetof(PinnedLayout, b), #a " overlaps " #b)
+SPHX_PIN_APART(scal, hsum); SPHX_PIN_APART(side, hsum); SPHX_PIN_APART(hsum, lag); SPHX_PIN_APART(lag, knn_lag);
+SPHX_PIN_APART(knn_lag, badc);
+#undef SPHX_PIN_APART
+static_assert(offsetof(PinnedLayout, badc) + sizeof(PinnedLayout::badc) == sizeof(PinnedLayout), "the buckets end the block");
+
+// Copies of whole f64 arrays between host and device on ctx->stream, from a small table (sphx_api.hip).
+struct CopyF64 { const void* host; const void* dev; size_t count; };       // count in doubles
+int sphx_upload_f64(sphx_ctx* ctx, const CopyF64* t, int nt);      // skips an entry whose host pointer is NULL
+int sphx_download_f64(sphx_ctx* ctx, const CopyF64* t, int nt);    // skips an entry with a NULL pointer or a count of 0
 
 // ---- kernel launch wrappers (defined in the .hip files) ---------------------------------
 // grid
@@ -503,6 +558,19 @@ struct GridBuildOpts {
 };
 int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const double* y, const double* z, double cell_hint,
                     const GridBuildOpts& opts = GridBuildOpts());   // fills grid, cell_start, perm
+// What a grid build between two steps changes on the host side of the context (and map_perm / qorder, which its caller
+// clears for it): sphx_state_sample saves it, builds a grid of its own, and puts it back (sphx_grid.hip).
+struct GridHostState {
+    GridParams grid;
+    const double* tbox;
+    double tbox_h[6], clip_lo[3], clip_hi[3], cell_size;     // (olev_L: olev.L; cells, cell_size: stats.cells, stats.cell_size)
+    bool clip_valid, cells_unsorted;
+    int olev_L;
+    int64_t cells;
+    const int *map_perm, *qorder;
+};
+GridHostState sphx_grid_host_save(const sphx_ctx* ctx);
+void sphx_grid_host_restore(sphx_ctx* ctx, const GridHostState& saved);
 int sphx_excl_scan_int(sphx_ctx* ctx, const int* in, int* out, int n);   // out[0..n] = exclusive prefix sums, out[n] = total (in[n] must be 0)
 // The drag reaction (nsc:741: every particle adds -f to each of its dust neighbours) as an ORDERED scatter: the
 // contributions to a particle are first laid side by side (slices from a count + scan), then added in the order the

@@ -800,7 +800,7 @@ int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const KnnIn& in, const KnnOut& out
         const bool ext = in.lag_external;
         if (lagged && (ext ? ctx->knn_lag_valid : ctx->olev_ev_valid)) {
             if (!ext) HIPCHK(hipEventSynchronize(ctx->olev_ev));
-            const u64* v = ext ? ctx->knn_lag : (const u64*)((const char*)ctx->pinned + 3072);   // slots SC_NFAILQ .. SC_BADHINT
+            const u64* v = ext ? ctx->knn_lag : ctx->pinned->knn_lag;   // slots SC_NFAILQ .. SC_BADHINT
             const int64_t fb = (int64_t)(u32)v[0];
             ctx->list_len_last = fb;
             ctx->farq_last = (int64_t)(v[2] >= ctx->farq_seen ? v[2] - ctx->farq_seen : v[2]);
@@ -886,7 +886,7 @@ int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const KnnIn& in, const KnnOut& out
         }
         if (lagged && !ext) {
             if (!ctx->olev_ev) HIPCHK(hipEventCreateWithFlags(&ctx->olev_ev, hipEventDisableTiming));
-            HIPCHK(hipMemcpyAsync((char*)ctx->pinned + 3072, ctx->scal.as<u64>() + SC_NFAILQ, 10 * sizeof(u64), hipMemcpyDeviceToHost,
+            HIPCHK(hipMemcpyAsync(ctx->pinned->knn_lag, ctx->scal.as<u64>() + SC_NFAILQ, sizeof(ctx->pinned->knn_lag), hipMemcpyDeviceToHost,
                                   ctx->stream));
             HIPCHK(hipEventRecord(ctx->olev_ev, ctx->stream));
             ctx->olev_ev_valid = true;

@@ -14,9 +14,8 @@
 //             and feeds RAD_SRC_CHUNK sums per weight (gd + 1)^-2.  Then exp, the distance factor and the two sums
 //             over the sources, in source order.
 // Vector stores from plain C++ only.
-#include "sphx_internal.h"
+#include "sphx_wave.h"
 #include "sphx_rad_pair.h"
-#include <rocprim/rocprim.hpp>
 
 #define RAD_TILE SPHX_RAD_TILE
 #define RAD_WG 128                              // lanes of a column workgroup
@@ -57,10 +56,7 @@ __global__ __launch_bounds__(256) void rad_hmin_kernel(int n, const double* __re
         if (s != s) nn += 1.0;
         else if (s < mn) mn = s;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mn = fmin(mn, __shfl_xor(mn, o, 64)); cn += __shfl_xor(cn, o, 64); nn += __shfl_xor(nn, o, 64);
-    }
+    mn = wave_min_f64(mn); cn = wave_sum_f64(cn); nn = wave_sum_f64(nn);
     const int wv = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { sm[wv][0] = mn; sm[wv][1] = cn; sm[wv][2] = nn; }
     __syncthreads();
@@ -74,10 +70,7 @@ __global__ __launch_bounds__(256) void rad_hmin_kernel(int n, const double* __re
 __global__ __launch_bounds__(64) void rad_hmin_final(int nb, const double* part, double* out) {
     double mn = INFINITY, cn = 0.0, nn = 0.0;
     for (int b = threadIdx.x; b < nb; b += 64) { mn = fmin(mn, part[3 * b]); cn += part[3 * b + 1]; nn += part[3 * b + 2]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mn = fmin(mn, __shfl_xor(mn, o, 64)); cn += __shfl_xor(cn, o, 64); nn += __shfl_xor(nn, o, 64);
-    }
+    mn = wave_min_f64(mn); cn = wave_sum_f64(cn); nn = wave_sum_f64(nn);
     if (threadIdx.x == 0) { out[0] = mn; out[1] = cn; out[2] = nn; }
 }
 // the non-star particles, caller's order kept: gidx[off[i]] = i
@@ -250,24 +243,6 @@ __global__ __launch_bounds__(256) void rad_by_id_kernel(int n, const int* __rest
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-// events of a call: [0] start, [1] inputs on the device and prepared, [2] columns done, [3] spread and deposit done,
-// [4] outputs on the host
-static int rad_begin(sphx_ctx* ctx) {
-    for (int i = 0; i < 5; ++i)
-        if (!ctx->rad_ev[i]) HIPCHK(hipEventCreate(&ctx->rad_ev[i]));
-    for (int i = 0; i < 4; ++i) ctx->rad_ms[i] = 0.0;
-    HIPCHK(hipEventRecord(ctx->rad_ev[0], ctx->stream));
-    return SPHX_OK;
-}
-static int rad_end(sphx_ctx* ctx) {                     // (after the call's last synchronise)
-    for (int i = 0; i < 4; ++i) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->rad_ev[i], ctx->rad_ev[i + 1]));
-        ctx->rad_ms[i] = ms;
-    }
-    return SPHX_OK;
-}
-
 static int rad_check(sphx_ctx* ctx, const char* who, int64_t n, int64_t n_src, const void* src, int64_t n_dst, const void* dst,
                      int mode) {
     if (n < 0 || n > 0x7FFFFFF0ll) return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld out of range", who, (long long)n);
@@ -319,23 +294,20 @@ static int rad_run(sphx_ctx* ctx, const char* who, RadPart pa, int64_t n_src, co
         hipLaunchKernelGGL(rad_hmin_kernel, dim3(rb), dim3(256), 0, ctx->stream, (int)n, pa.ptype, pa.sizes, red + 16);
         hipLaunchKernelGGL(rad_hmin_final, dim3(1), dim3(64), 0, ctx->stream, rb, red + 16, red);
         HIPCHK(hipGetLastError());
-        size_t tmp_bytes = 0;
-        HIPCHK(rocprim::exclusive_scan(nullptr, tmp_bytes, flag, off, 0, (size_t)n + 1, rocprim::plus<int>(), ctx->stream));
-        SPHX_TRY(sphx_ensure(ctx, ctx->rad_tmp, tmp_bytes + 64));
-        HIPCHK(rocprim::exclusive_scan(ctx->rad_tmp.p, tmp_bytes, flag, off, 0, (size_t)n + 1, rocprim::plus<int>(), ctx->stream));
+        SPHX_TRY(sphx_excl_scan_int(ctx, flag, off, (int)n));          // (flag[n] = 0; both start on 16-byte boundaries)
         hipLaunchKernelGGL(rad_compact_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n, flag, off, gidx);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(ctx->pinned, red, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync((char*)ctx->pinned + 32, off + n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        PinnedSide& pin = ctx->pinned->side;
+        HIPCHK(hipMemcpyAsync(pin.red, red, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(&pin.count, off + n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        double rd[3];
-        memcpy(rd, ctx->pinned, sizeof(rd));
-        ng = *(const int*)((const char*)ctx->pinned + 32);
+        const double* rd = pin.red;
+        ng = pin.count;
         if (!(rd[1] > 0.0))                                // the reference raises on the empty min (nsc:957)
             return sphx_set_err(ctx, SPHX_E_ARG, "%s: no particle with ptypes == 0 (the distance factor needs min(sizes) over them)", who);
         hmin = rd[2] > 0.0 ? NAN : rd[0];                  // (np.min hands a NaN on)
     }
-    HIPCHK(hipEventRecord(ctx->rad_ev[1], ctx->stream));
+    SPHX_TRY(ctx->rad_t.mark(ctx, 1));
     // columns
     if (R > 0) {
         const int64_t ray_tiles = (R + RAD_WG * RAD_RPL - 1) / (RAD_WG * RAD_RPL);
@@ -359,7 +331,7 @@ static int rad_run(sphx_ctx* ctx, const char* who, RadPart pa, int64_t n_src, co
                            ca.part, (int)n_dst, d_src, d_dst, d_blocked, d_sd, d_bs);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(ctx->rad_ev[2], ctx->stream));
+    SPHX_TRY(ctx->rad_t.mark(ctx, 2));
     // spread and deposit: lf2 | ext | momentum (3) | lum_factor (n_src)
     double *o_lf2 = nullptr, *o_ext = nullptr, *o_mom = nullptr, *o_lumf = nullptr;
     if (transfer && ng > 0) {
@@ -376,17 +348,14 @@ static int rad_run(sphx_ctx* ctx, const char* who, RadPart pa, int64_t n_src, co
         hipLaunchKernelGGL(rad_deposit_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, ctx->stream, da);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(ctx->rad_ev[3], ctx->stream));
-    struct P { void* host; const void* dev; size_t count; };
-    const P ps[] = {{ho.blocked, d_blocked, (size_t)R}, {ho.star_distance, d_sd, (size_t)R}, {ho.lf2, o_lf2, (size_t)ng},
-                    {ho.extinction, o_ext, (size_t)ng}, {ho.momentum, o_mom, 3 * (size_t)ng},
-                    {ho.lum_factor, o_lumf, (size_t)n_src * (size_t)ng}};
-    for (const P& p : ps)
-        if (p.host && p.dev && p.count > 0)
-            HIPCHK(hipMemcpyAsync(p.host, p.dev, p.count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipEventRecord(ctx->rad_ev[4], ctx->stream));
+    SPHX_TRY(ctx->rad_t.mark(ctx, 3));
+    const CopyF64 ps[] = {{ho.blocked, d_blocked, (size_t)R}, {ho.star_distance, d_sd, (size_t)R}, {ho.lf2, o_lf2, (size_t)ng},
+                          {ho.extinction, o_ext, (size_t)ng}, {ho.momentum, o_mom, 3 * (size_t)ng},
+                          {ho.lum_factor, o_lumf, (size_t)n_src * (size_t)ng}};
+    SPHX_TRY(sphx_download_f64(ctx, ps, 6));
+    SPHX_TRY(ctx->rad_t.mark(ctx, 4));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    return rad_end(ctx);
+    return ctx->rad_t.end(ctx);
 }
 
 // host arrays -> ctx->rad_in / rad_soa; fills pa's inputs and outputs (ptype may be NULL)
@@ -397,13 +366,11 @@ static int rad_stage_host(sphx_ctx* ctx, int64_t n, const double* points, const 
     SPHX_TRY(sphx_ensure(ctx, ctx->rad_soa, 5 * nn * sizeof(double)));
     double* in = ctx->rad_in.as<double>();
     double* soa = ctx->rad_soa.as<double>();
-    const size_t nb = (size_t)n * sizeof(double);
-    struct U { const double* host; double* dev; };
-    const U us[] = {{mass, in + 3 * nn}, {ptype, in + 4 * nn}, {sizes, in + 5 * nn}, {cross, in + 6 * nn}, {mu, in + 7 * nn}};
+    const size_t nd = (size_t)n;
+    const CopyF64 us[] = {{points, in, 3 * nd}, {mass, in + 3 * nn, nd}, {ptype, in + 4 * nn, nd}, {sizes, in + 5 * nn, nd},
+                          {cross, in + 6 * nn, nd}, {mu, in + 7 * nn, nd}};
     if (n > 0) {
-        HIPCHK(hipMemcpyAsync(in, points, 3 * nb, hipMemcpyHostToDevice, ctx->stream));
-        for (const U& u : us)
-            if (u.host) HIPCHK(hipMemcpyAsync(u.dev, u.host, nb, hipMemcpyHostToDevice, ctx->stream));
+        SPHX_TRY(sphx_upload_f64(ctx, us, 6));
         SPHX_TRY(sphx_aos_to_soa3(ctx, n, in, soa, soa + nn, soa + 2 * nn));
     }
     pa->n = (int)n;
@@ -423,7 +390,7 @@ extern "C" int sphx_rad_columns(sphx_ctx* ctx, int64_t n, const double* points, 
     if (n_src * n_dst == 0) return SPHX_OK;
     NEED(blocked);
     HIPCHK(hipSetDevice(ctx->device));
-    SPHX_TRY(rad_begin(ctx));
+    SPHX_TRY(ctx->rad_t.begin(ctx));
     RadPart pa;
     SPHX_TRY(rad_stage_host(ctx, n, points, nullptr, mass, sizes, cross, mu, &pa));
     const RadHostOut ho{nullptr, nullptr, nullptr, blocked, star_distance, nullptr};
@@ -441,7 +408,7 @@ extern "C" int sphx_rad_transfer(sphx_ctx* ctx, int64_t n, const double* points,
     if (n < 1) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_rad_transfer: no particle with ptypes == 0 (n = 0)");
     NEED(points); NEED(ptypes); NEED(mass); NEED(sizes); NEED(cross); NEED(mu);
     HIPCHK(hipSetDevice(ctx->device));
-    SPHX_TRY(rad_begin(ctx));
+    SPHX_TRY(ctx->rad_t.begin(ctx));
     RadPart pa;
     SPHX_TRY(rad_stage_host(ctx, n, points, ptypes, mass, sizes, cross, mu, &pa));
     const RadHostOut ho{lf2, momentum, extinction, blocked, star_distance, lum_factor};
@@ -450,7 +417,8 @@ extern "C" int sphx_rad_transfer(sphx_ctx* ctx, int64_t n, const double* points,
 
 // The same on the step loop's resident state.  Everything is read into buffers of this file's own, in the caller's
 // particle order (the order the sums then run in: the bits are those of sphx_rad_transfer on the downloaded state);
-// nothing the step owns is written and no host-side field of the context changes, so the loop goes on undisturbed.
+// nothing the step owns is written, and the one host-side field of the context that changes is the epoch counter of the
+// single-launch scan (lbs_epoch, which every scan bumps - as sphx_state_sample always has), so the loop goes on undisturbed.
 extern "C" int sphx_state_rad_transfer(sphx_ctx* ctx, const double* cross, int64_t n_src, const double* src,
                                        const double* luminosities, int64_t n_dst, const double* dst, double dt, int mode,
                                        double* lf2, double* momentum, double* extinction, double* blocked,
@@ -464,7 +432,7 @@ extern "C" int sphx_state_rad_transfer(sphx_ctx* ctx, const double* cross, int64
     NEED(cross);
     if (n_src > 0) NEED(luminosities);
     HIPCHK(hipSetDevice(ctx->device));
-    SPHX_TRY(rad_begin(ctx));
+    SPHX_TRY(ctx->rad_t.begin(ctx));
     const size_t nn = (size_t)n;
     SPHX_TRY(sphx_ensure(ctx, ctx->rad_in, 8 * nn * sizeof(double)));
     SPHX_TRY(sphx_ensure(ctx, ctx->rad_soa, 5 * nn * sizeof(double)));
@@ -486,12 +454,4 @@ extern "C" int sphx_state_rad_transfer(sphx_ctx* ctx, const double* cross, int64
     pa.flag = nullptr;
     const RadHostOut ho{lf2, momentum, extinction, blocked, star_distance, lum_factor};
     return rad_run(ctx, "sphx_state_rad_transfer", pa, n_src, src, luminosities, n_dst, dst, dt, mode, true, ho);
-}
-
-// Device time of the last sphx_rad_columns / sphx_rad_transfer / sphx_state_rad_transfer call on this context, from HIP
-// events on its stream.
-extern "C" int sphx_rad_last_timing(sphx_ctx* ctx, double ms[4]) {
-    if (!ctx || !ms) return SPHX_E_ARG;
-    for (int i = 0; i < 4; ++i) ms[i] = ctx->rad_ms[i];
-    return SPHX_OK;
 }

@@ -156,9 +156,9 @@ int sphx_knn_refresh(sphx_ctx* ctx, int64_t n, int k, const double* x, const dou
     a.nfail = sc + SC_NFAIL;
     hipLaunchKernelGGL(knn_refresh_kernel, dim3((unsigned)(sphx_pad64(n) / RF_PPB)), dim3(RF_BLOCK), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(ctx->pinned, sc + SC_NFAIL, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->pinned->scal, sc + SC_NFAIL, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    *nfail_out = (int64_t)(*(u64*)ctx->pinned);
+    *nfail_out = (int64_t)ctx->pinned->scal[0];
     return SPHX_OK;
 }
 

@@ -1,6 +1,6 @@
-// sphx_wave.h - wave64 building blocks shared by the search kernels: lane exchanges without the
+// sphx_wave.h - wave64 building blocks shared by the kernels: lane exchanges without the
 // LDS crossbar where the ISA allows it, bitonic networks on (u64 key, u32 index) pairs and on
-// unique 32-bit keys, SGPR broadcasts, SciPy-compatible squared distance.
+// unique 32-bit keys, min / max / sum of doubles, SGPR broadcasts, SciPy-compatible squared distance.
 #pragma once
 #include "sphx_internal.h"
 
@@ -136,6 +136,24 @@ __device__ __forceinline__ int wave_scan_incl(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);
     v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);
+    return v;
+}
+
+// wave-wide min / max / sum of a double by the xor butterfly 32 .. 1: every lane ends with the result, and a sum adds in
+// one fixed order (the reductions of the grid build, the arb samplers and the radiative transfer)
+__device__ __forceinline__ double wave_min_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
