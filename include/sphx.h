@@ -112,6 +112,15 @@ const char* sphx_tunables(const sphx_ctx* ctx);
  * n ran through the single-launch form (scans of more than 512 tiles of 8192 items take rocPRIM's either way).
  * Test infrastructure; replaces nothing in the reference. */
 int sphx_selftest_scan(sphx_ctx* ctx, int n, unsigned seed, long long* mismatches, int* single_launch);
+/* Self-test of the fused step's cell and blob order (sphx_grid.hip).  On the caller's n positions (host arrays) and a grid
+ * of cells of `cell_size`, the cells are counted, scanned and scattered once; the order is then finished twice - by the
+ * per-cell pass (member sort, curve counts, host cues), scan and scatter, and by the fused step's kernels (curve counts from
+ * the scatter, scan, member order by counting in the gather, the cues kernel) - and the finished cell order, the blob
+ * order, the curve's starts and total and the two cues are compared on the device: entries that differ in *mismatches
+ * (must be 0).  *new_chain_taken: 1 when the fused step's kernels ran (0: the curve's code space was refused for this
+ * grid, nothing to compare).  Test infrastructure; replaces nothing in the reference. */
+int sphx_selftest_grid_order(sphx_ctx* ctx, int n, const double* x, const double* y, const double* z, double cell_size,
+                             long long* mismatches, int* new_chain_taken);
 int sphx_selftest_mfma_cull(sphx_ctx* ctx, double E, int blocks, unsigned seed, double* max_err_over_E2,
                             double* wrong_signs, double* kappa);
 /* Page-locked host memory for the big arrays the array entry points hand back ((N,K) int64 + float64 from

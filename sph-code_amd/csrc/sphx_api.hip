@@ -604,6 +604,9 @@ static int step_search(sphx_ctx* ctx, int k, double dist, hipEvent_t* ev) {
         g.lagged = true;
         g.alias_ev = ev[1];               // (recorded below, behind the state's permutation)
         g.sort_cells_later = blob;        // the blob-order pass over the cells sorts their members too
+        // ... or no pass over the cells at all: the scatter counts them along the curve, the gather below orders their
+        // members, and the host's cues are counted on the side stream (sphx_permute_state, split)
+        g.count_curve = blob && ctx->side_stream && ctx->ev_perm;
         if (!ctx->use_verlet) { g.clamp_vel[0] = r.vx.as<double>(); g.clamp_vel[1] = r.vy.as<double>(); g.clamp_vel[2] = r.vz.as<double>(); }
         SPHX_TRY(sphx_build_grid(ctx, n, k, r.x.as<double>(), r.y.as<double>(), r.z.as<double>(), cell_hint, g));
         // (the blob order needs cell_of / perm / cell_start only: before the state is permuted, so that the

@@ -498,15 +498,24 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_phase3(int n, const int* in, 
 // bb_part != nullptr (the fused loop): the first BB_W blocks also fold one column each of the box statistics' block
 // partials (what bbox_final does: same order of operations) - they are wanted by the search and by the next step's host code,
 // not by anything before this kernel, so they need no launch of their own on the way (early blocks: off the kernel's tail).
+// cc.mcount != nullptr (with rank): the first arrival of every non-empty cell also writes the cell's count to its place on
+// the blob order's curve - what blob_count's pass over all the cells, most of them empty, does otherwise.
+struct CurveCount { int* mcount; BlobBits b; int nx, ny; };
 __global__ __launch_bounds__(256) void cell_scatter(int n, const int* cell_of, const int* cell_start,
                                                     int* fill, int* perm, int bb_nblocks, const double* bb_part,
-                                                    double* bb_out, double* bb_host, const int* __restrict__ rank) {
+                                                    double* bb_out, double* bb_host, const int* __restrict__ rank,
+                                                    CurveCount cc) {
     __shared__ double sw[4];
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && rank) {
         // (the count kernel kept every particle's arrival number: no second atomic per particle; the histogram was put
         //  back to zero by the scan that read it)
-        perm[cell_start[cell_of[i]] + rank[i]] = i;
+        const int c = cell_of[i], s0 = cell_start[c], r = rank[i];
+        perm[s0 + r] = i;
+        if (cc.mcount && r == 0) {
+            const int cx = c % cc.nx, cy = (c / cc.nx) % cc.ny, cz = c / (cc.nx * cc.ny);
+            cc.mcount[blob_rank(cx, cy, cz, cc.b)] = cell_start[c + 1] - s0;
+        }
     } else if (i < n) {
         int c = cell_of[i];
         // counts the histogram back down to zero; slots are handed out upwards (arrival order is mostly
@@ -543,8 +552,6 @@ __global__ __launch_bounds__(256) void cell_scatter(int n, const int* cell_of, c
 // one's rank by comparing it with all of them (broadcast lane by lane: members are distinct indices) and writes it to
 // its place - all reads before any write.  Beyond 512 the arrival order stays (a valid cell list; only run-to-run
 // tie-breaking is lost).  Every lane of the wave must call this (cnt = 0: nothing to do).
-#define CELL_SORT_SERIAL 16
-#define CELL_SORT_WAVE 512
 #define DENSE_CELL 48              // members from which a cell counts as dense (27 of them: 1300, a tile holds 1408)
 #define CROWDED_LIST_MIN 2048      // crowded cells at the last build the host knows of, from which they get a launch of their own
 // one crowded cell (m members from perm[bs]) by the whole wave: U = members per lane
@@ -603,6 +610,40 @@ __global__ __launch_bounds__(256) void cell_sort_members(int ncells, const int* 
 }
 
 #define SPHX_MAX_CELLS (SCAN_TILE * 4096)
+
+// ---- blob order, host side: the curve and its code space for a grid (the kernels: further down) ----
+// Hilbert curve over the cube of side 2^hb that holds the grid where its code space fits, else Morton codes with each
+// axis contributing only the bits it has.  Returns the bits of the code space; above BLOB_MAX_BITS no order is built.
+#define BLOB_MAX_BITS 27
+static int blob_code_space(const sphx_ctx* ctx, const GridParams& g, BlobBits* out) {
+    BlobBits b{0, 0, 0, 0};
+    while ((1 << b.bx) < g.nx) ++b.bx;
+    while ((1 << b.by) < g.ny) ++b.by;
+    while ((1 << b.bz) < g.nz) ++b.bz;
+    int bits = b.bx + b.by + b.bz;
+    int hb = b.bx > b.by ? b.bx : b.by;
+    if (b.bz > hb) hb = b.bz;
+    if (hb < 1) hb = 1;
+    // the cube's code space may be up to 8x the Morton one: taken while it stays within 2^24 codes (a
+    // 64 MB count + scan) or within 4x the tight code space
+    if (ctx->blob_curve != 1 && 3 * hb <= 27 && (3 * hb <= 24 || 3 * hb <= bits + 2)) { b.hilbert = hb; bits = 3 * hb; }
+    *out = b;
+    return bits;
+}
+// the order's arrays for M codes; the counts all zero on the stream before whoever counts next (blob_count, or the
+// grid build's scatter)
+static int blob_counts_prepare(sphx_ctx* ctx, int64_t n, int M) {
+    SPHX_TRY(sphx_ensure(ctx, ctx->porder, (size_t)n * sizeof(int)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->mcount, ((size_t)M + 2) * sizeof(int)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->mstart, ((size_t)M + 2) * sizeof(int)));
+    // (all zero between builds when the deferred scatter cleans up after the scan: no memset then, except once per
+    //  allocation or after a build that did not)
+    if (!(ctx->mcount_zeroed == ctx->mcount.p && ctx->mcount_zeroed_M == M)) {
+        HIPCHK(hipMemsetAsync(ctx->mcount.p, 0, ctx->mcount.cap, ctx->stream));
+    }
+    ctx->mcount_zeroed = nullptr;
+    return SPHX_OK;
+}
 
 // The host-side fields of the context a grid build between two steps must leave as it found them (GridHostState,
 // sphx_internal.h): a field sphx_build_grid comes to write, and the next step reads, belongs in these two functions too.
@@ -820,8 +861,21 @@ int sphx_build_grid(sphx_ctx* ctx, int64_t n, int k, const double* x, const doub
     //  the 104-byte copy that followed was a launch of its own on the step's stream, 5 us + its gaps)
     const bool to_host = bb_fold_part != nullptr && bb_fold_out && pb >= BB_W;
     double* bb_host = to_host ? ctx->pinned->lag[lag_cur].box : nullptr;
+    // the fused step (opts.count_curve): the curve's counts from this scatter, the members' order from the gather that
+    // follows - where every particle has its arrival number and the curve's code space is taken
+    CurveCount cc{nullptr, BlobBits{0, 0, 0, 0}, g.nx, g.ny};
+    ctx->curve_counted = false;
+    if (opts.count_curve && opts.sort_cells_later && rank_dev) {
+        const int bits = blob_code_space(ctx, g, &cc.b);
+        if (bits <= BLOB_MAX_BITS) {
+            SPHX_TRY(sphx_ensure(ctx, ctx->perm_fin, (size_t)n * sizeof(int)));
+            SPHX_TRY(blob_counts_prepare(ctx, n, 1 << bits));
+            cc.mcount = ctx->mcount.as<int>();
+            ctx->curve_counted = true;
+        }
+    }
     hipLaunchKernelGGL(cell_scatter, dim3(pb), dim3(256), 0, ctx->stream, (int)n,
-                       ctx->cell_of.as<int>(), start, fill, ctx->perm.as<int>(), bb_fold_blocks, bb_fold_part, bb_fold_out, bb_host, rank_dev);
+                       ctx->cell_of.as<int>(), start, fill, ctx->perm.as<int>(), bb_fold_blocks, bb_fold_part, bb_fold_out, bb_host, rank_dev, cc);
     if (rank_dev && !hist_zeroed) HIPCHK(hipMemsetAsync(fill, 0, ((size_t)nc + 1) * sizeof(int), ctx->stream));     // (rocPRIM's scan left the counts in place)
     if (bb_fold_out) {
         if (!to_host)
@@ -937,21 +991,39 @@ int sphx_build_outlier_levels(sphx_ctx* ctx, int64_t n, const double* xs, const 
 // crowded != nullptr: cells of 17 .. 512 members are not sorted here but listed (crowded[0] = how many, then their
 // indices) for cell_sort_crowded - a wave sorts its crowded cells one after the other, and the crowded cells of a cloud
 // with a dense core sit together: 64 in one wave and none in the next was 0.24 ms of a launch that takes 0.03
+// The host's cues from a wave's 64 cells (every lane calls; cnt = 0 beyond the last cell): how many crowded cells there
+// are (a step late: the list form), and the particles in dense cells (finer cells, sphx_api.hip) - those only of waves
+// that hold a crowded cell, which is what the cell-size feedback was tuned on.
+__device__ __forceinline__ void count_host_cues(int cnt, u64* counters) {
+    const u64 bm0 = __builtin_amdgcn_ballot_w64(cnt > CELL_SORT_SERIAL && cnt <= CELL_SORT_WAVE);
+    if (bm0 && counters && (threadIdx.x & 63) == 0) atomicAdd(&counters[SC_CROWDED], (u64)__popcll(bm0));
+    if (bm0 && counters) {
+        int dp = cnt >= DENSE_CELL ? cnt : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) dp += __shfl_xor(dp, o, 64);
+        if (dp && (threadIdx.x & 63) == 0) atomicAdd(&counters[SC_DENSEP], (u64)dp);
+    }
+}
+// the cues alone, for a build whose cells no other kernel walks (ctx->curve_counted): beside the search, off its chain
+__global__ __launch_bounds__(256) void cell_cues_kernel(int ncells, const int* __restrict__ cell_start, u64* counters) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    int cnt = 0;
+    if (c < ncells) cnt = cell_start[c + 1] - cell_start[c];
+    count_host_cues(cnt, counters);
+}
+int sphx_cell_cues(sphx_ctx* ctx, hipStream_t stream) {
+    const int nc = ctx->grid.ncells;
+    hipLaunchKernelGGL(cell_cues_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, nc,
+                       ctx->cell_start.as<int>(), ctx->scal.as<u64>());
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
+}
 __global__ __launch_bounds__(256) void blob_count(GridParams g, BlobBits b, const int* cell_start, int* mcount,
                                                   int* sort_perm, int* crowded, u64* counters) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     int s0 = 0, cnt = 0;
     if (c < g.ncells) { s0 = cell_start[c]; cnt = cell_start[c + 1] - s0; }
-    if (sort_perm) {          // how many crowded cells there are: the host's cue (a step late) for the list form
-        const u64 bm0 = __builtin_amdgcn_ballot_w64(cnt > CELL_SORT_SERIAL && cnt <= CELL_SORT_WAVE);
-        if (bm0 && counters && (threadIdx.x & 63) == 0) atomicAdd(&counters[SC_CROWDED], (u64)__popcll(bm0));
-        if (bm0 && counters) {            // particles in dense cells: the host's cue for finer cells (sphx_api.hip)
-            int dp = cnt >= DENSE_CELL ? cnt : 0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) dp += __shfl_xor(dp, o, 64);
-            if (dp && (threadIdx.x & 63) == 0) atomicAdd(&counters[SC_DENSEP], (u64)dp);
-        }
-    }
+    if (sort_perm) count_host_cues(cnt, counters);
     if (sort_perm && crowded) {
         sort_cell_members(sort_perm, s0, cnt <= CELL_SORT_SERIAL ? cnt : 0, true);
         const bool big = cnt > CELL_SORT_SERIAL && cnt <= CELL_SORT_WAVE;
@@ -994,19 +1066,11 @@ __global__ __launch_bounds__(256) void blob_scatter(int n, GridParams g, BlobBit
 // (left nullptr = identity when the code space would be unreasonably large).
 int sphx_build_blob_order(sphx_ctx* ctx, int64_t n, bool defer_scatter) {
     const GridParams g = ctx->grid;
-    BlobBits b{0, 0, 0, 0};
-    while ((1 << b.bx) < g.nx) ++b.bx;
-    while ((1 << b.by) < g.ny) ++b.by;
-    while ((1 << b.bz) < g.nz) ++b.bz;
-    int bits = b.bx + b.by + b.bz;
-    int hb = b.bx > b.by ? b.bx : b.by;
-    if (b.bz > hb) hb = b.bz;
-    if (hb < 1) hb = 1;
-    // the cube's code space may be up to 8x the Morton one: taken while it stays within 2^24 codes (a
-    // 64 MB count + scan) or within 4x the tight code space
-    if (ctx->blob_curve != 1 && 3 * hb <= 27 && (3 * hb <= 24 || 3 * hb <= bits + 2)) { b.hilbert = hb; bits = 3 * hb; }
+    BlobBits b;
+    const int bits = blob_code_space(ctx, g, &b);
     ctx->qorder = nullptr;
-    if (bits > 27) {
+    ctx->order_by_count = false;
+    if (bits > BLOB_MAX_BITS) {
         if (ctx->cells_unsorted) {
             hipLaunchKernelGGL(cell_sort_members, dim3((unsigned)((g.ncells + 255) / 256)), dim3(256), 0, ctx->stream,
                                g.ncells, ctx->cell_start.as<int>(), ctx->perm.as<int>());
@@ -1015,28 +1079,27 @@ int sphx_build_blob_order(sphx_ctx* ctx, int64_t n, bool defer_scatter) {
         return SPHX_OK;
     }
     const int M = 1 << bits;
-    SPHX_TRY(sphx_ensure(ctx, ctx->porder, (size_t)n * sizeof(int)));
-    SPHX_TRY(sphx_ensure(ctx, ctx->mcount, ((size_t)M + 2) * sizeof(int)));
-    SPHX_TRY(sphx_ensure(ctx, ctx->mstart, ((size_t)M + 2) * sizeof(int)));
+    // the grid build's scatter has counted the cells along the curve (GridBuildOpts::count_curve): the scan follows it
+    // directly, and the gather that carries the order's scatter puts every cell's members in order on the way
+    const bool counted = ctx->curve_counted;
+    ctx->curve_counted = false;
+    if (counted && !(defer_scatter && ctx->cells_unsorted))
+        return sphx_set_err(ctx, SPHX_E_STATE, "sphx_build_blob_order: a grid built with count_curve takes the deferred scatter");
+    if (!counted) SPHX_TRY(blob_counts_prepare(ctx, n, M));
     int* mc = ctx->mcount.as<int>();
     int* ms = ctx->mstart.as<int>();
-    // (all zero between builds when the deferred scatter below cleans up after the scan: no memset then, except once per
-    //  allocation or after a build that did not)
-    if (!(ctx->mcount_zeroed == ctx->mcount.p && ctx->mcount_zeroed_M == M)) {
-        HIPCHK(hipMemsetAsync(mc, 0, ctx->mcount.cap, ctx->stream));
-    }
-    ctx->mcount_zeroed = nullptr;
     int* crowded = nullptr;
     // many crowded cells (a dense core: they sit together, 64 to a wave) are sorted by a launch of their own, one wave
     // per cell; a few are sorted where they are found (two launches less: the headline's case)
-    if (ctx->cells_unsorted && ctx->crowded_last >= CROWDED_LIST_MIN) {          // (a crowded cell has >= 17 members: at most n / 17 of them)
+    if (!counted && ctx->cells_unsorted && ctx->crowded_last >= CROWDED_LIST_MIN) {          // (a crowded cell has >= 17 members: at most n / 17 of them)
         SPHX_TRY(sphx_ensure(ctx, ctx->crowded, ((size_t)n / 17 + 2) * sizeof(int)));
         crowded = ctx->crowded.as<int>();
         HIPCHK(hipMemsetAsync(crowded, 0, sizeof(int), ctx->stream));
     }
-    hipLaunchKernelGGL(blob_count, dim3((unsigned)((g.ncells + 255) / 256)), dim3(256), 0, ctx->stream, g, b,
-                       ctx->cell_start.as<int>(), mc, ctx->cells_unsorted ? ctx->perm.as<int>() : nullptr, crowded,
-                       ctx->scal.as<u64>());
+    if (!counted)
+        hipLaunchKernelGGL(blob_count, dim3((unsigned)((g.ncells + 255) / 256)), dim3(256), 0, ctx->stream, g, b,
+                           ctx->cell_start.as<int>(), mc, ctx->cells_unsorted ? ctx->perm.as<int>() : nullptr, crowded,
+                           ctx->scal.as<u64>());
     if (crowded)
         hipLaunchKernelGGL(cell_sort_crowded, dim3(1024), dim3(256), 0, ctx->stream, crowded, ctx->cell_start.as<int>(),
                            ctx->perm.as<int>());
@@ -1046,6 +1109,7 @@ int sphx_build_blob_order(sphx_ctx* ctx, int64_t n, bool defer_scatter) {
         // the fused loop: the scatter rides in the kernel that permutes the state next (sphx_permute_state), one
         // thread per stored particle there as here
         ctx->blob_scatter_pending = true;
+        ctx->order_by_count = counted;
         ctx->blob_scatter_bits = b;
         ctx->blob_scatter_mstart = ms;
         ctx->mcount_zeroed = ctx->mcount.p;        // (the scatter puts the counts it used back to zero)
@@ -1058,4 +1122,107 @@ int sphx_build_blob_order(sphx_ctx* ctx, int64_t n, bool defer_scatter) {
     HIPCHK(hipGetLastError());
     ctx->qorder = ctx->porder.as<int>();
     return SPHX_OK;
+}
+
+// ---- self-test of the fused step's order (tests/test_gpu_grid_order.py): on the caller's positions, count, scan and
+// scatter once; then the order finished twice - by blob_count (member sort, curve counts, cues), scan and blob_scatter, and
+// by the scatter's curve counts, scan, the counting gather and cell_cues_kernel - and compared on the device ----
+__global__ void order_selftest_rank(int n, const int* perm, const int* cell_of, const int* cell_start, int* rank) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const int p = perm[t];
+    rank[p] = t - cell_start[cell_of[p]];
+}
+// b == nullptr: a[] against zero
+__global__ void order_selftest_cmp(int n, const int* a, const int* b, unsigned long long* bad) {
+    unsigned long long c = 0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) c += (a[i] != (b ? b[i] : 0)) ? 1ull : 0ull;
+    if (c) atomicAdd(bad, c);
+}
+__global__ void order_selftest_cmp_cues(const u64* a, const u64* b, unsigned long long* bad) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        unsigned long long c = (a[SC_CROWDED] != b[SC_CROWDED] ? 1ull : 0ull) + (a[SC_DENSEP] != b[SC_DENSEP] ? 1ull : 0ull);
+        if (c) atomicAdd(bad, c);
+    }
+}
+extern "C" int sphx_selftest_grid_order(sphx_ctx* ctx, int n, const double* x, const double* y, const double* z, double cell_size,
+                                        long long* mismatches, int* new_chain_taken) {
+    if (!ctx || !x || !y || !z || !mismatches || !new_chain_taken || n < 1)
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_selftest_grid_order: bad argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    *mismatches = -1; *new_chain_taken = 0;
+    const GridHostState saved = sphx_grid_host_save(ctx);
+    DevBuf pos, rank, permA, permB0, permB, poA, poB, mcA, mcB, msA, msB, cues, bad;
+    int rc = SPHX_OK;
+    const size_t nb = (size_t)n * sizeof(int);
+    const unsigned pb = (unsigned)((n + 255) / 256);
+    do {
+        if ((rc = sphx_ensure(ctx, pos, (size_t)3 * n * sizeof(double))) != SPHX_OK) break;
+        double* dx = pos.as<double>(); double* dy = dx + n; double* dz = dy + n;
+        if (hipMemcpyAsync(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(dy, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(dz, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = SPHX_E_HIP; break; }
+        GridBuildOpts o;
+        o.sort_cells_later = true;
+        if ((rc = sphx_build_grid(ctx, n, 40, dx, dy, dz, cell_size, o)) != SPHX_OK) break;      // perm: arrival order
+        const GridParams g = ctx->grid;
+        BlobBits b;
+        const int bits = blob_code_space(ctx, g, &b);
+        if (bits > BLOB_MAX_BITS) { *mismatches = 0; break; }          // (no order for this grid: the step keeps the old kernels)
+        const int M = 1 << bits;
+        const size_t mb = ((size_t)M + 2) * sizeof(int);
+        for (DevBuf* q : {&rank, &permA, &permB0, &permB, &poA, &poB})
+            if ((rc = sphx_ensure(ctx, *q, nb)) != SPHX_OK) break;
+        if (rc != SPHX_OK) break;
+        for (DevBuf* q : {&mcA, &mcB, &msA, &msB})
+            if ((rc = sphx_ensure(ctx, *q, mb)) != SPHX_OK) break;
+        if (rc != SPHX_OK) break;
+        if ((rc = sphx_ensure(ctx, cues, 2 * SC_NSLOTS * sizeof(u64))) != SPHX_OK) break;
+        if ((rc = sphx_ensure(ctx, bad, 64)) != SPHX_OK) break;
+        u64* cuesA = cues.as<u64>(); u64* cuesB = cuesA + SC_NSLOTS;
+        const int* cell_of = ctx->cell_of.as<int>();
+        const int* start = ctx->cell_start.as<int>();
+        if (hipMemsetAsync(mcA.p, 0, mb, ctx->stream) != hipSuccess || hipMemsetAsync(mcB.p, 0, mb, ctx->stream) != hipSuccess ||
+            hipMemsetAsync(cues.p, 0, 2 * SC_NSLOTS * sizeof(u64), ctx->stream) != hipSuccess ||
+            hipMemsetAsync(bad.p, 0, 8, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(permA.p, ctx->perm.p, nb, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) { rc = SPHX_E_HIP; break; }
+        hipLaunchKernelGGL(order_selftest_rank, dim3(pb), dim3(256), 0, ctx->stream, n, ctx->perm.as<int>(), cell_of, start, rank.as<int>());
+        // the existing kernels
+        hipLaunchKernelGGL(blob_count, dim3((unsigned)((g.ncells + 255) / 256)), dim3(256), 0, ctx->stream, g, b, start,
+                           mcA.as<int>(), permA.as<int>(), (int*)nullptr, cuesA);
+        if ((rc = excl_scan_plus_total(ctx, mcA.as<int>(), msA.as<int>(), M)) != SPHX_OK) break;
+        hipLaunchKernelGGL(blob_scatter, dim3(pb), dim3(256), 0, ctx->stream, n, g, b, cell_of, permA.as<int>(), start,
+                           msA.as<int>(), poA.as<int>());
+        // the fused step's
+        const CurveCount cc{mcB.as<int>(), b, g.nx, g.ny};
+        hipLaunchKernelGGL(cell_scatter, dim3(pb), dim3(256), 0, ctx->stream, n, cell_of, start, (int*)nullptr, permB0.as<int>(), 0,
+                           (const double*)nullptr, (double*)nullptr, (double*)nullptr, rank.as<int>(), cc);
+        if ((rc = excl_scan_plus_total(ctx, mcB.as<int>(), msB.as<int>(), M)) != SPHX_OK) break;
+        OrderFinish f;
+        f.n = n; f.g = g; f.b = b;
+        f.perm_in = permB0.as<int>(); f.cell_of = cell_of; f.cell_start = start; f.mstart = msB.as<int>();
+        f.perm_out = permB.as<int>(); f.porder = poB.as<int>(); f.mcount = mcB.as<int>();
+        if ((rc = sphx_finish_order_only(ctx, f)) != SPHX_OK) break;
+        hipLaunchKernelGGL(cell_cues_kernel, dim3((unsigned)((g.ncells + 255) / 256)), dim3(256), 0, ctx->stream, g.ncells, start, cuesB);
+        // element for element: the scatter's output, the finished order, the blob order, the curve's starts and total, the
+        // counts put back to zero, the two cues
+        unsigned long long* bd = bad.as<unsigned long long>();
+        hipLaunchKernelGGL(order_selftest_cmp, dim3(256), dim3(256), 0, ctx->stream, n, permB0.as<int>(), ctx->perm.as<int>(), bd);
+        hipLaunchKernelGGL(order_selftest_cmp, dim3(256), dim3(256), 0, ctx->stream, n, permB.as<int>(), permA.as<int>(), bd);
+        hipLaunchKernelGGL(order_selftest_cmp, dim3(256), dim3(256), 0, ctx->stream, n, poB.as<int>(), poA.as<int>(), bd);
+        hipLaunchKernelGGL(order_selftest_cmp, dim3(256), dim3(256), 0, ctx->stream, M + 1, msB.as<int>(), msA.as<int>(), bd);
+        hipLaunchKernelGGL(order_selftest_cmp, dim3(256), dim3(256), 0, ctx->stream, M + 1, mcB.as<int>(), (const int*)nullptr, bd);
+        hipLaunchKernelGGL(order_selftest_cmp_cues, dim3(1), dim3(64), 0, ctx->stream, cuesA, cuesB, bd);
+        unsigned long long h = 0;
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, bad.p, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = SPHX_E_HIP; break; }
+        *mismatches = (long long)h;
+        *new_chain_taken = 1;
+    } while (false);
+    if (rc == SPHX_E_HIP) (void)sphx_set_err(ctx, SPHX_E_HIP, "sphx_selftest_grid_order: a HIP call failed");
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    sphx_grid_host_restore(ctx, saved);
+    for (DevBuf* q : {&pos, &rank, &permA, &permB0, &permB, &poA, &poB, &mcA, &mcB, &msA, &msB, &cues, &bad}) sphx_release(ctx, *q);
+    return rc;
 }

@@ -44,27 +44,45 @@ struct GatherArgs {
     const int *bs_cell_of, *bs_cell_start, *bs_mstart;
     int* bs_porder;
     int* bs_mcount;                    // the curve's per-cell counts: put back to zero here (the scan has read them)
+    // set (with bs_porder): perm holds every cell's members in arrival order, as the grid build's scatter left them.
+    // A member's place in its cell is then counted here - how many of the cell's members are smaller: distinct indices,
+    // so exactly the ascending order sort_cell_members makes (sphx_grid.hip), up to CELL_SORT_WAVE members and arrival
+    // order above, as there - and the finished order written to bs_perm_out.  The thread of slot t moves its particle to
+    // slot f of the same cell; every read of perm is of the scatter's output.
+    int* bs_perm_out;
 };
 __global__ __launch_bounds__(256) void gather_kernel(GatherArgs a) {
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= a.n) return;
     const int p = a.perm[t];
+    int f = t;                             // where the particle goes
     if (a.bs_porder) {
         const int c = a.bs_cell_of[p];
+        const int s0 = a.bs_cell_start[c];
+        if (a.bs_perm_out) {
+            const int cnt = a.bs_cell_start[c + 1] - s0;
+            if (cnt > 1 && cnt <= CELL_SORT_WAVE) {
+                int r = 0;
+#pragma unroll 4
+                for (int j = 0; j < cnt; ++j) r += a.perm[s0 + j] < p ? 1 : 0;
+                f = s0 + r;
+            }
+            a.bs_perm_out[f] = p;
+        }
         const int cx = c % a.bs_g.nx, cy = (c / a.bs_g.nx) % a.bs_g.ny, cz = c / (a.bs_g.nx * a.bs_g.ny);
         const unsigned rk = blob_rank(cx, cy, cz, a.bs_b);
-        a.bs_porder[a.bs_mstart[rk] + (t - a.bs_cell_start[c])] = t;
-        if (t == a.bs_cell_start[c]) a.bs_mcount[rk] = 0;          // (one member per cell cleans up)
+        a.bs_porder[a.bs_mstart[rk] + (f - s0)] = f;
+        if (f == s0) a.bs_mcount[rk] = 0;          // (one member per cell cleans up)
     }
-    for (int q = 0; q < a.narr; ++q) a.dst[q][t] = a.src[q][p];
+    for (int q = 0; q < a.narr; ++q) a.dst[q][f] = a.src[q][p];
     if (a.id_src) {
         const int id = a.id_src[p];
-        a.id_dst[t] = id;
-        if (a.inv) a.inv[id] = t;
+        a.id_dst[f] = id;
+        if (a.inv) a.inv[id] = f;
     }
     if (a.fun_src) {                       // rows of a.s doubles, a multiple of 16: aligned 16-B copies
         const double2* src = reinterpret_cast<const double2*>(a.fun_src + (size_t)p * a.s);
-        double2* dst = reinterpret_cast<double2*>(a.fun_dst + (size_t)t * a.s);
+        double2* dst = reinterpret_cast<double2*>(a.fun_dst + (size_t)f * a.s);
         for (int q = 0; q < a.s / 2; ++q) dst[q] = src[q];
     }
 }
@@ -82,7 +100,10 @@ int sphx_permute_state(sphx_ctx* ctx, int64_t n, bool split, hipEvent_t after_fi
     DevBuf* dst[] = {&b.x, &b.y, &b.z, &b.hprev, &b.vx, &b.vy, &b.vz, &b.ax, &b.ay, &b.az,
                      &b.m, &b.T, &b.mu, &b.gam, &b.E, &b.ptype};
     GatherArgs g;
-    g.bs_porder = nullptr;
+    g.bs_porder = nullptr; g.bs_perm_out = nullptr;
+    const bool by_count = ctx->blob_scatter_pending && ctx->order_by_count;
+    ctx->order_by_count = false;
+    if (by_count) g.bs_perm_out = ctx->perm_fin.as<int>();
     if (ctx->blob_scatter_pending) {
         g.bs_g = ctx->grid; g.bs_b = ctx->blob_scatter_bits;
         g.bs_cell_of = ctx->cell_of.as<int>(); g.bs_cell_start = ctx->cell_start.as<int>();
@@ -114,20 +135,41 @@ int sphx_permute_state(sphx_ctx* ctx, int64_t n, bool split, hipEvent_t after_fi
         rest.narr = g.narr - 4;
         for (int q = 0; q < rest.narr; ++q) { rest.src[q] = g.src[q + 4]; rest.dst[q] = g.dst[q + 4]; }
         rest.id_src = nullptr;
-        rest.bs_porder = nullptr;
+        rest.bs_porder = nullptr; rest.bs_perm_out = nullptr;
+        if (by_count) rest.perm = g.bs_perm_out;       // (the finished order: behind the first launch, like everything it reads)
         g.narr = 4;
         g.fun_src = nullptr; g.fun_dst = nullptr;
     }
     hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, g);
     HIPCHK(hipEventRecord(after_first, ctx->stream));
+    // ctx->perm names the finished order from here on (the side stream's part, tree gravity, the samplers)
+    if (by_count) { const DevBuf fin = ctx->perm_fin; ctx->perm_fin = ctx->perm; ctx->perm = fin; }
     if (split) {
         // (behind the search's part, not beside it: both are bound by the same memory system)
         HIPCHK(hipStreamWaitEvent(ctx->side_stream, after_first, 0));
         hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->side_stream, rest);
+        // the host's cues from the cell counts, which no kernel of this build has walked: here, beside the search and in
+        // front of this step's sum of h on the same stream, whose copy carries them out
+        if (by_count) SPHX_TRY(sphx_cell_cues(ctx, ctx->side_stream));
         HIPCHK(hipEventRecord(ctx->ev_perm, ctx->side_stream));
+    } else if (by_count) {
+        SPHX_TRY(sphx_cell_cues(ctx, ctx->stream));
     }
     HIPCHK(hipGetLastError());
     StateArrays tmp = ctx->st; ctx->st = ctx->alt; ctx->alt = tmp;
+    return SPHX_OK;
+}
+
+int sphx_finish_order_only(sphx_ctx* ctx, const OrderFinish& o) {
+    GatherArgs g;
+    g.n = o.n; g.narr = 0; g.s = 0;
+    g.perm = o.perm_in;
+    g.id_src = nullptr; g.id_dst = nullptr; g.inv = nullptr; g.fun_src = nullptr; g.fun_dst = nullptr;
+    g.bs_g = o.g; g.bs_b = o.b;
+    g.bs_cell_of = o.cell_of; g.bs_cell_start = o.cell_start; g.bs_mstart = o.mstart;
+    g.bs_porder = o.porder; g.bs_mcount = o.mcount; g.bs_perm_out = o.perm_out;
+    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((o.n + 255) / 256)), dim3(256), 0, ctx->stream, g);
+    HIPCHK(hipGetLastError());
     return SPHX_OK;
 }
 

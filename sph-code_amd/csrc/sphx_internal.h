@@ -252,6 +252,10 @@ struct sphx_ctx {
     double cell_scale = 1.0;        // the factor cell_feedback has reached (sphx_cell_feedback)
     // what a grid build or a blob order left for a later call to finish (outputs of sphx_build_grid / sphx_build_blob_order)
     bool cells_unsorted = false;         // the per-cell member sort rides in the blob-order pass
+    // the fused step's build (GridBuildOpts::count_curve): cell_scatter has written the curve's counts, and the members'
+    // order is finished by the gather that permutes the state (by counting, into perm_fin - swapped with perm there)
+    bool curve_counted = false;
+    bool order_by_count = false;
     bool blob_scatter_pending = false;   // the blob order's last scatter rides in the state's permutation
     BlobBits blob_scatter_bits;
     const int* blob_scatter_mstart = nullptr;
@@ -325,6 +329,7 @@ struct sphx_ctx {
     DevBuf olev_start, olev_fill, olev_list, olev_key;
     DevBuf lbs_state[2];                   // tile words of the look-back scan (sphx_grid.hip), per launching stream
     DevBuf cell_rank;                       // the particles' arrival numbers in their cells (grid build)
+    DevBuf perm_fin;                        // the finished cell order of a build whose members the gather puts in order (then swapped with perm)
     DevBuf tie_list;                       // int4 {query slot, rank, index a, index b}: near ties the grouped search leaves to the list-mode launch's tie blocks
     // sphx_blob.hip: per-workgroup distinct-neighbour lists + 16-bit slot lists for the LDS passes
     DevBuf slot16, uniq;
@@ -544,6 +549,21 @@ int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m);
 int sphx_blob_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m, u64* ct_bits);
 int sphx_blob_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted, double* F,
                       double* Z, double* agb, int agb_on);
+// Member order inside a cell (sphx_grid.hip; the counting form of sphx_integrate.hip's gather): ascending index up to
+// CELL_SORT_WAVE members - one lane's insertion sort up to CELL_SORT_SERIAL, the whole wave beyond - arrival order above.
+#define CELL_SORT_SERIAL 16
+#define CELL_SORT_WAVE 512
+// the host's cues SC_CROWDED / SC_DENSEP of the current grid, one thread per cell on `stream` (what blob_count adds up
+// on the way where it runs)
+int sphx_cell_cues(sphx_ctx* ctx, hipStream_t stream);
+// the gather's order-finishing part alone (no array moved), for sphx_selftest_grid_order
+struct OrderFinish {
+    int n;
+    GridParams g; BlobBits b;
+    const int *perm_in, *cell_of, *cell_start, *mstart;
+    int *perm_out, *porder, *mcount;
+};
+int sphx_finish_order_only(sphx_ctx* ctx, const OrderFinish& o);
 struct GridBuildOpts {
     // the grid is sized from the previous build's box statistics, already on the host; this build's are copied out for
     // the next one (the fused loop, sphx_dev_search): the host never waits for the step it launches
@@ -553,6 +573,10 @@ struct GridBuildOpts {
     hipEvent_t alias_ev = nullptr;
     // the per-cell member sort is left to sphx_build_blob_order, which the caller runs next (ctx->cells_unsorted says so)
     bool sort_cells_later = false;
+    // with sort_cells_later, from the fused step only: the caller runs sphx_build_blob_order(defer_scatter = true) and
+    // sphx_permute_state next.  Where the count kernel kept the arrival numbers and the curve's code space fits, the
+    // scatter then writes the curve's counts and the gather orders the members: no pass over the cells (ctx->curve_counted)
+    bool count_curve = false;
     // set (all three, vx vy vz): drv:233-238 is applied to ctx->st - positions and these velocities - by the build's first pass
     double* clamp_vel[3] = {nullptr, nullptr, nullptr};
 };
