@@ -1,6 +1,7 @@
 // sphx_blob.h - shared pieces of the LDS-staged sum passes (sphx_blob.hip: hydro_update's sums;
 // sphx_loopforms.hip: the loop forms of the step's loop-form mode): blob geometry, the LDS image
-// layout, staging, slot-list access and the lanes-per-particle reductions.
+// layout, staging, slot-list access, the lanes-per-particle reductions, the walk of a pass over its
+// blobs and slot lists (blob_pass: written once, for every pass description) and the launcher.
 #pragma once
 #include "sphx_internal.h"
 #include "sphx_pair.h"          // Q4, gload4; the pair terms the LDS kernels share with the gather kernels
@@ -30,16 +31,20 @@
 
 typedef unsigned short u16;
 
-__device__ __forceinline__ unsigned slot_hash(int j) {
-    return (unsigned)(((u64)((unsigned)j * 2654435761u) * (u64)BLOB_S) >> 32);
-}
-
 // ---- helpers -----------------------------------------------------------------------------------
 // chunks 2c, 2c+1 of slot s
 __device__ __forceinline__ Q4 lload4(const double2* img, int s, int c2) {
     const double2 lo = img[(2 * c2) * BLOB_S + s];
     const double2 hi = img[(2 * c2 + 1) * BLOB_S + s];
     return Q4{lo.x, lo.y, hi.x, hi.y};
+}
+// a whole 64-B record: from slot s of the image / from global memory
+struct Q8 { Q4 lo, hi; };
+__device__ __forceinline__ Q8 lload8(const double2* img, int s) { return Q8{lload4(img, s, 0), lload4(img, s, 1)}; }
+template <class Rec>
+__device__ __forceinline__ Q8 gload8(const Rec* r) {
+    const double* q = reinterpret_cast<const double*>(r);
+    return Q8{gload4(q), gload4(q + 4)};
 }
 // sqrt for the distances of the neighbour loops: the library's correctly rounded sequence (v_rsq_f64
 // seed, two coupled Newton steps on g ~ sqrt(x), h ~ 1/(2 sqrt(x)), residual corrections) without its
@@ -86,6 +91,17 @@ __device__ __forceinline__ double group_max(double v) {
     v = fmax(v, pair_swap(v));
     if (LPP == 4) v = fmax(v, pair_swap2(v));
     return v;
+}
+// group_total of every double of a struct of sums
+template <class S>
+__device__ __forceinline__ void group_total_fields(S& s) {
+    constexpr int NF = sizeof(S) / sizeof(double);
+    static_assert(sizeof(S) == NF * sizeof(double), "a struct of doubles");
+    double f[NF];
+    __builtin_memcpy(f, &s, sizeof(S));
+#pragma unroll
+    for (int q = 0; q < NF; ++q) f[q] = group_total(f[q]);
+    __builtin_memcpy(&s, f, sizeof(S));
 }
 
 #define NSTAGE ((BLOB_S + PASS_T - 1) / PASS_T)
@@ -179,3 +195,165 @@ BlobSel sphx_blob_sel(sphx_ctx* ctx, int part);
 int sphx_blob_grid(sphx_ctx* ctx, int nblk);       // persistent grid of the LDS passes (2 workgroups per CU)
 // allow `kernel` up to `bytes` of dynamic LDS on the context's device (once per kernel: sphx_ctx::lds_raised)
 int sphx_lds_opt_in(sphx_ctx* ctx, const void* kernel, size_t bytes);
+
+// the launch bounds of a pass kernel and the arguments every LDS kernel begins with
+#define BLOB_KERNEL __global__ __launch_bounds__(PASS_T, PASS_MINW) void
+#define BLOB_COMMON int n, int npad, int k, int nblk, const int* __restrict__ nbr, const u16* __restrict__ slot16, \
+                    const int* __restrict__ uniq, const int* __restrict__ qorder
+// One launch on the persistent grid: blob_launch fills in BLOB_COMMON, `rest` are the arguments behind it.
+// Dynamic LDS: per_slot bytes of image per slot (0: no image) and the slot tile, + extra.
+template <class Kern, class... Rest>
+static int blob_launch(sphx_ctx* ctx, Kern kern, int per_slot, size_t extra, int64_t n, int k, Rest... rest) {
+    const int64_t npad = sphx_pad64(n);
+    const int nblk = (int)((npad + BLOB_P - 1) / BLOB_P);
+    SPHX_TRY(sphx_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), IMG_BYTES(per_slot, SPHX_MAX_K) + extra));
+    hipLaunchKernelGGL(kern, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(per_slot, k) + extra, ctx->stream, (int)n,
+                       (int)npad, k, nblk, ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(), ctx->qorder, rest...);
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
+}
+
+// ---- the walk of an LDS sum pass ------------------------------------------------------------------------------------
+// How a pass goes through its blobs and its slot lists is written here once (blob_pass); a kernel is its __global__
+// signature, a pass description P and one call.  P says what differs between the passes and nothing of the walk:
+//   Rec, NSIDE, PER_SLOT, rec, sides()   what is staged: the 64-B records, the side values per slot (stage<>), and the
+//                                        image bytes per slot the launcher is given
+//   Row, load_row(i), load_out(row, o, on)
+//                                        the row particle's own loads, issued ahead of the barrier behind the staging:
+//                                        by stored particle i, then what is indexed by the output index o
+//   ROW_FROM_LIST, row_point(row, nb)    deltas are relative to the first list position (hydro_update, nsc:580-581)
+//                                        or to the particle itself (loop forms)
+//   wanted(row)                          whether the row particle sums at all
+//   Nb, staged(img, side, s, jp), global(j), none(row)
+//                                        one list position's operands: out of image slot s (jp: where the int32 list
+//                                        names it, for what is not staged), from global memory, or the stand-in of a
+//                                        position the list does not have
+//   Sums, term<CLIP>(sums, nb, row)      the pair's term (sphx_pair.h, or the loop forms'); its return value is the
+//                                        candidate of the crossing-time maximum (VOTES) or the species weight
+//   CLIPS                                whether the term distinguishes clipped gradients (4-way dispatch, else 2-way)
+//   finish(sums, max, row, i, o), VOTES  what the first lane of a particle writes; returns its crossing-time vote
+struct BlobSides { const double* g0 = nullptr; int s0 = 0; const double* g1 = nullptr; int s1 = 0; };   // stage<>'s g0, g1
+
+// dynamic LDS of a pass: 4 * BLOB_S chunks of image, BLOB_S side values (NSIDE > 0), the slot tile.  (Accessors, not
+// pointers handed on in a struct: the compiler has to see the LDS address space at every use, or it merges an image read
+// with the global-memory read of the other branch into one flat load.)
+template <int NSIDE>
+struct BlobLds {
+    // (`img`: the one dynamic-LDS symbol of every kernel of the library, blob_species_kernel's and blob_drag_kernel's too -
+    // with a second one in the module the species kernels came out with flat loads as well)
+    static __device__ __forceinline__ double2* img() { extern __shared__ double2 img[]; return img; }
+    static __device__ __forceinline__ double* side() { return reinterpret_cast<double*>(img() + 4 * BLOB_S); }
+    static __device__ __forceinline__ u16* tile() { return reinterpret_cast<u16*>(side() + (NSIDE ? BLOB_S : 0)); }
+};
+
+// A batch of NB list positions of this lane.  FAST: every lane of the wave has a staged neighbour at
+// each of them (the usual case): straight-line LDS reads and arithmetic, nothing to branch on.
+// Otherwise a position may be empty (skipped) or unstaged (fetched through the int32 list).
+// out: what the term returned (0 where the list has no neighbour).
+template <bool FAST, bool CLIP, class P>
+__device__ __forceinline__ void blob_batch(const P& ps, typename P::Sums& a, double (&out)[NB], const unsigned (&sl)[NB],
+                                           const int* __restrict__ jp, size_t colstep, const typename P::Row& row) {
+    typedef BlobLds<P::NSIDE> L;
+    typename P::Nb f[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+        if (FAST || sl[u] < SLOT_OVER) f[u] = ps.staged(L::img(), L::side(), (int)sl[u], jp + u * colstep);
+        else if (sl[u] == SLOT_OVER) f[u] = ps.global(jp[u * colstep]);
+        else f[u] = P::none(row);
+    }
+    if (FAST) __builtin_amdgcn_sched_barrier(0);       // all of the batch's LDS reads are issued before its arithmetic
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+        out[u] = 0.0;
+        if (!FAST && sl[u] == SLOT_NONE) continue;
+        out[u] = ps.template term<CLIP>(a, f[u], row);
+    }
+}
+// the batch in the form its slots and the runtime `clip` ask for
+template <class P>
+__device__ __forceinline__ void blob_batch_any(const P& ps, int clip, typename P::Sums& a, double (&out)[NB],
+                                               const unsigned (&sl)[NB], const int* __restrict__ jp, size_t colstep,
+                                               const typename P::Row& row) {
+    const bool fast = all_staged(sl);
+    if constexpr (P::CLIPS) {
+        if (fast && !clip) blob_batch<true, false>(ps, a, out, sl, jp, colstep, row);
+        else if (fast) blob_batch<true, true>(ps, a, out, sl, jp, colstep, row);
+        else if (!clip) blob_batch<false, false>(ps, a, out, sl, jp, colstep, row);
+        else blob_batch<false, true>(ps, a, out, sl, jp, colstep, row);
+    } else {
+        if (fast) blob_batch<true, false>(ps, a, out, sl, jp, colstep, row);
+        else blob_batch<false, false>(ps, a, out, sl, jp, colstep, row);
+    }
+}
+// the row point out of the first list position (column p of the list, particle t of the blob): image, global memory,
+// or - no first neighbour - what load_row left.  (The pass's whole fetch is called and row_point keeps what it wants:
+// the loads of the rest - a side value, ViscPwPass's bc[*jp] - are plain loads of valid addresses that the compiler
+// drops as dead; made volatile or atomic they would be executed.)
+template <class P>
+__device__ __forceinline__ void blob_row_point(const P& ps, typename P::Row& row, const int* __restrict__ nbr, int p,
+                                               int t) {
+    typedef BlobLds<P::NSIDE> L;
+    const unsigned sl0 = L::tile()[t];
+    if (sl0 < SLOT_OVER) P::row_point(row, ps.staged(L::img(), L::side(), (int)sl0, nbr + p));
+    else if (sl0 == SLOT_OVER) P::row_point(row, ps.global(nbr[p]));
+}
+
+// The pass.  A change to the walk - workgroups per CU, prefetch depth, how blobs are handed out - is made here.
+// clip: ignored unless P::CLIPS.  omap, n_active: outputs go to the caller's index o (device API: ghosts, o >= n_active,
+// are candidates only); omap == nullptr: o = the stored particle.  ct_bits: where P::VOTES passes vote.
+template <class P>
+__device__ __forceinline__ void blob_pass(const P& ps, int n, int npad, int k, int nblk, const int* __restrict__ nbr,
+                                          const u16* __restrict__ slot16, const int* __restrict__ uniq,
+                                          const int* __restrict__ qorder, int clip, const int* __restrict__ omap,
+                                          int n_active, u64* ct_bits, const BlobSel& sel) {
+    static_assert(P::PER_SLOT == 64 + (P::NSIDE ? 8 : 0), "image bytes per slot: the record and one side value");
+    typedef BlobLds<P::NSIDE> L;
+    const BlobSides sd = ps.sides();
+    const int t = threadIdx.x / LPP, half = threadIdx.x & (LPP - 1);     // half: which partial sum
+    u64 my_ct = SPHX_CT_NONE;
+    // persistent workgroups (two per CU): blob after blob, no dispatch gap between them
+    const int nsel = blob_sel_count(sel, nblk);
+    for (int bi = blockIdx.x; bi < nsel; bi += gridDim.x) {
+        const int b = blob_sel_at(sel, bi, nsel);
+        const int p = b * BLOB_P + t;
+        const int i = (p < n) ? qorder[p] : 0;
+        stage<P::NSIDE>(L::img(), L::side(), L::tile(), ps.rec, sd.g0, sd.s0, sd.g1, sd.s1, uniq + (size_t)b * BLOB_S,
+                        slot16, npad, k, b);
+        typename P::Row row = ps.load_row(i);                // (issued ahead of the wait for omap[i], not behind it)
+        const int o = (p < n) ? (omap ? omap[i] : i) : 0x7FFFFFFF;
+        ps.load_out(row, o, o < n_active);
+        __syncthreads();
+        if (o < n_active) {
+            if constexpr (P::ROW_FROM_LIST) blob_row_point(ps, row, nbr, p, t);
+            typename P::Sums a{};
+            double mx = 0.0;
+            if (P::wanted(row)) {
+                const int nm = KPAD(k) / LPP;
+                unsigned sl[NB];
+                load_slots(sl, L::tile(), 0, half, t);
+                for (int m0 = 0; m0 < nm; m0 += NB) {
+                    unsigned cur[NB];
+#pragma unroll
+                    for (int u = 0; u < NB; ++u) cur[u] = sl[u];
+                    // next batch's slots, behind this one's reads
+                    if (m0 + NB < nm) load_slots(sl, L::tile(), m0 + NB, half, t);
+                    double out[NB];
+                    blob_batch_any(ps, clip, a, out, cur, nbr + ((size_t)(LPP * m0 + half) * npad + p),
+                                   LPP * (size_t)npad, row);
+                    if (P::VOTES) {
+#pragma unroll
+                        for (int u = 0; u < NB; ++u) mx = fmax(mx, out[u]);
+                    }
+                }
+            }
+            group_total_fields(a);
+            if (P::VOTES) mx = group_max(mx);
+            if (!half) {
+                const u64 cb = ps.finish(a, mx, row, i, o);
+                my_ct = cb < my_ct ? cb : my_ct;
+            }
+        }
+        __syncthreads();                                   // the image is rewritten by the next blob
+    }
+    if (P::VOTES) block_min_vote<PASS_T>(my_ct, ct_bits);
+}

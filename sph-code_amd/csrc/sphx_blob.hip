@@ -22,8 +22,9 @@
 // distinct neighbours; the most seen at BLOB_P = 128 is ~800) keeps the 0xFFFE marker and is
 // fetched from global memory through the int32 list.
 //
-// What is computed for a neighbour is not written here: every *_batch function loads its records (LDS, or global
-// memory for an unstaged one) and hands them to the term functions of sphx_pair.h, which the gather kernels call too.
+// What is computed for a neighbour is not written here: a pass hands its operands to the term functions of sphx_pair.h,
+// which the gather kernels call too.  How a pass walks its blobs and slot lists is not written here either: blob_pass
+// (sphx_blob.h) does, for the pass descriptions below and those of sphx_loopforms.hip.
 #include "sphx_blob.h"
 #include "sphx_wave.h"
 #pragma clang fp contract(off)            // (as sphx_pair.h: NumPy never fuses a multiply into an add)
@@ -234,292 +235,152 @@ int sphx_blob_translate(sphx_ctx* ctx, int64_t n, int k) {
     return SPHX_OK;
 }
 
-// A batch of NB list positions of this lane.  FAST: every lane of the wave has a staged neighbour at
-// each of them (the usual case): straight-line LDS reads and arithmetic, nothing to branch on.
-// Otherwise a position may be empty (skipped) or unstaged (fetched through the int32 list).
-// wout: the batch's species weights Nw_j W_ij (nsc:626; 0 where the list has no neighbour), for the kernel that goes on to
-// the composition sweeps
-template <bool FAST, bool CLIP>
-__device__ __forceinline__ void density_batch(DensAcc& a, double (&wout)[NB], const unsigned (&sl)[NB], const double2* img,
-                                              const RecA* __restrict__ rec, const int* __restrict__ nbr,
-                                              size_t col0, size_t colstep, double xr, double yr, double zr,
-                                              double hi2, double ci, double Ai) {
-    Q4 q0b[NB], q1b[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        if (FAST || sl[u] < SLOT_OVER) { q0b[u] = lload4(img, (int)sl[u], 0); q1b[u] = lload4(img, (int)sl[u], 1); }
-        else if (sl[u] == SLOT_OVER) {
-            const double* q = reinterpret_cast<const double*>(&rec[nbr[col0 + u * colstep]]);
-            q0b[u] = gload4(q); q1b[u] = gload4(q + 4);
-        } else { q0b[u] = Q4{xr, yr, zr, 0.0}; q1b[u] = Q4{0.0, 0.0, 0.0, 0.0}; }
-    }
-    if (FAST) __builtin_amdgcn_sched_barrier(0);       // all of the batch's LDS reads are issued before its arithmetic
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        wout[u] = 0.0;
-        if (!FAST && sl[u] == SLOT_NONE) continue;
-        wout[u] = density_term<SqrtMid>(a, q0b[u], q1b[u], xr, yr, zr, hi2, ci, Ai, CLIP);
-    }
-}
+// ---- the four sum passes of hydro_update: what each stages, loads, computes per pair and writes.  How a pass walks
+// its blobs and slot lists is blob_pass (sphx_blob.h). ---------------------------------------------------------------
 
 // ---- pass 1: rho, rho_dust, n, grad P        nsc:588-619 --------------------------------------
-__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_kernel(int n, int npad, int k, int nblk,
-                                                              const int* __restrict__ nbr,
-                                                              const u16* __restrict__ slot16,
-                                                              const int* __restrict__ uniq,
-                                                              const int* __restrict__ qorder, int clip,
-                                                              const int* __restrict__ omap, int n_active,
-                                                              const RecA* __restrict__ rec, double* rho_s,
-                                                              double* rho, double* rhod, double* nden, double* G,
-                                                              double* ha, BlobSel sel) {
-    extern __shared__ double2 img[];                       // 4 * BLOB_S chunks, then the slot tile
-    u16* tile = reinterpret_cast<u16*>(img + 4 * BLOB_S);
-    const int t = threadIdx.x / LPP, half = threadIdx.x & (LPP - 1);     // half: which partial sum
-    // persistent workgroups (two per CU): blob after blob, no dispatch gap between them
-    const int nsel = blob_sel_count(sel, nblk);
-    for (int bi = blockIdx.x; bi < nsel; bi += gridDim.x) {
-        const int b = blob_sel_at(sel, bi, nsel);
-        const int p = b * BLOB_P + t;
-        const int i = (p < n) ? qorder[p] : 0;
-        stage<0>(img, nullptr, tile, rec, nullptr, 0, nullptr, 0, uniq + (size_t)b * BLOB_S, slot16, npad, k, b);
-        const double* self = reinterpret_cast<const double*>(&rec[i]);
-        const Q4 s0 = gload4(self), s1 = gload4(self + 4);     // x y z h2 | c1 ms A Nw
-        // outputs go to the caller's index o (device API: ghosts, o >= n_active, are candidates only)
-        const int o = (p < n) ? (omap ? omap[i] : i) : 0x7FFFFFFF;
-        __syncthreads();
-        if (o < n_active) {
-            double xr = s0.a, yr = s0.b, zr = s0.c;
-            {
-                const unsigned sl0 = tile[t];
-                if (sl0 < SLOT_OVER) { const Q4 r = lload4(img, (int)sl0, 0); xr = r.a; yr = r.b; zr = r.c; }
-                else if (sl0 == SLOT_OVER) { const int j0 = nbr[p]; xr = rec[j0].x; yr = rec[j0].y; zr = rec[j0].z; }
-            }
-            const double hi2 = s0.d, ci = -6.0 * s1.a, Ai = s1.c;
-            DensAcc a{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            const int nm = KPAD(k) / LPP;
-            unsigned sl[NB];
-            load_slots(sl, tile, 0, half, t);
-            for (int m0 = 0; m0 < nm; m0 += NB) {
-                unsigned cur[NB];
-#pragma unroll
-                for (int u = 0; u < NB; ++u) cur[u] = sl[u];
-                if (m0 + NB < nm) load_slots(sl, tile, m0 + NB, half, t);    // next batch's slots, behind this one's reads
-                const size_t col0 = (size_t)(LPP * m0 + half) * npad + p;
-                const bool fast = all_staged(cur);
-                double wo[NB];                                 // (the species weights: not wanted here)
-                if (fast && !clip) density_batch<true, false>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
-                else if (fast) density_batch<true, true>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
-                else if (!clip) density_batch<false, false>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
-                else density_batch<false, true>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
-            }
-            const double s_rho = group_total(a.rho), s_rd = group_total(a.rd), s_n = group_total(a.n);
-            const double gx = group_total(a.gx), gy = group_total(a.gy), gz = group_total(a.gz);
-            if (!half) {
-                rho[o] = s_rho; rhod[o] = s_rd; nden[o] = s_n;
-                rho_s[i] = s_rho;                                     // storage order: staged by pass 2
-                if (G) { G[3 * (size_t)o + 0] = -gx; G[3 * (size_t)o + 1] = -gy; G[3 * (size_t)o + 2] = -gz; }
-                ha[3 * (size_t)o + 0] = -gx / s_rho;                  // nsc:619
-                ha[3 * (size_t)o + 1] = -gy / s_rho;
-                ha[3 * (size_t)o + 2] = -gz / s_rho;
-            }
-        }
-        __syncthreads();                                   // the image is rewritten by the next blob
+struct DensityPass {
+    typedef RecA Rec;
+    typedef DensAcc Sums;
+    static constexpr int NSIDE = 0, PER_SLOT = 64;
+    static constexpr bool CLIPS = true, VOTES = false, ROW_FROM_LIST = true;
+    const RecA* __restrict__ rec;
+    double *rho_s, *rho, *rhod, *nden, *G, *ha;
+    struct Row { double xr, yr, zr, hi2, ci, Ai; };
+    typedef Q8 Nb;                                          // x y z h2 | c1 ms A Nw
+    __device__ __forceinline__ BlobSides sides() const { return {}; }
+    __device__ __forceinline__ Row load_row(int i) const {
+        const Q8 s = gload8(&rec[i]);
+        return Row{s.lo.a, s.lo.b, s.lo.c, s.lo.d, -6.0 * s.hi.a, s.hi.c};
     }
+    __device__ __forceinline__ static void load_out(Row&, int, bool) {}
+    __device__ __forceinline__ static void row_point(Row& r, const Nb& f) { r.xr = f.lo.a; r.yr = f.lo.b; r.zr = f.lo.c; }
+    __device__ __forceinline__ static bool wanted(const Row&) { return true; }
+    __device__ __forceinline__ Nb staged(const double2* img, const double*, int s, const int*) const {
+        return lload8(img, s);
+    }
+    __device__ __forceinline__ Nb global(int j) const { return gload8(&rec[j]); }
+    __device__ __forceinline__ static Nb none(const Row& r) { return Nb{Q4{r.xr, r.yr, r.zr, 0.0}, Q4{0.0, 0.0, 0.0, 0.0}}; }
+    // returns the species weight Nw_j W_ij (nsc:626), for the kernel that goes on to the composition sweeps
+    template <bool CLIP>
+    __device__ __forceinline__ double term(Sums& a, const Nb& f, const Row& r) const {
+        return density_term<SqrtMid>(a, f.lo, f.hi, r.xr, r.yr, r.zr, r.hi2, r.ci, r.Ai, CLIP);
+    }
+    __device__ __forceinline__ u64 finish(const Sums& a, double, const Row&, int i, int o) const {
+        rho[o] = a.rho; rhod[o] = a.rd; nden[o] = a.n;
+        rho_s[i] = a.rho;                                     // storage order: staged by pass 2
+        if (G) { G[3 * (size_t)o + 0] = -a.gx; G[3 * (size_t)o + 1] = -a.gy; G[3 * (size_t)o + 2] = -a.gz; }
+        ha[3 * (size_t)o + 0] = -a.gx / a.rho;                // nsc:619
+        ha[3 * (size_t)o + 1] = -a.gy / a.rho;
+        ha[3 * (size_t)o + 2] = -a.gz / a.rho;
+        return SPHX_CT_NONE;
+    }
+};
+BLOB_KERNEL blob_density_kernel(BLOB_COMMON, int clip, const int* __restrict__ omap, int n_active,
+                                const RecA* __restrict__ rec, double* rho_s, double* rho, double* rhod, double* nden,
+                                double* G, double* ha, BlobSel sel) {
+    blob_pass(DensityPass{rec, rho_s, rho, rhod, nden, G, ha}, n, npad, k, nblk, nbr, slot16, uniq, qorder, clip, omap,
+              n_active, nullptr, sel);
 }
 
 // ---- pass 2: Pi_i, crossing time             nsc:639-649, nsc:776-786 --------------------------
-template <bool FAST>
-__device__ __forceinline__ void pi_batch(double& s_pi, double& maxrel, const unsigned (&sl)[NB], const double2* img,
-                                         const double* lrho, const RecB* __restrict__ recb,
-                                         const double* __restrict__ rho_s, const int* __restrict__ nbr, size_t col0,
-                                         size_t colstep, const Q4& r0, const Q4& rv, double rho_i, double cs_i) {
-    Q4 q0b[NB], qvb[NB];
-    double rhob[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        if (FAST || sl[u] < SLOT_OVER) {
-            q0b[u] = lload4(img, (int)sl[u], 0); qvb[u] = lload4(img, (int)sl[u], 1);
-            rhob[u] = lrho[sl[u]];
-        } else if (sl[u] == SLOT_OVER) {
-            const int jj = nbr[col0 + u * colstep];
-            const double* qb = reinterpret_cast<const double*>(&recb[jj]);
-            q0b[u] = gload4(qb); qvb[u] = gload4(qb + 4);
-            rhob[u] = rho_s[jj];
-        } else { q0b[u] = r0; qvb[u] = rv; rhob[u] = rho_i; }
-    }
-    if (FAST) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        if (!FAST && sl[u] == SLOT_NONE) continue;
-        const PiPair t = pi_term<SqrtMid>(q0b[u], qvb[u], rhob[u], r0, rv, rho_i, cs_i);
-        s_pi += t.pi;
-        maxrel = fmax(maxrel, t.rel);
-    }
-}
-
-__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_pi_kernel(int n, int npad, int k, int nblk,
-                                                         const int* __restrict__ nbr,
-                                                         const u16* __restrict__ slot16,
-                                                         const int* __restrict__ uniq,
-                                                         const int* __restrict__ qorder,
-                                                         const int* __restrict__ omap, int n_active,
-                                                         const RecB* __restrict__ recb,
-                                                         const double* __restrict__ rho_s,
-                                                         const RecSelf* __restrict__ selfr, RecBC* bc, double* Pi,
-                                                         double* BwOut, u64* ct_bits, BlobSel sel) {
-    extern __shared__ double2 img[];                       // 4 * BLOB_S chunks, BLOB_S doubles, slot tile
-    double* lrho = reinterpret_cast<double*>(img + 4 * BLOB_S);
-    u16* tile = reinterpret_cast<u16*>(lrho + BLOB_S);
-    const int t = threadIdx.x / LPP, half = threadIdx.x & (LPP - 1);     // half: which partial sum
-    u64 my_ct = SPHX_CT_NONE;
-    const int nsel = blob_sel_count(sel, nblk);
-    for (int bi = blockIdx.x; bi < nsel; bi += gridDim.x) {
-        const int b = blob_sel_at(sel, bi, nsel);
-        const int p = b * BLOB_P + t;
-        const int i = (p < n) ? qorder[p] : 0;
-        stage<1>(img, lrho, tile, recb, rho_s, 1, nullptr, 0, uniq + (size_t)b * BLOB_S, slot16, npad, k, b);
+struct PiPass {
+    typedef RecB Rec;
+    struct Sums { double pi; };
+    static constexpr int NSIDE = 1, PER_SLOT = 72;          // side value: rho_j
+    static constexpr bool CLIPS = false, VOTES = true, ROW_FROM_LIST = true;
+    const RecB* __restrict__ rec;
+    const double* __restrict__ rho_s;
+    const RecSelf* __restrict__ selfr;
+    RecBC* bc;
+    double *Pi, *BwOut;
+    struct Row { Q4 r0, rv; double rho_i, cs_i, ms_i, h_i; };
+    struct Nb { Q8 q; double rho; };
+    __device__ __forceinline__ BlobSides sides() const { return {rho_s, 1}; }
+    __device__ __forceinline__ Row load_row(int i) const {
         const RecSelf sf = selfr[i];
-        const double rho_i = rho_s[i];
-        const double* selfq = reinterpret_cast<const double*>(&recb[i]);
-        const Q4 self0 = gload4(selfq), selfv = gload4(selfq + 4);
-        const int o = (p < n) ? (omap ? omap[i] : i) : 0x7FFFFFFF;
-        __syncthreads();
-        if (o < n_active) {
-            Q4 r0 = self0, rv = selfv;
-            {
-                const unsigned sl0 = tile[t];
-                if (sl0 < SLOT_OVER) { r0 = lload4(img, (int)sl0, 0); rv = lload4(img, (int)sl0, 1); }
-                else if (sl0 == SLOT_OVER) {
-                    const double* rq = reinterpret_cast<const double*>(&recb[nbr[p]]);
-                    r0 = gload4(rq); rv = gload4(rq + 4);
-                }
-            }
-            const double cs_i = sf.csi, ms_i = sf.mg, h_i = sf.h;
-            double s_pi = 0.0, maxrel = 0.0;
-            const int nm = KPAD(k) / LPP;
-            unsigned sl[NB];
-            load_slots(sl, tile, 0, half, t);
-            for (int m0 = 0; m0 < nm; m0 += NB) {
-                unsigned cur[NB];
-#pragma unroll
-                for (int u = 0; u < NB; ++u) cur[u] = sl[u];
-                if (m0 + NB < nm) load_slots(sl, tile, m0 + NB, half, t);
-                const size_t col0 = (size_t)(LPP * m0 + half) * npad + p;
-                if (all_staged(cur))
-                    pi_batch<true>(s_pi, maxrel, cur, img, lrho, recb, rho_s, nbr, col0, LPP * (size_t)npad, r0, rv, rho_i, cs_i);
-                else
-                    pi_batch<false>(s_pi, maxrel, cur, img, lrho, recb, rho_s, nbr, col0, LPP * (size_t)npad, r0, rv, rho_i, cs_i);
-            }
-            s_pi = group_total(s_pi);
-            maxrel = group_max(maxrel);
-            if (!half) {
-                Pi[o] = s_pi;
-                const double bw = fmax(ms_i, 0.0) * s_pi;                       // m Pi [t==0]  nsc:651
-                bc[i].Bw = bw;
-                if (BwOut) BwOut[o] = bw;
-                if (ms_i > 0.0) {                                               // gas only     nsc:782
-                    const u64 cb = ct_vote_bits(h_i, maxrel);
-                    my_ct = cb < my_ct ? cb : my_ct;
-                }
-            }
-        }
-        __syncthreads();
+        const Q8 s = gload8(&rec[i]);
+        return Row{s.lo, s.hi, rho_s[i], sf.csi, sf.mg, sf.h};
     }
-    block_min_vote<PASS_T>(my_ct, ct_bits);
+    __device__ __forceinline__ static void load_out(Row&, int, bool) {}
+    __device__ __forceinline__ static void row_point(Row& r, const Nb& f) { r.r0 = f.q.lo; r.rv = f.q.hi; }
+    __device__ __forceinline__ static bool wanted(const Row&) { return true; }
+    __device__ __forceinline__ Nb staged(const double2* img, const double* side, int s, const int*) const {
+        return Nb{lload8(img, s), side[s]};
+    }
+    __device__ __forceinline__ Nb global(int j) const { return Nb{gload8(&rec[j]), rho_s[j]}; }
+    __device__ __forceinline__ static Nb none(const Row& r) { return Nb{Q8{r.r0, r.rv}, r.rho_i}; }
+    template <bool CLIP>
+    __device__ __forceinline__ double term(Sums& a, const Nb& f, const Row& r) const {
+        const PiPair t = pi_term<SqrtMid>(f.q.lo, f.q.hi, f.rho, r.r0, r.rv, r.rho_i, r.cs_i);
+        a.pi += t.pi;
+        return t.rel;
+    }
+    __device__ __forceinline__ u64 finish(const Sums& a, double maxrel, const Row& r, int i, int o) const {
+        Pi[o] = a.pi;
+        const double bw = fmax(r.ms_i, 0.0) * a.pi;                         // m Pi [t==0]  nsc:651
+        bc[i].Bw = bw;
+        if (BwOut) BwOut[o] = bw;
+        return (r.ms_i > 0.0) ? ct_vote_bits(r.h_i, maxrel) : SPHX_CT_NONE; // gas only     nsc:782
+    }
+};
+BLOB_KERNEL blob_pi_kernel(BLOB_COMMON, const int* __restrict__ omap, int n_active, const RecB* __restrict__ recb,
+                           const double* __restrict__ rho_s, const RecSelf* __restrict__ selfr, RecBC* bc, double* Pi,
+                           double* BwOut, u64* ct_bits, BlobSel sel) {
+    blob_pass(PiPass{recb, rho_s, selfr, bc, Pi, BwOut}, n, npad, k, nblk, nbr, slot16, uniq, qorder, 0, omap, n_active,
+              ct_bits, sel);
 }
 
 // ---- pass 3: viscous acceleration + heat      nsc:651-654 --------------------------------------
-template <bool FAST, bool CLIP>
-__device__ __forceinline__ void visc_batch(ViscAcc& a, const unsigned (&sl)[NB], const double2* img,
-                                           const double* lc1, const RecB* __restrict__ recb,
-                                           const RecBC* __restrict__ bc, const int* __restrict__ nbr, size_t col0,
-                                           size_t colstep, const Q4& r0, const Q4& rv, double hi2, double ci,
-                                           double Bi) {
-    Q4 q0b[NB], qvb[NB];
-    double c1b[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        if (FAST || sl[u] < SLOT_OVER) {
-            q0b[u] = lload4(img, (int)sl[u], 0); qvb[u] = lload4(img, (int)sl[u], 1);     // qv.d = Bw_j
-            c1b[u] = lc1[sl[u]];
-        } else if (sl[u] == SLOT_OVER) {
-            const int jj = nbr[col0 + u * colstep];
-            const double* qb = reinterpret_cast<const double*>(&recb[jj]);
-            q0b[u] = gload4(qb); qvb[u] = gload4(qb + 4);
-            const double2 tt = *reinterpret_cast<const double2*>(&bc[jj]);
-            qvb[u].d = tt.x; c1b[u] = tt.y;
-        } else { q0b[u] = r0; qvb[u] = rv; c1b[u] = 0.0; }
+struct ViscPass {
+    typedef RecB Rec;
+    typedef ViscAcc Sums;
+    static constexpr int NSIDE = 2, PER_SLOT = 72;          // image {x y | z h2 | vx vy | vz Bw}, side value: c1
+    static constexpr bool CLIPS = true, VOTES = false, ROW_FROM_LIST = true;
+    const RecB* __restrict__ rec;
+    const RecBC* __restrict__ bc;
+    const double* __restrict__ m;
+    double *va, *vh;
+    struct Row { Q4 r0, rv; double hi2, ci, Bi, mi; };
+    struct Nb { Q8 q; double c1; };                          // q.hi.d = Bw_j
+    __device__ __forceinline__ BlobSides sides() const {
+        const double* bcd = reinterpret_cast<const double*>(bc);
+        return {bcd, 2, bcd + 1, 2};
     }
-    if (FAST) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        if (!FAST && sl[u] == SLOT_NONE) continue;
-        visc_term<SqrtMid>(a, q0b[u], qvb[u], qvb[u].d, c1b[u], r0, rv, hi2, ci, Bi, CLIP);
+    __device__ __forceinline__ Row load_row(int i) const {
+        const double2 bci = *reinterpret_cast<const double2*>(&bc[i]);      // Bw, c1
+        const Q8 s = gload8(&rec[i]);
+        return Row{s.lo, s.hi, s.lo.d, -6.0 * bci.y, bci.x, 0.0};
     }
-}
-
-__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_visc_kernel(int n, int npad, int k, int nblk,
-                                                           const int* __restrict__ nbr,
-                                                           const u16* __restrict__ slot16,
-                                                           const int* __restrict__ uniq,
-                                                           const int* __restrict__ qorder, int clip,
-                                                           const int* __restrict__ omap, int n_active,
-                                                           const RecB* __restrict__ recb,
-                                                           const RecBC* __restrict__ bc,
-                                                           const double* __restrict__ m, double* va, double* vh,
-                                                           BlobSel sel) {
-    extern __shared__ double2 img[];                       // 4 * BLOB_S chunks {x y | z h2 | vx vy | vz Bw}, c1, tile
-    double* lc1 = reinterpret_cast<double*>(img + 4 * BLOB_S);
-    u16* tile = reinterpret_cast<u16*>(lc1 + BLOB_S);
-    const int t = threadIdx.x / LPP, half = threadIdx.x & (LPP - 1);     // half: which partial sum
-    const double* bcd = reinterpret_cast<const double*>(bc);
-    const int nsel = blob_sel_count(sel, nblk);
-    for (int bi = blockIdx.x; bi < nsel; bi += gridDim.x) {
-        const int b = blob_sel_at(sel, bi, nsel);
-        const int p = b * BLOB_P + t;
-        const int i = (p < n) ? qorder[p] : 0;
-        stage<2>(img, lc1, tile, recb, bcd, 2, bcd + 1, 2, uniq + (size_t)b * BLOB_S, slot16, npad, k, b);
-        const double2 bci = *reinterpret_cast<const double2*>(&bc[i]);       // Bw, c1
-        const double* selfq = reinterpret_cast<const double*>(&recb[i]);
-        const Q4 self0 = gload4(selfq), selfv = gload4(selfq + 4);
-        const int o = (p < n) ? (omap ? omap[i] : i) : 0x7FFFFFFF;
-        const double mi = (o < n_active) ? m[o] : 0.0;                      // m in output order
-        __syncthreads();
-        if (o < n_active) {
-            Q4 r0 = self0, rv = selfv;
-            {
-                const unsigned sl0 = tile[t];
-                if (sl0 < SLOT_OVER) { r0 = lload4(img, (int)sl0, 0); rv = lload4(img, (int)sl0, 1); }
-                else if (sl0 == SLOT_OVER) {
-                    const double* rq = reinterpret_cast<const double*>(&recb[nbr[p]]);
-                    r0 = gload4(rq); rv = gload4(rq + 4);
-                }
-            }
-            const double hi2 = self0.d, ci = -6.0 * bci.y, Bi = bci.x;
-            ViscAcc a{0.0, 0.0, 0.0, 0.0};
-            const int nm = KPAD(k) / LPP;
-            unsigned sl[NB];
-            load_slots(sl, tile, 0, half, t);
-            for (int m0 = 0; m0 < nm; m0 += NB) {
-                unsigned cur[NB];
-#pragma unroll
-                for (int u = 0; u < NB; ++u) cur[u] = sl[u];
-                if (m0 + NB < nm) load_slots(sl, tile, m0 + NB, half, t);
-                const size_t col0 = (size_t)(LPP * m0 + half) * npad + p;
-                const bool fast = all_staged(cur);
-                if (fast && !clip) visc_batch<true, false>(a, cur, img, lc1, recb, bc, nbr, col0, LPP * (size_t)npad, r0, rv, hi2, ci, Bi);
-                else if (fast) visc_batch<true, true>(a, cur, img, lc1, recb, bc, nbr, col0, LPP * (size_t)npad, r0, rv, hi2, ci, Bi);
-                else if (!clip) visc_batch<false, false>(a, cur, img, lc1, recb, bc, nbr, col0, LPP * (size_t)npad, r0, rv, hi2, ci, Bi);
-                else visc_batch<false, true>(a, cur, img, lc1, recb, bc, nbr, col0, LPP * (size_t)npad, r0, rv, hi2, ci, Bi);
-            }
-            const double ax = group_total(a.x), ay = group_total(a.y), az = group_total(a.z), heat = group_total(a.h);
-            if (!half) {
-                va[3 * (size_t)o + 0] = -ax; va[3 * (size_t)o + 1] = -ay; va[3 * (size_t)o + 2] = -az;
-                vh[o] = heat * mi / 2.0;                                        // nsc:654
-            }
-        }
-        __syncthreads();
+    // m in output order
+    __device__ __forceinline__ void load_out(Row& r, int o, bool on) const { r.mi = on ? m[o] : 0.0; }
+    __device__ __forceinline__ static void row_point(Row& r, const Nb& f) { r.r0 = f.q.lo; r.rv = f.q.hi; }
+    __device__ __forceinline__ static bool wanted(const Row&) { return true; }
+    __device__ __forceinline__ Nb staged(const double2* img, const double* side, int s, const int*) const {
+        return Nb{lload8(img, s), side[s]};
     }
+    __device__ __forceinline__ Nb global(int j) const {
+        Nb f{gload8(&rec[j]), 0.0};
+        const double2 tt = *reinterpret_cast<const double2*>(&bc[j]);
+        f.q.hi.d = tt.x; f.c1 = tt.y;
+        return f;
+    }
+    __device__ __forceinline__ static Nb none(const Row& r) { return Nb{Q8{r.r0, r.rv}, 0.0}; }
+    template <bool CLIP>
+    __device__ __forceinline__ double term(Sums& a, const Nb& f, const Row& r) const {
+        visc_term<SqrtMid>(a, f.q.lo, f.q.hi, f.q.hi.d, f.c1, r.r0, r.rv, r.hi2, r.ci, r.Bi, CLIP);
+        return 0.0;
+    }
+    __device__ __forceinline__ u64 finish(const Sums& a, double, const Row& r, int, int o) const {
+        va[3 * (size_t)o + 0] = -a.x; va[3 * (size_t)o + 1] = -a.y; va[3 * (size_t)o + 2] = -a.z;
+        vh[o] = a.h * r.mi / 2.0;                                           // nsc:654
+        return SPHX_CT_NONE;
+    }
+};
+BLOB_KERNEL blob_visc_kernel(BLOB_COMMON, int clip, const int* __restrict__ omap, int n_active,
+                             const RecB* __restrict__ recb, const RecBC* __restrict__ bc, const double* __restrict__ m,
+                             double* va, double* vh, BlobSel sel) {
+    blob_pass(ViscPass{recb, bc, m, va, vh}, n, npad, k, nblk, nbr, slot16, uniq, qorder, clip, omap, n_active, nullptr, sel);
 }
 
 // ---- passes 2 + 3 fused: the pairwise viscosity (visc_mode 1; sphx_sums.hip pass_visc_pw_kernel) ------------------
@@ -527,107 +388,51 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_visc_kernel(int n, int
 // CU).  M_j = m_j [t_j==0] c1_j (RecBC[j].Bw) stays out of it and is fetched by an 8-B gather through the int32 list (the
 // list entry a coalesced load, the record a dependent one).  Staging M_j as well - 80 B per slot, 87 040 B, one workgroup
 // per CU - measured slower: 0.345 against 0.306 ms at 10^6.
-template <bool FAST, bool CLIP>
-__device__ __forceinline__ void visc_pw_batch(ViscAcc& a, double& maxrel, const unsigned (&sl)[NB], const double2* img,
-                                              const double* lrho, const RecB* __restrict__ recb,
-                                              const double* __restrict__ rho_s, const RecBC* __restrict__ bc,
-                                              const int* __restrict__ nbr, size_t col0, size_t colstep, const Q4& r0,
-                                              const Q4& rv, double rho_i, double cs_i, double hi2, double ci) {
-    Q4 q0b[NB], qvb[NB];
-    double rhob[NB], mcb[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        if (FAST || sl[u] < SLOT_OVER) {
-            q0b[u] = lload4(img, (int)sl[u], 0); qvb[u] = lload4(img, (int)sl[u], 1);
-            rhob[u] = lrho[sl[u]];
-            mcb[u] = bc[nbr[col0 + u * colstep]].Bw;
-        } else if (sl[u] == SLOT_OVER) {
-            const int jj = nbr[col0 + u * colstep];
-            const double* qb = reinterpret_cast<const double*>(&recb[jj]);
-            q0b[u] = gload4(qb); qvb[u] = gload4(qb + 4);
-            rhob[u] = rho_s[jj]; mcb[u] = bc[jj].Bw;
-        } else { q0b[u] = r0; qvb[u] = rv; rhob[u] = rho_i; mcb[u] = 0.0; }
-    }
-    if (FAST) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        if (!FAST && sl[u] == SLOT_NONE) continue;
-        maxrel = fmax(maxrel, visc_pw_term<SqrtMid>(a, q0b[u], qvb[u], rhob[u], mcb[u], r0, rv, rho_i, cs_i, hi2, ci, CLIP));
-    }
-}
-
-__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_visc_pw_kernel(int n, int npad, int k, int nblk,
-                                                              const int* __restrict__ nbr,
-                                                              const u16* __restrict__ slot16,
-                                                              const int* __restrict__ uniq,
-                                                              const int* __restrict__ qorder, int clip,
-                                                              const int* __restrict__ omap, int n_active,
-                                                              const RecB* __restrict__ recb,
-                                                              const double* __restrict__ rho_s,
-                                                              const RecBC* __restrict__ bc,
-                                                              const RecSelf* __restrict__ selfr,
-                                                              const double* __restrict__ m, double* va, double* vh,
-                                                              u64* ct_bits, BlobSel sel) {
-    extern __shared__ double2 img[];                       // 4 * BLOB_S chunks, BLOB_S rho_j, slot tile
-    double* lrho = reinterpret_cast<double*>(img + 4 * BLOB_S);
-    u16* tile = reinterpret_cast<u16*>(lrho + BLOB_S);
-    const int t = threadIdx.x / LPP, half = threadIdx.x & (LPP - 1);     // half: which partial sum
-    u64 my_ct = SPHX_CT_NONE;
-    const int nsel = blob_sel_count(sel, nblk);
-    for (int bi = blockIdx.x; bi < nsel; bi += gridDim.x) {
-        const int b = blob_sel_at(sel, bi, nsel);
-        const int p = b * BLOB_P + t;
-        const int i = (p < n) ? qorder[p] : 0;
-        stage<1>(img, lrho, tile, recb, rho_s, 1, nullptr, 0, uniq + (size_t)b * BLOB_S, slot16, npad, k, b);
+struct ViscPwPass {
+    typedef RecB Rec;
+    typedef ViscAcc Sums;
+    static constexpr int NSIDE = 1, PER_SLOT = 72;          // side value: rho_j
+    static constexpr bool CLIPS = true, VOTES = true, ROW_FROM_LIST = true;
+    const RecB* __restrict__ rec;
+    const double* __restrict__ rho_s;
+    const RecBC* __restrict__ bc;
+    const RecSelf* __restrict__ selfr;
+    const double* __restrict__ m;
+    double *va, *vh;
+    struct Row { Q4 r0, rv; double rho_i, cs_i, h_i, mg, hi2, ci, mi; };
+    struct Nb { Q8 q; double rho, mc; };
+    __device__ __forceinline__ BlobSides sides() const { return {rho_s, 1}; }
+    __device__ __forceinline__ Row load_row(int i) const {
         const RecSelf sf = selfr[i];
         const double rho_i = rho_s[i], mci = bc[i].Bw;
-        const double* selfq = reinterpret_cast<const double*>(&recb[i]);
-        const Q4 self0 = gload4(selfq), selfv = gload4(selfq + 4);
-        const int o = (p < n) ? (omap ? omap[i] : i) : 0x7FFFFFFF;
-        const double mi = (o < n_active) ? m[o] : 0.0;                      // m in output order
-        __syncthreads();
-        if (o < n_active) {
-            Q4 r0 = self0, rv = selfv;
-            {
-                const unsigned sl0 = tile[t];
-                if (sl0 < SLOT_OVER) { r0 = lload4(img, (int)sl0, 0); rv = lload4(img, (int)sl0, 1); }
-                else if (sl0 == SLOT_OVER) {
-                    const double* rq = reinterpret_cast<const double*>(&recb[nbr[p]]);
-                    r0 = gload4(rq); rv = gload4(rq + 4);
-                }
-            }
-            const double cs_i = sf.csi, h_i = sf.h, hi2 = self0.d, ci = -6.0 * mci;
-            ViscAcc a{0.0, 0.0, 0.0, 0.0};
-            double maxrel = 0.0;
-            const int nm = KPAD(k) / LPP;
-            unsigned sl[NB];
-            load_slots(sl, tile, 0, half, t);
-            for (int m0 = 0; m0 < nm; m0 += NB) {
-                unsigned cur[NB];
-#pragma unroll
-                for (int u = 0; u < NB; ++u) cur[u] = sl[u];
-                if (m0 + NB < nm) load_slots(sl, tile, m0 + NB, half, t);
-                const size_t col0 = (size_t)(LPP * m0 + half) * npad + p;
-                const bool fast = all_staged(cur);
-                if (fast && !clip) visc_pw_batch<true, false>(a, maxrel, cur, img, lrho, recb, rho_s, bc, nbr, col0, LPP * (size_t)npad, r0, rv, rho_i, cs_i, hi2, ci);
-                else if (fast) visc_pw_batch<true, true>(a, maxrel, cur, img, lrho, recb, rho_s, bc, nbr, col0, LPP * (size_t)npad, r0, rv, rho_i, cs_i, hi2, ci);
-                else if (!clip) visc_pw_batch<false, false>(a, maxrel, cur, img, lrho, recb, rho_s, bc, nbr, col0, LPP * (size_t)npad, r0, rv, rho_i, cs_i, hi2, ci);
-                else visc_pw_batch<false, true>(a, maxrel, cur, img, lrho, recb, rho_s, bc, nbr, col0, LPP * (size_t)npad, r0, rv, rho_i, cs_i, hi2, ci);
-            }
-            const double ax = group_total(a.x), ay = group_total(a.y), az = group_total(a.z), heat = group_total(a.h);
-            maxrel = group_max(maxrel);
-            if (!half) {
-                va[3 * (size_t)o + 0] = -ax; va[3 * (size_t)o + 1] = -ay; va[3 * (size_t)o + 2] = -az;
-                vh[o] = heat * mi / 2.0;                                        // nsc:654
-                if (sf.mg > 0.0) {                                              // gas only     nsc:782
-                    const u64 cb = ct_vote_bits(h_i, maxrel);
-                    my_ct = cb < my_ct ? cb : my_ct;
-                }
-            }
-        }
-        __syncthreads();
+        const Q8 s = gload8(&rec[i]);
+        return Row{s.lo, s.hi, rho_i, sf.csi, sf.h, sf.mg, s.lo.d, -6.0 * mci, 0.0};
     }
-    block_min_vote<PASS_T>(my_ct, ct_bits);
+    // m in output order
+    __device__ __forceinline__ void load_out(Row& r, int o, bool on) const { r.mi = on ? m[o] : 0.0; }
+    __device__ __forceinline__ static void row_point(Row& r, const Nb& f) { r.r0 = f.q.lo; r.rv = f.q.hi; }
+    __device__ __forceinline__ static bool wanted(const Row&) { return true; }
+    __device__ __forceinline__ Nb staged(const double2* img, const double* side, int s, const int* jp) const {
+        return Nb{lload8(img, s), side[s], bc[*jp].Bw};
+    }
+    __device__ __forceinline__ Nb global(int j) const { return Nb{gload8(&rec[j]), rho_s[j], bc[j].Bw}; }
+    __device__ __forceinline__ static Nb none(const Row& r) { return Nb{Q8{r.r0, r.rv}, r.rho_i, 0.0}; }
+    template <bool CLIP>
+    __device__ __forceinline__ double term(Sums& a, const Nb& f, const Row& r) const {
+        return visc_pw_term<SqrtMid>(a, f.q.lo, f.q.hi, f.rho, f.mc, r.r0, r.rv, r.rho_i, r.cs_i, r.hi2, r.ci, CLIP);
+    }
+    __device__ __forceinline__ u64 finish(const Sums& a, double maxrel, const Row& r, int, int o) const {
+        va[3 * (size_t)o + 0] = -a.x; va[3 * (size_t)o + 1] = -a.y; va[3 * (size_t)o + 2] = -a.z;
+        vh[o] = a.h * r.mi / 2.0;                                           // nsc:654
+        return (r.mg > 0.0) ? ct_vote_bits(r.h_i, maxrel) : SPHX_CT_NONE;   // gas only     nsc:782
+    }
+};
+BLOB_KERNEL blob_visc_pw_kernel(BLOB_COMMON, int clip, const int* __restrict__ omap, int n_active,
+                                const RecB* __restrict__ recb, const double* __restrict__ rho_s,
+                                const RecBC* __restrict__ bc, const RecSelf* __restrict__ selfr,
+                                const double* __restrict__ m, double* va, double* vh, u64* ct_bits, BlobSel sel) {
+    blob_pass(ViscPwPass{recb, rho_s, bc, selfr, m, va, vh}, n, npad, k, nblk, nbr, slot16, uniq, qorder, clip, omap, n_active,
+              ct_bits, sel);
 }
 
 // ---- sweeps (2), (3) of the species pass (blob_species_kernel) and its epilogue -------------------------------------
@@ -728,8 +533,9 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_species_kernel
         double* nden, double* G, double* ha,
         int S, const double* __restrict__ fun, const int* __restrict__ row_of, const double* __restrict__ m, AgbTable agb,
         int agb_on, double* F, double* Zout, double* agb_out) {
-    extern __shared__ double2 img[];                       // 4 * BLOB_S chunks, then the slot tile
-    u16* tile = reinterpret_cast<u16*>(img + 4 * BLOB_S);
+    const DensityPass ps{rec, rho_s, rho, rhod, nden, G, ha};      // pass 1 itself: its row, batches and epilogue
+    double2* img = BlobLds<0>::img();
+    u16* tile = BlobLds<0>::tile();
     const int t = threadIdx.x / LPP, half = threadIdx.x & (LPP - 1);
     const int nm = KPAD(k) / LPP;
     for (int bi = blockIdx.x; bi < nblk; bi += gridDim.x) {
@@ -739,47 +545,29 @@ __global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_density_species_kernel
         const int i = live ? qorder[p] : 0;
         const int* uq = uniq + (size_t)b * BLOB_S;
         stage<0>(img, nullptr, tile, rec, nullptr, 0, nullptr, 0, uq, slot16, npad, k, b);
-        const double* self = reinterpret_cast<const double*>(&rec[i]);
-        const Q4 s0 = gload4(self), s1 = gload4(self + 4);     // x y z h2 | c1 ms A Nw
+        DensityPass::Row row = ps.load_row(i);
         __syncthreads();
         double w[SPEC_MAXM];
 #pragma unroll
         for (int mm = 0; mm < SPEC_MAXM; ++mm) w[mm] = 0.0;
         if (live) {
-            double xr = s0.a, yr = s0.b, zr = s0.c;
-            {
-                const unsigned sl0 = tile[t];
-                if (sl0 < SLOT_OVER) { const Q4 r = lload4(img, (int)sl0, 0); xr = r.a; yr = r.b; zr = r.c; }
-                else if (sl0 == SLOT_OVER) { const int j0 = nbr[p]; xr = rec[j0].x; yr = rec[j0].y; zr = rec[j0].z; }
-            }
-            const double hi2 = s0.d, ci = -6.0 * s1.a, Ai = s1.c;
-            DensAcc a{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            blob_row_point(ps, row, nbr, p, t);
+            DensAcc a{};
+            // (unrolled at compile time, unlike blob_pass's loop: the weights' register indices must be constants)
 #pragma unroll
             for (int m0 = 0; m0 < SPEC_MAXM; m0 += NB) {
                 if (m0 < nm) {
                     unsigned cur[NB];
                     load_slots(cur, tile, m0, half, t);
-                    const size_t col0 = (size_t)(LPP * m0 + half) * npad + p;
-                    const bool fast = all_staged(cur);
                     double wo[NB];
-                    if (fast && !clip) density_batch<true, false>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
-                    else if (fast) density_batch<true, true>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
-                    else if (!clip) density_batch<false, false>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
-                    else density_batch<false, true>(a, wo, cur, img, rec, nbr, col0, LPP * (size_t)npad, xr, yr, zr, hi2, ci, Ai);
+                    blob_batch_any(ps, clip, a, wo, cur, nbr + ((size_t)(LPP * m0 + half) * npad + p),
+                                   LPP * (size_t)npad, row);
 #pragma unroll
                     for (int u = 0; u < NB; ++u) if (m0 + u < SPEC_MAXM) w[m0 + u] = wo[u];
                 }
             }
-            const double s_rho = group_total(a.rho), s_rd = group_total(a.rd), s_n = group_total(a.n);
-            const double gx = group_total(a.gx), gy = group_total(a.gy), gz = group_total(a.gz);
-            if (!half) {
-                rho[i] = s_rho; rhod[i] = s_rd; nden[i] = s_n;
-                rho_s[i] = s_rho;
-                if (G) { G[3 * (size_t)i + 0] = -gx; G[3 * (size_t)i + 1] = -gy; G[3 * (size_t)i + 2] = -gz; }
-                ha[3 * (size_t)i + 0] = -gx / s_rho;                  // nsc:619
-                ha[3 * (size_t)i + 1] = -gy / s_rho;
-                ha[3 * (size_t)i + 2] = -gz / s_rho;
-            }
+            group_total_fields(a);
+            if (!half) ps.finish(a, 0.0, row, i, i);
         }
         // ---- the composition sweeps of the species pass, on the weights in hand
         species_sweeps(w, img, tile, uq, nbr, n, npad, nm, p, i, t, half, live, S, fun, row_of, m, agb, agb_on, F, Zout, agb_out);
@@ -1005,45 +793,32 @@ int sphx_lds_opt_in(sphx_ctx* ctx, const void* kernel, size_t bytes) {
     return SPHX_OK;
 }
 
-// One launch on the persistent grid.  Every LDS kernel of this file begins with (n, npad, k, nblk, nbr, slot16, uniq,
-// qorder); `rest` are the arguments behind them.  Dynamic LDS: per_slot bytes of image per slot (0: no image) and the
-// slot tile, + extra.
-template <class Kern, class... Rest>
-static int blob_launch(sphx_ctx* ctx, Kern kern, int per_slot, size_t extra, int64_t n, int k, Rest... rest) {
-    const int64_t npad = sphx_pad64(n);
-    const int nblk = (int)((npad + BLOB_P - 1) / BLOB_P);
-    SPHX_TRY(sphx_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), IMG_BYTES(per_slot, SPHX_MAX_K) + extra));
-    hipLaunchKernelGGL(kern, dim3(sphx_blob_grid(ctx, nblk)), dim3(PASS_T), IMG_BYTES(per_slot, k) + extra, ctx->stream, (int)n,
-                       (int)npad, k, nblk, ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(), ctx->qorder, rest...);
-    HIPCHK(hipGetLastError());
-    return SPHX_OK;
-}
 // callers' particles that are computed (device API: the owned ones; ghosts, o >= n_active, are candidates only)
 static int blob_n_active(const sphx_ctx* ctx, int64_t n) { return ctx->map_perm ? ctx->map_nactive : (int)n; }
 
 int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k, bool lean) {
-    return blob_launch(ctx, blob_density_kernel, 64, 0, n, k, ctx->clip_grad, ctx->map_perm, blob_n_active(ctx, n),
-                       ctx->rec1.as<RecA>(), ctx->rho_s.as<double>(), ctx->rho.as<double>(), ctx->rhod.as<double>(),
-                       ctx->nden.as<double>(), lean ? nullptr : ctx->G.as<double>(), ctx->ha.as<double>(),
+    return blob_launch(ctx, blob_density_kernel, DensityPass::PER_SLOT, 0, n, k, ctx->clip_grad, ctx->map_perm,
+                       blob_n_active(ctx, n), ctx->rec1.as<RecA>(), ctx->rho_s.as<double>(), ctx->rho.as<double>(),
+                       ctx->rhod.as<double>(), ctx->nden.as<double>(), lean ? nullptr : ctx->G.as<double>(), ctx->ha.as<double>(),
                        sphx_blob_sel(ctx, ctx->pass_part));
 }
 
 int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits) {
-    return blob_launch(ctx, blob_pi_kernel, 72, 0, n, k, ctx->map_perm, blob_n_active(ctx, n), ctx->recv.as<RecB>(),
+    return blob_launch(ctx, blob_pi_kernel, PiPass::PER_SLOT, 0, n, k, ctx->map_perm, blob_n_active(ctx, n), ctx->recv.as<RecB>(),
                        ctx->rho_s.as<double>(), ctx->self_s.as<RecSelf>(), ctx->bc_s.as<RecBC>(), ctx->Pi.as<double>(),
                        ctx->map_perm ? ctx->Bw.as<double>() : nullptr, ct_bits, sphx_blob_sel(ctx, ctx->pass_part));
 }
 
 int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m) {
-    return blob_launch(ctx, blob_visc_kernel, 72, 0, n, k, ctx->clip_grad, ctx->map_perm, blob_n_active(ctx, n),
+    return blob_launch(ctx, blob_visc_kernel, ViscPass::PER_SLOT, 0, n, k, ctx->clip_grad, ctx->map_perm, blob_n_active(ctx, n),
                        ctx->recv.as<RecB>(), ctx->bc_s.as<RecBC>(), m, ctx->va.as<double>(), ctx->vh.as<double>(),
                        sphx_blob_sel(ctx, ctx->pass_part));
 }
 
 int sphx_blob_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m, u64* ct_bits) {
-    return blob_launch(ctx, blob_visc_pw_kernel, 72, 0, n, k, ctx->clip_grad, ctx->map_perm, blob_n_active(ctx, n),
-                       ctx->recv.as<RecB>(), ctx->rho_s.as<double>(), ctx->bc_s.as<RecBC>(), ctx->self_s.as<RecSelf>(), m,
-                       ctx->va.as<double>(), ctx->vh.as<double>(), ct_bits, sphx_blob_sel(ctx, ctx->pass_part));
+    return blob_launch(ctx, blob_visc_pw_kernel, ViscPwPass::PER_SLOT, 0, n, k, ctx->clip_grad, ctx->map_perm,
+                       blob_n_active(ctx, n), ctx->recv.as<RecB>(), ctx->rho_s.as<double>(), ctx->bc_s.as<RecBC>(),
+                       ctx->self_s.as<RecSelf>(), m, ctx->va.as<double>(), ctx->vh.as<double>(), ct_bits, sphx_blob_sel(ctx, ctx->pass_part));
 }
 
 // (the weights' registers are sized for K <= 40, else for SPHX_MAX_K: SPEC_MAXM)

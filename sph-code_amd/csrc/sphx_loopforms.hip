@@ -535,153 +535,93 @@ __global__ __launch_bounds__(256) void loop_pass2_kernel(int n, int npad, int k,
     block_min_vote<256>(mine, ct_bits);
 }
 
-// ---- LDS form (sphx_blob.h: blob image, LPP lanes per particle, persistent workgroups) ------------------
-__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_loop1_kernel(int n, int npad, int k, int nblk, double d9,
-                                                                          const int* __restrict__ nbr,
-                                                                          const u16* __restrict__ slot16,
-                                                                          const int* __restrict__ uniq,
-                                                                          const int* __restrict__ qorder,
-                                                                          const RecP1* __restrict__ p1,
-                                                                          const double* __restrict__ side, double* rho,
-                                                                          double* rhod, double* nden, double* G,
-                                                                          RecP2* p2, BlobSel sel) {
-    extern __shared__ double2 img[];                       // 4 * BLOB_S chunks, gamma, slot tile
-    double* lgam = reinterpret_cast<double*>(img + 4 * BLOB_S);
-    u16* tile = reinterpret_cast<u16*>(lgam + BLOB_S);
-    const int t = threadIdx.x / LPP, part = threadIdx.x & (LPP - 1);
-    const int nsel = blob_sel_count(sel, nblk);
-    for (int bi = blockIdx.x; bi < nsel; bi += gridDim.x) {
-        const int b = blob_sel_at(sel, bi, nsel);
-        const int p = b * BLOB_P + t;
-        const int i = (p < n) ? qorder[p] : 0;
-        stage<1>(img, lgam, tile, p1, side, 1, nullptr, 0, uniq + (size_t)b * BLOB_S, slot16, npad, k, b);
-        const double* sp = reinterpret_cast<const double*>(&p1[i]);
-        const Q4 s0 = gload4(sp), s1 = gload4(sp + 4);
-        __syncthreads();
-        if (p < n) {
-            const bool gas_i = s1.c > 0.0;
-            L1Acc a{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            const int nm = KPAD(k) / LPP;
-            for (int m0 = 0; m0 < nm; m0 += NB) {
-                unsigned sl[NB];
-                load_slots(sl, tile, m0, part, t);
-                Q4 q0b[NB], q1b[NB];
-                double gb[NB];
-                int jb[NB];
-                if (all_staged(sl)) {                          // the usual case: straight-line LDS reads
-#pragma unroll
-                    for (int u = 0; u < NB; ++u) {
-                        q0b[u] = lload4(img, (int)sl[u], 0); q1b[u] = lload4(img, (int)sl[u], 1); gb[u] = lgam[sl[u]];
-                        jb[u] = -1;
-                    }
-                } else {
-#pragma unroll
-                    for (int u = 0; u < NB; ++u) {
-                        jb[u] = -1;
-                        if (sl[u] < SLOT_OVER) {
-                            q0b[u] = lload4(img, (int)sl[u], 0); q1b[u] = lload4(img, (int)sl[u], 1); gb[u] = lgam[sl[u]];
-                        } else if (sl[u] == SLOT_OVER) {
-                            jb[u] = nbr[(size_t)(LPP * (m0 + u) + part) * npad + p];
-                            const double* q = reinterpret_cast<const double*>(&p1[jb[u]]);
-                            q0b[u] = gload4(q); q1b[u] = gload4(q + 4); gb[u] = side[jb[u]];
-                        } else { q0b[u] = s0; q1b[u] = s1; gb[u] = 1.0; }
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < NB; ++u) {
-                    if (sl[u] == SLOT_NONE) continue;
-                    double dm = -1.0, dh = 0.0;
-                    // not gas: a dust neighbour's mass travels in the side value, its size in the record's g1 (neither is
-                    // read for a neighbour that is not gas; loop_dust_side_kernel) - nothing is gathered here
-                    if (!(q1b[u].c > 0.0) && gb[u] >= 0.0) { dm = gb[u]; dh = q1b[u].b; }
-                    loop1_term(a, q0b[u], q1b[u], gb[u], dm, dh, s0.a, s0.b, s0.c, s1.d, gas_i, d9);
-                }
-            }
-            const double s_rho = group_total(a.rho), s_rd = group_total(a.rd), s_n = group_total(a.n);
-            const double gx = group_total(a.gx), gy = group_total(a.gy), gz = group_total(a.gz);
-            if (part == 0) {
-                rho[i] = s_rho; rhod[i] = s_rd; nden[i] = s_n;
-                G[3 * (size_t)i] = gx; G[3 * (size_t)i + 1] = gy; G[3 * (size_t)i + 2] = gz;
-                p2[i].rho = s_rho;
-            }
-        }
-        __syncthreads();
+// ---- LDS form (sphx_blob.h: blob image, LPP lanes per particle, persistent workgroups; blob_pass walks) --------
+// Deltas are relative to the particle itself and every stored particle is computed (ghosts too: the callers pick).
+struct Loop1Pass {
+    typedef RecP1 Rec;
+    typedef L1Acc Sums;
+    static constexpr int NSIDE = 1, PER_SLOT = 72;          // side value: loop_dust_side_kernel's
+    static constexpr bool CLIPS = false, VOTES = false, ROW_FROM_LIST = false;
+    double d9;
+    const RecP1* __restrict__ rec;
+    const double* __restrict__ gside;
+    double *rho, *rhod, *nden, *G;
+    RecP2* p2;
+    struct Row { Q4 s0, s1; bool gas_i; };
+    struct Nb { Q8 q; double g; };
+    __device__ __forceinline__ BlobSides sides() const { return {gside, 1}; }
+    __device__ __forceinline__ Row load_row(int i) const {
+        const Q8 s = gload8(&rec[i]);
+        return Row{s.lo, s.hi, s.hi.c > 0.0};
     }
+    __device__ __forceinline__ static void load_out(Row&, int, bool) {}
+    __device__ __forceinline__ static bool wanted(const Row&) { return true; }
+    __device__ __forceinline__ Nb staged(const double2* img, const double* side, int s, const int*) const {
+        return Nb{lload8(img, s), side[s]};
+    }
+    __device__ __forceinline__ Nb global(int j) const { return Nb{gload8(&rec[j]), gside[j]}; }
+    __device__ __forceinline__ static Nb none(const Row& r) { return Nb{Q8{r.s0, r.s1}, 1.0}; }
+    template <bool CLIP>
+    __device__ __forceinline__ double term(Sums& a, const Nb& f, const Row& r) const {
+        double dm = -1.0, dh = 0.0;
+        // not gas: a dust neighbour's mass travels in the side value, its size in the record's g1 (neither is
+        // read for a neighbour that is not gas; loop_dust_side_kernel) - nothing is gathered here
+        if (!(f.q.hi.c > 0.0) && f.g >= 0.0) { dm = f.g; dh = f.q.hi.b; }
+        loop1_term(a, f.q.lo, f.q.hi, f.g, dm, dh, r.s0.a, r.s0.b, r.s0.c, r.s1.d, r.gas_i, d9);
+        return 0.0;
+    }
+    __device__ __forceinline__ u64 finish(const Sums& a, double, const Row&, int i, int) const {
+        rho[i] = a.rho; rhod[i] = a.rd; nden[i] = a.n;
+        G[3 * (size_t)i] = a.gx; G[3 * (size_t)i + 1] = a.gy; G[3 * (size_t)i + 2] = a.gz;
+        p2[i].rho = a.rho;
+        return SPHX_CT_NONE;
+    }
+};
+BLOB_KERNEL blob_loop1_kernel(BLOB_COMMON, double d9, const RecP1* __restrict__ p1, const double* __restrict__ side,
+                              double* rho, double* rhod, double* nden, double* G, RecP2* p2, BlobSel sel) {
+    blob_pass(Loop1Pass{d9, p1, side, rho, rhod, nden, G, p2}, n, npad, k, nblk, nbr, slot16, uniq, qorder, 0, nullptr, n,
+              nullptr, sel);
 }
 
-__global__ __launch_bounds__(PASS_T, PASS_MINW) void blob_loop2_kernel(int n, int npad, int k, int nblk,
-                                                                          const int* __restrict__ nbr,
-                                                                          const u16* __restrict__ slot16,
-                                                                          const int* __restrict__ uniq,
-                                                                          const int* __restrict__ qorder,
-                                                                          const RecP1* __restrict__ p1,
-                                                                          const RecP2* __restrict__ p2,
-                                                                          const double* __restrict__ m,
-                                                                          const double* __restrict__ h, double* va,
-                                                                          double* vh, u64* ct_bits, BlobSel sel) {
-    extern __shared__ double2 img[];                       // 4 * BLOB_S chunks, m, slot tile
-    double* lm = reinterpret_cast<double*>(img + 4 * BLOB_S);
-    u16* tile = reinterpret_cast<u16*>(lm + BLOB_S);
-    const int t = threadIdx.x / LPP, part = threadIdx.x & (LPP - 1);
-    u64 mine = SPHX_CT_NONE;
-    const int nsel = blob_sel_count(sel, nblk);
-    for (int bi = blockIdx.x; bi < nsel; bi += gridDim.x) {
-        const int b = blob_sel_at(sel, bi, nsel);
-        const int p = b * BLOB_P + t;
-        const int i = (p < n) ? qorder[p] : 0;
-        stage<1>(img, lm, tile, p2, m, 1, nullptr, 0, uniq + (size_t)b * BLOB_S, slot16, npad, k, b);
-        const double* sp = reinterpret_cast<const double*>(&p2[i]);
-        const Q4 s0 = gload4(sp), sv = gload4(sp + 4);
-        const double hq_i = p1[i].hq, g1_i = p1[i].g1, m_i = m[i], h_i = h[i];
-        __syncthreads();
-        if (p < n) {
-            L2Acc a{0.0, 0.0, 0.0, 0.0};
-            double mx = 0.0;
-            if (s0.d >= 0.0) {
-                const int nm = KPAD(k) / LPP;
-                for (int m0 = 0; m0 < nm; m0 += NB) {
-                    unsigned sl[NB];
-                    load_slots(sl, tile, m0, part, t);
-                    Q4 q0b[NB], qvb[NB];
-                    double mb[NB];
-                    if (all_staged(sl)) {
-#pragma unroll
-                        for (int u = 0; u < NB; ++u) {
-                            q0b[u] = lload4(img, (int)sl[u], 0); qvb[u] = lload4(img, (int)sl[u], 1); mb[u] = lm[sl[u]];
-                        }
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < NB; ++u) {
-                            if (sl[u] < SLOT_OVER) {
-                                q0b[u] = lload4(img, (int)sl[u], 0); qvb[u] = lload4(img, (int)sl[u], 1); mb[u] = lm[sl[u]];
-                            } else if (sl[u] == SLOT_OVER) {
-                                const int j = nbr[(size_t)(LPP * (m0 + u) + part) * npad + p];
-                                const double* q = reinterpret_cast<const double*>(&p2[j]);
-                                q0b[u] = gload4(q); qvb[u] = gload4(q + 4); mb[u] = m[j];
-                            } else { q0b[u] = s0; qvb[u] = sv; mb[u] = m_i; }
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < NB; ++u) {
-                        if (sl[u] == SLOT_NONE) continue;
-                        mx = fmax(mx, loop2_term(a, q0b[u], qvb[u], mb[u], s0, sv, sv.d, m_i, hq_i, g1_i));
-                    }
-                }
-            }
-            const double ax = group_total(a.ax), ay = group_total(a.ay), az = group_total(a.az), heat = group_total(a.heat);
-            mx = group_max(mx);
-            if (part == 0) {
-                va[3 * (size_t)i] = ax; va[3 * (size_t)i + 1] = ay; va[3 * (size_t)i + 2] = az;
-                vh[i] = heat;
-                if (s0.d >= 0.0) {
-                    const u64 cb = ct_vote_bits(h_i, mx);
-                    mine = cb < mine ? cb : mine;
-                }
-            }
-        }
-        __syncthreads();
+struct Loop2Pass {
+    typedef RecP2 Rec;
+    typedef L2Acc Sums;
+    static constexpr int NSIDE = 1, PER_SLOT = 72;          // side value: m_j
+    static constexpr bool CLIPS = false, VOTES = true, ROW_FROM_LIST = false;
+    const RecP1* __restrict__ p1;
+    const RecP2* __restrict__ rec;
+    const double* __restrict__ m;
+    const double* __restrict__ h;
+    double *va, *vh;
+    struct Row { Q4 s0, sv; double hq_i, g1_i, m_i, h_i; };
+    struct Nb { Q8 q; double m; };
+    __device__ __forceinline__ BlobSides sides() const { return {m, 1}; }
+    __device__ __forceinline__ Row load_row(int i) const {
+        const Q8 s = gload8(&rec[i]);
+        return Row{s.lo, s.hi, p1[i].hq, p1[i].g1, m[i], h[i]};
     }
-    block_min_vote<PASS_T>(mine, ct_bits);
+    __device__ __forceinline__ static void load_out(Row&, int, bool) {}
+    // a gas particle (others: zeros, no vote)
+    __device__ __forceinline__ static bool wanted(const Row& r) { return r.s0.d >= 0.0; }
+    __device__ __forceinline__ Nb staged(const double2* img, const double* side, int s, const int*) const {
+        return Nb{lload8(img, s), side[s]};
+    }
+    __device__ __forceinline__ Nb global(int j) const { return Nb{gload8(&rec[j]), m[j]}; }
+    __device__ __forceinline__ static Nb none(const Row& r) { return Nb{Q8{r.s0, r.sv}, r.m_i}; }
+    template <bool CLIP>
+    __device__ __forceinline__ double term(Sums& a, const Nb& f, const Row& r) const {
+        return loop2_term(a, f.q.lo, f.q.hi, f.m, r.s0, r.sv, r.sv.d, r.m_i, r.hq_i, r.g1_i);
+    }
+    __device__ __forceinline__ u64 finish(const Sums& a, double mx, const Row& r, int i, int) const {
+        va[3 * (size_t)i] = a.ax; va[3 * (size_t)i + 1] = a.ay; va[3 * (size_t)i + 2] = a.az;
+        vh[i] = a.heat;
+        return wanted(r) ? ct_vote_bits(r.h_i, mx) : SPHX_CT_NONE;
+    }
+};
+BLOB_KERNEL blob_loop2_kernel(BLOB_COMMON, const RecP1* __restrict__ p1, const RecP2* __restrict__ p2,
+                              const double* __restrict__ m, const double* __restrict__ h, double* va, double* vh,
+                              u64* ct_bits, BlobSel sel) {
+    blob_pass(Loop2Pass{p1, p2, m, h, va, vh}, n, npad, k, nblk, nbr, slot16, uniq, qorder, 0, nullptr, n, ct_bits, sel);
 }
 
 // The three launches of the loop-form sums on a set of SORTED state arrays `st` (the fused loop: the resident
@@ -725,17 +665,12 @@ static int loop_pass1_launch(sphx_ctx* ctx, int64_t n, int k, double d, StateArr
     const int npad = (int)sphx_pad64(n);
     RecP1* p1 = ctx->lrec_a.as<RecP1>(); RecP2* p2 = ctx->lrec_v.as<RecP2>();
     if (ctx->qorder && ctx->blob_lists) {
-        SPHX_TRY(sphx_lds_opt_in(ctx, reinterpret_cast<const void*>(blob_loop1_kernel), IMG_BYTES(72, SPHX_MAX_K)));
-        const int nblk = (npad + BLOB_P - 1) / BLOB_P;
-        const int g = sphx_blob_grid(ctx, nblk);
         SPHX_TRY(sphx_ensure(ctx, ctx->loop_side, (size_t)n * sizeof(double)));
         hipLaunchKernelGGL(loop_dust_side_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n,
                            st.ptype.as<double>(), st.m.as<double>(), h, st.gam.as<double>(), p1, ctx->loop_side.as<double>());
-        hipLaunchKernelGGL(blob_loop1_kernel, dim3(g), dim3(PASS_T), IMG_BYTES(72, k), ctx->stream, (int)n, npad, k, nblk,
-                           d9, ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(), ctx->qorder, p1,
-                           ctx->loop_side.as<double>(),
-                           ctx->rho.as<double>(), ctx->rhod.as<double>(), ctx->nden.as<double>(), ctx->G.as<double>(), p2,
-                           sphx_blob_sel(ctx, 0));
+        SPHX_TRY(blob_launch(ctx, blob_loop1_kernel, Loop1Pass::PER_SLOT, 0, n, k, d9, p1, ctx->loop_side.as<double>(),
+                             ctx->rho.as<double>(), ctx->rhod.as<double>(), ctx->nden.as<double>(), ctx->G.as<double>(), p2,
+                             sphx_blob_sel(ctx, 0)));
     } else {
         hipLaunchKernelGGL(loop_pass1_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n, npad, k, d9,
                            ctx->nbr.as<int>(), p1, st.gam.as<double>(), st.ptype.as<double>(), st.m.as<double>(),
@@ -750,12 +685,8 @@ static int loop_pass2_launch(sphx_ctx* ctx, int64_t n, int k, StateArrays& st, c
     const int npad = (int)sphx_pad64(n);
     RecP1* p1 = ctx->lrec_a.as<RecP1>(); RecP2* p2 = ctx->lrec_v.as<RecP2>();
     if (ctx->qorder && ctx->blob_lists) {
-        SPHX_TRY(sphx_lds_opt_in(ctx, reinterpret_cast<const void*>(blob_loop2_kernel), IMG_BYTES(72, SPHX_MAX_K)));
-        const int nblk = (npad + BLOB_P - 1) / BLOB_P;
-        const int g = sphx_blob_grid(ctx, nblk);
-        hipLaunchKernelGGL(blob_loop2_kernel, dim3(g), dim3(PASS_T), IMG_BYTES(72, k), ctx->stream, (int)n, npad, k, nblk,
-                           ctx->nbr.as<int>(), ctx->slot16.as<u16>(), ctx->uniq.as<int>(), ctx->qorder, p1, p2,
-                           st.m.as<double>(), h, ctx->va.as<double>(), ctx->vh.as<double>(), ct, sphx_blob_sel(ctx, part));
+        SPHX_TRY(blob_launch(ctx, blob_loop2_kernel, Loop2Pass::PER_SLOT, 0, n, k, p1, p2, st.m.as<double>(), h,
+                             ctx->va.as<double>(), ctx->vh.as<double>(), ct, sphx_blob_sel(ctx, part)));
     } else {
         hipLaunchKernelGGL(loop_pass2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n, npad, k,
                            ctx->nbr.as<int>(), p1, p2, st.m.as<double>(), h, ctx->qorder, ctx->va.as<double>(),

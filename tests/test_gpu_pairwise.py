@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN_CASES, hydro_args, load_golden
+from test_gpu_parity import VARIANT_CASES, VARIANT_IDS
 from test_pairwise_cpu import signed_close, viscosity_sums
 
 pytestmark = pytest.mark.gpu
@@ -82,21 +83,19 @@ def test_pairwise_step_trajectory_vs_oracle(workload, clip_grad):
     np.testing.assert_allclose(got["T"], ref["T"], rtol=1e-9)
 
 
-@pytest.mark.parametrize("workload,n,K", [("polytrope", 20000, 40), ("dusty_sphere", 6000, 40),
-                                          ("uniform_sphere", 3000, 7), ("uniform_sphere", 5000, 33),
-                                          ("polytrope", 9000, 64), ("uniform_cube", 40, 64)])
-def test_pairwise_step_variants_are_bit_identical(workload, n, K, monkeypatch):
-    """LDS pass (default), LDS with 300 image slots (global-memory fallback), gathers in blob order, gathers in
-    storage order: one answer, bit for bit; no failure counter set."""
+@pytest.mark.parametrize("workload,n,K,clip_grad,slots", VARIANT_CASES, ids=VARIANT_IDS)
+def test_pairwise_step_variants_are_bit_identical(workload, n, K, clip_grad, slots, monkeypatch):
+    """LDS pass (default), LDS with 300 image slots (global-memory fallback; test_gpu_parity.py's VARIANT_CASES say where
+    fewer), gathers in blob order, gathers in storage order: one answer, bit for bit; no failure counter set."""
     import sph_code_amd.ics as ics
     from sph_code_amd.sim import Simulation
     s0 = ics.WORKLOADS[workload](n)
     res = {}
-    for name, env in (("lds", {}), ("lds_overflow", {"SPHX_BLOB_SLOTS": "300"}), ("blob_gather", {"SPHX_LDS": "0"}),
+    for name, env in (("lds", {}), ("lds_overflow", {"SPHX_BLOB_SLOTS": str(slots)}), ("blob_gather", {"SPHX_LDS": "0"}),
                       ("storage_order", {"SPHX_BLOB": "0"})):
         for k_, v in env.items():
             monkeypatch.setenv(k_, v)
-        sim = Simulation(s0, n_neigh=K, visc_mode="pairwise")
+        sim = Simulation(s0, n_neigh=K, clip_grad=clip_grad, visc_mode="pairwise")
         sim.step(4)
         res[name] = sim.download()
         assert sim.failures() == dict.fromkeys(Simulation.FAILURE_COUNTERS, 0), (name, sim.failures())

@@ -420,24 +420,35 @@ def test_incremental_search_is_exact():
     assert st["refresh_steps"] + st["rebuild_steps"] == nsteps
 
 
-@pytest.mark.parametrize("workload,n,K", [("polytrope", 20000, 40), ("dusty_sphere", 6000, 40),
-                                          ("uniform_sphere", 3000, 7), ("uniform_sphere", 5000, 33),
-                                          ("polytrope", 9000, 64), ("uniform_cube", 40, 64)])
-def test_step_loop_variants_are_bit_identical(workload, n, K, monkeypatch):
+# (workload, n, K, clip_grad, image slots of the lds_overflow variant) of the two variant tests (this one and
+# test_gpu_pairwise.py's).  Clipped gradients are the other half of the LDS batches' instantiations (FAST x CLIP).
+# Their K = 7 case squeezes the image to 100 slots, not 300: a list's first entry is the particle itself, so each of the
+# 23 full blobs of 128 particles names at least 128 distinct particles - an argument from the lists' make-up, not a
+# measured count: more than 100 whatever the blob order - and part of its references must take the global-memory
+# fallback (at K = 7 a blob may well name fewer than 300).  The n = 40 case has one blob of 40: nothing overflows there, every list has missing entries instead.
+VARIANT_CASES = [("polytrope", 20000, 40, False, 300), ("dusty_sphere", 6000, 40, False, 300),
+                 ("uniform_sphere", 3000, 7, False, 300), ("uniform_sphere", 5000, 33, False, 300),
+                 ("polytrope", 9000, 64, False, 300), ("uniform_cube", 40, 64, False, 300),
+                 ("uniform_sphere", 3000, 7, True, 100), ("uniform_cube", 40, 64, True, 300)]
+VARIANT_IDS = ["%s-%d-%d%s" % (c[0], c[1], c[2], "-clip" if c[3] else "") for c in VARIANT_CASES]
+
+
+@pytest.mark.parametrize("workload,n,K,clip_grad,slots", VARIANT_CASES, ids=VARIANT_IDS)
+def test_step_loop_variants_are_bit_identical(workload, n, K, clip_grad, slots, monkeypatch):
     """The step loop's passes exist in three forms that must agree bit for bit: gathers in storage
     order (SPHX_BLOB=0), gathers in blob order (SPHX_LDS=0), neighbour records staged in LDS
-    (default) - the last also with the image squeezed to 300 slots, so that part of the references
+    (default) - the last also with the image squeezed to 300 slots (VARIANT_CASES), so that part of the references
     take the global-memory fallback.  K = 7 / 33: odd list lengths (the two lanes of a particle split the
     list by parity); K = 64: the widest slot tile; n = 40 < K: lists with missing entries."""
     import sph_code_amd.ics as ics
     from sph_code_amd.sim import Simulation
     s0 = ics.WORKLOADS[workload](n)
     res = {}
-    for name, env in (("lds", {}), ("lds_overflow", {"SPHX_BLOB_SLOTS": "300"}), ("blob_gather", {"SPHX_LDS": "0"}),
+    for name, env in (("lds", {}), ("lds_overflow", {"SPHX_BLOB_SLOTS": str(slots)}), ("blob_gather", {"SPHX_LDS": "0"}),
                       ("storage_order", {"SPHX_BLOB": "0"})):
         for k_, v in env.items():
             monkeypatch.setenv(k_, v)
-        sim = Simulation(s0, n_neigh=K)           # a fresh context reads the switches
+        sim = Simulation(s0, n_neigh=K, clip_grad=clip_grad)           # a fresh context reads the switches
         sim.step(4)
         res[name] = sim.download()
         for k_ in env:
