@@ -436,6 +436,8 @@ class LibBackend:
 
     def set_agb(self, nspecies, table, mu_specie, solar_mass):
         splines, mapto, divisor = table
+        if int(nspecies) > len(mu_specie):                 # the C call reads one molecular weight per species
+            raise ValueError("agb: %d species, mu_specie has %d entries" % (int(nspecies), len(mu_specie)))
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
         ntx = i32([sp.get_knots()[0].size for sp in splines]); nty = i32([sp.get_knots()[1].size for sp in splines])

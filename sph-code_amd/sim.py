@@ -30,6 +30,11 @@ class Simulation:
         vmode = visc_mode_code(visc_mode)
         if vmode and forms == "loop":
             raise ValueError("visc_mode='pairwise' is for forms='hydro_update': the loop forms' viscosity is pairwise already")
+        if agb is not None and with_species and state.get("f_un") is not None:
+            from . import compat
+            if np.shape(state["f_un"])[-1] > len(compat.mu_specie):      # the C call reads one molecular weight per species
+                raise ValueError("agb: the state carries %d species, mu_specie has %d entries"
+                                 % (np.shape(state["f_un"])[-1], len(compat.mu_specie)))
         self.ctx = ctx if ctx is not None else _lib.Context(device)
         self.ctx.set_incremental(incremental)
         self.k = int(n_neigh)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oracle_bounds as ob
+from species_cases import live_composition
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +85,7 @@ def _loop_forms_full_size(nsc, workload, with_drag):
     d = ics.loop_d(s, K)
     m, pt, mu, gam = s["mass"], s["particle_type"], s["mu_array"], s["gamma_array"]
     f_un = s["f_un"] if with_drag else None
+    live = live_composition(s, 15, seed=N_FULL) if with_drag else None
     sim = Simulation(s, n_neigh=K, forms="loop", d=d, with_drag=with_drag)
     for label, p, v, T, E in _two_states(nsc, s, sim):
         label = "%s %s" % (workload, label)
@@ -97,8 +99,9 @@ def _loop_forms_full_size(nsc, workload, with_drag):
         if with_drag:
             assert np.abs(drag[0]).max() > 0 and np.abs(drag[1]).max() > 0          # on the gas, and back on the dust
             assert np.abs(ref["net_impulse"][0]).max() > 0 and np.abs(ref["net_impulse"][1]).max() > 0
-            # the species pass's array form: F (15 species) and the dust density of hydro_update
-            args = (idx, p, m, h, s["f_un"], pt, T, mu, gam, v)
+            # the species pass's array form: F (15 species, on a composition with every species > 0 and a row of its own
+            # per particle: tests/species_cases.py) and the dust density of hydro_update
+            args = (idx, p, m, h, live, pt, T, mu, gam, v)
             out = nsc.hydro_update(*args)
             href, scales = ob.hydro_reference(args)
             seen = ob.compare_hydro(out, href, scales, label + " hydro_update", which=(3, 4, 5, 6))
