@@ -74,7 +74,7 @@ typedef struct sphx_stats {
     int64_t rebuild_steps; /* steps with cell sort + full search                 */
     double  cell_size;     /* edge of the last grid's cells                     */
     double  ms_gravity;    /* self-gravity (0 unless sphx_state_set_gravity)    */
-    int64_t fallback_queries; /* last step: queries the grouped search left to the general kernel */
+    int64_t fallback_queries; /* last step (or sphx_dev_search): queries the grouped search left to the general kernel */
     double  ms_species;    /* species pass of the step (+ metallicity, AGB yields); ms_density excludes it */
     int64_t short_rows;    /* searches that gave up after the last radius of the retry ladder with fewer than K
                               neighbours although more particles exist (pathological states only; 0 otherwise) */
@@ -89,6 +89,11 @@ typedef struct sphx_stats {
     int64_t bad_state;     /* updated position or velocity NaN or inf (the next step's clamp, drv:233-238, catches them)    */
     int64_t bad_h;         /* kNN radius 0 (coincident points), NaN or inf                                                  */
     int64_t search_steps;  /* steps accumulated in ms_search                                                                */
+    /* The last hinted search's tie list (near ties of two consecutive ranks, which the grouped search leaves to the tie
+     * blocks of the list-mode launch): read when sphx_get_stats is called, behind the stream.                         */
+    int64_t tie_entries;   /* entries that search reserved; may exceed tie_capacity (the queries that did not fit went to
+                              the general kernel).  0 if it kept no tie list                                           */
+    int64_t tie_capacity;  /* entries its tie list had room for (npad / 16 + 1024)                                    */
 } sphx_stats;
 
 /* ---- context ----------------------------------------------------------------------- */

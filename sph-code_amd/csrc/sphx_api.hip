@@ -1019,6 +1019,21 @@ extern "C" int sphx_get_stats(sphx_ctx* ctx, sphx_stats* out) {
         HIPCHK(hipSetDevice(ctx->device));
         SPHX_TRY(sphx_badc_read(ctx));
     }
+    // the last hinted search's tie list: entries reserved (read behind the stream: the word stands until the next grid
+    // build) and room
+    ctx->stats.tie_entries = 0;
+    ctx->stats.tie_capacity = ctx->tie_cap_last;
+    if (ctx->tie_count_dev) {
+        int cnt = 0;
+        u64 nfail = 0;
+        HIPCHK(hipSetDevice(ctx->device));
+        HIPCHK(hipMemcpyAsync(&cnt, ctx->tie_count_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(&nfail, ctx->scal.as<u64>() + SC_NFAILQ, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        ctx->stats.tie_entries = (int64_t)(u32)cnt;
+        // (sphx_step reads this slot itself; the device-pointer API has no other place that does)
+        if (ctx->map_perm) ctx->stats.fallback_queries = (int64_t)(u32)nfail;
+    }
     *out = ctx->stats;
     // the grid build's single-launch scan bounds its waits; a wait that ran out raised a flag (and left wrong numbers)
     for (int w = 0; w < 2; ++w) {

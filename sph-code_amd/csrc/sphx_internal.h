@@ -266,6 +266,9 @@ struct sphx_ctx {
     int mcount_zeroed_M = 0;
     const void* fcount_zeroed = nullptr;   // the fail-list allocation whose counter the grid build has zeroed for this step
     int64_t fcount_zeroed_n = 0;
+    const void* tie_list_cleared = nullptr;   // the tie-list allocation that was filled with sentinels when it was made
+    const int* tie_count_dev = nullptr;    // the last hinted search's tie count (beside the fail count; nullptr: it kept no tie list)
+    int tie_cap_last = 0;                  // ... and its tie_cap
     const void* ds_cnt_zeroed = nullptr;
     const void* olev_fill_zeroed = nullptr;
     unsigned lbs_epoch[2] = {0u, 0u};

@@ -183,6 +183,7 @@ __global__ __launch_bounds__(KNN_BLOCK, OUTL ? KNN_OUTL_WAVES : LIST ? KNN_LIST_
         for (int e = ((int)blockIdx.x - nblk) * KNN_BLOCK + (int)threadIdx.x; e < nt; e += ((int)gridDim.x - nblk) * KNN_BLOCK) {
             const int4 t = a.tie_list[e];
             const int p = t.x, r = t.y, ia = t.z, ib = t.w;
+            if (p < 0) continue;              // sentinel: the slot's query failed over after reserving it (kg_tie_slots)
             const int qs_ = a.qorder ? a.qorder[p] : p;
             const double qx_ = a.x[qs_], qy_ = a.y[qs_], qz_ = a.z[qs_];
             const double da = dist2_nofma(a.x[ia] - qx_, a.y[ia] - qy_, a.z[ia] - qz_);
@@ -842,6 +843,7 @@ int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const KnnIn& in, const KnnOut& out
         if (ctx->distrust) {
             // every query by the general kernel, radii seeded from the cell counts (the hint is one rung of the ladder)
             a.distrust = 1;
+            ctx->tie_count_dev = nullptr; ctx->tie_cap_last = 0;       // (no grouped search, no tie list)
             if (a.ol.L > 0) {
                 if (lean) hipLaunchKernelGGL((knn_kernel<1, 0, 1>), dim3(blocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
                 else hipLaunchKernelGGL((knn_kernel<2, 0, 1>), dim3(blocks), dim3(KNN_BLOCK), tile_bytes, ctx->stream, a);
@@ -867,6 +869,11 @@ int sphx_knn(sphx_ctx* ctx, int64_t n, int k, const KnnIn& in, const KnnOut& out
             ga.tie_count = fcount + 1; ga.tie_cap = a.npad / 16 + 1024;
             SPHX_TRY(sphx_ensure(ctx, ctx->tie_list, (size_t)ga.tie_cap * sizeof(int4)));
             ga.tie_list = ctx->tie_list.as<int4>();
+            if (ctx->tie_list_cleared != ctx->tie_list.p) {       // a new allocation: all sentinels (every int -1)
+                HIPCHK(hipMemsetAsync(ctx->tie_list.p, 0xFF, ctx->tie_list.cap, ctx->stream));
+                ctx->tie_list_cleared = ctx->tie_list.p;
+            }
+            ctx->tie_count_dev = ga.tie_count; ctx->tie_cap_last = ga.tie_cap;      // (sphx_get_stats reads the count)
             SPHX_TRY(sphx_knn_group(ctx, ga));
             a.qlist = flist; a.qcount = fcount;
             int lblocks = (int)((ctx->list_len_last / 32 + 255) / 256) * 256;

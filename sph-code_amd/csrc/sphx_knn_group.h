@@ -1,5 +1,31 @@
 // sphx_knn_group.h - arguments of the lane-per-query grouped search (sphx_knn_group.hip)
 #pragma once
+
+// ---- room in the tie list (plain C++: the kernel and a host program that replays reservations both call it) --------
+// Each of a query's four lanes reserves its entries with one atomic add on the list's count: slots base .. base + ne - 1.
+// The count keeps every reservation, whether it fitted or not, and the tie blocks walk min(count, cap) slots - so EVERY
+// reserved slot below cap must be written by the search that reserved it, or the tie blocks apply what an earlier search
+// (or nobody) left there.  A lane whose reservation crosses cap fails its query over (all four lanes: the vote in the
+// kernel); `certified` is the query's state after that vote.
+//   slots base .. base + nwrite - 1: the lane's real entries if `real`, else the sentinel {-1, ..} the tie blocks skip
+//   slots from base + nwrite on:     nothing (they lie at or beyond cap)
+#if defined(__HIPCC__)
+#define KG_HD __host__ __device__
+#else
+#define KG_HD
+#endif
+struct KgTieSlots { int nwrite; bool real; };
+KG_HD inline bool kg_tie_overflows(int base, int ne, int cap) { return ne > 0 && (base < 0 || base > cap - ne); }
+KG_HD inline KgTieSlots kg_tie_slots(int base, int ne, int cap, bool certified) {
+    KgTieSlots s;
+    const int room = (base < 0 || base >= cap) ? 0 : cap - base;      // (base < 0: the count wrapped - nothing is written)
+    s.nwrite = ne < room ? ne : room;
+    if (s.nwrite < 0) s.nwrite = 0;
+    s.real = certified;
+    return s;
+}
+
+#ifndef SPHX_KG_TIE_SLOTS_ONLY           // (the host program wants the rule above and nothing of the device library)
 #include "sphx_internal.h"
 
 #ifndef KG_TCAP
@@ -35,3 +61,4 @@ struct KnnGroupArgs {
     u64* counters;
 };
 int sphx_knn_group(sphx_ctx* ctx, const KnnGroupArgs& a);
+#endif  // SPHX_KG_TIE_SLOTS_ONLY
