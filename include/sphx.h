@@ -94,6 +94,11 @@ typedef struct sphx_stats {
     int64_t tie_entries;   /* entries that search reserved; may exceed tie_capacity (the queries that did not fit went to
                               the general kernel).  0 if it kept no tie list                                           */
     int64_t tie_capacity;  /* entries its tie list had room for (npad / 16 + 1024)                                    */
+    /* Sums the LDS passes did not have to finish because they were NaN already (counted since sphx_reset_stats or the
+     * last state upload; read when sphx_get_stats is called, behind the stream).                                      */
+    int64_t visc_blobs_settled; /* pass 3: blobs of 128 rows whose own m Pi is NaN in every row: neither staged nor walked */
+    int64_t pi_waves_settled;   /* pass 2: waves (16 rows of one blob) that went on with the crossing-time term alone
+                                   after every row's sum had become NaN                                                */
 } sphx_stats;
 
 /* ---- context ----------------------------------------------------------------------- */

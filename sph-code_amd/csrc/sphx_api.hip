@@ -1034,6 +1034,15 @@ extern "C" int sphx_get_stats(sphx_ctx* ctx, sphx_stats* out) {
         // (sphx_step reads this slot itself; the device-pointer API has no other place that does)
         if (ctx->map_perm) ctx->stats.fallback_queries = (int64_t)(u32)nfail;
     }
+    // the sums the LDS passes found NaN before they were finished (sphx_blob.h: blob_pass)
+    if (ctx->scal.p) {
+        u64 cnt[2] = {0, 0};
+        HIPCHK(hipSetDevice(ctx->device));
+        HIPCHK(hipMemcpyAsync(cnt, ctx->scal.as<u64>() + SC_SETTLED, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        ctx->stats.visc_blobs_settled = (int64_t)cnt[0];
+        ctx->stats.pi_waves_settled = (int64_t)cnt[1];
+    }
     *out = ctx->stats;
     // the grid build's single-launch scan bounds its waits; a wait that ran out raised a flag (and left wrong numbers)
     for (int w = 0; w < 2; ++w) {
@@ -1057,6 +1066,7 @@ extern "C" int sphx_reset_stats(sphx_ctx* ctx) {
     memset(&ctx->stats, 0, sizeof(ctx->stats));
     HIPCHK(hipMemsetAsync(ctx->scal.as<u64>() + SC_CAND, 0, 2 * sizeof(u64), ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->scal.as<u64>() + SC_SHORT, 0, sizeof(u64), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->scal.as<u64>() + SC_SETTLED, 0, 2 * sizeof(u64), ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->badc.p, 0, (size_t)BADC_BUCKETS * BADC_STRIDE * sizeof(u64), ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return SPHX_OK;

@@ -5,6 +5,7 @@
 #pragma once
 #include "sphx_internal.h"
 #include "sphx_pair.h"          // Q4, gload4; the pair terms the LDS kernels share with the gather kernels
+#include "sphx_settled.h"       // when a row's sum is NaN without (further) summing
 
 #ifndef BLOB_P
 #define BLOB_P 128                  // particles per workgroup
@@ -232,6 +233,19 @@ static int blob_launch(sphx_ctx* ctx, Kern kern, int per_slot, size_t extra, int
 //                                        candidate of the crossing-time maximum (VOTES) or the species weight
 //   CLIPS                                whether the term distinguishes clipped gradients (4-way dispatch, else 2-way)
 //   finish(sums, max, row, i, o), VOTES  what the first lane of a particle writes; returns its crossing-time vote
+// and, optional (a description without them walks as before, instruction for instruction; sphx_settled.h):
+//   SETTLES, own(i), settle(o)           a row whose own value own(i) is NaN - and that writes, and has a first list
+//                                        position - sums to NaN whatever its neighbours hold: settle(o) writes that.  A
+//                                        blob of such rows is neither staged nor walked, a wave of them is not walked.
+//   SATURATES, saturated(sums), Vel, short_staged(img, s), short_global(j), short_none(row), term_short(vel, row)
+//                                        sums that stay NaN once they are: when every row of a wave has one, the wave's
+//                                        remaining batches fetch and compute only what term()'s return value needs
+template <class P, class = void> struct BlobSettles { static constexpr bool value = false; };
+template <class P> struct BlobSettles<P, decltype((void)P::SETTLES)> { static constexpr bool value = P::SETTLES; };
+template <class P, class = void> struct BlobSaturates { static constexpr bool value = false; };
+template <class P> struct BlobSaturates<P, decltype((void)P::SATURATES)> { static constexpr bool value = P::SATURATES; };
+// the counters of the two shortcuts behind a launch's pointer (nullptr: not counted)
+enum { BLOB_CNT_BLOBS_SETTLED = 0, BLOB_CNT_WAVES_SATURATED = 1 };
 struct BlobSides { const double* g0 = nullptr; int s0 = 0; const double* g1 = nullptr; int s1 = 0; };   // stage<>'s g0, g1
 
 // dynamic LDS of a pass: 4 * BLOB_S chunks of image, BLOB_S side values (NSIDE > 0), the slot tile.  (Accessors, not
@@ -285,6 +299,67 @@ __device__ __forceinline__ void blob_batch_any(const P& ps, int clip, typename P
         else blob_batch<false, false>(ps, a, out, sl, jp, colstep, row);
     }
 }
+// A batch of a saturated wave (P::SATURATES): the operands and the arithmetic of term()'s return value alone.
+template <bool FAST, class P>
+__device__ __forceinline__ void blob_batch_short(const P& ps, double (&out)[NB], const unsigned (&sl)[NB],
+                                                 const int* __restrict__ jp, size_t colstep, const typename P::Row& row) {
+    typedef BlobLds<P::NSIDE> L;
+    typename P::Vel f[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+        if (FAST || sl[u] < SLOT_OVER) f[u] = P::short_staged(L::img(), (int)sl[u]);
+        else if (sl[u] == SLOT_OVER) f[u] = ps.short_global(jp[u * colstep]);
+        else f[u] = P::short_none(row);
+    }
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+        out[u] = 0.0;
+        if (!FAST && sl[u] == SLOT_NONE) continue;
+        out[u] = P::term_short(f[u], row);
+    }
+}
+// what the vote on "settled" needs of a row (P::SETTLES), fetched a blob ahead of the vote: its particle's own value,
+// its output index and its first list position
+struct RowAhead { int i, o; unsigned first; double own; };
+template <class P>
+__device__ __forceinline__ RowAhead blob_row_ahead(const P& ps, int i, int p, int n, const u16* __restrict__ slot16,
+                                                   const int* __restrict__ omap) {
+    RowAhead r;
+    r.i = i;                                               // (p >= n: particle 0, a valid address; it writes nothing)
+    r.o = (p < n) ? (omap ? omap[i] : i) : 0x7FFFFFFF;
+    r.first = (p < n) ? slot16[p] : SLOT_NONE;
+    r.own = ps.own(i);
+    return r;
+}
+// Whether `mine` holds in every thread of the workgroup, decided AT a barrier the caller needs anyway (every thread
+// calls, in uniform control flow): each wave leaves its verdict in LDS ahead of the barrier and reads all of them behind
+// it.  Two sets of words by the parity of `round`, which the caller counts up: a wave that is through may vote again
+// (other set) while a slower one still reads; the set after that lies behind the next barrier.  (__syncthreads_and
+// is three barriers and an LDS atomic: measured slower on a pass whose blobs take 9 us each)
+template <int T>
+__device__ __forceinline__ bool block_all_at_barrier(bool mine, unsigned round) {
+    __shared__ int verdict[2][T / 64];
+    static_assert(T / 64 == 8, "eight waves: read as two 16-B pieces");
+    int* v = verdict[round & 1];
+    const int wave_all = __ballot(!mine) == 0ull;
+    if ((threadIdx.x & 63) == 0) v[threadIdx.x >> 6] = wave_all;
+    __syncthreads();
+    const int4 lo = *reinterpret_cast<const int4*>(v), hi = *reinterpret_cast<const int4*>(v + 4);
+    const int all = (lo.x & lo.y) & (lo.z & lo.w) & (hi.x & hi.y) & (hi.z & hi.w);
+    return __builtin_amdgcn_readfirstlane(all) != 0;
+}
+// sum of a count over the workgroup's waves (every thread calls; `v` is uniform in a wave), added to *dst by one thread
+template <int T>
+__device__ __forceinline__ void block_add_count(unsigned v, u64* dst) {
+    __shared__ unsigned sm[T / 64];
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned r = 0;
+        for (int w = 0; w < T / 64; ++w) r += sm[w];
+        if (r) atomicAdd(dst, (u64)r);
+    }
+}
 // the row point out of the first list position (column p of the list, particle t of the blob): image, global memory,
 // or - no first neighbour - what load_row left.  (The pass's whole fetch is called and row_point keeps what it wants:
 // the loads of the rest - a side value, ViscPwPass's bc[*jp] - are plain loads of valid addresses that the compiler
@@ -301,59 +376,138 @@ __device__ __forceinline__ void blob_row_point(const P& ps, typename P::Row& row
 // The pass.  A change to the walk - workgroups per CU, prefetch depth, how blobs are handed out - is made here.
 // clip: ignored unless P::CLIPS.  omap, n_active: outputs go to the caller's index o (device API: ghosts, o >= n_active,
 // are candidates only); omap == nullptr: o = the stored particle.  ct_bits: where P::VOTES passes vote.
+// counts: the shortcuts taken (BLOB_CNT_*; nullptr: not counted) - one atomic per workgroup, at its end.
 template <class P>
 __device__ __forceinline__ void blob_pass(const P& ps, int n, int npad, int k, int nblk, const int* __restrict__ nbr,
                                           const u16* __restrict__ slot16, const int* __restrict__ uniq,
                                           const int* __restrict__ qorder, int clip, const int* __restrict__ omap,
-                                          int n_active, u64* ct_bits, const BlobSel& sel) {
+                                          int n_active, u64* ct_bits, const BlobSel& sel, u64* counts = nullptr) {
     static_assert(P::PER_SLOT == 64 + (P::NSIDE ? 8 : 0), "image bytes per slot: the record and one side value");
+    constexpr bool SETTLES = BlobSettles<P>::value, SATURATES = BlobSaturates<P>::value;
+    static_assert(!SATURATES || LPP == 4, "sphx_wave_saturated: a row's lanes are one nibble of the wave's mask");
     typedef BlobLds<P::NSIDE> L;
     const BlobSides sd = ps.sides();
     const int t = threadIdx.x / LPP, half = threadIdx.x & (LPP - 1);     // half: which partial sum
     u64 my_ct = SPHX_CT_NONE;
+    unsigned blobs_settled = 0, waves_saturated = 0;         // shortcuts taken (the first: uniform in the workgroup)
     // persistent workgroups (two per CU): blob after blob, no dispatch gap between them
     const int nsel = blob_sel_count(sel, nblk);
-    for (int bi = blockIdx.x; bi < nsel; bi += gridDim.x) {
+    // SETTLES: the vote's operands hang on the chain qorder[p] -> own(i).  They are fetched a blob ahead, and the
+    // particle two blobs ahead, and a blob's vote rides on the barrier that ends the blob before it
+    // (block_all_at_barrier): a blob that runs meets no wait and no barrier it did not have.  Where blob after blob
+    // is settled, the workgroup goes at one round trip and one barrier per blob.
+    const int stride = gridDim.x;
+    auto particle_of = [&](int bq) -> int {
+        const int pq = blob_sel_at(sel, bq, nsel) * BLOB_P + t;
+        return (pq < n) ? qorder[pq] : 0;
+    };
+    auto nothing_left = [&](const RowAhead& r) -> bool {     // a row that writes nothing counts as settled for the vote
+        return !(r.o < n_active) || sphx_row_settled(r.own, r.first != SLOT_NONE, true);
+    };
+    RowAhead cur{0, 0x7FFFFFFF, SLOT_NONE, 0.0};
+    int i_next = 0;
+    bool blob_settled = false;                               // the vote on the blob about to begin
+    unsigned round = 0;
+    if constexpr (SETTLES) {
+        if ((int)blockIdx.x < nsel)
+            cur = blob_row_ahead(ps, particle_of(blockIdx.x), blob_sel_at(sel, blockIdx.x, nsel) * BLOB_P + t, n, slot16, omap);
+        if ((int)blockIdx.x + stride < nsel) i_next = particle_of(blockIdx.x + stride);
+        blob_settled = block_all_at_barrier<PASS_T>(nothing_left(cur), round++);
+    }
+    for (int bi = blockIdx.x; bi < nsel; bi += stride) {
         const int b = blob_sel_at(sel, bi, nsel);
         const int p = b * BLOB_P + t;
-        const int i = (p < n) ? qorder[p] : 0;
+        int i, o;
+        bool settled = false;
+        // the next blob's row operands and the particle of the one after it
+        auto fetch_ahead = [&]() {
+            if constexpr (SETTLES) {
+                if (bi + stride < nsel) {                   // (the last blob votes on itself once more: nobody asks)
+                    cur = blob_row_ahead(ps, i_next, blob_sel_at(sel, bi + stride, nsel) * BLOB_P + t, n, slot16, omap);
+                    if (bi + 2 * stride < nsel) i_next = particle_of(bi + 2 * stride);
+                }
+            }
+        };
+        if constexpr (SETTLES) {
+            i = cur.i; o = cur.o;
+            settled = sphx_row_settled(cur.own, cur.first != SLOT_NONE, o < n_active);
+            if (blob_settled) {                            // no image, no walk: the sums are NaN (sphx_settled.h)
+                fetch_ahead();
+                if (settled && !half) ps.settle(o);
+                ++blobs_settled;
+                blob_settled = block_all_at_barrier<PASS_T>(nothing_left(cur), round++);
+                continue;
+            }
+        } else {
+            i = (p < n) ? qorder[p] : 0;
+        }
         stage<P::NSIDE>(L::img(), L::side(), L::tile(), ps.rec, sd.g0, sd.s0, sd.g1, sd.s1, uniq + (size_t)b * BLOB_S,
                         slot16, npad, k, b);
         typename P::Row row = ps.load_row(i);                // (issued ahead of the wait for omap[i], not behind it)
-        const int o = (p < n) ? (omap ? omap[i] : i) : 0x7FFFFFFF;
+        if constexpr (!SETTLES) o = (p < n) ? (omap ? omap[i] : i) : 0x7FFFFFFF;
         ps.load_out(row, o, o < n_active);
+        // (behind the staging's loads, not in front of them: loads return in order, and a gather issued first would
+        //  hold back the slot table that the records' addresses wait for)
+        if constexpr (SETTLES) fetch_ahead();
         __syncthreads();
         if (o < n_active) {
-            if constexpr (P::ROW_FROM_LIST) blob_row_point(ps, row, nbr, p, t);
-            typename P::Sums a{};
-            double mx = 0.0;
-            if (P::wanted(row)) {
-                const int nm = KPAD(k) / LPP;
-                unsigned sl[NB];
-                load_slots(sl, L::tile(), 0, half, t);
-                for (int m0 = 0; m0 < nm; m0 += NB) {
-                    unsigned cur[NB];
+            if (SETTLES && __ballot(!settled) == 0ull) {    // a wave of settled rows in a blob that runs
+                if constexpr (SETTLES) { if (!half) ps.settle(o); }
+            } else {
+                if constexpr (P::ROW_FROM_LIST) blob_row_point(ps, row, nbr, p, t);
+                typename P::Sums a{};
+                double mx = 0.0;
+                if (P::wanted(row)) {
+                    const int nm = KPAD(k) / LPP;
+                    unsigned sl[NB];
+                    load_slots(sl, L::tile(), 0, half, t);
+                    bool short_form = false;         // SATURATES: every row of this wave has a NaN sum already
+                    bool short_used = false;
+                    for (int m0 = 0; m0 < nm; m0 += NB) {
+                        unsigned cur_sl[NB];
 #pragma unroll
-                    for (int u = 0; u < NB; ++u) cur[u] = sl[u];
-                    // next batch's slots, behind this one's reads
-                    if (m0 + NB < nm) load_slots(sl, L::tile(), m0 + NB, half, t);
-                    double out[NB];
-                    blob_batch_any(ps, clip, a, out, cur, nbr + ((size_t)(LPP * m0 + half) * npad + p),
-                                   LPP * (size_t)npad, row);
-                    if (P::VOTES) {
+                        for (int u = 0; u < NB; ++u) cur_sl[u] = sl[u];
+                        // next batch's slots, behind this one's reads
+                        if (m0 + NB < nm) load_slots(sl, L::tile(), m0 + NB, half, t);
+                        double out[NB];
+                        const int* jp = nbr + ((size_t)(LPP * m0 + half) * npad + p);
+                        if constexpr (SATURATES) {
+                            if (__builtin_expect(short_form, false)) {     // (laid out behind the full batch)
+                                short_used = true;
+                                if (all_staged(cur_sl)) blob_batch_short<true>(ps, out, cur_sl, jp, LPP * (size_t)npad, row);
+                                else blob_batch_short<false>(ps, out, cur_sl, jp, LPP * (size_t)npad, row);
+                            } else {
+                                blob_batch_any(ps, clip, a, out, cur_sl, jp, LPP * (size_t)npad, row);
+                                // (only the lanes of rows that sum are here: __ballot(true) is the wave's live rows)
+                                short_form = sphx_wave_saturated(__ballot(P::saturated(a)), __ballot(true));
+                            }
+                        } else {
+                            blob_batch_any(ps, clip, a, out, cur_sl, jp, LPP * (size_t)npad, row);
+                        }
+                        if (P::VOTES) {
 #pragma unroll
-                        for (int u = 0; u < NB; ++u) mx = fmax(mx, out[u]);
+                            for (int u = 0; u < NB; ++u) mx = fmax(mx, out[u]);
+                        }
                     }
+                    if (SATURATES && short_used) ++waves_saturated;
+                }
+                group_total_fields(a);
+                if (P::VOTES) mx = group_max(mx);
+                if (!half) {
+                    const u64 cb = ps.finish(a, mx, row, i, o);
+                    my_ct = cb < my_ct ? cb : my_ct;
                 }
             }
-            group_total_fields(a);
-            if (P::VOTES) mx = group_max(mx);
-            if (!half) {
-                const u64 cb = ps.finish(a, mx, row, i, o);
-                my_ct = cb < my_ct ? cb : my_ct;
-            }
         }
-        __syncthreads();                                   // the image is rewritten by the next blob
+        // the image is rewritten by the next blob
+        if constexpr (SETTLES) blob_settled = block_all_at_barrier<PASS_T>(nothing_left(cur), round++);
+        else __syncthreads();
     }
     if (P::VOTES) block_min_vote<PASS_T>(my_ct, ct_bits);
+    if constexpr (SETTLES) {
+        if (counts && threadIdx.x == 0 && blobs_settled) atomicAdd(counts + BLOB_CNT_BLOBS_SETTLED, (u64)blobs_settled);
+    }
+    if constexpr (SATURATES) {
+        if (counts) block_add_count<PASS_T>(waves_saturated, counts + BLOB_CNT_WAVES_SATURATED);      // (uniform: an argument)
+    }
 }

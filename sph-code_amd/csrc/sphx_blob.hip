@@ -31,6 +31,9 @@
 #include <float.h>
 #include <stdlib.h>
 #include <stdio.h>
+#ifndef BLOB_PI_SATURATES
+#define BLOB_PI_SATURATES 1          // pass 2 stops summing Pi in a wave whose rows' sums are all NaN (0: sums on)
+#endif
 
 // ---- once per step: distinct neighbours of each workgroup ------------------------------------
 // Phase 1: every reference is inserted into a sparse open-addressing table of particle indices
@@ -289,6 +292,7 @@ struct PiPass {
     struct Sums { double pi; };
     static constexpr int NSIDE = 1, PER_SLOT = 72;          // side value: rho_j
     static constexpr bool CLIPS = false, VOTES = true, ROW_FROM_LIST = true;
+    static constexpr bool SATURATES = BLOB_PI_SATURATES != 0;
     const RecB* __restrict__ rec;
     const double* __restrict__ rho_s;
     const RecSelf* __restrict__ selfr;
@@ -316,6 +320,13 @@ struct PiPass {
         a.pi += t.pi;
         return t.rel;
     }
+    // a NaN partial sum stays NaN: from then on only the neighbour's velocity chunks {vx vy | vz cs} are read, for the vote
+    typedef Q4 Vel;
+    __device__ __forceinline__ static bool saturated(const Sums& a) { return sphx_is_nan(a.pi); }
+    __device__ __forceinline__ static Vel short_staged(const double2* img, int s) { return lload4(img, s, 1); }
+    __device__ __forceinline__ Vel short_global(int j) const { return gload4(reinterpret_cast<const double*>(&rec[j]) + 4); }
+    __device__ __forceinline__ static Vel short_none(const Row& r) { return r.rv; }
+    __device__ __forceinline__ static double term_short(const Vel& qv, const Row& r) { return pi_rel(qv, r.rv); }
     __device__ __forceinline__ u64 finish(const Sums& a, double maxrel, const Row& r, int i, int o) const {
         Pi[o] = a.pi;
         const double bw = fmax(r.ms_i, 0.0) * a.pi;                         // m Pi [t==0]  nsc:651
@@ -326,9 +337,9 @@ struct PiPass {
 };
 BLOB_KERNEL blob_pi_kernel(BLOB_COMMON, const int* __restrict__ omap, int n_active, const RecB* __restrict__ recb,
                            const double* __restrict__ rho_s, const RecSelf* __restrict__ selfr, RecBC* bc, double* Pi,
-                           double* BwOut, u64* ct_bits, BlobSel sel) {
+                           double* BwOut, u64* ct_bits, BlobSel sel, u64* counts) {
     blob_pass(PiPass{recb, rho_s, selfr, bc, Pi, BwOut}, n, npad, k, nblk, nbr, slot16, uniq, qorder, 0, omap, n_active,
-              ct_bits, sel);
+              ct_bits, sel, counts);
 }
 
 // ---- pass 3: viscous acceleration + heat      nsc:651-654 --------------------------------------
@@ -337,6 +348,7 @@ struct ViscPass {
     typedef ViscAcc Sums;
     static constexpr int NSIDE = 2, PER_SLOT = 72;          // image {x y | z h2 | vx vy | vz Bw}, side value: c1
     static constexpr bool CLIPS = true, VOTES = false, ROW_FROM_LIST = true;
+    static constexpr bool SETTLES = true;
     const RecB* __restrict__ rec;
     const RecBC* __restrict__ bc;
     const double* __restrict__ m;
@@ -376,11 +388,19 @@ struct ViscPass {
         vh[o] = a.h * r.mi / 2.0;                                           // nsc:654
         return SPHX_CT_NONE;
     }
+    // every term holds Bw_i c_a: with a NaN Bw_i (Pi_i NaN: PiPass::finish, dust rows too) the four sums are NaN
+    __device__ __forceinline__ double own(int i) const { return bc[i].Bw; }
+    __device__ __forceinline__ void settle(int o) const {
+        const double q = __builtin_nan("");
+        va[3 * (size_t)o + 0] = q; va[3 * (size_t)o + 1] = q; va[3 * (size_t)o + 2] = q;
+        vh[o] = q;
+    }
 };
 BLOB_KERNEL blob_visc_kernel(BLOB_COMMON, int clip, const int* __restrict__ omap, int n_active,
                              const RecB* __restrict__ recb, const RecBC* __restrict__ bc, const double* __restrict__ m,
-                             double* va, double* vh, BlobSel sel) {
-    blob_pass(ViscPass{recb, bc, m, va, vh}, n, npad, k, nblk, nbr, slot16, uniq, qorder, clip, omap, n_active, nullptr, sel);
+                             double* va, double* vh, BlobSel sel, u64* counts) {
+    blob_pass(ViscPass{recb, bc, m, va, vh}, n, npad, k, nblk, nbr, slot16, uniq, qorder, clip, omap, n_active, nullptr, sel,
+              counts);
 }
 
 // ---- passes 2 + 3 fused: the pairwise viscosity (visc_mode 1; sphx_sums.hip pass_visc_pw_kernel) ------------------
@@ -806,13 +826,14 @@ int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k, bool lean) {
 int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits) {
     return blob_launch(ctx, blob_pi_kernel, PiPass::PER_SLOT, 0, n, k, ctx->map_perm, blob_n_active(ctx, n), ctx->recv.as<RecB>(),
                        ctx->rho_s.as<double>(), ctx->self_s.as<RecSelf>(), ctx->bc_s.as<RecBC>(), ctx->Pi.as<double>(),
-                       ctx->map_perm ? ctx->Bw.as<double>() : nullptr, ct_bits, sphx_blob_sel(ctx, ctx->pass_part));
+                       ctx->map_perm ? ctx->Bw.as<double>() : nullptr, ct_bits, sphx_blob_sel(ctx, ctx->pass_part),
+                       ctx->scal.as<u64>() + SC_SETTLED);
 }
 
 int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m) {
     return blob_launch(ctx, blob_visc_kernel, ViscPass::PER_SLOT, 0, n, k, ctx->clip_grad, ctx->map_perm, blob_n_active(ctx, n),
                        ctx->recv.as<RecB>(), ctx->bc_s.as<RecBC>(), m, ctx->va.as<double>(), ctx->vh.as<double>(),
-                       sphx_blob_sel(ctx, ctx->pass_part));
+                       sphx_blob_sel(ctx, ctx->pass_part), ctx->scal.as<u64>() + SC_SETTLED);
 }
 
 int sphx_blob_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m, u64* ct_bits) {

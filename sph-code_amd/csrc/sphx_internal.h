@@ -457,7 +457,8 @@ enum {
     SC_CROWDED = 13,  // u64, only grows: cells of 17 .. 512 members met by blob_count (sorted by a launch of their own when many)
     SC_DENSEP = 14,   // u64, only grows: particles in cells of >= DENSE_CELL members (a tile's 27 such cells overflow it)
     SC_KGDBG = 16,    // u64[8]: grouped search, queries handed on by reason (diagnostics)
-    SC_NSLOTS = 24
+    SC_SETTLED = 24,  // u64[2]: blobs pass 3 found settled, waves of pass 2 that saturated (BLOB_CNT_*; since sphx_reset_stats)
+    SC_NSLOTS = 26
 };
 
 // Failure counters (the reference's only guard is the nan_to_num of drv:233-238, 460-463, 490-491), u64 and

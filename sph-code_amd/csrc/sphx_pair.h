@@ -129,6 +129,13 @@ __device__ __forceinline__ PiPair pi_term(const Q4& q0, const Q4& qv, double rho
     return t;
 }
 
+// t.rel alone, in pi_term's very expression: what a row whose sum is NaN already still wants of a neighbour (its
+// crossing-time vote; sphx_settled.h).  qv, rv as above.
+__device__ __forceinline__ double pi_rel(const Q4& qv, const Q4& rv) {
+    const double dvx = qv.a - rv.a, dvy = qv.b - rv.b, dvz = qv.c - rv.c;
+    return dvx * dvx + dvy * dvy + dvz * dvz;                         // nsc:780
+}
+
 // ---- pass 3: viscous acceleration + heat      nsc:651-653 -----------------------------------------------
 struct ViscAcc { double x, y, z, h; };
 // q0 = {x y z h2}, qv = {vx vy vz .}, Bj = m_j Pi_j [t_j==0], c1_j of the neighbour; hi2, ci = -6 c1_i, Bi the particle's own
