@@ -250,6 +250,23 @@ int sphx_gravity_tree(sphx_ctx* ctx, int64_t n, const double* mass, const double
                       const double* sizes, double softening, double G, int ws, int k_cells,
                       double* accel);
 
+/* The same sum over a cloud held in nparts parts (part_of[i] in 0 .. nparts-1; a part may be empty): the out-of-core /
+ * multi-domain form, and the computation a decomposed run does across ranks, on one context.  Each part builds the grid
+ * and pyramid over its OWN particles and sums its own field as sphx_gravity_tree does (nparts = 1 gives that call's bits).
+ * To every other part q it exports its mass as a flat list decided against Q_q, the bounding box of q's particles: a
+ * cell c travels as one multipole record {M, centre; second moments} iff it is the first cell on the way down from the
+ * top whose box stands at least ws of its longest edges clear of Q_q (face cells reach out to the part's true bounding
+ * box: the grid clamps outliers into them); the particles of level-1 cells never so accepted travel as {x, y, z, m}.
+ * Every massive particle is in exactly one record, and every multipole has the clearance of the single-domain
+ * interaction list.  Each part then ADDS the field of the lists it received (fp64, in list order: sources in part
+ * order, cells top-down in index order, then particles in cell order - the same bits on every run).  Cell centres
+ * travel relative to the centre of the global bounding box.  ws = 0..4; ws = 0 exports everything as particles and sums
+ * the own field directly: the exact sum of sphx_gravity_direct.  counts (nparts, nparts, 2), nullable: cells and
+ * particles part a sent to part b.  The export holds one flag per (peer, cell): nparts x cells must stay below 2^31.  */
+int sphx_gravity_tree_parts(sphx_ctx* ctx, int64_t n, const double* mass, const double* points,
+                            const double* sizes, double softening, double G, int ws, int k_cells, int nparts,
+                            const int32_t* part_of, double* accel, int64_t* counts);
+
 /* AGB dust and gas return per star: calculate_interpolation, sph/config_helper.py:180-211, on the
  * splines of interpolate_amounts (config_helper.py:138-178; RectBivariateSpline kx = ky = 1).
  * Spline o has ntx[o] / nty[o] knots and (ntx[o]-2)*(nty[o]-2) coefficients; tx, ty, coeffs are the
@@ -650,6 +667,33 @@ int sphx_dev_drag(sphx_ctx* ctx, const double* mass, const double* ptype, const 
                   const double* mean_cross, double* drag_on, double* drag_reaction);
 int sphx_dev_set_drag_terms(sphx_ctx* ctx, const double* drag_on, const double* drag_reaction, const double* rho,
                             const double* rho_dust);
+/* Self-gravity of the decomposed step (the scheme of sphx_gravity_tree_parts between ranks; device pointers, the driver
+ * moves the records).  All after sphx_dev_search of the same particles and before the update:
+ *   _build   gathers pos (n_total,3) and mass (n_total,) in the search's cell order into buffers of its own (rows >=
+ *            n_owned - the ghosts - weigh 0: they sit in the grid but belong to their owners' pyramids) and builds the
+ *            pyramid about ref[3] (host), the point every rank passes alike, inside the global bounding box.
+ *   _local   accel (n_owned,3) = the field of this rank's own mass: the tree walk at ws = 1..4, the direct sum at ws = 0;
+ *            softening from device memory (eps_dev) or, with eps_dev NULL, by value.
+ *   _export  what every peer is to get, all peers in one call.  boxes (world,6) device: the true bounding boxes {min xyz,
+ *            max xyz} of every rank's owned particles, this rank's own in row `rank`; a rank without particles has max <
+ *            min and gets nothing.  cells: records of 12 doubles {M, centre - ref; Sxx Syy Szz Sxy; Sxz Syz 0 0}, parts:
+ *            {x, y, z, m}; peers in rank order, concatenated.  counts (world,2) int32 device: the records each peer is to
+ *            get - the WANTED numbers: nothing is written beyond cap_cells / cap_parts records, and a caller that reads a
+ *            total above its capacity enlarges the buffer and calls again.  ws = 0: everything as particles.
+ *   _remote  ADDS the field of the given lists to accel (n_owned,3), pos (n_owned,3): fp64, cells then particles, each
+ *            in list order - the same bits whenever the lists are the same.
+ * Order 1 / 2: sphx_set_gravity_order (one record layout serves both).  SPHX_E_STATE without a build for the current
+ * search, and for ws > 0 under incremental search.  sphx_dev_set_gravity_accel hands the completed field ((n_owned,3), or
+ * NULL for none) to the NEXT sphx_dev_integrate / _auto / _loop call: drv:448-449,477.                                 */
+int sphx_dev_gravity_build(sphx_ctx* ctx, int64_t n_total, int64_t n_owned, const double* pos, const double* mass,
+                           const double ref[3]);
+int sphx_dev_gravity_local(sphx_ctx* ctx, int ws, double G, const double* eps_dev, double eps, double* accel);
+int sphx_dev_gravity_export(sphx_ctx* ctx, int world, int rank, const double* boxes, int ws, double* cells,
+                            int64_t cap_cells, double* parts, int64_t cap_parts, int32_t* counts);
+int sphx_dev_gravity_remote(sphx_ctx* ctx, int64_t n_owned, const double* pos, const double* cells, int64_t ncells,
+                            const double* parts, int64_t nparts, double G, const double* eps_dev, double eps,
+                            double* accel);
+int sphx_dev_set_gravity_accel(sphx_ctx* ctx, const double* grav);
 /* Species pass (nsc:624-627) of the decomposed step: after sphx_dev_prep; f_un (n_total,nspecies), mass (n_total,) ghosts
  * included -> F (nspecies,n_total); with a table set (sphx_dev_set_agb, arguments as sphx_state_set_agb) also Z (n_total,)
  * and agb_dust (n_total,nspecies) as sphx_state_download_species defines them.  Owned entries written.                  */

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("SPHX_LIB") or os.path.join(HERE, "libsphx.so")     # 
 
 c_double_p = C.POINTER(C.c_double)
 c_int64_p = C.POINTER(C.c_int64)
+c_int32_p = C.POINTER(C.c_int32)
 
 
 class SphxConstants(C.Structure):
@@ -80,6 +81,8 @@ SIGNATURES = {
     "sphx_set_gravity_order": (C.c_int, [_P, C.c_int]),
     "sphx_gravity_direct": (C.c_int, [_P, C.c_int64, _D, _D, _D, C.c_double, C.c_double, _D]),
     "sphx_gravity_tree": (C.c_int, [_P, C.c_int64, _D, _D, _D, C.c_double, C.c_double, C.c_int, C.c_int, _D]),
+    "sphx_gravity_tree_parts": (C.c_int, [_P, C.c_int64, _D, _D, _D, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                                          c_int32_p, _D, _I]),
     "sphx_step": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double]),
     "sphx_state_download": (C.c_int, [_P] + [_D] * 10),
     "sphx_state_download_pressure": (C.c_int, [_P, _D]),
@@ -120,6 +123,11 @@ SIGNATURES = {
     "sphx_dev_integrate": (C.c_int, [_P, C.c_int64] + [_P] * 12 + [C.c_double]),
     "sphx_dev_drag": (C.c_int, [_P] + [_P] * 6),
     "sphx_dev_set_drag_terms": (C.c_int, [_P] + [_P] * 4),
+    "sphx_dev_gravity_build": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _D]),
+    "sphx_dev_gravity_local": (C.c_int, [_P, C.c_int, C.c_double, _P, C.c_double, _P]),
+    "sphx_dev_gravity_export": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int64, _P, C.c_int64, _P]),
+    "sphx_dev_gravity_remote": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, C.c_double, _P, C.c_double, _P]),
+    "sphx_dev_set_gravity_accel": (C.c_int, [_P, _P]),
     "sphx_dev_set_agb": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, _D, _D,
                                    C.POINTER(C.c_int32), C.c_double, _D, C.c_double]),
     "sphx_dev_species": (C.c_int, [_P, C.c_int] + [_P] * 5),

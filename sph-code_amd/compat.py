@@ -306,6 +306,35 @@ def grav_force_tree(mass, points, sizes, G=6.67430e-11, ws=1, order=2):
     return out
 
 
+def grav_force_tree_parts(mass, points, sizes, part_of, G=6.67430e-11, ws=1, order=2, return_counts=False):
+    """grav_force_tree over a cloud held in parts (domains of an out-of-core run, ranks of a decomposed one): every part
+    builds the pyramid over its own particles and sums its own field; to each other part it sends its mass as a flat
+    list - the coarsest cells that stand ws cell edges clear of that part's bounding box as multipole records, the rest
+    as particles - and every part adds the lists it receives (include/sphx.h: sphx_gravity_tree_parts).  part_of (n,)
+    holds labels 0 .. max; a label nobody carries is an empty part.  ws = 0 sends everything as particles: the exact sum
+    of grav_force_direct.  return_counts: also the (parts, parts, 2) array of cells and particles part a sent to part b."""
+    c = context()
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    n = pts.shape[0]
+    m = np.ascontiguousarray(mass, dtype=np.float64)
+    h = np.ascontiguousarray(sizes, dtype=np.float64)
+    lab = np.ascontiguousarray(part_of, dtype=np.int32)
+    if lab.shape != (n,):
+        raise ValueError("part_of must have one label per particle")
+    nparts = int(lab.max()) + 1 if n else 1
+    out = np.empty((n, 3))
+    counts = np.zeros((nparts, nparts, 2), dtype=np.int64)
+    dp = lambda a: a.ctypes.data_as(_lib.c_double_p)
+    c.check(c.lib.sphx_set_gravity_order(c.h, int(order)))
+    try:
+        c.check(c.lib.sphx_gravity_tree_parts(c.h, n, dp(m), dp(pts), dp(h), 0.0, float(G), int(ws), 40, nparts,
+                                              lab.ctypes.data_as(_lib.c_int32_p), dp(out),
+                                              counts.ctypes.data_as(_lib.c_int64_p)))
+    finally:
+        c.lib.sphx_set_gravity_order(c.h, 2)
+    return (out, counts) if return_counts else out
+
+
 # ==============================================================================================
 # The driver's inline integrator statements (the reference has no function for them)
 # ==============================================================================================

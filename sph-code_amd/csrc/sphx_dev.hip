@@ -74,6 +74,7 @@ extern "C" int sphx_dev_search(sphx_ctx* ctx, int64_t n_total, int64_t n_owned, 
     const size_t nb = (size_t)n * sizeof(double);
     ctx->map_perm = nullptr;
     ctx->qorder = nullptr;
+    ctx->gx_built = false;
     DevBuf* bufs[] = {&ctx->in_b, &ctx->in_c, &ctx->in_d, &ctx->in_e, &ctx->in_f, &ctx->in_g};
     for (DevBuf* b : bufs) SPHX_TRY(sphx_ensure(ctx, *b, nb));
     double *x = ctx->in_b.as<double>(), *y = ctx->in_c.as<double>(), *z = ctx->in_d.as<double>();
@@ -267,6 +268,7 @@ struct DevIntegArgs {
     const double *m, *mu, *gam, *ptype, *ha, *va, *vh;
     const double *G, *rho;        // loop-form mode (G != nullptr): ha unused; pressure = G / rho [gas], visc = va (drv:460,473)
     const double *drag_on, *drag_re, *drho, *drhod;   // gas-dust drag (drv:462-463,473); drag_on == nullptr: none
+    const double* grav;           // self-gravity (n,3) (drv:448-449,477); nullptr: none
     double dt, m_h, kB, lim;
     // device-side verdict and dt (sphx_dev_integrate_auto): red2 = {halo too thin?, -min crossing time}
     const double* red2;
@@ -314,10 +316,13 @@ __global__ __launch_bounds__(256) void dev_integrate_kernel(DevIntegArgs a) {
             bad_acc = bad_acc || !sphx_finite(draw) || !sphx_finite(rraw);
         }
     }
-    double x[3], old[3], tot[3];
+    double x[3], old[3], tot[3], gr[3] = {0.0, 0.0, 0.0};
 #pragma unroll
     for (int c = 0; c < 3; ++c) { x[c] = a.pos[3 * (size_t)i + c]; old[c] = a.acc[3 * (size_t)i + c]; }
-    sphx_leapfrog_update(dt, x, v, vis, pa, nullptr, old, tot);                  // drv:475-486
+    if (a.grav)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gr[c] = a.grav[3 * (size_t)i + c];
+    sphx_leapfrog_update(dt, x, v, vis, pa, a.grav ? gr : nullptr, old, tot);    // drv:475-486
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         a.pos[3 * (size_t)i + c] = x[c];
@@ -353,6 +358,8 @@ static DevIntegArgs dev_integ_args(sphx_ctx* ctx, int64_t n_owned, double* pos, 
     a.G = nullptr; a.rho = nullptr;
     a.drag_on = ctx->dev_drag_on; a.drag_re = ctx->dev_drag_re; a.drho = ctx->dev_drag_rho; a.drhod = ctx->dev_drag_rhod;
     ctx->dev_drag_on = ctx->dev_drag_re = ctx->dev_drag_rho = ctx->dev_drag_rhod = nullptr;
+    a.grav = ctx->dev_grav;
+    ctx->dev_grav = nullptr;
     a.dt = dt; a.m_h = ctx->cst.m_h; a.kB = ctx->cst.k_B; a.lim = ctx->cst.pos_clamp;
     a.red2 = nullptr; a.dt_out = nullptr; a.first = 0; a.fixed_dt = 0.0; a.dt_0 = ctx->cst.dt_0; a.max_age = ctx->cst.max_age;
     a.counters = ctx->badc.as<u64>();
@@ -487,6 +494,14 @@ extern "C" int sphx_dev_set_drag_terms(sphx_ctx* ctx, const double* drag_on, con
     if (!ctx) return SPHX_E_ARG;
     NEED(drag_on); NEED(drag_reaction); NEED(rho); NEED(rho_dust);
     ctx->dev_drag_on = drag_on; ctx->dev_drag_re = drag_reaction; ctx->dev_drag_rho = rho; ctx->dev_drag_rhod = rho_dust;
+    return SPHX_OK;
+}
+
+// drv:448-449,477 for the NEXT sphx_dev_integrate / _auto / _loop call: total = grav + pressure + visc.  grav (n_owned,3) device
+// array, the complete field (sphx_dev_gravity_local + _remote); NULL: none (the update's bits without gravity).
+extern "C" int sphx_dev_set_gravity_accel(sphx_ctx* ctx, const double* grav) {
+    if (!ctx) return SPHX_E_ARG;
+    ctx->dev_grav = grav;
     return SPHX_OK;
 }
 

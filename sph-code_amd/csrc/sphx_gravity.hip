@@ -136,13 +136,7 @@ extern "C" int sphx_gravity_direct(sphx_ctx* ctx, int64_t n, const double* mass,
 // differences in that frame: a centre sum m x / M of absolute coordinates carries ulp(|x|), which for a cloud of size D at
 // distance T from the origin is T / D times the round-off of the differences themselves (1e-7 of a row at T / D = 2^27).
 // The near field differences two particles directly and needs no frame.
-#define PYR_MAX 12
-struct GravRef { double x, y, z; };
-struct Pyr {
-    int nlev;                                   // levels 1..nlev exist; level nlev is a single cell
-    int nx[PYR_MAX + 1], ny[PYR_MAX + 1], nz[PYR_MAX + 1];
-    long long off[PYR_MAX + 1];                 // first record of level l in the pyramid buffer
-};
+// (PYR_MAX, GravRef, Pyr: sphx_internal.h)
 
 __global__ __launch_bounds__(256) void pyr_level1_kernel(GridParams g, Pyr py, const int* __restrict__ cell_start,
                                                          const double* __restrict__ x, const double* __restrict__ y,
@@ -548,13 +542,12 @@ __global__ __launch_bounds__(256) void sorted_cells_kernel(int n, const int* cel
     if (t < n) out[t] = cell_of[perm[t]];
 }
 
-// Gravity of the particles x,y,z,m held in the cell-sorted order of the CURRENT grid (ctx->grid,
-// cell_start, cell_of, perm as sphx_build_grid left them).  acc (n,3) is written at omap[i] (or i).
-int sphx_gravity_tree_launch(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z,
-                             const double* m, int ws, const double* eps_dev, double eps, double G, const int* omap,
-                             double* acc) {
+// The pyramid (and, at order 2, its second moments) of those particles, into ctx->grav_pyr / grav_quad; the fine cell
+// of every sorted particle into ctx->grav_cell.  py and ref say how it is laid out and about which point.
+// about: the frame to use (a decomposed run's ranks share one); nullptr: a point inside this cloud.
+static int grav_pyramid(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, const double* m,
+                        Pyr& py, GravRef& ref, const GravRef* about = nullptr) {
     const GridParams g = ctx->grid;
-    Pyr py;
     memset(&py, 0, sizeof(py));
     py.nx[0] = g.nx; py.ny[0] = g.ny; py.nz[0] = g.nz;
     long long tot = 0;
@@ -579,7 +572,8 @@ int sphx_gravity_tree_launch(sphx_ctx* ctx, int64_t n, const double* x, const do
     const double bc[3] = {g.xmin + 0.5 * g.nx * g.cell, g.ymin + 0.5 * g.ny * g.cell, g.zmin + 0.5 * g.nz * g.cell};
     double rc[3];
     for (int c = 0; c < 3; ++c) rc[c] = fmin(fmax(bc[c], ctx->tbox_h[c]), ctx->tbox_h[3 + c]);
-    const GravRef ref = {rc[0], rc[1], rc[2]};
+    ref.x = rc[0]; ref.y = rc[1]; ref.z = rc[2];
+    if (about) ref = *about;
     const int n1 = py.nx[1] * py.ny[1] * py.nz[1];
     hipLaunchKernelGGL(pyr_level1_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, ctx->stream, g, py,
                        ctx->cell_start.as<int>(), x, y, z, m, ref, pyr, quad);
@@ -589,6 +583,17 @@ int sphx_gravity_tree_launch(sphx_ctx* ctx, int64_t n, const double* x, const do
     }
     hipLaunchKernelGGL(sorted_cells_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n,
                        ctx->cell_of.as<int>(), ctx->perm.as<int>(), ctx->grav_cell.as<int>());
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
+}
+
+// the walk over a pyramid grav_pyramid built for these particles
+static int grav_tree_walk(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, const double* m,
+                          const Pyr& py, const GravRef& ref, int ws, const double* eps_dev, double eps, double G,
+                          const int* omap, double* acc) {
+    const GridParams g = ctx->grid;
+    const double4* pyr = ctx->grav_pyr.as<double4>();
+    const double4* quad = ctx->grav_order >= 2 ? ctx->grav_quad.as<double4>() : nullptr;
     if (ctx->grav_per_thread)         // SPHX_GRAV_KERNEL=0: the per-thread walk (the wave kernel's reference)
         hipLaunchKernelGGL(gravity_tree_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n, g, py,
                            ws, ctx->grav_cell.as<int>(), ctx->cell_start.as<int>(), x, y, z, m, pyr, quad, eps_dev, eps, G,
@@ -603,6 +608,17 @@ int sphx_gravity_tree_launch(sphx_ctx* ctx, int64_t n, const double* x, const do
                            eps_dev, eps, G, ref, ctx->qorder, omap, acc);
     HIPCHK(hipGetLastError());
     return SPHX_OK;
+}
+
+// Gravity of the particles x,y,z,m held in the cell-sorted order of the CURRENT grid (ctx->grid,
+// cell_start, cell_of, perm as sphx_build_grid left them).  acc (n,3) is written at omap[i] (or i).
+int sphx_gravity_tree_launch(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z,
+                             const double* m, int ws, const double* eps_dev, double eps, double G, const int* omap,
+                             double* acc) {
+    Pyr py;
+    GravRef ref;
+    SPHX_TRY(grav_pyramid(ctx, n, x, y, z, m, py, ref));
+    return grav_tree_walk(ctx, n, x, y, z, m, py, ref, ws, eps_dev, eps, G, omap, acc);
 }
 
 extern "C" int sphx_gravity_tree(sphx_ctx* ctx, int64_t n, const double* mass, const double* points,
@@ -643,5 +659,510 @@ extern "C" int sphx_gravity_tree(sphx_ctx* ctx, int64_t n, const double* mass, c
                                       ctx->perm.as<int>(), ctx->out_b.as<double>()));
     HIPCHK(hipMemcpyAsync(accel, ctx->out_b.p, 3 * nb, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SPHX_OK;
+}
+
+// =================================================================================================
+// Gravity between parts: each part exports its mass to every other part as a flat list of records
+// =================================================================================================
+// A part (a rank of a decomposed run, a domain of an out-of-core one) holds the pyramid over its own particles.  What a
+// peer q may see coarsely is decided cell by cell against Q_q, the bounding box of q's particles:
+//   box(c)    the cell's box; on a face of the grid it reaches out to the part's true bounding box (the grid covers
+//             mean +- 3 sigma and clamps outliers into its face cells), and ends with the grid where the cell overhangs it
+//   accept(c) dist(box(c), Q_q) >= ws * longest edge of box(c)
+// A child's box lies inside its parent's, so an accepted parent has accepted children only.  A cell is exported as one
+// multipole record iff it is the FIRST accepted cell on the way down from the top cell (the walk from the top makes the
+// choice unique whatever rounding does to the rule above); the particles of a level-1 cell with no accepted ancestor and
+// not accepted itself travel as {x, y, z, m}.  Every massive particle is therefore in exactly one record, and every
+// multipole a target in Q_q receives has ws cell edges of clearance - the guarantee of the single-domain interaction list.
+// ws = 0: nothing is accepted, everything travels as particles (the exact form).
+// Records are compacted by flag + exclusive scan + write (no atomics): peers in rank order, levels top-down, cells in
+// index order; particles by level-1 cell, in storage order.  A cell record is three 32-B pieces {M, centre}, {Sxx Syy Szz
+// Sxy}, {Sxz Syz 0 0} (zeros at order 1), its centre relative to a reference point all parts share.
+#define GX_CELL_TILE 84                 // cell records staged at a time (3 pieces each: 252 of the tile's 256)
+struct GxGeo {
+    GridParams g;
+    Pyr py;
+    long long toff[PYR_MAX + 1];        // first position of level l in top-down order
+    long long tot;                      // cells of all levels
+    double shift[3];                    // the pyramid's frame - the shared frame
+    double ws;                          // 0: never accept
+};
+
+// own: the exporter's TRUE bounding box {min xyz, max xyz}
+__device__ __forceinline__ bool gx_accept(const GxGeo& e, int l, int X, int Y, int Z, const double* __restrict__ own,
+                                          const double* __restrict__ Q) {
+    const int idx[3] = {X, Y, Z}, nf[3] = {e.g.nx, e.g.ny, e.g.nz};
+    const double org[3] = {e.g.xmin, e.g.ymin, e.g.zmin};
+    double side = 0.0, d2 = 0.0;
+    for (int c = 0; c < 3; ++c) {
+        const long long f0 = (long long)idx[c] << l, f1 = (long long)(idx[c] + 1) << l;
+        // (a face cell holds the outliers clamped into it: out to the true box, and no further than the grid inwards)
+        const double lo = idx[c] == 0 ? fmin(org[c], own[c]) : org[c] + (double)f0 * e.g.cell;
+        const double hi = f1 >= nf[c] ? fmax(org[c] + (double)nf[c] * e.g.cell, own[3 + c]) : org[c] + (double)f1 * e.g.cell;
+        side = fmax(side, hi - lo);
+        const double gap = fmax(0.0, fmax(Q[c] - hi, lo - Q[3 + c]));
+        d2 += gap * gap;
+    }
+    return sqrt(d2) >= e.ws * side;
+}
+
+// position in top-down order -> (level, cell)
+__device__ __forceinline__ void gx_locate(const GxGeo& e, long long pos, int& l, int& c) {
+    l = e.py.nlev;
+    while (l > 1 && pos >= e.toff[l - 1]) --l;
+    c = (int)(pos - e.toff[l]);
+}
+
+// the level at which the way from the top cell down to cell (l; X, Y, Z) is first accepted; 0: nowhere
+__device__ __forceinline__ int gx_first_accepted(const GxGeo& e, int l, int X, int Y, int Z, const double* __restrict__ own,
+                                                 const double* __restrict__ Q) {
+    if (!(e.ws > 0.0)) return 0;
+    for (int L = e.py.nlev; L >= l; --L)
+        if (gx_accept(e, L, X >> (L - l), Y >> (L - l), Z >> (L - l), own, Q)) return L;
+    return 0;
+}
+
+// massive members of level-1 cell (X, Y, Z), visited in storage order
+template <class F>
+__device__ __forceinline__ void gx_members(const GridParams& g, int X, int Y, int Z, const int* __restrict__ cell_start,
+                                           const double* __restrict__ m, F f) {
+    const int fx0 = 2 * X, fx1 = min(2 * X + 2, g.nx);
+    for (int fz = 2 * Z; fz < min(2 * Z + 2, g.nz); ++fz)
+        for (int fy = 2 * Y; fy < min(2 * Y + 2, g.ny); ++fy) {
+            const int row = (fz * g.ny + fy) * g.nx;
+            const int s = cell_start[row + fx0], en = cell_start[row + fx1];
+            for (int j = s; j < en; ++j)
+                if (m[j] > 0.0) f(j);
+        }
+}
+
+// one thread per (peer, cell): cflag = 1 where the cell travels as a record, pcnt = particles a level-1 cell sends
+__global__ __launch_bounds__(256) void gx_flag_kernel(GxGeo e, int world, int self, const double* __restrict__ boxes,
+                                                      const double4* __restrict__ pyr, const int* __restrict__ cell_start,
+                                                      const double* __restrict__ m, int* cflag, int* pcnt) {
+    const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= (long long)world * e.tot) return;
+    const int q = (int)(id / e.tot);
+    int l, c;
+    gx_locate(e, id - (long long)q * e.tot, l, c);
+    const int nxl = e.py.nx[l], nyl = e.py.ny[l];
+    const int X = c % nxl, Y = (c / nxl) % nyl, Z = c / (nxl * nyl);
+    const double* Q = boxes + 6 * (size_t)q;
+    const bool peer = q != self && Q[3] >= Q[0] && Q[4] >= Q[1] && Q[5] >= Q[2];      // (an empty part has hi < lo)
+    const bool massive = pyr[e.py.off[l] + c].x > 0.0;
+    int first = -1;
+    if (peer && massive) first = gx_first_accepted(e, l, X, Y, Z, boxes + 6 * (size_t)self, Q);
+    cflag[id] = first == l ? 1 : 0;
+    if (l == 1) {
+        int cnt = 0;
+        if (first == 0) gx_members(e.g, X, Y, Z, cell_start, m, [&](int) { ++cnt; });
+        pcnt[(size_t)q * e.toff[0] + c] = cnt;            // (toff[0]: cells of level 1)
+    }
+}
+
+__global__ __launch_bounds__(256) void gx_write_kernel(GxGeo e, int world, const double4* __restrict__ pyr,
+                                                       const double4* __restrict__ quad, const int* __restrict__ cell_start,
+                                                       const double* __restrict__ x, const double* __restrict__ y,
+                                                       const double* __restrict__ z, const double* __restrict__ m,
+                                                       const int* __restrict__ cflag, const int* __restrict__ coff,
+                                                       const int* __restrict__ pcnt, const int* __restrict__ poff,
+                                                       double4* cells, long long cap_cells, double4* parts,
+                                                       long long cap_parts) {
+    const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= (long long)world * e.tot) return;
+    const int q = (int)(id / e.tot);
+    int l, c;
+    gx_locate(e, id - (long long)q * e.tot, l, c);
+    if (cflag[id] && coff[id] < cap_cells) {
+        const size_t cc = (size_t)(e.py.off[l] + c);
+        double4 a = pyr[cc];
+        a.y += e.shift[0]; a.z += e.shift[1]; a.w += e.shift[2];
+        double4* rec = cells + 3 * (size_t)coff[id];
+        rec[0] = a;
+        rec[1] = quad ? quad[2 * cc] : make_double4(0.0, 0.0, 0.0, 0.0);
+        rec[2] = quad ? quad[2 * cc + 1] : make_double4(0.0, 0.0, 0.0, 0.0);
+    }
+    if (l != 1) return;
+    const size_t pc = (size_t)q * e.toff[0] + c;
+    if (pcnt[pc] == 0) return;
+    const int nxl = e.py.nx[1], nyl = e.py.ny[1];
+    long long at = poff[pc];
+    gx_members(e.g, c % nxl, (c / nxl) % nyl, c / (nxl * nyl), cell_start, m, [&](int j) {
+        if (at < cap_parts) parts[at] = make_double4(x[j], y[j], z[j], m[j]);
+        ++at;
+    });
+}
+
+// counts (world,2): the records each peer is to get, from the scans' ends
+__global__ void gx_counts_kernel(int world, long long tot, long long n1, const int* __restrict__ coff,
+                                 const int* __restrict__ poff, int* counts) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= world) return;
+    counts[2 * q] = coff[(size_t)(q + 1) * tot] - coff[(size_t)q * tot];
+    counts[2 * q + 1] = poff[(size_t)(q + 1) * n1] - poff[(size_t)q * n1];
+}
+
+// The field of received records on the targets tidx[0..nt) (rows of the AoS array pts), ADDED to acc: one thread per
+// target, the records staged through LDS in tiles and read by every lane at once (a broadcast), cells first, then
+// particles, each in list order.  Cell centres and the targets are taken relative to ref, particles are differenced directly.
+__global__ __launch_bounds__(GRAV_TILE) void gx_remote_kernel(int nt, const int* __restrict__ tidx,
+                                                              const double* __restrict__ pts, GravRef ref,
+                                                              const double4* __restrict__ cells, int ncells, int order,
+                                                              const double4* __restrict__ parts, int nparts,
+                                                              const double* eps_ptr, double eps_val, double G, double* acc) {
+    __shared__ double4 tile[GRAV_TILE];
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const double eps = eps_ptr ? *eps_ptr : eps_val;
+    const double e2 = eps * eps;
+    const int i = t < nt ? (tidx ? tidx[t] : t) : 0;
+    double xi = 0.0, yi = 0.0, zi = 0.0;
+    if (t < nt) { xi = pts[3 * (size_t)i]; yi = pts[3 * (size_t)i + 1]; zi = pts[3 * (size_t)i + 2]; }
+    const double xr = xi - ref.x, yr = yi - ref.y, zr = zi - ref.z;
+    double ax = 0.0, ay = 0.0, az = 0.0;
+    for (int c0 = 0; c0 < ncells; c0 += GX_CELL_TILE) {
+        const int cnt = min(GX_CELL_TILE, ncells - c0);
+        __syncthreads();
+        if ((int)threadIdx.x < 3 * cnt) tile[threadIdx.x] = cells[3 * (size_t)c0 + threadIdx.x];
+        __syncthreads();
+        if (order >= 2) {
+            for (int k = 0; k < cnt; ++k)
+                grav_term_quad(tile[3 * k], tile[3 * k + 1], tile[3 * k + 2], 1.0, xr, yr, zr, e2, ax, ay, az);
+        } else {
+            for (int k = 0; k < cnt; ++k) {
+                const double4 q = tile[3 * k];
+                grav_term(q.y, q.z, q.w, q.x, xr, yr, zr, e2, ax, ay, az);
+            }
+        }
+    }
+    for (int j0 = 0; j0 < nparts; j0 += GRAV_TILE) {
+        const int cnt = min(GRAV_TILE, nparts - j0);
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) tile[threadIdx.x] = parts[(size_t)j0 + threadIdx.x];
+        __syncthreads();
+        for (int k = 0; k < cnt; ++k) {
+            const double4 q = tile[k];
+            grav_term(q.x, q.y, q.z, q.w, xi, yi, zi, e2, ax, ay, az);
+        }
+    }
+    if (t < nt) {
+        acc[3 * (size_t)i] += G * ax; acc[3 * (size_t)i + 1] += G * ay; acc[3 * (size_t)i + 2] += G * az;
+    }
+}
+
+// Flags and scans of the export of the part in hand (grid and pyramid current) to `world` peers; counts_dev (world,2).
+// boxes_dev (world,6): every part's true bounding box, the exporter's own in row `self`.
+static int gx_plan(sphx_ctx* ctx, GxGeo& e, const Pyr& py, const GravRef& ref, const GravRef& shared, int ws, int world,
+                   int self, const double* boxes_dev, const double* m_sorted, int* counts_dev) {
+    e.g = ctx->grid;
+    e.py = py;
+    long long at = 0;
+    for (int l = py.nlev; l >= 1; --l) { e.toff[l] = at; at += (long long)py.nx[l] * py.ny[l] * py.nz[l]; }
+    e.tot = at;
+    e.toff[0] = (long long)py.nx[1] * py.ny[1] * py.nz[1];
+    e.shift[0] = ref.x - shared.x; e.shift[1] = ref.y - shared.y; e.shift[2] = ref.z - shared.z;
+    e.ws = (double)ws;
+    const long long nflag = (long long)world * e.tot, npc = (long long)world * e.toff[0];
+    if (nflag > 0x7FFFFF00ll)
+        return sphx_set_err(ctx, SPHX_E_ARG, "gravity export: %d peers x %lld cells exceed the flag array", world, e.tot);
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_cflag, ((size_t)nflag + 1) * sizeof(int)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_coff, ((size_t)nflag + 1) * sizeof(int)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_pcnt, ((size_t)npc + 1) * sizeof(int)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_poff, ((size_t)npc + 1) * sizeof(int)));
+    int *cflag = ctx->gx_cflag.as<int>(), *pcnt = ctx->gx_pcnt.as<int>();
+    HIPCHK(hipMemsetAsync(cflag + nflag, 0, sizeof(int), ctx->stream));          // (the scans' closing zero)
+    HIPCHK(hipMemsetAsync(pcnt + npc, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(gx_flag_kernel, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, ctx->stream, e, world, self,
+                       boxes_dev, ctx->grav_pyr.as<double4>(), ctx->cell_start.as<int>(), m_sorted, cflag, pcnt);
+    HIPCHK(hipGetLastError());
+    SPHX_TRY(sphx_excl_scan_int(ctx, cflag, ctx->gx_coff.as<int>(), (int)nflag));
+    SPHX_TRY(sphx_excl_scan_int(ctx, pcnt, ctx->gx_poff.as<int>(), (int)npc));
+    hipLaunchKernelGGL(gx_counts_kernel, dim3((unsigned)((world + 63) / 64)), dim3(64), 0, ctx->stream, world, e.tot,
+                       e.toff[0], ctx->gx_coff.as<int>(), ctx->gx_poff.as<int>(), counts_dev);
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
+}
+
+// ... and the records themselves, peers concatenated; nothing is written beyond the capacities
+static int gx_write(sphx_ctx* ctx, const GxGeo& e, int world, const double* xs, const double* ys, const double* zs,
+                    const double* m_sorted, double4* cells, long long cap_cells, double4* parts, long long cap_parts) {
+    const long long nflag = (long long)world * e.tot;
+    hipLaunchKernelGGL(gx_write_kernel, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, ctx->stream, e, world,
+                       ctx->grav_pyr.as<double4>(), ctx->grav_order >= 2 ? ctx->grav_quad.as<double4>() : nullptr,
+                       ctx->cell_start.as<int>(), xs, ys, zs, m_sorted, ctx->gx_cflag.as<int>(), ctx->gx_coff.as<int>(),
+                       ctx->gx_pcnt.as<int>(), ctx->gx_poff.as<int>(), cells, cap_cells, parts, cap_parts);
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
+}
+
+__global__ __launch_bounds__(256) void gx_gather_part_kernel(int n, const int* __restrict__ ord,
+                                                             const double* __restrict__ pts, const double* __restrict__ m,
+                                                             double* x, double* y, double* z, double* mo) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const size_t i = (size_t)ord[t];
+    x[t] = pts[3 * i]; y[t] = pts[3 * i + 1]; z[t] = pts[3 * i + 2]; mo[t] = m[i];
+}
+__global__ __launch_bounds__(256) void gx_compose_kernel(int n, const int* __restrict__ ord, const int* __restrict__ perm,
+                                                         int* out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) out[t] = ord[perm[t]];
+}
+
+extern "C" int sphx_gravity_tree_parts(sphx_ctx* ctx, int64_t n, const double* mass, const double* points,
+                                       const double* sizes, double softening, double G, int ws, int k_cells, int nparts,
+                                       const int32_t* part_of, double* accel, int64_t* counts) {
+    if (!ctx) return SPHX_E_ARG;
+    if (!mass || !points || !accel || !part_of)
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_gravity_tree_parts: NULL argument");
+    if (n < 1 || n > 0x7FFFFFF0ll) return sphx_set_err(ctx, SPHX_E_ARG, "n=%lld out of range", (long long)n);
+    if (ws < 0 || ws > 4) return sphx_set_err(ctx, SPHX_E_ARG, "ws=%d not in 0..4", ws);
+    if (nparts < 1 || nparts > 1024) return sphx_set_err(ctx, SPHX_E_ARG, "nparts=%d not in 1..1024", nparts);
+    if (!sizes && !(softening >= 0.0)) return sphx_set_err(ctx, SPHX_E_ARG, "softening must be >= 0");
+    if (k_cells < 1) k_cells = 40;
+    // ---- the parts on the host: members in caller order, bounding boxes, the shared reference point ----
+    std::vector<int64_t> start((size_t)nparts + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        if (part_of[i] < 0 || part_of[i] >= nparts)
+            return sphx_set_err(ctx, SPHX_E_ARG, "part_of[%lld]=%d not in 0..%d", (long long)i, (int)part_of[i], nparts - 1);
+        ++start[(size_t)part_of[i] + 1];
+    }
+    for (int a = 0; a < nparts; ++a) start[a + 1] += start[a];
+    std::vector<int> ord((size_t)n);
+    std::vector<double> box((size_t)nparts * 6);
+    for (int a = 0; a < nparts; ++a)
+        for (int c = 0; c < 3; ++c) { box[6 * a + c] = INFINITY; box[6 * a + 3 + c] = -INFINITY; }
+    {
+        std::vector<int64_t> fill(start.begin(), start.end() - 1);
+        for (int64_t i = 0; i < n; ++i) {
+            const int a = part_of[i];
+            ord[(size_t)fill[a]++] = (int)i;
+            for (int c = 0; c < 3; ++c) {
+                const double v = points[3 * i + c];
+                if (v < box[6 * a + c]) box[6 * a + c] = v;
+                if (v > box[6 * a + 3 + c]) box[6 * a + 3 + c] = v;
+            }
+        }
+    }
+    GravRef shared;
+    {
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int a = 0; a < nparts; ++a)
+            for (int c = 0; c < 3; ++c) { lo[c] = fmin(lo[c], box[6 * a + c]); hi[c] = fmax(hi[c], box[6 * a + 3 + c]); }
+        double mid[3];
+        for (int c = 0; c < 3; ++c) mid[c] = (hi[c] >= lo[c]) ? lo[c] + 0.5 * (hi[c] - lo[c]) : 0.0;
+        shared.x = mid[0]; shared.y = mid[1]; shared.z = mid[2];
+    }
+    if (counts) memset(counts, 0, (size_t)nparts * nparts * 2 * sizeof(int64_t));
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->map_perm = nullptr;
+    ctx->qorder = nullptr;
+    const size_t nb = (size_t)n * sizeof(double);
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_pts, 3 * nb));
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_m, nb));
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_ord, (size_t)n * sizeof(int)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_map, (size_t)n * sizeof(int)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_box, (size_t)nparts * 6 * sizeof(double)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_counts, (size_t)nparts * 2 * sizeof(int)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->out_b, 3 * nb));
+    HIPCHK(hipMemcpyAsync(ctx->gx_pts.p, points, 3 * nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->gx_m.p, mass, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->gx_ord.p, ord.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->gx_box.p, box.data(), box.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const double* eps_dev = nullptr;
+    if (sizes) {                                   // eps = median(sizes) over ALL particles, nsc:358
+        SPHX_TRY(sphx_ensure(ctx, ctx->in_a, nb));
+        HIPCHK(hipMemcpyAsync(ctx->in_a.p, sizes, nb, hipMemcpyHostToDevice, ctx->stream));
+        double* slot = ctx->scal.as<double>() + SC_GRAV_EPS;
+        SPHX_TRY(sphx_median(ctx, n, ctx->in_a.as<double>(), slot));
+        eps_dev = slot;
+    }
+    int64_t nmax = 0;
+    for (int a = 0; a < nparts; ++a) nmax = start[a + 1] - start[a] > nmax ? start[a + 1] - start[a] : nmax;
+    DevBuf* bufs[] = {&ctx->in_b, &ctx->in_c, &ctx->in_d, &ctx->in_e, &ctx->in_f, &ctx->in_g, &ctx->in_h, &ctx->in_i};
+    for (DevBuf* b : bufs) SPHX_TRY(sphx_ensure(ctx, *b, (size_t)nmax * sizeof(double)));
+    double *x = ctx->in_b.as<double>(), *y = ctx->in_c.as<double>(), *z = ctx->in_d.as<double>();
+    double *xs = ctx->in_e.as<double>(), *ys = ctx->in_f.as<double>(), *zs = ctx->in_g.as<double>();
+    double *mp = ctx->in_h.as<double>(), *ms = ctx->in_i.as<double>();
+    double* acc = ctx->out_b.as<double>();
+    // ---- every part: its own field, then what it sends to each of the others ----
+    std::vector<DevBuf> xc((size_t)nparts), xp((size_t)nparts);        // the parts' exports, kept until all are applied
+    std::vector<int> cnt((size_t)nparts * nparts * 2, 0);
+    int rc = SPHX_OK;
+    auto part = [&](int a) -> int {
+        const int64_t na = start[a + 1] - start[a];
+        const int* ord_a = ctx->gx_ord.as<int>() + start[a];
+        const unsigned gb = (unsigned)((na + 255) / 256);
+        hipLaunchKernelGGL(gx_gather_part_kernel, dim3(gb), dim3(256), 0, ctx->stream, (int)na, ord_a,
+                           ctx->gx_pts.as<double>(), ctx->gx_m.as<double>(), x, y, z, mp);
+        HIPCHK(hipGetLastError());
+        ctx->clip_valid = false;
+        SPHX_TRY(sphx_build_grid(ctx, na, k_cells, x, y, z, 0.0));
+        SPHX_TRY(sphx_gather3(ctx, na, ctx->perm.as<int>(), x, y, z, xs, ys, zs));
+        hipLaunchKernelGGL(gather1_kernel, dim3(gb), dim3(256), 0, ctx->stream, (int)na, ctx->perm.as<int>(), mp, ms);
+        hipLaunchKernelGGL(gx_compose_kernel, dim3(gb), dim3(256), 0, ctx->stream, (int)na, ord_a, ctx->perm.as<int>(),
+                           ctx->gx_map.as<int>());
+        HIPCHK(hipGetLastError());
+        Pyr py;
+        GravRef ref;
+        SPHX_TRY(grav_pyramid(ctx, na, xs, ys, zs, ms, py, ref));
+        if (ws > 0)
+            SPHX_TRY(grav_tree_walk(ctx, na, xs, ys, zs, ms, py, ref, ws, eps_dev, softening, G, ctx->gx_map.as<int>(), acc));
+        else
+            SPHX_TRY(sphx_gravity_launch(ctx, na, xs, ys, zs, 1, ms, eps_dev, softening, G, ctx->gx_map.as<int>(), acc));
+        if (nparts == 1) return SPHX_OK;
+        GxGeo e;
+        SPHX_TRY(gx_plan(ctx, e, py, ref, shared, ws, nparts, a, ctx->gx_box.as<double>(), ms, ctx->gx_counts.as<int>()));
+        int* ca = cnt.data() + (size_t)a * nparts * 2;
+        HIPCHK(hipMemcpyAsync(ca, ctx->gx_counts.p, (size_t)nparts * 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        long long tc = 0, tp = 0;
+        for (int q = 0; q < nparts; ++q) { tc += ca[2 * q]; tp += ca[2 * q + 1]; }
+        SPHX_TRY(sphx_ensure(ctx, xc[a], (size_t)(tc > 0 ? tc : 1) * 3 * sizeof(double4)));
+        SPHX_TRY(sphx_ensure(ctx, xp[a], (size_t)(tp > 0 ? tp : 1) * sizeof(double4)));
+        return gx_write(ctx, e, nparts, xs, ys, zs, ms, xc[a].as<double4>(), tc, xp[a].as<double4>(), tp);
+    };
+    for (int a = 0; a < nparts && rc == SPHX_OK; ++a)
+        if (start[a + 1] > start[a]) rc = part(a);
+    // ---- every part takes the others' records, sources in part order ----
+    for (int b = 0; b < nparts && rc == SPHX_OK; ++b) {
+        const int64_t nb_ = start[b + 1] - start[b];
+        if (nb_ == 0) continue;
+        for (int a = 0; a < nparts; ++a) {
+            if (a == b || start[a + 1] == start[a]) continue;
+            const int* ca = cnt.data() + (size_t)a * nparts * 2;
+            long long oc = 0, op = 0;
+            for (int q = 0; q < b; ++q) { oc += ca[2 * q]; op += ca[2 * q + 1]; }
+            if (ca[2 * b] == 0 && ca[2 * b + 1] == 0) continue;
+            hipLaunchKernelGGL(gx_remote_kernel, dim3((unsigned)((nb_ + GRAV_TILE - 1) / GRAV_TILE)), dim3(GRAV_TILE), 0,
+                               ctx->stream, (int)nb_, ctx->gx_ord.as<int>() + start[b], ctx->gx_pts.as<double>(), shared,
+                               xc[a].as<double4>() + 3 * oc, ca[2 * b], ctx->grav_order, xp[a].as<double4>() + op,
+                               ca[2 * b + 1], eps_dev, softening, G, acc);
+        }
+        if (hipGetLastError() != hipSuccess) rc = sphx_set_err(ctx, SPHX_E_HIP, "sphx_gravity_tree_parts: remote launch failed");
+    }
+    if (rc == SPHX_OK && hipMemcpyAsync(accel, acc, 3 * nb, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        rc = sphx_set_err(ctx, SPHX_E_HIP, "sphx_gravity_tree_parts: copy of the result failed");
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == SPHX_OK)
+        rc = sphx_set_err(ctx, SPHX_E_HIP, "sphx_gravity_tree_parts: synchronise failed");
+    for (int a = 0; a < nparts; ++a) { sphx_release(ctx, xc[a]); sphx_release(ctx, xp[a]); }
+    if (rc == SPHX_OK && counts)
+        for (size_t i = 0; i < cnt.size(); ++i) counts[i] = cnt[i];
+    return rc;
+}
+
+
+// =================================================================================================
+// The same between the ranks of a decomposed run (device pointers; multigpu.py drives the exchange)
+// =================================================================================================
+__global__ __launch_bounds__(256) void gx_dev_gather_kernel(int n, int n_owned, const int* __restrict__ perm,
+                                                            const double* __restrict__ pos, const double* __restrict__ mass,
+                                                            double* xs, double* ys, double* zs, double* ms) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const int c = perm[s];
+    xs[s] = pos[3 * (size_t)c]; ys[s] = pos[3 * (size_t)c + 1]; zs[s] = pos[3 * (size_t)c + 2];
+    ms[s] = c < n_owned ? mass[c] : 0.0;                 // a ghost sits in the grid but belongs to its owner's pyramid
+}
+
+static int gx_dev_ready(sphx_ctx* ctx, const char* who) {
+    if (!ctx->gx_built || !ctx->map_perm || ctx->n != ctx->gx_n)
+        return sphx_set_err(ctx, SPHX_E_STATE, "%s before sphx_dev_gravity_build of the current search", who);
+    return SPHX_OK;
+}
+
+extern "C" int sphx_dev_gravity_build(sphx_ctx* ctx, int64_t n_total, int64_t n_owned, const double* pos, const double* mass,
+                                      const double ref[3]) {
+    if (!ctx) return SPHX_E_ARG;
+    NEED(pos); NEED(mass); NEED(ref);
+    if (!ctx->map_perm || ctx->n != n_total || ctx->map_nactive != n_owned)
+        return sphx_set_err(ctx, SPHX_E_STATE, "sphx_dev_gravity_build: no sphx_dev_search over %lld particles, %lld owned",
+                            (long long)n_total, (long long)n_owned);
+    if (!(isfinite(ref[0]) && isfinite(ref[1]) && isfinite(ref[2])))
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_gravity_build: reference point not finite");
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->gx_built = false;
+    const size_t nb = (size_t)n_total * sizeof(double);
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_pts, 3 * nb));
+    SPHX_TRY(sphx_ensure(ctx, ctx->gx_m, nb));
+    double* xs = ctx->gx_pts.as<double>();
+    hipLaunchKernelGGL(gx_dev_gather_kernel, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, ctx->stream, (int)n_total,
+                       (int)n_owned, ctx->map_perm, pos, mass, xs, xs + n_total, xs + 2 * n_total, ctx->gx_m.as<double>());
+    HIPCHK(hipGetLastError());
+    const GravRef about = {ref[0], ref[1], ref[2]};
+    SPHX_TRY(grav_pyramid(ctx, n_total, xs, xs + n_total, xs + 2 * n_total, ctx->gx_m.as<double>(), ctx->gx_py, ctx->gx_ref,
+                          &about));
+    ctx->gx_built = true;
+    ctx->gx_n = n_total;
+    ctx->gx_nowned = n_owned;
+    return SPHX_OK;
+}
+
+extern "C" int sphx_dev_gravity_local(sphx_ctx* ctx, int ws, double G, const double* eps_dev, double eps, double* accel) {
+    if (!ctx) return SPHX_E_ARG;
+    NEED(accel);
+    if (ws < 0 || ws > 4) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_gravity_local: ws=%d not in 0..4", ws);
+    if (!eps_dev && !(eps >= 0.0)) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_gravity_local: softening must be >= 0");
+    SPHX_TRY(gx_dev_ready(ctx, "sphx_dev_gravity_local"));
+    if (ws > 0 && ctx->use_verlet)
+        return sphx_set_err(ctx, SPHX_E_STATE, "tree gravity is not combined with incremental search");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t n = ctx->gx_n;
+    // the walk writes every particle of the grid, ghosts included, at its caller index: into a buffer of that length,
+    // whose owned rows (the first n_owned) are the result
+    SPHX_TRY(sphx_ensure(ctx, ctx->grav, 3 * (size_t)n * sizeof(double)));
+    const double* xs = ctx->gx_pts.as<double>();
+    if (ws > 0)
+        SPHX_TRY(grav_tree_walk(ctx, n, xs, xs + n, xs + 2 * n, ctx->gx_m.as<double>(), ctx->gx_py, ctx->gx_ref, ws, eps_dev,
+                                eps, G, ctx->map_perm, ctx->grav.as<double>()));
+    else
+        SPHX_TRY(sphx_gravity_launch(ctx, n, xs, xs + n, xs + 2 * n, 1, ctx->gx_m.as<double>(), eps_dev, eps, G, ctx->map_perm,
+                                     ctx->grav.as<double>()));
+    if (ctx->gx_nowned > 0)
+        HIPCHK(hipMemcpyAsync(accel, ctx->grav.p, 3 * (size_t)ctx->gx_nowned * sizeof(double), hipMemcpyDeviceToDevice,
+                              ctx->stream));
+    return SPHX_OK;
+}
+
+extern "C" int sphx_dev_gravity_export(sphx_ctx* ctx, int world, int rank, const double* boxes, int ws, double* cells,
+                                       int64_t cap_cells, double* parts, int64_t cap_parts, int32_t* counts) {
+    if (!ctx) return SPHX_E_ARG;
+    NEED(boxes); NEED(counts);
+    if (world < 1 || world > 1024 || rank < 0 || rank >= world)
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_gravity_export: rank %d of %d", rank, world);
+    if (ws < 0 || ws > 4) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_gravity_export: ws=%d not in 0..4", ws);
+    if (cap_cells < 0 || cap_parts < 0 || (cap_cells > 0 && !cells) || (cap_parts > 0 && !parts))
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_gravity_export: capacity without a buffer");
+    SPHX_TRY(gx_dev_ready(ctx, "sphx_dev_gravity_export"));
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t n = ctx->gx_n;
+    const double* xs = ctx->gx_pts.as<double>();
+    GxGeo e;
+    const GravRef shared = ctx->gx_ref;                  // (the pyramid was built about the shared point: no shift)
+    SPHX_TRY(gx_plan(ctx, e, ctx->gx_py, ctx->gx_ref, shared, ws, world, rank, boxes, ctx->gx_m.as<double>(), counts));
+    return gx_write(ctx, e, world, xs, xs + n, xs + 2 * n, ctx->gx_m.as<double>(), (double4*)cells, cap_cells, (double4*)parts,
+                    cap_parts);
+}
+
+extern "C" int sphx_dev_gravity_remote(sphx_ctx* ctx, int64_t n_owned, const double* pos, const double* cells, int64_t ncells,
+                                       const double* parts, int64_t nparts, double G, const double* eps_dev, double eps,
+                                       double* accel) {
+    if (!ctx) return SPHX_E_ARG;
+    NEED(pos); NEED(accel);
+    if (ncells < 0 || nparts < 0 || ncells > 0x7FFFFFF0ll || nparts > 0x7FFFFFF0ll || (ncells > 0 && !cells) ||
+        (nparts > 0 && !parts))
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_gravity_remote: %lld cells, %lld particles", (long long)ncells,
+                            (long long)nparts);
+    if (!eps_dev && !(eps >= 0.0)) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_gravity_remote: softening must be >= 0");
+    SPHX_TRY(gx_dev_ready(ctx, "sphx_dev_gravity_remote"));
+    if (n_owned != ctx->gx_nowned)
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dev_gravity_remote: n_owned=%lld, built for %lld", (long long)n_owned,
+                            (long long)ctx->gx_nowned);
+    HIPCHK(hipSetDevice(ctx->device));
+    if (n_owned < 1 || (ncells == 0 && nparts == 0)) return SPHX_OK;
+    hipLaunchKernelGGL(gx_remote_kernel, dim3((unsigned)((n_owned + GRAV_TILE - 1) / GRAV_TILE)), dim3(GRAV_TILE), 0,
+                       ctx->stream, (int)n_owned, (const int*)nullptr, pos, ctx->gx_ref, (const double4*)cells, (int)ncells,
+                       ctx->grav_order, (const double4*)parts, (int)nparts, eps_dev, eps, G, accel);
+    HIPCHK(hipGetLastError());
     return SPHX_OK;
 }

@@ -57,6 +57,15 @@ struct __attribute__((aligned(32))) RecSelf { // read only by the owner's thread
     double pad;
 };
 
+// the cell pyramid of the tree gravity (sphx_gravity.hip)
+#define PYR_MAX 12
+struct GravRef { double x, y, z; };
+struct Pyr {
+    int nlev;                                   // levels 1..nlev exist; level nlev is a single cell
+    int nx[PYR_MAX + 1], ny[PYR_MAX + 1], nz[PYR_MAX + 1];
+    long long off[PYR_MAX + 1];                 // first record of level l in the pyramid buffer
+};
+
 struct GridParams {
     double xmin, ymin, zmin;      // origin of the (robust) grid box
     double cell, inv_cell;
@@ -242,6 +251,13 @@ struct sphx_ctx {
     bool dev_ev_pending = false;  // sphx_dev_search recorded ev[1]/ev[2] around its kNN launch: not yet read
     // device-pointer API: drag terms handed to the next sphx_dev_integrate* call (sphx_dev_set_drag_terms)
     const double *dev_drag_on = nullptr, *dev_drag_re = nullptr, *dev_drag_rho = nullptr, *dev_drag_rhod = nullptr;
+    // device-pointer API: gravity (n_owned,3) handed to the next sphx_dev_integrate* call (sphx_dev_set_gravity_accel)
+    const double* dev_grav = nullptr;
+    // ... and what sphx_dev_gravity_build left for _local / _export of the same search (sphx_dev_search clears gx_built)
+    bool gx_built = false;
+    int64_t gx_n = 0, gx_nowned = 0;
+    Pyr gx_py;
+    GravRef gx_ref;
     // ---- grid ----
     GridParams grid;
     const double* tbox = nullptr;   // device: TRUE bounding box {min xyz, max xyz} of the last grid build
@@ -324,6 +340,10 @@ struct sphx_ctx {
     DevBuf grav, grav_sort, grav_tmp;   // (n,3) accelerations, sorted h, radix-sort scratch
     DevBuf grav_pyr, grav_cell;         // cell pyramid (mass, centre of mass), fine cell of each sorted particle
     DevBuf grav_quad;
+    // gravity between parts (sphx_gravity_tree_parts): all points (AoS) and masses, the particles part by part, sorted ->
+    // caller index of the part in hand, the parts' boxes, export flags / counts and their scans, counts per peer
+    // (decomposed runs, sphx_dev_gravity_*: gx_pts holds the sorted positions x | y | z, gx_m the sorted masses, ghosts 0)
+    DevBuf gx_pts, gx_m, gx_ord, gx_map, gx_box, gx_cflag, gx_coff, gx_pcnt, gx_poff, gx_counts;
     DevBuf list64, dref, pos0, pos4;   // Verlet refresh: int32[n][64], f64[n], f64[3n] positions at list build, f64[4n] packed current
     DevBuf nbr;                   // int32 [k][npad], K-major, -1 = missing
     DevBuf porder, mcount, mstart;      // blob order (qorder points at porder)

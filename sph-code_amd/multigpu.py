@@ -434,6 +434,54 @@ class LibBackend:
         self._keep_terms = (onto.contiguous(), react.contiguous(), rho.contiguous(), rhod.contiguous())
         self._chk(self.lib.sphx_dev_set_drag_terms(self.ctx.h, *[self._p(t) for t in self._keep_terms]))
 
+    # ---- self-gravity between ranks (include/sphx.h sphx_dev_gravity_*) ----
+    def set_gravity_order(self, order):
+        self._chk(self.lib.sphx_set_gravity_order(self.ctx.h, int(order)))
+
+    def _eps(self, eps):
+        """softening as (device pointer, value): a (1,) device tensor travels as the pointer"""
+        if torch.is_tensor(eps):
+            self._keep_eps = eps
+            return self._p(eps), 0.0
+        return None, float(eps)
+
+    def gravity_build(self, pos, m, n_owned, ref):
+        self._keep_grav = (pos, m)
+        self._chk(self.lib.sphx_dev_gravity_build(self.ctx.h, int(pos.shape[0]), int(n_owned), self._p(pos), self._p(m),
+                                                  (C.c_double * 3)(*[float(v) for v in ref])))
+        self._grav_no = int(n_owned)
+
+    def gravity_local(self, ws, G, eps):
+        """-> (n_owned,3): the field of this rank's own mass (ws = 0: the direct sum)."""
+        acc = torch.zeros((self._grav_no, 3), dtype=torch.float64, device=self.device)
+        ep, ev = self._eps(eps)
+        self._chk(self.lib.sphx_dev_gravity_local(self.ctx.h, int(ws), float(G), ep, ev, self._p(acc)))
+        return acc
+
+    def gravity_export(self, boxes, rank, ws, cap_cells, cap_parts):
+        """-> (cells (cap_cells,12), parts (cap_parts,4), counts (world,2) int32): the records for every peer, peers
+        concatenated in rank order; counts are the WANTED numbers (nothing is written beyond the capacities)."""
+        world = int(boxes.shape[0])
+        cells = torch.empty((max(int(cap_cells), 1), 12), dtype=torch.float64, device=self.device)
+        parts = torch.empty((max(int(cap_parts), 1), 4), dtype=torch.float64, device=self.device)
+        counts = torch.zeros((world, 2), dtype=torch.int32, device=self.device)
+        boxes = boxes.contiguous()
+        self._chk(self.lib.sphx_dev_gravity_export(self.ctx.h, world, int(rank), self._p(boxes), int(ws), self._p(cells),
+                                                   int(cap_cells), self._p(parts), int(cap_parts), self._p(counts)))
+        return cells, parts, counts
+
+    def gravity_remote(self, pos_owned, cells, parts, G, eps, accel):
+        """accel (n_owned,3) += the field of the received records (cells (nc,12), parts (np,4), in list order)."""
+        cells, parts = cells.contiguous(), parts.contiguous()
+        ep, ev = self._eps(eps)
+        self._chk(self.lib.sphx_dev_gravity_remote(self.ctx.h, int(pos_owned.shape[0]), self._p(pos_owned), self._p(cells),
+                                                   int(cells.shape[0]), self._p(parts), int(parts.shape[0]), float(G), ep,
+                                                   ev, self._p(accel)))
+
+    def set_gravity_accel(self, grav):
+        self._keep_gacc = None if grav is None else grav.contiguous()
+        self._chk(self.lib.sphx_dev_set_gravity_accel(self.ctx.h, self._p(self._keep_gacc)))
+
     def set_agb(self, nspecies, table, mu_specie, solar_mass):
         splines, mapto, divisor = table
         if int(nspecies) > len(mu_specie):                 # the C call reads one molecular weight per species
@@ -535,15 +583,38 @@ class DistributedSim:
 
     def __init__(self, state, lo, hi, backend, rank=0, world=1, device="cpu", comm_device=None,
                  halo_scale=1.15, skin_frac=0.15, need_grid=96, migrate_every=4, forms="hydro_update", d=None,
-                 with_drag=False, with_species=False, agb=None, visc_mode=None):
+                 with_drag=False, with_species=False, agb=None, visc_mode=None, gravity=None, G=6.67430e-11, gravity_ws=1,
+                 gravity_order=2, gravity_softening=None):
         """forms: the sums of the step - "hydro_update" (nsc:556-671; four halo phases) or "loop", the loop forms the
         reference's time loop calls (drv:451-458, smoothing length from the driver's global `d`, drv:68; three halo
         phases: state + E, h_j, rho_j - no Pi_j).  visc_mode (hydro_update forms): "ref_axis0" or "pairwise" - the
         per-pair viscosity of include/sphx.h sphx_set_visc_mode, three halo phases (state, h_j, rho_j; no m Pi_j);
         it needs a backend with visc_pairwise (LibBackend).  The backend holds the mode (LibBackend(visc_mode=...));
-        None takes the backend's, a value that disagrees with it is a ValueError."""
+        None takes the backend's, a value that disagrees with it is a ValueError.
+        gravity: None, "direct" or "tree" - self-gravity (drv:448-449,477) between ranks by exported multipoles (_gravity;
+        DESIGN 5.7): every rank sums its own mass (tree walk, or directly) and adds the record lists its peers export to
+        its bounding box - cells standing gravity_ws edges clear of it as multipoles of gravity_order 1 or 2, the rest
+        as particles; "direct" sends particles only and is the exact sum.  Softening: gravity_softening, or, with None,
+        the median of ALL particles' h of the step (nsc:358; one exchange of the owned h per step)."""
         if forms not in ("hydro_update", "loop"):
             raise ValueError("forms must be 'hydro_update' or 'loop'")
+        if gravity not in (None, "direct", "tree"):
+            raise ValueError("gravity must be None, 'direct' or 'tree'")
+        if gravity is not None:
+            lacks = [a_ for a_ in self.GRAVITY_BACKEND if not hasattr(backend, a_)]
+            if lacks:
+                raise ValueError("gravity=%r needs a backend with %s (LibBackend)" % (gravity, ", ".join(lacks)))
+            if int(gravity_ws) not in (1, 2, 3, 4) or int(gravity_order) not in (1, 2):
+                raise ValueError("gravity_ws must be 1..4 and gravity_order 1 or 2")
+            if gravity_softening is not None and not float(gravity_softening) >= 0.0:
+                raise ValueError("gravity_softening must be >= 0")
+            if hasattr(backend, "set_gravity_order"):
+                backend.set_gravity_order(int(gravity_order))
+        self.gravity, self.grav_G = gravity, float(G)
+        self.gravity_ws, self.gravity_order = int(gravity_ws), int(gravity_order)
+        self.gravity_softening = None if gravity_softening is None else float(gravity_softening)
+        self._gcap = [0, 0]                         # capacity of the export buffers (cell records, particle records)
+        self.grav_ref = None                        # the point the cells' centres travel relative to (set below)
         from .compat import visc_mode_code
         be_mode = getattr(backend, "visc_mode", None)
         if visc_mode is None:
@@ -629,6 +700,9 @@ class DistributedSim:
             dist.all_reduce(t0, op=dist.ReduceOp.MIN); dist.all_reduce(t1, op=dist.ReduceOp.MAX)
             pmin, pmax = t0.to(self.device), t1.to(self.device)
         ext = torch.clamp(pmax - pmin, min=1e-300)
+        # gravity: the centre of the initial global bounding box - the same on every rank, kept for the whole run (a
+        # restart takes it from the snapshot); it only has to lie within a few cloud sizes of the cloud
+        self.grav_ref = [float(v) for v in (pmin + 0.5 * (pmax - pmin)).tolist()] if n or world > 1 else [0.0, 0.0, 0.0]
         self.G = int(need_grid)
         self.g_lo = pmin - 0.25 * ext
         self.g_cs = float((1.5 * ext).max()) / self.G             # cubic coarse cells
@@ -640,6 +714,8 @@ class DistributedSim:
         self.last = {}
         self.stats = dict(steps=0, ghosts=0, redo=0, migrated=0)
         self.host_ms = {}
+
+    GRAVITY_BACKEND = ("gravity_build", "gravity_local", "gravity_export", "gravity_remote", "set_gravity_accel")
 
     # ------------------------------------------------------------------------------------------
     class _Section:
@@ -932,6 +1008,72 @@ class DistributedSim:
             self.last_species = dict(f_un_neighbor=F[:, :no], metallicity=None if Z is None else Z[:no],
                                      agb_dust=None if A is None else A[:no])
 
+    def _gravity(self, be, pos, m, h, no):
+        """Self-gravity of the owned particles, (n_owned,3), after the search and before the update.  Collectives (all
+        inside the step's redo loop, entered alike by every rank): one all_gather of (count, box) per rank, one
+        all_gather of the export counts with one host read, two variable-length row exchanges (cell records, particle
+        records); without gravity_softening one more exchange, of every rank's owned h, for eps = median(h)."""
+        dev, world, rank = pos.device, self.world, self.rank
+        f64 = dict(dtype=torch.float64, device=dev)
+        ws = self.gravity_ws if self.gravity == "tree" else 0
+        # ---- who holds how many particles, and where (true bounding boxes of the OWNED particles) ----
+        if no:
+            mine = torch.cat([torch.full((1,), float(no), **f64), pos[:no].min(dim=0).values, pos[:no].max(dim=0).values])
+        else:
+            mine = torch.tensor([0.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0], **f64)          # (an empty box: max < min)
+        if world > 1:
+            t = mine.to(self.comm_device)
+            allb = [torch.zeros_like(t) for _ in range(world)]
+            dist.all_gather(allb, t)
+            allb = torch.stack(allb).to(dev)
+        else:
+            allb = mine[None]
+        boxes = allb[:, 1:].contiguous()
+        # ---- softening: median of every particle's h (NumPy's definition, on the device) ----
+        if self.gravity_softening is not None:
+            eps = self.gravity_softening
+        else:
+            with self._sec("gravity_eps"):
+                hall = h[:no]
+                if world > 1:
+                    counts_host = [int(v) for v in allb[:, 0].tolist()]
+                    got = self.ex.rows([h[:no].reshape(no, 1)] * world, counts_host, 1)
+                    hall = torch.cat([h[:no]] + [g_.reshape(-1) for g_ in got if g_ is not None])
+                srt = torch.sort(hall).values
+                nh = int(srt.shape[0])
+                eps = (srt[nh // 2] if nh % 2 else 0.5 * (srt[nh // 2 - 1] + srt[nh // 2])).reshape(1).contiguous()
+        # ---- this rank's own mass ----
+        be.gravity_build(pos, m, no, self.grav_ref)
+        grav = be.gravity_local(ws, self.grav_G, eps)
+        if world == 1:
+            return grav
+        # ---- what the peers get: wanted counts first (one host read for all ranks' counts), a larger buffer if needed ----
+        cells, parts, cnt = be.gravity_export(boxes, rank, ws, self._gcap[0], self._gcap[1])
+        t = cnt.to(torch.int64).to(self.comm_device)
+        allc = [torch.zeros_like(t) for _ in range(world)]
+        dist.all_gather(allc, t)
+        allc = torch.stack(allc).tolist()                         # [sender][receiver][cells | particles]
+        mine_c = allc[rank]
+        want = [sum(c_[0] for c_ in mine_c), sum(c_[1] for c_ in mine_c)]
+        if want[0] > self._gcap[0] or want[1] > self._gcap[1]:
+            self._gcap = [max(self._gcap[0], int(1.25 * want[0]) + 64), max(self._gcap[1], int(1.25 * want[1]) + 256)]
+            cells, parts, cnt = be.gravity_export(boxes, rank, ws, self._gcap[0], self._gcap[1])
+        self.stats["grav_cells"] = self.stats.get("grav_cells", 0) + want[0]
+        self.stats["grav_parts"] = self.stats.get("grav_parts", 0) + want[1]
+        got = []
+        for which, buf, width in ((0, cells, 12), (1, parts, 4)):
+            send, o = [], 0
+            for p in range(world):
+                c_ = mine_c[p][which]
+                send.append(buf[o:o + c_])
+                o += c_
+            recv = [0 if p == rank else allc[p][rank][which] for p in range(world)]
+            rows = self.ex.rows(send, recv, width)
+            rows = [r for r in rows if r is not None]             # (rank order)
+            got.append(torch.cat(rows) if rows else torch.zeros((0, width), **f64))
+        be.gravity_remote(pos[:no], got[0], got[1], self.grav_G, eps, grav)
+        return grav
+
     def step(self, fixed_dt=0.0):
         """One decomposed pass of the hot path.
 
@@ -1016,6 +1158,12 @@ class DistributedSim:
                 extra = dict(zip(self.extra_fields, regrouped[(9 if loop else 8):]))
             with self._sec("search"):
                 h = be.search(pos, no, hint, mean_h)
+            grav = None
+            if self.gravity is not None:
+                # after the search (its grid carries the pyramid), before the update: integrate_auto is launched
+                # before the host knows the verdict
+                with self._sec("gravity"):
+                    grav = self._gravity(be, pos, m, h, no)
             f64 = dict(dtype=torch.float64, device=h.device)
             fused = hasattr(be, "step_scalars") and no > 0
             # a kNN radius that outgrew its claimed reach (checked below, together with dt: the sums
@@ -1126,6 +1274,8 @@ class DistributedSim:
                 # the update is launched before the host learns the verdict: the kernel itself leaves the state
                 # alone when the step has to be redone, and works out dt from the reduced crossing time
                 red_dev = red if red.device == h.device else red.to(h.device)
+                if grav is not None:
+                    be.set_gravity_accel(grav)
                 if loop:
                     dt_t = be.integrate_loop(no, s["pos"], s["vel"], s["acc"], s["E"], s["T"], s["m"], s["mu"], s["gam"],
                                              s["ptype"], delp, rho, va, vh, 0.0, red2=red_dev.contiguous(),
@@ -1183,6 +1333,8 @@ class DistributedSim:
                 dt = self.DT_0 / 10. if self.first else max(self.DT_0 / 5., min(self.DT_0 * 2., ctv))
                 if ctv > self.MAX_AGE:
                     dt = self.MAX_AGE / 100.
+            if grav is not None:
+                be.set_gravity_accel(grav)
             if self.forms == "loop":
                 be.integrate_loop(no, s["pos"], s["vel"], s["acc"], s["E"], s["T"], s["m"], s["mu"], s["gam"], s["ptype"],
                                   delp, rho, va, vh, dt)
@@ -1275,6 +1427,10 @@ class DistributedSim:
                    # with the particles: the snapshot holds them in the owned order like everything else)
                    with_drag=np.int64(self.with_drag), with_species=np.int64(self.with_species),
                    has_agb=np.int64(self.agb is not None))
+        if self.gravity is not None:
+            out.update(gravity=np.array(self.gravity), grav_G=np.float64(self.grav_G), gravity_ws=np.int64(self.gravity_ws),
+                       gravity_order=np.int64(self.gravity_order), grav_ref=np.asarray(self.grav_ref, dtype=np.float64),
+                       gravity_softening=np.float64(-1.0 if self.gravity_softening is None else self.gravity_softening))
         if self.with_drag:
             out.update(mean_grain_mass=c(s["mgm"]), mean_cross_section=c(s["mcs"]))
         if self.with_species:
@@ -1301,10 +1457,18 @@ class DistributedSim:
         if int(z.get("has_agb", 0)) and kw.get("agb") is None:
             raise ValueError("the snapshot's run carried an AGB table (metallicity + yields in the species pass): pass agb=(splines, "
                              "mapto, divisor) to from_snapshot")
+        if "gravity" in z:                            # the gravity settings as the run had them
+            kw.setdefault("gravity", str(z["gravity"]))
+            kw.setdefault("G", float(z["grav_G"]))
+            kw.setdefault("gravity_ws", int(z["gravity_ws"]))
+            kw.setdefault("gravity_order", int(z["gravity_order"]))
+            kw.setdefault("gravity_softening", None if float(z["gravity_softening"]) < 0.0 else float(z["gravity_softening"]))
         forms = str(z["forms"])
         kw.setdefault("visc_mode", str(z["visc_mode"]) if "visc_mode" in z else "ref_axis0")    # (older files: none)
         sim = cls(state, z["lo"], z["hi"], backend, rank, world, forms=forms, d=(float(z["d"]) if forms == "loop" else None), **kw)
         sim.s["h"] = torch.as_tensor(np.ascontiguousarray(z["sizes"], dtype=np.float64)).to(sim.device)
+        if "grav_ref" in z:
+            sim.grav_ref = [float(v) for v in z["grav_ref"]]
         sim.first = bool(int(z["first"]))
         sim.dt_last = float(z["dt_last"])
         sim.hmean_prev, sim.hmax_prev = float(z["hmean_prev"]), float(z["hmax_prev"])
@@ -1425,6 +1589,7 @@ def bench_main(args, rank, local_rank, world):
             scale = (n_global / 1e6) ** (1. / 3.)
             dilution = "constant density: x%.3g in length" % scale
     species, drag = bool(getattr(args, "species", False)), bool(getattr(args, "drag", False))
+    gravity = getattr(args, "gravity", None)         # None, "direct" or "tree": self-gravity between the ranks
     full = species or drag                           # these need the (N,15) composition
     # Box-filling workloads at their natural size (the default of N > 1: uniform_cube / two_phase): every rank draws ITS
     # OWN brick's particles (ics.cube_slab, seeded per brick) - no rank builds or bisects the global state (8 x 8e6
@@ -1482,13 +1647,15 @@ def bench_main(args, rank, local_rank, world):
     be = LibBackend(dev_index, k=args.k, clip_grad=getattr(args, "clip_grad", False))
     try:
         sim = DistributedSim(mine, lo, hi, be, rank, world, device=dev, comm_device=comm_dev, forms=forms, d=d_loop,
-                             with_drag=drag, with_species=species, agb=agb_table)
+                             with_drag=drag, with_species=species, agb=agb_table, gravity=gravity)
         for _ in range(args.warmup):
             sim.step()
     except Exception as exc:                  # (RuntimeError of a timed-out / failed transfer, a library error ...)
         give_up("set-up / warm-up steps", exc)
     sim.ex.bytes_sent = 0
     sim.stats.update(ghosts=0, redo=0, migrated=0, replans=0)
+    if gravity:
+        sim.stats.update(grav_cells=0, grav_parts=0)
     sim.host_ms.clear()
     be.ctx.reset_stats()
     torch.cuda.synchronize()
@@ -1573,6 +1740,11 @@ def bench_main(args, rank, local_rank, world):
                            "achieved_GBs": 1248 * value / 1e9,
                            "frac_of_hbm_peak": 1248 * value / 1e9 / (8000.0 * world)},
         }
+        if gravity:                          # (without --gravity the line is as it was)
+            out["config"]["gravity"] = "%s: exported multipoles between ranks, ws %d, order %d, eps = median(h)" % (
+                gravity, sim.gravity_ws, sim.gravity_order)
+            out["gravity_export_rank0"] = {"cells_per_step": sim.stats.get("grav_cells", 0) / max(args.steps, 1),
+                                           "particles_per_step": sim.stats.get("grav_parts", 0) / max(args.steps, 1)}
         print(json.dumps(out))
     dist.barrier()
     dist.destroy_process_group()
