@@ -547,6 +547,58 @@ int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const double* point
  * up, records and the K-major list, ms[1] the row pass, ms[2] reverse list (scan, one host wait, fill, sort), gather and
  * epilogue, ms[3] outputs coming back.  Measurement aid; replaces nothing in the reference.                          */
 int sphx_cool_last_timing(sphx_ctx* ctx, double ms[4]);
+/* ---- nsc.supernova_destruction(points, velocities, neighbor, mass, f_un, mu_array, sizes, densities, particle_type)
+ *                                                                                         nsc:1211-1263 ----- *
+ * Shock sputtering of dust on the list `neighbors` returned (drv:411).  For a gas row j (type_j == 0) and every entry
+ * i = neighbor[j,k] that is dust (type_i == 2), with s = sizes, r^2 = |x_i - x_j|^2, C_i = [m_i > crit_mass]:
+ *   wd = m_i 315 (s_i^2 - r^2)^3 / (64 pi s_i^9) (Weigh2_dust, nsc:678-681), w0 = the same at r^2 = 0
+ *   rho = wd [wd > 0] C_i;  the row contributes only if sum_k rho > 0                      nsc:1237-1239
+ *   v = |v_i - v_j| / 1000                                                                 nsc:1241-1242
+ *   eff_c(v), eff_si(v): linear interpolation on the 8 knots (knots_v; knots_c, knots_si: nsc:148-150); 0 outside
+ *   [knots_v[0], knots_v[7]], the last knot itself inside; species t takes none, eff_c or eff_si by species_curve[t]
+ *   ff_t = (dens_j C_i / critical_density) (eff_t nan_to_num(rho / w0));  ff_t >= 0.99 -> 0.99   nsc:1242-1245
+ *   lost_t = ff_t f_un[i,t] N_i,  N_i = m_i / (mu_i amu)                                   nsc:1247-1251
+ *   in ascending j, list order inside a row:  accept = (acc[i,t] + lost_t < limit_i);  lost_t *= accept;
+ *   acc[i,t] += lost_t;  reup[j,t] += lost_t                                               nsc:1252-1258
+ *   frac_destruction = nan_to_num(acc / N), frac_reuptake = nan_to_num(reup / N) (N_j of row j itself)  nsc:1260-1261
+ * Repair: the reference's tuple of interpolants has 14 entries for 15 species and raises on its
+ * first contributing row; the selector is an argument of length s here.  The reference's tuple is
+ * (0,0,0,0,0,0,1,2,1,2,1,1,1,0), padded with 0 ("none") up to s: none of the entries it wrote changes (index 6, e-,
+ * keeps the carbon curve as committed; a dust row has f[6] = 0).
+ * Quirks of the reference kept on purpose:
+ *   1. guard_mode SPHX_DUST_GUARD_COUNT: limit_i = 1 - the comparison of a count of atoms (~1e50) with 1.
+ *   2. NaN x False = NaN: a NaN lost_t is not accepted and still poisons acc[i,t] and reup[j,t], as in NumPy.
+ *   3. A negative f_un entry gives a negative lost_t, which is always accepted.
+ *   4. The d argument of Weigh2_dust is unused: it is no argument here.
+ * Ours: guard_mode SPHX_DUST_GUARD_FRACTION sets limit_i = N_i - a species' accumulated loss stays below the
+ * particle's count of atoms, which is what the comparison evidently meant; the reference cannot produce it (pinned by
+ * tests/dust_oracle.py alone).  A list entry outside [0, n) contributes nothing.  Only (gas row, dust entry) pairs are
+ * formed and a species whose selector is 0 loses exactly 0: the reference's 0 x inf = NaN of a non-dust entry or an
+ * unselected species with non-finite data does not arise.  A row is taken to hold distinct indices; a repeated index
+ * counts once per occurrence, in list order (the reference's fancy-indexed += adds it once).
+ * Each dust particle walks the rows that hold it in ascending (j, k) from a reverse list (4 bytes per pair, key
+ * j k_total + k) sorted per particle, and leaves one 32-bit word of accept bits per pair; each row then sums its K pairs
+ * in list order under those bits.  No floating-point atomic: the same inputs give the same bits on every call.
+ * knots_v must be finite and strictly increasing.  amu: sphx_constants.
+ * Outputs: frac_destruction, frac_reuptake (n,s); counts int64[5] or NULL, over the (pair, selected species) elements
+ * of contributing rows: lost > 0 before the guard; of those accepted; of those rejected; of the rejected those with
+ * lost < limit on their own (rejected by what was accumulated); elements capped at 0.99.
+ * SPHX_E_ARG: a NULL required pointer, n < 1, k < 1 or k > 64, s < 1 or s > SPHX_MAX_SPECIES, a non-finite crit_mass,
+ * critical_density or knot, knots_v not increasing, a selector outside 0..2, an unknown guard mode, n k beyond 2^31.
+ * SPHX_DUST_WG: lanes (particles, rows) of a workgroup of its kernels.                                              */
+#define SPHX_DUST_WG              256
+#define SPHX_DUST_GUARD_COUNT     0
+#define SPHX_DUST_GUARD_FRACTION  1
+int sphx_supernova_destruction(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const double* velocities,
+                               const int64_t* neighbor, const double* mass, const double* f_un, const double* mu,
+                               const double* sizes, const double* densities, const double* ptype, double crit_mass,
+                               double critical_density, const int32_t* species_curve /* int32[s]: 0 none, 1 c, 2 si */,
+                               const double knots_v[8], const double knots_c[8], const double knots_si[8], int guard_mode,
+                               double* frac_destruction, double* frac_reuptake, int64_t* counts /* int64[5] or NULL */);
+/* Device time of the last sphx_supernova_destruction call on this context, from HIP events on its stream, in ms: ms[0]
+ * inputs going up, records and the K-major list, ms[1] the reverse list (scan, one host wait, fill, sort), ms[2] the dust
+ * pass, ms[3] the row pass and the outputs coming back.  Measurement aid; replaces nothing in the reference.        */
+int sphx_dust_last_timing(sphx_ctx* ctx, double ms[4]);
 int sphx_get_stats(sphx_ctx* ctx, sphx_stats* out);
 int sphx_reset_stats(sphx_ctx* ctx);
 

@@ -15,6 +15,7 @@ for the functions the driver sph/code_running.py ("drv") calls on the SPH inner 
     artificial_viscosity   nsc:788-816      drv:458
     crossing_time          nsc:776-786      drv:222
     rad_cooling            nsc:1019-1176    drv:276
+    supernova_destruction  nsc:1211-1263    drv:411
 
 Hidden inputs are honoured the way the driver uses them: it assigns `nsc.d`, `nsc.d_0`,
 `nsc.dt`, `nsc.dt_0` (drv:68-75,231) and the functions read the module attribute at call
@@ -664,3 +665,71 @@ def cool_last_timing():
     """Device time of the last rad_cooling call of this module, from HIP events (include/sphx.h sphx_cool_last_timing)
     -> dict of ms: upload, rows, gather, download."""
     return _last_timing("sphx_cool_last_timing", ("upload", "rows", "gather", "download"))
+
+
+# ==============================================================================================
+# Shock sputtering of dust: supernova_destruction (nsc:1211-1263)
+# ==============================================================================================
+critical_density = 1000 * amu * 10 ** 6                                         # nsc:49
+crit_mass = 0.0001 * solar_mass                                                 # nsc:50 (the driver rescales it by raise_factor)
+DUST_KNOTS_V = (0., 50., 75., 100., 125., 150., 175., 200.)                     # nsc:148-150, km/s
+DUST_KNOTS_C = (0., 0.01, 0.04, 0.10, 0.18, 0.17, 0.18, 0.23)
+DUST_KNOTS_SI = (0., 0.02, 0.09, 0.23, 0.41, 0.40, 0.42, 0.40)
+DUST_CURVES = (0, 0, 0, 0, 0, 0, 1, 2, 1, 2, 1, 1, 1, 0)                        # nsc:159: 0 none, 1 carbon, 2 silicon
+DUST_GUARDS = {"count": 0, "fraction": 1}
+DUST_COUNTS = ("lost", "accepted", "rejected", "rejected_by_accumulation", "capped")
+
+
+def dust_species_curve(S, species_curve=None):
+    """The selector of length S as int32: the reference's 14-entry tuple padded with 0 ("none") by default (SURVEY
+    Appendix B Q13); a given one must have S entries of 0, 1 or 2."""
+    if species_curve is None:
+        if S < len(DUST_CURVES):
+            return np.array(DUST_CURVES[:S], dtype=np.int32)
+        return np.array(DUST_CURVES + (0,) * (S - len(DUST_CURVES)), dtype=np.int32)
+    sc = np.ascontiguousarray(species_curve, dtype=np.int32)
+    if sc.shape != (S,) or np.any(sc < 0) or np.any(sc > 2):
+        raise ValueError("species_curve must hold S = %d entries of 0, 1 or 2" % S)
+    return sc
+
+
+def supernova_destruction(points, velocities, neighbor, mass, f_un, mu_array, sizes, densities, particle_type,
+                          crit_mass=None, critical_density=None, species_curve=None, guard="count", full=False):
+    """nsc:1211-1263 -> (frac_destruction (N,S), frac_reuptake (N,S)); full=True appends a dict of the regime counts
+    (DUST_COUNTS).  crit_mass and critical_density default to the module's values, read at call time (the driver
+    rescales crit_mass).  species_curve: per species 0 none, 1 the carbon curve, 2 the silicon curve; by default the
+    reference's 14-entry tuple padded with "none" to S - as committed that tuple is one entry short of the 15 species
+    and the function raises.  guard="count" is the reference's comparison of an atom count with 1; guard="fraction" (not
+    the reference's) keeps a species' accumulated loss below the particle's atom count.  include/sphx.h,
+    sphx_supernova_destruction, lists the quirks kept."""
+    if not isinstance(guard, str) or guard not in DUST_GUARDS:
+        raise ValueError("guard must be 'count' or 'fraction', not %r" % (guard,))
+    nb, n, K = _nk(neighbor)
+    pts, vel = f64(points, (n, 3)), f64(velocities, (n, 3))
+    m, mu, h = f64(mass, (n,)), f64(mu_array, (n,)), f64(sizes, (n,))
+    dens, pt = f64(densities, (n,)), f64(particle_type, (n,))
+    fun = f64(f_un)
+    if fun.ndim != 2 or fun.shape[0] != n:
+        raise ValueError("f_un must be (N, S)")
+    S = fun.shape[1]
+    sc = dust_species_curve(S, species_curve)
+    g = globals()
+    cm = float(g["crit_mass"] if crit_mass is None else crit_mass)
+    cd = float(g["critical_density"] if critical_density is None else critical_density)
+    kv, kc, ks = (np.array(a, dtype=np.float64) for a in (DUST_KNOTS_V, DUST_KNOTS_C, DUST_KNOTS_SI))
+    destr = np.empty((n, S)); reup = np.empty((n, S))
+    counts = np.zeros(len(DUST_COUNTS), dtype=np.int64) if full else None
+    c_ = context()
+    c_.set_constants(amu=amu)
+    c_.check(c_.lib.sphx_supernova_destruction(c_.h, n, K, S, dp(pts), dp(vel), ip(nb), dp(m), dp(fun), dp(mu), dp(h), dp(dens),
+                                               dp(pt), cm, cd, sc.ctypes.data_as(_lib.c_int32_p), dp(kv), dp(kc), dp(ks),
+                                               DUST_GUARDS[guard], dp(destr), dp(reup), ip(counts)))
+    if full:
+        return destr, reup, dict(zip(DUST_COUNTS, (int(v) for v in counts)))
+    return destr, reup
+
+
+def dust_last_timing():
+    """Device time of the last supernova_destruction call of this module, from HIP events (include/sphx.h
+    sphx_dust_last_timing) -> dict of ms: upload, reverse, dust, rows."""
+    return _last_timing("sphx_dust_last_timing", ("upload", "reverse", "dust", "rows"))

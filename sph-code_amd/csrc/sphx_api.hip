@@ -176,7 +176,7 @@ extern "C" void sphx_destroy(sphx_ctx* ctx) {
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (int i = 0; i < 10; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t})
+    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t})
         for (int i = 0; i < 5; ++i)
             if (t->ev[i]) (void)hipEventDestroy(t->ev[i]);
     for (int r = 0; r < 3; ++r)
@@ -279,6 +279,7 @@ static int last_timing(sphx_ctx* ctx, StageTimer sphx_ctx::*t, double ms[4]) {
 extern "C" int sphx_arb_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::arb_t, ms); }
 extern "C" int sphx_rad_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::rad_t, ms); }
 extern "C" int sphx_cool_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::cool_t, ms); }
+extern "C" int sphx_dust_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::dust_t, ms); }
 
 // =============================================================================================
 // nsc.neighbors                                                                nsc:541-552

@@ -1,0 +1,316 @@
+// sphx_dust.hip - supernova_destruction (nsc:1211-1263): shock sputtering of dust by the gas rows that hold it, on the
+// neighbour list `neighbors` returned.
+//
+// The reference loops over the gas rows j in ascending order; each row forms, for every dust entry i and species t, the
+// atoms lost, accepts them only while acc[i,t] + lost < 1 - which reads what EARLIER rows took from i - adds the
+// accepted ones to acc[i,:] and their sum over the row to reup[j,:].  The pair term depends on j's and i's data alone;
+// only the guard depends on the order.  Here:
+//   prep      one lane per particle: a 128-byte record of what a pair needs from either side (DustRec, sphx_dust_pair.h).
+//   list      one lane per list entry: the (n,k) int64 list becomes the K-major int32 list the row pass reads coalesced
+//             (an entry outside [0, n) becomes -1), the (gas row, dust entry) pairs are counted per dust particle, and the
+//             row's flag collects "has a dust entry", "some rho > 0", "some rho is NaN" (integer atomics): the row
+//             contributes when sum_k rho > 0 (nsc:1239), i.e. when the flag is 3.
+//   reverse   for each dust particle i the pairs that hold it - count (above), exclusive scan, fill, then each slice
+//             sorted.  An entry is the 4-byte key j K + k: ascending keys are ascending rows, and the key names the slot.
+//             The fill's order is whatever the atomics give; the sort removes it.  (The same sequence as sphx_cool.hip's,
+//             kept as a copy of its own: the fill's predicate and what it stores differ)
+//   dust      one lane per particle i: walks its slice in ascending key with acc[t] in registers for the selected
+//             species, applies the guard, leaves one word of accept bits per pair in an (K, npad) array, counts the
+//             regimes (integer atomics, one per wave and counter), writes frac_destruction[i,:].
+//   rows      one lane per row j: recomputes its K pairs in list order on the same operands, multiplies by the stored
+//             accept bits, sums, writes frac_reuptake[j,:].
+// No floating-point atomic anywhere: the same inputs give the same bits on every call.  Vector stores from plain C++
+// only.  Every operation separately rounded, as NumPy's are.
+#include "sphx_internal.h"
+#include "sphx_dust_pair.h"
+#include <rocprim/rocprim.hpp>
+#pragma clang fp contract(off)
+
+#define DUST_WG SPHX_DUST_WG
+#define DUST_NCOUNT 5
+
+struct DustPrep {
+    int n;
+    const double *pos, *vel, *m, *mu, *sizes;           // (n,3) x 2, (n,) x 3
+    double crit_mass, amu;
+    DustRec* rec;
+};
+__global__ __launch_bounds__(DUST_WG) void dust_prep_kernel(DustPrep a) {
+    const int i = blockIdx.x * DUST_WG + threadIdx.x;
+    if (i >= a.n) return;
+    DustRec r;
+    r.x = a.pos[3 * (size_t)i]; r.y = a.pos[3 * (size_t)i + 1]; r.z = a.pos[3 * (size_t)i + 2];
+    r.vx = a.vel[3 * (size_t)i]; r.vy = a.vel[3 * (size_t)i + 1]; r.vz = a.vel[3 * (size_t)i + 2];
+    const double m = a.m[i], s = a.sizes[i];
+    const bool big = m > a.crit_mass;
+    r.s2 = s * s;
+    r.den = PI64 * pow9(s);
+    r.cw = big ? m * 315.0 : 0.0;
+    const double q = r.s2 - 0.0;
+    r.w0 = m * 315.0 * (q * q * q) / r.den;
+    r.N = m / (a.mu[i] * a.amu);
+    r.C = big ? 1.0 : 0.0;
+    r.pad_[0] = r.pad_[1] = r.pad_[2] = r.pad_[3] = 0.0;
+    a.rec[i] = r;
+}
+
+// the pairs that exist: a gas row's dust entry (nsc:1220-1222, 1237)
+__device__ __forceinline__ bool dust_is_pair(const double* __restrict__ ptype, int j, int p) {
+    return p >= 0 && ptype[j] == 0.0 && ptype[p] == 2.0;
+}
+
+// entry e = (j, kk) of the (n,k) list
+__global__ __launch_bounds__(DUST_WG) void dust_list_kernel(int n, int npad, int k, const long long* __restrict__ nb,
+                                                            const double* __restrict__ ptype, const DustRec* __restrict__ rec,
+                                                            int* __restrict__ nbr, int* cnt, int* flag) {
+    const long long e = (long long)blockIdx.x * DUST_WG + threadIdx.x;
+    if (e >= (long long)n * k) return;
+    const int j = (int)(e / k), kk = (int)(e - (long long)j * k);
+    const long long q = nb[e];
+    const int p = (q >= 0 && q < n) ? (int)q : -1;
+    nbr[(size_t)kk * npad + j] = p;
+    if (dust_is_pair(ptype, j, p)) {
+        atomicAdd(&cnt[p], 1);
+        const DustRec r = rec[p];
+        const double rho = dust_rho(r, dust_r2(r.x, r.y, r.z, rec[j].x, rec[j].y, rec[j].z));
+        atomicOr(&flag[j], 1 | (rho > 0.0 ? 2 : 0) | (rho != rho ? 4 : 0));
+    }
+}
+// slice of i: the keys j k + kk of the pairs that hold it, in the order the atomics hand out (sorted afterwards)
+__global__ __launch_bounds__(DUST_WG) void dust_fill_kernel(int n, int npad, int k, const int* __restrict__ nbr,
+                                                            const double* __restrict__ ptype, const int* __restrict__ start,
+                                                            int* cur, int* __restrict__ rev) {
+    const long long e = (long long)blockIdx.x * DUST_WG + threadIdx.x;
+    if (e >= (long long)npad * k) return;
+    const int kk = (int)(e / npad), j = (int)(e - (long long)kk * npad);
+    if (j >= n) return;
+    const int p = nbr[e];
+    if (dust_is_pair(ptype, j, p)) rev[start[p] + atomicAdd(&cur[p], 1)] = j * k + kk;
+}
+
+struct DustWalk {
+    int n, npad, k, s;
+    unsigned sel, si;                                   // bit t: species t has a curve; that curve is the silicon one
+    int fraction;                                       // guard: limit = N_i instead of 1
+    const int *start, *rev, *nbr, *flag;
+    const DustRec* rec;
+    const double *dens, *fun, *ptype;                   // (n,), (n,s), (n,)
+    double crit_density;
+    const DustKnots* kn;                                // on the device
+    unsigned* msk;                                      // (k, npad): accept bits of pair (j, kk) at kk npad + j
+    unsigned long long* counts;                         // DUST_NCOUNT
+    double *destr, *reup;                               // (n,s) each
+};
+
+// one atomic per wave and counter (every lane of the wave calls this)
+__device__ __forceinline__ void dust_count(unsigned long long* slot, unsigned v) {
+    for (int off = warpSize / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
+    if ((threadIdx.x & (warpSize - 1)) == 0 && v) atomicAdd(slot, (unsigned long long)v);
+}
+
+__global__ __launch_bounds__(DUST_WG) void dust_pass_kernel(DustWalk a) {
+    const int i = blockIdx.x * DUST_WG + threadIdx.x;
+    unsigned c_pos = 0, c_acc = 0, c_rej = 0, c_rej_small = 0, c_cap = 0;
+    if (i < a.n) {
+        const DustRec me = a.rec[i];
+        const double limit = a.fraction ? me.N : 1.0;
+        double acc[SPHX_MAX_SPECIES], f[SPHX_MAX_SPECIES];
+#pragma unroll
+        for (int t = 0; t < SPHX_MAX_SPECIES; ++t) {
+            acc[t] = 0.0;
+            f[t] = (t < a.s && ((a.sel >> t) & 1u)) ? a.fun[(size_t)i * a.s + t] : 0.0;
+        }
+        const int t1 = a.start[i + 1];
+        for (int u = a.start[i]; u < t1; ++u) {                          // ascending (j, kk): the reference's loop order
+            const int key = a.rev[u];
+            const int j = key / a.k, kk = key - j * a.k;
+            unsigned word = 0;
+            if (a.flag[j] == 3) {
+                const DustRec* rj = a.rec + j;
+                const double r2 = dust_r2(me.x, me.y, me.z, rj->x, rj->y, rj->z);
+                const double dv2 = dust_r2(me.vx, me.vy, me.vz, rj->vx, rj->vy, rj->vz);
+                const DustPair pr = dust_pair(me, r2, dv2, a.dens[j], a.crit_density, *a.kn);
+#pragma unroll
+                for (int t = 0; t < SPHX_MAX_SPECIES; ++t) {
+                    if (!((a.sel >> t) & 1u)) continue;
+                    bool capped;
+                    const double ff = dust_ff(pr, ((a.si >> t) & 1u) ? pr.esi : pr.ec, capped);
+                    double lost = dust_lost(ff, f[t], me.N);
+                    const bool accept = acc[t] + lost < limit;           // nsc:1252
+                    c_cap += capped;
+                    if (lost > 0.0) {
+                        ++c_pos;
+                        if (accept) ++c_acc;
+                        else { ++c_rej; c_rej_small += lost < limit; }
+                    }
+                    lost = lost * (accept ? 1.0 : 0.0);                  // NaN x False = NaN
+                    acc[t] += lost;                                      // nsc:1257
+                    word |= accept ? (1u << t) : 0u;
+                }
+            }
+            a.msk[(size_t)kk * a.npad + j] = word;
+        }
+        double* out = a.destr + (size_t)i * a.s;
+#pragma unroll
+        for (int t = 0; t < SPHX_MAX_SPECIES; ++t)
+            if (t < a.s) out[t] = sphx_nan_to_num(acc[t] / me.N);        // nsc:1260
+    }
+    dust_count(a.counts + 0, c_pos); dust_count(a.counts + 1, c_acc); dust_count(a.counts + 2, c_rej);
+    dust_count(a.counts + 3, c_rej_small); dust_count(a.counts + 4, c_cap);
+}
+
+__global__ __launch_bounds__(DUST_WG) void dust_row_kernel(DustWalk a) {
+    const int j = blockIdx.x * DUST_WG + threadIdx.x;
+    if (j >= a.n) return;
+    double sum[SPHX_MAX_SPECIES];
+#pragma unroll
+    for (int t = 0; t < SPHX_MAX_SPECIES; ++t) sum[t] = 0.0;
+    const DustRec* me = a.rec + j;
+    if (a.flag[j] == 3) {
+        const double xj = me->x, yj = me->y, zj = me->z, vxj = me->vx, vyj = me->vy, vzj = me->vz, dens = a.dens[j];
+        for (int kk = 0; kk < a.k; ++kk) {                               // list order: np.sum(dust_lost, axis=0), nsc:1253
+            const int p = a.nbr[(size_t)kk * a.npad + j];
+            if (!dust_is_pair(a.ptype, j, p)) continue;
+            const DustRec r = a.rec[p];
+            const DustPair pr = dust_pair(r, dust_r2(r.x, r.y, r.z, xj, yj, zj), dust_r2(r.vx, r.vy, r.vz, vxj, vyj, vzj), dens,
+                                          a.crit_density, *a.kn);
+            const unsigned word = a.msk[(size_t)kk * a.npad + j];
+            const double* f = a.fun + (size_t)p * a.s;
+#pragma unroll
+            for (int t = 0; t < SPHX_MAX_SPECIES; ++t) {
+                if (!((a.sel >> t) & 1u)) continue;
+                bool capped;
+                const double ff = dust_ff(pr, ((a.si >> t) & 1u) ? pr.esi : pr.ec, capped);
+                sum[t] += dust_lost(ff, f[t], r.N) * (((word >> t) & 1u) ? 1.0 : 0.0);
+            }
+        }
+    }
+    const double N = me->N;
+    double* out = a.reup + (size_t)j * a.s;
+#pragma unroll
+    for (int t = 0; t < SPHX_MAX_SPECIES; ++t)
+        if (t < a.s) out[t] = sphx_nan_to_num(sum[t] / N);               // nsc:1261
+}
+
+// =====================================================================================================================
+// host side
+// =====================================================================================================================
+static_assert(sizeof(DustKnots) <= 40 * sizeof(double), "sphx_ctx::dust_kn holds the knots");
+static bool dust_finite(double v) { return v - v == 0.0; }
+
+extern "C" int sphx_supernova_destruction(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const double* velocities,
+                                          const int64_t* neighbor, const double* mass, const double* f_un, const double* mu,
+                                          const double* sizes, const double* densities, const double* ptype, double crit_mass,
+                                          double critical_density, const int32_t* species_curve, const double knots_v[8],
+                                          const double knots_c[8], const double knots_si[8], int guard_mode,
+                                          double* frac_destruction, double* frac_reuptake, int64_t* counts) {
+    if (!ctx) return SPHX_E_ARG;
+    if (n < 1 || k < 1 || k > 64 || s < 1 || s > SPHX_MAX_SPECIES)
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: n=%lld, k=%d, s=%d (need n >= 1, 1 <= k <= 64, 1 <= s <= %d)",
+                            (long long)n, k, s, SPHX_MAX_SPECIES);
+    if (n > 0x7FFFFFF0ll || sphx_pad64(n) * (int64_t)k > 0x7FFFFFF0ll)
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: n=%lld x k=%d out of range", (long long)n, k);
+    if (!dust_finite(crit_mass) || !dust_finite(critical_density))
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: crit_mass=%g, critical_density=%g must be finite", crit_mass,
+                            critical_density);
+    if (guard_mode != SPHX_DUST_GUARD_COUNT && guard_mode != SPHX_DUST_GUARD_FRACTION)
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: unknown guard mode %d", guard_mode);
+    NEED(points); NEED(velocities); NEED(neighbor); NEED(mass); NEED(f_un); NEED(mu); NEED(sizes); NEED(densities); NEED(ptype);
+    NEED(species_curve); NEED(knots_v); NEED(knots_c); NEED(knots_si); NEED(frac_destruction); NEED(frac_reuptake);
+    DustWalk wa;
+    DustKnots& kn = *reinterpret_cast<DustKnots*>(ctx->dust_kn);      // (held by the context: the upload below reads it)
+    wa.sel = wa.si = 0;
+    for (int t = 0; t < s; ++t) {
+        if (species_curve[t] < 0 || species_curve[t] > 2)
+            return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: species_curve[%d]=%d (need 0, 1 or 2)", t, (int)species_curve[t]);
+        if (species_curve[t]) wa.sel |= 1u << t;
+        if (species_curve[t] == 2) wa.si |= 1u << t;
+    }
+    for (int t = 0; t < 8; ++t) {
+        if (!dust_finite(knots_v[t]) || !dust_finite(knots_c[t]) || !dust_finite(knots_si[t]) || (t && !(knots_v[t] > knots_v[t - 1])))
+            return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: knot %d must be finite and knots_v increasing", t);
+        kn.v[t] = knots_v[t]; kn.c[t] = knots_c[t]; kn.si[t] = knots_si[t];
+    }
+    for (int t = 0; t < 7; ++t) {
+        kn.sc[t] = (knots_c[t + 1] - knots_c[t]) / (knots_v[t + 1] - knots_v[t]);
+        kn.ssi[t] = (knots_si[t + 1] - knots_si[t]) / (knots_v[t + 1] - knots_v[t]);
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    SPHX_TRY(ctx->dust_t.begin(ctx));
+    hipStream_t st = ctx->stream;
+    const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), ns = nn * (size_t)s, nk = nn * (size_t)k;
+    // ---- inputs: points, velocities (3n each) | mass | mu | sizes | densities | ptype (n each) | f_un (n s); the list ----
+    SPHX_TRY(sphx_ensure(ctx, ctx->dust_in, (11 * nn + ns) * sizeof(double)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->dust_nb, nk * sizeof(int64_t)));
+    double* in = ctx->dust_in.as<double>();
+    double *d_pos = in, *d_vel = in + 3 * nn, *d_m = in + 6 * nn, *d_mu = in + 7 * nn, *d_sz = in + 8 * nn, *d_dens = in + 9 * nn,
+           *d_pt = in + 10 * nn, *d_fun = in + 11 * nn;
+    const CopyF64 us[] = {{points, d_pos, 3 * nn}, {velocities, d_vel, 3 * nn}, {mass, d_m, nn}, {mu, d_mu, nn}, {sizes, d_sz, nn},
+                          {densities, d_dens, nn}, {ptype, d_pt, nn}, {f_un, d_fun, ns}};
+    SPHX_TRY(sphx_upload_f64(ctx, us, 8));
+    HIPCHK(hipMemcpyAsync(ctx->dust_nb.p, neighbor, nk * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    // ---- records; the K-major list, the rows' flags, the counts ----
+    SPHX_TRY(sphx_ensure(ctx, ctx->dust_rec, nn * sizeof(DustRec)));
+    // ints: nbr (k npad) | cnt (n + 1) | cur (n + 1) | flag (n + 1) | start (n + 1) | msk (k npad), each part a multiple of four
+    const size_t n1 = (nn + 4) & ~size_t(3);
+    SPHX_TRY(sphx_ensure(ctx, ctx->dust_int, (2 * (size_t)k * npad + 4 * n1) * sizeof(int)));
+    int* nbr = ctx->dust_int.as<int>();
+    int *cnt = nbr + (size_t)k * npad, *cur = cnt + n1, *flag = cur + n1, *start = flag + n1;
+    unsigned* msk = (unsigned*)(start + n1);
+    HIPCHK(hipMemsetAsync(cnt, 0, 3 * n1 * sizeof(int), st));
+    // outputs: counters (8 u64) | the knots (40 doubles) | frac_destruction (n s) | frac_reuptake (n s)
+    SPHX_TRY(sphx_ensure(ctx, ctx->dust_out, (48 + 2 * ns) * sizeof(double)));
+    HIPCHK(hipMemsetAsync(ctx->dust_out.p, 0, 8 * sizeof(double), st));
+    HIPCHK(hipMemcpyAsync(ctx->dust_out.as<double>() + 8, &kn, sizeof(DustKnots), hipMemcpyHostToDevice, st));
+    DustPrep pa;
+    pa.n = (int)n; pa.pos = d_pos; pa.vel = d_vel; pa.m = d_m; pa.mu = d_mu; pa.sizes = d_sz;
+    pa.crit_mass = crit_mass; pa.amu = ctx->cst.amu;
+    pa.rec = ctx->dust_rec.as<DustRec>();
+    const unsigned nblk = (unsigned)((nn + DUST_WG - 1) / DUST_WG);
+    hipLaunchKernelGGL(dust_prep_kernel, dim3(nblk), dim3(DUST_WG), 0, st, pa);
+    hipLaunchKernelGGL(dust_list_kernel, dim3((unsigned)((nk + DUST_WG - 1) / DUST_WG)), dim3(DUST_WG), 0, st, (int)n, (int)npad, k,
+                       (const long long*)ctx->dust_nb.p, d_pt, pa.rec, nbr, cnt, flag);
+    HIPCHK(hipGetLastError());
+    SPHX_TRY(ctx->dust_t.mark(ctx, 1));
+    // ---- the reverse list: scan, fill, sort each slice ----
+    SPHX_TRY(sphx_excl_scan_int(ctx, cnt, start, (int)n));             // (cnt[n] = 0: the memset above; both start on 16-byte boundaries)
+    HIPCHK(hipMemcpyAsync(&ctx->pinned->side.count, start + n, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const size_t M = (size_t)ctx->pinned->side.count;
+    if (M > nk) return sphx_set_err(ctx, SPHX_E_HIP, "sphx_supernova_destruction: reverse list of %zu entries from %zu pairs", M, nk);
+    SPHX_TRY(sphx_ensure(ctx, ctx->dust_rev, 2 * (M + 4) * sizeof(int)));
+    int* rev_raw = ctx->dust_rev.as<int>();
+    int* rev = rev_raw + M + 4;
+    if (M > 0) {
+        hipLaunchKernelGGL(dust_fill_kernel, dim3((unsigned)(((size_t)k * npad + DUST_WG - 1) / DUST_WG)), dim3(DUST_WG), 0, st, (int)n,
+                           (int)npad, k, nbr, d_pt, start, cur, rev_raw);
+        HIPCHK(hipGetLastError());
+        unsigned bits = 1;
+        while (bits < 32 && (1ull << bits) < (unsigned long long)nk) ++bits;
+        size_t sort_bytes = 0;
+        HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
+        SPHX_TRY(sphx_ensure(ctx, ctx->dust_tmp, sort_bytes + 64));
+        HIPCHK(rocprim::segmented_radix_sort_keys(ctx->dust_tmp.p, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
+    }
+    SPHX_TRY(ctx->dust_t.mark(ctx, 2));
+    // ---- the dust pass, then the row pass ----
+    wa.n = (int)n; wa.npad = (int)npad; wa.k = k; wa.s = s;
+    wa.fraction = guard_mode == SPHX_DUST_GUARD_FRACTION;
+    wa.start = start; wa.rev = rev; wa.nbr = nbr; wa.flag = flag; wa.rec = pa.rec;
+    wa.dens = d_dens; wa.fun = d_fun; wa.ptype = d_pt;
+    wa.crit_density = critical_density;
+    wa.msk = msk;
+    wa.counts = (unsigned long long*)ctx->dust_out.p;
+    wa.kn = reinterpret_cast<const DustKnots*>(ctx->dust_out.as<double>() + 8);
+    wa.destr = ctx->dust_out.as<double>() + 48; wa.reup = wa.destr + ns;
+    hipLaunchKernelGGL(dust_pass_kernel, dim3(nblk), dim3(DUST_WG), 0, st, wa);
+    HIPCHK(hipGetLastError());
+    SPHX_TRY(ctx->dust_t.mark(ctx, 3));
+    hipLaunchKernelGGL(dust_row_kernel, dim3(nblk), dim3(DUST_WG), 0, st, wa);
+    HIPCHK(hipGetLastError());
+    const CopyF64 ds[] = {{frac_destruction, wa.destr, ns}, {frac_reuptake, wa.reup, ns}, {counts, wa.counts, DUST_NCOUNT}};
+    SPHX_TRY(sphx_download_f64(ctx, ds, 3));
+    SPHX_TRY(ctx->dust_t.mark(ctx, 4));
+    HIPCHK(hipStreamSynchronize(st));
+    return ctx->dust_t.end(ctx);
+}

@@ -146,7 +146,7 @@ struct StateArrays {
     DevBuf mgm, mcs;                             // mean grain mass / cross-section (drag, optional)
 };
 
-// The stage timer of a side call (the arb, rad and cool entry points): five events on ctx->stream around its four stages.
+// The stage timer of a side call (the arb, rad, cool and dust entry points): five events on ctx->stream around its four stages.
 // (sphx_api.hip; a call that returns between begin and end leaves ms zeroed)
 struct StageTimer {
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
@@ -391,6 +391,14 @@ struct sphx_ctx {
     // events of a call: [0] start, [1] inputs on the device, records and list built, [2] rows done, [3] reverse list, gather
     // and epilogue done, [4] outputs on the host (sphx_cool_last_timing)
     StageTimer cool_t;
+    // supernova_destruction (sphx_dust.hip), buffers of its own: staged inputs, the list as given, the particles' records,
+    // ints (the K-major list, counts, cursors, row flags, slice starts, the accept words), the reverse list (as filled |
+    // sorted), outputs (eight u64 counters, the knots, then the two (n,s) arrays), scratch of the segmented sort
+    DevBuf dust_in, dust_nb, dust_rec, dust_int, dust_rev, dust_out, dust_tmp;
+    double dust_kn[40] = {0};     // the call's knots and slopes on the host (DustKnots, sphx_dust_pair.h), uploaded from here
+    // events of a call: [0] start, [1] inputs on the device, records and list built, [2] reverse list sorted, [3] dust pass
+    // done, [4] row pass done and outputs on the host (sphx_dust_last_timing)
+    StageTimer dust_t;
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
@@ -496,7 +504,7 @@ enum {
 int sphx_badc_read(sphx_ctx* ctx);          // sums the buckets into ctx->stats.bad_* (waits for the stream)
 
 // ---- ctx->pinned: who reads back what, and where (host code only) ------------------------------------
-// What a side call (arb / rad / cool) reads back beside its reduction: the reduction's 32 bytes, a 4-byte count, arb's
+// What a side call (arb / rad / cool / dust) reads back beside its reduction: the reduction's 32 bytes, a 4-byte count, arb's
 // candidate counter.
 struct PinnedSide { double red[4]; int count; int pad_[7]; u64 cand; };
 struct PinnedLag {
