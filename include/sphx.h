@@ -599,6 +599,67 @@ int sphx_supernova_destruction(sphx_ctx* ctx, int64_t n, int k, int s, const dou
  * inputs going up, records and the K-major list, ms[1] the reverse list (scan, one host wait, fill, sort), ms[2] the dust
  * pass, ms[3] the row pass and the outputs coming back.  Measurement aid; replaces nothing in the reference.        */
 int sphx_dust_last_timing(sphx_ctx* ctx, double ms[4]);
+/* ---- nsc.chemisputtering_2(points, neighbor, mass, f_un, mu_array, sizes, T, particle_type)      nsc:1265-1416 ----- *
+ * Thermal / chemical sputtering of the dust rows and reuptake by the gas entries of their lists, on the list `neighbors`
+ * returned (drv:405).  The module globals d and dt are arguments, and so are the per-species tables (nsc:41-52).
+ *   num[i,t] = f_un[i,t] mass_i / sum_t(f_un[i,t] mu_specie[t])                             nsc:1266-1267
+ * A dust row j (type_j == 2), its list entries p = neighbor[j,k]:
+ *   w_k = v [v > 0] [type_p == 0], v = Weigh2(x_p, x_j, m_p, d) / mu_p                      nsc:1284, 1290
+ *   the row contributes if it has a gas entry and sum_k w_k > 0                             nsc:1274, 1298
+ *   scd_t = (sum_k w_k f_un[p,t]) mu_specie[t];  T_sph = sum_k w_k T_p / sum_k w_k (a star's T is 2.73)
+ *   dc_t = Weigh2_dust(0; m_j, sizes_j) f_un[j,t] mu_specie[t]                              nsc:1296, 1303
+ *   J_t = -diff(mrn^-0.5) / diff(mrn^0.5) / (3 mineral_densities[t]) sqrt(k_B T_sph / (2 pi mu_specie[t] amu))
+ *   Y_H = min(max(0.5 exp(-4600 / T_sph), 1e-7), 1e-3) yields[t] / max(yields), Y_He the same with 5, 1e-6, 1e-2
+ *   sput_t = (scd_3 / mu_3 Y_H + scd_4 Y_He / mu_4) mu_specie[t], then min(sput_t, dc_t)     nsc:1311-1316
+ *   K = scd + dc - sput;  E = exp(K J dt);  L = scd + dc E - sput;  F = K / L E;  NaN -> 1;  F < 0.01 -> 0.01;
+ *   F_t = 1 for t < 6                                                                        nsc:1317-1326
+ *   reuptake weight wk_k (one number per entry, the same in every column >= 6, 0 below): w_k f_un[p,5] mu_specie[5] on
+ *   the entries with w_k > 0, divided by its sum over them, divided by the sum again; if the sum of all of it is below
+ *   1e-15 a NaN becomes 1 / (number of such entries), else 0; divided by its sum once more; nan_to_num   nsc:1336-1363
+ *   new0_t = (F_t - 1) num[j,t]                                                             nsc:1374
+ * and then, in ascending j, with the counts as the earlier rows left them:
+ *   loss_kt = new0_t wk_k;  clamp 1: num[p,t] - loss_kt < 0.01 num[p,t] -> 0.99 num[p,t];  clamp 2: num[p,t] < 0 ->
+ *   num[p,t] (both on every entry of the list, dust and star entries and j itself included, where loss = 0)
+ *   sum_t = sum_k loss_kt;  clamp 3: sum_t + num[j,t] < 0.01 num[j,t] -> -0.99 num[j,t]      nsc:1382-1387
+ *   num[p,t] += nan_to_num(-sum_t wk_k);  num[j,t] += sum_k nan_to_num(sum_t wk_k)          nsc:1388-1395
+ * Closing correction per column t (nsc:1400-1409): pos = the sum of the positive, neg of the negative counts; if
+ * neg < 0 the negative ones become 0 and the positive ones are multiplied by 1 + neg / pos.  Then
+ *   mass_new_i = sum_t num[i,t] mu_specie[t],  f_un_new[i,t] = num[i,t] / sum_t num[i,t].
+ * Quirks of the reference kept on purpose:
+ *   1. mu_array (the input) divides the weight; the recomputed sum(f_un mu_specie) divides the counts.
+ *   2. The reuptake weight is the He++ column (5) of the entry, for every species.
+ *   3. The weight is normalised twice, and once more after its NaNs are filled.
+ *   4. F of column 6 (e-) is computed, not masked.
+ *   5. exp overflow gives inf / inf = NaN, hence F = 1.
+ *   6. The final losses sum_t wk_k are not clamped again: counts may go negative, and only the closing correction
+ *      removes that.
+ *   7. Columns 3, 4, 5 and "the first 6" are fixed, as there; hence s >= 7.
+ * Ours: double throughout where the reference holds the losses in longdouble (the difference is inside the bounds of
+ * tests/chem_oracle.py).  A list entry outside [0, n) contributes nothing.  Only gas entries get a weight: the
+ * reference's NaN x False = NaN of a non-gas entry with non-finite data does not arise.  A row is taken to hold distinct
+ * indices.  rel_w2g, rel_w2d and w2d of the reference are dead code and are not formed.
+ * The order dependence is a DAG over the dust rows (j depends on j' < j where they share a list entry); it is solved by
+ * rounds: every row clamps against counts formed from the previous round's clamped sums of the earlier rows, taken in
+ * ascending (j, k) from a reverse list per gas particle (4 bytes per pair, sorted), until a round changes no bit - the
+ * sequential result, reached after at most (contributing rows + 1) rounds.  No floating-point atomic and no
+ * waiting between workgroups: the same inputs give the same bits on every call.
+ * Outputs: mass_new (n), f_un_new (n,s); counts int64[7] or NULL: contributing rows; (contributing row, gas entry)
+ * pairs; clamp-1, clamp-2, clamp-3 events of the last round over (entry, column >= 6); columns corrected; rounds.
+ * SPHX_E_ARG: a NULL required pointer, n < 1, k < 1 or k > 64, s < 7 or s > SPHX_MAX_SPECIES, a non-finite d, dt,
+ * constant or table entry, n k beyond 2^31.
+ * SPHX_CHEM_WG: lanes of a workgroup of its kernels.                                                                */
+#define SPHX_CHEM_WG              256
+int sphx_chemisputtering_2(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const int64_t* neighbor,
+                           const double* mass, const double* f_un, const double* mu, const double* sizes, const double* T,
+                           const double* ptype, double d, double dt, const double* mu_specie /* [s] */,
+                           const double* mineral_densities /* [s] */, const double* sputtering_yields /* [s] */,
+                           const double mrn[2], double k_B, double amu, double m_0, double* mass_new, double* f_un_new,
+                           int64_t* counts /* int64[7] or NULL */);
+/* Device time of the last sphx_chemisputtering_2 call on this context, from HIP events on its stream, in ms: ms[0] inputs
+ * going up, records and the K-major list, ms[1] the row passes, ms[2] the reverse list (count, scan, one host wait, fill,
+ * sort), ms[3] the rounds (one host wait each), ms[4] the closing correction and the outputs coming back.  Measurement
+ * aid; replaces nothing in the reference.                                                                         */
+int sphx_chem_last_timing(sphx_ctx* ctx, double ms[5]);
 int sphx_get_stats(sphx_ctx* ctx, sphx_stats* out);
 int sphx_reset_stats(sphx_ctx* ctx);
 

@@ -16,6 +16,7 @@ for the functions the driver sph/code_running.py ("drv") calls on the SPH inner 
     crossing_time          nsc:776-786      drv:222
     rad_cooling            nsc:1019-1176    drv:276
     supernova_destruction  nsc:1211-1263    drv:411
+    chemisputtering_2      nsc:1265-1416    drv:405
 
 Hidden inputs are honoured the way the driver uses them: it assigns `nsc.d`, `nsc.d_0`,
 `nsc.dt`, `nsc.dt_0` (drv:68-75,231) and the functions read the module attribute at call
@@ -55,6 +56,7 @@ gamma = np.array([7. / 5, 5. / 3, 5. / 3, 5. / 3, 5. / 3, 5. / 3, 5. / 3, 15.635
 f_u = np.array([.86, .14] + [0] * 13, dtype=float)
 mineral_densities = np.array([1.e19] * 7 + [3320, 2260, 2266, 2329, 7870, 3250, 3250., 3166.])
 mrn_constants = np.array([50e-10, 5000e-10])
+sputtering_yields = np.array([0, 0, 0, 0, 0, 0, 0, 0.137, 0.295, 0.137, 0.295, 0.137, 0.137, 0.137, 0.137])   # nsc:45
 
 # ---- driver-injected globals (drv:68-75); d has no default in the reference either ---------
 d = None
@@ -546,8 +548,8 @@ def photoionization_arb(points, arb_points, mass, N_PART, photoionization, parti
 
 
 def _last_timing(getter, names):
-    """The four stage times (ms) a family's sphx_*_last_timing reports for the module context, under `names`."""
-    out = np.zeros(4)
+    """The stage times (ms) a family's sphx_*_last_timing reports for the module context, under `names`."""
+    out = np.zeros(len(names))
     c = context()
     c.check(getattr(c.lib, getter)(c.h, dp(out)))
     return dict(zip(names, out.tolist()))
@@ -733,3 +735,57 @@ def dust_last_timing():
     """Device time of the last supernova_destruction call of this module, from HIP events (include/sphx.h
     sphx_dust_last_timing) -> dict of ms: upload, reverse, dust, rows."""
     return _last_timing("sphx_dust_last_timing", ("upload", "reverse", "dust", "rows"))
+
+
+# ==============================================================================================
+# Thermal / chemical sputtering and reuptake: chemisputtering_2 (nsc:1265-1416)
+# ==============================================================================================
+CHEM_COUNTS = ("rows", "pairs", "clamp1", "clamp2", "clamp3", "columns_corrected", "rounds")
+
+
+def chem_table(S, given, name):
+    """A per-species table of length S as float64: `given`, or the module's `name` (the reference's 15 entries, cut to S
+    where S < 15; S > 15 needs a given one)."""
+    t = f64(globals()[name] if given is None else given)
+    if given is None and S < t.shape[0]:
+        t = np.ascontiguousarray(t[:S])
+    if t.shape != (S,):
+        raise ValueError("%s must hold S = %d entries" % (name, S))
+    return t
+
+
+def chemisputtering_2(points, neighbor, mass, f_un, mu_array, sizes, T, particle_type, d=None, dt=None, mu_specie=None,
+                      mineral_densities=None, sputtering_yields=None, mrn_constants=None, full=False):
+    """nsc:1265-1416 -> (mass_new (N,), f_un_new (N,S)); full=True appends a dict of the counts (CHEM_COUNTS).  d and dt
+    default to the module attributes, read at call time as the reference reads its globals (the driver assigns both);
+    the tables default to the module's, which are the reference's.  The reference's prints are dropped.  The rows'
+    order dependence is resolved by rounds on the device that end on the sequential result; include/sphx.h,
+    sphx_chemisputtering_2, has the formulas and lists the quirks kept."""
+    nb, n, K = _nk(neighbor)
+    pts, m, mu = f64(points, (n, 3)), f64(mass, (n,)), f64(mu_array, (n,))
+    h, temp, pt = f64(sizes, (n,)), f64(T, (n,)), f64(particle_type, (n,))
+    fun = f64(f_un)
+    if fun.ndim != 2 or fun.shape[0] != n:
+        raise ValueError("f_un must be (N, S)")
+    S = fun.shape[1]
+    g = globals()
+    mus = chem_table(S, mu_specie, "mu_specie")
+    dens = chem_table(S, mineral_densities, "mineral_densities")
+    ys = chem_table(S, sputtering_yields, "sputtering_yields")
+    mrn = f64(g["mrn_constants"] if mrn_constants is None else mrn_constants, (2,))
+    tstep = float(g["dt"] if dt is None else dt)
+    mass_new = np.empty(n); f_new = np.empty((n, S))
+    counts = np.zeros(len(CHEM_COUNTS), dtype=np.int64) if full else None
+    c_ = context()
+    c_.check(c_.lib.sphx_chemisputtering_2(c_.h, n, K, S, dp(pts), ip(nb), dp(m), dp(fun), dp(mu), dp(h), dp(temp), dp(pt), _d(d),
+                                           tstep, dp(mus), dp(dens), dp(ys), dp(mrn), float(k), float(amu), float(m_0),
+                                           dp(mass_new), dp(f_new), ip(counts)))
+    if full:
+        return mass_new, f_new, dict(zip(CHEM_COUNTS, (int(v) for v in counts)))
+    return mass_new, f_new
+
+
+def chem_last_timing():
+    """Device time of the last chemisputtering_2 call of this module, from HIP events (include/sphx.h
+    sphx_chem_last_timing) -> dict of ms: upload, rows, reverse, rounds, closing."""
+    return _last_timing("sphx_chem_last_timing", ("upload", "rows", "reverse", "rounds", "closing"))

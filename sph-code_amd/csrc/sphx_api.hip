@@ -176,8 +176,8 @@ extern "C" void sphx_destroy(sphx_ctx* ctx) {
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (int i = 0; i < 10; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t})
-        for (int i = 0; i < 5; ++i)
+    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t, &ctx->chem_t})
+        for (int i = 0; i < 6; ++i)
             if (t->ev[i]) (void)hipEventDestroy(t->ev[i]);
     for (int r = 0; r < 3; ++r)
         for (int i = 0; i < 10; ++i)
@@ -253,9 +253,9 @@ int sphx_download_f64(sphx_ctx* ctx, const CopyF64* t, int nt) {
 
 // ---- the side calls' stage timer ----------------------------------------------------------------
 int StageTimer::begin(sphx_ctx* ctx) {
-    for (int i = 0; i < 5; ++i)
+    for (int i = 0; i <= stages; ++i)
         if (!ev[i]) HIPCHK(hipEventCreate(&ev[i]));
-    for (int i = 0; i < 4; ++i) ms[i] = 0.0;
+    for (int i = 0; i < stages; ++i) ms[i] = 0.0;
     return mark(ctx, 0);
 }
 int StageTimer::mark(sphx_ctx* ctx, int i) {
@@ -263,23 +263,24 @@ int StageTimer::mark(sphx_ctx* ctx, int i) {
     return SPHX_OK;
 }
 int StageTimer::end(sphx_ctx* ctx) {
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < stages; ++i) {
         float t = 0.f;
         HIPCHK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
         ms[i] = t;
     }
     return SPHX_OK;
 }
-// Device time of the four stages of the family's last call on this context, from HIP events on its stream.
-static int last_timing(sphx_ctx* ctx, StageTimer sphx_ctx::*t, double ms[4]) {
+// Device time of the stages of the family's last call on this context, from HIP events on its stream.
+static int last_timing(sphx_ctx* ctx, StageTimer sphx_ctx::*t, double* ms) {
     if (!ctx || !ms) return SPHX_E_ARG;
-    for (int i = 0; i < 4; ++i) ms[i] = (ctx->*t).ms[i];
+    for (int i = 0; i < (ctx->*t).stages; ++i) ms[i] = (ctx->*t).ms[i];
     return SPHX_OK;
 }
 extern "C" int sphx_arb_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::arb_t, ms); }
 extern "C" int sphx_rad_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::rad_t, ms); }
 extern "C" int sphx_cool_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::cool_t, ms); }
 extern "C" int sphx_dust_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::dust_t, ms); }
+extern "C" int sphx_chem_last_timing(sphx_ctx* ctx, double ms[5]) { return last_timing(ctx, &sphx_ctx::chem_t, ms); }
 
 // =============================================================================================
 // nsc.neighbors                                                                nsc:541-552

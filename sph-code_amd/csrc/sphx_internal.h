@@ -146,11 +146,12 @@ struct StateArrays {
     DevBuf mgm, mcs;                             // mean grain mass / cross-section (drag, optional)
 };
 
-// The stage timer of a side call (the arb, rad, cool and dust entry points): five events on ctx->stream around its four stages.
-// (sphx_api.hip; a call that returns between begin and end leaves ms zeroed)
+// The stage timer of a side call (the arb, rad, cool, dust and chem entry points): events on ctx->stream around its stages -
+// four of them, five for chem.  (sphx_api.hip; a call that returns between begin and end leaves ms zeroed)
 struct StageTimer {
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
-    double ms[4] = {0, 0, 0, 0};
+    int stages = 4;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
+    double ms[5] = {0, 0, 0, 0, 0};
     int begin(sphx_ctx* ctx);           // creates the events, zeroes ms, records ev[0]
     int mark(sphx_ctx* ctx, int i);     // records ev[i]
     int end(sphx_ctx* ctx);             // ms[i] = ev[i] .. ev[i + 1]; after the call's last synchronise
@@ -399,6 +400,17 @@ struct sphx_ctx {
     // events of a call: [0] start, [1] inputs on the device, records and list built, [2] reverse list sorted, [3] dust pass
     // done, [4] row pass done and outputs on the host (sphx_dust_last_timing)
     StageTimer dust_t;
+    // chemisputtering_2 (sphx_chem.hip), buffers of its own: staged inputs and tables, the list as given, the particles'
+    // records, ints per particle (the K-major list, dust flags and ordinals, counts, cursors, slice starts), per dust row
+    // doubles (gas and reuptake weights, row scalars, new0 and the two generations of clamped sums) and ints (particle of an
+    // ordinal, contributes, place of an entry in the reverse list), the reverse list (as filled | sorted), the first-stage
+    // losses per (pair, column), outputs (the counters, num0, the final counts, mass_new, f_un_new, partial sums),
+    // scratch of the segmented sort
+    DevBuf chem_in, chem_nb, chem_rec, chem_int, chem_row, chem_rowi, chem_rev, chem_first, chem_out, chem_tmp;
+    double chem_tab[4 * SPHX_MAX_SPECIES] = {0};   // the call's tables on the host, uploaded from here
+    // events of a call: [0] start, [1] inputs on the device, records and list built, [2] row passes done, [3] reverse list
+    // sorted, [4] rounds done, [5] closing correction done and outputs on the host (sphx_chem_last_timing)
+    StageTimer chem_t{5};
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
@@ -504,7 +516,7 @@ enum {
 int sphx_badc_read(sphx_ctx* ctx);          // sums the buckets into ctx->stats.bad_* (waits for the stream)
 
 // ---- ctx->pinned: who reads back what, and where (host code only) ------------------------------------
-// What a side call (arb / rad / cool / dust) reads back beside its reduction: the reduction's 32 bytes, a 4-byte count, arb's
+// What a side call (arb / rad / cool / dust / chem) reads back beside its reduction: the reduction's 32 bytes, a 4-byte count, arb's
 // candidate counter.
 struct PinnedSide { double red[4]; int count; int pad_[7]; u64 cand; };
 struct PinnedLag {
