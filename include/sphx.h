@@ -660,6 +660,81 @@ int sphx_chemisputtering_2(sphx_ctx* ctx, int64_t n, int k, int s, const double*
  * sort), ms[3] the rounds (one host wait each), ms[4] the closing correction and the outputs coming back.  Measurement
  * aid; replaces nothing in the reference.                                                                         */
 int sphx_chem_last_timing(sphx_ctx* ctx, double ms[5]);
+/* ---- the dust phase of the time loop, code_running.py:399-435 --------------------------------------------------- *
+ * sphx_dust_bookkeeping: drv:412-433 on arrays.  mass and f_un are chemisputtering_2's outputs, mu_array the one that
+ * went INTO the phase, frac_destruction / frac_reuptake supernova_destruction's outputs.  Per particle i:
+ *   delta_n[t] = nan_to_num(-frac_destruction[i,t] + frac_reuptake[i,t])                                 drv:416
+ *   mass_change = nan_to_num(sum_t mass_i / mu_i delta_n[t] mu_specie[t])                                drv:417
+ *   f[t] = f_un[i,t] + delta_n[t];  NaN -> 1e-15;  f[t] /= sum_t f[t]                                    drv:421-424
+ *   mass_out = mass_i + mass_change;  mass_out < 0 -> crit_mass / 200                                    drv:425, 431
+ *   mu_out = sum_t f[t] mu_specie[t] / sum_t f[t];  gamma_out likewise with gamma_specie                 drv:432-433
+ * The driver's prints come back as numbers.  totals[6]: the sum of mass_before (NaN when mass_before is NULL: the
+ * masses before chemisputtering, used for nothing else), of mass, of mass_out; mass_reduction (drv:412, negative),
+ * mass_increase (drv:413), the sum of mass_change (drv:419, in kg - the driver prints solar masses).  counts int64[2]:
+ * masses reset at drv:431, NaN entries filled at drv:423.  Either may be NULL.
+ * Quirks kept: mass_change uses the post-chem mass with the pre-phase mu; a NaN composition entry becomes 1e-15 BEFORE the
+ * row is renormalised; a reset mass is crit_mass / 200 whatever it was.  The "negative compositions" prints are not
+ * reproduced; cross_array and optical_depth (drv:434-435) feed rad_heating alone and are not formed.
+ * Ours: double where the driver has longdouble (f_un, delta_n: DESIGN 5.12); every sum over species runs t = 0 .. s - 1
+ * one by one; sums over particles are sums of chunks of 256 in index order, the chunks added in a fixed order by one
+ * workgroup: no floating-point atomic, the same bits on every call.
+ * SPHX_E_ARG: a NULL required pointer, n < 1, s < 1 or s > SPHX_MAX_SPECIES, a non-finite crit_mass.               */
+int sphx_dust_bookkeeping(sphx_ctx* ctx, int64_t n, int s, const double* mass, const double* mu_array, const double* f_un,
+                          const double* frac_destruction, const double* frac_reuptake, const double* mass_before /* or NULL */,
+                          const double* mu_specie /* [s] */, const double* gamma_specie /* [s] */, double crit_mass,
+                          double* mass_out, double* f_un_out, double* mu_out, double* gamma_out, double* totals /* [6] or NULL */,
+                          int64_t* counts /* int64[2] or NULL */);
+/* sphx_state_dust_phase: the whole block on the step loop's resident state - the first side call that WRITES it.
+ *   drv:399      every row of f_un divided by its sum
+ *   drv:400      density = nsc.density (sphx_density) on the current positions, the pre-phase mass, the list and d
+ *   drv:401-402  dust_density and num_dens are dead in the block: not formed
+ *   drv:407-408  chemisputtering_2 on (points, list, mass, the normalised f_un, the pre-phase mu, sizes, T, ptype)
+ *   drv:411      supernova_destruction on (points, velocities, list, the post-chem mass and f_un, the pre-phase mu, sizes,
+ *                the density of drv:400, ptype)
+ *   drv:412-433  sphx_dust_bookkeeping's arithmetic
+ * Inputs are the state as the last sphx_step left it; sizes is the step's kNN radius, as sphx_state_rad_transfer takes
+ * it.  THE LIST IS THE LAST STEP'S OWN neighbour list, translated to particle ids: as in the driver, where `neighbor` at
+ * drv:407 is what drv:437 made in the previous pass and drv:481 has moved the points since.  A missing entry (fewer
+ * than k particles) is outside [0, n), which both stages ignore.  Everything is gathered into the order of upload and the
+ * two ordered stages run their rows ascending in it: every output has the bits of the array calls (sphx_density,
+ * sphx_chemisputtering_2, sphx_supernova_destruction, sphx_dust_bookkeeping) on the downloaded state and
+ * sphx_state_download_neighbors' list.  dt, d, the tables, crit_mass, critical_density, species_curve, the knots and
+ * guard_mode are those calls' arguments; m_0 is also sphx_density's and amu also sphx_supernova_destruction's (which
+ * read them from the context's constants).
+ * Written: mass, mu_array, gamma_array and the composition of the resident state; with drag on also mean_grain_mass and
+ * mean_cross (sphx_state_set_drag), formed from the new f_un and the per-species tables grain_mass / sigma_effective as
+ * np.sum(table * f_un, axis=1) - the reference recomputes them on every net_impulse call (nsc:720-726).  Nothing else
+ * of the step's is touched (T, E, positions, velocities, sizes, the list).
+ * Optional outputs in the order of upload, any may be NULL: density (n), mass_chem (n), f_un_chem (n,s),
+ * frac_destruction, frac_reuptake (n,s); chem_counts int64[7] and dust_counts int64[5] as the array calls define them;
+ * totals[6] and book_counts int64[2] as sphx_dust_bookkeeping's (totals[0] is the sum of the masses before the phase).
+ * SPHX_E_STATE: no state, no sphx_step yet (the list and sizes do not exist), incremental search on (its refreshed
+ * lists are not the driver's), the step's list no longer standing (since the step a call on this context has rewritten
+ * the K-major list, the processing order or the ids: an array call that uploads a list, a device-API search, an upload;
+ * sphx_neighbors and the samplers leave it alone), no composition of s >= 7.
+ * SPHX_E_ARG: drag on without grain_mass and sigma_effective, and what the array calls refuse.  A refused call leaves the
+ * state as it was.                                                                                                  */
+int sphx_state_dust_phase(sphx_ctx* ctx, double dt, double d, const double* mu_specie, const double* gamma_specie,
+                          const double* mineral_densities, const double* sputtering_yields, const double mrn[2], double k_B,
+                          double amu, double m_0, double crit_mass, double critical_density, const int32_t* species_curve,
+                          const double knots_v[8], const double knots_c[8], const double knots_si[8], int guard_mode,
+                          const double* grain_mass /* [s] or NULL */, const double* sigma_effective /* [s] or NULL */,
+                          double* density, double* mass_chem, double* f_un_chem, double* frac_destruction,
+                          double* frac_reuptake, int64_t* chem_counts, int64_t* dust_counts, double* totals,
+                          int64_t* book_counts);
+/* Device time of the last sphx_state_dust_phase call, from HIP events, in ms: ms[0] the state gathered and the list
+ * translated, ms[1] the density, ms[2] chemisputtering, ms[3] supernova_destruction, ms[4] the bookkeeping, the
+ * write-back and the outputs coming back.  Measurement aid.                                                        */
+int sphx_phase_last_timing(sphx_ctx* ctx, double ms[5]);
+/* The last sphx_step's neighbour list as (n,k) int64 in particle ids, rows in the order of upload, a missing entry n
+ * (nsc.neighbors' convention).  SPHX_E_STATE as sphx_state_dust_phase's first four.                                */
+int sphx_state_download_neighbors(sphx_ctx* ctx, int64_t* neighbor);
+/* mass (n), f_un (n,s), mu_array (n), gamma_array (n) as they are on the device, in the order of upload; any may be
+ * NULL.  SPHX_E_STATE: no state; f_un asked of a state uploaded without one.                                       */
+int sphx_state_download_composition(sphx_ctx* ctx, double* mass, double* f_un, double* mu_array, double* gamma_array);
+/* The per-particle drag coefficients (sphx_state_set_drag; refreshed by sphx_state_dust_phase) in the order of upload;
+ * either may be NULL.  SPHX_E_STATE: no state, or drag off.                                                        */
+int sphx_state_download_drag(sphx_ctx* ctx, double* mean_grain_mass, double* mean_cross);
 int sphx_get_stats(sphx_ctx* ctx, sphx_stats* out);
 int sphx_reset_stats(sphx_ctx* ctx);
 

@@ -102,6 +102,13 @@ SIGNATURES = {
     "sphx_chemisputtering_2": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _D, _I] + [_D] * 6 + [C.c_double, C.c_double] + [_D] * 4 +
                                          [C.c_double] * 3 + [_D, _D, _I]),
     "sphx_chem_last_timing": (C.c_int, [_P, _D]),
+    "sphx_dust_bookkeeping": (C.c_int, [_P, C.c_int64, C.c_int] + [_D] * 8 + [C.c_double] + [_D] * 5 + [_I]),
+    "sphx_state_dust_phase": (C.c_int, [_P, C.c_double, C.c_double] + [_D] * 5 + [C.c_double] * 5 + [c_int32_p, _D, _D, _D, C.c_int] +
+                                        [_D] * 7 + [_I, _I, _D, _I]),
+    "sphx_phase_last_timing": (C.c_int, [_P, _D]),
+    "sphx_state_download_neighbors": (C.c_int, [_P, _I]),
+    "sphx_state_download_composition": (C.c_int, [_P, _D, _D, _D, _D]),
+    "sphx_state_download_drag": (C.c_int, [_P, _D, _D]),
     "sphx_get_stats": (C.c_int, [_P, C.POINTER(SphxStats)]),
     "sphx_reset_stats": (C.c_int, [_P]),
     "sphx_set_stream": (C.c_int, [_P, C.c_void_p]),

@@ -789,3 +789,90 @@ def chem_last_timing():
     """Device time of the last chemisputtering_2 call of this module, from HIP events (include/sphx.h
     sphx_chem_last_timing) -> dict of ms: upload, rows, reverse, rounds, closing."""
     return _last_timing("sphx_chem_last_timing", ("upload", "rows", "reverse", "rounds", "closing"))
+
+
+# ==============================================================================================
+# The dust phase of the time loop: code_running.py:399-435
+# ==============================================================================================
+PHASE_TOTALS = ("mass_before", "mass_after_chem", "mass_after", "mass_reduction", "mass_increase", "mass_change")
+PHASE_COUNTS = ("masses_reset", "nan_filled")
+
+
+def dust_bookkeeping(mass, mu_array, f_un, frac_destruction, frac_reuptake, mass_before=None, mu_specie=None, gamma=None,
+                     crit_mass=None):
+    """drv:412-433 -> (mass, f_un, mu_array, gamma_array, totals).  mass and f_un are chemisputtering_2's outputs,
+    mu_array the one that went into the phase, the fractions supernova_destruction's.  totals: dict of the numbers the
+    driver prints (PHASE_TOTALS, in kg; mass_before is NaN unless the masses from before chemisputtering are given) and
+    the counts PHASE_COUNTS.  The tables and crit_mass default to the module's, read at call time.  include/sphx.h,
+    sphx_dust_bookkeeping, has the formulas and the quirks kept."""
+    fun = f64(f_un)
+    if fun.ndim != 2:
+        raise ValueError("f_un must be (N, S)")
+    n, S = fun.shape
+    m, mu = f64(mass, (n,)), f64(mu_array, (n,))
+    destr, reup = f64(frac_destruction, (n, S)), f64(frac_reuptake, (n, S))
+    mb = None if mass_before is None else f64(mass_before, (n,))
+    g = globals()
+    mus = chem_table(S, mu_specie, "mu_specie")
+    gam = chem_table(S, gamma, "gamma")
+    cm = float(g["crit_mass"] if crit_mass is None else crit_mass)
+    m_out = np.empty(n); f_out = np.empty((n, S)); mu_out = np.empty(n); g_out = np.empty(n)
+    tot = np.zeros(len(PHASE_TOTALS)); cnt = np.zeros(len(PHASE_COUNTS), dtype=np.int64)
+    c_ = context()
+    c_.check(c_.lib.sphx_dust_bookkeeping(c_.h, n, S, dp(m), dp(mu), dp(fun), dp(destr), dp(reup), dp(mb), dp(mus), dp(gam), cm,
+                                          dp(m_out), dp(f_out), dp(mu_out), dp(g_out), dp(tot), ip(cnt)))
+    totals = dict(zip(PHASE_TOTALS, (float(v) for v in tot)))
+    totals.update(zip(PHASE_COUNTS, (int(v) for v in cnt)))
+    return m_out, f_out, mu_out, g_out, totals
+
+
+def normalise_rows(f_un):
+    """drv:399 / drv:424: every row divided by its sum, the sum taken over the species one by one (the order the
+    resident call's kernel adds them in; np.sum pairs them differently from eight species on)."""
+    fun = f64(f_un)
+    tot = fun[:, 0].copy()
+    for t in range(1, fun.shape[1]):
+        tot = tot + fun[:, t]
+    return fun / tot[:, None]
+
+
+def dust_phase(points, velocities, neighbor, mass, f_un, mu_array, sizes, T, particle_type, d=None, dt=None, mu_specie=None,
+               gamma=None, mineral_densities=None, sputtering_yields=None, mrn_constants=None, crit_mass=None,
+               critical_density=None, species_curve=None, guard="count", full=False):
+    """The block code_running.py:399-435 as a chain of the array calls - density, chemisputtering_2,
+    supernova_destruction, dust_bookkeeping - on the caller's arrays and `neighbor` -> (mass, f_un, mu_array, gamma_array,
+    totals); full=True appends a dict of the stage outputs (density, mass_chem, f_un_chem, frac_destruction,
+    frac_reuptake, chem_counts, dust_counts).  dust_density and num_dens (drv:401-402) are dead in the block and are not
+    formed; cross_array and optical_depth (drv:434-435) are left to the caller.  Simulation.dust_phase is the same on the
+    resident state, bit for bit."""
+    m0 = f64(mass)
+    fun = normalise_rows(f_un)                                                         # drv:399
+    dens = density(points, m0, particle_type, neighbor, d=d)                           # drv:400
+    m1, f1, cc = chemisputtering_2(points, neighbor, m0, fun, mu_array, sizes, T, particle_type, d=d, dt=dt, mu_specie=mu_specie,
+                                   mineral_densities=mineral_densities, sputtering_yields=sputtering_yields,
+                                   mrn_constants=mrn_constants, full=True)             # drv:407-408
+    destr, reup, dc = supernova_destruction(points, velocities, neighbor, m1, f1, mu_array, sizes, dens, particle_type,
+                                            crit_mass=crit_mass, critical_density=critical_density, species_curve=species_curve,
+                                            guard=guard, full=True)                    # drv:411
+    out = dust_bookkeeping(m1, mu_array, f1, destr, reup, mass_before=m0, mu_specie=mu_specie, gamma=gamma, crit_mass=crit_mass)
+    if full:
+        return out + (dict(density=dens, mass_chem=m1, f_un_chem=f1, frac_destruction=destr, frac_reuptake=reup,
+                           chem_counts=cc, dust_counts=dc),)
+    return out
+
+
+def phase_tables(S, dt=None, mu_specie=None, gamma=None, mineral_densities=None, sputtering_yields=None, mrn_constants=None,
+                 crit_mass=None, critical_density=None, species_curve=None, guard="count"):
+    """The table and scalar arguments of sphx_state_dust_phase from the module's values, read at call time (what
+    dust_phase's stages read one by one) -> dict."""
+    if not isinstance(guard, str) or guard not in DUST_GUARDS:
+        raise ValueError("guard must be 'count' or 'fraction', not %r" % (guard,))
+    g = globals()
+    return dict(dt=float(g["dt"] if dt is None else dt), mu_specie=chem_table(S, mu_specie, "mu_specie"),
+                gamma=chem_table(S, gamma, "gamma"), mineral_densities=chem_table(S, mineral_densities, "mineral_densities"),
+                sputtering_yields=chem_table(S, sputtering_yields, "sputtering_yields"),
+                mrn=f64(g["mrn_constants"] if mrn_constants is None else mrn_constants, (2,)),
+                crit_mass=float(g["crit_mass"] if crit_mass is None else crit_mass),
+                critical_density=float(g["critical_density"] if critical_density is None else critical_density),
+                species_curve=dust_species_curve(S, species_curve), guard=DUST_GUARDS[guard],
+                knots=tuple(np.array(a, dtype=np.float64) for a in (DUST_KNOTS_V, DUST_KNOTS_C, DUST_KNOTS_SI)))

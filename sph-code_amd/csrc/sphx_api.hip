@@ -176,7 +176,7 @@ extern "C" void sphx_destroy(sphx_ctx* ctx) {
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (int i = 0; i < 10; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t, &ctx->chem_t})
+    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t, &ctx->chem_t, &ctx->phase_t})
         for (int i = 0; i < 6; ++i)
             if (t->ev[i]) (void)hipEventDestroy(t->ev[i]);
     for (int r = 0; r < 3; ++r)
@@ -281,6 +281,7 @@ extern "C" int sphx_rad_last_timing(sphx_ctx* ctx, double ms[4]) { return last_t
 extern "C" int sphx_cool_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::cool_t, ms); }
 extern "C" int sphx_dust_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::dust_t, ms); }
 extern "C" int sphx_chem_last_timing(sphx_ctx* ctx, double ms[5]) { return last_timing(ctx, &sphx_ctx::chem_t, ms); }
+extern "C" int sphx_phase_last_timing(sphx_ctx* ctx, double ms[5]) { return last_timing(ctx, &sphx_ctx::phase_t, ms); }
 
 // =============================================================================================
 // nsc.neighbors                                                                nsc:541-552
@@ -454,6 +455,7 @@ extern "C" int sphx_state_upload(sphx_ctx* ctx, int64_t n, int s, const double* 
     HIPCHK(hipMemsetAsync(ctx->badc.p, 0, (size_t)BADC_BUCKETS * BADC_STRIDE * sizeof(u64), ctx->stream));
     ctx->ct_primed = false;       // SC_CT_BITS was just zeroed: the next pass 2 must prime it again
     ctx->nbr_api_valid = false;
+    sphx_step_list_drop(ctx);
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->n = n;
     ctx->npad = sphx_pad64(n);
@@ -755,6 +757,7 @@ static int one_step(sphx_ctx* ctx, int k, double dist, int first, double fixed_d
     ctx->blob_split_valid = false;
     ctx->pass_part = 0;
     ctx->nbr_api_valid = false;   // the step overwrites the K-major list (search or Verlet refresh)
+    sphx_step_list_drop(ctx);
     if (rec0) HIPCHK(hipEventRecord(ev[0], ctx->stream));
     SPHX_TRY(step_search(ctx, k, dist, ev));
     HIPCHK(hipEventRecord(ev[2], ctx->stream));
@@ -842,6 +845,8 @@ extern "C" int sphx_step(sphx_ctx* ctx, int nsteps, int k, double dist, int firs
         ctx->ev_pending |= 1u << ring;
         SPHX_TRY(collect_stats(ctx, (ring + 1) % 3));  // two steps ago: finished long since, no wait
     }
+    // the list, its column order and the ids are this step's until something rewrites them (sphx_phase.hip reads them)
+    ctx->step_list_valid = true; ctx->step_qorder = ctx->qorder; ctx->step_list_n = ctx->n; ctx->step_list_k = k;
     if (per_call) HIPCHK(hipEventRecord(ctx->ev[9], ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->pinned->scal, ctx->scal.p, SC_NSLOTS * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -377,58 +377,101 @@ __global__ __launch_bounds__(CHEM_WG) void chem_final_kernel(int n, int s, const
 }
 
 // =====================================================================================================================
-// host side
+// host side: three parts (as sphx_rad.hip's rad_stage_host / rad_run) - the tables and the host inputs staged
+// (sphx_chem_tables, chem_stage_host), the run on device inputs (sphx_chem_run: sphx_state_dust_phase calls it on the
+// gathered resident state and leaves the outputs where they are), the outputs brought back.
 // =====================================================================================================================
 static bool chem_finite(double v) { return v - v == 0.0; }
 static size_t chem_up4(size_t v) { return (v + 3) & ~size_t(3); }
 
-extern "C" int sphx_chemisputtering_2(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const int64_t* neighbor,
-                                      const double* mass, const double* f_un, const double* mu, const double* sizes, const double* T,
-                                      const double* ptype, double d, double dt, const double* mu_specie, const double* mineral_densities,
-                                      const double* sputtering_yields, const double mrn[2], double k_B, double amu, double m_0,
-                                      double* mass_new, double* f_un_new, int64_t* counts) {
-    if (!ctx) return SPHX_E_ARG;
+// the range checks every caller shares: the shape, then (behind the callers' NULL checks) the scalars
+int sphx_chem_check_shape(sphx_ctx* ctx, const char* who, int64_t n, int k, int s) {
     if (n < 1 || k < 1 || k > 64 || s < CHEM_FIRST + 1 || s > SPHX_MAX_SPECIES)
-        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_chemisputtering_2: n=%lld, k=%d, s=%d (need n >= 1, 1 <= k <= 64, %d <= s <= %d)",
-                            (long long)n, k, s, CHEM_FIRST + 1, SPHX_MAX_SPECIES);
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld, k=%d, s=%d (need n >= 1, 1 <= k <= 64, %d <= s <= %d)", who, (long long)n, k, s,
+                            CHEM_FIRST + 1, SPHX_MAX_SPECIES);
     if (n > 0x7FFFFFF0ll || sphx_pad64(n) * (int64_t)k > 0x7FFFFFF0ll)
-        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_chemisputtering_2: n=%lld x k=%d out of range", (long long)n, k);
-    NEED(points); NEED(neighbor); NEED(mass); NEED(f_un); NEED(mu); NEED(sizes); NEED(T); NEED(ptype);
-    NEED(mu_specie); NEED(mineral_densities); NEED(sputtering_yields); NEED(mrn); NEED(mass_new); NEED(f_un_new);
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld x k=%d out of range", who, (long long)n, k);
+    return SPHX_OK;
+}
+int sphx_chem_check_scalars(sphx_ctx* ctx, const char* who, double d, double dt, const double mrn[2], double k_B, double amu,
+                            double m_0) {
     if (!chem_finite(d) || !chem_finite(dt) || !chem_finite(k_B) || !chem_finite(amu) || !chem_finite(m_0) || !chem_finite(mrn[0]) ||
         !chem_finite(mrn[1]))
-        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_chemisputtering_2: d=%g, dt=%g, k_B=%g, amu=%g, m_0=%g, mrn=(%g, %g) must be finite", d, dt,
-                            k_B, amu, m_0, mrn[0], mrn[1]);
-    // the tables: mu_specie | j0 | b | sputtering_yields, s entries each
-    double tab[4 * SPHX_MAX_SPECIES];
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: d=%g, dt=%g, k_B=%g, amu=%g, m_0=%g, mrn=(%g, %g) must be finite", who, d, dt, k_B, amu,
+                            m_0, mrn[0], mrn[1]);
+    return SPHX_OK;
+}
+
+// the tables mu_specie | j0 | b | sputtering_yields, s entries each, into ctx->chem_tab (held by the context: the upload reads it)
+int sphx_chem_tables(sphx_ctx* ctx, const char* who, int s, const double* mu_specie, const double* mineral_densities,
+                     const double* sputtering_yields, const double mrn[2], double amu, double* symax_out) {
+    double* tab = ctx->chem_tab;
     const double c0 = -(pow(mrn[1], -0.5) - pow(mrn[0], -0.5)) / (pow(mrn[1], 0.5) - pow(mrn[0], 0.5));   // nsc:1305
     double symax = sputtering_yields[0];
     for (int t = 0; t < s; ++t) {
         if (!chem_finite(mu_specie[t]) || !chem_finite(mineral_densities[t]) || !chem_finite(sputtering_yields[t]))
-            return sphx_set_err(ctx, SPHX_E_ARG, "sphx_chemisputtering_2: table entry %d must be finite", t);
+            return sphx_set_err(ctx, SPHX_E_ARG, "%s: table entry %d must be finite", who, t);
         tab[t] = mu_specie[t];
         tab[s + t] = c0 / (3.0 * mineral_densities[t]);
         tab[2 * s + t] = 2.0 * 3.141592653589793 * mu_specie[t] * amu;      // nsc:1306
         tab[3 * s + t] = sputtering_yields[t];
         if (sputtering_yields[t] > symax) symax = sputtering_yields[t];
     }
-    HIPCHK(hipSetDevice(ctx->device));
-    SPHX_TRY(ctx->chem_t.begin(ctx));
+    *symax_out = symax;
+    return SPHX_OK;
+}
+
+// ints per particle: nbr (k npad) | isd | ord | cnt | cur | start (n + 1 each, a multiple of four).  -> the K-major list's place
+int sphx_chem_ints(sphx_ctx* ctx, int64_t n, int k, int** nbr) {
+    const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), n1 = (nn + 4) & ~size_t(3);
+    SPHX_TRY(sphx_ensure(ctx, ctx->chem_int, ((size_t)k * npad + 5 * n1) * sizeof(int)));
+    *nbr = ctx->chem_int.as<int>();
+    return SPHX_OK;
+}
+
+// inputs in ctx->chem_in: points (3n) | mass | mu | sizes | T | ptype (n each) | f_un (n s) | the tables (4 s)
+int sphx_chem_inputs(sphx_ctx* ctx, int64_t n, int s, ChemDev* in) {
+    const size_t nn = (size_t)n, ns_ = nn * (size_t)s;
+    SPHX_TRY(sphx_ensure(ctx, ctx->chem_in, (8 * nn + ns_ + 4 * (size_t)s) * sizeof(double)));
+    double* p = ctx->chem_in.as<double>();
+    in->pos = p; in->m = p + 3 * nn; in->mu = p + 4 * nn; in->sizes = p + 5 * nn; in->T = p + 6 * nn; in->ptype = p + 7 * nn;
+    in->fun = p + 8 * nn; in->tab = p + 8 * nn + ns_;
+    return SPHX_OK;
+}
+
+// the host arrays and the (n,k) int64 list onto the device; the list into its K-major int32 form
+static int chem_stage_host(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const int64_t* neighbor, const double* mass,
+                           const double* f_un, const double* mu, const double* sizes, const double* T, const double* ptype,
+                           ChemDev* in, int** nbr_out) {
     hipStream_t st = ctx->stream;
     const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), ns_ = nn * (size_t)s, nk = nn * (size_t)k;
-    const int ns = s - CHEM_FIRST;
-    // ---- inputs: points (3n) | mass | mu | sizes | T | ptype (n each) | f_un (n s) | the tables (4 s); the list ----
-    SPHX_TRY(sphx_ensure(ctx, ctx->chem_in, (8 * nn + ns_ + 4 * (size_t)s) * sizeof(double)));
+    SPHX_TRY(sphx_chem_inputs(ctx, n, s, in));
     SPHX_TRY(sphx_ensure(ctx, ctx->chem_nb, nk * sizeof(int64_t)));
-    double* in = ctx->chem_in.as<double>();
-    double *d_pos = in, *d_m = in + 3 * nn, *d_mu = in + 4 * nn, *d_sz = in + 5 * nn, *d_T = in + 6 * nn, *d_pt = in + 7 * nn,
-           *d_fun = in + 8 * nn, *d_tab = in + 8 * nn + ns_;
-    std::memcpy(ctx->chem_tab, tab, sizeof(tab));                            // (held by the context: the upload below reads it)
-    const CopyF64 us[] = {{points, d_pos, 3 * nn}, {mass, d_m, nn}, {mu, d_mu, nn}, {sizes, d_sz, nn}, {T, d_T, nn}, {ptype, d_pt, nn},
-                          {f_un, d_fun, ns_}, {ctx->chem_tab, d_tab, 4 * (size_t)s}};
+    const CopyF64 us[] = {{points, in->pos, 3 * nn}, {mass, in->m, nn}, {mu, in->mu, nn}, {sizes, in->sizes, nn}, {T, in->T, nn},
+                          {ptype, in->ptype, nn}, {f_un, in->fun, ns_}, {ctx->chem_tab, in->tab, 4 * (size_t)s}};
     SPHX_TRY(sphx_upload_f64(ctx, us, 8));
     HIPCHK(hipMemcpyAsync(ctx->chem_nb.p, neighbor, nk * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    // ---- records, num0, the K-major list, the dust rows' ordinals ----
+    int* nbr;
+    SPHX_TRY(sphx_chem_ints(ctx, n, k, &nbr));
+    hipLaunchKernelGGL(chem_list_kernel, dim3((unsigned)((nk + CHEM_WG - 1) / CHEM_WG)), dim3(CHEM_WG), 0, st, (int)n, (int)npad, k,
+                       (const long long*)ctx->chem_nb.p, nbr);
+    HIPCHK(hipGetLastError());
+    *nbr_out = nbr;
+    return SPHX_OK;
+}
+
+// The middle part: everything between the inputs on the device (in; the K-major list nbr, which may lie anywhere) and
+// mass_new / f_un_new on the device (res).  t: the caller's stage timer, marks 1 .. 4 (NULL: none).  The counters 4 .. 7
+// are on their way into ctx->pinned->side.red when this returns: sphx_chem_counts after the caller's next synchronise.
+int sphx_chem_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const ChemDev& in, const int* nbr, const ChemPar& par,
+                  StageTimer* t, ChemRes* res) {
+    hipStream_t st = ctx->stream;
+    const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), ns_ = nn * (size_t)s;
+    const int ns = s - CHEM_FIRST;
+    const double *d_pos = in.pos, *d_m = in.m, *d_mu = in.mu, *d_sz = in.sizes, *d_T = in.T, *d_pt = in.ptype, *d_fun = in.fun,
+                 *d_tab = in.tab;
+    const double d = par.d;
+    // ---- records, num0, the dust rows' ordinals ----
     SPHX_TRY(sphx_ensure(ctx, ctx->chem_rec, nn * sizeof(ChemRec)));
     const size_t nchunk = (nn + CHEM_CHUNK - 1) / CHEM_CHUNK;
     // per particle: counters (CH_HEADER u64) | num0 (n s) | numfin (n s) | mass_new (n) | f_un_new (n s) | partial sums (2 nchunk s) | factors (2 s)
@@ -437,27 +480,26 @@ extern "C" int sphx_chemisputtering_2(sphx_ctx* ctx, int64_t n, int k, int s, co
     double *num0 = ctx->chem_out.as<double>() + CH_HEADER, *numfin = num0 + ns_, *d_mass = numfin + ns_, *d_fnew = d_mass + nn,
            *part = d_fnew + ns_, *fac = part + 2 * nchunk * (size_t)s;
     HIPCHK(hipMemsetAsync(d_cnt, 0, CH_HEADER * sizeof(double), st));
-    // ints: nbr (k npad) | isd | ord | cnt | cur | start (n + 1 each, a multiple of four)
+    // ints (sphx_chem_ints): isd | ord | cnt | cur | start behind the list's place
     const size_t n1 = (nn + 4) & ~size_t(3);
-    SPHX_TRY(sphx_ensure(ctx, ctx->chem_int, ((size_t)k * npad + 5 * n1) * sizeof(int)));
-    int* nbr = ctx->chem_int.as<int>();
-    int *isd = nbr + (size_t)k * npad, *ord = isd + n1, *cnt = ord + n1, *cur = cnt + n1, *start = cur + n1;
+    int* own;
+    SPHX_TRY(sphx_chem_ints(ctx, n, k, &own));
+    int *isd = own + (size_t)k * npad, *ord = isd + n1, *cnt = ord + n1, *cur = cnt + n1, *start = cur + n1;
     HIPCHK(hipMemsetAsync(isd, 0, 5 * n1 * sizeof(int), st));
     ChemPrep pa;
     pa.n = (int)n; pa.s = s; pa.pos = d_pos; pa.m = d_m; pa.mu = d_mu; pa.T = d_T; pa.ptype = d_pt; pa.fun = d_fun; pa.mus = d_tab;
-    pa.d = d; pa.m0 = m_0; pa.rec = ctx->chem_rec.as<ChemRec>(); pa.num0 = num0; pa.numfin = numfin; pa.isd = isd;
+    pa.d = d; pa.m0 = par.m_0; pa.rec = ctx->chem_rec.as<ChemRec>(); pa.num0 = num0; pa.numfin = numfin; pa.isd = isd;
     const unsigned nblk = (unsigned)((nn + CHEM_WG - 1) / CHEM_WG);
     hipLaunchKernelGGL(chem_prep_kernel, dim3(nblk), dim3(CHEM_WG), 0, st, pa);
-    hipLaunchKernelGGL(chem_list_kernel, dim3((unsigned)((nk + CHEM_WG - 1) / CHEM_WG)), dim3(CHEM_WG), 0, st, (int)n, (int)npad, k,
-                       (const long long*)ctx->chem_nb.p, nbr);
     HIPCHK(hipGetLastError());
     SPHX_TRY(sphx_excl_scan_int(ctx, isd, ord, (int)n));                 // (isd[n] = 0: the memset above; both start on 16-byte boundaries)
     HIPCHK(hipMemcpyAsync(&ctx->pinned->side.count, ord + n, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     const size_t nd = (size_t)ctx->pinned->side.count;
-    if (nd > nn) return sphx_set_err(ctx, SPHX_E_HIP, "sphx_chemisputtering_2: %zu dust rows of %zu particles", nd, nn);
-    SPHX_TRY(ctx->chem_t.mark(ctx, 1));
-    unsigned long long hc[CH_NCOUNT] = {0};
+    if (nd > nn) return sphx_set_err(ctx, SPHX_E_HIP, "%s: %zu dust rows of %zu particles", who, nd, nn);
+    if (t) SPHX_TRY(t->mark(ctx, 1));
+    unsigned long long* hc = res->hc;
+    for (int q = 0; q < CH_NCOUNT; ++q) hc[q] = 0;
     size_t M = 0;
     int64_t rounds = 0;
     if (nd > 0) {
@@ -475,7 +517,7 @@ extern "C" int sphx_chemisputtering_2(sphx_ctx* ctx, int64_t n, int k, int s, co
         HIPCHK(hipMemsetAsync(ra.dustid, 0, 2 * ndpad * sizeof(int), st));
         ra.rec = pa.rec; ra.fun = d_fun; ra.num0 = num0; ra.sizes = d_sz; ra.m = d_m;
         ra.tab.mu = d_tab; ra.tab.j0 = d_tab + s; ra.tab.b = d_tab + 2 * s; ra.tab.sy = d_tab + 3 * s;
-        ra.tab.symax = symax; ra.tab.kB = k_B; ra.tab.dt = dt;
+        ra.tab.symax = par.symax; ra.tab.kB = par.k_B; ra.tab.dt = par.dt;
         const double d2 = d * d, d4 = d2 * d2;
         ra.d9 = d4 * d4 * d;
         ra.wg = ctx->chem_row.as<double>(); ra.wk = ra.wg + (size_t)k * ndpad;
@@ -490,7 +532,7 @@ extern "C" int sphx_chemisputtering_2(sphx_ctx* ctx, int64_t n, int k, int s, co
         hipLaunchKernelGGL(chem_row_b_kernel, dim3(rblk), dim3(CHEM_WG), 0, st, ra);
         hipLaunchKernelGGL(chem_fold_kernel, dim3(1), dim3(64), 0, st, d_cnt, (int)CH_ROWS, 1);
         HIPCHK(hipGetLastError());
-        SPHX_TRY(ctx->chem_t.mark(ctx, 2));
+        if (t) SPHX_TRY(t->mark(ctx, 2));
         // ---- the reverse list: count, scan, fill, sort each slice, positions ----
         const unsigned eblk = (unsigned)(((size_t)k * ndpad + CHEM_WG - 1) / CHEM_WG);
         hipLaunchKernelGGL(chem_count_kernel, dim3(eblk), dim3(CHEM_WG), 0, st, ra, cnt);
@@ -501,7 +543,7 @@ extern "C" int sphx_chemisputtering_2(sphx_ctx* ctx, int64_t n, int k, int s, co
         HIPCHK(hipStreamSynchronize(st));
         M = (size_t)ctx->pinned->side.count;
         std::memcpy(hc + CH_ROWS - CH_ROWS % 4, ctx->pinned->side.red, 4 * sizeof(double));
-        if (M > (size_t)k * nd) return sphx_set_err(ctx, SPHX_E_HIP, "sphx_chemisputtering_2: reverse list of %zu entries from %zu pairs", M, (size_t)k * nd);
+        if (M > (size_t)k * nd) return sphx_set_err(ctx, SPHX_E_HIP, "%s: reverse list of %zu entries from %zu pairs", who, M, (size_t)k * nd);
         if (M > 0) {
             SPHX_TRY(sphx_ensure(ctx, ctx->chem_rev, 2 * (M + 4) * sizeof(int)));
             SPHX_TRY(sphx_ensure(ctx, ctx->chem_first, M * (size_t)ns * sizeof(double)));
@@ -517,7 +559,7 @@ extern "C" int sphx_chemisputtering_2(sphx_ctx* ctx, int64_t n, int k, int s, co
             HIPCHK(rocprim::segmented_radix_sort_keys(ctx->chem_tmp.p, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
             hipLaunchKernelGGL(chem_pos_kernel, dim3((unsigned)((M + CHEM_WG - 1) / CHEM_WG)), dim3(CHEM_WG), 0, st, (int)M, k, (int)ndpad, rev, pos);
             HIPCHK(hipGetLastError());
-            SPHX_TRY(ctx->chem_t.mark(ctx, 3));
+            if (t) SPHX_TRY(t->mark(ctx, 3));
             // ---- the rounds: until one changes no bit; (contributing rows + 1) always suffice ----
             ChemRound wa;
             wa.n = (int)n; wa.npad = (int)npad; wa.k = k; wa.s = s; wa.ns = ns; wa.nd = (int)nd; wa.ndpad = (int)ndpad;
@@ -540,28 +582,60 @@ extern "C" int sphx_chemisputtering_2(sphx_ctx* ctx, int64_t n, int k, int s, co
                 if (hc[CH_CHANGED] == 0 || rounds >= limit) break;
             }
         } else {
-            SPHX_TRY(ctx->chem_t.mark(ctx, 3));
+            if (t) SPHX_TRY(t->mark(ctx, 3));
         }
     } else {
-        SPHX_TRY(ctx->chem_t.mark(ctx, 2));
-        SPHX_TRY(ctx->chem_t.mark(ctx, 3));
+        if (t) SPHX_TRY(t->mark(ctx, 2));
+        if (t) SPHX_TRY(t->mark(ctx, 3));
     }
-    SPHX_TRY(ctx->chem_t.mark(ctx, 4));
+    if (t) SPHX_TRY(t->mark(ctx, 4));
     // ---- the closing correction, the outputs ----
     hipLaunchKernelGGL(chem_colsum_kernel, dim3((unsigned)((nchunk * (size_t)s + CHEM_WG - 1) / CHEM_WG)), dim3(CHEM_WG), 0, st, (int)n, s,
                        (int)nchunk, numfin, part);
     hipLaunchKernelGGL(chem_colfac_kernel, dim3((unsigned)s), dim3(CHEM_WG), 0, st, s, (int)nchunk, part, fac, d_cnt);
     hipLaunchKernelGGL(chem_final_kernel, dim3(nblk), dim3(CHEM_WG), 0, st, (int)n, s, numfin, fac, d_tab, d_mass, d_fnew);
     HIPCHK(hipGetLastError());
-    const CopyF64 ds[] = {{mass_new, d_mass, nn}, {f_un_new, d_fnew, ns_}};
-    SPHX_TRY(sphx_download_f64(ctx, ds, 2));
-    HIPCHK(hipMemcpyAsync(ctx->pinned->side.red, d_cnt + 4, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-    SPHX_TRY(ctx->chem_t.mark(ctx, 5));
-    HIPCHK(hipStreamSynchronize(st));
+    res->mass_new = d_mass; res->fun_new = d_fnew; res->M = M; res->rounds = rounds;
+    res->counters = d_cnt;
+    return SPHX_OK;
+}
+
+// counts[7] as sphx_chemisputtering_2 defines them; after the synchronise behind the copy of res.counters + 4 into
+// ctx->pinned->side.red
+void sphx_chem_counts(sphx_ctx* ctx, ChemRes* res, int64_t* counts) {
+    unsigned long long* hc = res->hc;
     std::memcpy(hc + 4, ctx->pinned->side.red, 4 * sizeof(double));
     if (counts) {
-        counts[0] = (int64_t)hc[CH_ROWS]; counts[1] = (int64_t)M; counts[2] = (int64_t)hc[CH_C1]; counts[3] = (int64_t)hc[CH_C2];
-        counts[4] = (int64_t)hc[CH_C3]; counts[5] = (int64_t)hc[CH_CORR]; counts[6] = rounds;
+        counts[0] = (int64_t)hc[CH_ROWS]; counts[1] = (int64_t)res->M; counts[2] = (int64_t)hc[CH_C1]; counts[3] = (int64_t)hc[CH_C2];
+        counts[4] = (int64_t)hc[CH_C3]; counts[5] = (int64_t)hc[CH_CORR]; counts[6] = res->rounds;
     }
+}
+
+extern "C" int sphx_chemisputtering_2(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const int64_t* neighbor,
+                                      const double* mass, const double* f_un, const double* mu, const double* sizes, const double* T,
+                                      const double* ptype, double d, double dt, const double* mu_specie, const double* mineral_densities,
+                                      const double* sputtering_yields, const double mrn[2], double k_B, double amu, double m_0,
+                                      double* mass_new, double* f_un_new, int64_t* counts) {
+    if (!ctx) return SPHX_E_ARG;
+    SPHX_TRY(sphx_chem_check_shape(ctx, "sphx_chemisputtering_2", n, k, s));
+    NEED(points); NEED(neighbor); NEED(mass); NEED(f_un); NEED(mu); NEED(sizes); NEED(T); NEED(ptype);
+    NEED(mu_specie); NEED(mineral_densities); NEED(sputtering_yields); NEED(mrn); NEED(mass_new); NEED(f_un_new);
+    SPHX_TRY(sphx_chem_check_scalars(ctx, "sphx_chemisputtering_2", d, dt, mrn, k_B, amu, m_0));
+    ChemPar par;
+    par.d = d; par.dt = dt; par.k_B = k_B; par.m_0 = m_0;
+    SPHX_TRY(sphx_chem_tables(ctx, "sphx_chemisputtering_2", s, mu_specie, mineral_densities, sputtering_yields, mrn, amu, &par.symax));
+    HIPCHK(hipSetDevice(ctx->device));
+    SPHX_TRY(ctx->chem_t.begin(ctx));
+    ChemDev in;
+    int* nbr;
+    SPHX_TRY(chem_stage_host(ctx, n, k, s, points, neighbor, mass, f_un, mu, sizes, T, ptype, &in, &nbr));
+    ChemRes res;
+    SPHX_TRY(sphx_chem_run(ctx, "sphx_chemisputtering_2", n, k, s, in, nbr, par, &ctx->chem_t, &res));
+    const CopyF64 ds[] = {{mass_new, res.mass_new, (size_t)n}, {f_un_new, res.fun_new, (size_t)n * (size_t)s}};
+    SPHX_TRY(sphx_download_f64(ctx, ds, 2));
+    HIPCHK(hipMemcpyAsync(ctx->pinned->side.red, res.counters + 4, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SPHX_TRY(ctx->chem_t.mark(ctx, 5));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    sphx_chem_counts(ctx, &res, counts);
     return ctx->chem_t.end(ctx);
 }

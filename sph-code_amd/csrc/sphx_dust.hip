@@ -59,16 +59,28 @@ __device__ __forceinline__ bool dust_is_pair(const double* __restrict__ ptype, i
     return p >= 0 && ptype[j] == 0.0 && ptype[p] == 2.0;
 }
 
-// entry e = (j, kk) of the (n,k) list
+// entry e of the list.  FROM64: e = (j, kk) of the (n,k) int64 list nb, whose K-major int32 form is written to nbr_out;
+// else e = (kk, j) of a K-major int32 list that exists already (nbr_in; sphx_state_dust_phase's)
+template <bool FROM64>
 __global__ __launch_bounds__(DUST_WG) void dust_list_kernel(int n, int npad, int k, const long long* __restrict__ nb,
-                                                            const double* __restrict__ ptype, const DustRec* __restrict__ rec,
-                                                            int* __restrict__ nbr, int* cnt, int* flag) {
+                                                            const int* __restrict__ nbr_in, const double* __restrict__ ptype,
+                                                            const DustRec* __restrict__ rec, int* __restrict__ nbr_out, int* cnt,
+                                                            int* flag) {
     const long long e = (long long)blockIdx.x * DUST_WG + threadIdx.x;
-    if (e >= (long long)n * k) return;
-    const int j = (int)(e / k), kk = (int)(e - (long long)j * k);
-    const long long q = nb[e];
-    const int p = (q >= 0 && q < n) ? (int)q : -1;
-    nbr[(size_t)kk * npad + j] = p;
+    int j, p;
+    if (FROM64) {
+        if (e >= (long long)n * k) return;
+        j = (int)(e / k);
+        const int kk = (int)(e - (long long)j * k);
+        const long long q = nb[e];
+        p = (q >= 0 && q < n) ? (int)q : -1;
+        nbr_out[(size_t)kk * npad + j] = p;
+    } else {
+        if (e >= (long long)npad * k) return;
+        j = (int)(e % npad);
+        if (j >= n) return;
+        p = nbr_in[e];
+    }
     if (dust_is_pair(ptype, j, p)) {
         atomicAdd(&cnt[p], 1);
         const DustRec r = rec[p];
@@ -193,91 +205,119 @@ __global__ __launch_bounds__(DUST_WG) void dust_row_kernel(DustWalk a) {
 }
 
 // =====================================================================================================================
-// host side
+// host side: three parts (as sphx_rad.hip's rad_stage_host / rad_run) - the parameters checked and the host inputs staged
+// (sphx_dust_params, dust_stage_host), the run on device inputs (sphx_dust_run: sphx_state_dust_phase calls it on the
+// gathered resident state and leaves the outputs where they are), the outputs brought back.
 // =====================================================================================================================
 static_assert(sizeof(DustKnots) <= 40 * sizeof(double), "sphx_ctx::dust_kn holds the knots");
 static bool dust_finite(double v) { return v - v == 0.0; }
 
-extern "C" int sphx_supernova_destruction(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const double* velocities,
-                                          const int64_t* neighbor, const double* mass, const double* f_un, const double* mu,
-                                          const double* sizes, const double* densities, const double* ptype, double crit_mass,
-                                          double critical_density, const int32_t* species_curve, const double knots_v[8],
-                                          const double knots_c[8], const double knots_si[8], int guard_mode,
-                                          double* frac_destruction, double* frac_reuptake, int64_t* counts) {
-    if (!ctx) return SPHX_E_ARG;
+int sphx_dust_check_shape(sphx_ctx* ctx, const char* who, int64_t n, int k, int s) {
     if (n < 1 || k < 1 || k > 64 || s < 1 || s > SPHX_MAX_SPECIES)
-        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: n=%lld, k=%d, s=%d (need n >= 1, 1 <= k <= 64, 1 <= s <= %d)",
-                            (long long)n, k, s, SPHX_MAX_SPECIES);
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld, k=%d, s=%d (need n >= 1, 1 <= k <= 64, 1 <= s <= %d)", who, (long long)n, k, s,
+                            SPHX_MAX_SPECIES);
     if (n > 0x7FFFFFF0ll || sphx_pad64(n) * (int64_t)k > 0x7FFFFFF0ll)
-        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: n=%lld x k=%d out of range", (long long)n, k);
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld x k=%d out of range", who, (long long)n, k);
+    return SPHX_OK;
+}
+int sphx_dust_check_scalars(sphx_ctx* ctx, const char* who, double crit_mass, double critical_density, int guard_mode) {
     if (!dust_finite(crit_mass) || !dust_finite(critical_density))
-        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: crit_mass=%g, critical_density=%g must be finite", crit_mass,
-                            critical_density);
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: crit_mass=%g, critical_density=%g must be finite", who, crit_mass, critical_density);
     if (guard_mode != SPHX_DUST_GUARD_COUNT && guard_mode != SPHX_DUST_GUARD_FRACTION)
-        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: unknown guard mode %d", guard_mode);
-    NEED(points); NEED(velocities); NEED(neighbor); NEED(mass); NEED(f_un); NEED(mu); NEED(sizes); NEED(densities); NEED(ptype);
-    NEED(species_curve); NEED(knots_v); NEED(knots_c); NEED(knots_si); NEED(frac_destruction); NEED(frac_reuptake);
-    DustWalk wa;
-    DustKnots& kn = *reinterpret_cast<DustKnots*>(ctx->dust_kn);      // (held by the context: the upload below reads it)
-    wa.sel = wa.si = 0;
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: unknown guard mode %d", who, guard_mode);
+    return SPHX_OK;
+}
+// the selector's bits into par; the knots and their slopes into ctx->dust_kn (held by the context: the upload reads it)
+int sphx_dust_params(sphx_ctx* ctx, const char* who, int s, double crit_mass, double critical_density, const int32_t* species_curve,
+                     const double knots_v[8], const double knots_c[8], const double knots_si[8], int guard_mode, DustPar* par) {
+    DustKnots& kn = *reinterpret_cast<DustKnots*>(ctx->dust_kn);
+    par->crit_mass = crit_mass; par->crit_density = critical_density;
+    par->fraction = guard_mode == SPHX_DUST_GUARD_FRACTION;
+    par->sel = par->si = 0;
     for (int t = 0; t < s; ++t) {
         if (species_curve[t] < 0 || species_curve[t] > 2)
-            return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: species_curve[%d]=%d (need 0, 1 or 2)", t, (int)species_curve[t]);
-        if (species_curve[t]) wa.sel |= 1u << t;
-        if (species_curve[t] == 2) wa.si |= 1u << t;
+            return sphx_set_err(ctx, SPHX_E_ARG, "%s: species_curve[%d]=%d (need 0, 1 or 2)", who, t, (int)species_curve[t]);
+        if (species_curve[t]) par->sel |= 1u << t;
+        if (species_curve[t] == 2) par->si |= 1u << t;
     }
     for (int t = 0; t < 8; ++t) {
         if (!dust_finite(knots_v[t]) || !dust_finite(knots_c[t]) || !dust_finite(knots_si[t]) || (t && !(knots_v[t] > knots_v[t - 1])))
-            return sphx_set_err(ctx, SPHX_E_ARG, "sphx_supernova_destruction: knot %d must be finite and knots_v increasing", t);
+            return sphx_set_err(ctx, SPHX_E_ARG, "%s: knot %d must be finite and knots_v increasing", who, t);
         kn.v[t] = knots_v[t]; kn.c[t] = knots_c[t]; kn.si[t] = knots_si[t];
     }
     for (int t = 0; t < 7; ++t) {
         kn.sc[t] = (knots_c[t + 1] - knots_c[t]) / (knots_v[t + 1] - knots_v[t]);
         kn.ssi[t] = (knots_si[t + 1] - knots_si[t]) / (knots_v[t + 1] - knots_v[t]);
     }
-    HIPCHK(hipSetDevice(ctx->device));
-    SPHX_TRY(ctx->dust_t.begin(ctx));
+    return SPHX_OK;
+}
+
+// inputs in ctx->dust_in: points, velocities (3n each) | mass | mu | sizes | densities | ptype (n each) | f_un (n s)
+int sphx_dust_inputs(sphx_ctx* ctx, int64_t n, int s, DustDev* in) {
+    const size_t nn = (size_t)n;
+    SPHX_TRY(sphx_ensure(ctx, ctx->dust_in, (11 * nn + nn * (size_t)s) * sizeof(double)));
+    double* p = ctx->dust_in.as<double>();
+    in->pos = p; in->vel = p + 3 * nn; in->m = p + 6 * nn; in->mu = p + 7 * nn; in->sizes = p + 8 * nn; in->dens = p + 9 * nn;
+    in->ptype = p + 10 * nn; in->fun = p + 11 * nn;
+    return SPHX_OK;
+}
+
+static int dust_stage_host(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const double* velocities,
+                           const int64_t* neighbor, const double* mass, const double* f_un, const double* mu, const double* sizes,
+                           const double* densities, const double* ptype, DustDev* in) {
+    const size_t nn = (size_t)n, ns = nn * (size_t)s, nk = nn * (size_t)k;
+    SPHX_TRY(sphx_dust_inputs(ctx, n, s, in));
+    SPHX_TRY(sphx_ensure(ctx, ctx->dust_nb, nk * sizeof(int64_t)));
+    const CopyF64 us[] = {{points, in->pos, 3 * nn}, {velocities, in->vel, 3 * nn}, {mass, in->m, nn}, {mu, in->mu, nn}, {sizes, in->sizes, nn},
+                          {densities, in->dens, nn}, {ptype, in->ptype, nn}, {f_un, in->fun, ns}};
+    SPHX_TRY(sphx_upload_f64(ctx, us, 8));
+    HIPCHK(hipMemcpyAsync(ctx->dust_nb.p, neighbor, nk * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    return SPHX_OK;
+}
+
+// The middle part: everything between the inputs on the device and frac_destruction / frac_reuptake / the five counters
+// on the device (res).  nbr: a K-major int32 list that exists already, or NULL: the (n,k) int64 list in ctx->dust_nb, whose
+// K-major form is made on the way.  t: the caller's stage timer, marks 1 .. 3 (NULL: none).
+int sphx_dust_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const DustDev& in, const int* nbr_given, const DustPar& par,
+                  StageTimer* t, DustRes* res) {
     hipStream_t st = ctx->stream;
     const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), ns = nn * (size_t)s, nk = nn * (size_t)k;
-    // ---- inputs: points, velocities (3n each) | mass | mu | sizes | densities | ptype (n each) | f_un (n s); the list ----
-    SPHX_TRY(sphx_ensure(ctx, ctx->dust_in, (11 * nn + ns) * sizeof(double)));
-    SPHX_TRY(sphx_ensure(ctx, ctx->dust_nb, nk * sizeof(int64_t)));
-    double* in = ctx->dust_in.as<double>();
-    double *d_pos = in, *d_vel = in + 3 * nn, *d_m = in + 6 * nn, *d_mu = in + 7 * nn, *d_sz = in + 8 * nn, *d_dens = in + 9 * nn,
-           *d_pt = in + 10 * nn, *d_fun = in + 11 * nn;
-    const CopyF64 us[] = {{points, d_pos, 3 * nn}, {velocities, d_vel, 3 * nn}, {mass, d_m, nn}, {mu, d_mu, nn}, {sizes, d_sz, nn},
-                          {densities, d_dens, nn}, {ptype, d_pt, nn}, {f_un, d_fun, ns}};
-    SPHX_TRY(sphx_upload_f64(ctx, us, 8));
-    HIPCHK(hipMemcpyAsync(ctx->dust_nb.p, neighbor, nk * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    const DustKnots& kn = *reinterpret_cast<const DustKnots*>(ctx->dust_kn);
+    const double *d_pt = in.ptype;
     // ---- records; the K-major list, the rows' flags, the counts ----
     SPHX_TRY(sphx_ensure(ctx, ctx->dust_rec, nn * sizeof(DustRec)));
     // ints: nbr (k npad) | cnt (n + 1) | cur (n + 1) | flag (n + 1) | start (n + 1) | msk (k npad), each part a multiple of four
     const size_t n1 = (nn + 4) & ~size_t(3);
     SPHX_TRY(sphx_ensure(ctx, ctx->dust_int, (2 * (size_t)k * npad + 4 * n1) * sizeof(int)));
-    int* nbr = ctx->dust_int.as<int>();
-    int *cnt = nbr + (size_t)k * npad, *cur = cnt + n1, *flag = cur + n1, *start = flag + n1;
+    int* own = ctx->dust_int.as<int>();
+    int *cnt = own + (size_t)k * npad, *cur = cnt + n1, *flag = cur + n1, *start = flag + n1;
     unsigned* msk = (unsigned*)(start + n1);
+    const int* nbr = nbr_given ? nbr_given : own;
     HIPCHK(hipMemsetAsync(cnt, 0, 3 * n1 * sizeof(int), st));
     // outputs: counters (8 u64) | the knots (40 doubles) | frac_destruction (n s) | frac_reuptake (n s)
     SPHX_TRY(sphx_ensure(ctx, ctx->dust_out, (48 + 2 * ns) * sizeof(double)));
     HIPCHK(hipMemsetAsync(ctx->dust_out.p, 0, 8 * sizeof(double), st));
     HIPCHK(hipMemcpyAsync(ctx->dust_out.as<double>() + 8, &kn, sizeof(DustKnots), hipMemcpyHostToDevice, st));
     DustPrep pa;
-    pa.n = (int)n; pa.pos = d_pos; pa.vel = d_vel; pa.m = d_m; pa.mu = d_mu; pa.sizes = d_sz;
-    pa.crit_mass = crit_mass; pa.amu = ctx->cst.amu;
+    pa.n = (int)n; pa.pos = in.pos; pa.vel = in.vel; pa.m = in.m; pa.mu = in.mu; pa.sizes = in.sizes;
+    pa.crit_mass = par.crit_mass; pa.amu = par.amu;
     pa.rec = ctx->dust_rec.as<DustRec>();
     const unsigned nblk = (unsigned)((nn + DUST_WG - 1) / DUST_WG);
     hipLaunchKernelGGL(dust_prep_kernel, dim3(nblk), dim3(DUST_WG), 0, st, pa);
-    hipLaunchKernelGGL(dust_list_kernel, dim3((unsigned)((nk + DUST_WG - 1) / DUST_WG)), dim3(DUST_WG), 0, st, (int)n, (int)npad, k,
-                       (const long long*)ctx->dust_nb.p, d_pt, pa.rec, nbr, cnt, flag);
+    if (nbr_given)
+        hipLaunchKernelGGL(dust_list_kernel<false>, dim3((unsigned)(((size_t)k * npad + DUST_WG - 1) / DUST_WG)), dim3(DUST_WG), 0, st, (int)n,
+                           (int)npad, k, (const long long*)nullptr, nbr, d_pt, pa.rec, (int*)nullptr, cnt, flag);
+    else
+        hipLaunchKernelGGL(dust_list_kernel<true>, dim3((unsigned)((nk + DUST_WG - 1) / DUST_WG)), dim3(DUST_WG), 0, st, (int)n, (int)npad, k,
+                           (const long long*)ctx->dust_nb.p, (const int*)nullptr, d_pt, pa.rec, own, cnt, flag);
     HIPCHK(hipGetLastError());
-    SPHX_TRY(ctx->dust_t.mark(ctx, 1));
+    if (t) SPHX_TRY(t->mark(ctx, 1));
     // ---- the reverse list: scan, fill, sort each slice ----
     SPHX_TRY(sphx_excl_scan_int(ctx, cnt, start, (int)n));             // (cnt[n] = 0: the memset above; both start on 16-byte boundaries)
     HIPCHK(hipMemcpyAsync(&ctx->pinned->side.count, start + n, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     const size_t M = (size_t)ctx->pinned->side.count;
-    if (M > nk) return sphx_set_err(ctx, SPHX_E_HIP, "sphx_supernova_destruction: reverse list of %zu entries from %zu pairs", M, nk);
+    if (M > nk) return sphx_set_err(ctx, SPHX_E_HIP, "%s: reverse list of %zu entries from %zu pairs", who, M, nk);
     SPHX_TRY(sphx_ensure(ctx, ctx->dust_rev, 2 * (M + 4) * sizeof(int)));
     int* rev_raw = ctx->dust_rev.as<int>();
     int* rev = rev_raw + M + 4;
@@ -292,25 +332,53 @@ extern "C" int sphx_supernova_destruction(sphx_ctx* ctx, int64_t n, int k, int s
         SPHX_TRY(sphx_ensure(ctx, ctx->dust_tmp, sort_bytes + 64));
         HIPCHK(rocprim::segmented_radix_sort_keys(ctx->dust_tmp.p, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
     }
-    SPHX_TRY(ctx->dust_t.mark(ctx, 2));
+    if (t) SPHX_TRY(t->mark(ctx, 2));
     // ---- the dust pass, then the row pass ----
+    DustWalk wa;
+    wa.sel = par.sel; wa.si = par.si;
     wa.n = (int)n; wa.npad = (int)npad; wa.k = k; wa.s = s;
-    wa.fraction = guard_mode == SPHX_DUST_GUARD_FRACTION;
+    wa.fraction = par.fraction;
     wa.start = start; wa.rev = rev; wa.nbr = nbr; wa.flag = flag; wa.rec = pa.rec;
-    wa.dens = d_dens; wa.fun = d_fun; wa.ptype = d_pt;
-    wa.crit_density = critical_density;
+    wa.dens = in.dens; wa.fun = in.fun; wa.ptype = d_pt;
+    wa.crit_density = par.crit_density;
     wa.msk = msk;
     wa.counts = (unsigned long long*)ctx->dust_out.p;
     wa.kn = reinterpret_cast<const DustKnots*>(ctx->dust_out.as<double>() + 8);
     wa.destr = ctx->dust_out.as<double>() + 48; wa.reup = wa.destr + ns;
     hipLaunchKernelGGL(dust_pass_kernel, dim3(nblk), dim3(DUST_WG), 0, st, wa);
     HIPCHK(hipGetLastError());
-    SPHX_TRY(ctx->dust_t.mark(ctx, 3));
+    if (t) SPHX_TRY(t->mark(ctx, 3));
     hipLaunchKernelGGL(dust_row_kernel, dim3(nblk), dim3(DUST_WG), 0, st, wa);
     HIPCHK(hipGetLastError());
-    const CopyF64 ds[] = {{frac_destruction, wa.destr, ns}, {frac_reuptake, wa.reup, ns}, {counts, wa.counts, DUST_NCOUNT}};
+    res->destr = wa.destr; res->reup = wa.reup; res->counters = wa.counts;
+    return SPHX_OK;
+}
+
+extern "C" int sphx_supernova_destruction(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const double* velocities,
+                                          const int64_t* neighbor, const double* mass, const double* f_un, const double* mu,
+                                          const double* sizes, const double* densities, const double* ptype, double crit_mass,
+                                          double critical_density, const int32_t* species_curve, const double knots_v[8],
+                                          const double knots_c[8], const double knots_si[8], int guard_mode,
+                                          double* frac_destruction, double* frac_reuptake, int64_t* counts) {
+    if (!ctx) return SPHX_E_ARG;
+    SPHX_TRY(sphx_dust_check_shape(ctx, "sphx_supernova_destruction", n, k, s));
+    SPHX_TRY(sphx_dust_check_scalars(ctx, "sphx_supernova_destruction", crit_mass, critical_density, guard_mode));
+    NEED(points); NEED(velocities); NEED(neighbor); NEED(mass); NEED(f_un); NEED(mu); NEED(sizes); NEED(densities); NEED(ptype);
+    NEED(species_curve); NEED(knots_v); NEED(knots_c); NEED(knots_si); NEED(frac_destruction); NEED(frac_reuptake);
+    DustPar par;
+    SPHX_TRY(sphx_dust_params(ctx, "sphx_supernova_destruction", s, crit_mass, critical_density, species_curve, knots_v, knots_c, knots_si,
+                              guard_mode, &par));
+    par.amu = ctx->cst.amu;
+    HIPCHK(hipSetDevice(ctx->device));
+    SPHX_TRY(ctx->dust_t.begin(ctx));
+    DustDev in;
+    SPHX_TRY(dust_stage_host(ctx, n, k, s, points, velocities, neighbor, mass, f_un, mu, sizes, densities, ptype, &in));
+    DustRes res;
+    SPHX_TRY(sphx_dust_run(ctx, "sphx_supernova_destruction", n, k, s, in, nullptr, par, &ctx->dust_t, &res));
+    const size_t ns = (size_t)n * (size_t)s;
+    const CopyF64 ds[] = {{frac_destruction, res.destr, ns}, {frac_reuptake, res.reup, ns}, {counts, res.counters, DUST_NCOUNT}};
     SPHX_TRY(sphx_download_f64(ctx, ds, 3));
     SPHX_TRY(ctx->dust_t.mark(ctx, 4));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return ctx->dust_t.end(ctx);
 }

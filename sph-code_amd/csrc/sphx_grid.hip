@@ -1092,6 +1092,7 @@ int sphx_build_blob_order(sphx_ctx* ctx, int64_t n, bool defer_scatter) {
     BlobBits b;
     const int bits = blob_code_space(ctx, g, &b);
     ctx->qorder = nullptr;
+    sphx_step_list_drop(ctx);            // (porder is rewritten)
     ctx->order_by_count = false;
     if (bits > BLOB_MAX_BITS) {
         if (ctx->cells_unsorted) {

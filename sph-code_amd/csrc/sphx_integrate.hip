@@ -94,6 +94,7 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherArgs a) {
 int sphx_permute_state(sphx_ctx* ctx, int64_t n, bool split, hipEvent_t after_first) {
     StateArrays& a = ctx->st;
     StateArrays& b = ctx->alt;
+    sphx_step_list_drop(ctx);            // (the ids move, and porder with a pending scatter)
     // (the search's arrays first)
     DevBuf* src[] = {&a.x, &a.y, &a.z, &a.hprev, &a.vx, &a.vy, &a.vz, &a.ax, &a.ay, &a.az,
                      &a.m, &a.T, &a.mu, &a.gam, &a.E, &a.ptype};

@@ -147,7 +147,7 @@ struct StateArrays {
 };
 
 // The stage timer of a side call (the arb, rad, cool, dust and chem entry points): events on ctx->stream around its stages -
-// four of them, five for chem.  (sphx_api.hip; a call that returns between begin and end leaves ms zeroed)
+// four of them, five for chem and the dust phase.  (sphx_api.hip; a call that returns between begin and end leaves ms zeroed)
 struct StageTimer {
     int stages = 4;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // created on first use
@@ -231,6 +231,15 @@ struct sphx_ctx {
     bool nbr_api_valid = false;
     int64_t nbr_api_n = 0;
     int nbr_api_k = 0;
+    // The last sphx_step's own list, for the calls that read it BETWEEN steps (sphx_phase.hip): ctx->nbr, the order of its
+    // columns (step_qorder: a copy of qorder as the step left it - other entry points reset qorder itself) and st.id are
+    // still what that step wrote.  Set at the end of sphx_step; dropped (sphx_step_list_drop) by everything that rewrites
+    // one of the three: sphx_knn with a K-major output, sphx_transpose_nbr, sphx_build_blob_order, sphx_permute_state,
+    // sphx_state_upload.
+    bool step_list_valid = false;
+    const int* step_qorder = nullptr;
+    int64_t step_list_n = 0;
+    int step_list_k = 0;
     // ---- Verlet refresh (sphx_refresh.hip) ----
     bool list_valid = false;
     int64_t list_n = 0;
@@ -411,6 +420,14 @@ struct sphx_ctx {
     // events of a call: [0] start, [1] inputs on the device, records and list built, [2] row passes done, [3] reverse list
     // sorted, [4] rounds done, [5] closing correction done and outputs on the host (sphx_chem_last_timing)
     StageTimer chem_t{5};
+    // the dust phase on the resident state (sphx_phase.hip): ints (column of a caller id | dense rows scratch), doubles (the
+    // loop-form density, the bookkeeping's outputs and per-particle terms, the chunks' partial sums, the totals).  The
+    // gathered inputs go straight into chem_in / dust_in, the translated list into chem_int.
+    DevBuf phase_int, phase_out;
+    double phase_tab[4 * SPHX_MAX_SPECIES] = {0};   // mu_specie | gamma | grain_mass | sigma_effective on the host, uploaded from here
+    // events of a call: [0] start, [1] state gathered and list translated, [2] density, [3] chem, [4] dust, [5] bookkeeping
+    // done, state written back and totals on the host (sphx_phase_last_timing)
+    StageTimer phase_t{5};
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
@@ -448,6 +465,7 @@ void sphx_release(sphx_ctx* ctx, DevBuf& b);      // frees b's allocation now (t
         if (r_ != SPHX_OK) return r_;                                                        \
     } while (0)
 
+static inline void sphx_step_list_drop(sphx_ctx* ctx) { ctx->step_list_valid = false; ctx->step_qorder = nullptr; }
 static inline int64_t sphx_pad64(int64_t n) { return (n + 63) & ~int64_t(63); }
 
 // XCD-aware block remap: workgroups are dealt round-robin over the 8 XCDs (block b runs on
@@ -705,6 +723,33 @@ int sphx_species_on(sphx_ctx* ctx, int64_t n, int k, int S, int SP, const double
 int sphx_agb_table_set(sphx_ctx* ctx, int S, int nspl, const int32_t* ntx, const int32_t* nty, const double* tx, const double* ty,
                        const double* coeffs, const int32_t* mapto, double divisor, const double* mu_specie, double solar_mass);
 int sphx_transpose_nbr(sphx_ctx* ctx, int64_t n, int k, const int64_t* nb_rowmajor);
+
+// the loop-form density (nsc:693-702) on device inputs: points (n,3), the K-major list (sphx_loopforms.hip; sphx_density's kernel)
+int sphx_loop_density_dev(sphx_ctx* ctx, int64_t n, int k, const int* nbr, const double* points, const double* mass,
+                          const double* ptype, double d, double m_0, double* out);
+// ---- the middle parts of chemisputtering_2 and supernova_destruction, on device inputs (sphx_chem.hip, sphx_dust.hip) ----
+struct ChemDev { double *pos, *m, *mu, *sizes, *T, *ptype, *fun, *tab; };       // (n,3), (n,) x 5, (n,s), the tables (4 s)
+struct ChemPar { double d, dt, k_B, m_0, symax; };
+struct ChemRes { double *mass_new, *fun_new; unsigned long long* counters; unsigned long long hc[8]; size_t M; int64_t rounds; };
+int sphx_chem_check_shape(sphx_ctx* ctx, const char* who, int64_t n, int k, int s);
+int sphx_chem_check_scalars(sphx_ctx* ctx, const char* who, double d, double dt, const double mrn[2], double k_B, double amu, double m_0);
+int sphx_chem_tables(sphx_ctx* ctx, const char* who, int s, const double* mu_specie, const double* mineral_densities,
+                     const double* sputtering_yields, const double mrn[2], double amu, double* symax_out);
+int sphx_chem_ints(sphx_ctx* ctx, int64_t n, int k, int** nbr);
+int sphx_chem_inputs(sphx_ctx* ctx, int64_t n, int s, ChemDev* in);
+int sphx_chem_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const ChemDev& in, const int* nbr, const ChemPar& par,
+                  StageTimer* t, ChemRes* res);
+void sphx_chem_counts(sphx_ctx* ctx, ChemRes* res, int64_t* counts);
+struct DustDev { double *pos, *vel, *m, *mu, *sizes, *dens, *ptype, *fun; };    // (n,3) x 2, (n,) x 5, (n,s)
+struct DustPar { double crit_mass, crit_density, amu; unsigned sel, si; int fraction; };
+struct DustRes { double *destr, *reup; unsigned long long* counters; };
+int sphx_dust_check_shape(sphx_ctx* ctx, const char* who, int64_t n, int k, int s);
+int sphx_dust_check_scalars(sphx_ctx* ctx, const char* who, double crit_mass, double critical_density, int guard_mode);
+int sphx_dust_params(sphx_ctx* ctx, const char* who, int s, double crit_mass, double critical_density, const int32_t* species_curve,
+                     const double knots_v[8], const double knots_c[8], const double knots_si[8], int guard_mode, DustPar* par);
+int sphx_dust_inputs(sphx_ctx* ctx, int64_t n, int s, DustDev* in);
+int sphx_dust_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const DustDev& in, const int* nbr_given, const DustPar& par,
+                  StageTimer* t, DustRes* res);
 
 // integrate / layout helpers (sphx_integrate.hip)
 int sphx_clamp(sphx_ctx* ctx, int64_t n, StateArrays& s);

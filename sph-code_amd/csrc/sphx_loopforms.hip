@@ -222,6 +222,18 @@ extern "C" int sphx_density(sphx_ctx* ctx, int64_t n, int k, const double* point
     return down(ctx, out, a.out1, (size_t)n * sizeof(double));
 }
 
+int sphx_loop_density_dev(sphx_ctx* ctx, int64_t n, int k, const int* nbr, const double* points, const double* mass,
+                          const double* ptype, double d, double m_0, double* out) {
+    LoopArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = (int)n; a.npad = (int)sphx_pad64(n); a.k = k;
+    a.nbr = nbr; a.pos = points; a.m = mass; a.pt = ptype;
+    a.d = d; a.m0 = m_0;
+    a.out1 = out;
+    LAUNCH1(loop_density_kernel<0>);
+    return SPHX_OK;
+}
+
 extern "C" int sphx_dust_density(sphx_ctx* ctx, int64_t n, int k, const double* points, const double* mass,
                                  const int64_t* neighbor, const double* particle_type,
                                  const double* sizes, double* out) {

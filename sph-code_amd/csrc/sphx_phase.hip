@@ -1,0 +1,467 @@
+// sphx_phase.hip - the dust phase of the reference's time loop, code_running.py:399-435, on the resident state
+// (sphx_state_dust_phase), its bookkeeping as an array call (sphx_dust_bookkeeping), and the two downloads that go with
+// them (sphx_state_download_neighbors, sphx_state_download_composition).
+//
+// The block, statement by statement:
+//   drv:399      f_un rows divided by their sums                                     phase_normalise_kernel
+//   drv:400      the loop-form density (nsc:693-702) on the current positions, the pre-phase mass, the list and d
+//                                                                                    sphx_loop_density_dev (sphx_density's kernel)
+//   drv:401-402  dust_density and num_dens: dead in the block (nothing below reads them) - not formed
+//   drv:407-408  chemisputtering_2 on (points, list, mass, normalised f_un, pre-phase mu, sizes, T, ptype)   sphx_chem_run
+//   drv:411      supernova_destruction on (points, velocities, list, post-chem mass and f_un, pre-phase mu, sizes, the
+//                density of drv:400, ptype)                                          sphx_dust_run
+//   drv:412-433  the bookkeeping                                                      phase_book_kernel + the chunked sums
+//   drv:434-435  cross_array and optical_depth feed rad_heating alone - not kept
+// THE LIST IS THE LAST STEP'S OWN (ctx->nbr: int32, K-major, storage slots, -1 = missing), translated to caller ids
+// through st.id (sphx_phase_map.h).  That is what the driver does: at drv:407 `neighbor` is the list drv:437 made in the
+// previous pass of the loop, and drv:481 has moved the positions since - the list is one update older than the points.
+// `sizes` is st.hprev, as sphx_state_rad_transfer takes it.  Everything is gathered into the caller's particle order
+// (the order of upload), in which the two ordered stages then run their rows ascending: the bits are those of the array
+// calls on the downloaded state.  Only st.m, st.mu, st.gam (with drag: st.mgm, st.mcs) and the composition rows fun_id
+// are written.  Writing st alone is enough: the next step's first act on the state is the permutation st -> alt
+// (sphx_permute_state), which overwrites every array of alt before the two swap, and every mass-derived quantity the step
+// reads - the gather records, the loop-form records with h(m), the tree's sort - is rebuilt from st by that step.
+// Sums over particles: per chunk of 256 in index order, then the chunks by one workgroup in a fixed order
+// (chem_colsum_kernel's scheme).  No floating-point atomic anywhere.  Vector stores from plain C++ only.  Every operation
+// separately rounded; double where the driver has longdouble.
+#include "sphx_internal.h"
+#include "sphx_phase_map.h"
+#include <cstring>
+#pragma clang fp contract(off)
+
+#define PHASE_WG 256
+#define PHASE_CHUNK 256
+// per-particle terms of the totals
+enum { PQ_MPRE = 0, PQ_MCHEM, PQ_MFIN, PQ_RED, PQ_INC, PQ_CHG, PQ_RESET, PQ_FILL, PQ_N };
+
+// ---- the state into caller order; the column of every caller id ----
+struct PhaseGather {
+    int n;
+    const int *qorder, *id;
+    const double *x, *y, *z, *vx, *vy, *vz, *m, *mu, *h, *T, *pt;
+    int* col;
+    double *pos, *vel, *om, *omu, *oh, *oT, *opt;
+};
+__global__ __launch_bounds__(PHASE_WG) void phase_gather_kernel(PhaseGather a) {
+    const int p = blockIdx.x * PHASE_WG + threadIdx.x;
+    if (p >= a.n) return;
+    const int j = sphx_phase_slot(a.qorder, p);
+    const int i = a.id[j];
+    sphx_phase_col_lane(a.qorder, a.id, p, a.col);           // (col[i] = p: the header's rule, replayed on the host)
+    a.pos[3 * (size_t)i] = a.x[j]; a.pos[3 * (size_t)i + 1] = a.y[j]; a.pos[3 * (size_t)i + 2] = a.z[j];
+    a.vel[3 * (size_t)i] = a.vx[j]; a.vel[3 * (size_t)i + 1] = a.vy[j]; a.vel[3 * (size_t)i + 2] = a.vz[j];
+    a.om[i] = a.m[j]; a.omu[i] = a.mu[j]; a.oh[i] = a.h[j]; a.oT[i] = a.T[j]; a.opt[i] = a.pt[j];
+}
+__global__ __launch_bounds__(PHASE_WG) void phase_col_kernel(int n, const int* __restrict__ qorder, const int* __restrict__ id, int* col) {
+    const int p = blockIdx.x * PHASE_WG + threadIdx.x;
+    if (p < n) sphx_phase_col_lane(qorder, id, p, col);
+}
+// lane e = (kk, i), i fastest: coalesced stores
+__global__ __launch_bounds__(PHASE_WG) void phase_list_kernel(int n, int npad, int k, const int* __restrict__ nbr, const int* __restrict__ id,
+                                                              const int* __restrict__ col, int* __restrict__ out) {
+    const long long e = (long long)blockIdx.x * PHASE_WG + threadIdx.x;
+    if (e >= (long long)k * npad) return;
+    const int kk = (int)(e / npad), i = (int)(e - (long long)kk * npad);
+    out[e] = sphx_phase_entry(nbr, id, col, n, npad, kk, i);
+}
+__global__ __launch_bounds__(PHASE_WG) void phase_list64_kernel(int n, int npad, int k, const int* __restrict__ list, long long* __restrict__ out) {
+    const long long e = (long long)blockIdx.x * PHASE_WG + threadIdx.x;
+    if (e < (long long)n * k) out[e] = sphx_phase_entry64(list, n, npad, k, e);
+}
+
+// drv:399: the rows of fun_id (sp doubles apart) divided by their sums, into dense rows of s
+__global__ __launch_bounds__(PHASE_WG) void phase_normalise_kernel(int n, int s, int sp, const double* __restrict__ fun_id, double* __restrict__ out) {
+    const int i = blockIdx.x * PHASE_WG + threadIdx.x;
+    if (i >= n) return;
+    const double* f = fun_id + (size_t)i * sp;
+    double tot = f[0];
+    for (int t = 1; t < s; ++t) tot += f[t];
+    for (int t = 0; t < s; ++t) out[(size_t)i * s + t] = f[t] / tot;
+}
+
+// np.sum over a contiguous row of s < 128 values term(0) .. term(s - 1), in NumPy's order (eight running sums over the
+// whole blocks of eight, combined pairwise, then the rest one by one): what Simulation forms mean_grain_mass and
+// mean_cross with
+template <class Term>
+__device__ __forceinline__ double phase_np_sum(int s, Term term) {
+    if (s < 8) {
+        double res = 0.0;
+        for (int t = 0; t < s; ++t) res += term(t);
+        return res;
+    }
+    double r0 = term(0), r1 = term(1), r2 = term(2), r3 = term(3), r4 = term(4), r5 = term(5), r6 = term(6), r7 = term(7);
+    int t = 8;
+    for (; t < s - (s % 8); t += 8) {
+        r0 += term(t); r1 += term(t + 1); r2 += term(t + 2); r3 += term(t + 3);
+        r4 += term(t + 4); r5 += term(t + 5); r6 += term(t + 6); r7 += term(t + 7);
+    }
+    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+    for (; t < s; ++t) res += term(t);
+    return res;
+}
+
+// ---- drv:412-433, one particle per lane ----
+struct PhaseBook {
+    int n, s, so;                                    // so: doubles between two rows of f_out
+    const double *m, *mu, *f, *destr, *reup;         // post-chem mass, pre-phase mu, post-chem f_un (n,s), the fractions (n,s)
+    const double* m_before;                          // pre-phase mass for the totals (nullable)
+    const double *mus, *gam;                         // mu_specie, gamma (s each)
+    const double *gm, *se;                           // grain_mass, sigma_effective (s each; nullable: no drag terms)
+    double crit_mass;
+    double *m_out, *f_out, *mu_out, *gam_out, *mgm_out, *mcs_out;
+    double* pp;                                      // (PQ_N, n): the totals' per-particle terms
+};
+__global__ __launch_bounds__(PHASE_WG) void phase_book_kernel(PhaseBook a) {
+    const int i = blockIdx.x * PHASE_WG + threadIdx.x;
+    if (i >= a.n) return;
+    const size_t n = (size_t)a.n;
+    const double mi = a.m[i];
+    const double r = mi / a.mu[i];                                           // mass / mu_array                  drv:412
+    const double *de = a.destr + (size_t)i * a.s, *re = a.reup + (size_t)i * a.s, *f = a.f + (size_t)i * a.s;
+    double* fo = a.f_out + (size_t)i * a.so;
+    double red = 0.0, inc = 0.0, chg = 0.0, tot = 0.0;
+    int fills = 0;
+    for (int t = 0; t < a.s; ++t) {
+        const double mst = a.mus[t];
+        const double dn = sphx_nan_to_num(-de[t] + re[t]);                   // drv:416
+        const double tr = r * de[t] * mst, ti = r * re[t] * mst, tc = r * dn * mst;
+        red = t ? red + tr : tr; inc = t ? inc + ti : ti; chg = t ? chg + tc : tc;   // drv:412, 413, 417
+        double v = f[t] + dn;                                                // drv:421
+        if (v != v) { v = 1e-15; ++fills; }                                  // drv:423
+        fo[t] = v;
+        tot = t ? tot + v : v;
+    }
+    chg = sphx_nan_to_num(chg);                                              // drv:417
+    double smu = 0.0, sg = 0.0, sf = 0.0;
+    for (int t = 0; t < a.s; ++t) {
+        const double v = fo[t] / tot;                                        // drv:424
+        fo[t] = v;
+        const double tm = v * a.mus[t], tg = v * a.gam[t];
+        smu = t ? smu + tm : tm; sg = t ? sg + tg : tg; sf = t ? sf + v : v;
+    }
+    double mo = mi + chg;                                                    // drv:425
+    const bool reset = mo < 0.0;
+    if (reset) mo = a.crit_mass / 200.;                                      // drv:431
+    a.m_out[i] = mo;
+    a.mu_out[i] = smu / sf;                                                  // drv:432
+    a.gam_out[i] = sg / sf;                                                  // drv:433
+    if (a.gm) {                                                              // nsc:720-726, as Simulation forms them
+        a.mgm_out[i] = phase_np_sum(a.s, [&](int t) { return a.gm[t] * fo[t]; });
+        a.mcs_out[i] = phase_np_sum(a.s, [&](int t) { return a.se[t] * fo[t]; });
+    }
+    a.pp[PQ_MPRE * n + i] = a.m_before ? a.m_before[i] : 0.0;
+    a.pp[PQ_MCHEM * n + i] = mi; a.pp[PQ_MFIN * n + i] = mo;
+    a.pp[PQ_RED * n + i] = red; a.pp[PQ_INC * n + i] = inc; a.pp[PQ_CHG * n + i] = chg;
+    a.pp[PQ_RESET * n + i] = reset ? 1.0 : 0.0; a.pp[PQ_FILL * n + i] = (double)fills;
+}
+// lane t = (quantity q, chunk c): the chunk's sum in index order
+__global__ __launch_bounds__(PHASE_WG) void phase_chunksum_kernel(int n, int nchunk, const double* __restrict__ pp, double* __restrict__ part) {
+    const int t = blockIdx.x * PHASE_WG + threadIdx.x;
+    if (t >= PQ_N * nchunk) return;
+    const int q = t / nchunk, c = t - q * nchunk;
+    const int i1 = min(n, (c + 1) * PHASE_CHUNK);
+    double sum = 0.0;
+    for (int i = c * PHASE_CHUNK; i < i1; ++i) sum += pp[(size_t)q * n + i];
+    part[t] = sum;
+}
+// one workgroup per quantity: lane l adds the chunks l, l + PHASE_WG, ... in order, then a tree over the lanes
+__global__ __launch_bounds__(PHASE_WG) void phase_total_kernel(int nchunk, const double* __restrict__ part, double* __restrict__ tot) {
+    __shared__ double sm[PHASE_WG];
+    const int q = blockIdx.x, l = threadIdx.x;
+    double sum = 0.0;
+    for (int c = l; c < nchunk; c += PHASE_WG) sum += part[(size_t)q * nchunk + c];
+    sm[l] = sum;
+    __syncthreads();
+    for (int h = PHASE_WG / 2; h > 0; h >>= 1) {
+        if (l < h) sm[l] += sm[l + h];
+        __syncthreads();
+    }
+    if (l == 0) tot[q] = sm[0];
+}
+
+// the new mass, mu, gamma (and drag coefficients) from caller order back into the storage slots
+struct PhaseBack { int n; const int* id; const double* in[5]; double* out[5]; int narr; };
+__global__ __launch_bounds__(PHASE_WG) void phase_back_kernel(PhaseBack a) {
+    const int j = blockIdx.x * PHASE_WG + threadIdx.x;
+    if (j >= a.n) return;
+    const int i = a.id[j];
+    for (int q = 0; q < a.narr; ++q) a.out[q][j] = a.in[q][i];
+}
+
+// =====================================================================================================================
+// host side
+// =====================================================================================================================
+static bool phase_finite(double v) { return v - v == 0.0; }
+static unsigned phase_blocks(size_t lanes) { return (unsigned)((lanes + PHASE_WG - 1) / PHASE_WG); }
+
+// ctx->phase_out (doubles): density (n) | m_out | mu_out | gam_out | mgm | mcs (n each) | f_out (n s) | pp (PQ_N n) |
+// part (PQ_N nchunk) | totals (PQ_N) | tables mus, gam, gm, se (s each)
+struct PhaseOut { double *dens, *m, *mu, *gam, *mgm, *mcs, *f, *pp, *part, *tot, *tab; size_t nchunk; };
+static int phase_out(sphx_ctx* ctx, int64_t n, int s, PhaseOut* o) {
+    const size_t nn = (size_t)n, nchunk = (nn + PHASE_CHUNK - 1) / PHASE_CHUNK;
+    SPHX_TRY(sphx_ensure(ctx, ctx->phase_out, (6 * nn + nn * (size_t)s + PQ_N * nn + PQ_N * nchunk + PQ_N + 4 * (size_t)s) * sizeof(double)));
+    double* p = ctx->phase_out.as<double>();
+    o->dens = p; o->m = p + nn; o->mu = p + 2 * nn; o->gam = p + 3 * nn; o->mgm = p + 4 * nn; o->mcs = p + 5 * nn;
+    o->f = p + 6 * nn; o->pp = o->f + nn * (size_t)s; o->part = o->pp + PQ_N * nn; o->tot = o->part + PQ_N * nchunk;
+    o->tab = o->tot + PQ_N;
+    o->nchunk = nchunk;
+    return SPHX_OK;
+}
+
+// the bookkeeping kernel and the sums behind it; the totals' copy to the host is queued (phase_totals reads it after a synchronise)
+static int phase_book_run(sphx_ctx* ctx, PhaseBook a, const PhaseOut& o) {
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(phase_book_kernel, dim3(phase_blocks((size_t)a.n)), dim3(PHASE_WG), 0, st, a);
+    hipLaunchKernelGGL(phase_chunksum_kernel, dim3(phase_blocks(PQ_N * o.nchunk)), dim3(PHASE_WG), 0, st, a.n, (int)o.nchunk, a.pp, o.part);
+    hipLaunchKernelGGL(phase_total_kernel, dim3(PQ_N), dim3(PHASE_WG), 0, st, (int)o.nchunk, o.part, o.tot);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ctx->pinned->scal, o.tot, PQ_N * sizeof(double), hipMemcpyDeviceToHost, st));
+    return SPHX_OK;
+}
+static void phase_totals(sphx_ctx* ctx, bool has_before, double* totals, int64_t* counts) {
+    double t[PQ_N];
+    std::memcpy(t, ctx->pinned->scal, sizeof(t));
+    if (totals) {
+        totals[0] = has_before ? t[PQ_MPRE] : NAN; totals[1] = t[PQ_MCHEM]; totals[2] = t[PQ_MFIN];
+        totals[3] = -t[PQ_RED]; totals[4] = t[PQ_INC]; totals[5] = t[PQ_CHG];       // drv:412: mass_reduction carries the sign
+    }
+    if (counts) { counts[0] = (int64_t)t[PQ_RESET]; counts[1] = (int64_t)t[PQ_FILL]; }
+}
+static_assert(PQ_N <= SC_NSLOTS, "the totals fit the pinned scalar block");
+
+extern "C" int sphx_dust_bookkeeping(sphx_ctx* ctx, int64_t n, int s, const double* mass, const double* mu_array, const double* f_un,
+                                     const double* frac_destruction, const double* frac_reuptake, const double* mass_before,
+                                     const double* mu_specie, const double* gamma_specie, double crit_mass, double* mass_out,
+                                     double* f_un_out, double* mu_out, double* gamma_out, double* totals, int64_t* counts) {
+    if (!ctx) return SPHX_E_ARG;
+    if (n < 1 || n > 0x7FFFFFF0ll || s < 1 || s > SPHX_MAX_SPECIES)
+        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dust_bookkeeping: n=%lld, s=%d (need n >= 1, 1 <= s <= %d)", (long long)n, s, SPHX_MAX_SPECIES);
+    if (!phase_finite(crit_mass)) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dust_bookkeeping: crit_mass=%g must be finite", crit_mass);
+    NEED(mass); NEED(mu_array); NEED(f_un); NEED(frac_destruction); NEED(frac_reuptake); NEED(mu_specie); NEED(gamma_specie);
+    NEED(mass_out); NEED(f_un_out); NEED(mu_out); NEED(gamma_out);
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n, ns = nn * (size_t)s;
+    PhaseOut o;
+    SPHX_TRY(phase_out(ctx, n, s, &o));
+    // inputs in ctx->chem_in: mass | mu | mass_before (n each) | f_un | destr | reup (n s each)
+    SPHX_TRY(sphx_ensure(ctx, ctx->chem_in, (3 * nn + 3 * ns) * sizeof(double)));
+    double* in = ctx->chem_in.as<double>();
+    double *d_m = in, *d_mu = in + nn, *d_mb = in + 2 * nn, *d_f = in + 3 * nn, *d_de = d_f + ns, *d_re = d_de + ns;
+    std::memcpy(ctx->phase_tab, mu_specie, (size_t)s * sizeof(double));       // (held by the context: the upload reads it)
+    std::memcpy(ctx->phase_tab + s, gamma_specie, (size_t)s * sizeof(double));
+    const CopyF64 us[] = {{mass, d_m, nn}, {mu_array, d_mu, nn}, {mass_before, d_mb, nn}, {f_un, d_f, ns}, {frac_destruction, d_de, ns},
+                          {frac_reuptake, d_re, ns}, {ctx->phase_tab, o.tab, 2 * (size_t)s}};
+    SPHX_TRY(sphx_upload_f64(ctx, us, 7));
+    PhaseBook a;
+    a.n = (int)n; a.s = s; a.so = s;
+    a.m = d_m; a.mu = d_mu; a.f = d_f; a.destr = d_de; a.reup = d_re; a.m_before = mass_before ? d_mb : nullptr;
+    a.mus = o.tab; a.gam = o.tab + s; a.gm = nullptr; a.se = nullptr;
+    a.crit_mass = crit_mass;
+    a.m_out = o.m; a.f_out = o.f; a.mu_out = o.mu; a.gam_out = o.gam; a.mgm_out = nullptr; a.mcs_out = nullptr;
+    a.pp = o.pp;
+    SPHX_TRY(phase_book_run(ctx, a, o));
+    const CopyF64 ds[] = {{mass_out, o.m, nn}, {f_un_out, o.f, ns}, {mu_out, o.mu, nn}, {gamma_out, o.gam, nn}};
+    SPHX_TRY(sphx_download_f64(ctx, ds, 4));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    phase_totals(ctx, mass_before != nullptr, totals, counts);
+    return SPHX_OK;
+}
+
+// what both resident calls need: a state that has stepped, whose list is still the step's
+static int phase_need_list(sphx_ctx* ctx, const char* who) {
+    if (!ctx->has_state) return sphx_set_err(ctx, SPHX_E_STATE, "%s: no state uploaded", who);
+    if (ctx->step_count < 1)
+        return sphx_set_err(ctx, SPHX_E_STATE, "%s before the first sphx_step: the list and sizes do not exist yet", who);
+    if (ctx->use_verlet)
+        return sphx_set_err(ctx, SPHX_E_STATE, "%s: not with incremental search (the refreshed lists are not the driver's list)", who);
+    // (step_list_valid, not nbr_api_valid or qorder: other entry points reset those without touching the list, or touch
+    //  the list and have the flag cleared again by a later search)
+    if (!ctx->step_list_valid || ctx->step_list_n != ctx->n || ctx->step_list_k != ctx->k || !ctx->nbr.p || ctx->k < 1)
+        return sphx_set_err(ctx, SPHX_E_STATE, "%s: the last step's list is gone (a call on this context has overwritten it since)", who);
+    return SPHX_OK;
+}
+// col (n ints) and the caller-order K-major list (k npad ints) into `list`
+static int phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list) {
+    const int64_t n = ctx->n;
+    const int k = ctx->k, npad = (int)sphx_pad64(n);
+    const int* id = ctx->st.id.as<int>();
+    if (!col_done) hipLaunchKernelGGL(phase_col_kernel, dim3(phase_blocks((size_t)n)), dim3(PHASE_WG), 0, ctx->stream, (int)n, ctx->step_qorder, id, col);
+    hipLaunchKernelGGL(phase_list_kernel, dim3(phase_blocks((size_t)k * npad)), dim3(PHASE_WG), 0, ctx->stream, (int)n, npad, k,
+                       ctx->nbr.as<int>(), id, col, list);
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
+}
+
+extern "C" int sphx_state_download_neighbors(sphx_ctx* ctx, int64_t* neighbor) {
+    if (!ctx) return SPHX_E_ARG;
+    SPHX_TRY(phase_need_list(ctx, "sphx_state_download_neighbors"));
+    NEED(neighbor);
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t n = ctx->n;
+    const int k = ctx->k;
+    const size_t npad = (size_t)sphx_pad64(n), nk = (size_t)n * (size_t)k;
+    SPHX_TRY(sphx_ensure(ctx, ctx->phase_int, (npad + (size_t)k * npad) * sizeof(int)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->idx64, nk * sizeof(int64_t)));
+    int* col = ctx->phase_int.as<int>();
+    int* list = col + npad;
+    SPHX_TRY(phase_translate(ctx, col, false, list));
+    hipLaunchKernelGGL(phase_list64_kernel, dim3(phase_blocks(nk)), dim3(PHASE_WG), 0, ctx->stream, (int)n, (int)npad, k, list,
+                       (long long*)ctx->idx64.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(neighbor, ctx->idx64.p, nk * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SPHX_OK;
+}
+
+extern "C" int sphx_state_download_composition(sphx_ctx* ctx, double* mass, double* f_un, double* mu_array, double* gamma_array) {
+    if (!ctx) return SPHX_E_ARG;
+    if (!ctx->has_state) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_state_download_composition: no state uploaded");
+    if (f_un && (ctx->s < 1 || !ctx->fun_id.p))
+        return sphx_set_err(ctx, SPHX_E_STATE, "sphx_state_download_composition: the state carries no composition (f_un)");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t n = ctx->n;
+    const size_t nb = (size_t)n * sizeof(double);
+    const StateArrays& s = ctx->st;
+    SPHX_TRY(sphx_ensure(ctx, ctx->out_a, nb));
+    double* stage = ctx->out_a.as<double>();
+    struct V1 { double* host; const double* dev; };
+    const V1 v1[] = {{mass, s.m.as<double>()}, {mu_array, s.mu.as<double>()}, {gamma_array, s.gam.as<double>()}};
+    for (const V1& v : v1) {
+        if (!v.host) continue;
+        SPHX_TRY(sphx_scatter_rows_by_id(ctx, n, 1, s.id.as<int>(), v.dev, stage));
+        HIPCHK(hipMemcpyAsync(v.host, stage, nb, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    if (f_un) {                                      // the rows are in upload order already; the padding stays behind
+        HIPCHK(hipMemcpy2DAsync(f_un, (size_t)ctx->s * sizeof(double), ctx->fun_id.p, (size_t)ctx->sp * sizeof(double),
+                                (size_t)ctx->s * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    return SPHX_OK;
+}
+
+extern "C" int sphx_state_download_drag(sphx_ctx* ctx, double* mean_grain_mass, double* mean_cross) {
+    if (!ctx) return SPHX_E_ARG;
+    if (!ctx->has_state || !ctx->drag) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_state_download_drag: no state with drag on");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t n = ctx->n;
+    const size_t nb = (size_t)n * sizeof(double);
+    SPHX_TRY(sphx_ensure(ctx, ctx->out_a, nb));
+    double* stage = ctx->out_a.as<double>();
+    struct V1 { double* host; const double* dev; };
+    const V1 v1[] = {{mean_grain_mass, ctx->st.mgm.as<double>()}, {mean_cross, ctx->st.mcs.as<double>()}};
+    for (const V1& v : v1) {
+        if (!v.host) continue;
+        SPHX_TRY(sphx_scatter_rows_by_id(ctx, n, 1, ctx->st.id.as<int>(), v.dev, stage));
+        HIPCHK(hipMemcpyAsync(v.host, stage, nb, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    return SPHX_OK;
+}
+
+extern "C" int sphx_state_dust_phase(sphx_ctx* ctx, double dt, double d, const double* mu_specie, const double* gamma_specie,
+                                     const double* mineral_densities, const double* sputtering_yields, const double mrn[2], double k_B,
+                                     double amu, double m_0, double crit_mass, double critical_density, const int32_t* species_curve,
+                                     const double knots_v[8], const double knots_c[8], const double knots_si[8], int guard_mode,
+                                     const double* grain_mass, const double* sigma_effective, double* density, double* mass_chem,
+                                     double* f_un_chem, double* frac_destruction, double* frac_reuptake, int64_t* chem_counts,
+                                     int64_t* dust_counts, double* totals, int64_t* book_counts) {
+    if (!ctx) return SPHX_E_ARG;
+    const char* who = "sphx_state_dust_phase";
+    SPHX_TRY(phase_need_list(ctx, who));
+    if (ctx->s < 7 || !ctx->fun_id.p)
+        return sphx_set_err(ctx, SPHX_E_STATE, "%s: the state carries no composition (f_un) of >= 7 species", who);
+    if (ctx->drag && (!grain_mass || !sigma_effective))
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: drag is on: the per-species tables grain_mass and sigma_effective are needed to refresh "
+                                               "mean_grain_mass and mean_cross", who);
+    const int64_t n = ctx->n;
+    const int k = ctx->k, s = ctx->s, sp = ctx->sp;
+    NEED(mu_specie); NEED(gamma_specie); NEED(mineral_densities); NEED(sputtering_yields); NEED(mrn);
+    NEED(species_curve); NEED(knots_v); NEED(knots_c); NEED(knots_si);
+    SPHX_TRY(sphx_chem_check_shape(ctx, who, n, k, s));
+    SPHX_TRY(sphx_chem_check_scalars(ctx, who, d, dt, mrn, k_B, amu, m_0));
+    SPHX_TRY(sphx_dust_check_scalars(ctx, who, crit_mass, critical_density, guard_mode));
+    for (int t = 0; t < s; ++t)
+        if (!phase_finite(gamma_specie[t]) || (ctx->drag && (!phase_finite(grain_mass[t]) || !phase_finite(sigma_effective[t]))))
+            return sphx_set_err(ctx, SPHX_E_ARG, "%s: table entry %d must be finite", who, t);
+    ChemPar cpar;
+    cpar.d = d; cpar.dt = dt; cpar.k_B = k_B; cpar.m_0 = m_0;
+    SPHX_TRY(sphx_chem_tables(ctx, who, s, mu_specie, mineral_densities, sputtering_yields, mrn, amu, &cpar.symax));
+    DustPar dpar;
+    SPHX_TRY(sphx_dust_params(ctx, who, s, crit_mass, critical_density, species_curve, knots_v, knots_c, knots_si, guard_mode, &dpar));
+    dpar.amu = amu;
+    HIPCHK(hipSetDevice(ctx->device));
+    SPHX_TRY(ctx->phase_t.begin(ctx));
+    hipStream_t stream = ctx->stream;
+    const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), ns = nn * (size_t)s;
+    // ---- the state into caller order (straight into the stages' input buffers), the list into caller ids ----
+    ChemDev cin;
+    DustDev din;
+    int* list;
+    PhaseOut o;
+    SPHX_TRY(sphx_chem_inputs(ctx, n, s, &cin));
+    SPHX_TRY(sphx_dust_inputs(ctx, n, s, &din));
+    SPHX_TRY(sphx_chem_ints(ctx, n, k, &list));
+    SPHX_TRY(phase_out(ctx, n, s, &o));
+    SPHX_TRY(sphx_ensure(ctx, ctx->phase_int, (npad + (size_t)k * npad) * sizeof(int)));
+    int* col = ctx->phase_int.as<int>();
+    const StateArrays& st = ctx->st;
+    PhaseGather ga;
+    ga.n = (int)n; ga.qorder = ctx->step_qorder; ga.id = st.id.as<int>();
+    ga.x = st.x.as<double>(); ga.y = st.y.as<double>(); ga.z = st.z.as<double>();
+    ga.vx = st.vx.as<double>(); ga.vy = st.vy.as<double>(); ga.vz = st.vz.as<double>();
+    ga.m = st.m.as<double>(); ga.mu = st.mu.as<double>(); ga.h = st.hprev.as<double>(); ga.T = st.T.as<double>(); ga.pt = st.ptype.as<double>();
+    ga.col = col; ga.pos = cin.pos; ga.vel = din.vel; ga.om = cin.m; ga.omu = cin.mu; ga.oh = cin.sizes; ga.oT = cin.T; ga.opt = cin.ptype;
+    hipLaunchKernelGGL(phase_gather_kernel, dim3(phase_blocks(nn)), dim3(PHASE_WG), 0, stream, ga);
+    hipLaunchKernelGGL(phase_normalise_kernel, dim3(phase_blocks(nn)), dim3(PHASE_WG), 0, stream, (int)n, s, sp, ctx->fun_id.as<double>(), cin.fun);
+    HIPCHK(hipGetLastError());
+    SPHX_TRY(phase_translate(ctx, col, true, list));
+    // the tables: chem's four (ctx->chem_tab) beside its inputs; mu_specie | gamma | grain_mass | sigma_effective in phase_out
+    double* ptab = ctx->phase_tab;                   // (held by the context: the upload below reads it)
+    for (int t = 0; t < s; ++t) {
+        ptab[t] = mu_specie[t]; ptab[s + t] = gamma_specie[t];
+        ptab[2 * s + t] = ctx->drag ? grain_mass[t] : 0.0; ptab[3 * s + t] = ctx->drag ? sigma_effective[t] : 0.0;
+    }
+    HIPCHK(hipMemcpyAsync(cin.tab, ctx->chem_tab, 4 * (size_t)s * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(o.tab, ptab, 4 * (size_t)s * sizeof(double), hipMemcpyHostToDevice, stream));
+    SPHX_TRY(ctx->phase_t.mark(ctx, 1));
+    // ---- drv:400 ----
+    SPHX_TRY(sphx_loop_density_dev(ctx, n, k, list, cin.pos, cin.m, cin.ptype, d, m_0, o.dens));
+    SPHX_TRY(ctx->phase_t.mark(ctx, 2));
+    // ---- drv:407-408 ----
+    ChemRes cres;
+    SPHX_TRY(sphx_chem_run(ctx, who, n, k, s, cin, list, cpar, nullptr, &cres));
+    HIPCHK(hipMemcpyAsync(ctx->pinned->side.red, cres.counters + 4, 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    SPHX_TRY(ctx->phase_t.mark(ctx, 3));
+    HIPCHK(hipStreamSynchronize(stream));
+    sphx_chem_counts(ctx, &cres, chem_counts);
+    // ---- drv:411 ----
+    din.pos = cin.pos; din.m = cres.mass_new; din.mu = cin.mu; din.sizes = cin.sizes; din.dens = o.dens; din.ptype = cin.ptype;
+    din.fun = cres.fun_new;
+    DustRes dres;
+    SPHX_TRY(sphx_dust_run(ctx, who, n, k, s, din, list, dpar, nullptr, &dres));
+    SPHX_TRY(ctx->phase_t.mark(ctx, 4));
+    // ---- drv:412-433; the composition rows straight into fun_id ----
+    PhaseBook a;
+    a.n = (int)n; a.s = s; a.so = sp;
+    a.m = cres.mass_new; a.mu = cin.mu; a.f = cres.fun_new; a.destr = dres.destr; a.reup = dres.reup; a.m_before = cin.m;
+    a.mus = o.tab; a.gam = o.tab + s; a.gm = ctx->drag ? o.tab + 2 * s : nullptr; a.se = ctx->drag ? o.tab + 3 * s : nullptr;
+    a.crit_mass = crit_mass;
+    a.m_out = o.m; a.f_out = ctx->fun_id.as<double>(); a.mu_out = o.mu; a.gam_out = o.gam; a.mgm_out = o.mgm; a.mcs_out = o.mcs;
+    a.pp = o.pp;
+    SPHX_TRY(phase_book_run(ctx, a, o));
+    PhaseBack ba;
+    ba.n = (int)n; ba.id = st.id.as<int>(); ba.narr = ctx->drag ? 5 : 3;
+    const double* from[5] = {o.m, o.mu, o.gam, o.mgm, o.mcs};
+    double* to[5] = {st.m.as<double>(), st.mu.as<double>(), st.gam.as<double>(), st.mgm.as<double>(), st.mcs.as<double>()};
+    for (int q = 0; q < 5; ++q) { ba.in[q] = from[q]; ba.out[q] = to[q]; }
+    hipLaunchKernelGGL(phase_back_kernel, dim3(phase_blocks(nn)), dim3(PHASE_WG), 0, stream, ba);
+    HIPCHK(hipGetLastError());
+    const CopyF64 ds[] = {{density, o.dens, nn}, {mass_chem, cres.mass_new, nn}, {f_un_chem, cres.fun_new, ns}, {frac_destruction, dres.destr, ns},
+                          {frac_reuptake, dres.reup, ns}, {dust_counts, dres.counters, 5}};
+    SPHX_TRY(sphx_download_f64(ctx, ds, 6));
+    SPHX_TRY(ctx->phase_t.mark(ctx, 5));
+    HIPCHK(hipStreamSynchronize(stream));
+    phase_totals(ctx, true, totals, book_counts);
+    return ctx->phase_t.end(ctx);
+}

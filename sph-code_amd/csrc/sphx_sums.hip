@@ -101,6 +101,7 @@ __global__ __launch_bounds__(256) void transpose_nbr_kernel(long long n, int k, 
 
 int sphx_transpose_nbr(sphx_ctx* ctx, int64_t n, int k, const int64_t* nb_dev) {
     int64_t npad = sphx_pad64(n);
+    sphx_step_list_drop(ctx);
     SPHX_TRY(sphx_ensure(ctx, ctx->nbr, (size_t)k * npad * sizeof(int)));
     HIPCHK(hipMemsetAsync(ctx->nbr.p, 0xFF, (size_t)k * npad * sizeof(int), ctx->stream));
     long long tot = (long long)n * k;

@@ -40,6 +40,8 @@ class Simulation:
         self.k = int(n_neigh)
         self.dist = 0.0 if dist is None or not np.isfinite(dist) else float(dist)
         self.first = True
+        self._phase_ran = False          # a dust_phase has rewritten mass, f_un, mu_array, gamma_array on the device
+        self._with_drag = bool(with_drag)
         pts = f64(state["points"])
         n = pts.shape[0]
         self.n = n
@@ -224,12 +226,91 @@ class Simulation:
         c.check(c.lib.sphx_state_download_species(c.h, dp(out["f_un_neighbor"]), dp(Z), dp(A)))
         return out
 
+    # ---- the dust phase of the time loop (code_running.py:399-435) on the resident state ----------------------------
+    def neighbors(self):
+        """The last step's neighbour list -> (N, K) int64 in the particle order of the uploaded state, a missing entry N
+        (compat.neighbors' convention).  It is the list of the positions the step started from: the driver's `neighbor`
+        at drv:407.  After the first step; not with incremental=True."""
+        out = np.empty((self.n, self.k), dtype=np.int64)
+        c = self.ctx
+        c.check(c.lib.sphx_state_download_neighbors(c.h, _lib.ip(out)))
+        return out
+
+    def download_composition(self):
+        """-> dict: mass (N,), mu_array (N,), gamma_array (N,) and, with with_species=True, f_un (N,S), as they are on the
+        device (a dust_phase rewrites them)."""
+        n, S = self.n, self.n_species
+        out = dict(mass=np.empty(n), mu_array=np.empty(n), gamma_array=np.empty(n))
+        fu = None
+        if S > 0:
+            out["f_un"] = fu = np.empty((n, S))
+        c = self.ctx
+        c.check(c.lib.sphx_state_download_composition(c.h, dp(out["mass"]), dp(fu), dp(out["mu_array"]), dp(out["gamma_array"])))
+        return out
+
+    def download_drag(self):
+        """-> (mean_grain_mass (N,), mean_cross (N,)) as the drag pass reads them (with_drag=True)."""
+        mgm, mcs = np.empty(self.n), np.empty(self.n)
+        c = self.ctx
+        c.check(c.lib.sphx_state_download_drag(c.h, dp(mgm), dp(mcs)))
+        return mgm, mcs
+
+    def dust_phase(self, dt, d, guard="count", full=False, **tables):
+        """code_running.py:399-435 on the state as it is on the device (include/sphx.h sphx_state_dust_phase): f_un
+        normalised, the loop-form density, chemisputtering_2, supernova_destruction on its outputs, and the bookkeeping
+        that folds both into mass, f_un, mu_array and gamma_array - which the next step then reads.  The list is the last
+        step's own (neighbors()), sizes the step's radii.  -> dict of the totals the driver prints (compat.PHASE_TOTALS,
+        compat.PHASE_COUNTS) plus chem_counts and dust_counts; full=True adds the stage outputs density, mass_chem,
+        f_un_chem, frac_destruction, frac_reuptake in the particle order of the uploaded state.  dt and d are the
+        driver's; **tables as compat.dust_phase takes them (mu_specie, gamma, mineral_densities, sputtering_yields,
+        mrn_constants, crit_mass, critical_density, species_curve), by default the module's.  With with_drag=True the
+        per-particle drag coefficients are formed again from the new f_un (compat.grain_mass(), compat.sigma_effective()).
+        The bits are those of compat.dust_phase on the downloaded state.  Needs with_species=True and one step."""
+        from . import compat
+        n = self.n
+        # (a state without a composition: the library refuses the call; the tables are sized by themselves)
+        S = self.n_species or int(np.shape(tables["mu_specie"] if tables.get("mu_specie") is not None else compat.mu_specie)[0])
+        t = compat.phase_tables(S, dt=dt, guard=guard, **tables)
+        gm = se = None
+        if self._with_drag:              # (the tables Simulation formed the coefficients from at upload)
+            gm = np.ascontiguousarray(compat.grain_mass(), dtype=np.float64)
+            se = np.ascontiguousarray(compat.sigma_effective(), dtype=np.float64)
+            if gm.shape != (S,) or se.shape != (S,):
+                raise ValueError("with_drag: grain_mass and sigma_effective hold %d species, the state %d" % (gm.shape[0], S))
+        st = dict(density=np.empty(n), mass_chem=np.empty(n), f_un_chem=np.empty((n, S)), frac_destruction=np.empty((n, S)),
+                  frac_reuptake=np.empty((n, S))) if full else {}
+        cc = np.zeros(len(compat.CHEM_COUNTS), dtype=np.int64); dc = np.zeros(len(compat.DUST_COUNTS), dtype=np.int64)
+        tot = np.zeros(len(compat.PHASE_TOTALS)); bc = np.zeros(len(compat.PHASE_COUNTS), dtype=np.int64)
+        kv, kc, ks = t["knots"]
+        c = self.ctx
+        c.check(c.lib.sphx_state_dust_phase(
+            c.h, t["dt"], float(d), dp(t["mu_specie"]), dp(t["gamma"]), dp(t["mineral_densities"]), dp(t["sputtering_yields"]),
+            dp(t["mrn"]), float(compat.k), float(compat.amu), float(compat.m_0), t["crit_mass"], t["critical_density"],
+            t["species_curve"].ctypes.data_as(_lib.c_int32_p), dp(kv), dp(kc), dp(ks), t["guard"], dp(gm), dp(se),
+            dp(st.get("density")), dp(st.get("mass_chem")), dp(st.get("f_un_chem")), dp(st.get("frac_destruction")),
+            dp(st.get("frac_reuptake")), _lib.ip(cc), _lib.ip(dc), dp(tot), _lib.ip(bc)))
+        self._phase_ran = True
+        out = dict(zip(compat.PHASE_TOTALS, (float(v) for v in tot)))
+        out.update(zip(compat.PHASE_COUNTS, (int(v) for v in bc)))
+        out["chem_counts"] = dict(zip(compat.CHEM_COUNTS, (int(v) for v in cc)))
+        out["dust_counts"] = dict(zip(compat.DUST_COUNTS, (int(v) for v in dc)))
+        out.update(st)
+        return out
+
+    def phase_timing(self):
+        """Device time of the last dust_phase() from HIP events -> dict of ms: gather, density, chem, dust, bookkeeping."""
+        ms = np.zeros(5)
+        c = self.ctx
+        c.check(c.lib.sphx_phase_last_timing(c.h, dp(ms)))
+        return dict(zip(("gather", "density", "chem", "dust", "bookkeeping"), ms.tolist()))
+
     # ---- snapshot / restart and per-step diagnostics (SURVEY 8f-4; the reference only wrote summary
     # statistics at the end of a run, sph/code_running.py:670, and printed the mass-weighted net
     # accelerations every step, sph/code_running.py:465-468) ----------------------------------------
     def snapshot(self, path, state):
         """Write a restartable particle-state snapshot (.npz): the downloaded dynamic arrays plus the
-        static per-particle arrays of `state` (mass, particle_type, mu_array, gamma_array, f_un)."""
+        static per-particle arrays of `state` (mass, particle_type, mu_array, gamma_array, f_un).  Once a dust_phase has
+        run, mass, mu_array, gamma_array and f_un are no longer static: they then come from download_composition()."""
         d = self.download()
         out = dict(points=d["points"], velocities=d["velocities"], total_accel=d["total_accel"],
                    E_internal=d["E_internal"], T=d["T"], sizes=d["sizes"], dt=np.float64(d["dt"]),
@@ -238,6 +319,8 @@ class Simulation:
             out[key] = np.asarray(state[key], dtype=np.float64)
         if state.get("f_un") is not None:
             out["f_un"] = np.asarray(state["f_un"], dtype=np.float64)
+        if self._phase_ran:
+            out.update(self.download_composition())
         np.savez(path, **out)
 
     @classmethod
@@ -254,7 +337,8 @@ class Simulation:
         """Mass-weighted net acceleration, momentum and energies of the current state
         (sph/code_running.py:465-468 prints the first of these every step)."""
         d = self.download()
-        m = np.asarray(state["mass"], dtype=np.float64)
+        # (once a dust_phase has run the caller's masses are stale: the device's)
+        m = self.download_composition()["mass"] if self._phase_ran else np.asarray(state["mass"], dtype=np.float64)
         mt = m.sum()
         return dict(net_accel=(d["total_accel"] * m[:, None]).sum(axis=0) / mt,
                     momentum=(d["velocities"] * m[:, None]).sum(axis=0),
