@@ -99,6 +99,9 @@ typedef struct sphx_stats {
     int64_t visc_blobs_settled; /* pass 3: blobs of 128 rows whose own m Pi is NaN in every row: neither staged nor walked */
     int64_t pi_waves_settled;   /* pass 2: waves (16 rows of one blob) that went on with the crossing-time term alone
                                    after every row's sum had become NaN                                                */
+    int64_t visc_launches_skipped; /* pass 3 (fused single-GPU step, LDS passes): launches that returned at once because pass 2
+                                      had marked no blob for them - it writes the NaN rows itself and marks the blobs with
+                                      other rows; the blobs pass 3 does not walk count in visc_blobs_settled           */
 } sphx_stats;
 
 /* ---- context ----------------------------------------------------------------------- */

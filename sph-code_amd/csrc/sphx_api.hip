@@ -727,9 +727,16 @@ static int step_sums(sphx_ctx* ctx, int k, hipEvent_t* ev, hipEvent_t search_end
         if (ctx->visc_mode == 1) {                 // passes 2 + 3 in one (pairwise viscosity): ms_pi stays 0
             SPHX_TRY(sphx_pass_visc_pw(ctx, n, k, s.m.as<double>()));
         } else {
-            SPHX_TRY(sphx_pass_pi(ctx, n, k, s.hprev.as<double>(), s.ptype.as<double>()));
+            // the LDS passes on all blobs of one GPU: pass 2 settles pass 3's NaN rows and marks the blobs with others (sphx_blob.hip)
+            const bool hand_visc = sphx_blob_can_hand_visc(ctx, n);
+            if (hand_visc) {                       // (pass 2 writes them: sized here, not in front of pass 3)
+                SPHX_TRY(sphx_ensure(ctx, ctx->va, (size_t)n * 3 * sizeof(double)));
+                SPHX_TRY(sphx_ensure(ctx, ctx->vh, (size_t)n * sizeof(double)));
+                SPHX_TRY(sphx_blob_size_marks(ctx, n));
+            }
+            SPHX_TRY(sphx_pass_pi(ctx, n, k, s.hprev.as<double>(), s.ptype.as<double>(), hand_visc));
             if (detail) HIPCHK(hipEventRecord(ev[5], ctx->stream));
-            SPHX_TRY(sphx_pass_visc(ctx, n, k, s.m.as<double>()));
+            SPHX_TRY(sphx_pass_visc(ctx, n, k, s.m.as<double>(), hand_visc));
         }
     }
     if (ctx->drag)
@@ -1043,12 +1050,13 @@ extern "C" int sphx_get_stats(sphx_ctx* ctx, sphx_stats* out) {
     }
     // the sums the LDS passes found NaN before they were finished (sphx_blob.h: blob_pass)
     if (ctx->scal.p) {
-        u64 cnt[2] = {0, 0};
+        u64 cnt[3] = {0, 0, 0};
         HIPCHK(hipSetDevice(ctx->device));
         HIPCHK(hipMemcpyAsync(cnt, ctx->scal.as<u64>() + SC_SETTLED, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         ctx->stats.visc_blobs_settled = (int64_t)cnt[0];
         ctx->stats.pi_waves_settled = (int64_t)cnt[1];
+        ctx->stats.visc_launches_skipped = (int64_t)cnt[2];
     }
     *out = ctx->stats;
     // the grid build's single-launch scan bounds its waits; a wait that ran out raised a flag (and left wrong numbers)
@@ -1073,7 +1081,7 @@ extern "C" int sphx_reset_stats(sphx_ctx* ctx) {
     memset(&ctx->stats, 0, sizeof(ctx->stats));
     HIPCHK(hipMemsetAsync(ctx->scal.as<u64>() + SC_CAND, 0, 2 * sizeof(u64), ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->scal.as<u64>() + SC_SHORT, 0, sizeof(u64), ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->scal.as<u64>() + SC_SETTLED, 0, 2 * sizeof(u64), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->scal.as<u64>() + SC_SETTLED, 0, 3 * sizeof(u64), ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->badc.p, 0, (size_t)BADC_BUCKETS * BADC_STRIDE * sizeof(u64), ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return SPHX_OK;

@@ -240,12 +240,20 @@ static int blob_launch(sphx_ctx* ctx, Kern kern, int per_slot, size_t extra, int
 //   SATURATES, saturated(sums), Vel, short_staged(img, s), short_global(j), short_none(row), term_short(vel, row)
 //                                        sums that stay NaN once they are: when every row of a wave has one, the wave's
 //                                        remaining batches fetch and compute only what term()'s return value needs
+//   HANDS_ON, hands_on(), finish(sums, max, row, i, o, has_first, live), hand_on(b, any_live)
+//                                        a pass that knows at finish how the NEXT pass's vote on the row will go: finish is
+//                                        told whether the row has a first list position and settles the row for that pass,
+//                                        or says that it is `live`; behind the barrier that closes blob b, hand_on is told
+//                                        whether any of its rows is (one thread; hands_on() false: neither is asked for)
 template <class P, class = void> struct BlobSettles { static constexpr bool value = false; };
 template <class P> struct BlobSettles<P, decltype((void)P::SETTLES)> { static constexpr bool value = P::SETTLES; };
 template <class P, class = void> struct BlobSaturates { static constexpr bool value = false; };
 template <class P> struct BlobSaturates<P, decltype((void)P::SATURATES)> { static constexpr bool value = P::SATURATES; };
+template <class P, class = void> struct BlobHandsOn { static constexpr bool value = false; };
+template <class P> struct BlobHandsOn<P, decltype((void)P::HANDS_ON)> { static constexpr bool value = P::HANDS_ON; };
 // the counters of the two shortcuts behind a launch's pointer (nullptr: not counted)
-enum { BLOB_CNT_BLOBS_SETTLED = 0, BLOB_CNT_WAVES_SATURATED = 1 };
+// (LAUNCHES_SKIPPED: launches of pass 3 that found no live row left by pass 2 and returned; their blobs count as settled)
+enum { BLOB_CNT_BLOBS_SETTLED = 0, BLOB_CNT_WAVES_SATURATED = 1, BLOB_CNT_LAUNCHES_SKIPPED = 2 };
 struct BlobSides { const double* g0 = nullptr; int s0 = 0; const double* g1 = nullptr; int s1 = 0; };   // stage<>'s g0, g1
 
 // dynamic LDS of a pass: 4 * BLOB_S chunks of image, BLOB_S side values (NSIDE > 0), the slot tile.  (Accessors, not
@@ -360,6 +368,18 @@ __device__ __forceinline__ void block_add_count(unsigned v, u64* dst) {
         if (r) atomicAdd(dst, (u64)r);
     }
 }
+// the blobs a workgroup takes where it is not dealt them by its number (blob_pass, own_n >= 0): filled by the kernel
+#define BLOB_OWN_MAX 64
+__device__ __forceinline__ int* blob_own_list() {
+    __shared__ int own[BLOB_OWN_MAX];
+    return own;
+}
+// HANDS_ON: whether a row of the blob in hand is live for the next pass (raised at finish, read and lowered by thread 0
+// behind the barrier that closes the blob)
+__device__ __forceinline__ int* blob_live_flag() {
+    __shared__ int flag;
+    return &flag;
+}
 // the row point out of the first list position (column p of the list, particle t of the blob): image, global memory,
 // or - no first neighbour - what load_row left.  (The pass's whole fetch is called and row_point keeps what it wants:
 // the loads of the rest - a side value, ViscPwPass's bc[*jp] - are plain loads of valid addresses that the compiler
@@ -377,13 +397,15 @@ __device__ __forceinline__ void blob_row_point(const P& ps, typename P::Row& row
 // clip: ignored unless P::CLIPS.  omap, n_active: outputs go to the caller's index o (device API: ghosts, o >= n_active,
 // are candidates only); omap == nullptr: o = the stored particle.  ct_bits: where P::VOTES passes vote.
 // counts: the shortcuts taken (BLOB_CNT_*; nullptr: not counted) - one atomic per workgroup, at its end.
+// own_n (-1: the blobs of `sel`, dealt out by workgroup number): THIS workgroup takes the blobs blob_own_list()[0 .. own_n).
 template <class P>
 __device__ __forceinline__ void blob_pass(const P& ps, int n, int npad, int k, int nblk, const int* __restrict__ nbr,
                                           const u16* __restrict__ slot16, const int* __restrict__ uniq,
                                           const int* __restrict__ qorder, int clip, const int* __restrict__ omap,
-                                          int n_active, u64* ct_bits, const BlobSel& sel, u64* counts = nullptr) {
+                                          int n_active, u64* ct_bits, const BlobSel& sel, u64* counts = nullptr,
+                                          int own_n = -1) {
     static_assert(P::PER_SLOT == 64 + (P::NSIDE ? 8 : 0), "image bytes per slot: the record and one side value");
-    constexpr bool SETTLES = BlobSettles<P>::value, SATURATES = BlobSaturates<P>::value;
+    constexpr bool SETTLES = BlobSettles<P>::value, SATURATES = BlobSaturates<P>::value, HANDS_ON = BlobHandsOn<P>::value;
     static_assert(!SATURATES || LPP == 4, "sphx_wave_saturated: a row's lanes are one nibble of the wave's mask");
     typedef BlobLds<P::NSIDE> L;
     const BlobSides sd = ps.sides();
@@ -391,14 +413,21 @@ __device__ __forceinline__ void blob_pass(const P& ps, int n, int npad, int k, i
     u64 my_ct = SPHX_CT_NONE;
     unsigned blobs_settled = 0, waves_saturated = 0;         // shortcuts taken (the first: uniform in the workgroup)
     // persistent workgroups (two per CU): blob after blob, no dispatch gap between them
-    const int nsel = blob_sel_count(sel, nblk);
+    if constexpr (HANDS_ON) {
+        if (threadIdx.x == 0) *blob_live_flag() = 0;         // (raised only behind the first staging's barrier)
+    }
+    const int stride = gridDim.x;
+    const bool own = own_n >= 0;
+    const int nsel = own ? (own_n ? (int)blockIdx.x + (own_n - 1) * stride + 1 : 0) : blob_sel_count(sel, nblk);
+    auto blob_at = [&](int bq) -> int {
+        return own ? blob_own_list()[(bq - (int)blockIdx.x) / stride] : blob_sel_at(sel, bq, nsel);
+    };
     // SETTLES: the vote's operands hang on the chain qorder[p] -> own(i).  They are fetched a blob ahead, and the
     // particle two blobs ahead, and a blob's vote rides on the barrier that ends the blob before it
     // (block_all_at_barrier): a blob that runs meets no wait and no barrier it did not have.  Where blob after blob
     // is settled, the workgroup goes at one round trip and one barrier per blob.
-    const int stride = gridDim.x;
     auto particle_of = [&](int bq) -> int {
-        const int pq = blob_sel_at(sel, bq, nsel) * BLOB_P + t;
+        const int pq = blob_at(bq) * BLOB_P + t;
         return (pq < n) ? qorder[pq] : 0;
     };
     auto nothing_left = [&](const RowAhead& r) -> bool {     // a row that writes nothing counts as settled for the vote
@@ -410,12 +439,12 @@ __device__ __forceinline__ void blob_pass(const P& ps, int n, int npad, int k, i
     unsigned round = 0;
     if constexpr (SETTLES) {
         if ((int)blockIdx.x < nsel)
-            cur = blob_row_ahead(ps, particle_of(blockIdx.x), blob_sel_at(sel, blockIdx.x, nsel) * BLOB_P + t, n, slot16, omap);
+            cur = blob_row_ahead(ps, particle_of(blockIdx.x), blob_at(blockIdx.x) * BLOB_P + t, n, slot16, omap);
         if ((int)blockIdx.x + stride < nsel) i_next = particle_of(blockIdx.x + stride);
         blob_settled = block_all_at_barrier<PASS_T>(nothing_left(cur), round++);
     }
     for (int bi = blockIdx.x; bi < nsel; bi += stride) {
-        const int b = blob_sel_at(sel, bi, nsel);
+        const int b = blob_at(bi);
         const int p = b * BLOB_P + t;
         int i, o;
         bool settled = false;
@@ -423,7 +452,7 @@ __device__ __forceinline__ void blob_pass(const P& ps, int n, int npad, int k, i
         auto fetch_ahead = [&]() {
             if constexpr (SETTLES) {
                 if (bi + stride < nsel) {                   // (the last blob votes on itself once more: nobody asks)
-                    cur = blob_row_ahead(ps, i_next, blob_sel_at(sel, bi + stride, nsel) * BLOB_P + t, n, slot16, omap);
+                    cur = blob_row_ahead(ps, i_next, blob_at(bi + stride) * BLOB_P + t, n, slot16, omap);
                     if (bi + 2 * stride < nsel) i_next = particle_of(bi + 2 * stride);
                 }
             }
@@ -494,7 +523,14 @@ __device__ __forceinline__ void blob_pass(const P& ps, int n, int npad, int k, i
                 group_total_fields(a);
                 if (P::VOTES) mx = group_max(mx);
                 if (!half) {
-                    const u64 cb = ps.finish(a, mx, row, i, o);
+                    u64 cb;
+                    if constexpr (HANDS_ON) {
+                        bool live = false;
+                        cb = ps.finish(a, mx, row, i, o, L::tile()[t] != SLOT_NONE, live);
+                        if (live) *blob_live_flag() = 1;       // (every live row the same word, the same value)
+                    } else {
+                        cb = ps.finish(a, mx, row, i, o);
+                    }
                     my_ct = cb < my_ct ? cb : my_ct;
                 }
             }
@@ -502,6 +538,10 @@ __device__ __forceinline__ void blob_pass(const P& ps, int n, int npad, int k, i
         // the image is rewritten by the next blob
         if constexpr (SETTLES) blob_settled = block_all_at_barrier<PASS_T>(nothing_left(cur), round++);
         else __syncthreads();
+        if constexpr (HANDS_ON) {
+            // (the next blob's rows raise the flag behind the barrier that follows its staging: this thread is through here)
+            if (ps.hands_on() && threadIdx.x == 0) { ps.hand_on(b, *blob_live_flag() != 0); *blob_live_flag() = 0; }
+        }
     }
     if (P::VOTES) block_min_vote<PASS_T>(my_ct, ct_bits);
     if constexpr (SETTLES) {

@@ -286,18 +286,33 @@ BLOB_KERNEL blob_density_kernel(BLOB_COMMON, int clip, const int* __restrict__ o
               n_active, nullptr, sel);
 }
 
+// what pass 3 writes for a settled row (sphx_settled.h): by ViscPass::settle, or by pass 2 where it hands its rows on
+__device__ __forceinline__ void visc_settle_store(double* va, double* vh, int o) {
+    const double q = __builtin_nan("");
+    va[3 * (size_t)o + 0] = q; va[3 * (size_t)o + 1] = q; va[3 * (size_t)o + 2] = q;
+    vh[o] = q;
+}
+
 // ---- pass 2: Pi_i, crossing time             nsc:639-649, nsc:776-786 --------------------------
+// Handing on (marks != nullptr; the fused single-GPU step): m Pi_i, which pass 3's vote on "settled" turns on, is in a
+// register at finish.  A settled row gets pass 3's NaNs here; a blob that holds a row that is not is marked, and pass 3
+// walks the marked blobs alone (blob_visc_kernel).
 struct PiPass {
     typedef RecB Rec;
     struct Sums { double pi; };
     static constexpr int NSIDE = 1, PER_SLOT = 72;          // side value: rho_j
     static constexpr bool CLIPS = false, VOTES = true, ROW_FROM_LIST = true;
     static constexpr bool SATURATES = BLOB_PI_SATURATES != 0;
+    static constexpr bool HANDS_ON = true;
     const RecB* __restrict__ rec;
     const double* __restrict__ rho_s;
     const RecSelf* __restrict__ selfr;
     RecBC* bc;
     double *Pi, *BwOut;
+    double *va, *vh;                                        // pass 3's outputs and, per blob, whether it has rows left to sum
+    unsigned char* marks;                                   // (nullptr: nothing is handed on)
+    __device__ __forceinline__ bool hands_on() const { return marks != nullptr; }
+    __device__ __forceinline__ void hand_on(int b, bool any_live) const { marks[b] = any_live ? 1 : 0; }
     struct Row { Q4 r0, rv; double rho_i, cs_i, ms_i, h_i; };
     struct Nb { Q8 q; double rho; };
     __device__ __forceinline__ BlobSides sides() const { return {rho_s, 1}; }
@@ -327,19 +342,25 @@ struct PiPass {
     __device__ __forceinline__ Vel short_global(int j) const { return gload4(reinterpret_cast<const double*>(&rec[j]) + 4); }
     __device__ __forceinline__ static Vel short_none(const Row& r) { return r.rv; }
     __device__ __forceinline__ static double term_short(const Vel& qv, const Row& r) { return pi_rel(qv, r.rv); }
-    __device__ __forceinline__ u64 finish(const Sums& a, double maxrel, const Row& r, int i, int o) const {
+    __device__ __forceinline__ u64 finish(const Sums& a, double maxrel, const Row& r, int i, int o, bool has_first,
+                                          bool& live) const {
         Pi[o] = a.pi;
         const double bw = fmax(r.ms_i, 0.0) * a.pi;                         // m Pi [t==0]  nsc:651
         bc[i].Bw = bw;
         if (BwOut) BwOut[o] = bw;
+        if (marks) {                                                        // (uniform: an argument; the row writes)
+            live = !sphx_row_settled(bw, has_first, true);
+            if (!live) visc_settle_store(va, vh, o);
+        }
         return (r.ms_i > 0.0) ? ct_vote_bits(r.h_i, maxrel) : SPHX_CT_NONE; // gas only     nsc:782
     }
 };
 BLOB_KERNEL blob_pi_kernel(BLOB_COMMON, const int* __restrict__ omap, int n_active, const RecB* __restrict__ recb,
                            const double* __restrict__ rho_s, const RecSelf* __restrict__ selfr, RecBC* bc, double* Pi,
-                           double* BwOut, u64* ct_bits, BlobSel sel, u64* counts) {
-    blob_pass(PiPass{recb, rho_s, selfr, bc, Pi, BwOut}, n, npad, k, nblk, nbr, slot16, uniq, qorder, 0, omap, n_active,
-              ct_bits, sel, counts);
+                           double* BwOut, u64* ct_bits, BlobSel sel, u64* counts, double* va, double* vh,
+                           unsigned char* marks) {
+    blob_pass(PiPass{recb, rho_s, selfr, bc, Pi, BwOut, va, vh, marks}, n, npad, k, nblk, nbr, slot16, uniq, qorder, 0, omap,
+              n_active, ct_bits, sel, counts);
 }
 
 // ---- pass 3: viscous acceleration + heat      nsc:651-654 --------------------------------------
@@ -353,6 +374,7 @@ struct ViscPass {
     const RecBC* __restrict__ bc;
     const double* __restrict__ m;
     double *va, *vh;
+    bool handed;                                             // pass 2 has written the settled rows (PiPass, handing on)
     struct Row { Q4 r0, rv; double hi2, ci, Bi, mi; };
     struct Nb { Q8 q; double c1; };                          // q.hi.d = Bw_j
     __device__ __forceinline__ BlobSides sides() const {
@@ -391,16 +413,96 @@ struct ViscPass {
     // every term holds Bw_i c_a: with a NaN Bw_i (Pi_i NaN: PiPass::finish, dust rows too) the four sums are NaN
     __device__ __forceinline__ double own(int i) const { return bc[i].Bw; }
     __device__ __forceinline__ void settle(int o) const {
-        const double q = __builtin_nan("");
-        va[3 * (size_t)o + 0] = q; va[3 * (size_t)o + 1] = q; va[3 * (size_t)o + 2] = q;
-        vh[o] = q;
+        if (!handed) visc_settle_store(va, vh, o);
     }
 };
+// The blobs of a launch of pass 3 that pass 2 has marked (one byte per blob: it holds a row that is not settled; the rows
+// that are, pass 2 has written), dealt out over the workgroups without a global list, an atomic or anything to reset:
+// every workgroup counts the marks (16 per thread and round, VISC_ROUND blobs per round), then numbers the marked blobs
+// in blob order - one prefix sum over the workgroup per round - and keeps in blob_own_list() those that fall to it.
+// Number r of `total` goes where blob r of as many goes (xcd_block: neighbouring blobs on one XCD).  Returns
+//   VISC_NONE   nothing is marked: nothing to stage, walk or write
+//   -1          every blob is marked: the walk as without marks (a healthy state pays the count alone)
+//   own_n >= 0  entries of blob_own_list() to walk (at most BLOB_OWN_MAX: sphx_blob_can_hand_visc)
+// and the number of marked blobs in `total`.  Every thread of the workgroup calls (barriers inside); the results are
+// uniform over the grid: every workgroup reads the same marks.
+#define VISC_NONE (-2)
+#define VISC_ROUND (16 * PASS_T)
+__device__ __forceinline__ int visc_own_blobs(const unsigned char* __restrict__ marks, int nblk, int& total) {
+    __shared__ int wave_tot[PASS_T / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    auto marked = [&](int b0, unsigned (&w)[4]) -> int {         // this thread's 16 marks from blob b0 on, and how many are set
+        w[0] = w[1] = w[2] = w[3] = 0u;
+        if (b0 >= nblk) return 0;
+        const uint4 mk = *reinterpret_cast<const uint4*>(marks + b0);              // (the buffer ends on a whole piece)
+        w[0] = mk.x; w[1] = mk.y; w[2] = mk.z; w[3] = mk.w;
+        int cnt = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            if (b0 + q >= nblk) w[q >> 2] &= ~(0xFFu << (8 * (q & 3)));             // (beyond the last blob: not written)
+            cnt += ((w[q >> 2] >> (8 * (q & 3))) & 0xFFu) ? 1 : 0;
+        }
+        return cnt;
+    };
+    unsigned w[4];
+    int mine = 0;
+    for (int base = 0; base < nblk; base += VISC_ROUND) mine += marked(base + 16 * (int)threadIdx.x, w);
+    mine = wave_scan_incl(mine);
+    if (lane == 63) wave_tot[wv] = mine;
+    __syncthreads();
+    total = 0;
+#pragma unroll
+    for (int q = 0; q < PASS_T / 64; ++q) total += wave_tot[q];
+    if (total == 0) return VISC_NONE;
+    if (total == nblk) return -1;
+    int before = 0;                                              // marked blobs in the rounds before this one
+    for (int base = 0; base < nblk; base += VISC_ROUND) {
+        __syncthreads();                                         // (wave_tot is read above, and in the round before)
+        const int b0 = base + 16 * (int)threadIdx.x;
+        const int cnt = marked(b0, w);
+        const int incl = wave_scan_incl(cnt);
+        if (lane == 63) wave_tot[wv] = incl;
+        __syncthreads();
+        int r = before + incl - cnt;                             // the number of this thread's first marked blob
+#pragma unroll
+        for (int q = 0; q < PASS_T / 64; ++q) {
+            const int tw = wave_tot[q];
+            if (q < wv) r += tw;
+            before += tw;
+        }
+        if (cnt) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                if ((w[q >> 2] >> (8 * (q & 3))) & 0xFFu) {
+                    const int bi = xcd_block_inv(r, total);      // the workgroup-strided index that lands on number r
+                    if (bi % (int)gridDim.x == (int)blockIdx.x) blob_own_list()[bi / (int)gridDim.x] = b0 + q;
+                    ++r;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    return ((int)blockIdx.x < total) ? (total - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
+}
+
+// marks (nullptr: every blob of `sel`, as without): the fused step's hand-over from pass 2 (PiPass) - the launch walks
+// the marked blobs alone, counts the others as settled, and `settle` stores nothing.
 BLOB_KERNEL blob_visc_kernel(BLOB_COMMON, int clip, const int* __restrict__ omap, int n_active,
                              const RecB* __restrict__ recb, const RecBC* __restrict__ bc, const double* __restrict__ m,
-                             double* va, double* vh, BlobSel sel, u64* counts) {
-    blob_pass(ViscPass{recb, bc, m, va, vh}, n, npad, k, nblk, nbr, slot16, uniq, qorder, clip, omap, n_active, nullptr, sel,
-              counts);
+                             double* va, double* vh, BlobSel sel, u64* counts,
+                             const unsigned char* __restrict__ marks) {
+    int own_n = -1;
+    if (marks) {
+        int total;
+        own_n = visc_own_blobs(marks, nblk, total);
+        if (counts && blockIdx.x == 0 && threadIdx.x == 0) {
+            atomicAdd(counts + BLOB_CNT_BLOBS_SETTLED, (u64)(nblk - total));
+            if (own_n == VISC_NONE) atomicAdd(counts + BLOB_CNT_LAUNCHES_SKIPPED, (u64)1);
+        }
+        if (own_n == VISC_NONE) return;                          // (uniform over the grid)
+    }
+    blob_pass(ViscPass{recb, bc, m, va, vh, marks != nullptr}, n, npad, k, nblk, nbr, slot16, uniq, qorder, clip, omap, n_active,
+              nullptr, sel, counts, own_n);
 }
 
 // ---- passes 2 + 3 fused: the pairwise viscosity (visc_mode 1; sphx_sums.hip pass_visc_pw_kernel) ------------------
@@ -823,17 +925,34 @@ int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k, bool lean) {
                        sphx_blob_sel(ctx, ctx->pass_part));
 }
 
-int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits) {
+// Whether the passes 2 and 3 of this step can hand over (sphx_pass_pi): all blobs of one GPU, and no workgroup of pass 3
+// with more blobs than its list holds (BLOB_OWN_MAX x 512 blobs = 4 x 10^6 particles).  The caller sizes ctx->va, ctx->vh
+// and the marks (sphx_blob_size_marks).
+bool sphx_blob_can_hand_visc(sphx_ctx* ctx, int64_t n) {
+    if (!ctx->qorder || !ctx->blob_lists || ctx->map_perm || ctx->blob_split_valid) return false;
+    const int nblk = (int)((sphx_pad64(n) + BLOB_P - 1) / BLOB_P);
+    return nblk <= BLOB_OWN_MAX * sphx_blob_grid(ctx, nblk);
+}
+int sphx_blob_size_marks(sphx_ctx* ctx, int64_t n) {            // one byte per blob, read in 16-B pieces
+    const size_t nblk = (size_t)((sphx_pad64(n) + BLOB_P - 1) / BLOB_P);
+    return sphx_ensure(ctx, ctx->visc_live, (nblk + 15) / 16 * 16);
+}
+
+// hand_on: pass 2 settles pass 3's rows and marks the blobs with others (ctx->va, ctx->vh, ctx->visc_live are sized)
+int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits, bool hand_on) {
     return blob_launch(ctx, blob_pi_kernel, PiPass::PER_SLOT, 0, n, k, ctx->map_perm, blob_n_active(ctx, n), ctx->recv.as<RecB>(),
                        ctx->rho_s.as<double>(), ctx->self_s.as<RecSelf>(), ctx->bc_s.as<RecBC>(), ctx->Pi.as<double>(),
                        ctx->map_perm ? ctx->Bw.as<double>() : nullptr, ct_bits, sphx_blob_sel(ctx, ctx->pass_part),
-                       ctx->scal.as<u64>() + SC_SETTLED);
+                       ctx->scal.as<u64>() + SC_SETTLED, hand_on ? ctx->va.as<double>() : nullptr,
+                       hand_on ? ctx->vh.as<double>() : nullptr, hand_on ? ctx->visc_live.as<unsigned char>() : nullptr);
 }
 
-int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m) {
+// handed: the pass 2 before it ran with hand_on
+int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m, bool handed) {
     return blob_launch(ctx, blob_visc_kernel, ViscPass::PER_SLOT, 0, n, k, ctx->clip_grad, ctx->map_perm, blob_n_active(ctx, n),
                        ctx->recv.as<RecB>(), ctx->bc_s.as<RecBC>(), m, ctx->va.as<double>(), ctx->vh.as<double>(),
-                       sphx_blob_sel(ctx, ctx->pass_part), ctx->scal.as<u64>() + SC_SETTLED);
+                       sphx_blob_sel(ctx, ctx->pass_part), ctx->scal.as<u64>() + SC_SETTLED,
+                       handed ? ctx->visc_live.as<const unsigned char>() : nullptr);
 }
 
 int sphx_blob_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m, u64* ct_bits) {

@@ -368,6 +368,7 @@ struct sphx_ctx {
     DevBuf slot16, uniq;
     // blob_split: int list[nblk] (interior blobs, then boundary blobs), then cnt[3] {interior, boundary, idle}
     DevBuf blob_class, blob_split;
+    DevBuf visc_live;             // one byte per blob: pass 2 found a row that pass 3 has to sum (the fused step's hand-over)
     DevBuf rho, rhod, nden, G, Pi, Bw, va, vh, ha, F;
     DevBuf scal;                  // small device scalars: ct bits, dt, counters
     DevBuf cell_of, cell_start, cell_fill, perm, inv, scan_tmp, bbox_tmp;      // grid
@@ -476,6 +477,13 @@ __device__ __forceinline__ int xcd_block(int b, int nb) {
     const int q = nb >> 3, r = nb & 7, x = b & 7, s = b >> 3;
     return x * q + (x < r ? x : r) + s;
 }
+// ... and the block that xcd_block maps to position p of the range
+__device__ __forceinline__ int xcd_block_inv(int p, int nb) {
+    const int q = nb >> 3, r = nb & 7, head = r * (q + 1);
+    const int x = p < head ? p / (q + 1) : r + (p - head) / q;       // (p >= head only where q > 0)
+    const int s = p < head ? p % (q + 1) : (p - head) % q;
+    return s * 8 + x;
+}
 
 // Every neighbour sum is kept as this many partial sums over the list positions k mod SPHX_SUM_PARTS,
 // combined as (p0 + p1) [+ (p2 + p3)]: one fixed order for the gather kernels (sphx_sums.hip) and the
@@ -515,8 +523,9 @@ enum {
     SC_CROWDED = 13,  // u64, only grows: cells of 17 .. 512 members met by blob_count (sorted by a launch of their own when many)
     SC_DENSEP = 14,   // u64, only grows: particles in cells of >= DENSE_CELL members (a tile's 27 such cells overflow it)
     SC_KGDBG = 16,    // u64[8]: grouped search, queries handed on by reason (diagnostics)
-    SC_SETTLED = 24,  // u64[2]: blobs pass 3 found settled, waves of pass 2 that saturated (BLOB_CNT_*; since sphx_reset_stats)
-    SC_NSLOTS = 26
+    SC_SETTLED = 24,  // u64[3]: blobs pass 3 did not walk, waves of pass 2 that saturated, launches of pass 3 that found no
+                      //         blob to walk (BLOB_CNT_*; since sphx_reset_stats)
+    SC_NSLOTS = 27
 };
 
 // Failure counters (the reference's only guard is the nan_to_num of drv:233-238, 460-463, 490-491), u64 and
@@ -606,8 +615,8 @@ int sphx_blob_translate(sphx_ctx* ctx, int64_t n, int k);
 int sphx_blob_density_species(sphx_ctx* ctx, int64_t n, int k, bool lean, int S, const double* fun, const int* row_of,
                               const double* m_sorted, double* F, double* Z, double* agb, int agb_on);
 int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k, bool lean);
-int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits);
-int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m);
+int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits, bool hand_on);
+int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m, bool handed);
 int sphx_blob_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m, u64* ct_bits);
 int sphx_blob_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted, double* F,
                       double* Z, double* agb, int agb_on);
@@ -712,8 +721,12 @@ struct PrepIn {
 // the records of every pass from `in`, launched on `stream`; pairwise: they feed the pairwise viscous pass (RecBC.Bw)
 int sphx_prep(sphx_ctx* ctx, int64_t n, const PrepIn& in, bool pairwise, hipStream_t stream);
 int sphx_pass_density(sphx_ctx* ctx, int64_t n, int k, bool lean = false);      // lean: G is not stored
-int sphx_pass_pi(sphx_ctx* ctx, int64_t n, int k, const double* h, const double* ptype);
-int sphx_pass_visc(sphx_ctx* ctx, int64_t n, int k, const double* m);
+// hand_visc (both or neither; the fused single-GPU step with the LDS passes): pass 2 writes the rows of pass 3 that are
+// settled (sphx_settled.h) and marks the blobs that hold another; pass 3 walks those alone.  Ignored by the gather kernels.
+bool sphx_blob_can_hand_visc(sphx_ctx* ctx, int64_t n);
+int sphx_blob_size_marks(sphx_ctx* ctx, int64_t n);         // ctx->visc_live, which pass 2 then writes
+int sphx_pass_pi(sphx_ctx* ctx, int64_t n, int k, const double* h, const double* ptype, bool hand_visc = false);
+int sphx_pass_visc(sphx_ctx* ctx, int64_t n, int k, const double* m, bool hand_visc = false);
 int sphx_pass_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m);   // passes 2 + 3 fused, visc_mode 1
 int sphx_pass_species(sphx_ctx* ctx, int64_t n, int k, int s, const double* fun, double* F);
 int sphx_step_species(sphx_ctx* ctx, int64_t n, int k);
