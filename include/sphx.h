@@ -738,6 +738,117 @@ int sphx_state_download_composition(sphx_ctx* ctx, double* mass, double* f_un, d
 /* The per-particle drag coefficients (sphx_state_set_drag; refreshed by sphx_state_dust_phase) in the order of upload;
  * either may be NULL.  SPHX_E_STATE: no state, or drag off.                                                        */
 int sphx_state_download_drag(sphx_ctx* ctx, double* mean_grain_mass, double* mean_cross);
+/* ---- the radiative block of the time loop, code_running.py:247-316, its elementwise half ------------------------ *
+ * Between sphx_rad_transfer (nsc:922-965) and sphx_rad_cooling (nsc:1019-1176) the driver and rad_heating do per-particle
+ * arithmetic on the composition rows: these three array calls.  In all of them n_gas is the number of particles with
+ * ptypes != 1 (checked on the device: SPHX_E_ARG when it differs), the order of lf2 / momentum / frac_destroyed is the
+ * caller's order over those particles (what rad_heating returns), every sum over species runs t = 0 .. s - 1 one by
+ * one, every operation is rounded on its own, nan_to_num is NumPy's (NaN -> 0, +-inf -> +-DBL_MAX), and the same inputs
+ * give the same bits on every call (no floating-point atomic).
+ *
+ * sphx_rad_ionise: nsc:976-1012.  Per particle i with ptypes != 1, g its ordinal among them:
+ *   n_photons = photons_per_joule lf2[g]                                                                  nsc:976
+ *   mols = mass_i / sum_t (f_un[i,t] mu_specie[t] amu)                                                    nsc:977
+ *   weighted_interception[t] = f_un[i,t] cross_sections[t] / sum_t (cross_sections[t] f_un[i,t])          nsc:979
+ *   atoms_destroyed[t] = weighted_interception[t] frac_dest[t] n_photons;  atoms_total[t] = f_un[i,t] mols   nsc:980-981
+ *   frac[t] = nan_to_num(0.99 - 0.99 exp(-nan_to_num(atoms_destroyed[t] / atoms_total[t])));
+ *   atoms_total[t] / amu < 1e-10 -> 0, then atoms_total[t] / amu < 0 -> 0.99                              nsc:983-988
+ *   the forward reactions with the reference's literal columns: f2 += 2 f0 frac[0]; f3 += f2 frac[2]; f4 += f1 frac[1];
+ *   f5 += f2 frac[2] + f1 frac[1]; f0 -= f0 frac[0]; f1 -= f1 frac[1]; f2 -= f2 frac[2] (right sides from the old row)
+ *                                                                                                         nsc:999-1007
+ * and for EVERY particle, stars and dust included, the row divided by its sum (nsc:1012).  Only frac[0..2] are ever
+ * read, so only those are formed: frac_dest needs s entries, of which three are used.  photons_per_joule is the scalar
+ * nsc:976 multiplies lf2 by (compat.stellar_spectrum).  Outputs: f_un_new (n,s); frac_destroyed (n_gas,3) or NULL.
+ * SPHX_E_ARG: a NULL required pointer, n < 1, s < 6 or s > SPHX_MAX_SPECIES, n_gas not the count.                  */
+int sphx_rad_ionise(sphx_ctx* ctx, int64_t n, int s, int64_t n_gas, const double* f_un, const double* ptypes, const double* mass,
+                    const double* lf2 /* [n_gas] */, const double* frac_dest /* [s] */, double photons_per_joule,
+                    const double* mu_specie /* [s] */, const double* cross_sections /* [s] */, double amu, double* f_un_new,
+                    double* frac_destroyed /* (n_gas,3) or NULL */);
+/* sphx_rad_heat_bookkeeping: drv:258-273.  f_un is sphx_rad_ionise's output.  Per particle:
+ *   mu = sum_t f mu_specie / sum_t f; gamma, cross likewise with gamma_specie, cross_sections             drv:258-260
+ *   where ptypes == 0: c0 = nan_to_num(lf2[g] / E); c0 >= 0 -> c0 + 1, else exp(c0); E *= c0;             drv:263-267
+ *                      T = E / (N_PART gamma k_B), N_PART = mass / (m_h mu_before)                        drv:268, 248
+ *   E < t_cmb gamma mass k_B / (mu m_h) -> that; E > t_max gamma mass k_B / (mu m_h) -> that;
+ *   T < t_cmb -> t_cmb; T >= t_max -> t_max (all particles; a NaN stays)                                  drv:270-273
+ * Quirk kept: N_PART at drv:268 is the value of drv:248, formed with the mu_array from BEFORE the heating - mu_before is
+ * an input.  The driver never defines t_max (a NameError as committed): it is an argument.  The driver's cross_sections
+ * are the module's plus sigma_effective (drv:58), not the table sphx_rad_ionise takes.
+ * Outputs (n each): mu_out, gamma_out, cross_out, E_out, T_out.  totals[2] or NULL: the sum of E_internal on entry and
+ * of E_out (chunks of 256 in index order, the chunks in a fixed order); counts int64[4] or NULL: E raised, E lowered,
+ * T raised, T lowered by the clamps.                                                                                */
+int sphx_rad_heat_bookkeeping(sphx_ctx* ctx, int64_t n, int s, int64_t n_gas, const double* f_un, const double* ptypes,
+                              const double* mass, const double* mu_before, const double* E_internal, const double* T,
+                              const double* lf2 /* [n_gas] */, const double* mu_specie, const double* gamma_specie,
+                              const double* cross_sections, double t_cmb, double t_max, double k_B, double m_h, double* mu_out,
+                              double* gamma_out, double* cross_out, double* E_out, double* T_out, double* totals /* [2] or NULL */,
+                              int64_t* counts /* int64[4] or NULL */);
+/* sphx_rad_cool_bookkeeping: drv:283-311.  final_comp and energy are sphx_rad_cooling's; lf2 and momentum
+ * sphx_rad_transfer's; E_internal and T sphx_rad_heat_bookkeeping's.  Per particle:
+ *   mu, gamma, cross from final_comp as above; N_PART = mass / (m_h mu)                                   drv:283-289
+ *   where ptypes == 0: c1 = nan_to_num(-(energy N_PART) / E); c1 >= 0 -> c1 + 1, else exp(c1);
+ *                      c1 *= exp(-dt / cooling_timescale sqrt(T / 1e4)); E *= c1; T = E / (N_PART gamma k_B)   drv:293-298
+ *   where ptypes == 2: optd = 1 - exp(-(N_PART cross) 9 / (4 pi sizes^2));
+ *                      T = (lf2[g] / (optd 4 pi sizes^2 sb 1e-5 dt) + t_cmb^(1/6))^(1/6); E = N_PART k_B T gamma   drv:286-301
+ *   where ptypes != 1: velocities += momentum[g]                                                          drv:303
+ *   the clamps of drv:270-273 again, with the new mu and gamma                                            drv:308-311
+ * Quirks kept: the sixth root with t_cmb^(1/6) inside, as written; the T in the cooling_timescale factor is the T of the
+ * moment (the heating's).  cooling_timescale and t_max are undefined in the driver: arguments here.
+ * Outputs: mu_out, gamma_out, cross_out, E_out, T_out (n each), vel_out (n,3); totals and counts as above.
+ * SPHX_E_ARG as above, and non-finite constants or cooling_timescale == 0.                                          */
+int sphx_rad_cool_bookkeeping(sphx_ctx* ctx, int64_t n, int s, int64_t n_gas, const double* final_comp, const double* energy,
+                              const double* ptypes, const double* mass, const double* sizes, const double* E_internal,
+                              const double* T, const double* velocities, const double* lf2 /* [n_gas] */,
+                              const double* momentum /* (n_gas,3) */, const double* mu_specie, const double* gamma_specie,
+                              const double* cross_sections, double dt, double t_cmb, double t_max, double cooling_timescale,
+                              double sb, double k_B, double m_h, double* mu_out, double* gamma_out, double* cross_out,
+                              double* E_out, double* T_out, double* vel_out, double* totals /* [2] or NULL */,
+                              int64_t* counts /* int64[4] or NULL */);
+/* Device time of the last of the three calls above on this context, from HIP events on its stream, in ms: ms[0] inputs
+ * going up and the non-star ordinals (flags, scan, one host wait), ms[1] the row kernel, ms[2] the sums behind the totals
+ * (two events back to back for sphx_rad_ionise), ms[3] the outputs coming back.  Measurement aid.               */
+int sphx_radphase_last_timing(sphx_ctx* ctx, double ms[4]);
+/* sphx_state_rad_phase: the whole radiative block, code_running.py:247-316 with N_RADIATIVE = 1, on the step loop's
+ * resident state - the second side call that WRITES it.  In this order:
+ *   1  the state gathered through its ids into the order of upload: positions, velocities, mass, mu_array, sizes (the
+ *      step's kNN radius, as sphx_state_rad_transfer takes it), T, E_internal, particle_type; the step's own list
+ *      translated to particle ids (as sphx_state_dust_phase does); the composition rows; cross_array = sum_t f
+ *      driver_cross_sections / sum_t f (drv:434: a ratio, so the normalisation of drv:399/424 does not change it beyond
+ *      rounding)
+ *   2  the positions of the sources and targets, by their ids
+ *   3  nsc:922-965      sphx_rad_transfer's kernels
+ *   4  nsc:976-1012     sphx_rad_ionise's
+ *   5  drv:258-273      sphx_rad_heat_bookkeeping's (mu_before = the resident mu_array)
+ *   6  nsc:1019-1176    sphx_rad_cooling's, on the step's list, with cross_array, f_un, mu_array, T as stage 5 left them
+ *   7  drv:283-311      sphx_rad_cool_bookkeeping's
+ *   8  the write-back through the ids: velocities, E_internal, T, mu_array, gamma_array and the composition rows of the
+ *      resident state; with drag on also mean_grain_mass and mean_cross, formed from the new f_un as
+ *      sphx_state_dust_phase forms them.  Positions, mass, sizes, the list and the previous temperature behind
+ *      sphx_state_download_pressure are not touched.
+ * Every stage runs in the order of upload on the kernels of the array calls: every output has the bits of
+ * sphx_rad_transfer, sphx_rad_ionise, sphx_rad_heat_bookkeeping, sphx_rad_cooling and sphx_rad_cool_bookkeeping chained
+ * on the downloaded state and sphx_state_download_neighbors' list.  source_ids / target_ids: particle ids (the order of
+ * upload) of the selected stars and the sampled non-star particles; n_dst = 0 is legal (lum_factor = 0).  The physics
+ * stages read amu, solar_luminosity, c, k_B, m_h and m_0 from the context's constants, as their array calls do.
+ * With no star in the state the driver skips the block (drv:243): *skipped = 1, nothing is computed or written.
+ * Optional outputs in the order of upload, any may be NULL: cross_array (n), lf2 (G), momentum (G,3), extinction (G),
+ * f_un_ionised (n,s), frac_destroyed (G,3), heat_out (5,n): mu, gamma, cross, E_internal, T after stage 5, energy (n) and
+ * rec_array (s,n) of stage 6, cross_out (n) of stage 7; totals[3]: the sum of E_internal before, after the heating, after
+ * the cooling; counts int64[8]: the four clamp counts of stage 5, then of stage 7; *n_gas_out = G.
+ * SPHX_E_STATE as sphx_state_dust_phase (no state, no step yet, incremental search, the step's list gone), or no
+ * composition of s >= 6.  SPHX_E_ARG: drag on without grain_mass and sigma_effective, an id outside [0, n), and what the
+ * array calls refuse (no particle with ptypes == 0 among them).  A refused call leaves the state as it was.        */
+int sphx_state_rad_phase(sphx_ctx* ctx, double dt, double d, int64_t n_src, const int64_t* source_ids, const double* luminosities,
+                         int64_t n_dst, const int64_t* target_ids, const double* frac_dest /* [s] */, double photons_per_joule,
+                         const double* mu_specie, const double* gamma_specie, const double* cross_sections,
+                         const double* driver_cross_sections, double amu, double t_cmb, double t_max, double cooling_timescale,
+                         double sb, double k_B, double m_h, int mode, const double* grain_mass /* [s] or NULL */,
+                         const double* sigma_effective /* [s] or NULL */, double* cross_array, double* lf2, double* momentum,
+                         double* extinction, double* f_un_ionised, double* frac_destroyed, double* heat_out, double* energy,
+                         double* rec_array, double* cross_out, double* totals, int64_t* counts, int64_t* n_gas_out, int* skipped);
+/* Device time of the last sphx_state_rad_phase call that was not skipped, from HIP events, in ms: ms[0] the state
+ * gathered, the list translated, cross_array and the rays' ends, ms[1] the transfer, ms[2] ionise + heat, ms[3] the
+ * cooling, ms[4] the cooling's bookkeeping, the write-back and the outputs coming back.  Measurement aid.          */
+int sphx_state_radphase_last_timing(sphx_ctx* ctx, double ms[5]);
 int sphx_get_stats(sphx_ctx* ctx, sphx_stats* out);
 int sphx_reset_stats(sphx_ctx* ctx);
 

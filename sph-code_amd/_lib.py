@@ -107,6 +107,13 @@ SIGNATURES = {
     "sphx_state_dust_phase": (C.c_int, [_P, C.c_double, C.c_double] + [_D] * 5 + [C.c_double] * 5 + [c_int32_p, _D, _D, _D, C.c_int] +
                                         [_D] * 7 + [_I, _I, _D, _I]),
     "sphx_phase_last_timing": (C.c_int, [_P, _D]),
+    "sphx_radphase_last_timing": (C.c_int, [_P, _D]),
+    "sphx_state_radphase_last_timing": (C.c_int, [_P, _D]),
+    "sphx_state_rad_phase": (C.c_int, [_P, C.c_double, C.c_double, C.c_int64, _I, _D, C.c_int64, _I, _D, C.c_double, _D, _D, _D, _D] +
+                                       [C.c_double] * 7 + [C.c_int, _D, _D] + [_D] * 11 + [_I, _I, C.POINTER(C.c_int)]),
+    "sphx_rad_ionise": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64] + [_D] * 5 + [C.c_double, _D, _D, C.c_double, _D, _D]),
+    "sphx_rad_heat_bookkeeping": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64] + [_D] * 10 + [C.c_double] * 4 + [_D] * 6 + [_I]),
+    "sphx_rad_cool_bookkeeping": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64] + [_D] * 13 + [C.c_double] * 7 + [_D] * 7 + [_I]),
     "sphx_state_download_neighbors": (C.c_int, [_P, _I]),
     "sphx_state_download_composition": (C.c_int, [_P, _D, _D, _D, _D]),
     "sphx_state_download_drag": (C.c_int, [_P, _D, _D]),

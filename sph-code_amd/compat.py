@@ -17,6 +17,11 @@ for the functions the driver sph/code_running.py ("drv") calls on the SPH inner 
     rad_cooling            nsc:1019-1176    drv:276
     supernova_destruction  nsc:1211-1263    drv:411
     chemisputtering_2      nsc:1265-1416    drv:405
+    luminosity_relation    nsc:174-200      (without its unused `imf` argument)
+
+and, under names of their own, the pieces rad_heating (nsc:893-1017) and the driver's radiative block (drv:247-316)
+fall into: rad_setup, rad_transfer, stellar_spectrum, rad_ionise, rad_heat_bookkeeping, rad_cool_bookkeeping, and
+rad_phase, which chains them with rad_cooling.
 
 Hidden inputs are honoured the way the driver uses them: it assigns `nsc.d`, `nsc.d_0`,
 `nsc.dt`, `nsc.dt_0` (drv:68-75,231) and the functions read the module attribute at call
@@ -876,3 +881,280 @@ def phase_tables(S, dt=None, mu_specie=None, gamma=None, mineral_densities=None,
                 critical_density=float(g["critical_density"] if critical_density is None else critical_density),
                 species_curve=dust_species_curve(S, species_curve), guard=DUST_GUARDS[guard],
                 knots=tuple(np.array(a, dtype=np.float64) for a in (DUST_KNOTS_V, DUST_KNOTS_C, DUST_KNOTS_SI)))
+
+
+# ==============================================================================================
+# The radiative block of the time loop: code_running.py:247-316
+# ==============================================================================================
+planck_h = 6.62607015e-34                       # nsc:26 (scipy.constants.h)
+sb = 5.6703744191844314e-08                     # nsc:23
+wien = 0.0028977719551851727                    # nsc:28
+t_cmb = 2.732                                   # nsc:33
+t_solar = 5776                                  # nsc:34
+supernova_energy = 1e44                         # nsc:35
+cross_sections = np.array([6.3e-22, 6.3e-22, 6.3e-22, 1e-60, 1e-60, 1.e-60, 6.65e-60 * 80] + [0.] * 8) / 80. + 1e-80       # nsc:42
+destruction_energies = np.array([7.2418e-19, 3.93938891e-18, 2.18e-18, 10000, 10000, 8.71584082e-18] + [10000] * 9)      # nsc:43
+RADPHASE_TOTALS = ("E_before", "E_after_heating", "E_after_cooling")
+RADPHASE_COUNTS = ("E_raised", "E_lowered", "T_raised", "T_lowered")
+
+
+def driver_cross_sections(S=15):
+    """The per-species cross-sections of the DRIVER (drv:46, 58): the module's plus sigma_effective.  The bookkeeping of
+    drv:260 / 285 forms cross_array with these; rad_heating's own chemistry (nsc:979) reads the module's.  The effective
+    cross-section is formed factor by factor as nsc:73 has it (this module's sigma_effective multiplies by the ratio of
+    the two differences, an ulp away on some species), so that the table has the driver's bits."""
+    lo, hi = _mrn_limits(mrn_constants)
+    seff = chem_table(S, None, "mu_specie") * amu / chem_table(S, None, "mineral_densities") * (3. / 4.) * \
+        -(hi ** -0.5 - lo ** -0.5) / (hi ** 0.5 - lo ** 0.5)
+    return chem_table(S, None, "cross_sections") + seff
+
+
+def _mass_laws(base_imf):
+    """Coefficient and exponent of the mass-luminosity and mass-radius power laws (nsc:175-188, 210-223), per star: the
+    luminosity law breaks at 0.7, the radius law at 1.66 solar masses; a NaN mass falls on neither side and gets zeros."""
+    b = f64(base_imf).reshape(-1)
+    laws = []
+    for brk, lo, hi in ((0.7, (0.35, 2.62), (1.02, 3.92)), (1.66, (1.06, 0.945), (1.2916594319, 0.555))):
+        coeff, expo = np.zeros(b.shape[0]), np.zeros(b.shape[0])
+        coeff[b < brk], expo[b < brk] = lo
+        coeff[b >= brk], expo[b >= brk] = hi
+        laws += [coeff, expo]
+    return (b,) + tuple(laws)
+
+
+def luminosity_relation(base_imf, lifetime=0):
+    """nsc:174-200 without its unused `imf` argument -> luminosity in solar units of stars of base_imf solar masses, or
+    with lifetime=1 their lifetime in units of 1e10 years, floored at 3.6e-4."""
+    b, cl, el, _, _ = _mass_laws(base_imf)
+    if lifetime == 0:
+        return cl * b ** el
+    if lifetime == 1:
+        life = cl ** (-1) * b ** (1 - el)
+        life[life < 3.6e-4] = 3.6e-4
+        return life
+    return None
+
+
+def rad_setup(ptypes, masses, supernova_pos, dt, rng=np.random):
+    """nsc:897-921, the random half of rad_heating -> (source_ids, luminosities, target_ids): caller indices of the
+    selected stars, their luminosities (solar units, renormalised to the total of ALL stars), caller indices of the
+    sampled non-star particles.  rng.rand(n_stars) is drawn first and rng.rand(n_nonstar) second, as the reference
+    draws them: with the global np.random seeded alike, the selection is the reference's.  Quirks kept: a star is
+    taken with probability m / (4 solar masses) + n_stars^-0.5; none drawn -> all stars; a star listed in supernova_pos
+    adds 0.264 supernova_energy / solar_luminosity / dt; a non-star particle is sampled with probability
+    n_nonstar^-0.65, all of them only when there is no star at all."""
+    pt, m = f64(ptypes).reshape(-1), f64(masses).reshape(-1)
+    stars, others = np.nonzero(pt == 1)[0], np.nonzero(pt != 1)[0]
+    n_s, n_o = len(stars), len(others)
+    msun = m[stars] / solar_mass
+    chosen = np.arange(n_s)
+    if n_s > 0:
+        chosen = np.nonzero(rng.rand(n_s) < (m[stars] / (4 * solar_mass)) + n_s ** -0.5)[0]
+        if len(chosen) == 0:
+            chosen = np.arange(n_s)
+    exploding = np.zeros(len(m))
+    exploding[np.asarray(supernova_pos, dtype=np.int64)] += 1
+    base = luminosity_relation(msun[chosen]) + 0.264 * supernova_energy / solar_luminosity / dt * exploding[stars][chosen]
+    total = np.sum(luminosity_relation(msun))
+    with np.errstate(all="ignore"):
+        lum = base / np.sum(base) * total
+    targets = others[:0]
+    if n_o > 0:
+        targets = others[rng.rand(n_o) < n_o ** -0.65]
+        if len(chosen) == 0:
+            targets = others
+    return stars[chosen].astype(np.int64), lum, targets.astype(np.int64)
+
+
+def planck_law(temp, wl, dwl):
+    """nsc:202-207: the black-body spectrum at `temp` on the wavelengths wl, its first entry zeroed, normalised over dwl."""
+    with np.errstate(all="ignore"):
+        emission = np.nan_to_num((2 * planck_h * c ** 2 / wl ** 5) / (np.exp(planck_h * c / (wl * k * temp)) - 1))
+        emission[0] = 0
+        return np.nan_to_num(emission / np.sum(emission * dwl))
+
+
+def overall_spectrum(base_imf):
+    """nsc:209-245 with imf = 1 per star (all rad_heating asks for) -> (wl, spectrum, dwl): the stars' black bodies at
+    the temperatures of the two power laws, weighted by luminosity, on 10000 wavelengths spaced by logarithm around the
+    solar Wien peak."""
+    b, cl, el, cr, er = _mass_laws(base_imf)
+    lum = cl * b ** el
+    temp = (cl / cr) ** (1. / 4.) * b ** ((el - er) / 4.)
+    peak = np.log10(wien / t_solar)
+    wl = np.logspace(peak - 5, peak + 3, 10000)
+    dwl = np.append(wl[0], np.diff(wl))
+    spec = np.zeros(len(wl))
+    for u in range(len(b)):
+        spec += np.nan_to_num(np.nan_to_num(planck_law(temp[u] * t_solar, wl, dwl)) * 1. * lum[u])
+    with np.errstate(all="ignore"):
+        spec /= np.sum(dwl * spec)
+        spec *= np.sum(lum) / np.sum(b) * solar_luminosity / solar_mass
+    return wl, spec, dwl
+
+
+def stellar_spectrum(star_masses, destruction_energies=None):
+    """nsc:967-976 -> (frac_dest (S,), photons_per_joule).  star_masses: masses[ptypes == 1], in kg.  frac_dest[t] is
+    the share of the stars' summed spectrum (weighted by wavelength and bin width) short of species t's destruction
+    wavelength; photons_per_joule the scalar nsc:976 multiplies lf2 by to get n_photons."""
+    de = f64(globals()["destruction_energies"] if destruction_energies is None else destruction_energies)
+    wl, spec, dwl = overall_spectrum(f64(star_masses) / solar_mass)
+    hc = planck_h * c
+    limit = de ** (-1) * hc
+    weighted = spec * dwl * wl
+    with np.errstate(all="ignore"):
+        frac = np.array([np.sum(weighted[wl < limit[t]]) for t in range(len(limit))])
+        frac /= np.sum(weighted)
+        ppj = np.sum(wl * spec * dwl / hc) / np.sum(spec * dwl)
+    return frac, float(ppj)
+
+
+def _radphase_tables(S, mu_specie=None, gamma=None, cross_sections=None):
+    cs = driver_cross_sections(S) if cross_sections is None else chem_table(S, cross_sections, "cross_sections")
+    return chem_table(S, mu_specie, "mu_specie"), chem_table(S, gamma, "gamma"), cs
+
+
+def _n_gas(pt, what, arr, width=None):
+    g = int(np.count_nonzero(pt != 1))
+    a = f64(arr)
+    if a.shape != ((g,) if width is None else (g, width)):
+        raise ValueError("%s must hold one row per particle with ptypes != 1 (%d)" % (what, g))
+    return g, a
+
+
+def rad_ionise(f_un, ptypes, masses, lf2, frac_dest, photons_per_joule, mu_specie=None, cross_sections=None, full=False):
+    """nsc:976-1012, the photoionisation chemistry of rad_heating -> f_un_new (N,S): the second element of rad_heating's
+    return tuple.  lf2 is rad_transfer's (over the particles with ptypes != 1), frac_dest and photons_per_joule
+    stellar_spectrum's.  cross_sections defaults to the MODULE's (nsc:42), as inside the reference.  full=True appends
+    frac_destroyed_by_species[:, :3] (G,3), the three columns the reactions read.  include/sphx.h, sphx_rad_ionise."""
+    fun = f64(f_un)
+    if fun.ndim != 2:
+        raise ValueError("f_un must be (N, S)")
+    n, S = fun.shape
+    pt, m = f64(ptypes, (n,)), f64(masses, (n,))
+    g, lf = _n_gas(pt, "lf2", lf2)
+    fd = f64(frac_dest, (S,))
+    mus, cs = chem_table(S, mu_specie, "mu_specie"), chem_table(S, cross_sections, "cross_sections")
+    out = np.empty((n, S)); frac = np.empty((g, 3)) if full else None
+    c_ = context()
+    c_.check(c_.lib.sphx_rad_ionise(c_.h, n, S, g, dp(fun), dp(pt), dp(m), dp(lf), dp(fd), float(photons_per_joule), dp(mus), dp(cs),
+                                    float(amu), dp(out), dp(frac)))
+    return (out, frac) if full else out
+
+
+def _radphase_totals(tot, cnt, names):
+    out = dict(zip(names, (float(v) for v in tot)))
+    out.update(zip(RADPHASE_COUNTS, (int(v) for v in cnt)))
+    return out
+
+
+def rad_heat_bookkeeping(f_un, ptypes, masses, mu_before, E_internal, T, lf2, t_max, t_cmb=None, mu_specie=None, gamma=None,
+                         cross_sections=None):
+    """drv:258-273 -> (mu_array, gamma_array, cross_array, E_internal, T, totals).  f_un is rad_ionise's, mu_before the
+    mu_array from before the heating (N_PART at drv:268 is drv:248's), lf2 rad_transfer's.  t_max is undefined in the
+    driver and has no default here.  cross_sections defaults to the DRIVER's (driver_cross_sections).  totals: the sum of
+    E_internal before and after, and how many entries each clamp moved (RADPHASE_COUNTS).  include/sphx.h,
+    sphx_rad_heat_bookkeeping."""
+    fun = f64(f_un)
+    if fun.ndim != 2:
+        raise ValueError("f_un must be (N, S)")
+    n, S = fun.shape
+    pt, m, mub = f64(ptypes, (n,)), f64(masses, (n,)), f64(mu_before, (n,))
+    E, temp = f64(E_internal, (n,)), f64(T, (n,))
+    g, lf = _n_gas(pt, "lf2", lf2)
+    mus, gam, cs = _radphase_tables(S, mu_specie, gamma, cross_sections)
+    outs = [np.empty(n) for _ in range(5)]
+    tot = np.zeros(2); cnt = np.zeros(4, dtype=np.int64)
+    c_ = context()
+    c_.check(c_.lib.sphx_rad_heat_bookkeeping(c_.h, n, S, g, dp(fun), dp(pt), dp(m), dp(mub), dp(E), dp(temp), dp(lf), dp(mus), dp(gam),
+                                              dp(cs), float(globals()["t_cmb"] if t_cmb is None else t_cmb), float(t_max), float(k),
+                                              float(m_h), *([dp(a) for a in outs] + [dp(tot), ip(cnt)])))
+    return tuple(outs) + (_radphase_totals(tot, cnt, ("E_before", "E_after")),)
+
+
+def rad_cool_bookkeeping(final_comp, energy, ptypes, masses, sizes, E_internal, T, velocities, lf2, momentum, dt, t_max,
+                         cooling_timescale, t_cmb=None, mu_specie=None, gamma=None, cross_sections=None):
+    """drv:283-311 -> (mu_array, gamma_array, cross_array, E_internal, T, velocities, totals).  final_comp and energy are
+    rad_cooling's first two results, lf2 and momentum rad_transfer's, E_internal and T rad_heat_bookkeeping's.  t_max and
+    cooling_timescale are undefined in the driver and have no default here.  include/sphx.h, sphx_rad_cool_bookkeeping."""
+    fun = f64(final_comp)
+    if fun.ndim != 2:
+        raise ValueError("final_comp must be (N, S)")
+    n, S = fun.shape
+    pt, m, h, en = f64(ptypes, (n,)), f64(masses, (n,)), f64(sizes, (n,)), f64(energy, (n,))
+    E, temp, vel = f64(E_internal, (n,)), f64(T, (n,)), f64(velocities, (n, 3))
+    g, lf = _n_gas(pt, "lf2", lf2)
+    _, mom = _n_gas(pt, "momentum", momentum, 3)
+    mus, gam, cs = _radphase_tables(S, mu_specie, gamma, cross_sections)
+    outs = [np.empty(n) for _ in range(5)] + [np.empty((n, 3))]
+    tot = np.zeros(2); cnt = np.zeros(4, dtype=np.int64)
+    c_ = context()
+    c_.check(c_.lib.sphx_rad_cool_bookkeeping(c_.h, n, S, g, dp(fun), dp(en), dp(pt), dp(m), dp(h), dp(E), dp(temp), dp(vel), dp(lf),
+                                              dp(mom), dp(mus), dp(gam), dp(cs), float(dt),
+                                              float(globals()["t_cmb"] if t_cmb is None else t_cmb), float(t_max),
+                                              float(cooling_timescale), float(sb), float(k), float(m_h),
+                                              *([dp(a) for a in outs] + [dp(tot), ip(cnt)])))
+    return tuple(outs) + (_radphase_totals(tot, cnt, ("E_before", "E_after")),)
+
+
+def row_ratio(f_un, table):
+    """sum_t f_un[i,t] table[t] / sum_t f_un[i,t] per particle, both sums taken over the species one by one (the order the
+    library's kernels add a row in; np.sum pairs them differently from eight species on)."""
+    fun = f64(f_un)
+    cols = np.ascontiguousarray(fun.T)               # (contiguous columns: the sums below run over whole arrays)
+    num, den = cols[0] * table[0], cols[0].copy()
+    for t in range(1, cols.shape[0]):
+        num = num + cols[t] * table[t]
+        den = den + cols[t]
+    with np.errstate(all="ignore"):
+        return num / den
+
+
+def cross_array_of(f_un, cross_sections=None):
+    """cross_array as drv:434 leaves it for rad_heating: row_ratio of f_un with the driver's cross-sections."""
+    S = f64(f_un).shape[1]
+    return row_ratio(f_un, driver_cross_sections(S) if cross_sections is None else chem_table(S, cross_sections, "cross_sections"))
+
+
+def rad_phase(points, velocities, neighbor, mass, f_un, mu_array, sizes, T, E_internal, particle_type, source_ids, luminosities,
+              target_ids, frac_dest, photons_per_joule, dt, d, t_max, cooling_timescale, mode="line", full=False, t_cmb=None,
+              mu_specie=None, gamma=None, cross_sections=None, driver_cross=None):
+    """The block code_running.py:247-316 with N_RADIATIVE = 1 as a chain of the array calls - rad_transfer, rad_ionise,
+    rad_heat_bookkeeping, rad_cooling, rad_cool_bookkeeping - on the caller's arrays and `neighbor`
+    -> (f_un, mu_array, gamma_array, E_internal, T, velocities, totals); full=True appends a dict of the stage outputs.
+    source_ids, luminosities, target_ids are rad_setup's, frac_dest and photons_per_joule stellar_spectrum's.
+    cross_sections is the module's table (rad_ionise), driver_cross the driver's (the bookkeeping and the cross_array
+    that goes into rad_transfer).  With no star (drv:243) the driver skips the block: no GPU call is made, f_un, mu_array,
+    E_internal, T and velocities come back as given, gamma_array - which is no input - is row_ratio(f_un, gamma), what
+    drv:162 formed it as from the same f_un, and totals is {"skipped": True}."""
+    pt = f64(particle_type)
+    pts = f64(points)
+    if not np.any(pt == 1):
+        gam0 = row_ratio(f_un, chem_table(f64(f_un).shape[1], gamma, "gamma"))
+        return (f64(f_un), f64(mu_array), gam0, f64(E_internal), f64(T), f64(velocities), dict(skipped=True)) + ((dict(),) if full else ())
+    src = np.asarray(source_ids, dtype=np.int64); dst = np.asarray(target_ids, dtype=np.int64)
+    cross0 = cross_array_of(f_un, driver_cross)
+    lf2, mom, ext = rad_transfer(pts, pt, mass, sizes, cross0, mu_array, pts[src], luminosities, pts[dst], dt, mode=mode)
+    f1, frac = rad_ionise(f_un, pt, mass, lf2, frac_dest, photons_per_joule, mu_specie=mu_specie, cross_sections=cross_sections,
+                          full=True)
+    mu1, g1, cr1, E1, T1, tot1 = rad_heat_bookkeeping(f1, pt, mass, mu_array, E_internal, T, lf2, t_max, t_cmb=t_cmb,
+                                                      mu_specie=mu_specie, gamma=gamma, cross_sections=driver_cross)
+    final, energy, rec = rad_cooling(pts, pt, mass, sizes, cr1, f1, neighbor, mu1, T1, dt, d=d)
+    mu2, g2, cr2, E2, T2, v2, tot2 = rad_cool_bookkeeping(final, energy, pt, mass, sizes, E1, T1, velocities, lf2, mom, dt, t_max,
+                                                          cooling_timescale, t_cmb=t_cmb, mu_specie=mu_specie, gamma=gamma,
+                                                          cross_sections=driver_cross)
+    totals = dict(skipped=False, E_before=tot1["E_before"], E_after_heating=tot1["E_after"], E_after_cooling=tot2["E_after"])
+    for nm in RADPHASE_COUNTS:
+        totals["heat_" + nm], totals["cool_" + nm] = tot1[nm], tot2[nm]
+    out = (final, mu2, g2, E2, T2, v2, totals)
+    if full:
+        out += (dict(cross_array=cross0, lf2=lf2, momentum=mom, extinction=ext, f_un_ionised=f1, frac_destroyed=frac, mu_heat=mu1,
+                     gamma_heat=g1, cross_heat=cr1, E_heat=E1, T_heat=T1, final_comp=final, energy=energy, rec_array=rec,
+                     cross_array_out=cr2),)
+    return out
+
+
+def radphase_last_timing():
+    """Device time of the last rad_ionise / rad_heat_bookkeeping / rad_cool_bookkeeping call of this module, from HIP
+    events (include/sphx.h sphx_radphase_last_timing) -> dict of ms: upload, kernel, sums, download."""
+    return _last_timing("sphx_radphase_last_timing", ("upload", "kernel", "sums", "download"))

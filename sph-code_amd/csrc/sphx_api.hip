@@ -176,7 +176,7 @@ extern "C" void sphx_destroy(sphx_ctx* ctx) {
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (int i = 0; i < 10; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t, &ctx->chem_t, &ctx->phase_t})
+    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t, &ctx->chem_t, &ctx->phase_t, &ctx->radphase_t, &ctx->radstate_t})
         for (int i = 0; i < 6; ++i)
             if (t->ev[i]) (void)hipEventDestroy(t->ev[i]);
     for (int r = 0; r < 3; ++r)
@@ -282,6 +282,8 @@ extern "C" int sphx_cool_last_timing(sphx_ctx* ctx, double ms[4]) { return last_
 extern "C" int sphx_dust_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::dust_t, ms); }
 extern "C" int sphx_chem_last_timing(sphx_ctx* ctx, double ms[5]) { return last_timing(ctx, &sphx_ctx::chem_t, ms); }
 extern "C" int sphx_phase_last_timing(sphx_ctx* ctx, double ms[5]) { return last_timing(ctx, &sphx_ctx::phase_t, ms); }
+extern "C" int sphx_state_radphase_last_timing(sphx_ctx* ctx, double ms[5]) { return last_timing(ctx, &sphx_ctx::radstate_t, ms); }
+extern "C" int sphx_radphase_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::radphase_t, ms); }
 
 // =============================================================================================
 // nsc.neighbors                                                                nsc:541-552

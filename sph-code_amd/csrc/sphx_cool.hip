@@ -51,16 +51,24 @@ __global__ __launch_bounds__(COOL_WG) void cool_prep_kernel(CoolPrep a) {
     a.rec[i] = r;
 }
 
-// entry e = (j, kk) of the (n,k) list
+// entry e = (j, kk) of the list.  KMAJOR false: the caller's (n,k) int64 list, turned into the K-major int32 list nbr;
+// KMAJOR true: nbr is given (K-major, rows of npad columns, caller ids, -1 = missing: what phase_list_kernel makes of the
+// step's own list) and is only read.  Either way the reverse list's counts and the rows' flags.
+template <bool KMAJOR>
 __global__ __launch_bounds__(COOL_WG) void cool_list_kernel(int n, int npad, int k, const long long* __restrict__ nb,
-                                                            const double* __restrict__ ptype, int* __restrict__ nbr,
-                                                            int* cnt, int* flag) {
+                                                            const double* __restrict__ ptype, int* nbr, int* cnt, int* flag) {
     const long long e = (long long)blockIdx.x * COOL_WG + threadIdx.x;
     if (e >= (long long)n * k) return;
     const int j = (int)(e / k), kk = (int)(e - (long long)j * k);
-    const long long q = nb[e];
-    const int p = (q >= 0 && q < n) ? (int)q : -1;
-    nbr[(size_t)kk * npad + j] = p;
+    int p;
+    if (KMAJOR) {
+        const int q = nbr[(size_t)kk * npad + j];
+        p = (q >= 0 && q < n) ? q : -1;
+    } else {
+        const long long q = nb[e];
+        p = (q >= 0 && q < n) ? (int)q : -1;
+        nbr[(size_t)kk * npad + j] = p;
+    }
     if (p >= 0 && ptype[j] == 0.0 && ptype[p] == 0.0) {
         atomicAdd(&cnt[p], 1);
         flag[j] = 1;
@@ -182,49 +190,33 @@ __global__ __launch_bounds__(COOL_WG) void cool_gather_kernel(CoolGather a) {
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-extern "C" int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const double* ptype,
-                                const double* mass, const double* f_un, const int64_t* neighbor, const double* mu,
-                                const double* T, double dt, double d, double* final_comp, double* energy, double* rec_array,
-                                double* row_table) {
-    if (!ctx) return SPHX_E_ARG;
-    if (n < 1 || k < 1 || s < 6)
-        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_rad_cooling: n=%lld, k=%d, s=%d (need n >= 1, k >= 1, s >= 6)", (long long)n, k, s);
-    if (n > 0x7FFFFFF0ll || sphx_pad64(n) * (int64_t)k > 0x7FFFFFF0ll || n * (int64_t)s > (1ll << 40))
-        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_rad_cooling: n=%lld x k=%d (or x s=%d) out of range", (long long)n, k, s);
-    if (!(dt - dt == 0.0) || !(d - d == 0.0))
-        return sphx_set_err(ctx, SPHX_E_ARG, "sphx_rad_cooling: dt=%g, d=%g must be finite", dt, d);
-    NEED(points); NEED(ptype); NEED(mass); NEED(f_un); NEED(neighbor); NEED(mu); NEED(T);
-    NEED(final_comp); NEED(energy); NEED(rec_array);
-    HIPCHK(hipSetDevice(ctx->device));
-    SPHX_TRY(ctx->cool_t.begin(ctx));
+// nsc:1019-1176 on inputs that are on the device, in the caller's particle order.  The list: nb64, the (n,k) int64 list
+// on the device, or kmajor, the K-major int32 list in caller ids (nb64 NULL).  t: the stage timer whose stages 1 .. 3 are
+// marked, or NULL.  Results on the device (ctx->cool_out, ctx->cool_tab).
+int sphx_cool_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const CoolDev& in, const long long* nb64, const int* kmajor,
+                  double dt, double d, StageTimer* t, CoolRes* res) {
     hipStream_t st = ctx->stream;
     const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), ns = nn * (size_t)s, nk = nn * (size_t)k;
-    // ---- inputs: points (3n) | ptype | mass | mu | T (n each) | f_un (n s); the list as given ----
-    SPHX_TRY(sphx_ensure(ctx, ctx->cool_in, (7 * nn + ns) * sizeof(double)));
-    SPHX_TRY(sphx_ensure(ctx, ctx->cool_nb, nk * sizeof(int64_t)));
-    double* in = ctx->cool_in.as<double>();
-    double *d_pos = in, *d_pt = in + 3 * nn, *d_m = in + 4 * nn, *d_mu = in + 5 * nn, *d_T = in + 6 * nn, *d_fun = in + 7 * nn;
-    const CopyF64 us[] = {{points, d_pos, 3 * nn}, {ptype, d_pt, nn}, {mass, d_m, nn}, {mu, d_mu, nn}, {T, d_T, nn}, {f_un, d_fun, ns}};
-    SPHX_TRY(sphx_upload_f64(ctx, us, 6));
-    HIPCHK(hipMemcpyAsync(ctx->cool_nb.p, neighbor, nk * sizeof(int64_t), hipMemcpyHostToDevice, st));
     // ---- records; the K-major list, the rows' flags, the counts ----
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_rec, nn * sizeof(CoolRec)));
     // ints: nbr (k npad) | cnt (n + 1) | cur (n + 1) | flag (n + 1) | start (n + 1), each part a multiple of four
     const size_t n1 = (nn + 4) & ~size_t(3);
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_int, ((size_t)k * npad + 4 * n1) * sizeof(int)));
-    int* nbr = ctx->cool_int.as<int>();
-    int *cnt = nbr + (size_t)k * npad, *cur = cnt + n1, *flag = cur + n1, *start = flag + n1;
+    int* own = ctx->cool_int.as<int>();
+    int* nbr = nb64 ? own : const_cast<int*>(kmajor);
+    int *cnt = own + (size_t)k * npad, *cur = cnt + n1, *flag = cur + n1, *start = flag + n1;
     HIPCHK(hipMemsetAsync(cnt, 0, 3 * n1 * sizeof(int), st));
     CoolPrep pa;
-    pa.n = (int)n; pa.s = s; pa.pos = d_pos; pa.ptype = d_pt; pa.m = d_m; pa.mu = d_mu; pa.T = d_T; pa.fun = d_fun;
+    pa.n = (int)n; pa.s = s; pa.pos = in.pos; pa.ptype = in.pt; pa.m = in.m; pa.mu = in.mu; pa.T = in.T; pa.fun = in.fun;
     pa.d = d; pa.m0 = ctx->cst.m_0; pa.m_h = ctx->cst.m_h; pa.kB = ctx->cst.k_B;
     pa.rec = ctx->cool_rec.as<CoolRec>();
     const unsigned nblk = (unsigned)((nn + COOL_WG - 1) / COOL_WG);
+    const dim3 lgrid((unsigned)((nk + COOL_WG - 1) / COOL_WG));
     hipLaunchKernelGGL(cool_prep_kernel, dim3(nblk), dim3(COOL_WG), 0, st, pa);
-    hipLaunchKernelGGL(cool_list_kernel, dim3((unsigned)((nk + COOL_WG - 1) / COOL_WG)), dim3(COOL_WG), 0, st, (int)n, (int)npad, k,
-                       (const long long*)ctx->cool_nb.p, d_pt, nbr, cnt, flag);
+    if (nb64) hipLaunchKernelGGL(cool_list_kernel<false>, lgrid, dim3(COOL_WG), 0, st, (int)n, (int)npad, k, nb64, in.pt, nbr, cnt, flag);
+    else hipLaunchKernelGGL(cool_list_kernel<true>, lgrid, dim3(COOL_WG), 0, st, (int)n, (int)npad, k, nb64, in.pt, nbr, cnt, flag);
     HIPCHK(hipGetLastError());
-    SPHX_TRY(ctx->cool_t.mark(ctx, 1));
+    if (t) SPHX_TRY(t->mark(ctx, 1));
     // ---- rows ----
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_tab, 6 * nn * sizeof(double)));
     CoolRows ra;
@@ -232,19 +224,19 @@ extern "C" int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const do
     ra.tab = ctx->cool_tab.as<double>();
     hipLaunchKernelGGL(cool_row_kernel, dim3(nblk), dim3(COOL_WG), 0, st, ra);
     HIPCHK(hipGetLastError());
-    SPHX_TRY(ctx->cool_t.mark(ctx, 2));
+    if (t) SPHX_TRY(t->mark(ctx, 2));
     // ---- the reverse list: scan, fill, sort each slice ----
     SPHX_TRY(sphx_excl_scan_int(ctx, cnt, start, (int)n));             // (cnt[n] = 0: the memset above; both start on 16-byte boundaries)
     HIPCHK(hipMemcpyAsync(&ctx->pinned->side.count, start + n, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     const size_t M = (size_t)ctx->pinned->side.count;
-    if (M > nk) return sphx_set_err(ctx, SPHX_E_HIP, "sphx_rad_cooling: reverse list of %zu entries from %zu pairs", M, nk);
+    if (M > nk) return sphx_set_err(ctx, SPHX_E_HIP, "%s: reverse list of %zu entries from %zu pairs", who, M, nk);
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_rev, 2 * (M + 4) * sizeof(int)));
     int* rev_raw = ctx->cool_rev.as<int>();
     int* rev = rev_raw + M + 4;
     if (M > 0) {
         hipLaunchKernelGGL(cool_fill_kernel, dim3((unsigned)(((size_t)k * npad + COOL_WG - 1) / COOL_WG)), dim3(COOL_WG), 0, st, (int)n,
-                           (int)npad, k, nbr, d_pt, start, cur, rev_raw);
+                           (int)npad, k, nbr, in.pt, start, cur, rev_raw);
         HIPCHK(hipGetLastError());
         unsigned bits = 1;
         while (bits < 32 && (1ull << bits) < (unsigned long long)n) ++bits;
@@ -256,12 +248,48 @@ extern "C" int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const do
     // ---- gather and epilogue: final_comp (n s) | energy (n) | rec_array (s n) ----
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_out, (2 * ns + nn) * sizeof(double)));
     CoolGather ga;
-    ga.n = (int)n; ga.s = s; ga.start = start; ga.rev = rev; ga.rec = pa.rec; ga.tab = ra.tab; ga.fun = d_fun; ga.d = d;
+    ga.n = (int)n; ga.s = s; ga.start = start; ga.rev = rev; ga.rec = pa.rec; ga.tab = ra.tab; ga.fun = in.fun; ga.d = d;
     ga.final_comp = ctx->cool_out.as<double>(); ga.energy = ga.final_comp + ns; ga.rec_array = ga.energy + nn;
     hipLaunchKernelGGL(cool_gather_kernel, dim3(nblk), dim3(COOL_WG), 0, st, ga);
     HIPCHK(hipGetLastError());
-    SPHX_TRY(ctx->cool_t.mark(ctx, 3));
-    const CopyF64 ds[] = {{final_comp, ga.final_comp, ns}, {energy, ga.energy, nn}, {rec_array, ga.rec_array, ns}, {row_table, ra.tab, 6 * nn}};
+    if (t) SPHX_TRY(t->mark(ctx, 3));
+    res->final_comp = ga.final_comp; res->energy = ga.energy; res->rec_array = ga.rec_array; res->tab = ra.tab;
+    return SPHX_OK;
+}
+int sphx_cool_check(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, double dt, double d) {
+    if (n < 1 || k < 1 || s < 6)
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld, k=%d, s=%d (need n >= 1, k >= 1, s >= 6)", who, (long long)n, k, s);
+    if (n > 0x7FFFFFF0ll || sphx_pad64(n) * (int64_t)k > 0x7FFFFFF0ll || n * (int64_t)s > (1ll << 40))
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld x k=%d (or x s=%d) out of range", who, (long long)n, k, s);
+    if (!(dt - dt == 0.0) || !(d - d == 0.0))
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: dt=%g, d=%g must be finite", who, dt, d);
+    return SPHX_OK;
+}
+
+extern "C" int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const double* ptype,
+                                const double* mass, const double* f_un, const int64_t* neighbor, const double* mu,
+                                const double* T, double dt, double d, double* final_comp, double* energy, double* rec_array,
+                                double* row_table) {
+    if (!ctx) return SPHX_E_ARG;
+    SPHX_TRY(sphx_cool_check(ctx, "sphx_rad_cooling", n, k, s, dt, d));
+    NEED(points); NEED(ptype); NEED(mass); NEED(f_un); NEED(neighbor); NEED(mu); NEED(T);
+    NEED(final_comp); NEED(energy); NEED(rec_array);
+    HIPCHK(hipSetDevice(ctx->device));
+    SPHX_TRY(ctx->cool_t.begin(ctx));
+    hipStream_t st = ctx->stream;
+    const size_t nn = (size_t)n, ns = nn * (size_t)s, nk = nn * (size_t)k;
+    // ---- inputs: points (3n) | ptype | mass | mu | T (n each) | f_un (n s); the list as given ----
+    SPHX_TRY(sphx_ensure(ctx, ctx->cool_in, (7 * nn + ns) * sizeof(double)));
+    SPHX_TRY(sphx_ensure(ctx, ctx->cool_nb, nk * sizeof(int64_t)));
+    double* in = ctx->cool_in.as<double>();
+    double *d_pos = in, *d_pt = in + 3 * nn, *d_m = in + 4 * nn, *d_mu = in + 5 * nn, *d_T = in + 6 * nn, *d_fun = in + 7 * nn;
+    const CopyF64 us[] = {{points, d_pos, 3 * nn}, {ptype, d_pt, nn}, {mass, d_m, nn}, {mu, d_mu, nn}, {T, d_T, nn}, {f_un, d_fun, ns}};
+    SPHX_TRY(sphx_upload_f64(ctx, us, 6));
+    HIPCHK(hipMemcpyAsync(ctx->cool_nb.p, neighbor, nk * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    const CoolDev din{d_pos, d_pt, d_m, d_mu, d_T, d_fun};
+    CoolRes r;
+    SPHX_TRY(sphx_cool_run(ctx, "sphx_rad_cooling", n, k, s, din, (const long long*)ctx->cool_nb.p, nullptr, dt, d, &ctx->cool_t, &r));
+    const CopyF64 ds[] = {{final_comp, r.final_comp, ns}, {energy, r.energy, nn}, {rec_array, r.rec_array, ns}, {row_table, r.tab, 6 * nn}};
     SPHX_TRY(sphx_download_f64(ctx, ds, 4));
     SPHX_TRY(ctx->cool_t.mark(ctx, 4));
     HIPCHK(hipStreamSynchronize(st));

@@ -429,6 +429,20 @@ struct sphx_ctx {
     // events of a call: [0] start, [1] state gathered and list translated, [2] density, [3] chem, [4] dust, [5] bookkeeping
     // done, state written back and totals on the host (sphx_phase_last_timing)
     StageTimer phase_t{5};
+    // the elementwise half of the radiative block (sphx_radphase.hip), buffers of its own: doubles (staged inputs, outputs,
+    // the totals' per-particle terms, the chunks' partial sums, the totals), ints (the non-star flags and their scan)
+    DevBuf radphase_buf, radphase_int;
+    double radphase_tab[3 * SPHX_MAX_SPECIES] = {0};   // the call's three per-species tables on the host, uploaded from here
+    // events of a call: [0] start, [1] inputs on the device and the ordinals scanned, [2] the row kernel done, [3] the
+    // totals' sums done, [4] outputs on the host (sphx_radphase_last_timing)
+    StageTimer radphase_t;
+    // the radiative phase on the resident state (sphx_state_rad_phase): doubles (the state gathered into caller order, dense
+    // composition rows, every stage's outputs), ints (column of a caller id | the translated list | source and target ids).
+    // events: [0] start, [1] gathered, list translated, [2] transfer, [3] ionise + heat, [4] cooling, [5] bookkeeping,
+    // write-back, outputs on the host (sphx_state_radphase_last_timing)
+    DevBuf radstate_buf, radstate_int;
+    double radstate_tab[8 * SPHX_MAX_SPECIES] = {0};
+    StageTimer radstate_t{5};
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
@@ -763,6 +777,22 @@ int sphx_dust_params(sphx_ctx* ctx, const char* who, int s, double crit_mass, do
 int sphx_dust_inputs(sphx_ctx* ctx, int64_t n, int s, DustDev* in);
 int sphx_dust_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const DustDev& in, const int* nbr_given, const DustPar& par,
                   StageTimer* t, DustRes* res);
+
+// ---- the middle parts of rad_transfer and rad_cooling on device inputs, for the resident radiative phase (sphx_rad.hip, sphx_cool.hip) ----
+struct RadDevOut { double *lf2, *ext, *mom; int64_t ng; };                       // (ng), (ng), (ng,3) in ctx->rad_out; NULL when ng = 0
+int sphx_rad_run_dev(sphx_ctx* ctx, const char* who, int64_t n, const double* x, const double* y, const double* z, const double* m,
+                     const double* ptype, const double* sizes, const double* cross, const double* mu, int64_t n_src,
+                     const double* src_dev, const double* lum_host, int64_t n_dst, const double* dst_dev, double dt, int mode,
+                     RadDevOut* out);
+struct CoolDev { const double *pos, *pt, *m, *mu, *T, *fun; };                   // (n,3), (n,) x 4, (n,s)
+struct CoolRes { double *final_comp, *energy, *rec_array, *tab; };               // (n,s), (n), (s,n), (n,6)
+int sphx_cool_check(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, double dt, double d);
+int sphx_cool_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const CoolDev& in, const long long* nb64, const int* kmajor,
+                  double dt, double d, StageTimer* t, CoolRes* res);
+// ---- shared by the two resident phases (sphx_phase.hip) ----
+int sphx_phase_need_list(sphx_ctx* ctx, const char* who);                          // SPHX_E_STATE unless the last step's list stands
+int sphx_phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list);       // col (n) and the caller-order K-major list (k npad)
+int sphx_phase_drag_refresh(sphx_ctx* ctx, int64_t n, int s, const double* f, const double* gm, const double* se, double* mgm, double* mcs);
 
 // integrate / layout helpers (sphx_integrate.hip)
 int sphx_clamp(sphx_ctx* ctx, int64_t n, StateArrays& s);

@@ -292,6 +292,24 @@ static int phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list) {
     return SPHX_OK;
 }
 
+// what the resident radiative phase (sphx_radphase.hip) shares with the dust phase: the list guard, the translation of the
+// step's list, and the drag coefficients from dense composition rows (n,s) in caller order
+int sphx_phase_need_list(sphx_ctx* ctx, const char* who) { return phase_need_list(ctx, who); }
+int sphx_phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list) { return phase_translate(ctx, col, col_done, list); }
+__global__ __launch_bounds__(PHASE_WG) void phase_drag_kernel(int n, int s, const double* __restrict__ f, const double* __restrict__ gm,
+                                                              const double* __restrict__ se, double* mgm, double* mcs) {
+    const int i = blockIdx.x * PHASE_WG + threadIdx.x;
+    if (i >= n) return;
+    const double* fo = f + (size_t)i * s;
+    mgm[i] = phase_np_sum(s, [&](int t) { return gm[t] * fo[t]; });          // nsc:720-726, as Simulation forms them
+    mcs[i] = phase_np_sum(s, [&](int t) { return se[t] * fo[t]; });
+}
+int sphx_phase_drag_refresh(sphx_ctx* ctx, int64_t n, int s, const double* f, const double* gm, const double* se, double* mgm, double* mcs) {
+    hipLaunchKernelGGL(phase_drag_kernel, dim3(phase_blocks((size_t)n)), dim3(PHASE_WG), 0, ctx->stream, (int)n, s, f, gm, se, mgm, mcs);
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
+}
+
 extern "C" int sphx_state_download_neighbors(sphx_ctx* ctx, int64_t* neighbor) {
     if (!ctx) return SPHX_E_ARG;
     SPHX_TRY(phase_need_list(ctx, "sphx_state_download_neighbors"));

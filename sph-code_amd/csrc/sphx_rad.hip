@@ -259,8 +259,12 @@ struct RadHostOut { double *lf2, *momentum, *extinction, *blocked, *star_distanc
 // Device layout of ctx->rad_in (doubles): [0,3n) points AoS (host path) | m | ptype | sizes | cross | mu  (n each)
 //                  ctx->rad_soa:          x | y | z | h2 | w (n each)
 // The particles' attributes are on the device (RadPart's inputs filled); sources, luminosities and targets come from the host.
+// rays_on_device: src and dst are device pointers (the resident radiative phase gathers them by id); t: the stage timer to
+// mark, or NULL; dev (nullable): where the deposit's results lie on the device afterwards
 static int rad_run(sphx_ctx* ctx, const char* who, RadPart pa, int64_t n_src, const double* src, const double* lum,
-                   int64_t n_dst, const double* dst, double dt, int mode, bool transfer, const RadHostOut& ho) {
+                   int64_t n_dst, const double* dst, double dt, int mode, bool transfer, const RadHostOut& ho,
+                   bool rays_on_device, StageTimer* t, RadDevOut* dev) {
+    const hipMemcpyKind ray_copy = rays_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const int64_t n = pa.n;
     const int64_t R = n_src * n_dst;
     // rays, their outputs, the sources' luminosities: src | dst | lum | blocked | sd | bs
@@ -272,8 +276,8 @@ static int rad_run(sphx_ctx* ctx, const char* who, RadPart pa, int64_t n_src, co
     double* d_blocked = d_lum + n_src;
     double* d_sd = d_blocked + R;
     double* d_bs = d_sd + R;
-    if (n_src > 0) HIPCHK(hipMemcpyAsync(d_src, src, (size_t)n_src * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (n_dst > 0) HIPCHK(hipMemcpyAsync(d_dst, dst, (size_t)n_dst * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (n_src > 0) HIPCHK(hipMemcpyAsync(d_src, src, (size_t)n_src * 3 * sizeof(double), ray_copy, ctx->stream));
+    if (n_dst > 0) HIPCHK(hipMemcpyAsync(d_dst, dst, (size_t)n_dst * 3 * sizeof(double), ray_copy, ctx->stream));
     if (transfer && n_src > 0) HIPCHK(hipMemcpyAsync(d_lum, lum, (size_t)n_src * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     // per particle
     const size_t ints = ((size_t)n + 8) & ~size_t(3);
@@ -307,7 +311,7 @@ static int rad_run(sphx_ctx* ctx, const char* who, RadPart pa, int64_t n_src, co
             return sphx_set_err(ctx, SPHX_E_ARG, "%s: no particle with ptypes == 0 (the distance factor needs min(sizes) over them)", who);
         hmin = rd[2] > 0.0 ? NAN : rd[0];                  // (np.min hands a NaN on)
     }
-    SPHX_TRY(ctx->rad_t.mark(ctx, 1));
+    if (t) SPHX_TRY(t->mark(ctx, 1));
     // columns
     if (R > 0) {
         const int64_t ray_tiles = (R + RAD_WG * RAD_RPL - 1) / (RAD_WG * RAD_RPL);
@@ -331,7 +335,7 @@ static int rad_run(sphx_ctx* ctx, const char* who, RadPart pa, int64_t n_src, co
                            ca.part, (int)n_dst, d_src, d_dst, d_blocked, d_sd, d_bs);
         HIPCHK(hipGetLastError());
     }
-    SPHX_TRY(ctx->rad_t.mark(ctx, 2));
+    if (t) SPHX_TRY(t->mark(ctx, 2));
     // spread and deposit: lf2 | ext | momentum (3) | lum_factor (n_src)
     double *o_lf2 = nullptr, *o_ext = nullptr, *o_mom = nullptr, *o_lumf = nullptr;
     if (transfer && ng > 0) {
@@ -348,14 +352,15 @@ static int rad_run(sphx_ctx* ctx, const char* who, RadPart pa, int64_t n_src, co
         hipLaunchKernelGGL(rad_deposit_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, ctx->stream, da);
         HIPCHK(hipGetLastError());
     }
-    SPHX_TRY(ctx->rad_t.mark(ctx, 3));
+    if (t) SPHX_TRY(t->mark(ctx, 3));
     const CopyF64 ps[] = {{ho.blocked, d_blocked, (size_t)R}, {ho.star_distance, d_sd, (size_t)R}, {ho.lf2, o_lf2, (size_t)ng},
                           {ho.extinction, o_ext, (size_t)ng}, {ho.momentum, o_mom, 3 * (size_t)ng},
                           {ho.lum_factor, o_lumf, (size_t)n_src * (size_t)ng}};
     SPHX_TRY(sphx_download_f64(ctx, ps, 6));
-    SPHX_TRY(ctx->rad_t.mark(ctx, 4));
+    if (t) SPHX_TRY(t->mark(ctx, 4));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    return ctx->rad_t.end(ctx);
+    if (dev) { dev->lf2 = o_lf2; dev->ext = o_ext; dev->mom = o_mom; dev->ng = ng; }
+    return t ? t->end(ctx) : SPHX_OK;
 }
 
 // host arrays -> ctx->rad_in / rad_soa; fills pa's inputs and outputs (ptype may be NULL)
@@ -394,7 +399,7 @@ extern "C" int sphx_rad_columns(sphx_ctx* ctx, int64_t n, const double* points, 
     RadPart pa;
     SPHX_TRY(rad_stage_host(ctx, n, points, nullptr, mass, sizes, cross, mu, &pa));
     const RadHostOut ho{nullptr, nullptr, nullptr, blocked, star_distance, nullptr};
-    return rad_run(ctx, "sphx_rad_columns", pa, n_src, src, nullptr, n_dst, dst, 0.0, mode, false, ho);
+    return rad_run(ctx, "sphx_rad_columns", pa, n_src, src, nullptr, n_dst, dst, 0.0, mode, false, ho, false, &ctx->rad_t, nullptr);
 }
 
 extern "C" int sphx_rad_transfer(sphx_ctx* ctx, int64_t n, const double* points, const double* ptypes, const double* mass,
@@ -412,7 +417,7 @@ extern "C" int sphx_rad_transfer(sphx_ctx* ctx, int64_t n, const double* points,
     RadPart pa;
     SPHX_TRY(rad_stage_host(ctx, n, points, ptypes, mass, sizes, cross, mu, &pa));
     const RadHostOut ho{lf2, momentum, extinction, blocked, star_distance, lum_factor};
-    return rad_run(ctx, "sphx_rad_transfer", pa, n_src, src, luminosities, n_dst, dst, dt, mode, true, ho);
+    return rad_run(ctx, "sphx_rad_transfer", pa, n_src, src, luminosities, n_dst, dst, dt, mode, true, ho, false, &ctx->rad_t, nullptr);
 }
 
 // The same on the step loop's resident state.  Everything is read into buffers of this file's own, in the caller's
@@ -453,5 +458,25 @@ extern "C" int sphx_state_rad_transfer(sphx_ctx* ctx, const double* cross, int64
     pa.m = in + 3 * nn; pa.ptype = in + 4 * nn; pa.sizes = in + 5 * nn; pa.cross = in + 6 * nn; pa.mu = in + 7 * nn;
     pa.flag = nullptr;
     const RadHostOut ho{lf2, momentum, extinction, blocked, star_distance, lum_factor};
-    return rad_run(ctx, "sphx_state_rad_transfer", pa, n_src, src, luminosities, n_dst, dst, dt, mode, true, ho);
+    return rad_run(ctx, "sphx_state_rad_transfer", pa, n_src, src, luminosities, n_dst, dst, dt, mode, true, ho, false, &ctx->rad_t, nullptr);
+}
+
+// nsc:922-965 on particle attributes that are on the device already, in the caller's particle order (the resident
+// radiative phase, sphx_phase.hip): x, y, z SoA; src and dst device pointers; lum on the host.  No timer of this family
+// is touched.  The same kernels on the same values as sphx_rad_transfer: the same bits.
+int sphx_rad_run_dev(sphx_ctx* ctx, const char* who, int64_t n, const double* x, const double* y, const double* z, const double* m,
+                     const double* ptype, const double* sizes, const double* cross, const double* mu, int64_t n_src,
+                     const double* src_dev, const double* lum_host, int64_t n_dst, const double* dst_dev, double dt, int mode,
+                     RadDevOut* out) {
+    SPHX_TRY(rad_check(ctx, who, n, n_src, src_dev, n_dst, dst_dev, mode));
+    const size_t nn = (size_t)n;
+    SPHX_TRY(sphx_ensure(ctx, ctx->rad_soa, 5 * nn * sizeof(double)));
+    double* soa = ctx->rad_soa.as<double>();
+    RadPart pa;
+    pa.n = (int)n;
+    pa.x = x; pa.y = y; pa.z = z; pa.h2 = soa + 3 * nn; pa.w = soa + 4 * nn;
+    pa.m = m; pa.ptype = ptype; pa.sizes = sizes; pa.cross = cross; pa.mu = mu;
+    pa.flag = nullptr;
+    const RadHostOut ho{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return rad_run(ctx, who, pa, n_src, src_dev, lum_host, n_dst, dst_dev, dt, mode, true, ho, true, nullptr, out);
 }

@@ -304,6 +304,86 @@ class Simulation:
         c.check(c.lib.sphx_phase_last_timing(c.h, dp(ms)))
         return dict(zip(("gather", "density", "chem", "dust", "bookkeeping"), ms.tolist()))
 
+    # ---- the radiative block of the time loop (code_running.py:247-316) on the resident state ------------------------
+    RADPHASE_STAGES = ("cross_array", "lf2", "momentum", "extinction", "f_un_ionised", "frac_destroyed", "mu_heat", "gamma_heat",
+                       "cross_heat", "E_heat", "T_heat", "energy", "rec_array", "cross_array_out")
+
+    def rad_phase(self, dt, d, source_ids, luminosities, target_ids, frac_dest, photons_per_joule, t_max, cooling_timescale,
+                  mode="line", full=False, t_cmb=None, mu_specie=None, gamma=None, cross_sections=None, driver_cross=None):
+        """code_running.py:247-316 with N_RADIATIVE = 1 on the state as it is on the device (include/sphx.h
+        sphx_state_rad_phase): rad_transfer, the photoionisation chemistry, the heating's bookkeeping, rad_cooling on the
+        last step's own list, the cooling's bookkeeping - and f_un, mu_array, gamma_array, E_internal, T and the velocities
+        written where the next step() and dust_phase() read them.  source_ids, luminosities, target_ids as compat.rad_setup
+        returns them (particle indices of the uploaded state), frac_dest and photons_per_joule as compat.stellar_spectrum
+        does; t_max and cooling_timescale are undefined in the driver and have no default; the tables as compat.rad_phase
+        takes them.  -> dict of totals (compat.rad_phase's: skipped, E_before, E_after_heating, E_after_cooling, the clamp
+        counts); full=True adds every stage's output (RADPHASE_STAGES) in the particle order of the uploaded state.  With
+        no star the driver skips the block: {"skipped": True}, nothing written.  With with_drag=True the drag coefficients
+        are formed again from the new f_un.  The bits are those of compat.rad_phase on the downloaded state and
+        neighbors().  Needs with_species=True and one step."""
+        from . import compat
+        n = self.n
+        S = self.n_species or int(np.shape(mu_specie if mu_specie is not None else compat.mu_specie)[0])
+        code = rad_mode_code(mode)
+        mus, gam = compat.chem_table(S, mu_specie, "mu_specie"), compat.chem_table(S, gamma, "gamma")
+        cs = compat.chem_table(S, cross_sections, "cross_sections")
+        csd = compat.driver_cross_sections(S) if driver_cross is None else compat.chem_table(S, driver_cross, "cross_sections")
+        fd = f64(frac_dest, (S,))
+        src = np.ascontiguousarray(np.asarray(source_ids, dtype=np.int64).reshape(-1))
+        dst = np.ascontiguousarray(np.asarray(target_ids, dtype=np.int64).reshape(-1))
+        L = f64(luminosities).reshape(-1)
+        if L.shape[0] != src.shape[0]:
+            raise ValueError("luminosities must have one entry per source")
+        gm = se = None
+        if self._with_drag:
+            gm = np.ascontiguousarray(compat.grain_mass(), dtype=np.float64)
+            se = np.ascontiguousarray(compat.sigma_effective(), dtype=np.float64)
+            if gm.shape != (S,) or se.shape != (S,):
+                raise ValueError("with_drag: grain_mass and sigma_effective hold %d species, the state %d" % (gm.shape[0], S))
+        if not hasattr(self, "_n_gas"):
+            self._n_gas = int(np.count_nonzero(self._ptype != 1))
+        G = self._n_gas
+        st = {}
+        heat = None
+        if full:
+            st = dict(cross_array=np.zeros(n), lf2=np.zeros(G), momentum=np.zeros((G, 3)), extinction=np.zeros(G),
+                      f_un_ionised=np.zeros((n, S)), frac_destroyed=np.zeros((G, 3)), energy=np.zeros(n), rec_array=np.zeros((S, n)),
+                      cross_array_out=np.zeros(n))
+            heat = np.zeros((5, n))
+        tot = np.zeros(3); cnt = np.zeros(8, dtype=np.int64); ng = np.zeros(1, dtype=np.int64)
+        skipped = C.c_int(0)
+        c = self.ctx
+        # the physics stages read these from the context, as compat's array calls set them on theirs
+        c.set_constants(k_B=compat.k, amu=compat.amu, m_h=compat.m_h, m_0=compat.m_0, solar_luminosity=compat.solar_luminosity, c=compat.c)
+        c.check(c.lib.sphx_state_rad_phase(
+            c.h, float(dt), float(d), src.shape[0], _lib.ip(src), dp(L), dst.shape[0], _lib.ip(dst), dp(fd), float(photons_per_joule),
+            dp(mus), dp(gam), dp(cs), dp(csd), float(compat.amu), float(compat.t_cmb if t_cmb is None else t_cmb), float(t_max),
+            float(cooling_timescale), float(compat.sb), float(compat.k), float(compat.m_h), code, dp(gm), dp(se),
+            dp(st.get("cross_array")), dp(st.get("lf2")), dp(st.get("momentum")), dp(st.get("extinction")), dp(st.get("f_un_ionised")),
+            dp(st.get("frac_destroyed")), dp(heat), dp(st.get("energy")), dp(st.get("rec_array")), dp(st.get("cross_array_out")),
+            dp(tot), _lib.ip(cnt), _lib.ip(ng), C.byref(skipped)))
+        if skipped.value:
+            return dict(skipped=True)
+        if int(ng[0]) != G:
+            raise RuntimeError("the state holds %d non-star particles, the uploaded particle_type %d" % (int(ng[0]), G))
+        self._phase_ran = True
+        out = dict(skipped=False, E_before=float(tot[0]), E_after_heating=float(tot[1]), E_after_cooling=float(tot[2]))
+        for q, nm in enumerate(compat.RADPHASE_COUNTS):
+            out["heat_" + nm], out["cool_" + nm] = int(cnt[q]), int(cnt[4 + q])
+        if full:
+            for q, nm in enumerate(("mu_heat", "gamma_heat", "cross_heat", "E_heat", "T_heat")):
+                st[nm] = heat[q].copy()
+            out.update(st)
+        return out
+
+    def radphase_timing(self):
+        """Device time of the last rad_phase() from HIP events -> dict of ms: gather, transfer, ionise_heat, cooling,
+        bookkeeping (the last with the write-back and the outputs coming back)."""
+        ms = np.zeros(5)
+        c = self.ctx
+        c.check(c.lib.sphx_state_radphase_last_timing(c.h, dp(ms)))
+        return dict(zip(("gather", "transfer", "ionise_heat", "cooling", "bookkeeping"), ms.tolist()))
+
     # ---- snapshot / restart and per-step diagnostics (SURVEY 8f-4; the reference only wrote summary
     # statistics at the end of a run, sph/code_running.py:670, and printed the mass-weighted net
     # accelerations every step, sph/code_running.py:465-468) ----------------------------------------
