@@ -14,10 +14,10 @@
 //   row A     one lane per dust row: the gas weights of its entries, their sums, whether it contributes, the
 //             temperature, the reuptake weight wk of every entry (three normalisations over the stored column).
 //   row B     one lane per (dust row, column >= 6): the composition density, F_sput, new0.
-//   reverse   for each gas particle the (contributing row, entry) pairs that hold it: count, exclusive scan, fill, each
-//             slice sorted.  An entry is the 4-byte key ordinal K + k: ascending keys are ascending rows.  (The same
-//             sequence as sphx_cool.hip's and sphx_dust.hip's, a copy of its own: DESIGN 5.11.)  `pos` maps a row's
-//             entry back to its place in the reverse list.
+//   reverse   for each gas particle the (contributing row, entry) pairs that hold it: count, then scan, fill
+//             (chem_fill_kernel) and the sort of each slice by sphx_rev_build (sphx_side.hip, which rad_cooling and
+//             supernova_destruction use as well).  An entry is the 4-byte key ordinal K + k: ascending keys are
+//             ascending rows.  `pos` maps a row's entry back to its place in the reverse list.
 //   gas pass  one lane per (gas particle, column >= 6): walks the slice in ascending row with the running count in a
 //             register, applies clamps 1 and 2 to new0 wk, stores the clamped first-stage loss per (pair, column), then
 //             subtracts the previous round's nan_to_num(sumc wk).
@@ -32,7 +32,6 @@
 // only.  Every operation separately rounded, as NumPy's are; double where the reference has longdouble.
 #include "sphx_internal.h"
 #include "sphx_chem_pair.h"
-#include <rocprim/rocprim.hpp>
 #include <cstring>
 #pragma clang fp contract(off)
 
@@ -100,8 +99,7 @@ __global__ __launch_bounds__(CHEM_WG) void chem_list_kernel(int n, int npad, int
     const long long e = (long long)blockIdx.x * CHEM_WG + threadIdx.x;
     if (e >= (long long)n * k) return;
     const int j = (int)(e / k), kk = (int)(e - (long long)j * k);
-    const long long q = nb[e];
-    nbr[(size_t)kk * npad + j] = (q >= 0 && q < n) ? (int)q : -1;
+    nbr[(size_t)kk * npad + j] = sphx_list_entry64(nb[e], n);
 }
 
 // what the kernels after the scan of the dust flags share
@@ -381,8 +379,6 @@ __global__ __launch_bounds__(CHEM_WG) void chem_final_kernel(int n, int s, const
 // (sphx_chem_tables, chem_stage_host), the run on device inputs (sphx_chem_run: sphx_state_dust_phase calls it on the
 // gathered resident state and leaves the outputs where they are), the outputs brought back.
 // =====================================================================================================================
-static bool chem_finite(double v) { return v - v == 0.0; }
-static size_t chem_up4(size_t v) { return (v + 3) & ~size_t(3); }
 
 // the range checks every caller shares: the shape, then (behind the callers' NULL checks) the scalars
 int sphx_chem_check_shape(sphx_ctx* ctx, const char* who, int64_t n, int k, int s) {
@@ -395,8 +391,8 @@ int sphx_chem_check_shape(sphx_ctx* ctx, const char* who, int64_t n, int k, int 
 }
 int sphx_chem_check_scalars(sphx_ctx* ctx, const char* who, double d, double dt, const double mrn[2], double k_B, double amu,
                             double m_0) {
-    if (!chem_finite(d) || !chem_finite(dt) || !chem_finite(k_B) || !chem_finite(amu) || !chem_finite(m_0) || !chem_finite(mrn[0]) ||
-        !chem_finite(mrn[1]))
+    if (!sphx_finite(d) || !sphx_finite(dt) || !sphx_finite(k_B) || !sphx_finite(amu) || !sphx_finite(m_0) || !sphx_finite(mrn[0]) ||
+        !sphx_finite(mrn[1]))
         return sphx_set_err(ctx, SPHX_E_ARG, "%s: d=%g, dt=%g, k_B=%g, amu=%g, m_0=%g, mrn=(%g, %g) must be finite", who, d, dt, k_B, amu,
                             m_0, mrn[0], mrn[1]);
     return SPHX_OK;
@@ -409,7 +405,7 @@ int sphx_chem_tables(sphx_ctx* ctx, const char* who, int s, const double* mu_spe
     const double c0 = -(pow(mrn[1], -0.5) - pow(mrn[0], -0.5)) / (pow(mrn[1], 0.5) - pow(mrn[0], 0.5));   // nsc:1305
     double symax = sputtering_yields[0];
     for (int t = 0; t < s; ++t) {
-        if (!chem_finite(mu_specie[t]) || !chem_finite(mineral_densities[t]) || !chem_finite(sputtering_yields[t]))
+        if (!sphx_finite(mu_specie[t]) || !sphx_finite(mineral_densities[t]) || !sphx_finite(sputtering_yields[t]))
             return sphx_set_err(ctx, SPHX_E_ARG, "%s: table entry %d must be finite", who, t);
         tab[t] = mu_specie[t];
         tab[s + t] = c0 / (3.0 * mineral_densities[t]);
@@ -453,7 +449,7 @@ static int chem_stage_host(sphx_ctx* ctx, int64_t n, int k, int s, const double*
     HIPCHK(hipMemcpyAsync(ctx->chem_nb.p, neighbor, nk * sizeof(int64_t), hipMemcpyHostToDevice, st));
     int* nbr;
     SPHX_TRY(sphx_chem_ints(ctx, n, k, &nbr));
-    hipLaunchKernelGGL(chem_list_kernel, dim3((unsigned)((nk + CHEM_WG - 1) / CHEM_WG)), dim3(CHEM_WG), 0, st, (int)n, (int)npad, k,
+    hipLaunchKernelGGL(chem_list_kernel, dim3(sphx_blocks(nk, CHEM_WG)), dim3(CHEM_WG), 0, st, (int)n, (int)npad, k,
                        (const long long*)ctx->chem_nb.p, nbr);
     HIPCHK(hipGetLastError());
     *nbr_out = nbr;
@@ -489,7 +485,7 @@ int sphx_chem_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
     ChemPrep pa;
     pa.n = (int)n; pa.s = s; pa.pos = d_pos; pa.m = d_m; pa.mu = d_mu; pa.T = d_T; pa.ptype = d_pt; pa.fun = d_fun; pa.mus = d_tab;
     pa.d = d; pa.m0 = par.m_0; pa.rec = ctx->chem_rec.as<ChemRec>(); pa.num0 = num0; pa.numfin = numfin; pa.isd = isd;
-    const unsigned nblk = (unsigned)((nn + CHEM_WG - 1) / CHEM_WG);
+    const unsigned nblk = sphx_blocks(nn, CHEM_WG);
     hipLaunchKernelGGL(chem_prep_kernel, dim3(nblk), dim3(CHEM_WG), 0, st, pa);
     HIPCHK(hipGetLastError());
     SPHX_TRY(sphx_excl_scan_int(ctx, isd, ord, (int)n));                 // (isd[n] = 0: the memset above; both start on 16-byte boundaries)
@@ -527,37 +523,29 @@ int sphx_chem_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
         double* new2[2] = {ra.new0 + 3 * row, ra.new0 + 4 * row};
         ra.sumc0 = sumc[0]; ra.new20 = new2[0];
         ra.counts = d_cnt;
-        const unsigned rblk = (unsigned)((nd * (size_t)ns + CHEM_WG - 1) / CHEM_WG);
+        const unsigned rblk = sphx_blocks(nd * (size_t)ns, CHEM_WG);
         hipLaunchKernelGGL(chem_row_a_kernel, dim3(nblk), dim3(CHEM_WG), 0, st, ra);
         hipLaunchKernelGGL(chem_row_b_kernel, dim3(rblk), dim3(CHEM_WG), 0, st, ra);
         hipLaunchKernelGGL(chem_fold_kernel, dim3(1), dim3(64), 0, st, d_cnt, (int)CH_ROWS, 1);
         HIPCHK(hipGetLastError());
         if (t) SPHX_TRY(t->mark(ctx, 2));
-        // ---- the reverse list: count, scan, fill, sort each slice, positions ----
-        const unsigned eblk = (unsigned)(((size_t)k * ndpad + CHEM_WG - 1) / CHEM_WG);
+        // ---- the reverse list: count; scan, fill and sort of keys ordinal k + kk (sphx_rev_build); positions ----
+        const unsigned eblk = sphx_blocks((size_t)k * ndpad, CHEM_WG);
         hipLaunchKernelGGL(chem_count_kernel, dim3(eblk), dim3(CHEM_WG), 0, st, ra, cnt);
         HIPCHK(hipGetLastError());
-        SPHX_TRY(sphx_excl_scan_int(ctx, cnt, start, (int)n));
-        HIPCHK(hipMemcpyAsync(&ctx->pinned->side.count, start + n, sizeof(int), hipMemcpyDeviceToHost, st));
+        // (the row counter rides on the builder's synchronise)
         HIPCHK(hipMemcpyAsync(ctx->pinned->side.red, d_cnt + CH_ROWS - CH_ROWS % 4, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        M = (size_t)ctx->pinned->side.count;
+        RevList rl;
+        SPHX_TRY(sphx_rev_build(ctx, who, n, cnt, start, (size_t)k * nd, (unsigned long long)nd * (unsigned long long)k,
+                                [&](const int* start_, int* rev_raw) {
+                                    hipLaunchKernelGGL(chem_fill_kernel, dim3(eblk), dim3(CHEM_WG), 0, st, ra, start_, cur, rev_raw);
+                                }, &rl));
+        M = rl.M;
         std::memcpy(hc + CH_ROWS - CH_ROWS % 4, ctx->pinned->side.red, 4 * sizeof(double));
-        if (M > (size_t)k * nd) return sphx_set_err(ctx, SPHX_E_HIP, "%s: reverse list of %zu entries from %zu pairs", who, M, (size_t)k * nd);
         if (M > 0) {
-            SPHX_TRY(sphx_ensure(ctx, ctx->chem_rev, 2 * (M + 4) * sizeof(int)));
             SPHX_TRY(sphx_ensure(ctx, ctx->chem_first, M * (size_t)ns * sizeof(double)));
-            int* rev_raw = ctx->chem_rev.as<int>();
-            int* rev = rev_raw + chem_up4(M + 1);
-            hipLaunchKernelGGL(chem_fill_kernel, dim3(eblk), dim3(CHEM_WG), 0, st, ra, start, cur, rev_raw);
-            HIPCHK(hipGetLastError());
-            unsigned bits = 1;
-            while (bits < 32 && (1ull << bits) < (unsigned long long)nd * (unsigned long long)k) ++bits;
-            size_t sort_bytes = 0;
-            HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
-            SPHX_TRY(sphx_ensure(ctx, ctx->chem_tmp, sort_bytes + 64));
-            HIPCHK(rocprim::segmented_radix_sort_keys(ctx->chem_tmp.p, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
-            hipLaunchKernelGGL(chem_pos_kernel, dim3((unsigned)((M + CHEM_WG - 1) / CHEM_WG)), dim3(CHEM_WG), 0, st, (int)M, k, (int)ndpad, rev, pos);
+            const int* rev = rl.rev;
+            hipLaunchKernelGGL(chem_pos_kernel, dim3(sphx_blocks(M, CHEM_WG)), dim3(CHEM_WG), 0, st, (int)M, k, (int)ndpad, rev, pos);
             HIPCHK(hipGetLastError());
             if (t) SPHX_TRY(t->mark(ctx, 3));
             // ---- the rounds: until one changes no bit; (contributing rows + 1) always suffice ----
@@ -566,7 +554,7 @@ int sphx_chem_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
             wa.nbr = nbr; wa.ord = ord; wa.dustid = ra.dustid; wa.contrib = ra.contrib; wa.start = start; wa.rev = rev; wa.pos = pos;
             wa.rec = pa.rec; wa.num0 = num0; wa.wk = ra.wk; wa.new0 = ra.new0;
             wa.first = ctx->chem_first.as<double>(); wa.numfin = numfin; wa.counts = d_cnt;
-            const unsigned gblk = (unsigned)((nn * (size_t)ns + CHEM_WG - 1) / CHEM_WG);
+            const unsigned gblk = sphx_blocks(nn * (size_t)ns, CHEM_WG);
             const int64_t limit = (int64_t)hc[CH_ROWS] + 1;
             for (;;) {
                 const int a = (int)(rounds & 1);
@@ -590,7 +578,7 @@ int sphx_chem_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
     }
     if (t) SPHX_TRY(t->mark(ctx, 4));
     // ---- the closing correction, the outputs ----
-    hipLaunchKernelGGL(chem_colsum_kernel, dim3((unsigned)((nchunk * (size_t)s + CHEM_WG - 1) / CHEM_WG)), dim3(CHEM_WG), 0, st, (int)n, s,
+    hipLaunchKernelGGL(chem_colsum_kernel, dim3(sphx_blocks(nchunk * (size_t)s, CHEM_WG)), dim3(CHEM_WG), 0, st, (int)n, s,
                        (int)nchunk, numfin, part);
     hipLaunchKernelGGL(chem_colfac_kernel, dim3((unsigned)s), dim3(CHEM_WG), 0, st, s, (int)nchunk, part, fac, d_cnt);
     hipLaunchKernelGGL(chem_final_kernel, dim3(nblk), dim3(CHEM_WG), 0, st, (int)n, s, numfin, fac, d_tab, d_mass, d_fnew);

@@ -9,17 +9,16 @@
 //             coalesced (an entry outside [0, n) becomes -1 and contributes nothing), the rows that contribute are
 //             flagged (a gas row with a gas neighbour, nsc:1028-1030) and the gas-gas pairs are counted per neighbour.
 //   rows      one lane per row: the sums over K in list order, the six row scalars -> table (n,6).
-//   reverse   the scatter is turned round: for each particle p the rows j that hold it - count (above), exclusive scan,
-//             fill, then each slice sorted, so that p adds its contributions in ascending j, the order the reference's
-//             loop adds them in.  An entry is a 4-byte row index.  The fill's order is whatever the atomics give; the
-//             sort removes it: the same inputs give the same bits on every call.  No floating-point atomic anywhere.
+//   reverse   the scatter is turned round: for each particle p the rows j that hold it - count (above), then scan, fill
+//             (cool_fill_kernel) and the sort of each slice by sphx_rev_build (sphx_side.hip), so that p adds its
+//             contributions in ascending j, the order the reference's loop adds them in.  An entry is a 4-byte row
+//             index.  The same inputs give the same bits on every call.  No floating-point atomic anywhere.
 //   gather    one lane per particle p: walks its slice (of any length: a hub particle sits in many rows), recomputes
 //             the pair's weight and masks from its own record and x_j - cool_pair on the same r^2 the row pass used -
 //             reads row j's six scalars, and then runs the elementwise epilogue (nsc:1112-1176) on what it holds.
 // Vector stores from plain C++ only.  Every operation separately rounded, as NumPy's are.
 #include "sphx_internal.h"
 #include "sphx_cool_pair.h"
-#include <rocprim/rocprim.hpp>
 #pragma clang fp contract(off)
 
 #define COOL_WG SPHX_COOL_WG
@@ -65,8 +64,7 @@ __global__ __launch_bounds__(COOL_WG) void cool_list_kernel(int n, int npad, int
         const int q = nbr[(size_t)kk * npad + j];
         p = (q >= 0 && q < n) ? q : -1;
     } else {
-        const long long q = nb[e];
-        p = (q >= 0 && q < n) ? (int)q : -1;
+        p = sphx_list_entry64(nb[e], n);
         nbr[(size_t)kk * npad + j] = p;
     }
     if (p >= 0 && ptype[j] == 0.0 && ptype[p] == 0.0) {
@@ -210,8 +208,8 @@ int sphx_cool_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
     pa.n = (int)n; pa.s = s; pa.pos = in.pos; pa.ptype = in.pt; pa.m = in.m; pa.mu = in.mu; pa.T = in.T; pa.fun = in.fun;
     pa.d = d; pa.m0 = ctx->cst.m_0; pa.m_h = ctx->cst.m_h; pa.kB = ctx->cst.k_B;
     pa.rec = ctx->cool_rec.as<CoolRec>();
-    const unsigned nblk = (unsigned)((nn + COOL_WG - 1) / COOL_WG);
-    const dim3 lgrid((unsigned)((nk + COOL_WG - 1) / COOL_WG));
+    const unsigned nblk = sphx_blocks(nn, COOL_WG);
+    const dim3 lgrid(sphx_blocks(nk, COOL_WG));
     hipLaunchKernelGGL(cool_prep_kernel, dim3(nblk), dim3(COOL_WG), 0, st, pa);
     if (nb64) hipLaunchKernelGGL(cool_list_kernel<false>, lgrid, dim3(COOL_WG), 0, st, (int)n, (int)npad, k, nb64, in.pt, nbr, cnt, flag);
     else hipLaunchKernelGGL(cool_list_kernel<true>, lgrid, dim3(COOL_WG), 0, st, (int)n, (int)npad, k, nb64, in.pt, nbr, cnt, flag);
@@ -225,30 +223,16 @@ int sphx_cool_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
     hipLaunchKernelGGL(cool_row_kernel, dim3(nblk), dim3(COOL_WG), 0, st, ra);
     HIPCHK(hipGetLastError());
     if (t) SPHX_TRY(t->mark(ctx, 2));
-    // ---- the reverse list: scan, fill, sort each slice ----
-    SPHX_TRY(sphx_excl_scan_int(ctx, cnt, start, (int)n));             // (cnt[n] = 0: the memset above; both start on 16-byte boundaries)
-    HIPCHK(hipMemcpyAsync(&ctx->pinned->side.count, start + n, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const size_t M = (size_t)ctx->pinned->side.count;
-    if (M > nk) return sphx_set_err(ctx, SPHX_E_HIP, "%s: reverse list of %zu entries from %zu pairs", who, M, nk);
-    SPHX_TRY(sphx_ensure(ctx, ctx->cool_rev, 2 * (M + 4) * sizeof(int)));
-    int* rev_raw = ctx->cool_rev.as<int>();
-    int* rev = rev_raw + M + 4;
-    if (M > 0) {
-        hipLaunchKernelGGL(cool_fill_kernel, dim3((unsigned)(((size_t)k * npad + COOL_WG - 1) / COOL_WG)), dim3(COOL_WG), 0, st, (int)n,
-                           (int)npad, k, nbr, in.pt, start, cur, rev_raw);
-        HIPCHK(hipGetLastError());
-        unsigned bits = 1;
-        while (bits < 32 && (1ull << bits) < (unsigned long long)n) ++bits;
-        size_t sort_bytes = 0;
-        HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
-        SPHX_TRY(sphx_ensure(ctx, ctx->cool_tmp, sort_bytes + 64));
-        HIPCHK(rocprim::segmented_radix_sort_keys(ctx->cool_tmp.p, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
-    }
+    // ---- the reverse list: keys are rows (cnt[n] = 0: the memset above; cnt and start lie on 16-byte boundaries) ----
+    RevList rl;
+    SPHX_TRY(sphx_rev_build(ctx, who, n, cnt, start, nk, (unsigned long long)n, [&](const int* start_, int* rev_raw) {
+        hipLaunchKernelGGL(cool_fill_kernel, dim3(sphx_blocks((size_t)k * npad, COOL_WG)), dim3(COOL_WG), 0, st, (int)n, (int)npad, k, nbr,
+                           in.pt, start_, cur, rev_raw);
+    }, &rl));
     // ---- gather and epilogue: final_comp (n s) | energy (n) | rec_array (s n) ----
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_out, (2 * ns + nn) * sizeof(double)));
     CoolGather ga;
-    ga.n = (int)n; ga.s = s; ga.start = start; ga.rev = rev; ga.rec = pa.rec; ga.tab = ra.tab; ga.fun = in.fun; ga.d = d;
+    ga.n = (int)n; ga.s = s; ga.start = start; ga.rev = rl.rev; ga.rec = pa.rec; ga.tab = ra.tab; ga.fun = in.fun; ga.d = d;
     ga.final_comp = ctx->cool_out.as<double>(); ga.energy = ga.final_comp + ns; ga.rec_array = ga.energy + nn;
     hipLaunchKernelGGL(cool_gather_kernel, dim3(nblk), dim3(COOL_WG), 0, st, ga);
     HIPCHK(hipGetLastError());
@@ -261,7 +245,7 @@ int sphx_cool_check(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, dou
         return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld, k=%d, s=%d (need n >= 1, k >= 1, s >= 6)", who, (long long)n, k, s);
     if (n > 0x7FFFFFF0ll || sphx_pad64(n) * (int64_t)k > 0x7FFFFFF0ll || n * (int64_t)s > (1ll << 40))
         return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld x k=%d (or x s=%d) out of range", who, (long long)n, k, s);
-    if (!(dt - dt == 0.0) || !(d - d == 0.0))
+    if (!sphx_finite(dt) || !sphx_finite(d))
         return sphx_set_err(ctx, SPHX_E_ARG, "%s: dt=%g, d=%g must be finite", who, dt, d);
     return SPHX_OK;
 }

@@ -10,10 +10,9 @@
 //             (an entry outside [0, n) becomes -1), the (gas row, dust entry) pairs are counted per dust particle, and the
 //             row's flag collects "has a dust entry", "some rho > 0", "some rho is NaN" (integer atomics): the row
 //             contributes when sum_k rho > 0 (nsc:1239), i.e. when the flag is 3.
-//   reverse   for each dust particle i the pairs that hold it - count (above), exclusive scan, fill, then each slice
-//             sorted.  An entry is the 4-byte key j K + k: ascending keys are ascending rows, and the key names the slot.
-//             The fill's order is whatever the atomics give; the sort removes it.  (The same sequence as sphx_cool.hip's,
-//             kept as a copy of its own: the fill's predicate and what it stores differ)
+//   reverse   for each dust particle i the pairs that hold it - count (above), then scan, fill (dust_fill_kernel) and the
+//             sort of each slice by sphx_rev_build (sphx_side.hip, which rad_cooling and chemisputtering_2 use as well).
+//             An entry is the 4-byte key j K + k: ascending keys are ascending rows, and the key names the slot.
 //   dust      one lane per particle i: walks its slice in ascending key with acc[t] in registers for the selected
 //             species, applies the guard, leaves one word of accept bits per pair in an (K, npad) array, counts the
 //             regimes (integer atomics, one per wave and counter), writes frac_destruction[i,:].
@@ -23,7 +22,6 @@
 // only.  Every operation separately rounded, as NumPy's are.
 #include "sphx_internal.h"
 #include "sphx_dust_pair.h"
-#include <rocprim/rocprim.hpp>
 #pragma clang fp contract(off)
 
 #define DUST_WG SPHX_DUST_WG
@@ -72,8 +70,7 @@ __global__ __launch_bounds__(DUST_WG) void dust_list_kernel(int n, int npad, int
         if (e >= (long long)n * k) return;
         j = (int)(e / k);
         const int kk = (int)(e - (long long)j * k);
-        const long long q = nb[e];
-        p = (q >= 0 && q < n) ? (int)q : -1;
+        p = sphx_list_entry64(nb[e], n);
         nbr_out[(size_t)kk * npad + j] = p;
     } else {
         if (e >= (long long)npad * k) return;
@@ -210,7 +207,6 @@ __global__ __launch_bounds__(DUST_WG) void dust_row_kernel(DustWalk a) {
 // gathered resident state and leaves the outputs where they are), the outputs brought back.
 // =====================================================================================================================
 static_assert(sizeof(DustKnots) <= 40 * sizeof(double), "sphx_ctx::dust_kn holds the knots");
-static bool dust_finite(double v) { return v - v == 0.0; }
 
 int sphx_dust_check_shape(sphx_ctx* ctx, const char* who, int64_t n, int k, int s) {
     if (n < 1 || k < 1 || k > 64 || s < 1 || s > SPHX_MAX_SPECIES)
@@ -221,7 +217,7 @@ int sphx_dust_check_shape(sphx_ctx* ctx, const char* who, int64_t n, int k, int 
     return SPHX_OK;
 }
 int sphx_dust_check_scalars(sphx_ctx* ctx, const char* who, double crit_mass, double critical_density, int guard_mode) {
-    if (!dust_finite(crit_mass) || !dust_finite(critical_density))
+    if (!sphx_finite(crit_mass) || !sphx_finite(critical_density))
         return sphx_set_err(ctx, SPHX_E_ARG, "%s: crit_mass=%g, critical_density=%g must be finite", who, crit_mass, critical_density);
     if (guard_mode != SPHX_DUST_GUARD_COUNT && guard_mode != SPHX_DUST_GUARD_FRACTION)
         return sphx_set_err(ctx, SPHX_E_ARG, "%s: unknown guard mode %d", who, guard_mode);
@@ -241,7 +237,7 @@ int sphx_dust_params(sphx_ctx* ctx, const char* who, int s, double crit_mass, do
         if (species_curve[t] == 2) par->si |= 1u << t;
     }
     for (int t = 0; t < 8; ++t) {
-        if (!dust_finite(knots_v[t]) || !dust_finite(knots_c[t]) || !dust_finite(knots_si[t]) || (t && !(knots_v[t] > knots_v[t - 1])))
+        if (!sphx_finite(knots_v[t]) || !sphx_finite(knots_c[t]) || !sphx_finite(knots_si[t]) || (t && !(knots_v[t] > knots_v[t - 1])))
             return sphx_set_err(ctx, SPHX_E_ARG, "%s: knot %d must be finite and knots_v increasing", who, t);
         kn.v[t] = knots_v[t]; kn.c[t] = knots_c[t]; kn.si[t] = knots_si[t];
     }
@@ -302,43 +298,28 @@ int sphx_dust_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
     pa.n = (int)n; pa.pos = in.pos; pa.vel = in.vel; pa.m = in.m; pa.mu = in.mu; pa.sizes = in.sizes;
     pa.crit_mass = par.crit_mass; pa.amu = par.amu;
     pa.rec = ctx->dust_rec.as<DustRec>();
-    const unsigned nblk = (unsigned)((nn + DUST_WG - 1) / DUST_WG);
+    const unsigned nblk = sphx_blocks(nn, DUST_WG), eblk = sphx_blocks((size_t)k * npad, DUST_WG);
     hipLaunchKernelGGL(dust_prep_kernel, dim3(nblk), dim3(DUST_WG), 0, st, pa);
     if (nbr_given)
-        hipLaunchKernelGGL(dust_list_kernel<false>, dim3((unsigned)(((size_t)k * npad + DUST_WG - 1) / DUST_WG)), dim3(DUST_WG), 0, st, (int)n,
-                           (int)npad, k, (const long long*)nullptr, nbr, d_pt, pa.rec, (int*)nullptr, cnt, flag);
+        hipLaunchKernelGGL(dust_list_kernel<false>, dim3(eblk), dim3(DUST_WG), 0, st, (int)n, (int)npad, k, (const long long*)nullptr, nbr,
+                           d_pt, pa.rec, (int*)nullptr, cnt, flag);
     else
-        hipLaunchKernelGGL(dust_list_kernel<true>, dim3((unsigned)((nk + DUST_WG - 1) / DUST_WG)), dim3(DUST_WG), 0, st, (int)n, (int)npad, k,
+        hipLaunchKernelGGL(dust_list_kernel<true>, dim3(sphx_blocks(nk, DUST_WG)), dim3(DUST_WG), 0, st, (int)n, (int)npad, k,
                            (const long long*)ctx->dust_nb.p, (const int*)nullptr, d_pt, pa.rec, own, cnt, flag);
     HIPCHK(hipGetLastError());
     if (t) SPHX_TRY(t->mark(ctx, 1));
-    // ---- the reverse list: scan, fill, sort each slice ----
-    SPHX_TRY(sphx_excl_scan_int(ctx, cnt, start, (int)n));             // (cnt[n] = 0: the memset above; both start on 16-byte boundaries)
-    HIPCHK(hipMemcpyAsync(&ctx->pinned->side.count, start + n, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const size_t M = (size_t)ctx->pinned->side.count;
-    if (M > nk) return sphx_set_err(ctx, SPHX_E_HIP, "%s: reverse list of %zu entries from %zu pairs", who, M, nk);
-    SPHX_TRY(sphx_ensure(ctx, ctx->dust_rev, 2 * (M + 4) * sizeof(int)));
-    int* rev_raw = ctx->dust_rev.as<int>();
-    int* rev = rev_raw + M + 4;
-    if (M > 0) {
-        hipLaunchKernelGGL(dust_fill_kernel, dim3((unsigned)(((size_t)k * npad + DUST_WG - 1) / DUST_WG)), dim3(DUST_WG), 0, st, (int)n,
-                           (int)npad, k, nbr, d_pt, start, cur, rev_raw);
-        HIPCHK(hipGetLastError());
-        unsigned bits = 1;
-        while (bits < 32 && (1ull << bits) < (unsigned long long)nk) ++bits;
-        size_t sort_bytes = 0;
-        HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
-        SPHX_TRY(sphx_ensure(ctx, ctx->dust_tmp, sort_bytes + 64));
-        HIPCHK(rocprim::segmented_radix_sort_keys(ctx->dust_tmp.p, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
-    }
+    // ---- the reverse list: keys j k + kk (cnt[n] = 0: the memset above; cnt and start lie on 16-byte boundaries) ----
+    RevList rl;
+    SPHX_TRY(sphx_rev_build(ctx, who, n, cnt, start, nk, (unsigned long long)nk, [&](const int* start_, int* rev_raw) {
+        hipLaunchKernelGGL(dust_fill_kernel, dim3(eblk), dim3(DUST_WG), 0, st, (int)n, (int)npad, k, nbr, d_pt, start_, cur, rev_raw);
+    }, &rl));
     if (t) SPHX_TRY(t->mark(ctx, 2));
     // ---- the dust pass, then the row pass ----
     DustWalk wa;
     wa.sel = par.sel; wa.si = par.si;
     wa.n = (int)n; wa.npad = (int)npad; wa.k = k; wa.s = s;
     wa.fraction = par.fraction;
-    wa.start = start; wa.rev = rev; wa.nbr = nbr; wa.flag = flag; wa.rec = pa.rec;
+    wa.start = start; wa.rev = rl.rev; wa.nbr = nbr; wa.flag = flag; wa.rec = pa.rec;
     wa.dens = in.dens; wa.fun = in.fun; wa.ptype = d_pt;
     wa.crit_density = par.crit_density;
     wa.msk = msk;

@@ -7,6 +7,7 @@
 #include <math.h>
 #include <float.h>
 #include <vector>
+#include <functional>
 #include "../../include/sphx.h"
 #include "sphx_agb.h"
 
@@ -395,17 +396,23 @@ struct sphx_ctx {
     // events of a call: [0] start, [1] inputs on the device and prepared, [2] columns done, [3] spread and deposit done,
     // [4] outputs on the host (sphx_rad_last_timing)
     StageTimer rad_t;
+    // The reverse list of rad_cooling, supernova_destruction and chemisputtering_2 (sphx_rev_build, sphx_side.hip: as filled
+    // | sorted) and the scratch of its segmented sort: ONE pair for the three stages.  Sound because a stage's list is dead
+    // when its *_run returns - the kernels that read it are queued by then, on the one stream every later writer is queued
+    // on too, and CoolRes, DustRes and ChemRes carry no pointer into it - and because the stages of a context run strictly
+    // one after the other: the dust phase runs sphx_chem_run, then sphx_dust_run; the radiative phase sphx_cool_run alone.
+    DevBuf side_rev, side_tmp;
     // rad_cooling (sphx_cool.hip), buffers of its own: staged inputs, the list as given, the particles' records, ints (the
-    // K-major list, counts, cursors, flags, slice starts), the reverse list (as filled | sorted), the rows' table, outputs,
-    // scratch of the segmented sort (the counts are scanned by sphx_excl_scan_int)
-    DevBuf cool_in, cool_nb, cool_rec, cool_int, cool_rev, cool_tab, cool_out, cool_tmp;
+    // K-major list, counts, cursors, flags, slice starts), the rows' table, outputs (the counts are scanned by
+    // sphx_excl_scan_int; the reverse list is side_rev)
+    DevBuf cool_in, cool_nb, cool_rec, cool_int, cool_tab, cool_out;
     // events of a call: [0] start, [1] inputs on the device, records and list built, [2] rows done, [3] reverse list, gather
     // and epilogue done, [4] outputs on the host (sphx_cool_last_timing)
     StageTimer cool_t;
     // supernova_destruction (sphx_dust.hip), buffers of its own: staged inputs, the list as given, the particles' records,
-    // ints (the K-major list, counts, cursors, row flags, slice starts, the accept words), the reverse list (as filled |
-    // sorted), outputs (eight u64 counters, the knots, then the two (n,s) arrays), scratch of the segmented sort
-    DevBuf dust_in, dust_nb, dust_rec, dust_int, dust_rev, dust_out, dust_tmp;
+    // ints (the K-major list, counts, cursors, row flags, slice starts, the accept words), outputs (eight u64 counters, the
+    // knots, then the two (n,s) arrays); the reverse list is side_rev
+    DevBuf dust_in, dust_nb, dust_rec, dust_int, dust_out;
     double dust_kn[40] = {0};     // the call's knots and slopes on the host (DustKnots, sphx_dust_pair.h), uploaded from here
     // events of a call: [0] start, [1] inputs on the device, records and list built, [2] reverse list sorted, [3] dust pass
     // done, [4] row pass done and outputs on the host (sphx_dust_last_timing)
@@ -413,10 +420,9 @@ struct sphx_ctx {
     // chemisputtering_2 (sphx_chem.hip), buffers of its own: staged inputs and tables, the list as given, the particles'
     // records, ints per particle (the K-major list, dust flags and ordinals, counts, cursors, slice starts), per dust row
     // doubles (gas and reuptake weights, row scalars, new0 and the two generations of clamped sums) and ints (particle of an
-    // ordinal, contributes, place of an entry in the reverse list), the reverse list (as filled | sorted), the first-stage
-    // losses per (pair, column), outputs (the counters, num0, the final counts, mass_new, f_un_new, partial sums),
-    // scratch of the segmented sort
-    DevBuf chem_in, chem_nb, chem_rec, chem_int, chem_row, chem_rowi, chem_rev, chem_first, chem_out, chem_tmp;
+    // ordinal, contributes, place of an entry in the reverse list), the first-stage losses per (pair, column), outputs (the
+    // counters, num0, the final counts, mass_new, f_un_new, partial sums); the reverse list is side_rev
+    DevBuf chem_in, chem_nb, chem_rec, chem_int, chem_row, chem_rowi, chem_first, chem_out;
     double chem_tab[4 * SPHX_MAX_SPECIES] = {0};   // the call's tables on the host, uploaded from here
     // events of a call: [0] start, [1] inputs on the device, records and list built, [2] row passes done, [3] reverse list
     // sorted, [4] rounds done, [5] closing correction done and outputs on the host (sphx_chem_last_timing)
@@ -482,6 +488,12 @@ void sphx_release(sphx_ctx* ctx, DevBuf& b);      // frees b's allocation now (t
 
 static inline void sphx_step_list_drop(sphx_ctx* ctx) { ctx->step_list_valid = false; ctx->step_qorder = nullptr; }
 static inline int64_t sphx_pad64(int64_t n) { return (n + 63) & ~int64_t(63); }
+// workgroups of wg lanes that cover `lanes` lanes
+static inline unsigned sphx_blocks(size_t lanes, unsigned wg) { return (unsigned)((lanes + wg - 1) / wg); }
+// neither NaN nor inf
+__host__ __device__ __forceinline__ bool sphx_finite(double v) { return v - v == 0.0; }
+// an entry of a caller's (n,k) int64 neighbour list as the K-major int32 lists hold it: outside [0, n) it is missing
+__device__ __forceinline__ int sphx_list_entry64(long long q, int n) { return (q >= 0 && q < n) ? (int)q : -1; }
 
 // XCD-aware block remap: workgroups are dealt round-robin over the 8 XCDs (block b runs on
 // XCD b % 8, each with its own 4 MiB L2).  Map the blocks of one XCD onto one CONTIGUOUS
@@ -789,7 +801,33 @@ struct CoolRes { double *final_comp, *energy, *rec_array, *tab; };              
 int sphx_cool_check(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, double dt, double d);
 int sphx_cool_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const CoolDev& in, const long long* nb64, const int* kmajor,
                   double dt, double d, StageTimer* t, CoolRes* res);
+// ---- shared by the side stages (sphx_side.hip) ----
+// the reverse list of a stage: M entries, each slice sorted, valid until the next sphx_rev_build on the context
+struct RevList { size_t M; const int* rev; };
+int sphx_rev_build(sphx_ctx* ctx, const char* who, int64_t n, const int* cnt, int* start, size_t pairs, unsigned long long key_end,
+                   const std::function<void(const int* start, int* rev_raw)>& fill, RevList* out);
+// the sums over n particles of nq per-particle terms pp (nq, n), in a fixed order, queued into ctx->pinned->scal
+#define SPHX_TOT_CHUNK 256
+static inline size_t sphx_tot_chunks(int64_t n) { return ((size_t)n + SPHX_TOT_CHUNK - 1) / SPHX_TOT_CHUNK; }
+int sphx_ordered_totals(sphx_ctx* ctx, int64_t n, int nq, const double* pp, double* part, double* tot);
 // ---- shared by the two resident phases (sphx_phase.hip) ----
+// The state from the storage slots into the caller's particle order (lane p: the slot of column p, its caller id i;
+// col[i] = p, sphx_phase_map.h) - m, mu, h, ptype always; col, the (n,3) positions, the SoA positions, the (n,3)
+// velocities, T and E where the pointer is not NULL (sx, T, E: with their sources) - and named arrays back through st.id.
+struct PhaseGather {
+    int n;
+    const int *qorder, *id;
+    const double *x, *y, *z, *vx, *vy, *vz, *m, *mu, *h, *pt, *T, *E;
+    int* col;
+    double *pos, *sx, *sy, *sz, *vel, *om, *omu, *oh, *opt, *oT, *oE;
+};
+int sphx_phase_gather(sphx_ctx* ctx, const PhaseGather& a);
+// out[q][j] = in[q][id[j]] for q < narr; vel (n,3) into vx, vy, vz the same way where vel is not NULL
+struct PhaseBack { int n; const int* id; const double* vel; double *vx, *vy, *vz; int narr; const double* in[6]; double* out[6]; };
+int sphx_phase_back(sphx_ctx* ctx, const PhaseBack& a);
+// the refusal of a state with drag on and no per-species drag tables; gamma (and with drag the two tables) finite
+int sphx_phase_check_tables(sphx_ctx* ctx, const char* who, int s, const double* gamma, const double* grain_mass,
+                            const double* sigma_effective);
 int sphx_phase_need_list(sphx_ctx* ctx, const char* who);                          // SPHX_E_STATE unless the last step's list stands
 int sphx_phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list);       // col (n) and the caller-order K-major list (k npad)
 int sphx_phase_drag_refresh(sphx_ctx* ctx, int64_t n, int s, const double* f, const double* gm, const double* se, double* mgm, double* mcs);

@@ -49,7 +49,6 @@ __device__ __forceinline__ void sphx_leapfrog_update(double dt, double x[3], dou
     }
 }
 
-__device__ __forceinline__ bool sphx_finite(double v) { return v - v == 0.0; }
 // failure counters of the update kernels: one ballot per class, one atomic per wave that met any (never in a sane run)
 // (counters: [64 buckets][16] u64, the bucket chosen by wave - sphx_internal.h BADC_*; 1-D launches of 256 threads)
 __device__ __forceinline__ void sphx_count_bad(unsigned long long* counters, int which, bool bad) {

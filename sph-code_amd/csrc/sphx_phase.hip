@@ -1,6 +1,8 @@
 // sphx_phase.hip - the dust phase of the reference's time loop, code_running.py:399-435, on the resident state
 // (sphx_state_dust_phase), its bookkeeping as an array call (sphx_dust_bookkeeping), and the two downloads that go with
-// them (sphx_state_download_neighbors, sphx_state_download_composition).
+// them (sphx_state_download_neighbors, sphx_state_download_composition).  Also what the radiative phase
+// (sphx_radphase.hip) and sphx_state_rad_transfer share with it: the gather of the state into caller order and the
+// write-back through st.id (phase_gather_kernel, phase_back_kernel), the list's translation, the tables' check.
 //
 // The block, statement by statement:
 //   drv:399      f_un rows divided by their sums                                     phase_normalise_kernel
@@ -10,7 +12,7 @@
 //   drv:407-408  chemisputtering_2 on (points, list, mass, normalised f_un, pre-phase mu, sizes, T, ptype)   sphx_chem_run
 //   drv:411      supernova_destruction on (points, velocities, list, post-chem mass and f_un, pre-phase mu, sizes, the
 //                density of drv:400, ptype)                                          sphx_dust_run
-//   drv:412-433  the bookkeeping                                                      phase_book_kernel + the chunked sums
+//   drv:412-433  the bookkeeping                                                      phase_book_kernel + sphx_ordered_totals
 //   drv:434-435  cross_array and optical_depth feed rad_heating alone - not kept
 // THE LIST IS THE LAST STEP'S OWN (ctx->nbr: int32, K-major, storage slots, -1 = missing), translated to caller ids
 // through st.id (sphx_phase_map.h).  That is what the driver does: at drv:407 `neighbor` is the list drv:437 made in the
@@ -21,36 +23,31 @@
 // are written.  Writing st alone is enough: the next step's first act on the state is the permutation st -> alt
 // (sphx_permute_state), which overwrites every array of alt before the two swap, and every mass-derived quantity the step
 // reads - the gather records, the loop-form records with h(m), the tree's sort - is rebuilt from st by that step.
-// Sums over particles: per chunk of 256 in index order, then the chunks by one workgroup in a fixed order
-// (chem_colsum_kernel's scheme).  No floating-point atomic anywhere.  Vector stores from plain C++ only.  Every operation
-// separately rounded; double where the driver has longdouble.
+// Sums over particles: sphx_ordered_totals (sphx_side.hip).  No floating-point atomic anywhere.  Vector stores from plain
+// C++ only.  Every operation separately rounded; double where the driver has longdouble.
 #include "sphx_internal.h"
 #include "sphx_phase_map.h"
 #include <cstring>
 #pragma clang fp contract(off)
 
 #define PHASE_WG 256
-#define PHASE_CHUNK 256
 // per-particle terms of the totals
 enum { PQ_MPRE = 0, PQ_MCHEM, PQ_MFIN, PQ_RED, PQ_INC, PQ_CHG, PQ_RESET, PQ_FILL, PQ_N };
 
-// ---- the state into caller order; the column of every caller id ----
-struct PhaseGather {
-    int n;
-    const int *qorder, *id;
-    const double *x, *y, *z, *vx, *vy, *vz, *m, *mu, *h, *T, *pt;
-    int* col;
-    double *pos, *vel, *om, *omu, *oh, *oT, *opt;
-};
+// ---- the state into caller order; the column of every caller id (PhaseGather, sphx_internal.h) ----
 __global__ __launch_bounds__(PHASE_WG) void phase_gather_kernel(PhaseGather a) {
     const int p = blockIdx.x * PHASE_WG + threadIdx.x;
     if (p >= a.n) return;
     const int j = sphx_phase_slot(a.qorder, p);
-    const int i = a.id[j];
-    sphx_phase_col_lane(a.qorder, a.id, p, a.col);           // (col[i] = p: the header's rule, replayed on the host)
-    a.pos[3 * (size_t)i] = a.x[j]; a.pos[3 * (size_t)i + 1] = a.y[j]; a.pos[3 * (size_t)i + 2] = a.z[j];
-    a.vel[3 * (size_t)i] = a.vx[j]; a.vel[3 * (size_t)i + 1] = a.vy[j]; a.vel[3 * (size_t)i + 2] = a.vz[j];
-    a.om[i] = a.m[j]; a.omu[i] = a.mu[j]; a.oh[i] = a.h[j]; a.oT[i] = a.T[j]; a.opt[i] = a.pt[j];
+    const size_t i = (size_t)a.id[j];
+    if (a.col) sphx_phase_col_lane(a.qorder, a.id, p, a.col);   // (col[i] = p: the header's rule, replayed on the host)
+    const double x = a.x[j], y = a.y[j], z = a.z[j];
+    if (a.pos) { a.pos[3 * i] = x; a.pos[3 * i + 1] = y; a.pos[3 * i + 2] = z; }
+    if (a.sx) { a.sx[i] = x; a.sy[i] = y; a.sz[i] = z; }
+    if (a.vel) { a.vel[3 * i] = a.vx[j]; a.vel[3 * i + 1] = a.vy[j]; a.vel[3 * i + 2] = a.vz[j]; }
+    a.om[i] = a.m[j]; a.omu[i] = a.mu[j]; a.oh[i] = a.h[j]; a.opt[i] = a.pt[j];
+    if (a.oT) a.oT[i] = a.T[j];
+    if (a.oE) a.oE[i] = a.E[j];
 }
 __global__ __launch_bounds__(PHASE_WG) void phase_col_kernel(int n, const int* __restrict__ qorder, const int* __restrict__ id, int* col) {
     const int p = blockIdx.x * PHASE_WG + threadIdx.x;
@@ -154,51 +151,53 @@ __global__ __launch_bounds__(PHASE_WG) void phase_book_kernel(PhaseBook a) {
     a.pp[PQ_RED * n + i] = red; a.pp[PQ_INC * n + i] = inc; a.pp[PQ_CHG * n + i] = chg;
     a.pp[PQ_RESET * n + i] = reset ? 1.0 : 0.0; a.pp[PQ_FILL * n + i] = (double)fills;
 }
-// lane t = (quantity q, chunk c): the chunk's sum in index order
-__global__ __launch_bounds__(PHASE_WG) void phase_chunksum_kernel(int n, int nchunk, const double* __restrict__ pp, double* __restrict__ part) {
-    const int t = blockIdx.x * PHASE_WG + threadIdx.x;
-    if (t >= PQ_N * nchunk) return;
-    const int q = t / nchunk, c = t - q * nchunk;
-    const int i1 = min(n, (c + 1) * PHASE_CHUNK);
-    double sum = 0.0;
-    for (int i = c * PHASE_CHUNK; i < i1; ++i) sum += pp[(size_t)q * n + i];
-    part[t] = sum;
-}
-// one workgroup per quantity: lane l adds the chunks l, l + PHASE_WG, ... in order, then a tree over the lanes
-__global__ __launch_bounds__(PHASE_WG) void phase_total_kernel(int nchunk, const double* __restrict__ part, double* __restrict__ tot) {
-    __shared__ double sm[PHASE_WG];
-    const int q = blockIdx.x, l = threadIdx.x;
-    double sum = 0.0;
-    for (int c = l; c < nchunk; c += PHASE_WG) sum += part[(size_t)q * nchunk + c];
-    sm[l] = sum;
-    __syncthreads();
-    for (int h = PHASE_WG / 2; h > 0; h >>= 1) {
-        if (l < h) sm[l] += sm[l + h];
-        __syncthreads();
-    }
-    if (l == 0) tot[q] = sm[0];
-}
 
-// the new mass, mu, gamma (and drag coefficients) from caller order back into the storage slots
-struct PhaseBack { int n; const int* id; const double* in[5]; double* out[5]; int narr; };
+// the phases' new arrays from caller order back into the storage slots (PhaseBack, sphx_internal.h)
 __global__ __launch_bounds__(PHASE_WG) void phase_back_kernel(PhaseBack a) {
     const int j = blockIdx.x * PHASE_WG + threadIdx.x;
     if (j >= a.n) return;
-    const int i = a.id[j];
-    for (int q = 0; q < a.narr; ++q) a.out[q][j] = a.in[q][i];
+    const size_t i = (size_t)a.id[j];
+    double w[3] = {0.0, 0.0, 0.0}, v[6];                     // (every load in flight before the first store)
+    if (a.vel) { w[0] = a.vel[3 * i]; w[1] = a.vel[3 * i + 1]; w[2] = a.vel[3 * i + 2]; }
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+        if (q < a.narr) v[q] = a.in[q][i];
+    if (a.vel) { a.vx[j] = w[0]; a.vy[j] = w[1]; a.vz[j] = w[2]; }
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+        if (q < a.narr) a.out[q][j] = v[q];
 }
 
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-static bool phase_finite(double v) { return v - v == 0.0; }
-static unsigned phase_blocks(size_t lanes) { return (unsigned)((lanes + PHASE_WG - 1) / PHASE_WG); }
+static unsigned phase_blocks(size_t lanes) { return sphx_blocks(lanes, PHASE_WG); }
+int sphx_phase_gather(sphx_ctx* ctx, const PhaseGather& a) {
+    hipLaunchKernelGGL(phase_gather_kernel, dim3(phase_blocks((size_t)a.n)), dim3(PHASE_WG), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
+}
+int sphx_phase_back(sphx_ctx* ctx, const PhaseBack& a) {
+    hipLaunchKernelGGL(phase_back_kernel, dim3(phase_blocks((size_t)a.n)), dim3(PHASE_WG), 0, ctx->stream, a);
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
+}
+int sphx_phase_check_tables(sphx_ctx* ctx, const char* who, int s, const double* gamma, const double* grain_mass,
+                            const double* sigma_effective) {
+    if (ctx->drag && (!grain_mass || !sigma_effective))
+        return sphx_set_err(ctx, SPHX_E_ARG, "%s: drag is on: the per-species tables grain_mass and sigma_effective are needed to refresh "
+                                               "mean_grain_mass and mean_cross", who);
+    for (int t = 0; t < s; ++t)
+        if (!sphx_finite(gamma[t]) || (ctx->drag && (!sphx_finite(grain_mass[t]) || !sphx_finite(sigma_effective[t]))))
+            return sphx_set_err(ctx, SPHX_E_ARG, "%s: table entry %d must be finite", who, t);
+    return SPHX_OK;
+}
 
 // ctx->phase_out (doubles): density (n) | m_out | mu_out | gam_out | mgm | mcs (n each) | f_out (n s) | pp (PQ_N n) |
 // part (PQ_N nchunk) | totals (PQ_N) | tables mus, gam, gm, se (s each)
 struct PhaseOut { double *dens, *m, *mu, *gam, *mgm, *mcs, *f, *pp, *part, *tot, *tab; size_t nchunk; };
 static int phase_out(sphx_ctx* ctx, int64_t n, int s, PhaseOut* o) {
-    const size_t nn = (size_t)n, nchunk = (nn + PHASE_CHUNK - 1) / PHASE_CHUNK;
+    const size_t nn = (size_t)n, nchunk = sphx_tot_chunks(n);
     SPHX_TRY(sphx_ensure(ctx, ctx->phase_out, (6 * nn + nn * (size_t)s + PQ_N * nn + PQ_N * nchunk + PQ_N + 4 * (size_t)s) * sizeof(double)));
     double* p = ctx->phase_out.as<double>();
     o->dens = p; o->m = p + nn; o->mu = p + 2 * nn; o->gam = p + 3 * nn; o->mgm = p + 4 * nn; o->mcs = p + 5 * nn;
@@ -210,13 +209,9 @@ static int phase_out(sphx_ctx* ctx, int64_t n, int s, PhaseOut* o) {
 
 // the bookkeeping kernel and the sums behind it; the totals' copy to the host is queued (phase_totals reads it after a synchronise)
 static int phase_book_run(sphx_ctx* ctx, PhaseBook a, const PhaseOut& o) {
-    hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(phase_book_kernel, dim3(phase_blocks((size_t)a.n)), dim3(PHASE_WG), 0, st, a);
-    hipLaunchKernelGGL(phase_chunksum_kernel, dim3(phase_blocks(PQ_N * o.nchunk)), dim3(PHASE_WG), 0, st, a.n, (int)o.nchunk, a.pp, o.part);
-    hipLaunchKernelGGL(phase_total_kernel, dim3(PQ_N), dim3(PHASE_WG), 0, st, (int)o.nchunk, o.part, o.tot);
+    hipLaunchKernelGGL(phase_book_kernel, dim3(phase_blocks((size_t)a.n)), dim3(PHASE_WG), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(ctx->pinned->scal, o.tot, PQ_N * sizeof(double), hipMemcpyDeviceToHost, st));
-    return SPHX_OK;
+    return sphx_ordered_totals(ctx, a.n, PQ_N, a.pp, o.part, o.tot);
 }
 static void phase_totals(sphx_ctx* ctx, bool has_before, double* totals, int64_t* counts) {
     double t[PQ_N];
@@ -236,7 +231,7 @@ extern "C" int sphx_dust_bookkeeping(sphx_ctx* ctx, int64_t n, int s, const doub
     if (!ctx) return SPHX_E_ARG;
     if (n < 1 || n > 0x7FFFFFF0ll || s < 1 || s > SPHX_MAX_SPECIES)
         return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dust_bookkeeping: n=%lld, s=%d (need n >= 1, 1 <= s <= %d)", (long long)n, s, SPHX_MAX_SPECIES);
-    if (!phase_finite(crit_mass)) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dust_bookkeeping: crit_mass=%g must be finite", crit_mass);
+    if (!sphx_finite(crit_mass)) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_dust_bookkeeping: crit_mass=%g must be finite", crit_mass);
     NEED(mass); NEED(mu_array); NEED(f_un); NEED(frac_destruction); NEED(frac_reuptake); NEED(mu_specie); NEED(gamma_specie);
     NEED(mass_out); NEED(f_un_out); NEED(mu_out); NEED(gamma_out);
     HIPCHK(hipSetDevice(ctx->device));
@@ -267,8 +262,8 @@ extern "C" int sphx_dust_bookkeeping(sphx_ctx* ctx, int64_t n, int s, const doub
     return SPHX_OK;
 }
 
-// what both resident calls need: a state that has stepped, whose list is still the step's
-static int phase_need_list(sphx_ctx* ctx, const char* who) {
+// what the resident calls need: a state that has stepped, whose list is still the step's
+int sphx_phase_need_list(sphx_ctx* ctx, const char* who) {
     if (!ctx->has_state) return sphx_set_err(ctx, SPHX_E_STATE, "%s: no state uploaded", who);
     if (ctx->step_count < 1)
         return sphx_set_err(ctx, SPHX_E_STATE, "%s before the first sphx_step: the list and sizes do not exist yet", who);
@@ -281,7 +276,7 @@ static int phase_need_list(sphx_ctx* ctx, const char* who) {
     return SPHX_OK;
 }
 // col (n ints) and the caller-order K-major list (k npad ints) into `list`
-static int phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list) {
+int sphx_phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list) {
     const int64_t n = ctx->n;
     const int k = ctx->k, npad = (int)sphx_pad64(n);
     const int* id = ctx->st.id.as<int>();
@@ -292,10 +287,7 @@ static int phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list) {
     return SPHX_OK;
 }
 
-// what the resident radiative phase (sphx_radphase.hip) shares with the dust phase: the list guard, the translation of the
-// step's list, and the drag coefficients from dense composition rows (n,s) in caller order
-int sphx_phase_need_list(sphx_ctx* ctx, const char* who) { return phase_need_list(ctx, who); }
-int sphx_phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list) { return phase_translate(ctx, col, col_done, list); }
+// the drag coefficients from dense composition rows (n,s) in caller order (the radiative phase's refresh)
 __global__ __launch_bounds__(PHASE_WG) void phase_drag_kernel(int n, int s, const double* __restrict__ f, const double* __restrict__ gm,
                                                               const double* __restrict__ se, double* mgm, double* mcs) {
     const int i = blockIdx.x * PHASE_WG + threadIdx.x;
@@ -312,7 +304,7 @@ int sphx_phase_drag_refresh(sphx_ctx* ctx, int64_t n, int s, const double* f, co
 
 extern "C" int sphx_state_download_neighbors(sphx_ctx* ctx, int64_t* neighbor) {
     if (!ctx) return SPHX_E_ARG;
-    SPHX_TRY(phase_need_list(ctx, "sphx_state_download_neighbors"));
+    SPHX_TRY(sphx_phase_need_list(ctx, "sphx_state_download_neighbors"));
     NEED(neighbor);
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t n = ctx->n;
@@ -322,12 +314,28 @@ extern "C" int sphx_state_download_neighbors(sphx_ctx* ctx, int64_t* neighbor) {
     SPHX_TRY(sphx_ensure(ctx, ctx->idx64, nk * sizeof(int64_t)));
     int* col = ctx->phase_int.as<int>();
     int* list = col + npad;
-    SPHX_TRY(phase_translate(ctx, col, false, list));
+    SPHX_TRY(sphx_phase_translate(ctx, col, false, list));
     hipLaunchKernelGGL(phase_list64_kernel, dim3(phase_blocks(nk)), dim3(PHASE_WG), 0, ctx->stream, (int)n, (int)npad, k, list,
                        (long long*)ctx->idx64.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(neighbor, ctx->idx64.p, nk * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SPHX_OK;
+}
+
+// per-particle arrays of the state, storage order on the device, into the caller's order on the host (host NULL: skipped)
+struct ById { double* host; const double* dev; };
+static int phase_download_by_id(sphx_ctx* ctx, const ById* v, int nv) {
+    const int64_t n = ctx->n;
+    const size_t nb = (size_t)n * sizeof(double);
+    SPHX_TRY(sphx_ensure(ctx, ctx->out_a, nb));
+    double* stage = ctx->out_a.as<double>();
+    for (int q = 0; q < nv; ++q) {
+        if (!v[q].host) continue;
+        SPHX_TRY(sphx_scatter_rows_by_id(ctx, n, 1, ctx->st.id.as<int>(), v[q].dev, stage));
+        HIPCHK(hipMemcpyAsync(v[q].host, stage, nb, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
     return SPHX_OK;
 }
 
@@ -338,18 +346,9 @@ extern "C" int sphx_state_download_composition(sphx_ctx* ctx, double* mass, doub
         return sphx_set_err(ctx, SPHX_E_STATE, "sphx_state_download_composition: the state carries no composition (f_un)");
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t n = ctx->n;
-    const size_t nb = (size_t)n * sizeof(double);
     const StateArrays& s = ctx->st;
-    SPHX_TRY(sphx_ensure(ctx, ctx->out_a, nb));
-    double* stage = ctx->out_a.as<double>();
-    struct V1 { double* host; const double* dev; };
-    const V1 v1[] = {{mass, s.m.as<double>()}, {mu_array, s.mu.as<double>()}, {gamma_array, s.gam.as<double>()}};
-    for (const V1& v : v1) {
-        if (!v.host) continue;
-        SPHX_TRY(sphx_scatter_rows_by_id(ctx, n, 1, s.id.as<int>(), v.dev, stage));
-        HIPCHK(hipMemcpyAsync(v.host, stage, nb, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
+    const ById v1[] = {{mass, s.m.as<double>()}, {mu_array, s.mu.as<double>()}, {gamma_array, s.gam.as<double>()}};
+    SPHX_TRY(phase_download_by_id(ctx, v1, 3));
     if (f_un) {                                      // the rows are in upload order already; the padding stays behind
         HIPCHK(hipMemcpy2DAsync(f_un, (size_t)ctx->s * sizeof(double), ctx->fun_id.p, (size_t)ctx->sp * sizeof(double),
                                 (size_t)ctx->s * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
@@ -362,19 +361,8 @@ extern "C" int sphx_state_download_drag(sphx_ctx* ctx, double* mean_grain_mass, 
     if (!ctx) return SPHX_E_ARG;
     if (!ctx->has_state || !ctx->drag) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_state_download_drag: no state with drag on");
     HIPCHK(hipSetDevice(ctx->device));
-    const int64_t n = ctx->n;
-    const size_t nb = (size_t)n * sizeof(double);
-    SPHX_TRY(sphx_ensure(ctx, ctx->out_a, nb));
-    double* stage = ctx->out_a.as<double>();
-    struct V1 { double* host; const double* dev; };
-    const V1 v1[] = {{mean_grain_mass, ctx->st.mgm.as<double>()}, {mean_cross, ctx->st.mcs.as<double>()}};
-    for (const V1& v : v1) {
-        if (!v.host) continue;
-        SPHX_TRY(sphx_scatter_rows_by_id(ctx, n, 1, ctx->st.id.as<int>(), v.dev, stage));
-        HIPCHK(hipMemcpyAsync(v.host, stage, nb, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
-    return SPHX_OK;
+    const ById v1[] = {{mean_grain_mass, ctx->st.mgm.as<double>()}, {mean_cross, ctx->st.mcs.as<double>()}};
+    return phase_download_by_id(ctx, v1, 2);
 }
 
 extern "C" int sphx_state_dust_phase(sphx_ctx* ctx, double dt, double d, const double* mu_specie, const double* gamma_specie,
@@ -386,12 +374,9 @@ extern "C" int sphx_state_dust_phase(sphx_ctx* ctx, double dt, double d, const d
                                      int64_t* dust_counts, double* totals, int64_t* book_counts) {
     if (!ctx) return SPHX_E_ARG;
     const char* who = "sphx_state_dust_phase";
-    SPHX_TRY(phase_need_list(ctx, who));
+    SPHX_TRY(sphx_phase_need_list(ctx, who));
     if (ctx->s < 7 || !ctx->fun_id.p)
         return sphx_set_err(ctx, SPHX_E_STATE, "%s: the state carries no composition (f_un) of >= 7 species", who);
-    if (ctx->drag && (!grain_mass || !sigma_effective))
-        return sphx_set_err(ctx, SPHX_E_ARG, "%s: drag is on: the per-species tables grain_mass and sigma_effective are needed to refresh "
-                                               "mean_grain_mass and mean_cross", who);
     const int64_t n = ctx->n;
     const int k = ctx->k, s = ctx->s, sp = ctx->sp;
     NEED(mu_specie); NEED(gamma_specie); NEED(mineral_densities); NEED(sputtering_yields); NEED(mrn);
@@ -399,9 +384,7 @@ extern "C" int sphx_state_dust_phase(sphx_ctx* ctx, double dt, double d, const d
     SPHX_TRY(sphx_chem_check_shape(ctx, who, n, k, s));
     SPHX_TRY(sphx_chem_check_scalars(ctx, who, d, dt, mrn, k_B, amu, m_0));
     SPHX_TRY(sphx_dust_check_scalars(ctx, who, crit_mass, critical_density, guard_mode));
-    for (int t = 0; t < s; ++t)
-        if (!phase_finite(gamma_specie[t]) || (ctx->drag && (!phase_finite(grain_mass[t]) || !phase_finite(sigma_effective[t]))))
-            return sphx_set_err(ctx, SPHX_E_ARG, "%s: table entry %d must be finite", who, t);
+    SPHX_TRY(sphx_phase_check_tables(ctx, who, s, gamma_specie, grain_mass, sigma_effective));
     ChemPar cpar;
     cpar.d = d; cpar.dt = dt; cpar.k_B = k_B; cpar.m_0 = m_0;
     SPHX_TRY(sphx_chem_tables(ctx, who, s, mu_specie, mineral_densities, sputtering_yields, mrn, amu, &cpar.symax));
@@ -429,11 +412,13 @@ extern "C" int sphx_state_dust_phase(sphx_ctx* ctx, double dt, double d, const d
     ga.x = st.x.as<double>(); ga.y = st.y.as<double>(); ga.z = st.z.as<double>();
     ga.vx = st.vx.as<double>(); ga.vy = st.vy.as<double>(); ga.vz = st.vz.as<double>();
     ga.m = st.m.as<double>(); ga.mu = st.mu.as<double>(); ga.h = st.hprev.as<double>(); ga.T = st.T.as<double>(); ga.pt = st.ptype.as<double>();
-    ga.col = col; ga.pos = cin.pos; ga.vel = din.vel; ga.om = cin.m; ga.omu = cin.mu; ga.oh = cin.sizes; ga.oT = cin.T; ga.opt = cin.ptype;
-    hipLaunchKernelGGL(phase_gather_kernel, dim3(phase_blocks(nn)), dim3(PHASE_WG), 0, stream, ga);
+    ga.E = nullptr;
+    ga.col = col; ga.pos = cin.pos; ga.sx = ga.sy = ga.sz = nullptr; ga.vel = din.vel; ga.om = cin.m; ga.omu = cin.mu; ga.oh = cin.sizes;
+    ga.oT = cin.T; ga.opt = cin.ptype; ga.oE = nullptr;
+    SPHX_TRY(sphx_phase_gather(ctx, ga));
     hipLaunchKernelGGL(phase_normalise_kernel, dim3(phase_blocks(nn)), dim3(PHASE_WG), 0, stream, (int)n, s, sp, ctx->fun_id.as<double>(), cin.fun);
     HIPCHK(hipGetLastError());
-    SPHX_TRY(phase_translate(ctx, col, true, list));
+    SPHX_TRY(sphx_phase_translate(ctx, col, true, list));
     // the tables: chem's four (ctx->chem_tab) beside its inputs; mu_specie | gamma | grain_mass | sigma_effective in phase_out
     double* ptab = ctx->phase_tab;                   // (held by the context: the upload below reads it)
     for (int t = 0; t < s; ++t) {
@@ -468,13 +453,10 @@ extern "C" int sphx_state_dust_phase(sphx_ctx* ctx, double dt, double d, const d
     a.m_out = o.m; a.f_out = ctx->fun_id.as<double>(); a.mu_out = o.mu; a.gam_out = o.gam; a.mgm_out = o.mgm; a.mcs_out = o.mcs;
     a.pp = o.pp;
     SPHX_TRY(phase_book_run(ctx, a, o));
-    PhaseBack ba;
-    ba.n = (int)n; ba.id = st.id.as<int>(); ba.narr = ctx->drag ? 5 : 3;
-    const double* from[5] = {o.m, o.mu, o.gam, o.mgm, o.mcs};
-    double* to[5] = {st.m.as<double>(), st.mu.as<double>(), st.gam.as<double>(), st.mgm.as<double>(), st.mcs.as<double>()};
-    for (int q = 0; q < 5; ++q) { ba.in[q] = from[q]; ba.out[q] = to[q]; }
-    hipLaunchKernelGGL(phase_back_kernel, dim3(phase_blocks(nn)), dim3(PHASE_WG), 0, stream, ba);
-    HIPCHK(hipGetLastError());
+    const PhaseBack ba{(int)n, st.id.as<int>(), nullptr, nullptr, nullptr, nullptr, ctx->drag ? 5 : 3,
+                       {o.m, o.mu, o.gam, o.mgm, o.mcs, nullptr},
+                       {st.m.as<double>(), st.mu.as<double>(), st.gam.as<double>(), st.mgm.as<double>(), st.mcs.as<double>(), nullptr}};
+    SPHX_TRY(sphx_phase_back(ctx, ba));
     const CopyF64 ds[] = {{density, o.dens, nn}, {mass_chem, cres.mass_new, nn}, {f_un_chem, cres.fun_new, ns}, {frac_destruction, dres.destr, ns},
                           {frac_reuptake, dres.reup, ns}, {dust_counts, dres.counters, 5}};
     SPHX_TRY(sphx_download_f64(ctx, ds, 6));

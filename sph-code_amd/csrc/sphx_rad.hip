@@ -230,16 +230,6 @@ __global__ __launch_bounds__(256) void rad_deposit_kernel(RadDepArgs a) {
     if (a.ext) a.ext[g] = extg;                                                              // nsc:954
 }
 
-// the resident state (storage order) into the caller's order: out[id[j]] = in[j], seven arrays at once
-struct RadGather { const double* in[7]; double* out[7]; };
-__global__ __launch_bounds__(256) void rad_by_id_kernel(int n, const int* __restrict__ id, RadGather ga) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    const int i = id[j];
-#pragma unroll
-    for (int f = 0; f < 7; ++f) ga.out[f][i] = ga.in[f][j];
-}
-
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
@@ -445,13 +435,14 @@ extern "C" int sphx_state_rad_transfer(sphx_ctx* ctx, const double* cross, int64
     double* soa = ctx->rad_soa.as<double>();
     HIPCHK(hipMemcpyAsync(in + 6 * nn, cross, nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     const StateArrays& s = ctx->st;
-    RadGather ga;
-    const double* from[7] = {s.x.as<double>(), s.y.as<double>(), s.z.as<double>(), s.m.as<double>(), s.ptype.as<double>(),
-                             s.hprev.as<double>(), s.mu.as<double>()};
-    double* to[7] = {soa, soa + nn, soa + 2 * nn, in + 3 * nn, in + 4 * nn, in + 5 * nn, in + 7 * nn};
-    for (int f = 0; f < 7; ++f) { ga.in[f] = from[f]; ga.out[f] = to[f]; }
-    hipLaunchKernelGGL(rad_by_id_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n, s.id.as<int>(), ga);
-    HIPCHK(hipGetLastError());
+    // the resident state (storage order) into the caller's order: the SoA positions, m, ptype, hprev, mu (slot by slot: no
+    // list is read here, so no processing order and no col)
+    PhaseGather ga = {};
+    ga.n = (int)n; ga.id = s.id.as<int>();
+    ga.x = s.x.as<double>(); ga.y = s.y.as<double>(); ga.z = s.z.as<double>();
+    ga.m = s.m.as<double>(); ga.pt = s.ptype.as<double>(); ga.h = s.hprev.as<double>(); ga.mu = s.mu.as<double>();
+    ga.sx = soa; ga.sy = soa + nn; ga.sz = soa + 2 * nn; ga.om = in + 3 * nn; ga.opt = in + 4 * nn; ga.oh = in + 5 * nn; ga.omu = in + 7 * nn;
+    SPHX_TRY(sphx_phase_gather(ctx, ga));
     RadPart pa;
     pa.n = (int)n;
     pa.x = soa; pa.y = soa + nn; pa.z = soa + 2 * nn; pa.h2 = soa + 3 * nn; pa.w = soa + 4 * nn;

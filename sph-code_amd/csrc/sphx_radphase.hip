@@ -13,17 +13,15 @@
 // are contiguous over the wave; a row sits (s | 1) doubles from the next, so that the lanes' walks along their rows
 // spread over the banks.  Each lane then works on its particle's row alone, in species order: no reduction crosses
 // lanes, and no result depends on the launch shape.
-// Sums over particles (the totals the driver prints): per chunk of RP_CHUNK in index order, then the chunks by one
-// workgroup in a fixed order (chem_colsum_kernel's scheme).  No floating-point atomic.  Vector stores from plain C++.
+// Sums over particles (the totals the driver prints): sphx_ordered_totals (sphx_side.hip).  No floating-point atomic.
+// Vector stores from plain C++.
 #include "sphx_internal.h"
 #include "sphx_radphase_pair.h"
-#include "sphx_phase_map.h"
 #include <cstring>
 #include <vector>
 #pragma clang fp contract(off)
 
 #define RP_WG 128
-#define RP_CHUNK 256
 // per-particle terms of the totals: E_internal on entry and on exit, the four clamps
 enum { RQ_EIN = 0, RQ_EOUT, RQ_ELO, RQ_EHI, RQ_TLO, RQ_THI, RQ_N };
 static_assert(RQ_N <= SC_NSLOTS, "the totals fit the pinned scalar block");
@@ -143,36 +141,9 @@ __global__ __launch_bounds__(RP_WG) void rp_book_kernel(RpBook a) {
     a.pp[RQ_TLO * n + i] = (hit & SPHX_RP_T_LO) ? 1.0 : 0.0; a.pp[RQ_THI * n + i] = (hit & SPHX_RP_T_HI) ? 1.0 : 0.0;
 }
 
-// lane t = (quantity q, chunk c): the chunk's sum in index order
-__global__ __launch_bounds__(256) void rp_chunksum_kernel(int n, int nchunk, const double* __restrict__ pp, double* __restrict__ part) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= RQ_N * nchunk) return;
-    const int q = t / nchunk, c = t - q * nchunk;
-    const int i1 = min(n, (c + 1) * RP_CHUNK);
-    double sum = 0.0;
-    for (int i = c * RP_CHUNK; i < i1; ++i) sum += pp[(size_t)q * n + i];
-    part[t] = sum;
-}
-// one workgroup per quantity: lane l adds the chunks l, l + 256, ... in order, then a tree over the lanes
-__global__ __launch_bounds__(256) void rp_total_kernel(int nchunk, const double* __restrict__ part, double* __restrict__ tot) {
-    __shared__ double sm[256];
-    const int q = blockIdx.x, l = threadIdx.x;
-    double sum = 0.0;
-    for (int c = l; c < nchunk; c += 256) sum += part[(size_t)q * nchunk + c];
-    sm[l] = sum;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (l < h) sm[l] += sm[l + h];
-        __syncthreads();
-    }
-    if (l == 0) tot[q] = sm[0];
-}
-
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-static bool rp_finite(double v) { return v - v == 0.0; }
-static unsigned rp_blocks(size_t lanes, unsigned wg) { return (unsigned)((lanes + wg - 1) / wg); }
 
 // doubles out of ctx->radphase_buf, one after the other
 struct RpBump {
@@ -195,7 +166,7 @@ static int rp_ordinals(sphx_ctx* ctx, const char* who, int64_t n, const double* 
     SPHX_TRY(sphx_ensure(ctx, ctx->radphase_int, 2 * ints * sizeof(int)));
     int* flag = ctx->radphase_int.as<int>();
     int* off = flag + ints;
-    hipLaunchKernelGGL(rp_flag_kernel, dim3(rp_blocks((size_t)n + 1, 256)), dim3(256), 0, ctx->stream, (int)n, d_pt, flag);
+    hipLaunchKernelGGL(rp_flag_kernel, dim3(sphx_blocks((size_t)n + 1, 256)), dim3(256), 0, ctx->stream, (int)n, d_pt, flag);
     HIPCHK(hipGetLastError());
     SPHX_TRY(sphx_excl_scan_int(ctx, flag, off, (int)n));
     PinnedSide& pin = ctx->pinned->side;
@@ -240,7 +211,7 @@ extern "C" int sphx_rad_ionise(sphx_ctx* ctx, int64_t n, int s, int64_t n_gas, c
     a.ppj = photons_per_joule; a.amu = amu;
     a.f_out = d_fo; a.frac = frac_destroyed ? d_fr : nullptr;
     SPHX_TRY(ctx->radphase_t.mark(ctx, 1));
-    hipLaunchKernelGGL(rp_ionise_kernel, dim3(rp_blocks(nn, RP_WG)), dim3(RP_WG), rp_lds_bytes(s, 3), ctx->stream, a);
+    hipLaunchKernelGGL(rp_ionise_kernel, dim3(sphx_blocks(nn, RP_WG)), dim3(RP_WG), rp_lds_bytes(s, 3), ctx->stream, a);
     HIPCHK(hipGetLastError());
     SPHX_TRY(ctx->radphase_t.mark(ctx, 2));
     SPHX_TRY(ctx->radphase_t.mark(ctx, 3));                                  // (no sums behind this kernel)
@@ -255,16 +226,12 @@ extern "C" int sphx_rad_ionise(sphx_ctx* ctx, int64_t n, int s, int64_t n_gas, c
 // synchronise: totals[2] = sum E on entry, on exit; counts[4] = E raised, E lowered, T raised, T lowered)
 static int rp_book_run(sphx_ctx* ctx, bool cool, RpBook a, double* part, double* tot, StageTimer* t) {
     hipStream_t st = ctx->stream;
-    const size_t nchunk = ((size_t)a.n + RP_CHUNK - 1) / RP_CHUNK;
-    const dim3 grid(rp_blocks((size_t)a.n, RP_WG));
+    const dim3 grid(sphx_blocks((size_t)a.n, RP_WG));
     if (cool) hipLaunchKernelGGL(rp_book_kernel<true>, grid, dim3(RP_WG), rp_lds_bytes(a.s, 3), st, a);
     else hipLaunchKernelGGL(rp_book_kernel<false>, grid, dim3(RP_WG), rp_lds_bytes(a.s, 3), st, a);
     HIPCHK(hipGetLastError());
     if (t) SPHX_TRY(t->mark(ctx, 2));
-    hipLaunchKernelGGL(rp_chunksum_kernel, dim3(rp_blocks(RQ_N * nchunk, 256)), dim3(256), 0, st, a.n, (int)nchunk, a.pp, part);
-    hipLaunchKernelGGL(rp_total_kernel, dim3(RQ_N), dim3(256), 0, st, (int)nchunk, part, tot);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(ctx->pinned->scal, tot, RQ_N * sizeof(double), hipMemcpyDeviceToHost, st));
+    SPHX_TRY(sphx_ordered_totals(ctx, a.n, RQ_N, a.pp, part, tot));
     return t ? t->mark(ctx, 3) : SPHX_OK;
 }
 static void rp_totals(sphx_ctx* ctx, double* totals, int64_t* counts) {
@@ -274,9 +241,9 @@ static void rp_totals(sphx_ctx* ctx, double* totals, int64_t* counts) {
     if (counts) for (int q = 0; q < 4; ++q) counts[q] = (int64_t)t[RQ_ELO + q];
 }
 static int rp_check_const(sphx_ctx* ctx, const char* who, const SphxRpConst& c, bool cool) {
-    if (!rp_finite(c.t_cmb) || !rp_finite(c.t_max) || !rp_finite(c.k) || !rp_finite(c.m_h))
+    if (!sphx_finite(c.t_cmb) || !sphx_finite(c.t_max) || !sphx_finite(c.k) || !sphx_finite(c.m_h))
         return sphx_set_err(ctx, SPHX_E_ARG, "%s: t_cmb, t_max, k_B and m_h must be finite", who);
-    if (cool && (!rp_finite(c.sb) || !rp_finite(c.dt) || !rp_finite(c.cooling_timescale) || c.cooling_timescale == 0.0))
+    if (cool && (!sphx_finite(c.sb) || !sphx_finite(c.dt) || !sphx_finite(c.cooling_timescale) || c.cooling_timescale == 0.0))
         return sphx_set_err(ctx, SPHX_E_ARG, "%s: sb, dt and cooling_timescale must be finite, cooling_timescale not 0", who);
     return SPHX_OK;
 }
@@ -291,7 +258,7 @@ static int rp_book_host(sphx_ctx* ctx, const char* who, bool cool, int64_t n, in
     SPHX_TRY(rp_check_const(ctx, who, c, cool));
     HIPCHK(hipSetDevice(ctx->device));
     SPHX_TRY(ctx->radphase_t.begin(ctx));
-    const size_t nn = (size_t)n, ns = nn * (size_t)s, ng = (size_t)n_gas, nchunk = (nn + RP_CHUNK - 1) / RP_CHUNK;
+    const size_t nn = (size_t)n, ns = nn * (size_t)s, ng = (size_t)n_gas, nchunk = sphx_tot_chunks(n);
     SPHX_TRY(sphx_ensure(ctx, ctx->radphase_buf, (rp_even(ns) + 12 * rp_even(nn) + 2 * rp_even(3 * nn) + rp_even(ng) + rp_even(3 * ng) +
                                                   rp_even(3 * (size_t)s) + rp_even(RQ_N * nn) + rp_even(RQ_N * nchunk) + RQ_N + 8) * sizeof(double)));
     RpBump b{ctx->radphase_buf.as<double>()};
@@ -366,27 +333,9 @@ extern "C" int sphx_rad_cool_bookkeeping(sphx_ctx* ctx, int64_t n, int s, int64_
 // =====================================================================================================================
 // the whole block on the resident state: sphx_state_rad_phase
 // =====================================================================================================================
-// The state into the caller's particle order (the order of upload), in which every stage then runs: the bits are those of
-// the array calls on the downloaded state.  col[i] = the column of caller id i in the step's list (sphx_phase_map.h).
-struct RsGather {
-    int n;
-    const int *qorder, *id;
-    const double *x, *y, *z, *vx, *vy, *vz, *m, *mu, *h, *T, *pt, *E;
-    int* col;
-    double *pos, *sx, *sy, *sz, *vel, *om, *omu, *oh, *oT, *opt, *oE;
-};
-__global__ __launch_bounds__(256) void rs_gather_kernel(RsGather a) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= a.n) return;
-    const int j = sphx_phase_slot(a.qorder, p);
-    const int i = a.id[j];
-    sphx_phase_col_lane(a.qorder, a.id, p, a.col);
-    const double x = a.x[j], y = a.y[j], z = a.z[j];
-    a.pos[3 * (size_t)i] = x; a.pos[3 * (size_t)i + 1] = y; a.pos[3 * (size_t)i + 2] = z;
-    a.sx[i] = x; a.sy[i] = y; a.sz[i] = z;
-    a.vel[3 * (size_t)i] = a.vx[j]; a.vel[3 * (size_t)i + 1] = a.vy[j]; a.vel[3 * (size_t)i + 2] = a.vz[j];
-    a.om[i] = a.m[j]; a.omu[i] = a.mu[j]; a.oh[i] = a.h[j]; a.oT[i] = a.T[j]; a.opt[i] = a.pt[j]; a.oE[i] = a.E[j];
-}
+// The state goes into the caller's particle order (the order of upload; sphx_phase_gather, sphx_phase.hip), in which every
+// stage then runs: the bits are those of the array calls on the downloaded state.  The new velocities, E, T, mu, gamma
+// (and drag coefficients) go back into the storage slots by sphx_phase_back.
 // cross_array of drv:434 from dense rows: sum_t f cross_sections / sum_t f, t = 0 .. s - 1 (compat.cross_array_of's order)
 __global__ __launch_bounds__(256) void rs_cross_kernel(int n, int s, const double* __restrict__ f, const double* __restrict__ tab, double* cross) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -401,21 +350,6 @@ __global__ __launch_bounds__(256) void rs_pick_kernel(int count, const int* __re
     if (q >= count) return;
     const size_t i = (size_t)ids[q];
     out[3 * (size_t)q] = pos[3 * i]; out[3 * (size_t)q + 1] = pos[3 * i + 1]; out[3 * (size_t)q + 2] = pos[3 * i + 2];
-}
-// the new velocities, E, T, mu, gamma (and drag coefficients) from caller order back into the storage slots
-struct RsBack {
-    int n;
-    const int* id;
-    const double *vel, *E, *T, *mu, *gam, *mgm, *mcs;        // mgm, mcs: nullable
-    double *vx, *vy, *vz, *oE, *oT, *omu, *ogam, *omgm, *omcs;
-};
-__global__ __launch_bounds__(256) void rs_back_kernel(RsBack a) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= a.n) return;
-    const size_t i = (size_t)a.id[j];
-    a.vx[j] = a.vel[3 * i]; a.vy[j] = a.vel[3 * i + 1]; a.vz[j] = a.vel[3 * i + 2];
-    a.oE[j] = a.E[i]; a.oT[j] = a.T[i]; a.omu[j] = a.mu[i]; a.ogam[j] = a.gam[i];
-    if (a.mgm) { a.omgm[j] = a.mgm[i]; a.omcs[j] = a.mcs[i]; }
 }
 
 extern "C" int sphx_state_rad_phase(sphx_ctx* ctx, double dt, double d, int64_t n_src, const int64_t* source_ids, const double* luminosities,
@@ -432,9 +366,6 @@ extern "C" int sphx_state_rad_phase(sphx_ctx* ctx, double dt, double d, int64_t 
     SPHX_TRY(sphx_phase_need_list(ctx, who));
     if (ctx->s < 6 || !ctx->fun_id.p)
         return sphx_set_err(ctx, SPHX_E_STATE, "%s: the state carries no composition (f_un) of >= 6 species", who);
-    if (ctx->drag && (!grain_mass || !sigma_effective))
-        return sphx_set_err(ctx, SPHX_E_ARG, "%s: drag is on: the per-species tables grain_mass and sigma_effective are needed to refresh "
-                                               "mean_grain_mass and mean_cross", who);
     const int64_t n = ctx->n;
     const int k = ctx->k, s = ctx->s, sp = ctx->sp;
     NEED(frac_dest); NEED(mu_specie); NEED(gamma_specie); NEED(cross_sections); NEED(driver_cross_sections); NEED(skipped);
@@ -451,9 +382,7 @@ extern "C" int sphx_state_rad_phase(sphx_ctx* ctx, double dt, double d, int64_t 
         if (source_ids[q] < 0 || source_ids[q] >= n) return sphx_set_err(ctx, SPHX_E_ARG, "%s: source id %lld outside [0, n)", who, (long long)source_ids[q]);
     for (int64_t q = 0; q < n_dst; ++q)
         if (target_ids[q] < 0 || target_ids[q] >= n) return sphx_set_err(ctx, SPHX_E_ARG, "%s: target id %lld outside [0, n)", who, (long long)target_ids[q]);
-    for (int t = 0; t < s; ++t)
-        if (!rp_finite(gamma_specie[t]) || (ctx->drag && (!rp_finite(grain_mass[t]) || !rp_finite(sigma_effective[t]))))
-            return sphx_set_err(ctx, SPHX_E_ARG, "%s: table entry %d must be finite", who, t);
+    SPHX_TRY(sphx_phase_check_tables(ctx, who, s, gamma_specie, grain_mass, sigma_effective));
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
     const StateArrays& st = ctx->st;
@@ -467,7 +396,7 @@ extern "C" int sphx_state_rad_phase(sphx_ctx* ctx, double dt, double d, int64_t 
     if (ng == n) { *skipped = 1; return SPHX_OK; }
     SPHX_TRY(ctx->radstate_t.begin(ctx));
     // ---- buffers ----
-    const size_t nchunk = (nn + RP_CHUNK - 1) / RP_CHUNK, g = (size_t)ng;
+    const size_t nchunk = sphx_tot_chunks(n), g = (size_t)ng;
     const size_t doubles = 4 * rp_even(3 * nn) + 20 * rp_even(nn) + 2 * rp_even(ns) + rp_even(3 * g) + rp_even(3 * (size_t)n_src) +
                            rp_even(3 * (size_t)n_dst) + rp_even(8 * ss) + rp_even(RQ_N * nn) + rp_even(RQ_N * nchunk) + RQ_N + 16;
     SPHX_TRY(sphx_ensure(ctx, ctx->radstate_buf, doubles * sizeof(double)));
@@ -498,7 +427,7 @@ extern "C" int sphx_state_rad_phase(sphx_ctx* ctx, double dt, double d, int64_t 
     for (int64_t q = 0; q < n_dst; ++q) ids[(size_t)(n_src + q)] = (int)target_ids[q];
     if (!ids.empty()) HIPCHK(hipMemcpy(d_ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice));   // (pageable, so synchronous)
     // ---- 1, 2: the state through st.id; the list into caller ids; the dense rows; cross_array; the rays' ends ----
-    RsGather ga;
+    PhaseGather ga;
     ga.n = (int)n; ga.qorder = ctx->step_qorder; ga.id = st.id.as<int>();
     ga.x = st.x.as<double>(); ga.y = st.y.as<double>(); ga.z = st.z.as<double>();
     ga.vx = st.vx.as<double>(); ga.vy = st.vy.as<double>(); ga.vz = st.vz.as<double>();
@@ -506,14 +435,13 @@ extern "C" int sphx_state_rad_phase(sphx_ctx* ctx, double dt, double d, int64_t 
     ga.pt = st.ptype.as<double>(); ga.E = st.E.as<double>();
     ga.col = col; ga.pos = g_pos; ga.sx = g_x; ga.sy = g_y; ga.sz = g_z; ga.vel = g_vel; ga.om = g_m; ga.omu = g_mu; ga.oh = g_h;
     ga.oT = g_T; ga.opt = g_pt; ga.oE = g_E;
-    hipLaunchKernelGGL(rs_gather_kernel, dim3(rp_blocks(nn, 256)), dim3(256), 0, stream, ga);
-    HIPCHK(hipGetLastError());
+    SPHX_TRY(sphx_phase_gather(ctx, ga));
     SPHX_TRY(sphx_phase_translate(ctx, col, true, list));
     HIPCHK(hipMemcpy2DAsync(f0, ss * sizeof(double), ctx->fun_id.p, (size_t)sp * sizeof(double), ss * sizeof(double), nn,
                             hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(rs_cross_kernel, dim3(rp_blocks(nn, 256)), dim3(256), 0, stream, (int)n, s, f0, d_tab + 3 * ss, cross0);
-    if (n_src > 0) hipLaunchKernelGGL(rs_pick_kernel, dim3(rp_blocks((size_t)n_src, 256)), dim3(256), 0, stream, (int)n_src, d_ids, g_pos, d_src);
-    if (n_dst > 0) hipLaunchKernelGGL(rs_pick_kernel, dim3(rp_blocks((size_t)n_dst, 256)), dim3(256), 0, stream, (int)n_dst, d_ids + n_src, g_pos, d_dst);
+    hipLaunchKernelGGL(rs_cross_kernel, dim3(sphx_blocks(nn, 256)), dim3(256), 0, stream, (int)n, s, f0, d_tab + 3 * ss, cross0);
+    if (n_src > 0) hipLaunchKernelGGL(rs_pick_kernel, dim3(sphx_blocks((size_t)n_src, 256)), dim3(256), 0, stream, (int)n_src, d_ids, g_pos, d_src);
+    if (n_dst > 0) hipLaunchKernelGGL(rs_pick_kernel, dim3(sphx_blocks((size_t)n_dst, 256)), dim3(256), 0, stream, (int)n_dst, d_ids + n_src, g_pos, d_dst);
     HIPCHK(hipGetLastError());
     SPHX_TRY(ctx->radstate_t.mark(ctx, 1));
     // ---- 3: nsc:922-965 ----
@@ -529,7 +457,7 @@ extern "C" int sphx_state_rad_phase(sphx_ctx* ctx, double dt, double d, int64_t 
     ia.f_in = f0; ia.m = g_m; ia.pt = g_pt; ia.lf2 = rad.lf2; ia.off = off; ia.tab = d_tab;
     ia.ppj = photons_per_joule; ia.amu = amu;
     ia.f_out = f1; ia.frac = frac_destroyed ? d_fr : nullptr;
-    hipLaunchKernelGGL(rp_ionise_kernel, dim3(rp_blocks(nn, RP_WG)), dim3(RP_WG), rp_lds_bytes(s, 3), stream, ia);
+    hipLaunchKernelGGL(rp_ionise_kernel, dim3(sphx_blocks(nn, RP_WG)), dim3(RP_WG), rp_lds_bytes(s, 3), stream, ia);
     HIPCHK(hipGetLastError());
     RpBook ha;
     ha.n = (int)n; ha.s = s;
@@ -556,14 +484,10 @@ extern "C" int sphx_state_rad_phase(sphx_ctx* ctx, double dt, double d, int64_t 
     SPHX_TRY(rp_book_run(ctx, true, ca, d_part, d_tot, nullptr));
     // ---- 8: the write-back through st.id; the composition rows into fun_id ----
     if (ctx->drag) SPHX_TRY(sphx_phase_drag_refresh(ctx, n, s, cres.final_comp, d_tab + 6 * ss, d_tab + 7 * ss, d_mgm, d_mcs));
-    RsBack ba;
-    ba.n = (int)n; ba.id = st.id.as<int>();
-    ba.vel = c_vel; ba.E = c_E; ba.T = c_T; ba.mu = c_mu; ba.gam = c_g; ba.mgm = ctx->drag ? d_mgm : nullptr; ba.mcs = ctx->drag ? d_mcs : nullptr;
-    ba.vx = st.vx.as<double>(); ba.vy = st.vy.as<double>(); ba.vz = st.vz.as<double>();
-    ba.oE = st.E.as<double>(); ba.oT = st.T.as<double>(); ba.omu = st.mu.as<double>(); ba.ogam = st.gam.as<double>();
-    ba.omgm = ctx->drag ? st.mgm.as<double>() : nullptr; ba.omcs = ctx->drag ? st.mcs.as<double>() : nullptr;
-    hipLaunchKernelGGL(rs_back_kernel, dim3(rp_blocks(nn, 256)), dim3(256), 0, stream, ba);
-    HIPCHK(hipGetLastError());
+    const PhaseBack ba{(int)n, st.id.as<int>(), c_vel, st.vx.as<double>(), st.vy.as<double>(), st.vz.as<double>(), ctx->drag ? 6 : 4,
+                       {c_E, c_T, c_mu, c_g, d_mgm, d_mcs},
+                       {st.E.as<double>(), st.T.as<double>(), st.mu.as<double>(), st.gam.as<double>(), st.mgm.as<double>(), st.mcs.as<double>()}};
+    SPHX_TRY(sphx_phase_back(ctx, ba));
     HIPCHK(hipMemcpy2DAsync(ctx->fun_id.p, (size_t)sp * sizeof(double), cres.final_comp, ss * sizeof(double), ss * sizeof(double), nn,
                             hipMemcpyDeviceToDevice, stream));
     const CopyF64 ds[] = {{cross_array, cross0, nn}, {lf2, rad.lf2, g}, {momentum, rad.mom, 3 * g}, {extinction, rad.ext, g},

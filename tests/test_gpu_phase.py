@@ -84,16 +84,13 @@ CASES = [(pf.SHAPES[0], "fraction", "loop"), (pf.SHAPES[1], "count", "hydro_upda
          (pf.SHAPES[6], "count", "loop"), (SPHERE, "fraction", "hydro_update"), (SPHERE, "count", "loop")]
 
 
-@pytest.mark.parametrize("spec,guard,forms", CASES, ids=["%s-%s-%s" % (spec_id(c[0]), c[1], c[2]) for c in CASES])
-def test_resident_phase_equals_the_array_route(nsc, spec, guard, forms):
-    """2. Simulation.dust_phase against compat.dust_phase on the downloaded state, neighbors() and download_composition():
-    every stage output, the final composition, all counts and all totals with np.array_equal.  Nothing else of the state
-    changes.  guard="count" is compared here and only here: bit for bit needs no margin."""
-    sim, f = prepared(spec, forms)
+def assert_equals_array_route(nsc, sim, f, guard, what=""):
+    """Simulation.dust_phase on the stepped `sim` against compat.dust_phase on its downloads -> (the resident result, the
+    composition before).  The array route runs on compat's own context."""
     arr, st, nb, comp = array_route(nsc, sim, f, guard)
     res = sim.dust_phase(f["dt"], f["d"], guard=guard, full=True, **pf.tables(f))
     m, fu, mu, gam, totals, stages = arr
-    print(spec_id(spec), guard, forms, res["chem_counts"], res["dust_counts"], {k_: res[k_] for k_ in nsc.PHASE_TOTALS + nsc.PHASE_COUNTS},
+    print(what, guard, res["chem_counts"], res["dust_counts"], {k_: res[k_] for k_ in nsc.PHASE_TOTALS + nsc.PHASE_COUNTS},
           sim.phase_timing())
     for name in STAGES:
         assert same(res[name], stages[name]), name
@@ -109,6 +106,16 @@ def test_resident_phase_equals_the_array_route(nsc, spec, guard, forms):
         assert same(st[key], st2[key]), key
     assert np.array_equal(sim.neighbors(), nb)
     assert np.all(np.isfinite(after["mass"])) and np.all(after["mass"] > 0)
+    return res, comp
+
+
+@pytest.mark.parametrize("spec,guard,forms", CASES, ids=["%s-%s-%s" % (spec_id(c[0]), c[1], c[2]) for c in CASES])
+def test_resident_phase_equals_the_array_route(nsc, spec, guard, forms):
+    """2. Simulation.dust_phase against compat.dust_phase on the downloaded state, neighbors() and download_composition():
+    every stage output, the final composition, all counts and all totals with np.array_equal.  Nothing else of the state
+    changes.  guard="count" is compared here and only here: bit for bit needs no margin."""
+    sim, f = prepared(spec, forms)
+    assert_equals_array_route(nsc, sim, f, guard, "%s %s" % (spec_id(spec), forms))
 
 
 def test_phase_refreshes_the_drag_coefficients(nsc):

@@ -116,22 +116,20 @@ def _cxx():
     return None
 
 
-@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
-def test_list_translation_slot_arithmetic_on_the_host(tmp_path, sanitize):
-    """tests/host/phase_map_check.cpp replays sphx_phase_map.h's two passes over random storage orders, processing orders
-    and lists with missing entries (n = 1, 33, 63 .. 65, 257, 2049; K = 1, 7, 40, 64) against a direct construction, and
-    the (n,k) int64 form; a rule that forgets the processing order must break it (the program fails otherwise)."""
+def _host_check(tmp_path, name, sanitize, verdict):
+    """Builds tests/host/<name>.cpp (with sanitizers: a program of its own) and runs it: it must report `verdict`, and a
+    deliberately broken rule must fail inside it (the program prints how often)."""
     cxx = _cxx()
     if cxx is None:
         pytest.skip("no host C++ compiler on this machine")
-    exe = str(tmp_path / "phase_map_check")
+    exe = str(tmp_path / name)
     flags = ["-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror"]
     if sanitize:
         flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
         ver = subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
         if "clang" not in ver.lower():
             flags += ["-static-libasan", "-static-libubsan"]
-    res = subprocess.run([cxx] + flags + ["-o", exe, os.path.join(ROOT, "tests", "host", "phase_map_check.cpp")],
+    res = subprocess.run([cxx] + flags + ["-o", exe, os.path.join(ROOT, "tests", "host", name + ".cpp")],
                          capture_output=True, text=True)
     no_runtime = any(("cannot find" in ln or "no such file" in ln.lower()) and ("asan" in ln or "ubsan" in ln)
                      for ln in res.stderr.splitlines())
@@ -141,6 +139,23 @@ def test_list_translation_slot_arithmetic_on_the_host(tmp_path, sanitize):
     run = subprocess.run([exe], capture_output=True, text=True)
     print(run.stdout, run.stderr)
     assert run.returncode == 0, run.stdout + run.stderr
-    assert "sphx_phase_map: 0 violations" in run.stdout
+    assert verdict in run.stdout
     broken = [ln for ln in run.stdout.splitlines() if ln.startswith("broken rule:")]
     assert broken and int(broken[0].split()[2]) > 0              # the check can fail
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_list_translation_slot_arithmetic_on_the_host(tmp_path, sanitize):
+    """tests/host/phase_map_check.cpp replays sphx_phase_map.h's two passes over random storage orders, processing orders
+    and lists with missing entries (n = 1, 33, 63 .. 65, 257, 2049; K = 1, 7, 40, 64) against a direct construction, and
+    the (n,k) int64 form; a rule that forgets the processing order must break it (the program fails otherwise)."""
+    _host_check(tmp_path, "phase_map_check", sanitize, "sphx_phase_map: 0 violations")
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_reverse_list_size_rules_on_the_host(tmp_path, sanitize):
+    """tests/host/revlist_check.cpp checks sphx_revlist.h, the size rules of the reverse list that rad_cooling,
+    supernova_destruction and chemisputtering_2 build with sphx_rev_build, by brute force: the sort looks at the least b in
+    [1, 32] bits with 2^b >= key_end (key_end = 1 .. 5, 2^16 - 1 .. 2^16 + 1, 2^31 - 16), and for M = 0, 1, 3, 4, 5, 1023
+    the sorted half starts on a 16-byte boundary at least M ints behind the raw one and both fit the ints ensured."""
+    _host_check(tmp_path, "revlist_check", sanitize, "sphx_revlist: 0 violations")
