@@ -602,6 +602,76 @@ int sphx_supernova_destruction(sphx_ctx* ctx, int64_t n, int k, int s, const dou
  * inputs going up, records and the K-major list, ms[1] the reverse list (scan, one host wait, fill, sort), ms[2] the dust
  * pass, ms[3] the row pass and the outputs coming back.  Measurement aid; replaces nothing in the reference.        */
 int sphx_dust_last_timing(sphx_ctx* ctx, double ms[4]);
+/* ---- nsc.supernova_impulse(points, masses, supernova_pos, ptypes)                               nsc:1192-1204 ----- *
+ * The kick of an exploding star on the gas around it, for n_sn stars in the order given - the driver's loop drv:350-352.
+ * The module globals are arguments: mass_displaced (nsc:1193: 194.28 solar_mass) and kick_energy = supernova_energy 0.736
+ * (nsc:1200; 2 kick_energy is exact, so it is the reference's 2 supernova_energy 0.736).  For each star ku:
+ *   s_i = (dx^2 + dy^2) + dz^2, dx = points[i] - points[ku] per column                      nsc:1194 (NumPy's order)
+ *   the candidates: the rows with ptypes == 0, by s ascending                               nsc:1195-1196
+ *   selected while running < mass_displaced, running the LEFT-TO-RIGHT sum of their masses  nsc:1197 (np.cumsum)
+ *   true_mass = the sum of the selected masses                                              nsc:1198
+ *   vel = sqrt(2 kick_energy / true_mass)                                                   nsc:1200
+ *   d_vels = (dx / sqrt(s)) vel per component, s formed again as above                      nsc:1201
+ *   velocities_inout[selected] += d_vels                                                    drv:351-352
+ * Star t + 1's additions land on top of star t's, as the driver's sequential += does; positions and masses do not
+ * change between the stars.  The selection and kick of a star are written behind the previous star's in sel_ids, d_vels.
+ * Ours, where the reference leaves it open or differs:
+ *   1. Ties: rows at bit-equal distance are ordered by ASCENDING INDEX (the stable order).  The reference's np.argsort is
+ *      the default quicksort, not stable: its order among exact ties is unspecified, ours is one of those it may give.
+ *   2. A NaN distance orders last, by index.
+ *   3. true_mass is summed in the library's fixed order (sphx_ordered_totals) over the selection IN SORTED ORDER: chunks
+ *      of 256 consecutive rows summed left to right, lane l of 256 adds the chunks l, l + 256, ... in order, the lanes by
+ *      a binary tree (l += l + 128, l + 64, ...).  np.sum's pairwise order differs: at most (n_sel - 1) 2^-53 relative.
+ *   4. Masses that are not all positive and finite: the reference's mask cumsum < M need not be a prefix then; ours is
+ *      the prefix up to the first row whose running sum is not < mass_displaced (a NaN mass ends it).  Such rows are
+ *      counted among the candidates (bad_mass; once per pass over them: again when a star is done again).
+ * Quirks kept: a gas row at distance 0 (a gas "star", a coincident row) gets NaN kicks - 0 / 0 - and is counted
+ * (zero_distance), not guarded; an empty selection gives true_mass = 0 and vel = inf.
+ * The same inputs give the same bits and the same counts on every call: the key bound comes from integer histograms,
+ * the candidates are sorted by (distance bits, index), no floating-point atomic is used.
+ * Outputs: sel_count int64[n_sn]; sel_ids int64[cap], d_vels (cap,3): the first sum(sel_count) rows are written;
+ * true_mass, vel [n_sn]; velocities_inout (n,3) or NULL; counts int64[SPHX_SN_NCOUNT] or NULL, over the call:
+ * candidates sorted, sorts in one workgroup's LDS (up to SPHX_SN_LDS_CAP candidates), sorts in global memory,
+ * widenings (a walk ran out of candidates and the star was redone over every gas row), selected rows at distance 0,
+ * candidates whose mass is not positive and finite.
+ * SPHX_E_ARG: a NULL required pointer, n < 1 or n >= 2^31 - 16, n_sn < 0, a star outside [0, n), mass_displaced not
+ * positive and finite, and cap < sum(sel_count): the error text names the size needed and NO output is written.      */
+#define SPHX_SN_LDS_CAP        4096
+#define SPHX_SN_CANDIDATES     0
+#define SPHX_SN_LDS_SORTS      1
+#define SPHX_SN_GLOBAL_SORTS   2
+#define SPHX_SN_WIDENINGS      3
+#define SPHX_SN_ZERO_DISTANCE  4
+#define SPHX_SN_BAD_MASS       5
+#define SPHX_SN_NCOUNT         6
+#define SPHX_SN_STAGES         6
+int sphx_supernova_impulse(sphx_ctx* ctx, int64_t n, const double* points, const double* masses, const double* ptypes,
+                           int64_t n_sn, const int64_t* supernova_pos, double mass_displaced, double kick_energy,
+                           double* velocities_inout /* (n,3) or NULL */, int64_t cap, int64_t* sel_count /* int64[n_sn] */,
+                           int64_t* sel_ids /* int64[cap] */, double* d_vels /* (cap,3) */, double* true_mass /* [n_sn] */,
+                           double* vel /* [n_sn] */, int64_t* counts /* int64[SPHX_SN_NCOUNT] or NULL */);
+/* ---- the supernova event on the resident state, N unchanged                                       drv:350-358 ----- *
+ * sphx_supernova_impulse on the state as it is on the device, for the stars ids[n_sn] (particle indices of the uploaded
+ * state, in the driver's order), the kicks added to the resident velocities (drv:350-352), then
+ *   ct = crossing_time(neighbor, velocities, sizes, particle_type)                                     drv:357
+ *   dt_event = min(dt_0 / 100, ct)                                                                     drv:358
+ * with the last sphx_step's own list (sphx_state_download_neighbors), the step's radii as sizes and the KICKED
+ * velocities.  The state is gathered into the caller's particle order as the phases gather it and the selection runs
+ * on that copy: the bits are those of sphx_supernova_impulse and sphx_crossing_time on the downloaded state.  Only the
+ * velocities are written, and only when the call succeeds: a refused call leaves the state as it was.  The insertion of
+ * the new particles (drv:361-396) changes N and is the caller's.
+ * Outputs as sphx_supernova_impulse's (sel_ids in the caller's order); ct, dt_event: scalars.
+ * SPHX_E_STATE as sphx_state_dust_phase: no state, no step yet, incremental search, the step's list gone.
+ * SPHX_E_ARG: an id outside [0, n), mass_displaced not positive and finite, cap too small (the text names the size).  */
+int sphx_state_supernova_impulse(sphx_ctx* ctx, int64_t n_sn, const int64_t* ids, double mass_displaced, double kick_energy,
+                                 double dt_0, int64_t cap, int64_t* sel_count /* int64[n_sn] */, int64_t* sel_ids /* int64[cap] */,
+                                 double* d_vels /* (cap,3) */, double* true_mass /* [n_sn] */, double* vel /* [n_sn] */,
+                                 int64_t* counts /* int64[SPHX_SN_NCOUNT] or NULL */, double* ct, double* dt_event);
+/* Device time of the stages of the last sphx_supernova_impulse call on this context, from HIP events on its stream, in
+ * ms and added up over its stars: ms[0] keys, ms[1] the bound (histograms, one host wait per level), ms[2] compaction,
+ * ms[3] the sort, ms[4] the walk and its host wait, ms[5] true_mass, vel and the kick.  Also after
+ * sphx_state_supernova_impulse (the gather, the crossing time and the write-back are not in it).  Measurement aid.  */
+int sphx_sn_last_timing(sphx_ctx* ctx, double ms[SPHX_SN_STAGES]);
 /* ---- nsc.chemisputtering_2(points, neighbor, mass, f_un, mu_array, sizes, T, particle_type)      nsc:1265-1416 ----- *
  * Thermal / chemical sputtering of the dust rows and reuptake by the gas entries of their lists, on the list `neighbors`
  * returned (drv:405).  The module globals d and dt are arguments, and so are the per-species tables (nsc:41-52).

@@ -17,6 +17,7 @@ for the functions the driver sph/code_running.py ("drv") calls on the SPH inner 
     rad_cooling            nsc:1019-1176    drv:276
     supernova_destruction  nsc:1211-1263    drv:411
     chemisputtering_2      nsc:1265-1416    drv:405
+    supernova_impulse      nsc:1192-1204    drv:351 (supernova_impulses: the loop drv:350-352)
     luminosity_relation    nsc:174-200      (without its unused `imf` argument)
 
 and, under names of their own, the pieces rad_heating (nsc:893-1017) and the driver's radiative block (drv:247-316)
@@ -740,6 +741,88 @@ def dust_last_timing():
     """Device time of the last supernova_destruction call of this module, from HIP events (include/sphx.h
     sphx_dust_last_timing) -> dict of ms: upload, reverse, dust, rows."""
     return _last_timing("sphx_dust_last_timing", ("upload", "reverse", "dust", "rows"))
+
+
+# ==============================================================================================
+# The kick of an exploding star on the gas around it: supernova_impulse (nsc:1192-1204)
+# ==============================================================================================
+supernova_energy = 1e44                                                         # nsc:35, J
+mass_displaced = 194.28 * solar_mass                                            # nsc:1193
+SN_KICK_FRACTION = 0.736                                                        # nsc:1200
+SN_COUNTS = ("candidates", "lds_sorts", "global_sorts", "widenings", "zero_distance", "bad_mass")
+_SN_FIRST_CAP = 1 << 16
+
+
+def _sn_call(points, masses, stars, ptypes, velocities, mass_displaced, supernova_energy):
+    """sphx_supernova_impulse on host arrays -> (velocities or None, sel_count, sel_ids, d_vels, true_mass, vel, counts)."""
+    import re
+    pts = f64(points)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("points must be (N, 3)")
+    n = pts.shape[0]
+    m, pt = f64(masses, (n,)), f64(ptypes, (n,))
+    ku = i64(stars)
+    if ku.ndim != 1:
+        raise ValueError("supernova_pos must be a scalar or a 1-D array of indices")
+    n_sn = ku.shape[0]
+    v = None if velocities is None else np.array(f64(velocities, (n, 3)))        # (a copy: the call adds in place)
+    g = globals()
+    M = float(g["mass_displaced"] if mass_displaced is None else mass_displaced)
+    E = float(g["supernova_energy"] if supernova_energy is None else supernova_energy) * SN_KICK_FRACTION
+    most = int(np.count_nonzero(pt == 0)) * n_sn
+    cap = min(most, _SN_FIRST_CAP)
+    c_ = context()
+    while True:
+        sel_count = np.zeros(n_sn, dtype=np.int64)
+        sel_ids = np.zeros(max(cap, 1), dtype=np.int64); d_vels = np.zeros((max(cap, 1), 3))
+        true_mass = np.zeros(n_sn); vel = np.zeros(n_sn)
+        counts = np.zeros(len(SN_COUNTS), dtype=np.int64)
+        rc = c_.lib.sphx_supernova_impulse(c_.h, n, dp(pts), dp(m), dp(pt), n_sn, ip(ku), M, E, dp(v), cap, ip(sel_count), ip(sel_ids),
+                                           dp(d_vels), dp(true_mass), dp(vel), ip(counts))
+        if rc == -1 and cap < most:
+            # (cap too small: the error text names the size needed, include/sphx.h)
+            need = re.search(r"the selections hold (\d+) rows", (c_.lib.sphx_last_error(c_.h) or b"").decode())
+            if need:
+                cap = int(need.group(1))
+                continue
+        c_.check(rc)
+        break
+    total = int(sel_count.sum())
+    return v, sel_count, sel_ids[:total], d_vels[:total], true_mass, vel, dict(zip(SN_COUNTS, (int(x) for x in counts)))
+
+
+def supernova_impulse(points, masses, supernova_pos, ptypes, mass_displaced=None, supernova_energy=None, full=False):
+    """nsc:1192-1204 for one star (a scalar supernova_pos) -> (d_vels (n_sel,3), selected_points (n_sel,) int64): the
+    nearest gas rows whose running mass stays below mass_displaced (nsc:1193) and their radial kick.  Rows at bit-equal
+    distance are taken in ascending index (the reference's argsort leaves their order open); include/sphx.h,
+    sphx_supernova_impulse, lists the rest.  mass_displaced and supernova_energy default to the module's values, read at
+    call time.  full=True appends a dict: true_mass, vel, counts (SN_COUNTS)."""
+    if np.ndim(supernova_pos) != 0:
+        raise ValueError("supernova_pos must be a scalar (supernova_impulses takes an array of stars)")
+    _, _, ids, d_vels, tm, vel, counts = _sn_call(points, masses, [int(supernova_pos)], ptypes, None, mass_displaced, supernova_energy)
+    if full:
+        return d_vels, ids, {"true_mass": float(tm[0]), "vel": float(vel[0]), "counts": counts}
+    return d_vels, ids
+
+
+def supernova_impulses(points, masses, supernova_pos, ptypes, velocities, mass_displaced=None, supernova_energy=None, full=False):
+    """The driver's loop drv:350-352 over the stars supernova_pos, in their order -> (velocities_new (N,3), selections):
+    selections[t] = (d_vels, selected_points) of star t as supernova_impulse returns them; a star's kicks are added on top
+    of the previous stars'.  The given velocities are not modified.  full=True appends a dict: true_mass, vel (per star),
+    counts (SN_COUNTS)."""
+    v, sel_count, ids, d_vels, tm, vel, counts = _sn_call(points, masses, np.atleast_1d(supernova_pos), ptypes, velocities,
+                                                          mass_displaced, supernova_energy)
+    ends = np.cumsum(sel_count)
+    sels = [(d_vels[e - c:e], ids[e - c:e]) for c, e in zip(sel_count, ends)]
+    if full:
+        return v, sels, {"true_mass": tm, "vel": vel, "counts": counts}
+    return v, sels
+
+
+def sn_last_timing():
+    """Device time of the last supernova_impulse(s) call of this module, from HIP events and added up over its stars
+    (include/sphx.h sphx_sn_last_timing) -> dict of ms: keys, bound, compact, sort, walk, kick."""
+    return _last_timing("sphx_sn_last_timing", ("keys", "bound", "compact", "sort", "walk", "kick"))
 
 
 # ==============================================================================================

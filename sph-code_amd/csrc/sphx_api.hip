@@ -179,6 +179,8 @@ extern "C" void sphx_destroy(sphx_ctx* ctx) {
     for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t, &ctx->chem_t, &ctx->phase_t, &ctx->radphase_t, &ctx->radstate_t})
         for (int i = 0; i < 6; ++i)
             if (t->ev[i]) (void)hipEventDestroy(t->ev[i]);
+    for (int i = 0; i <= SPHX_SN_STAGES; ++i)
+        if (ctx->sn_ev[i]) (void)hipEventDestroy(ctx->sn_ev[i]);
     for (int r = 0; r < 3; ++r)
         for (int i = 0; i < 10; ++i)
             if (ctx->evring[r][i]) (void)hipEventDestroy(ctx->evring[r][i]);

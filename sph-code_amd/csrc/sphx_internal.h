@@ -449,6 +449,14 @@ struct sphx_ctx {
     DevBuf radstate_buf, radstate_int;
     double radstate_tab[8 * SPHX_MAX_SPECIES] = {0};
     StageTimer radstate_t{5};
+    // supernova_impulse (sphx_sn.hip), buffers of its own: staged inputs, work (keys, histograms, scalars, the selection's
+    // masses and their partial sums), the candidates (key, id), outputs (d_vels, true_mass, vel, sel_ids)
+    DevBuf sn_in, sn_work, sn_cand, sn_out;
+    // events of a star: [0] start, [1] keys, [2] bound, [3] compacted, [4] sorted, [5] walked, [6] kicked; the stages' times
+    // are added up over the stars of a call (sphx_sn_last_timing), and so are the counts (SPHX_SN_*)
+    hipEvent_t sn_ev[SPHX_SN_STAGES + 1] = {nullptr};
+    double sn_ms[SPHX_SN_STAGES] = {0};
+    int64_t sn_counts[SPHX_SN_NCOUNT] = {0};
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
@@ -766,6 +774,11 @@ int sphx_transpose_nbr(sphx_ctx* ctx, int64_t n, int k, const int64_t* nb_rowmaj
 // the loop-form density (nsc:693-702) on device inputs: points (n,3), the K-major list (sphx_loopforms.hip; sphx_density's kernel)
 int sphx_loop_density_dev(sphx_ctx* ctx, int64_t n, int k, const int* nbr, const double* points, const double* mass,
                           const double* ptype, double d, double m_0, double* out);
+// crossing_time (nsc:776-786) on device inputs: velocities (n,3), sizes, ptype (n), a K-major list; *ct_bits is primed, then
+// holds the votes' minimum; sphx_loop_ct_value turns it into the function's return value (sphx_loopforms.hip)
+int sphx_loop_ct_dev(sphx_ctx* ctx, int64_t n, int k, const int* nbr, const double* velocities, const double* sizes, const double* ptype,
+                     u64* ct_bits);
+double sphx_loop_ct_value(const sphx_ctx* ctx, u64 bits);
 // ---- the middle parts of chemisputtering_2 and supernova_destruction, on device inputs (sphx_chem.hip, sphx_dust.hip) ----
 struct ChemDev { double *pos, *m, *mu, *sizes, *T, *ptype, *fun, *tab; };       // (n,3), (n,) x 5, (n,s), the tables (4 s)
 struct ChemPar { double d, dt, k_B, m_0, symax; };
@@ -801,6 +814,12 @@ struct CoolRes { double *final_comp, *energy, *rec_array, *tab; };              
 int sphx_cool_check(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, double dt, double d);
 int sphx_cool_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const CoolDev& in, const long long* nb64, const int* kmajor,
                   double dt, double d, StageTimer* t, CoolRes* res);
+// ---- supernova_impulse on device inputs (sphx_sn.hip) ----
+// the outputs on the device (in ctx->sn_out, cap rows), the selections' sizes on the host; total: the rows they hold together
+struct SnRes { double *d_vels, *true_mass, *vel; long long* sel_ids; std::vector<int64_t> sel_count; int64_t total; };
+int sphx_sn_check(sphx_ctx* ctx, const char* who, int64_t n, int64_t n_sn, const int64_t* supernova_pos, double mass_displaced, int64_t cap);
+int sphx_sn_run(sphx_ctx* ctx, const char* who, int64_t n, const double* pos, const double* mass, const double* ptype, int64_t n_sn,
+                const int64_t* supernova_pos, double mass_displaced, double kick_energy, double* velocities, int64_t cap, SnRes* res);
 // ---- shared by the side stages (sphx_side.hip) ----
 // the reverse list of a stage: M entries, each slice sorted, valid until the next sphx_rev_build on the context
 struct RevList { size_t M; const int* rev; };

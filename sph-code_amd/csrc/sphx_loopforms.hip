@@ -312,20 +312,32 @@ extern "C" int sphx_crossing_time(sphx_ctx* ctx, int64_t n, int k, const int64_t
     LoopArgs a;
     SPHX_TRY(loop_begin(ctx, n, k, neighbor, &a));
     UPF(in_b, velocities, 3 * n, vel); UPF(in_d, sizes, n, h); UPF(in_h, particle_type, n, pt);
-    a.ct_bits = ctx->scal.as<u64>() + SC_CT_BITS;
-    SPHX_TRY(sphx_prime_ct(ctx, a.ct_bits));
+    u64* ct_bits = ctx->scal.as<u64>() + SC_CT_BITS;
     ctx->ct_primed = false;
-    LAUNCH1(loop_ct_kernel);
+    SPHX_TRY(sphx_loop_ct_dev(ctx, n, k, a.nbr, a.vel, a.h, a.pt, ct_bits));
     u64 bits = 0;
-    SPHX_TRY(down(ctx, &bits, a.ct_bits, sizeof(u64)));
-    if (bits == SPHX_CT_NONE) {
-        *out = ctx->cst.dt_0 / 10.0;                      // nsc:783-784
-    } else {
-        double v;
-        memcpy(&v, &bits, 8);
-        *out = v + 0.0001;                                // nsc:786
-    }
+    SPHX_TRY(down(ctx, &bits, ct_bits, sizeof(u64)));
+    *out = sphx_loop_ct_value(ctx, bits);
     return SPHX_OK;
+}
+// ... on device inputs: velocities (n,3), sizes and ptype (n), a K-major list; the votes' minimum into *ct_bits (primed here)
+int sphx_loop_ct_dev(sphx_ctx* ctx, int64_t n, int k, const int* nbr, const double* velocities, const double* sizes, const double* ptype,
+                     u64* ct_bits) {
+    LoopArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = (int)n; a.npad = (int)sphx_pad64(n); a.k = k;
+    a.nbr = nbr; a.vel = velocities; a.h = sizes; a.pt = ptype;
+    a.ct_bits = ct_bits;
+    SPHX_TRY(sphx_prime_ct(ctx, ct_bits));
+    LAUNCH1(loop_ct_kernel);
+    return SPHX_OK;
+}
+// nsc:783-786 from the votes' minimum
+double sphx_loop_ct_value(const sphx_ctx* ctx, u64 bits) {
+    if (bits == SPHX_CT_NONE) return ctx->cst.dt_0 / 10.0;    // nsc:783-784
+    double v;
+    memcpy(&v, &bits, 8);
+    return v + 0.0001;                                        // nsc:786
 }
 
 extern "C" int sphx_net_impulse(sphx_ctx* ctx, int64_t n, int k, const double* points, const double* mass,

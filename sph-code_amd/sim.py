@@ -384,6 +384,60 @@ class Simulation:
         c.check(c.lib.sphx_state_radphase_last_timing(c.h, dp(ms)))
         return dict(zip(("gather", "transfer", "ionise_heat", "cooling", "bookkeeping"), ms.tolist()))
 
+    # ---- the supernova event of the time loop (code_running.py:350-358) on the resident state, N unchanged ----------
+    def supernova_impulse(self, supernova_ids, dt_0=None, mass_displaced=None, supernova_energy=None):
+        """code_running.py:350-358 on the state as it is on the device (include/sphx.h sphx_state_supernova_impulse): for
+        every star of supernova_ids (particle indices of the uploaded state, in the driver's order) the kick of
+        nsc.supernova_impulse added to the resident velocities, then ct = crossing_time on the last step's own list
+        (neighbors()), the step's radii and the kicked velocities, and the event's time step min(dt_0 / 100, ct).
+        -> dict: dt (what the caller hands to dust_phase and step(fixed_dt=...)), ct, selections (per star (d_vels,
+        selected ids) as compat.supernova_impulse returns them), sel_count, true_mass, vel, counts (compat.SN_COUNTS).
+        The bits are those of compat.supernova_impulses and compat.crossing_time on the downloaded state.  dt_0,
+        mass_displaced and supernova_energy default to compat's.  An empty supernova_ids is a no-op: dt is None.  The
+        insertion of the new particles (drv:361-396) changes N and stays with the caller.  Needs one step; not with
+        incremental=True."""
+        import re
+        from . import compat
+        ids = np.ascontiguousarray(np.asarray(supernova_ids, dtype=np.int64).reshape(-1))
+        n_sn = ids.shape[0]
+        if n_sn == 0:
+            return dict(dt=None, ct=None, selections=[], sel_count=np.zeros(0, dtype=np.int64), true_mass=np.zeros(0), vel=np.zeros(0),
+                        counts=dict.fromkeys(compat.SN_COUNTS, 0))
+        M = float(compat.mass_displaced if mass_displaced is None else mass_displaced)
+        E = float(compat.supernova_energy if supernova_energy is None else supernova_energy) * compat.SN_KICK_FRACTION
+        dt0 = float(compat.dt_0 if dt_0 is None else dt_0)
+        most = int(np.count_nonzero(self._ptype == 0)) * n_sn
+        cap = min(most, compat._SN_FIRST_CAP)
+        c = self.ctx
+        while True:
+            sel_count = np.zeros(n_sn, dtype=np.int64)
+            sel_ids = np.zeros(max(cap, 1), dtype=np.int64); d_vels = np.zeros((max(cap, 1), 3))
+            true_mass = np.zeros(n_sn); vel = np.zeros(n_sn)
+            counts = np.zeros(len(compat.SN_COUNTS), dtype=np.int64)
+            ct = C.c_double(0.0); dt = C.c_double(0.0)
+            rc = c.lib.sphx_state_supernova_impulse(c.h, n_sn, _lib.ip(ids), M, E, dt0, cap, _lib.ip(sel_count), _lib.ip(sel_ids),
+                                                    dp(d_vels), dp(true_mass), dp(vel), _lib.ip(counts),
+                                                    C.cast(C.byref(ct), _lib.c_double_p), C.cast(C.byref(dt), _lib.c_double_p))
+            if rc == -1 and cap < most:              # (cap too small: the error text names the size needed)
+                need = re.search(r"the selections hold (\d+) rows", (c.lib.sphx_last_error(c.h) or b"").decode())
+                if need:
+                    cap = int(need.group(1))
+                    continue
+            c.check(rc)
+            break
+        ends = np.cumsum(sel_count)
+        sels = [(d_vels[e - k_:e].copy(), sel_ids[e - k_:e].copy()) for k_, e in zip(sel_count, ends)]
+        return dict(dt=dt.value, ct=ct.value, selections=sels, sel_count=sel_count, true_mass=true_mass, vel=vel,
+                    counts=dict(zip(compat.SN_COUNTS, (int(v) for v in counts))))
+
+    def sn_timing(self):
+        """Device time of the selection stages of the last supernova_impulse() from HIP events, added up over its stars
+        -> dict of ms: keys, bound, compact, sort, walk, kick."""
+        ms = np.zeros(6)
+        c = self.ctx
+        c.check(c.lib.sphx_sn_last_timing(c.h, dp(ms)))
+        return dict(zip(("keys", "bound", "compact", "sort", "walk", "kick"), ms.tolist()))
+
     # ---- snapshot / restart and per-step diagnostics (SURVEY 8f-4; the reference only wrote summary
     # statistics at the end of a run, sph/code_running.py:670, and printed the mass-weighted net
     # accelerations every step, sph/code_running.py:465-468) ----------------------------------------
