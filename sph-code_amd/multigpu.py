@@ -27,20 +27,33 @@ Halo coverage is verified every step (h_i + 2 x displacement <= claimed reach fo
 particle, otherwise all ranks replan with a wider halo and redo the step's search and sums), so
 the decomposed result equals the single-GPU result.
 
-Compute is injected through a small backend interface; the product backend `LibBackend` calls
-libsphx.so's sphx_dev_* entry points on the rank's GPU (no CPU fallback).
+Compute is injected through one backend contract: `TensorBackend` holds the tensor-library form of every helper the
+driver needs besides the physics; the product backend `LibBackend` overrides each with a libsphx.so sphx_dev_* kernel on
+the rank's GPU and adds the physics (no CPU fallback).
 """
 import ctypes as C
 import json
 import os
 import sys
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
 HUGE_CT = float("inf")      # "no gas particle voted a crossing time" (SPHX_CT_NONE: votes are at most DBL_MAX)
+DT_0 = 60. * 60. * 24. * 365. * 250000.      # nsc:38
+MAX_AGE = 3e7 * 60. * 60. * 24. * 365.       # drv:79
+
+
+def timestep_rule(ct_min, first, fixed_dt=0.0):
+    """The driver's dt (drv:222-229) from the global minimum crossing time (nsc:786; HUGE_CT: nobody voted)."""
+    ctv = DT_0 / 10. if ct_min >= HUGE_CT else ct_min + 0.0001
+    if fixed_dt > 0:
+        return fixed_dt
+    dt = DT_0 / 10. if first else max(DT_0 / 5., min(DT_0 * 2., ctv))
+    return MAX_AGE / 100. if ctv > MAX_AGE else dt
 
 
 # ==============================================================================================
@@ -195,9 +208,139 @@ class Exchanger:
 
 
 # ==============================================================================================
+# the backend contract: the driver's helpers in their tensor-library form
+# ==============================================================================================
+def _as_f64(t):
+    return t.view(torch.float64) if t.dtype == torch.int64 else t        # ids travel as raw 8-byte words
+
+
+def _coarse_cell(pos, g_lo, g_cs, G):
+    """Index of each position's cell on the coarse global grid (origin g_lo: 3 host floats; G^3 cubic cells of edge g_cs)."""
+    lo = torch.tensor(list(g_lo), dtype=torch.float64, device=pos.device)
+    c = torch.floor((pos - lo[None]) / g_cs).to(torch.int64).clamp_(0, G - 1)
+    return (c[:, 2] * G + c[:, 1]) * G + c[:, 0]
+
+
+class TensorBackend:
+    """What DistributedSim asks of a backend besides the physics, as tensor-library expressions: the specification.  The CPU
+    tests' backends add the physics from the CPU checker; LibBackend overrides every method with one kernel launch and the GPU
+    tests compare the two.  The fields of pack_rows / regroup are (n,) or (n, w) arrays of float64 or int64 (8-byte words)."""
+
+    reach_cap = 0.0       # head-room of a claimed reach limited to this length (0: not)
+
+    def set_reach_cap(self, cap_abs):
+        self.reach_cap = float(cap_abs)
+
+    def _reach(self, h, vel, halo_scale, skin_frac, dtv):
+        speed = torch.sqrt((vel * vel).sum(dim=1))
+        if self.reach_cap > 0.0:
+            cap = torch.full_like(h, self.reach_cap)
+            a = torch.minimum((halo_scale + skin_frac - 1.0) * h, cap)
+            b = torch.minimum((halo_scale - 1.0) * h, cap)
+            return torch.maximum(h + a, (h + b) + speed * dtv)
+        return torch.maximum((halo_scale + skin_frac) * h, halo_scale * h + speed * dtv)
+
+    def reach(self, h, vel, halo_scale, skin_frac, dt_last):
+        """Reach claimed by each owned particle, w_i = max((halo + skin) h_i, halo h_i + |v_i| dt): its kNN radius with head-room
+        for one step of growth (a radius changes by at most twice the local displacement, so fast movers claim more)."""
+        return self._reach(h, vel, halo_scale, skin_frac, float(dt_last))
+
+    def reach_dt(self, h, vel, halo_scale, skin_frac, dt_dev):
+        """reach with dt taken from the (1,) tensor integrate_auto / integrate_loop(red2=...) returned."""
+        return self._reach(h, vel, halo_scale, skin_frac, float(dt_dev.reshape(-1)[0]))
+
+    def need_map(self, pos, w, g_lo, g_cs, G):
+        """uint8 (G^3,): coarse cells from which a particle could lie within w_i of one of the owned particles at pos.  A cell
+        d = (dx, dy, dz) cells away from an owned particle's cell is marked when sum_a max(|d_a| - 1, 0)^2 <= (w_i / cell)^2:
+        a sphere of cells (distances under-estimated by one cell per axis), not the cube around it - the wide claims of
+        rim particles would otherwise pull in the dense cloud at the cube's corners.
+        (A NaN reach - a broken radius - claims everything, here and in the kernel: as a NaN it would drop out of the
+        kernel's comparisons and, in the form below, swallow its cell's genuine claims in the running maximum.)"""
+        # The rule is monotone in w, so a cell's widest claim stands for all its particles; cells are handled per integer
+        # radius class, each against its stencil of offsets.
+        dev, cs = pos.device, g_cs
+        out = torch.zeros(G * G * G, dtype=torch.uint8, device=dev)
+        if not w.numel():
+            return out
+        w = torch.nan_to_num(w, nan=float("inf"), posinf=float("inf"), neginf=0.0)
+        wmax = torch.zeros(G * G * G, dtype=torch.float64, device=dev)
+        wmax.scatter_reduce_(0, _coarse_cell(pos, g_lo, cs, G), w, reduce="amax", include_self=True)
+        occ = torch.nonzero(wmax > 0).flatten()
+        if not occ.numel():
+            return out
+        q = wmax[occ] / cs
+        r = torch.clamp(torch.floor(q) + 1.0, max=float(G)).to(torch.int64)
+        q2 = q * q
+        cz, cy, cx = occ // (G * G), (occ // G) % G, occ % G
+        for rv in torch.unique(r).tolist():
+            sel = torch.nonzero(r == rv).flatten()
+            lo_r = max(-rv, -(G - 1)); hi_r = min(rv, G - 1)
+            o1 = torch.arange(lo_r, hi_r + 1, device=dev, dtype=torch.int64)
+            a1 = torch.clamp(o1.abs() - 1, min=0)
+            # stencil of this radius class: offsets and their under-estimated squared distance in cells
+            dz, dy, dx = torch.meshgrid(o1, o1, o1, indexing="ij")
+            s2 = (a1 * a1)[:, None, None] + (a1 * a1)[None, :, None] + (a1 * a1)[None, None, :]
+            dz, dy, dx, s2 = dz.reshape(-1), dy.reshape(-1), dx.reshape(-1), s2.reshape(-1).to(torch.float64)
+            chunk = max(1, int(4_000_000 // max(int(s2.numel()), 1)))
+            for c0 in range(0, int(sel.numel()), chunk):
+                ss = sel[c0:c0 + chunk]
+                hit = s2[None, :] <= q2[ss][:, None]                                  # (cells, offsets)
+                z = cz[ss][:, None] + dz[None, :]; y = cy[ss][:, None] + dy[None, :]; x = cx[ss][:, None] + dx[None, :]
+                hit &= (z >= 0) & (z < G) & (y >= 0) & (y < G) & (x >= 0) & (x < G)
+                out[((z * G + y) * G + x)[hit]] = 1
+        return out
+
+    def plan_mask(self, pos, g_lo, g_cs, G, maps, rank):
+        """(mask (W, n), counts (W,) int64): which owned particle goes to which peer as a ghost, and how many, from the
+        ranks' need maps (W, G^3): to every rank but this one whose map covers the particle's cell."""
+        mask = maps[:, _coarse_cell(pos, g_lo, g_cs, G)] != 0
+        mask[rank] = False
+        return mask, mask.sum(dim=1)
+
+    def pack_rows(self, idx, fields):
+        """(len(idx), W) float64 rows of the particles idx (None: all): their entries of `fields`, concatenated."""
+        rows = torch.cat([f if f.dim() == 2 else f[:, None] for f in map(_as_f64, fields)], dim=1)
+        return rows if idx is None else rows[idx]
+
+    def regroup(self, sel, n_sel, rows, fields):
+        """New arrays: fields[sel] (None: the first n_sel as they are) followed by the particles in `rows`."""
+        outs, c = [], 0
+        for f in fields:
+            w = 1 if f.dim() == 1 else f.shape[1]
+            own = _as_f64(f)[:n_sel] if sel is None else _as_f64(f)[sel]
+            if rows is not None and rows.shape[0]:
+                own = torch.cat([own, rows[:, c] if f.dim() == 1 else rows[:, c:c + w]], dim=0)
+            outs.append(own.contiguous().view(f.dtype))
+            c += w
+        return outs
+
+    def append_rows(self, n_owned, rows, fields):
+        """The owned float64 `fields` with the particles in `rows` behind them -> (complete, owned arrays the caller keeps)."""
+        return self.regroup(None, n_owned, rows, fields), fields
+
+    def step_scalars(self, n_owned, h, w_plan, D, hclip, ct):
+        """(4,) tensor {halo too thin? (a kNN radius h_i + 2 D outgrew its claimed reach), -crossing time (ct: (1,)), max h,
+        mean h} of the owned particles.  hclip > 0: escapers' radii (beyond it) must not size the cells - left out of the mean."""
+        if not n_owned:
+            return torch.cat([ct.new_zeros(1), -ct, ct.new_zeros(2)])
+        ho = h[:n_owned]
+        bad = (ho + 2.0 * D > w_plan).any().to(torch.float64).reshape(1)
+        if hclip > 0.0:
+            keep = ho <= hclip
+            hm = (ho * keep).sum() / keep.sum().clamp(min=1)
+        else:
+            hm = ho.mean()
+        return torch.cat([bad, -ct, ho.max().reshape(1), hm.reshape(1)])
+
+    def order(self, n_total):
+        """Cell order of the last search (sorted position -> caller index) where the backend has one; here: None."""
+        return None
+
+
+# ==============================================================================================
 # compute backend on the GPU: libsphx sphx_dev_* (include/sphx.h)
 # ==============================================================================================
-class LibBackend:
+class LibBackend(TensorBackend):
     def __init__(self, device_index, k=40, dist_bound=0.0, clip_grad=False, visc_mode="ref_axis0"):
         from . import _lib
         self.ctx = _lib.Context(device_index)
@@ -229,7 +372,7 @@ class LibBackend:
 
     def pack_rows(self, idx, fields):
         """rows[t] = concatenated fields of particle idx[t] (one launch; include/sphx.h sphx_dev_pack_rows)."""
-        fields = [f.contiguous() for f in fields]
+        fields = [_as_f64(f).contiguous() for f in fields]
         n = int(fields[0].shape[0] if idx is None else idx.numel())
         W = sum(1 if f.dim() == 1 else int(f.shape[1]) for f in fields)
         rows = torch.empty((n, W), dtype=torch.float64, device=self.device)
@@ -243,7 +386,8 @@ class LibBackend:
     def regroup(self, sel, n_sel, rows, fields):
         """New arrays: fields[sel] followed by the particles in `rows` (one launch; sphx_dev_regroup).  Each comes with
         room behind it (SLACK), so that append_rows can put the step's ghosts there without copying the owned part."""
-        fields = [f.contiguous() for f in fields]
+        dts = [f.dtype for f in fields]
+        fields = [_as_f64(f).contiguous() for f in fields]
         nr = 0 if rows is None else int(rows.shape[0])
         n = n_sel + nr
         cap = n + int(self.SLACK * n) + 1024
@@ -253,7 +397,7 @@ class LibBackend:
             oarr, _ = self._table(outs)
             self._chk(self.lib.sphx_dev_regroup(self.ctx.h, n_sel, self._p(sel), nr,
                                                 self._p(rows.contiguous()) if nr else None, len(fields), arr, wid, oarr))
-        return outs
+        return [o.view(d) for o, d in zip(outs, dts)]
 
     def append_rows(self, n_owned, rows, fields):
         """The owned arrays `fields` ((n_owned,) or (n_owned, w), float64) with the particles in `rows` appended IN PLACE:
@@ -283,8 +427,7 @@ class LibBackend:
         return complete, owned
 
     def need_map(self, pos, w, g_lo, g_cs, G):
-        """uint8 (G^3,) map of the coarse cells a neighbour of an owned particle can lie in (one launch;
-        include/sphx.h sphx_dev_need_map).  g_lo: 3 host floats."""
+        """uint8 (G^3,) map of the coarse cells a neighbour of an owned particle can lie in (one launch; sphx_dev_need_map)."""
         out = torch.empty(G * G * G, dtype=torch.uint8, device=self.device)
         lo = (C.c_double * 3)(*g_lo)
         self._chk(self.lib.sphx_dev_need_map(self.ctx.h, int(pos.shape[0]), self._p(pos.contiguous()),
@@ -292,10 +435,13 @@ class LibBackend:
         return out
 
     def set_reach_cap(self, cap_abs):
+        TensorBackend.set_reach_cap(self, cap_abs)
         self._chk(self.lib.sphx_dev_set_reach_cap(self.ctx.h, float(cap_abs)))
 
     def reach(self, h, vel, halo_scale, skin_frac, dt_last):
         """w_i = max((halo + skin) h_i, halo h_i + |v_i| dt) in one launch (sphx_dev_reach)."""
+        if not h.shape[0]:                      # a rank without particles launches nothing
+            return TensorBackend.reach(self, h, vel, halo_scale, skin_frac, dt_last)
         w = torch.empty_like(h)
         self._chk(self.lib.sphx_dev_reach(self.ctx.h, int(h.shape[0]), self._p(h.contiguous()), self._p(vel.contiguous()),
                                           float(halo_scale), float(skin_frac), float(dt_last), self._p(w)))
@@ -320,8 +466,9 @@ class LibBackend:
         return mask, counts
 
     def step_scalars(self, n_owned, h, w_plan, D, hclip, ct):
-        """(4,) device tensor {halo too thin?, -crossing time, max h, clipped mean h} in one launch
-        (sphx_dev_step_scalars)."""
+        """(4,) device tensor {halo too thin?, -crossing time, max h, clipped mean h} in one launch (sphx_dev_step_scalars)."""
+        if not n_owned:                         # a rank without particles launches nothing
+            return TensorBackend.step_scalars(self, n_owned, h, w_plan, D, hclip, ct)
         out = torch.empty(4, dtype=torch.float64, device=self.device)
         self._chk(self.lib.sphx_dev_step_scalars(self.ctx.h, int(n_owned), self._p(h), self._p(w_plan), float(D),
                                                  float(hclip), self._p(ct), self._p(out)))
@@ -355,27 +502,23 @@ class LibBackend:
             self._chk(rc)
         return rc == 1
 
+    def _new(self, *shape, zero=False):
+        """A float64 array on the device for a pass to fill."""
+        return (torch.zeros if zero else torch.empty)(shape, dtype=torch.float64, device=self.device)
+
     def density(self, want_dust=False, out=None):
-        n, dev = self.n_total, self.device
+        n = self.n_total
         # the passes write every owned particle's entry straight into these (no copy); ghosts' entries are
         # either filled by the halo exchange (rho, m Pi) or never read
         if out is None:
-            rho = torch.empty(n, dtype=torch.float64, device=dev)
-            nden = torch.empty(n, dtype=torch.float64, device=dev)
-            ha = torch.empty((n, 3), dtype=torch.float64, device=dev)
-            self.rhod = torch.empty(n, dtype=torch.float64, device=dev) if want_dust else None
-        else:
-            rho, nden, ha = out
+            out = self._new(n), self._new(n), self._new(n, 3)
+            self.rhod = self._new(n) if want_dust else None
+        rho, nden, ha = out
         self._chk(self.lib.sphx_dev_density(self.ctx.h, self._p(rho), self._p(self.rhod), self._p(nden), self._p(ha)))
         return rho, nden, ha
 
     def pi(self, rho_complete, out=None):
-        n, dev = self.n_total, self.device
-        if out is None:
-            bw = torch.empty(n, dtype=torch.float64, device=dev)
-            ct = torch.zeros(1, dtype=torch.float64, device=dev)
-        else:
-            bw, ct = out
+        bw, ct = out if out is not None else (self._new(self.n_total), self._new(1, zero=True))
         self._chk(self.lib.sphx_dev_pi(self.ctx.h, self._p(rho_complete), None, self._p(bw), self._p(ct)))
         return bw, ct
 
@@ -388,24 +531,14 @@ class LibBackend:
 
     def visc_pairwise(self, rho_complete, m, out=None):
         """Pairwise viscosity (sphx_dev_visc_pairwise): needs only the ghosts' densities -> (va, vh, ct)."""
-        n, dev = self.n_total, self.device
-        if out is None:
-            va = torch.empty((n, 3), dtype=torch.float64, device=dev)
-            vh = torch.empty(n, dtype=torch.float64, device=dev)
-            ct = torch.zeros(1, dtype=torch.float64, device=dev)
-        else:
-            va, vh, ct = out
+        n = self.n_total
+        va, vh, ct = out if out is not None else (self._new(n, 3), self._new(n), self._new(1, zero=True))
         self._chk(self.lib.sphx_dev_visc_pairwise(self.ctx.h, self._p(rho_complete), self._p(m), self._p(va), self._p(vh),
                                                   self._p(ct)))
         return va, vh, ct
 
     def visc(self, bw_complete, m, out=None):
-        n, dev = self.n_total, self.device
-        if out is None:
-            va = torch.empty((n, 3), dtype=torch.float64, device=dev)
-            vh = torch.empty(n, dtype=torch.float64, device=dev)
-        else:
-            va, vh = out
+        va, vh = out if out is not None else (self._new(self.n_total, 3), self._new(self.n_total))
         self._chk(self.lib.sphx_dev_visc(self.ctx.h, self._p(bw_complete), self._p(m), self._p(va), self._p(vh)))
         return va, vh
 
@@ -413,18 +546,14 @@ class LibBackend:
         """Leapfrog with verdict and dt taken on the device (sphx_dev_integrate_auto) -> dt as a (1,) device tensor
         (0 when the verdict says the step must be redone: nothing was changed then)."""
         dt = torch.empty(1, dtype=torch.float64, device=self.device)
-        self._chk(self.lib.sphx_dev_integrate_auto(self.ctx.h, n_owned, self._p(pos), self._p(vel), self._p(acc),
-                                                   self._p(E), self._p(T), self._p(m), self._p(mu), self._p(gam),
-                                                   self._p(ptype), self._p(ha), self._p(va), self._p(vh),
-                                                   self._p(red2), 1 if first else 0, float(fixed_dt), self._p(dt)))
+        ptrs = [self._p(t) for t in (pos, vel, acc, E, T, m, mu, gam, ptype, ha, va, vh, red2)]
+        self._chk(self.lib.sphx_dev_integrate_auto(self.ctx.h, n_owned, *ptrs, 1 if first else 0, float(fixed_dt), self._p(dt)))
         return dt
 
     # ---- gas-dust drag (nsc:719-742) and the species pass (nsc:624-627, + metallicity and AGB yields) ----
     def drag(self, m, ptype, mgm, mcs):
         """-> (drag_on (n_total,3): owned rows; drag_reaction (n_total,3): every row, ghosts' rows go back to their owners)."""
-        n, dev = self.n_total, self.device
-        onto = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-        react = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        onto, react = self._new(self.n_total, 3, zero=True), self._new(self.n_total, 3, zero=True)
         self._keep_drag = (m, ptype, mgm, mcs)
         self._chk(self.lib.sphx_dev_drag(self.ctx.h, self._p(m), self._p(ptype), self._p(mgm), self._p(mcs), self._p(onto),
                                          self._p(react)))
@@ -500,13 +629,9 @@ class LibBackend:
 
     def species(self, fun, m):
         """-> (F (S,n_total), Z (n_total,) | None, agb_dust (n_total,S) | None); owned entries are meaningful."""
-        n, dev = self.n_total, self.device
-        S = int(fun.shape[1])
-        F = torch.zeros((S, n), dtype=torch.float64, device=dev)
-        Z = A = None
-        if getattr(self, "has_agb", False):
-            Z = torch.zeros(n, dtype=torch.float64, device=dev)
-            A = torch.zeros((n, S), dtype=torch.float64, device=dev)
+        n, S = self.n_total, int(fun.shape[1])
+        F = self._new(S, n, zero=True)
+        Z, A = (self._new(n, zero=True), self._new(n, S, zero=True)) if getattr(self, "has_agb", False) else (None, None)
         fun = fun.contiguous()
         self._chk(self.lib.sphx_dev_species(self.ctx.h, S, self._p(fun), self._p(m), self._p(F), self._p(Z), self._p(A)))
         return F, Z, A
@@ -517,11 +642,8 @@ class LibBackend:
         self._chk(self.lib.sphx_dev_loop_prep(self.ctx.h, *[self._p(t) for t in self._keep], float(d)))
 
     def loop_pass1(self, h_complete):
-        n, dev = self.n_total, self.device
-        rho = torch.empty(n, dtype=torch.float64, device=dev)
-        rhod = torch.empty(n, dtype=torch.float64, device=dev)
-        nden = torch.empty(n, dtype=torch.float64, device=dev)
-        delp = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        n = self.n_total
+        rho, rhod, nden, delp = self._new(n), self._new(n), self._new(n), self._new(n, 3)
         self._chk(self.lib.sphx_dev_loop_pass1(self.ctx.h, self._p(h_complete), self._p(rho), self._p(rhod), self._p(nden),
                                                self._p(delp)))
         return rho, rhod, nden, delp
@@ -541,10 +663,7 @@ class LibBackend:
         return [int(v) for v in out]
 
     def loop_pass2(self, rho_complete):
-        n, dev = self.n_total, self.device
-        va = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        vh = torch.empty(n, dtype=torch.float64, device=dev)
-        ct = torch.zeros(1, dtype=torch.float64, device=dev)
+        va, vh, ct = self._new(self.n_total, 3), self._new(self.n_total), self._new(1, zero=True)
         self._chk(self.lib.sphx_dev_loop_pass2(self.ctx.h, self._p(rho_complete), self._p(va), self._p(vh), self._p(ct)))
         return va, vh, ct
 
@@ -552,34 +671,27 @@ class LibBackend:
                        first=False, fixed_dt=0.0):
         """drv:460-491 on the loop forms' outputs; red2 given: verdict and dt on the device -> dt as a (1,) tensor."""
         dt_t = torch.empty(1, dtype=torch.float64, device=self.device) if red2 is not None else None
-        self._chk(self.lib.sphx_dev_integrate_loop(self.ctx.h, n_owned, self._p(pos), self._p(vel), self._p(acc),
-                                                   self._p(E), self._p(T), self._p(m), self._p(mu), self._p(gam),
-                                                   self._p(ptype), self._p(delp), self._p(rho), self._p(va), self._p(vh),
-                                                   self._p(red2), 1 if first else 0, float(fixed_dt), float(dt),
+        ptrs = [self._p(t) for t in (pos, vel, acc, E, T, m, mu, gam, ptype, delp, rho, va, vh, red2)]
+        self._chk(self.lib.sphx_dev_integrate_loop(self.ctx.h, n_owned, *ptrs, 1 if first else 0, float(fixed_dt), float(dt),
                                                    self._p(dt_t)))
         return dt_t
 
     def integrate(self, n_owned, pos, vel, acc, E, T, m, mu, gam, ptype, ha, va, vh, dt):
-        self._chk(self.lib.sphx_dev_integrate(self.ctx.h, n_owned, self._p(pos), self._p(vel), self._p(acc),
-                                              self._p(E), self._p(T), self._p(m), self._p(mu), self._p(gam),
-                                              self._p(ptype), self._p(ha), self._p(va), self._p(vh), float(dt)))
+        ptrs = [self._p(t) for t in (pos, vel, acc, E, T, m, mu, gam, ptype, ha, va, vh)]
+        self._chk(self.lib.sphx_dev_integrate(self.ctx.h, n_owned, *ptrs, float(dt)))
 
 
 # ==============================================================================================
 # the decomposed step loop
 # ==============================================================================================
-GHOST_FIELDS = ("vel", "m", "T", "mu", "gam", "ptype", "h")      # + pos; sent in halo phase 1
-OWNED_FIELDS = ("pos", "vel", "acc", "m", "T", "mu", "gam", "ptype", "E", "h", "gid")
-
-
 class DistributedSim:
     """Owned particles of one rank + the per-step halo protocol.  `state` holds this rank's
     owned particles (reference array conventions, sph/code_running.py:114-177) plus 'gid'
-    (global particle ids); `lo`/`hi` are the (world,3) region boxes of rcb_regions."""
+    (global particle ids); `lo`/`hi` are the (world,3) region boxes of rcb_regions.  `backend`: a TensorBackend with the
+    physics; what it may have beyond that is looked up once, in __init__ (has_auto_update, has_select_blobs, ...)."""
 
     phase = "setup"                              # the section of step() this process is in (class-wide: one sim per process)
-    DT_0 = 60. * 60. * 24. * 365. * 250000.      # nsc:38
-    MAX_AGE = 3e7 * 60. * 60. * 24. * 365.       # drv:79
+    DT_0, MAX_AGE = DT_0, MAX_AGE
 
     def __init__(self, state, lo, hi, backend, rank=0, world=1, device="cpu", comm_device=None,
                  halo_scale=1.15, skin_frac=0.15, need_grid=96, migrate_every=4, forms="hydro_update", d=None,
@@ -610,11 +722,6 @@ class DistributedSim:
                 raise ValueError("gravity_softening must be >= 0")
             if hasattr(backend, "set_gravity_order"):
                 backend.set_gravity_order(int(gravity_order))
-        self.gravity, self.grav_G = gravity, float(G)
-        self.gravity_ws, self.gravity_order = int(gravity_ws), int(gravity_order)
-        self.gravity_softening = None if gravity_softening is None else float(gravity_softening)
-        self._gcap = [0, 0]                         # capacity of the export buffers (cell records, particle records)
-        self.grav_ref = None                        # the point the cells' centres travel relative to (set below)
         from .compat import visc_mode_code
         be_mode = getattr(backend, "visc_mode", None)
         if visc_mode is None:
@@ -625,9 +732,14 @@ class DistributedSim:
             raise ValueError("visc_mode=%r but the backend was made with visc_mode=%r" % (visc_mode, be_mode))
         if visc_mode == "pairwise" and not hasattr(backend, "visc_pairwise"):
             raise ValueError("visc_mode='pairwise' needs a backend with visc_pairwise (LibBackend)")
-        self.visc_mode = visc_mode
         if forms == "loop" and not (d is not None and d > 0):
             raise ValueError("forms='loop' needs the driver's global d (code_running.py:67-68)")
+        self.visc_mode = visc_mode
+        self.gravity, self.grav_G = gravity, float(G)
+        self.gravity_ws, self.gravity_order = int(gravity_ws), int(gravity_order)
+        self.gravity_softening = None if gravity_softening is None else float(gravity_softening)
+        self._gcap = [0, 0]                         # capacity of the export buffers (cell records, particle records)
+        self.grav_ref = None                        # the point the cells' centres travel relative to (set below)
         self.forms, self.d = forms, (float(d) if d is not None else None)
         # with_drag: the dust -> gas drag of nsc.net_impulse in the step (drv:455,462-463,473): ghosts carry their mean
         # grain mass / cross-section, and the reaction scatter-added onto ghost neighbours travels back to their owners
@@ -638,10 +750,54 @@ class DistributedSim:
         if (self.with_species or (self.with_drag and not drag_given)) and state.get("f_un") is None:
             raise ValueError("with_drag / with_species need a state with f_un")
         self.rank, self.world, self.backend = rank, world, backend
+        if not isinstance(backend, TensorBackend):       # a backend of its own making gets the base form of every helper it lacks
+            for name, form in vars(TensorBackend).items():
+                if not name.startswith("__") and not hasattr(backend, name):
+                    setattr(backend, name, form.__get__(backend) if callable(form) else form)
+        # what the backend may have beyond the contract and the physics.  The update launched before the host reads the step's
+        # scalars, verdict and dt taken on the device (integrate_auto, integrate_loop(red2=...)); with it plans are made ahead
+        self.has_auto_update = hasattr(backend, "integrate_auto")
+        # a pass run once for the interior and once for the boundary blobs, around a halo phase
+        self.has_select_blobs = hasattr(backend, "select_blobs")                # (hydro_update's passes)
+        self.has_pass2_interior = hasattr(backend, "loop_pass2_interior")      # (pass 2 of the loop forms)
         self.device = torch.device(device)
         self.comm_device = torch.device(comm_device) if comm_device is not None else self.device
         self.ex = Exchanger(rank, world, self.comm_device)
         self.ex.warm_up()
+        self._load_state(state, drag_given)
+        if self.with_species and agb is not None and hasattr(backend, "set_agb"):
+            from . import compat
+            backend.set_agb(int(self.s["fun"].shape[1]), agb, compat.mu_specie, compat.solar_mass)
+        self.lo = torch.as_tensor(lo, dtype=torch.float64).to(self.device)
+        self.hi = torch.as_tensor(hi, dtype=torch.float64).to(self.device)
+        self.halo_scale = halo_scale
+        self.skin_frac = skin_frac          # plan is reused while displacements stay below skin/2
+        self.w_plan = self.send_idx = self.recv_counts = self.send_cat = self.pos_plan = None
+        # strays are handed to their region's owner (and the owned arrays re-sorted) on every
+        # `migrate_every`-th replan: ownership is bookkeeping, the halo is built from where the owned
+        # particles ARE, so a particle a little outside its region's box costs nothing but reach
+        self.migrate_every = max(1, int(migrate_every))
+        # when the plan went stale on three steps running (large dt: some particle always moves more
+        # than the skin), the next steps replan without asking - two host-synchronising reductions less
+        self.stale_streak, self.force_replan = 0, 0
+        self._nonzero_static = None       # torch.nonzero_static usable on this device? (found out at the first plan)
+        # how much of |v_i| dt a particle adds to the reach it claims (1: a radius may grow by the particle's own displacement
+        # per step; every plan is verified after the search and redone if too thin, so this only trades ghosts for redos)
+        self.reach_vfac = float(os.environ.get("SPHX_REACH_VFAC", "1.0"))
+        # head-room of a claim limited to this many MEAN radii (0: not): the rim of an expanding cloud (radii tens of times
+        # the mean, growing by a fraction of a per cent per step) otherwise claims 30 % of its own radius into the dense core
+        self.reach_cap = float(os.environ.get("SPHX_REACH_CAP", "1.0"))
+        self.cap_abs = 0.0                # the cap as a length: set when particles migrate (the same for every plan in between)
+        self.overlap = os.environ.get("SPHX_MG_OVERLAP", "1") != "0"      # interior blobs' sums under the scalar halo phases
+        self.plan_next = None             # the NEXT step's plan, made at the end of this one (see step)
+        self.plan_ahead = True
+        self._make_need_grid(need_grid)
+        self.hmax_prev, self.hmean_prev, self.dt_last = 0.0, 0.0, 0.0
+        self.first, self.last, self.last_ntotal = True, {}, None
+        self.stats, self.host_ms = dict(steps=0, ghosts=0, redo=0, migrated=0), {}
+
+    def _load_state(self, state, drag_given):
+        """self.s: the owned particles' arrays on the device; self.extra_fields: those beyond the core set."""
         f = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(self.device)
         self.s = dict(pos=f(state["points"]), vel=f(state["velocities"]), m=f(state["mass"]), T=f(state["T"]),
                       mu=f(state["mu_array"]), gam=f(state["gamma_array"]), ptype=f(state["particle_type"]),
@@ -664,35 +820,10 @@ class DistributedSim:
         if self.with_species:
             self.s["fun"] = f(state["f_un"])
             self.extra_fields += ["fun"]
-            if agb is not None and hasattr(backend, "set_agb"):
-                from . import compat
-                backend.set_agb(int(self.s["fun"].shape[1]), agb, compat.mu_specie, compat.solar_mass)
-        self.lo = torch.as_tensor(lo, dtype=torch.float64).to(self.device)
-        self.hi = torch.as_tensor(hi, dtype=torch.float64).to(self.device)
-        self.halo_scale = halo_scale
-        self.skin_frac = skin_frac          # plan is reused while displacements stay below skin/2
-        self.w_plan, self.send_idx, self.recv_counts, self.pos_plan = None, None, None, None
-        self.send_cat = None
-        self.grow = 1.0
-        # strays are handed to their region's owner (and the owned arrays re-sorted) on every
-        # `migrate_every`-th replan: ownership is bookkeeping, the halo is built from where the owned
-        # particles ARE, so a particle a little outside its region's box costs nothing but reach
-        self.migrate_every = max(1, int(migrate_every))
-        # when the plan went stale on three steps running (large dt: some particle always moves more
-        # than the skin), the next steps replan without asking - two host-synchronising reductions less
-        self.stale_streak, self.force_replan = 0, 0
-        self._nonzero_static = None       # torch.nonzero_static usable on this device? (found out at the first plan)
-        # how much of |v_i| dt a particle adds to the reach it claims (1: a radius may grow by the particle's own displacement
-        # per step; every plan is verified after the search and redone if too thin, so this only trades ghosts for redos)
-        self.reach_vfac = float(os.environ.get("SPHX_REACH_VFAC", "1.0"))
-        # head-room of a claim limited to this many MEAN radii (0: not): the rim of an expanding cloud (radii tens of times
-        # the mean, growing by a fraction of a per cent per step) otherwise claims 30 % of its own radius into the dense core
-        self.reach_cap = float(os.environ.get("SPHX_REACH_CAP", "1.0"))
-        self.cap_abs = 0.0                # the cap as a length: set when particles migrate (the same for every plan in between)
-        self.overlap = os.environ.get("SPHX_MG_OVERLAP", "1") != "0"      # interior blobs' sums under the scalar halo phases
-        self.plan_next = None             # the NEXT step's plan, made at the end of this one (see step)
-        self.plan_ahead = True
-        # coarse global grid for the need maps: global bounding box of the initial state + 25 %
+
+    def _make_need_grid(self, need_grid):
+        """The coarse global grid of the need maps: the initial state's global bounding box + 25 % (and gravity's reference point)."""
+        n, world = self.n_owned, self.world
         pmin = self.s["pos"].min(dim=0).values if n else torch.full((3,), 1e300, dtype=torch.float64, device=self.device)
         pmax = self.s["pos"].max(dim=0).values if n else torch.full((3,), -1e300, dtype=torch.float64, device=self.device)
         if world > 1:
@@ -704,16 +835,8 @@ class DistributedSim:
         # restart takes it from the snapshot); it only has to lie within a few cloud sizes of the cloud
         self.grav_ref = [float(v) for v in (pmin + 0.5 * (pmax - pmin)).tolist()] if n or world > 1 else [0.0, 0.0, 0.0]
         self.G = int(need_grid)
-        self.g_lo = pmin - 0.25 * ext
+        self.g_lo_host = [float(v) for v in (pmin - 0.25 * ext).tolist()]
         self.g_cs = float((1.5 * ext).max()) / self.G             # cubic coarse cells
-        self.g_lo_host = [float(v) for v in self.g_lo.tolist()]
-        self.hmax_prev, self.hmean_prev = 0.0, 0.0
-        self.last_ntotal = None
-        self.first = True
-        self.dt_last = 0.0
-        self.last = {}
-        self.stats = dict(steps=0, ghosts=0, redo=0, migrated=0)
-        self.host_ms = {}
 
     GRAVITY_BACKEND = ("gravity_build", "gravity_local", "gravity_export", "gravity_remote", "set_gravity_accel")
 
@@ -741,21 +864,6 @@ class DistributedSim:
     def n_owned(self):
         return self.s["pos"].shape[0]
 
-    def _allgather_scalar(self, v):
-        if self.world == 1:
-            return [float(v)]
-        t = torch.tensor([float(v)], dtype=torch.float64, device=self.comm_device)
-        out = [torch.zeros_like(t) for _ in range(self.world)]
-        dist.all_gather(out, t)
-        return [float(o[0]) for o in out]
-
-    def _allreduce_min(self, v):
-        if self.world == 1:
-            return float(v)
-        t = torch.tensor([float(v)], dtype=torch.float64, device=self.comm_device)
-        dist.all_reduce(t, op=dist.ReduceOp.MIN)
-        return float(t[0])
-
     def _allreduce_max(self, v):
         if self.world == 1:
             return float(v)
@@ -763,70 +871,15 @@ class DistributedSim:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t[0])
 
-    def _coarse_cell(self, pos):
-        c = torch.floor((pos - self.g_lo[None]) / self.g_cs).to(torch.int64).clamp_(0, self.G - 1)
-        return (c[:, 2] * self.G + c[:, 1]) * self.G + c[:, 0]
-
-    def _need_map(self, w_owned):
-        """uint8 (G^3,): coarse cells from which a particle could lie within w_i of one of my owned particles.  A cell
-        d = (dx, dy, dz) cells away from an owned particle's cell is marked when sum_a max(|d_a| - 1, 0)^2 <= (w_i / cell)^2:
-        a sphere of cells (distances under-estimated by one cell per axis), not the cube around it - the wide claims of
-        rim particles would otherwise pull in the dense cloud at the cube's corners."""
-        G, cs = self.G, self.g_cs
-        # (a NaN reach - a broken radius - claims everything, in both forms: as a NaN it would drop out of the kernel's
-        #  comparisons and, in the form below, swallow its cell's genuine claims in the running maximum)
-        if hasattr(self.backend, "need_map"):          # fused: one launch, no host synchronisation
-            return self.backend.need_map(self.s["pos"], w_owned, self.g_lo_host, cs, G)
-        # the tensor-library form (the specification: what the CPU tests run, what the kernel is tested against).  The
-        # rule is monotone in w, so a cell's widest claim stands for all its particles; cells are handled per integer
-        # radius class, each against its stencil of offsets.
-        dev = self.device
-        out = torch.zeros(G * G * G, dtype=torch.uint8, device=dev)
-        if not w_owned.numel():
-            return out
-        w_owned = torch.nan_to_num(w_owned, nan=float("inf"), posinf=float("inf"), neginf=0.0)
-        wmax = torch.zeros(G * G * G, dtype=torch.float64, device=dev)
-        wmax.scatter_reduce_(0, self._coarse_cell(self.s["pos"]), w_owned, reduce="amax", include_self=True)
-        occ = torch.nonzero(wmax > 0).flatten()
-        if not occ.numel():
-            return out
-        q = wmax[occ] / cs
-        r = torch.clamp(torch.floor(q) + 1.0, max=float(G)).to(torch.int64)
-        q2 = q * q
-        cz, cy, cx = occ // (G * G), (occ // G) % G, occ % G
-        for rv in torch.unique(r).tolist():
-            sel = torch.nonzero(r == rv).flatten()
-            lo_r = max(-rv, -(G - 1)); hi_r = min(rv, G - 1)
-            o1 = torch.arange(lo_r, hi_r + 1, device=dev, dtype=torch.int64)
-            a1 = torch.clamp(o1.abs() - 1, min=0)
-            # stencil of this radius class: offsets and their under-estimated squared distance in cells
-            dz, dy, dx = torch.meshgrid(o1, o1, o1, indexing="ij")
-            s2 = (a1 * a1)[:, None, None] + (a1 * a1)[None, :, None] + (a1 * a1)[None, None, :]
-            dz, dy, dx, s2 = dz.reshape(-1), dy.reshape(-1), dx.reshape(-1), s2.reshape(-1).to(torch.float64)
-            chunk = max(1, int(4_000_000 // max(int(s2.numel()), 1)))
-            for c0 in range(0, int(sel.numel()), chunk):
-                ss = sel[c0:c0 + chunk]
-                hit = s2[None, :] <= q2[ss][:, None]                                  # (cells, offsets)
-                z = cz[ss][:, None] + dz[None, :]; y = cy[ss][:, None] + dy[None, :]; x = cx[ss][:, None] + dx[None, :]
-                hit &= (z >= 0) & (z < G) & (y >= 0) & (y < G) & (x >= 0) & (x < G)
-                out[((z * G + y) * G + x)[hit]] = 1
-        return out
-
     def _plan_launch(self, w_owned):
         """Device work and collectives of a plan (one all_gather of G^3 bytes per rank, one of W counts): -> (mask (W, n),
         both (2, W) int64 on the communication device: what I send to / receive from every peer).  No host read."""
-        W = self.world
-        mine = self._need_map(w_owned).to(self.comm_device)
+        W, grid = self.world, (self.g_lo_host, self.g_cs, self.G)
+        mine = self.backend.need_map(self.s["pos"], w_owned, *grid).to(self.comm_device)
         maps = [torch.zeros_like(mine) for _ in range(W)]
         dist.all_gather(maps, mine)
         maps = torch.stack(maps).to(self.device)                              # (W, G^3)
-        if hasattr(self.backend, "plan_mask"):
-            mask, cnt = self.backend.plan_mask(self.s["pos"], self.g_lo_host, self.g_cs, self.G, maps, self.rank)
-        else:
-            cell = self._coarse_cell(self.s["pos"])
-            mask = maps[:, cell] != 0                                         # (W, n)
-            mask[self.rank] = False
-            cnt = mask.sum(dim=1)
+        mask, cnt = self.backend.plan_mask(self.s["pos"], *grid, maps, self.rank)
         # counts to every peer, exchanged while still on the device: ONE host read (the caller's) serves both the
         # send lists and what the peers will send (each read drains the stream)
         cnt = cnt.to(self.comm_device)                                        # (W,) int64
@@ -835,7 +888,7 @@ class DistributedSim:
         return mask, torch.stack([cnt, torch.stack(allc)[:, self.rank]])
 
     def _plan_finish(self, mask, both):
-        """Send lists from the mask, now that the host knows the counts (`both` as nested lists)."""
+        """Send lists from the mask, now that the host knows the counts (`both` as nested lists) -> (send_idx, recv_counts, send_cat)."""
         counts, recv_counts = [int(v) for v in both[0]], [int(v) for v in both[1]]
         total = sum(counts)
         pk = None
@@ -853,44 +906,12 @@ class DistributedSim:
         for p in range(self.world):
             send_idx.append(None if p == self.rank else pk[o:o + counts[p], 1].contiguous())
             o += counts[p]
-        return send_idx, recv_counts
+        return send_idx, recv_counts, self._cat_lists(send_idx)
 
-    def _plan(self, w_owned):
-        """Send lists from the ranks' need maps."""
-        mask, both = self._plan_launch(w_owned)
-        return self._plan_finish(mask, both.tolist())
-
-    # rows <-> separate arrays.  Backends with fused kernels (LibBackend) do each in one launch; the
-    # tensor-library forms below are the specification (and what the CPU tests run).
-    @staticmethod
-    def _as_f64(t):
-        return t.view(torch.float64) if t.dtype == torch.int64 else t        # ids travel as raw 8-byte words
-
-    def _pack(self, idx, fields):
-        """(len(idx), W) rows of the particles idx (None: all) from the given (n,) / (n,w) fields."""
-        fields = [self._as_f64(f) for f in fields]
-        if hasattr(self.backend, "pack_rows"):
-            return self.backend.pack_rows(idx, fields)
-        rows = torch.cat([f if f.dim() == 2 else f[:, None] for f in fields], dim=1)
-        return rows if idx is None else rows[idx]
-
-    def _regroup(self, sel, n_sel, rows, fields):
-        """fields[sel] (None: the first n_sel as they are) followed by the particles in rows."""
-        dts = [f.dtype for f in fields]
-        f64 = [self._as_f64(f) for f in fields]
-        if hasattr(self.backend, "regroup"):
-            outs = self.backend.regroup(sel, n_sel, rows, f64)
-        else:
-            outs, c = [], 0
-            for f in f64:
-                w = 1 if f.dim() == 1 else f.shape[1]
-                own = f[:n_sel] if sel is None else f[sel]
-                if rows is not None and rows.shape[0]:
-                    g = rows[:, c] if f.dim() == 1 else rows[:, c:c + w]
-                    own = torch.cat([own, g], dim=0)
-                outs.append(own.contiguous())
-                c += w
-        return [o.view(torch.int64) if d == torch.int64 else o for o, d in zip(outs, dts)]
+    def _cat_lists(self, send_idx):
+        """The peers' send lists in one (what pack_rows gathers by)."""
+        parts = [ix for ix in send_idx if ix is not None and ix.numel()]
+        return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=self.device)
 
     def _exchange(self, send_idx, recv_counts, fields, into=None, send_cat=None, defer=False):
         """Rows of `fields` for every peer's send list -> the received rows (n_recv, W), ordered by
@@ -903,9 +924,8 @@ class DistributedSim:
             res1 = into if into is not None else torch.zeros((0, W), dtype=torch.float64, device=dev)
             return (lambda: res1) if defer else res1
         if send_cat is None:
-            parts = [ix for ix in send_idx if ix is not None and ix.numel()]
-            send_cat = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=dev)
-        rows = self._pack(send_cat, fields)
+            send_cat = self._cat_lists(send_idx)
+        rows = self.backend.pack_rows(send_cat, fields)
         bufs, o = [], 0
         for ix in send_idx:
             c = 0 if ix is None else int(ix.numel())
@@ -936,33 +956,18 @@ class DistributedSim:
 
     def _replan(self):
         """Migrate strays to their region's owner, then rebuild the send lists: every owned particle
-        claims the radius w_i = (halo_scale + skin_frac) * grow * h_i around itself."""
+        claims the reach w_i (the backend's reach) around itself."""
         if self._migration_due():
             self._reorder_and_migrate()
             self.cap_abs = self.reach_cap * self.hmean_prev if self.hmean_prev > 0.0 else 0.0
-            if hasattr(self.backend, "set_reach_cap"):
-                self.backend.set_reach_cap(self.cap_abs)
+            self.backend.set_reach_cap(self.cap_abs)
         s = self.s
-        # reach claimed by each owned particle: its kNN radius with head-room for one step of growth
-        # (a radius changes by at most twice the local displacement, so fast movers claim more)
-        if hasattr(self.backend, "reach") and self.n_owned:
-            self.w_plan = self.backend.reach(s["h"], s["vel"], self.halo_scale, self.skin_frac, self.dt_last * self.reach_vfac)
-        else:
-            speed = torch.sqrt((s["vel"] * s["vel"]).sum(dim=1))
-            dtv = self.dt_last * self.reach_vfac
-            if self.cap_abs > 0.0:
-                cap = torch.full_like(s["h"], self.cap_abs)
-                a = torch.minimum((self.halo_scale + self.skin_frac - 1.0) * s["h"], cap)
-                b = torch.minimum((self.halo_scale - 1.0) * s["h"], cap)
-                self.w_plan = torch.maximum(s["h"] + a, (s["h"] + b) + speed * dtv)
-            else:
-                self.w_plan = torch.maximum((self.halo_scale + self.skin_frac) * s["h"], self.halo_scale * s["h"] + speed * dtv)
+        self.w_plan = self.backend.reach(s["h"], s["vel"], self.halo_scale, self.skin_frac, self.dt_last * self.reach_vfac)
         if self.world > 1:
-            self.send_idx, self.recv_counts = self._plan(self.w_plan)
+            mask, both = self._plan_launch(self.w_plan)
+            self.send_idx, self.recv_counts, self.send_cat = self._plan_finish(mask, both.tolist())
         else:
-            self.send_idx, self.recv_counts = [None], [0]
-        parts = [ix for ix in self.send_idx if ix is not None and ix.numel()]
-        self.send_cat = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=self.device)
+            self.send_idx, self.recv_counts, self.send_cat = [None], [0], self._cat_lists([None])
         # (positions at plan time: only read by the staleness check, which forced replanning skips)
         self.pos_plan = s["pos"].clone() if self.force_replan <= 0 else None
         self.stats["replans"] = self.stats.get("replans", 0) + 1
@@ -971,10 +976,10 @@ class DistributedSim:
         """Owned particles in the cell order of the last search (when the backend exposes it), or None.
         Keeping the owned arrays in that order makes the library's gathers / scatters between caller
         order and cell order nearly sequential, as in the fused single-GPU loop."""
-        if self.last_ntotal is None or not hasattr(self.backend, "order"):
+        order = None if self.last_ntotal is None else self.backend.order(self.last_ntotal)
+        if order is None:
             return None
         no = self.n_owned
-        order = self.backend.order(self.last_ntotal)
         order = order[order < no]
         self.last_ntotal = None
         return order if order.numel() == no else None
@@ -996,15 +1001,16 @@ class DistributedSim:
             if got[p] is not None and back[p]:
                 owned_acc.index_add_(0, send_idx[p], got[p].to(owned_acc.device))
 
-    def _step_extras(self, be, no, ng, send_idx, recv_counts, m, ptype, extra, rho, rhod):
+    def _step_extras(self, a, rhod):
         """Drag (nsc:719-742; the completed terms are handed to the coming update) and the species pass (nsc:624-627)."""
+        be, no = self.backend, a.no
         if self.with_drag:
-            onto, react = be.drag(m, ptype, extra["mgm"], extra["mcs"])
+            onto, react = be.drag(a.m, a.ptype, a.extra["mgm"], a.extra["mcs"])
             own = react[:no].clone()
-            self._reverse_add(send_idx, recv_counts, react[no:].contiguous(), own)
-            be.set_drag_terms(onto[:no], own, rho[:no], rhod[:no])
+            self._reverse_add(a.send_idx, a.recv_counts, react[no:].contiguous(), own)
+            be.set_drag_terms(onto[:no], own, a.rho[:no], rhod[:no])
         if self.with_species:
-            F, Z, A = be.species(extra["fun"], m)
+            F, Z, A = be.species(a.extra["fun"], a.m)
             self.last_species = dict(f_un_neighbor=F[:, :no], metallicity=None if Z is None else Z[:no],
                                      agb_dust=None if A is None else A[:no])
 
@@ -1074,8 +1080,11 @@ class DistributedSim:
         be.gravity_remote(pos[:no], got[0], got[1], self.grav_G, eps, grav)
         return grav
 
+    # ---- the step, phase by phase.  What one attempt works on and finds travels in one record `a`: D, no, ng, the lists; the
+    # complete (owned + ghost) arrays pos .. ptype, hint, E, extra; h, grav; the sums' rho, nden, ha | delp, va, vh, ct; red, loc, vals
     def step(self, fixed_dt=0.0):
-        """One decomposed pass of the hot path.
+        """One decomposed pass of the hot path: a plan (_ensure_plan), then attempts - the ghosts' state, the search, gravity,
+        the sums, ONE reduction of the step's scalars - until the halo proved thick enough, and the update.
 
         Halo validity.  When the plan was made every foreign particle within w_i of owned particle
         i became a ghost.  With D the largest displacement of ANY particle since, a foreign
@@ -1083,19 +1092,72 @@ class DistributedSim:
         owned or ghosts as long as  h_i + 2D <= w_i.  That is checked for every owned particle after
         every search; if it fails anywhere all ranks replan (with a larger factor) and redo the
         search.  A plan is reused as long as halo_scale*h_i + 2D <= w_i holds everywhere."""
-        s, be = self.s, self.backend
-        be.clamp(s["pos"], s["vel"])                                        # drv:233-238
-        no = self.n_owned
-        bootstrap = self.first or self.w_plan is None or self.hmax_prev <= 0.0
-        if bootstrap:
-            # a search without ghosts over-estimates every h (fewer candidates): a rigorous radius
-            # for the first exchange
-            if no:
-                s["h"] = be.search(s["pos"], no, None, 0.0)[:no].contiguous()
+        be = self.backend
+        be.clamp(self.s["pos"], self.s["vel"])                              # drv:233-238
+        D = self._ensure_plan()
+        while True:
+            a = self._halo_state(D)
+            with self._sec("search"):
+                a.h = be.search(a.pos, a.no, a.hint, self.hmean_prev)
+            if self.gravity is not None:
+                # after the search (its grid carries the pyramid), before the update: the update is launched
+                # before the host knows the verdict
+                with self._sec("gravity"):
+                    a.grav = self._gravity(be, a.pos, a.m, a.h, a.no)
+            # the sums are run on the assumption that the halo was sufficient, which it nearly always is
+            with self._sec("sums+halo_scalars"):
+                if self.forms == "loop":
+                    self._sums_loop(a)
+                else:
+                    self._sums_hydro(a)
+            a.t_dt = time.perf_counter()
+            self._step_scalars(a)
+            # (a rank without particles has nothing to update: it reads the scalars like a backend without the call)
+            a.auto = self.has_auto_update and a.no > 0
+            if a.auto:
+                self._launch_update(a, fixed_dt)
+            else:
+                self._read_scalars(a)
+            if a.vals[0] < 0.5:
+                break
+            # the halo was too thin somewhere: those particles claim their new radius (x1.5), everybody
+            # replans and the step's search and sums are redone
+            if a.no:
+                fail = a.h[:a.no] + 2.0 * D > self.w_plan
+                self.s["h"] = torch.where(fail, 1.5 * (a.h[:a.no] + 2.0 * D), self.s["h"])
+            # (a migration inside the redo sorts by THIS attempt's search: the state has not moved since)
+            self.last_ntotal = int(a.pos.shape[0])
             with self._sec("replan"):
                 self._replan()
             D = 0.0
-        elif self.force_replan > 0 or self.pos_plan is None:
+            self.stats["redo"] += 1
+        ct_min, self.hmax_prev, self.hmean_prev = -a.vals[1], a.vals[2], a.vals[3]
+        self.plan_next = None
+        if a.ahead is not None:                   # the plan made ahead is the next step's, now that the host knows its counts
+            with self._sec("plan_ahead"):
+                self.plan_next = (a.ahead[0],) + self._plan_finish(a.ahead[1], a.both_host)
+        dt = a.vals[4] if a.auto else self._finish_update(a, ct_min, fixed_dt)      # (auto: worked out and applied on the device)
+        self.host_ms["dt+integrate"] = self.host_ms.get("dt+integrate", 0.0) + (time.perf_counter() - a.t_dt) * 1e3
+        self.s["h"] = a.h[:a.no].contiguous()
+        self.last = dict(rho=a.rho[:a.no], nden=a.nden[:a.no], visc_heat=a.vh[:a.no])
+        self.dt_last = dt
+        self.last_ntotal = int(a.pos.shape[0])
+        self.first = False
+        self.stats["steps"] += 1
+        self.stats["ghosts"] += a.ng
+
+    def _ensure_plan(self):
+        """A plan this step can start with -> D, the bound on any particle's displacement since it was made (0: made now)."""
+        s, no = self.s, self.n_owned
+        if self.first or self.w_plan is None or self.hmax_prev <= 0.0:
+            # bootstrap.  A search without ghosts over-estimates every h (fewer candidates): a rigorous radius
+            # for the first exchange
+            if no:
+                s["h"] = self.backend.search(s["pos"], no, None, 0.0)[:no].contiguous()
+            with self._sec("replan"):
+                self._replan()
+            return 0.0
+        if self.force_replan > 0 or self.pos_plan is None:
             # forced, or the last plan kept no positions to measure the displacement against: a plan
             # made now is exact (D = 0); never compare against positions the plan was not made at
             self.force_replan = max(self.force_replan - 1, 0)
@@ -1109,246 +1171,183 @@ class DistributedSim:
                 else:
                     self._replan()
             self.plan_next = None
-            D = 0.0
+            return 0.0
+        with self._sec("stale_check"):
+            d_loc = float((s["pos"] - self.pos_plan).abs().max()) * 1.7320508075688772 if no else 0.0
+            D = self._allreduce_max(d_loc)                    # bound on the displacement norm
+            hr = (self.halo_scale - 1.0) * s["h"]              # (the head-room a plan is expected to keep)
+            if self.cap_abs > 0.0:
+                hr = torch.clamp(hr, max=self.cap_abs)
+            stale = float((s["h"] + hr + 2.0 * D > self.w_plan).any()) if no else 0.0
+            is_stale = self._allreduce_max(stale) > 0.5       # (the same verdict on every rank)
+        if not is_stale:
+            self.stale_streak = 0
+            return D
+        with self._sec("replan"):
+            self._replan()
+        self.stale_streak += 1
+        if self.stale_streak >= 3:
+            self.stale_streak, self.force_replan = 0, 16
+        return 0.0
+
+    def _halo_state(self, D):
+        """Halo phase 1: the ghosts' state (88 B + previous h) behind the owned particles' -> the attempt's record."""
+        s, loop = self.s, self.forms == "loop"
+        a = SimpleNamespace(D=D, no=self.n_owned, send_idx=self.send_idx, recv_counts=self.recv_counts,
+                            ng=sum(self.recv_counts), grav=None, ha=None, delp=None, ahead=None, both_host=None)
+        keys = ["pos", "vel", "m", "T", "mu", "gam", "ptype", "h"]
+        if loop:
+            keys.append("E")                          # del_pressure reads the neighbour's E (nsc:755)
+        keys += list(self.extra_fields)               # drag coefficients / composition rows of the ghosts
+        fields = [s[k_] for k_ in keys]
+        with self._sec("halo_state"):
+            g = self._exchange(a.send_idx, a.recv_counts, fields, send_cat=self.send_cat)
+            if all(f.dtype == torch.float64 for f in fields):
+                # LibBackend: the ghosts go behind the owned particles in the owned arrays' own storage, nothing else is copied
+                complete, owned = self.backend.append_rows(a.no, g, fields)
+                for k_, v in zip(keys, owned):
+                    s[k_] = v
+            else:
+                complete = self.backend.regroup(None, a.no, g, fields)
+            a.pos, a.vel, a.m, a.T, a.mu, a.gam, a.ptype, a.hint = complete[:8]
+            a.E = complete[8] if loop else None
+            a.extra = dict(zip(self.extra_fields, complete[(9 if loop else 8):]))
+        return a
+
+    def _halo_scalar(self, a, arr, defer=False):
+        """Halo phases 2-4, 8 B per ghost: received straight into the tail of the (n_total,) array the backend just filled."""
+        tail = arr[a.no:].view(a.ng, 1)
+        return self._exchange(a.send_idx, a.recv_counts, [arr[:a.no]], into=tail, send_cat=self.send_cat, defer=defer)
+
+    def _sums_loop(self, a):
+        """The loop forms (drv:451-458): h_j, records, pass 1, rho_j, pass 2 (+ drag and species)."""
+        be = self.backend
+        # h_j (nsc:711) travels while the step's records are built (they do not read h)
+        h_done = self._halo_scalar(a, a.h, defer=True)
+        be.loop_prep(a.pos, a.vel, a.m, a.T, a.mu, a.gam, a.ptype, a.E, self.d)
+        h_done()
+        a.rho, rhod, a.nden, a.delp = be.loop_pass1(a.h)
+        # rho_j (nsc:803) travels while pass 2 runs for the blobs without ghost neighbours
+        rho_done = self._halo_scalar(a, a.rho, defer=True)
+        if self.overlap and self.has_pass2_interior:
+            be.loop_pass2_interior()
+        rho_done()
+        a.va, a.vh, a.ct = be.loop_pass2(a.rho)
+        if self.with_drag or self.with_species:      # both read hydro_update's records (complete h)
+            be.prep(a.pos, a.vel, a.m, a.h, a.T, a.mu, a.gam, a.ptype)
+        self._step_extras(a, rhod)
+
+    def _halo_pass(self, a, arr, run, selected=False):
+        """One scalar halo phase and the pass that reads it: `arr` is the array whose ghost tail travels, run(**kw) the pass.
+        Plain: the exchange, then the pass.  Overlapped: the phase travels while the pass runs for the interior blobs - their
+        particles have no ghost neighbour, they read nothing the phase delivers - and the pass runs again, into the same arrays
+        (out=), for the boundary blobs once it has arrived.  selected: the interior blobs are selected already."""
+        if not a.overlapped:
+            self._halo_scalar(a, arr)
+            return run()
+        done = self._halo_scalar(a, arr, defer=True)
+        if not selected:
+            self.backend.select_blobs(1)
+        out = run()
+        done()
+        self.backend.select_blobs(2)
+        return run(out=out)
+
+    def _sums_hydro(self, a):
+        """hydro_update's sums (nsc:556-671): h_j -> density, rho_j -> Pi (or the pairwise viscosity: no m Pi_j phase),
+        m Pi_j -> viscosity (+ drag and species)."""
+        be = self.backend
+        a.overlapped = self.overlap and self.world > 1 and self.has_select_blobs and be.select_blobs(1)
+
+        def density(**kw):
+            be.prep(a.pos, a.vel, a.m, a.h, a.T, a.mu, a.gam, a.ptype)    # (overlapped: the owned particles' records, then the ghosts')
+            return be.density(self.with_drag, **kw)
+        a.rho, a.nden, a.ha = self._halo_pass(a, a.h, density, selected=True)
+        if self.visc_mode == "pairwise":
+            a.va, a.vh, a.ct = self._halo_pass(a, a.rho, lambda **kw: be.visc_pairwise(a.rho, a.m, **kw))
         else:
-            with self._sec("stale_check"):
-                if no:
-                    d_loc = float((s["pos"] - self.pos_plan).abs().max()) * 1.7320508075688772
-                else:
-                    d_loc = 0.0
-                D = self._allreduce_max(d_loc)                    # bound on the displacement norm
-                hr = (self.halo_scale - 1.0) * s["h"]              # (the head-room a plan is expected to keep)
-                if self.cap_abs > 0.0:
-                    hr = torch.clamp(hr, max=self.cap_abs)
-                stale = float((s["h"] + hr + 2.0 * D > self.w_plan).any()) if no else 0.0
-                is_stale = self._allreduce_max(stale) > 0.5       # (the same verdict on every rank)
-            if is_stale:
-                with self._sec("replan"):
-                    self._replan()
-                D = 0.0
-                self.stale_streak += 1
-                if self.stale_streak >= 3:
-                    self.stale_streak, self.force_replan = 0, 16
+            bw, a.ct = self._halo_pass(a, a.rho, lambda **kw: be.pi(a.rho, **kw))
+            a.va, a.vh = self._halo_pass(a, bw, lambda **kw: be.visc(bw, a.m, **kw))
+        if a.overlapped:
+            be.select_blobs(0)
+        self._step_extras(a, be.rhod if self.with_drag else None)
+
+    def _step_scalars(self, a):
+        """ONE reduction for the step's scalars: halo verdict (max) and the global minimum crossing time for dt (nsc:786,
+        drv:222-229; as max of the negative) -> a.red; this rank's max / mean h -> a.loc.  No host read."""
+        f64 = dict(dtype=torch.float64, device=a.h.device)
+        ct = a.ct.reshape(-1)[:1].to(**f64) if torch.is_tensor(a.ct) else torch.tensor([float(a.ct)], **f64)
+        out4 = self.backend.step_scalars(a.no, a.h, self.w_plan, a.D, 8.0 * self.hmean_prev if self.hmean_prev > 0.0 else 0.0, ct)
+        red, a.loc = out4[:2], out4[2:]
+        if self.world > 1:
+            if red.device == self.comm_device:
+                dist.all_reduce(red, op=dist.ReduceOp.MAX)          # (in place: a view of out4)
             else:
-                self.stale_streak = 0
-        while True:
-            s, no = self.s, self.n_owned                      # (a replan may have migrated particles)
-            send_idx, recv_counts = self.send_idx, self.recv_counts
-            ng = sum(recv_counts)
-            hint_owned = s["h"]
-            mean_h = self.hmean_prev
-            # ---- halo phase 1: ghosts' state (88 B + previous h) ------------------------------
-            loop = self.forms == "loop"
-            state_keys = ["pos", "vel", "m", "T", "mu", "gam", "ptype", "h"]
-            if loop:
-                state_keys.append("E")                    # del_pressure reads the neighbour's E (nsc:755)
-            state_keys += list(self.extra_fields)         # drag coefficients / composition rows of the ghosts
-            state_fields = [s[k_] for k_ in state_keys]
-            with self._sec("halo_state"):
-                g = self._exchange(send_idx, recv_counts, state_fields, send_cat=self.send_cat)
-                if hasattr(be, "append_rows") and all(f.dtype == torch.float64 for f in state_fields):
-                    # the ghosts go behind the owned particles in the owned arrays' own storage: nothing else is copied
-                    regrouped, owned = be.append_rows(no, g, state_fields)
-                    for k_, v in zip(state_keys, owned):
-                        s[k_] = v
-                else:
-                    regrouped = self._regroup(None, no, g, state_fields)
-                pos, vel, m, T, mu, gam, ptype, hint = regrouped[:8]
-                E_all = regrouped[8] if loop else None
-                extra = dict(zip(self.extra_fields, regrouped[(9 if loop else 8):]))
-            with self._sec("search"):
-                h = be.search(pos, no, hint, mean_h)
-            grav = None
-            if self.gravity is not None:
-                # after the search (its grid carries the pyramid), before the update: integrate_auto is launched
-                # before the host knows the verdict
-                with self._sec("gravity"):
-                    grav = self._gravity(be, pos, m, h, no)
-            f64 = dict(dtype=torch.float64, device=h.device)
-            fused = hasattr(be, "step_scalars") and no > 0
-            # a kNN radius that outgrew its claimed reach (checked below, together with dt: the sums
-            # are run on the assumption that the halo was sufficient, which it nearly always is)
-            if not fused:
-                bad_t = (h[:no] + 2.0 * D > self.w_plan).any().to(torch.float64).reshape(1) if no else torch.zeros(1, **f64)
-            # ---- halo phases 2-4: 8 B per ghost, received straight into the tail of the (n_total,)
-            # array the library just filled for the owned particles ----------------------------
-            tail = lambda a: a[no:].view(ng, 1)
-            if loop:
-                with self._sec("sums+halo_scalars"):
-                    # h_j (nsc:711) travels while the step's records are built (they do not read h)
-                    h_done = self._exchange(send_idx, recv_counts, [h[:no]], into=tail(h), send_cat=self.send_cat, defer=True)
-                    be.loop_prep(pos, vel, m, T, mu, gam, ptype, E_all, self.d)
-                    h_done()
-                    rho, rhod, nden, delp = be.loop_pass1(h)
-                    # rho_j (nsc:803) travels while pass 2 runs for the blobs without ghost neighbours
-                    rho_done = self._exchange(send_idx, recv_counts, [rho[:no]], into=tail(rho), send_cat=self.send_cat,
-                                              defer=True)
-                    if self.overlap and hasattr(be, "loop_pass2_interior"):
-                        be.loop_pass2_interior()
-                    rho_done()
-                    va, vh, ct = be.loop_pass2(rho)
-                    ha = None
-                    if self.with_drag or self.with_species:      # both read hydro_update's records (complete h)
-                        be.prep(pos, vel, m, h, T, mu, gam, ptype)
-                    self._step_extras(be, no, ng, send_idx, recv_counts, m, ptype, extra, rho, rhod)
-            else:
-              with self._sec("sums+halo_scalars"):
-                pairwise = self.visc_mode == "pairwise"
-                xch = lambda a, defer=False: self._exchange(send_idx, recv_counts, [a[:no]], into=tail(a), send_cat=self.send_cat,
-                                                            defer=defer)
-                if self.overlap and self.world > 1 and hasattr(be, "select_blobs") and be.select_blobs(1):
-                    # every scalar phase travels while the pass that follows it runs for the blobs whose particles have
-                    # no ghost neighbour (they read nothing the phase delivers); the boundary blobs run after it
-                    done = xch(h, True)                                        # h_j
-                    be.prep(pos, vel, m, h, T, mu, gam, ptype)                 # (owned particles' records)
-                    o1 = be.density(self.with_drag)
-                    done(); be.select_blobs(2)
-                    be.prep(pos, vel, m, h, T, mu, gam, ptype)                 # (ghosts' records)
-                    rho, nden, ha = be.density(self.with_drag, out=o1)
-                    done = xch(rho, True); be.select_blobs(1)                  # rho_j
-                    if pairwise:                                               # (no m Pi_j phase)
-                        o2 = be.visc_pairwise(rho, m)
-                        done(); be.select_blobs(2)
-                        va, vh, ct = be.visc_pairwise(rho, m, out=o2)
-                    else:
-                        o2 = be.pi(rho)
-                        done(); be.select_blobs(2)
-                        bw, ct = be.pi(rho, out=o2)
-                        done = xch(bw, True); be.select_blobs(1)               # m Pi_j
-                        o3 = be.visc(bw, m)
-                        done(); be.select_blobs(2)
-                        va, vh = be.visc(bw, m, out=o3)
-                    be.select_blobs(0)
-                else:
-                    xch(h)                                                     # h_j
-                    be.prep(pos, vel, m, h, T, mu, gam, ptype)
-                    rho, nden, ha = be.density(True) if self.with_drag else be.density()
-                    xch(rho)                                                   # rho_j
-                    if pairwise:
-                        va, vh, ct = be.visc_pairwise(rho, m)
-                    else:
-                        bw, ct = be.pi(rho)
-                        xch(bw)                                                # m Pi_j
-                        va, vh = be.visc(bw, m)
-                self._step_extras(be, no, ng, send_idx, recv_counts, m, ptype, extra, rho,
-                                  getattr(be, "rhod", None) if self.with_drag else None)
-            # ---- ONE reduction and ONE host read for the step's scalars: halo verdict (max), global
-            # minimum crossing time for dt (nsc:786, drv:222-229; as max of the negative), max / mean h
-            t_dt = time.perf_counter()
-            ctt = ct.reshape(-1)[:1].to(**f64) if torch.is_tensor(ct) else torch.tensor([float(ct)], **f64)
-            if fused:                              # one launch: {verdict, -ct, max h, robust mean h}
-                out4 = be.step_scalars(no, h, self.w_plan, D, 8.0 * self.hmean_prev if self.hmean_prev > 0.0 else 0.0,
-                                       ctt)
-                red, loc = out4[:2], out4[2:]
-            else:
-                red = torch.cat([bad_t, -ctt])
-                if no:
-                    ho = h[:no]
-                    if self.hmean_prev > 0.0:          # escapers' radii must not size the cells (robust mean)
-                        keep = ho <= 8.0 * self.hmean_prev
-                        hm = (ho * keep).sum() / keep.sum().clamp(min=1)
-                    else:
-                        hm = ho.mean()
-                    loc = torch.stack([ho.max(), hm])
-                else:
-                    loc = torch.zeros(2, **f64)
-            if self.world > 1:
-                if red.device == self.comm_device:
-                    dist.all_reduce(red, op=dist.ReduceOp.MAX)          # (in place: a view of out4 when fused)
-                else:
-                    red = red.to(self.comm_device)
-                    dist.all_reduce(red, op=dist.ReduceOp.MAX)
-                    red = red.to(h.device)
-            auto = fused and hasattr(be, "integrate_auto")
-            # (the same on every rank: the plan's collectives are entered by all or by none)
-            ahead_ok = (self.plan_ahead and self.world > 1 and self.force_replan > 0 and not self._migration_due()
-                        and all(hasattr(be, a_) for a_ in ("reach_dt", "plan_mask", "step_scalars", "integrate_auto")))
-            ahead = None
-            if ahead_ok and not auto:
-                # a rank without owned particles: nothing to send, but the collectives are collective
-                with self._sec("plan_ahead"):
-                    mask_next, both_next = self._plan_launch(torch.zeros(0, **f64))
-                    ahead = (torch.zeros(0, **f64), mask_next)
-                    both_host = both_next.tolist()
-            if auto:
-                # the update is launched before the host learns the verdict: the kernel itself leaves the state
-                # alone when the step has to be redone, and works out dt from the reduced crossing time
-                red_dev = red if red.device == h.device else red.to(h.device)
-                if grav is not None:
-                    be.set_gravity_accel(grav)
-                if loop:
-                    dt_t = be.integrate_loop(no, s["pos"], s["vel"], s["acc"], s["E"], s["T"], s["m"], s["mu"], s["gam"],
-                                             s["ptype"], delp, rho, va, vh, 0.0, red2=red_dev.contiguous(),
-                                             first=self.first, fixed_dt=fixed_dt)
-                else:
-                    dt_t = be.integrate_auto(no, s["pos"], s["vel"], s["acc"], s["E"], s["T"], s["m"], s["mu"], s["gam"],
-                                             s["ptype"], ha, va, vh, red_dev.contiguous(), self.first, fixed_dt)
-                # ---- the NEXT step's plan, while the host still has not looked at this one's scalars: the update is
-                # on its way, so the positions the next step starts from are known to the device.  Reach, need map,
-                # both all_gathers and the send mask are launched now; their counts ride in this step's one host read.
-                # (Speculative: a "redo" verdict leaves the state untouched and this plan is dropped.)
-                if ahead_ok:
-                    with self._sec("plan_ahead"):
-                        be.clamp(s["pos"], s["vel"])            # drv:233-238, early: the next step's own clamp finds nothing to do
-                        w_next = be.reach_dt(h[:no].contiguous(), s["vel"], self.halo_scale, self.skin_frac,
-                                             dt_t if self.reach_vfac == 1.0 else dt_t * self.reach_vfac)
-                        mask_next, both_next = self._plan_launch(w_next)
-                        ahead = (w_next, mask_next)
-                if ahead is not None and both_next.device == red_dev.device:
-                    vals = torch.cat([red_dev, loc, dt_t, both_next.reshape(-1).to(torch.float64)]).tolist()
-                    both_host = [vals[5:5 + self.world], vals[5 + self.world:5 + 2 * self.world]]
-                else:
-                    vals = torch.cat([red_dev, loc, dt_t]).tolist()
-                    both_host = both_next.tolist() if ahead is not None else None     # (host-memory halo: already there)
-            else:
-                vals = out4.tolist() if (fused and red.data_ptr() == out4.data_ptr()) else torch.cat([red, loc]).tolist()
-            if vals[0] < 0.5:
-                break
-            # the halo was too thin somewhere: those particles claim their new radius (x1.5), everybody
-            # replans and the step's search and sums are redone
-            if no:
-                fail = h[:no] + 2.0 * D > self.w_plan
-                s["h"] = torch.where(fail, 1.5 * (h[:no] + 2.0 * D), s["h"])
-            # (a migration inside the redo sorts by THIS attempt's search: the state has not moved since)
-            self.last_ntotal = int(pos.shape[0])
-            with self._sec("replan"):
-                self._replan()
-            D = 0.0
-            self.stats["redo"] += 1
-        ct_min, self.hmax_prev, self.hmean_prev = -vals[1], vals[2], vals[3]
-        self.plan_next = None
-        if ahead is not None:
+                red = red.to(self.comm_device)
+                dist.all_reduce(red, op=dist.ReduceOp.MAX)
+                red = red.to(a.h.device)
+        a.red = red
+
+    def _update_args(self, a):
+        return (a.no,) + tuple(self.s[k_] for k_ in ("pos", "vel", "acc", "E", "T", "m", "mu", "gam", "ptype"))
+
+    def _plan_ahead_due(self):
+        """Make the NEXT step's plan at the end of this one?  (The same on every rank: its collectives are entered by all or none.)"""
+        return self.has_auto_update and self.plan_ahead and self.world > 1 and self.force_replan > 0 and not self._migration_due()
+
+    def _launch_update(self, a, fixed_dt):
+        """The update launched before the host learns the verdict: the kernel itself leaves the state alone when the step
+        has to be redone, and works out dt from the reduced crossing time.  Then the step's ONE host read -> a.vals."""
+        s, be, W = self.s, self.backend, self.world
+        red_dev = a.red if a.red.device == a.h.device else a.red.to(a.h.device)
+        if a.grav is not None:
+            be.set_gravity_accel(a.grav)
+        if self.forms == "loop":
+            dt_t = be.integrate_loop(*self._update_args(a), a.delp, a.rho, a.va, a.vh, 0.0, red2=red_dev.contiguous(),
+                                     first=self.first, fixed_dt=fixed_dt)
+        else:
+            dt_t = be.integrate_auto(*self._update_args(a), a.ha, a.va, a.vh, red_dev.contiguous(), self.first, fixed_dt)
+        # ---- the NEXT step's plan, while the host still has not looked at this one's scalars: the update is
+        # on its way, so the positions the next step starts from are known to the device.  Reach, need map,
+        # both all_gathers and the send mask are launched now; their counts ride in this step's one host read.
+        # (Speculative: a "redo" verdict leaves the state untouched and this plan is dropped.)
+        both_next = None
+        if self._plan_ahead_due():
             with self._sec("plan_ahead"):
-                send_idx_n, recv_n = self._plan_finish(ahead[1], both_host)
-                parts = [ix for ix in send_idx_n if ix is not None and ix.numel()]
-                cat_n = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=self.device)
-                self.plan_next = (ahead[0], send_idx_n, recv_n, cat_n)
-        if auto:
-            dt = vals[4]                                   # (worked out and applied on the device)
+                be.clamp(s["pos"], s["vel"])            # drv:233-238, early: the next step's own clamp finds nothing to do
+                w_next = be.reach_dt(a.h[:a.no].contiguous(), s["vel"], self.halo_scale, self.skin_frac,
+                                     dt_t if self.reach_vfac == 1.0 else dt_t * self.reach_vfac)
+                mask_next, both_next = self._plan_launch(w_next)
+                a.ahead = (w_next, mask_next)
+        if both_next is not None and both_next.device == red_dev.device:
+            a.vals = torch.cat([red_dev, a.loc, dt_t, both_next.reshape(-1).to(torch.float64)]).tolist()
+            a.both_host = [a.vals[5:5 + W], a.vals[5 + W:5 + 2 * W]]
         else:
-            ctv = self.DT_0 / 10. if ct_min >= HUGE_CT else ct_min + 0.0001
-            if fixed_dt > 0:
-                dt = fixed_dt
-            else:
-                dt = self.DT_0 / 10. if self.first else max(self.DT_0 / 5., min(self.DT_0 * 2., ctv))
-                if ctv > self.MAX_AGE:
-                    dt = self.MAX_AGE / 100.
-            if grav is not None:
-                be.set_gravity_accel(grav)
-            if self.forms == "loop":
-                be.integrate_loop(no, s["pos"], s["vel"], s["acc"], s["E"], s["T"], s["m"], s["mu"], s["gam"], s["ptype"],
-                                  delp, rho, va, vh, dt)
-            else:
-                be.integrate(no, s["pos"], s["vel"], s["acc"], s["E"], s["T"], s["m"], s["mu"], s["gam"], s["ptype"],
-                             ha, va, vh, dt)
-        self.host_ms["dt+integrate"] = self.host_ms.get("dt+integrate", 0.0) + (time.perf_counter() - t_dt) * 1e3
-        s["h"] = h[:no].contiguous()
-        self.last = dict(rho=rho[:no], nden=nden[:no], visc_heat=vh[:no])
-        self.dt_last = dt
-        self.last_ntotal = int(pos.shape[0])
-        self.first = False
-        self.stats["steps"] += 1
-        self.stats["ghosts"] += ng
+            a.vals = torch.cat([red_dev, a.loc, dt_t]).tolist()
+            a.both_host = both_next.tolist() if both_next is not None else None     # (host-memory halo: already there)
+
+    def _read_scalars(self, a):
+        """The host reads the step's scalars -> a.vals; the update follows when the verdict is known (_finish_update)."""
+        if self._plan_ahead_due():
+            # a rank without owned particles: nothing to send, but the collectives are collective
+            with self._sec("plan_ahead"):
+                w_next = torch.zeros(0, dtype=torch.float64, device=a.h.device)
+                mask_next, both_next = self._plan_launch(w_next)
+                a.ahead = (w_next, mask_next)
+                a.both_host = both_next.tolist()
+        a.vals = torch.cat([a.red, a.loc]).tolist()
+
+    def _finish_update(self, a, ct_min, fixed_dt):
+        """The update with dt worked out on the host (timestep_rule) -> dt."""
+        be = self.backend
+        dt = timestep_rule(ct_min, self.first, fixed_dt)
+        if a.grav is not None:
+            be.set_gravity_accel(a.grav)
+        if self.forms == "loop":
+            be.integrate_loop(*self._update_args(a), a.delp, a.rho, a.va, a.vh, dt)
+        else:
+            be.integrate(*self._update_args(a), a.ha, a.va, a.vh, dt)
+        return dt
 
     # ------------------------------------------------------------------------------------------
     MIG_FIELDS = ("pos", "vel", "acc", "m", "T", "mu", "gam", "ptype", "E", "h", "gid")
@@ -1391,7 +1390,7 @@ class DistributedSim:
         if sel is None and (got is None or got.shape[0] == 0):
             return                                             # nothing moved, no order to apply
         n_sel = n if sel is None else int(sel.numel())
-        new = self._regroup(sel, n_sel, got, fields)
+        new = self.backend.regroup(sel, n_sel, got, fields)
         for k_, v in zip(mig, new):
             s[k_] = v
         self.last = dict(rho=new[-3], nden=new[-2], visc_heat=new[-1])
@@ -1409,7 +1408,6 @@ class DistributedSim:
         if sp:
             out.update({k_: c(v) for k_, v in sp.items() if v is not None})
         return out
-
 
     # ---- snapshot / restart and per-step diagnostics (for the decomposed run) -------------------------
     def snapshot(self, prefix):
@@ -1532,7 +1530,7 @@ def decompose_state(state, world, rank):
 # bench leg for N > 1 (called by bench.py under torch.distributed.run)
 # ==============================================================================================
 def _blob_split(be, sim):
-    if not (getattr(sim, "overlap", False) and hasattr(be, "blob_split_counts")):
+    if not sim.overlap:
         return None
     try:
         c = be.blob_split_counts()

@@ -338,10 +338,10 @@ def test_two_ranks_sharing_one_gpu_drag_species_agb(forms, tmp_path):
 @pytest.mark.gpu
 def test_fused_row_kernels_match_tensor_forms():
     """sphx_dev_pack_rows / sphx_dev_regroup (one launch each) against the tensor-library forms the
-    CPU tests run (DistributedSim._pack / _regroup without a fused backend)."""
+    CPU tests run (TensorBackend.pack_rows / regroup)."""
     import torch
-    from sph_code_amd.multigpu import LibBackend, DistributedSim
-    be = LibBackend(0, k=8)
+    from sph_code_amd.multigpu import LibBackend, TensorBackend
+    be, spec = LibBackend(0, k=8), TensorBackend()
     dev = be.device
     g = torch.Generator(device="cpu").manual_seed(3)
     n, nr = 1000, 37
@@ -349,23 +349,16 @@ def test_fused_row_kernels_match_tensor_forms():
     m = torch.rand(n, generator=g, dtype=torch.float64).to(dev)
     gid = torch.randint(0, 1 << 40, (n,), generator=g, dtype=torch.int64).to(dev)
     idx = torch.randperm(n, generator=g)[:123].to(dev)
-
-    class Plain:                        # no fused helpers: DistributedSim falls back to torch
-        pass
-    shim = DistributedSim.__new__(DistributedSim)
-    shim.backend = Plain()
-    fused = DistributedSim.__new__(DistributedSim)
-    fused.backend = be
     fields = [pos, m, gid]
     for ix in (idx, None):
-        a, b = shim._pack(ix, fields), fused._pack(ix, fields)
+        a, b = spec.pack_rows(ix, fields), be.pack_rows(ix, fields)
         assert torch.equal(a.view(torch.int64), b.view(torch.int64))
-    rows = shim._pack(idx[:nr], fields)
+    rows = spec.pack_rows(idx[:nr], fields)
     sel = torch.randperm(n, generator=g)[:800].to(dev)
     for s_, ns in ((sel, 800), (None, n)):
         for r_ in (rows, None):
-            a = shim._regroup(s_, ns, r_, fields)
-            b = fused._regroup(s_, ns, r_, fields)
+            a = spec.regroup(s_, ns, r_, fields)
+            b = be.regroup(s_, ns, r_, fields)
             for x, y in zip(a, b):
                 assert x.dtype == y.dtype and x.shape == y.shape and torch.equal(x, y)
     torch.cuda.synchronize()
@@ -373,10 +366,10 @@ def test_fused_row_kernels_match_tensor_forms():
 
 def test_need_map_kernel_matches_tensor_form():
     """sphx_dev_need_map (one launch, no host sync) gives the very map of the tensor-library form
-    (DistributedSim._need_map without a fused backend): owned particles inside, on the edge of and
+    (TensorBackend.need_map): owned particles inside, on the edge of and
     outside the coarse grid, reaches from 0 to several cells to the whole grid."""
     import torch
-    from sph_code_amd.multigpu import LibBackend, DistributedSim
+    from sph_code_amd.multigpu import LibBackend, TensorBackend
     be = LibBackend(0, k=8)
     dev = be.device
     g = torch.Generator(device="cpu").manual_seed(11)
@@ -393,17 +386,10 @@ def test_need_map_kernel_matches_tensor_form():
     w[7] = 1.0 / 24                      # exactly one cell edge
     w[3] = 50.0                          # the whole grid
 
-    class Plain:
-        pass
+    Plain = TensorBackend
 
     def sim(backend, pos_, w_):
-        s_ = DistributedSim.__new__(DistributedSim)
-        s_.backend, s_.device, s_.G = backend, dev, G
-        s_.g_lo = torch.zeros(3, dtype=torch.float64, device=dev)
-        s_.g_lo_host = [0.0, 0.0, 0.0]
-        s_.g_cs = 1.0 / G
-        s_.s = dict(pos=pos_.to(dev))
-        return s_._need_map(w_.to(dev))
+        return backend.need_map(pos_.to(dev), w_.to(dev), [0.0, 0.0, 0.0], 1.0 / G, G)
 
     for sl in (slice(None), slice(8, None), slice(0, 3), slice(0, 0), slice(8, 400), slice(11, 12)):
         a, b = sim(Plain(), pos[sl], w[sl]), sim(be, pos[sl], w[sl])
@@ -419,11 +405,11 @@ def test_need_map_kernel_matches_tensor_form():
 
 
 def test_fused_reach_and_step_scalars_match_tensor_forms():
-    """sphx_dev_reach / sphx_dev_step_scalars (one launch each) against the tensor-library expressions of
-    DistributedSim._replan / .step that the CPU tests run."""
+    """sphx_dev_reach / sphx_dev_step_scalars (one launch each) against the tensor-library forms that the CPU tests run
+    (TensorBackend.reach / reach_dt / step_scalars), and against the expressions restated here."""
     import torch
-    from sph_code_amd.multigpu import LibBackend
-    be = LibBackend(0, k=8)
+    from sph_code_amd.multigpu import LibBackend, TensorBackend
+    be, spec = LibBackend(0, k=8), TensorBackend()
     dev = be.device
     g = torch.Generator(device="cpu").manual_seed(5)
     n, no = 70000, 65537
@@ -435,6 +421,8 @@ def test_fused_reach_and_step_scalars_match_tensor_forms():
     speed = torch.sqrt((vel * vel).sum(dim=1))
     w_ref = torch.maximum((halo + skin) * h, halo * h + speed * dt)
     assert float(((w - w_ref).abs() / w_ref).max()) <= 4e-16      # (the same expression, to rounding)
+    w_spec = spec.reach(h, vel, halo, skin, dt)
+    assert float(((w - w_spec).abs() / w_spec).max()) <= 4e-16
     # head-room capped at an absolute length (sphx_dev_set_reach_cap): the escaper claims h + cap (+ its displacement)
     cap = 0.2
     be.set_reach_cap(cap)
@@ -445,6 +433,9 @@ def test_fused_reach_and_step_scalars_match_tensor_forms():
     capt = torch.full_like(h, cap)
     wc_ref = torch.maximum(h + torch.minimum((halo + skin - 1.0) * h, capt), (h + torch.minimum((halo - 1.0) * h, capt)) + speed * dt)
     assert float(((wc - wc_ref).abs() / wc_ref).max()) <= 4e-16 and torch.equal(wc_dt, wc)
+    spec.set_reach_cap(cap)
+    wc_spec = spec.reach(h, vel, halo, skin, dt)
+    assert float(((wc - wc_spec).abs() / wc_spec).max()) <= 4e-16 and torch.equal(spec.reach_dt(h, vel, halo, skin, dt_dev), wc_spec)
     assert float(wc[17]) <= 40.0 + cap + float(speed[17]) * dt + 1e-9 and float(w[17]) >= 52.0 - 1e-9
     assert bool((wc <= w * (1 + 1e-15)).all()) and bool((wc >= h).all())
     ct = torch.tensor([3.25], dtype=torch.float64, device=dev)
@@ -460,6 +451,8 @@ def test_fused_reach_and_step_scalars_match_tensor_forms():
             hm = float(ho.mean())
         assert out[0] == bad and out[1] == -3.25 and out[2] == float(ho.max())
         assert abs(out[3] - hm) <= 1e-13 * hm
+        out_spec = spec.step_scalars(no, h, w[:no], D, hclip, ct).tolist()
+        assert out[:3] == out_spec[:3] and abs(out[3] - out_spec[3]) <= 1e-13 * hm
     assert be.step_scalars(no, h, w, 0.0, 8.0, ct).tolist()[0] == 0.0 and be.step_scalars(no, h, w, 0.4, 8.0, ct).tolist()[0] == 1.0
     torch.cuda.synchronize()
 

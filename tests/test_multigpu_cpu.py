@@ -13,12 +13,14 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from conftest import ROOT
+from sph_code_amd.multigpu import TensorBackend, timestep_rule
 
 K = 16
 
 
-class OracleBackend:
-    """Test-only stand-in for multigpu.LibBackend built on the oracle's phase hooks."""
+class OracleBackend(TensorBackend):
+    """Test-only stand-in for multigpu.LibBackend: the physics from the oracle's phase hooks, the driver's helpers in
+    their tensor-library forms (TensorBackend)."""
 
     def __init__(self, k):
         from oracle import sph_oracle as orc
@@ -134,51 +136,12 @@ class OracleBackend:
 
 
 class OracleFusedBackend(OracleBackend):
-    """OracleBackend + the tensor-library forms of the library's fused helpers (sphx_dev_reach_dt, sphx_dev_step_scalars,
-    sphx_dev_integrate_auto / _loop with the verdict and dt taken from device memory): with them DistributedSim takes the path
-    it takes on the GPU - the update launched before the host reads the step's scalars, the NEXT step's plan made at the end
-    of the current one - over gloo on the CPU."""
-
-    cap = 0.0
-
-    def set_reach_cap(self, cap_abs):
-        self.cap = float(cap_abs)
-
-    def _reach(self, h, vel, halo, skin, dtv):
-        speed = torch.sqrt((vel * vel).sum(dim=1))
-        if self.cap > 0.0:
-            cap = torch.full_like(h, self.cap)
-            a = torch.minimum((halo + skin - 1.0) * h, cap)
-            b = torch.minimum((halo - 1.0) * h, cap)
-            return torch.maximum(h + a, (h + b) + speed * dtv)
-        return torch.maximum((halo + skin) * h, halo * h + speed * dtv)
-
-    def reach(self, h, vel, halo_scale, skin_frac, dt_last):
-        return self._reach(h, vel, halo_scale, skin_frac, float(dt_last))
-
-    def reach_dt(self, h, vel, halo_scale, skin_frac, dt_dev):
-        return self._reach(h, vel, halo_scale, skin_frac, float(dt_dev.reshape(-1)[0]))
-
-    def plan_mask(self, pos, g_lo, g_cs, G, maps, rank):
-        lo = torch.tensor(g_lo, dtype=torch.float64)
-        c = torch.floor((pos - lo[None]) / g_cs).to(torch.int64).clamp_(0, G - 1)
-        cell = (c[:, 2] * G + c[:, 1]) * G + c[:, 0]
-        mask = maps[:, cell] != 0
-        mask[rank] = False
-        return mask, mask.sum(dim=1)
-
-    def step_scalars(self, n_owned, h, w_plan, D, hclip, ct):
-        ho = h[:n_owned]
-        bad = (ho + 2.0 * D > w_plan).any().to(torch.float64).reshape(1)
-        keep = (ho <= hclip) if hclip > 0.0 else torch.ones_like(ho, dtype=torch.bool)
-        hm = (ho * keep).sum() / keep.sum().clamp(min=1)
-        return torch.cat([bad, -ct.reshape(-1)[:1].to(torch.float64), ho.max().reshape(1), hm.reshape(1)])
+    """OracleBackend + the update that takes the verdict and dt from device memory (sphx_dev_integrate_auto / _loop's
+    counterparts): with them DistributedSim takes the path it takes on the GPU - the update launched before the host reads
+    the step's scalars, the NEXT step's plan made at the end of the current one - over gloo on the CPU."""
 
     def _dt(self, red2, first, fixed_dt):
-        o = self.orc
-        ct_min = -float(red2[1])
-        ctv = o.DT_0 / 10. if ct_min >= float("inf") else ct_min + 0.0001
-        return fixed_dt if fixed_dt > 0 else o.timestep(ctv, first)
+        return timestep_rule(-float(red2[1]), first, fixed_dt)
 
     def integrate_auto(self, no, pos, vel, acc, E, T, m, mu, gam, ptype, ha, va, vh, red2, first, fixed_dt):
         if float(red2[0]) > 0.5:                        # the halo was too thin: the state stays as it is
@@ -196,6 +159,45 @@ class OracleFusedBackend(OracleBackend):
         dt = self._dt(red2, first, fixed_dt)
         OracleBackend.integrate_loop(self, no, pos, vel, acc, E, T, m, mu, gam, ptype, delp, rho, va, vh, dt)
         return torch.tensor([dt], dtype=torch.float64)
+
+
+class OverlapRecorder(OracleBackend):
+    """OracleBackend that says its blobs are split into interior and boundary ones (select_blobs -> True), so that
+    DistributedSim runs every pass of hydro_update's sums once per part, and keeps the names of the calls it gets.  The
+    oracle's passes take all particles whatever the part and return new arrays (out= is ignored): a pass run twice gives
+    what it gives run once after the exchange."""
+
+    def __init__(self, k):
+        OracleBackend.__init__(self, k)
+        self.calls = []
+
+    def select_blobs(self, part):
+        self.calls.append("select_blobs(%d)" % part)
+        return True
+
+    def search(self, *a):
+        self.calls.append("search")
+        return OracleBackend.search(self, *a)
+
+    def prep(self, *a):
+        self.calls.append("prep")
+        OracleBackend.prep(self, *a)
+
+    def density(self, want_dust=False, out=None):
+        self.calls.append("density")
+        return OracleBackend.density(self, want_dust)
+
+    def pi(self, rho_complete, out=None):
+        self.calls.append("pi")
+        return OracleBackend.pi(self, rho_complete)
+
+    def visc(self, bw_complete, m, out=None):
+        self.calls.append("visc")
+        return OracleBackend.visc(self, bw_complete, m)
+
+    def integrate(self, *a):
+        self.calls.append("integrate")
+        OracleBackend.integrate(self, *a)
 
 
 def _free_port():
@@ -222,7 +224,8 @@ def _worker(rank, world, port, n, nsteps, workload, out_dir, sim_kw=None):
         sim_kw["d"] = ics.loop_d(state, K)
     fused = sim_kw.pop("_fused_backend", False)
     force = sim_kw.pop("_force_replan", 0)
-    sim = mg.DistributedSim(mine, lo, hi, (OracleFusedBackend if fused else OracleBackend)(K), rank, world, device="cpu", **sim_kw)
+    Backend = OverlapRecorder if sim_kw.pop("_overlap_recorder", False) else OracleFusedBackend if fused else OracleBackend
+    sim = mg.DistributedSim(mine, lo, hi, Backend(K), rank, world, device="cpu", **sim_kw)
     if force:
         sim.force_replan = force                     # the regime of the reference's dt rule: a new plan every step
     for _ in range(nsteps):
@@ -233,6 +236,8 @@ def _worker(rank, world, port, n, nsteps, workload, out_dir, sim_kw=None):
     res["stats"] = np.array([sim.stats["ghosts"], sim.stats["redo"], sim.stats["migrated"], sim.ex.bytes_sent,
                              sim.stats.get("replans", 0)])
     res["ahead_ms"] = np.float64(sim.host_ms.get("plan_ahead", 0.0))
+    if hasattr(sim.backend, "calls"):
+        res["calls"] = np.array(sim.backend.calls)
     np.savez(os.path.join(out_dir, "rank%d.npz" % rank), **res)
     dist.barrier()
     dist.destroy_process_group()
@@ -251,6 +256,7 @@ def _run_world(world, n, nsteps, workload, tmp_path, sim_kw=None):
     merged["dt"] = [float(p["dt"]) for p in parts]
     merged["stats"] = np.sum([p["stats"] for p in parts], axis=0)
     merged["ahead_ms"] = [float(p["ahead_ms"]) for p in parts] if "ahead_ms" in parts[0] else None
+    merged["calls"] = [p["calls"].tolist() for p in parts] if "calls" in parts[0] else None
     return merged
 
 
@@ -501,3 +507,33 @@ def test_world2_gloo_drag_with_reverse_halo_and_species(tmp_path):
     F = orc.hydro_update(ref["neighbor"], p, prev["mass"], ref["sizes"], prev["f_un"], prev["particle_type"], prev["T"],
                          prev["mu_array"], prev["gamma_array"], v)[5]
     np.testing.assert_allclose(got["f_un_neighbor"].T, F, rtol=1e-12, atol=0)
+
+
+def test_world2_interior_blobs_under_the_halo_phases_call_sequence(tmp_path):
+    """The overlapped form of hydro_update's sums (a backend with select_blobs; on the GPU: the interior blobs' share of
+    a pass runs while the scalar halo phase it does not read is in flight, the boundary blobs' share after it).  Between
+    the search and the scalar reduction of every attempt the backend is called in exactly the order below - prep twice,
+    every pass once per part, everything selected again at the end - and the result is the plain sequence's, bit for bit."""
+    n, nsteps = 2000, 3
+    sequence = ["select_blobs(1)", "prep", "density", "select_blobs(2)", "prep", "density",
+                "select_blobs(1)", "pi", "select_blobs(2)", "pi",
+                "select_blobs(1)", "visc", "select_blobs(2)", "visc", "select_blobs(0)"]
+    dirs = {}
+    for name in ("overlapped", "plain"):
+        dirs[name] = tmp_path / name
+        dirs[name].mkdir()
+    got = _run_world(2, n, nsteps, "uniform_sphere", dirs["overlapped"], sim_kw=dict(forms="hydro_update", _overlap_recorder=True))
+    ref = _run_world(2, n, nsteps, "uniform_sphere", dirs["plain"], sim_kw=dict(forms="hydro_update"))
+    redo = int(ref["stats"][1]) // 2                                  # (the same on both ranks: summed)
+    for calls in got["calls"]:
+        # a search followed by another one is the bootstrap's (no ghosts yet, no sums); every other one opens an attempt
+        opens = [i for i, c in enumerate(calls) if c == "search" and calls[i + 1:i + 2] != ["search"]]
+        attempts = [calls[i + 1:j] for i, j in zip(opens, opens[1:] + [len(calls)])]
+        assert len(attempts) == nsteps + redo
+        assert calls.count("integrate") == nsteps
+        for att in attempts:
+            assert [c for c in att if c != "integrate"] == sequence, att
+            assert att[len(sequence):] in ([], ["integrate"])        # (the update comes after the reduction)
+    assert got["dt"] == ref["dt"] and np.array_equal(got["stats"], ref["stats"])
+    for k_ in ("points", "velocities", "total_accel", "E_internal", "T", "sizes", "densities"):
+        assert np.array_equal(got[k_], ref[k_]), k_
