@@ -659,7 +659,7 @@ int sphx_supernova_impulse(sphx_ctx* ctx, int64_t n, const double* points, const
  * velocities.  The state is gathered into the caller's particle order as the phases gather it and the selection runs
  * on that copy: the bits are those of sphx_supernova_impulse and sphx_crossing_time on the downloaded state.  Only the
  * velocities are written, and only when the call succeeds: a refused call leaves the state as it was.  The insertion of
- * the new particles (drv:361-396) changes N and is the caller's.
+ * the new particles (drv:361-396) changes N: sphx_state_insert_rows, below.
  * Outputs as sphx_supernova_impulse's (sel_ids in the caller's order); ct, dt_event: scalars.
  * SPHX_E_STATE as sphx_state_dust_phase: no state, no step yet, incremental search, the step's list gone.
  * SPHX_E_ARG: an id outside [0, n), mass_displaced not positive and finite, cap too small (the text names the size).  */
@@ -672,6 +672,52 @@ int sphx_state_supernova_impulse(sphx_ctx* ctx, int64_t n_sn, const int64_t* ids
  * ms[3] the sort, ms[4] the walk and its host wait, ms[5] true_mass, vel and the kick.  Also after
  * sphx_state_supernova_impulse (the gather, the crossing time and the write-back are not in it).  Measurement aid.  */
 int sphx_sn_last_timing(sphx_ctx* ctx, double ms[SPHX_SN_STAGES]);
+/* ---- the insertion of a supernova's new particles into the resident state                       drv:361-396 ----- *
+ * The block of the time loop that changes N.  The host forms the few new rows (nsc.supernova_explosion, nsc:820-882, on
+ * the exploding stars' rows alone); the state itself never leaves the device.
+ *
+ * sphx_state_download_rows: the rows with the caller ids ids[n_rows] (particle indices of the uploaded state, each once)
+ * in the order given: pos, vel (n_rows,3), mass, E_internal (n_rows), f_un (n_rows,s) or NULL.  One kernel over the state:
+ * every storage slot looks its id up in the sorted list by binary search (no N-sized inverse table).
+ * SPHX_E_STATE: no state; f_un asked of a state without one.  SPHX_E_ARG: an id outside [0, n) or given twice.
+ *
+ * sphx_state_insert_rows, in the driver's order:
+ *   the rows rew_ids[n_rew] get rew_mass, rew_E and the composition rows rew_f_un (n_rew,s)             drv:364-366
+ *   n_app rows are appended: app_pos, app_vel (n_app,3), app_mass, app_ptype, app_E (n_app), app_f_un (n_app,s); their
+ *     caller ids are N .. N + n_app - 1 in the order given (the driver appends dust, then gas), their previous radius and
+ *     previous acceleration 0                                                                           drv:363, 367-372
+ *   T of the new rows is 0, then T[T < t_cmb] = t_cmb over ALL rows (a NaN stays)                       drv:379-382
+ *   mu_array = sum(f_un mu_specie, axis=1) / sum(f_un, axis=1), gamma_array likewise with gamma_specie, formed again for
+ *     EVERY row of a state that carries its composition, in NumPy's order of the row sums (a state uploaded without
+ *     f_un: for the rewritten and the new rows only, from the rows given)                               drv:393-394
+ *   with drag on, the rewritten and the new rows' mean grain mass and cross-section from grain_mass, sigma_effective
+ *   the search of drv:386 on the N + n_app rows (k, dist as sphx_step takes them), run as the first step's search is (no
+ *     radius handed to it); its list and radii are then the step's own: sphx_state_dust_phase, sphx_state_rad_phase,
+ *     sphx_state_supernova_impulse, sphx_state_download_neighbors and sphx_state_download (sizes) read them; the next
+ *     sphx_step sizes its grid from this search
+ *   the first step of the next sphx_step call integrates dv = a dt for every row (drv:482-485: the previous acceleration
+ *     has the old shape); the step after it averages again.
+ * Every per-particle buffer of the state is grown with its contents kept, only where the head-room of its allocation does
+ * not already hold N + n_app rows; the host checks that each holds them before the first kernel is launched.  Until the
+ * next step, densities, num_densities, visc_heat and the pressure download as zeros ("not stepped yet") and
+ * sphx_state_download_species is refused.
+ * SPHX_E_STATE (as sphx_state_dust_phase): no state, no step yet, incremental search, the step's list gone.
+ * SPHX_E_ARG: an id outside [0, N) or given twice, s not the state's, N + n_app over 2^31 - 16, a non-finite new position
+ * or table entry, drag on without grain_mass and sigma_effective.  A refused call has written nothing.
+ *
+ * sphx_insert_last_info: info[0] buffers reallocated, [1] rows appended, [2] rows rewritten, [3] rows whose T the clamp
+ * moved (new rows included).  sphx_insert_last_timing: device time of the stages of the last sphx_state_insert_rows, ms:
+ * [0] checks' upload, [1] grow, [2] the insert kernel, [3] the search.                                              */
+int sphx_state_download_rows(sphx_ctx* ctx, int64_t n_rows, const int64_t* ids, double* pos, double* vel, double* mass,
+                             double* E_internal, double* f_un /* or NULL */);
+int sphx_state_insert_rows(sphx_ctx* ctx, int s, int64_t n_rew, const int64_t* rew_ids, const double* rew_mass, const double* rew_E,
+                           const double* rew_f_un, int64_t n_app, const double* app_pos, const double* app_vel,
+                           const double* app_mass, const double* app_ptype, const double* app_E, const double* app_f_un, double t_cmb,
+                           const double* mu_specie /* [s] */, const double* gamma_specie /* [s] */,
+                           const double* grain_mass /* [s] or NULL */, const double* sigma_effective /* [s] or NULL */, int k,
+                           double dist);
+int sphx_insert_last_info(sphx_ctx* ctx, int64_t info[4]);
+int sphx_insert_last_timing(sphx_ctx* ctx, double ms[4]);
 /* ---- nsc.chemisputtering_2(points, neighbor, mass, f_un, mu_array, sizes, T, particle_type)      nsc:1265-1416 ----- *
  * Thermal / chemical sputtering of the dust rows and reuptake by the gas entries of their lists, on the list `neighbors`
  * returned (drv:405).  The module globals d and dt are arguments, and so are the per-species tables (nsc:41-52).

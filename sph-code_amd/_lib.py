@@ -105,6 +105,11 @@ SIGNATURES = {
     "sphx_state_supernova_impulse": (C.c_int, [_P, C.c_int64, _I, C.c_double, C.c_double, C.c_double, C.c_int64, _I, _I, _D, _D, _D, _I,
                                                _D, _D]),
     "sphx_sn_last_timing": (C.c_int, [_P, _D]),
+    "sphx_state_download_rows": (C.c_int, [_P, C.c_int64, _I, _D, _D, _D, _D, _D]),
+    "sphx_state_insert_rows": (C.c_int, [_P, C.c_int, C.c_int64, _I, _D, _D, _D, C.c_int64] + [_D] * 6 + [C.c_double] + [_D] * 4 +
+                                         [C.c_int, C.c_double]),
+    "sphx_insert_last_info": (C.c_int, [_P, _I]),
+    "sphx_insert_last_timing": (C.c_int, [_P, _D]),
     "sphx_chemisputtering_2": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _D, _I] + [_D] * 6 + [C.c_double, C.c_double] + [_D] * 4 +
                                          [C.c_double] * 3 + [_D, _D, _I]),
     "sphx_chem_last_timing": (C.c_int, [_P, _D]),

@@ -1241,3 +1241,171 @@ def radphase_last_timing():
     """Device time of the last rad_ionise / rad_heat_bookkeeping / rad_cool_bookkeeping call of this module, from HIP
     events (include/sphx.h sphx_radphase_last_timing) -> dict of ms: upload, kernel, sums, download."""
     return _last_timing("sphx_radphase_last_timing", ("upload", "kernel", "sums", "download"))
+
+
+# ==============================================================================================
+# The explosion itself and the insertion of its particles: supernova_explosion (nsc:820-882), drv:361-396
+# ==============================================================================================
+# Host code, on the few rows of the exploding stars: the one part of this module that computes in NumPy.  It restates the
+# reference's statements with the same NumPy operations on arrays of the same layout, so the bits are the reference's.
+SN_PROGEN_MASS = (0, 20, 25, 30, 35, 40)                                        # nsc:82, solar masses
+# nsc:81-99, the mixed CCSN dust yields by species: None is the reference's zero_function, an entry the yields at
+# SN_PROGEN_MASS (written as the reference writes them: 7*10**(-2) is not the double 0.07)
+SN_YIELDS = (None, None, None, None, None, None,
+             (6 * 10 ** (-2), 10 ** (-1) * 1.5, 2 * 10 ** (-1), 8 * 10 ** (-1), 1, 1),                     # Mg2SiO4
+             (4 * 10 ** (-2), 4 * 10 ** (-1), 4.1 * 10 ** (-1), 5 * 10 ** (-1), 10 ** (-1) * 8, 10 ** (-1) * 8),   # SiO2
+             None, None,
+             (10 ** (-2), 7 * 10 ** (-2), 7 * 10 ** (-2), 7 * 10 ** (-2), 7 * 10 ** (-2), 7 * 10 ** (-2)),  # Fe
+             (2 * 10 ** (-2), 5 * 10 ** (-2), 6 * 10 ** (-2), 9 * 10 ** (-3), 0, 0),                        # MgSiO3
+             None, None)
+SN_REMNANT_MASS = 2.                                                            # nsc:837, 849: solar masses left as the star
+SN_DUST_ROW_MASS = 0.05                                                         # nsc:840: solar masses per dust row
+EXPLOSION_FIELDS = ("dust_comps", "gas_comps", "star_comps", "dust_mass", "gas_mass", "stars_mass", "newpoints", "newvels",
+                    "newgastype", "newdusttype", "new_eint_stars", "new_eint_dust", "new_eint_gas", "supernova_pos", "dustpoints",
+                    "dustvels")
+
+
+def sn_yield_table(S, yields=None):
+    """The per-species yields as a list of S entries, each None ("none") or the six values at SN_PROGEN_MASS: `yields`, or
+    the reference's 14-entry tuple padded with None to S (as dust_species_curve pads)."""
+    y = list(SN_YIELDS if yields is None else yields)
+    if yields is None:
+        y = y[:S] + [None] * (S - len(y))
+    if len(y) != S:
+        raise ValueError("yields must hold S = %d entries" % S)
+    out = []
+    for e in y:
+        if e is None:
+            out.append(None)
+            continue
+        e = np.array(e, dtype=np.float64)
+        if e.shape != (len(SN_PROGEN_MASS),):
+            raise ValueError("a yield entry holds %d values at SN_PROGEN_MASS" % len(SN_PROGEN_MASS))
+        out.append(e)
+    return out
+
+
+def _interp_linear(x, y, x_new):
+    """scipy.interpolate.interp1d(x, y, kind='linear')(x_new) with its default bounds_error: the same statements
+    (searchsorted, clip, slope = (y_hi - y_lo) / (x_hi - x_lo), slope (x_new - x_lo) + y_lo), so the same bits."""
+    if np.any(x_new < x[0]) or np.any(x_new > x[-1]):
+        raise ValueError("A value in x_new is outside the interpolation range [%g, %g] solar masses." % (x[0], x[-1]))
+    idx = np.searchsorted(x, x_new).clip(1, len(x) - 1).astype(int)
+    lo, hi = idx - 1, idx
+    x_lo, x_hi, y_lo, y_hi = x[lo], x[hi], y[lo], y[hi]
+    slope = (y_hi - y_lo) / (x_hi - x_lo)
+    return slope * (x_new - x_lo) + y_lo
+
+
+def supernova_explosion(mass, points, velocities, E_internal, supernova_pos, f_un, d_0=None, noise_dust=None, noise_gas=None,
+                        yields=None, full=False):
+    """nsc:820-882 -> the reference's 16-entry tuple (EXPLOSION_FIELDS) for the stars supernova_pos.  Kept as committed:
+    grsum, drsum and trsum run over ALL stars; dust_mass is uniform over all dust rows; a star sheds
+    int(dust_masses / (0.05 solar_mass)) dust rows and one gas row; stars_mass = 2 solar masses; new_eint_gas = E / 2;
+    star_comps is gas_comps.  d_0 defaults to the module's (drv:70).  The noise is drawn as the reference draws it,
+    np.random.normal(size=(n_dust, 3)) and then (n_sn, 3): under its seed the positions are its bits; noise_dust and
+    noise_gas (standard normal, of those shapes) replace the draws.  yields: sn_yield_table.  A progenitor outside
+    [0, 40] solar masses raises ValueError, as the reference's interp1d does.
+    Two readings are this module's: every dust row takes its OWN star's velocity (nsc:858-859 indexes with
+    the stale `position`: with two or more stars every dust row gets the last star's velocity, and their number is
+    wrong); and an event without a single dust row, where the reference raises in np.vstack, gives empty dust arrays.
+    The inputs are not modified.  full=True appends a dict: dust_len (the dust rows per star)."""
+    m, E = f64(mass), f64(E_internal)
+    pts, vel = f64(points), f64(velocities)
+    fun = f64(f_un)
+    sp = np.ascontiguousarray(np.asarray(supernova_pos, dtype=np.int64).reshape(-1))
+    n_sn, S = sp.shape[0], fun.shape[1]
+    d0 = globals()["d_0"] if d_0 is None else d_0
+    if d0 is None:
+        raise NameError("name 'd_0' is not defined (assign nsc.d_0 as sph/code_running.py:70 does)")
+    d0 = float(d0)
+    table = sn_yield_table(S, yields)
+    knots = np.array(SN_PROGEN_MASS)
+    gas_release = fun[sp]                                                        # nsc:823 (a copy)
+    grsum = np.sum(gas_release)
+    rel = m[sp] / solar_mass
+    dust_release = np.array([np.zeros(len(rel)) if y is None else _interp_linear(knots, y, rel) for y in table]).T     # nsc:826
+    drsum = np.sum(dust_release)
+    total_release = dust_release + gas_release
+    trsum = np.sum(total_release)
+    gas_release /= grsum
+    dust_release /= drsum
+    dust_masses = (m[sp] - SN_REMNANT_MASS * solar_mass) * drsum / trsum
+    gas_masses = (m[sp] - SN_REMNANT_MASS * solar_mass) * grsum / trsum
+    dust_len = np.array(dust_masses / (SN_DUST_ROW_MASS * solar_mass)).astype('int')
+    n_dust = int(np.sum(dust_len))
+    stars_mass = np.ones(n_sn) * 2 * solar_mass
+    if n_dust > 0:
+        dust_mass = np.ones(n_dust) * np.sum(dust_masses) / n_dust
+        noise = np.random.normal(size=(n_dust, 3)) if noise_dust is None else f64(noise_dust, (n_dust, 3))
+        dustpoints = np.vstack([pts[sp[t]] for t in range(n_sn) for _ in range(dust_len[t])]) + noise * d0
+        dustvels = np.vstack([vel[sp[t]] for t in range(n_sn) for _ in range(dust_len[t])])
+        dust_comps = np.array([dust_release[t] for t in range(n_sn) for _ in range(dust_len[t])])
+    else:
+        dust_mass = np.zeros(0)
+        dustpoints, dustvels, dust_comps = np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, S))
+    noise = np.random.normal(size=(n_sn, 3)) if noise_gas is None else f64(noise_gas, (n_sn, 3))
+    newpoints = pts[sp] + noise * d0
+    newvels = vel[sp]
+    out = (dust_comps, gas_release, gas_release, dust_mass, gas_masses, stars_mass, newpoints, newvels, np.zeros(n_sn),
+           np.ones(n_dust) * 2, np.zeros(n_sn), np.zeros(n_dust), E[sp] / 2., sp, dustpoints, dustvels)
+    return out + (dict(dust_len=dust_len),) if full else out
+
+
+def row_means(f_un, mu_specie=None, gamma=None):
+    """drv:393-394 -> (mu_array, gamma_array) = sum(f_un table, axis=1) / sum(f_un, axis=1)."""
+    fun = f64(f_un)
+    S = fun.shape[1]
+    mus, gam = chem_table(S, mu_specie, "mu_specie"), chem_table(S, gamma, "gamma")
+    tot = np.sum(fun, axis=1)
+    return np.sum(fun * mus, axis=1) / tot, np.sum(fun * gam, axis=1) / tot
+
+
+def supernova_insert(state, explosion, t_cmb=None, star_ages=None, sizes=None, d=None, m_0=None, mu_specie=None, gamma=None):
+    """drv:363-382 and drv:393-394 on arrays -> a new state dict; `state` (particle_type, E_internal, f_un, mass,
+    velocities, points, T) and `explosion` (supernova_explosion's tuple) are not modified.  In the driver's order: the
+    star rows rewritten (E_internal, f_un, mass), the dust rows and then the gas rows appended, T extended by zeros and
+    clamped as a whole (T[T < t_cmb] = t_cmb; a NaN stays), mu_array and gamma_array formed again for every row.
+    star_ages is extended by -2 when given; sizes by the rule of drv:373-378 when sizes, d and m_0 are given.  total_accel
+    keeps its old shape: the caller sees the mismatch the driver sees (drv:482-485).  With mean_grain_mass and mean_cross
+    in the state, the rewritten and the new rows get theirs from grain_mass() and sigma_effective()."""
+    (dust_comps, gas_comps, star_comps, dust_mass, gas_mass, stars_mass, newpoints, newvels, newgastype, newdusttype, new_eint_stars,
+     new_eint_dust, new_eint_gas, sp, dustpoints, dustvels) = tuple(explosion)[:16]          # (full=True's dict is not read)
+    sp = np.asarray(sp, dtype=np.int64).reshape(-1)
+    tc = float(globals()["t_cmb"] if t_cmb is None else t_cmb)
+    pt = np.concatenate((f64(state["particle_type"]), newdusttype, newgastype))           # drv:363
+    E, fun, m = np.array(f64(state["E_internal"])), np.array(f64(state["f_un"])), np.array(f64(state["mass"]))
+    n_old = m.shape[0]
+    E[sp] = new_eint_stars
+    fun[sp] = star_comps
+    m[sp] = stars_mass
+    E = np.concatenate((E, new_eint_dust, new_eint_gas))
+    m = np.concatenate((m, dust_mass, gas_mass))
+    fun = np.vstack([fun, dust_comps, gas_comps])
+    vel = np.concatenate((f64(state["velocities"]), dustvels, newvels))
+    pts = np.vstack([f64(state["points"]), dustpoints, newpoints])
+    n = pts.shape[0]
+    out = dict(state)
+    if star_ages is not None:
+        out["star_ages"] = np.concatenate((star_ages, np.ones(len(dustpoints)) * (-2), np.ones(len(sp)) * (-2)))
+    if sizes is not None and d is not None and m_0 is not None:
+        sz = np.zeros(n)
+        sz[:n_old] = sizes
+        new = (pt == 0) & (sz == 0)
+        sz[new] = (m[new] / m_0) ** (1. / 3.) * d
+        sz[(pt == 1) & (sz == 0)] = d / 10000.
+        sz[(pt == 2) & (sz == 0)] = d
+        out["sizes"] = sz
+    T = np.zeros(n)
+    T[:n_old] += f64(state["T"])
+    T[T < tc] = tc
+    mu, gam = row_means(fun, mu_specie, gamma)
+    out.update(particle_type=pt, E_internal=E, f_un=fun, mass=m, velocities=vel, points=pts, T=T, mu_array=mu, gamma_array=gam)
+    if state.get("mean_grain_mass") is not None and state.get("mean_cross") is not None:
+        touched = np.concatenate((sp, np.arange(n_old, n)))
+        mgm = np.concatenate((f64(state["mean_grain_mass"]), np.zeros(n - n_old)))
+        mcs = np.concatenate((f64(state["mean_cross"]), np.zeros(n - n_old)))
+        mgm[touched] = np.sum(grain_mass() * fun[touched], axis=1)
+        mcs[touched] = np.sum(sigma_effective() * fun[touched], axis=1)
+        out["mean_grain_mass"], out["mean_cross"] = mgm, mcs
+    return out

@@ -42,6 +42,44 @@ int sphx_ensure(sphx_ctx* ctx, DevBuf& b, size_t bytes, hipStream_t in_use_on) {
     return SPHX_OK;
 }
 
+// The keeping variant (sphx_insert.hip: the state grows and its rows stay): the new allocation is made first, the first
+// `keep` bytes are copied device to device on the context's stream, and the outgrown allocation is handed to `retired` -
+// the caller frees those (sphx_free_retired) once the stream has passed the copies.  Inside the head-room nothing happens.
+int sphx_ensure_keep(sphx_ctx* ctx, DevBuf& b, size_t bytes, size_t keep, std::vector<void*>& retired, int* grown) {
+    if (bytes == 0) bytes = 8;
+    if (b.cap >= bytes) return SPHX_OK;
+    const size_t want = bytes + bytes / 8 + 256;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess) return sphx_set_err(ctx, SPHX_E_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+    if (b.p && keep > 0) {
+        if (keep > b.cap) keep = b.cap;
+        e = hipMemcpyAsync(p, b.p, keep, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return sphx_set_err(ctx, SPHX_E_HIP, "sphx_ensure_keep: copy failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (b.p) {
+        for (size_t q = 0; q < ctx->allocs.size(); ++q)
+            if (ctx->allocs[q] == b.p) { ctx->allocs[q] = ctx->allocs.back(); ctx->allocs.pop_back(); break; }
+        retired.push_back(b.p);
+    }
+    b.p = p;
+    b.cap = want;
+    ctx->allocs.push_back(p);
+    if (grown) ++*grown;
+    return SPHX_OK;
+}
+int sphx_free_retired(sphx_ctx* ctx, std::vector<void*>& retired) {
+    if (retired.empty()) return SPHX_OK;
+    hipError_t e = hipStreamSynchronize(ctx->stream);          // the copies out of them are done
+    for (void* p : retired) (void)hipFree(p);
+    retired.clear();
+    if (e != hipSuccess) return sphx_set_err(ctx, SPHX_E_HIP, "sphx_free_retired: %s", hipGetErrorString(e));
+    return SPHX_OK;
+}
+
 static void default_constants(sphx_constants* c) {
     c->k_B = 1.380649e-23;
     c->amu = 1.66053906892e-27;
@@ -176,7 +214,7 @@ extern "C" void sphx_destroy(sphx_ctx* ctx) {
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (int i = 0; i < 10; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t, &ctx->chem_t, &ctx->phase_t, &ctx->radphase_t, &ctx->radstate_t})
+    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t, &ctx->chem_t, &ctx->phase_t, &ctx->radphase_t, &ctx->radstate_t, &ctx->ins_t})
         for (int i = 0; i < 6; ++i)
             if (t->ev[i]) (void)hipEventDestroy(t->ev[i]);
     for (int i = 0; i <= SPHX_SN_STAGES; ++i)
@@ -286,6 +324,7 @@ extern "C" int sphx_chem_last_timing(sphx_ctx* ctx, double ms[5]) { return last_
 extern "C" int sphx_phase_last_timing(sphx_ctx* ctx, double ms[5]) { return last_timing(ctx, &sphx_ctx::phase_t, ms); }
 extern "C" int sphx_state_radphase_last_timing(sphx_ctx* ctx, double ms[5]) { return last_timing(ctx, &sphx_ctx::radstate_t, ms); }
 extern "C" int sphx_radphase_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::radphase_t, ms); }
+extern "C" int sphx_insert_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::ins_t, ms); }
 
 // =============================================================================================
 // nsc.neighbors                                                                nsc:541-552
@@ -475,6 +514,8 @@ extern "C" int sphx_state_upload(sphx_ctx* ctx, int64_t n, int s, const double* 
     ctx->step_count = 0;
     ctx->tprev_valid = false;
     ctx->dt_last = 0.0;
+    ctx->no_old_once = false;
+    ctx->sums_stale = false;
     return SPHX_OK;
 }
 
@@ -584,7 +625,9 @@ static int step_cell_hint(sphx_ctx* ctx, int64_t n, double* cell_hint) {
 
 // Phase 1: the neighbour list of this step in ctx->nbr and the radii in st.hprev - refreshed from the Verlet lists, or by
 // grid build, blob order, permutation of the state and search.  Records ev[1] in front of the search.
-static int step_search(sphx_ctx* ctx, int k, double dist, hipEvent_t* ev) {
+// fresh: the search of a state that has just grown (sphx_state_insert_rows, drv:386) - no radius is handed to it, as none
+// is to the first step's.
+static int step_search(sphx_ctx* ctx, int k, double dist, hipEvent_t* ev, bool fresh = false) {
     const int64_t n = ctx->n;
     // drv:233-238: applied by the grid build's first pass over the particles (sphx_grid.hip); the Verlet path looks at
     // the positions before any grid is built, so it clamps here
@@ -627,8 +670,8 @@ static int step_search(sphx_ctx* ctx, int k, double dist, hipEvent_t* ev) {
     KnnIn in;
     in.xs = r.x.as<double>(); in.ys = r.y.as<double>(); in.zs = r.z.as<double>();
     in.id = r.id.as<int>(); in.inv = ctx->inv.as<int>();
-    in.rsearch = r.hprev.as<double>();
-    in.hinted = ctx->step_count > 0 && !ctx->use_verlet;     // hprev holds the previous step's radii
+    in.rsearch = fresh ? nullptr : r.hprev.as<double>();
+    in.hinted = !fresh && ctx->step_count > 0 && !ctx->use_verlet;     // hprev holds the previous step's radii
     in.lag_external = true;              // (step_cell_hint has handed the previous search's counters over)
     in.rscale = ctx->rscale;
     in.rbound = dist;
@@ -749,7 +792,8 @@ static int step_sums(sphx_ctx* ctx, int k, hipEvent_t* ev, hipEvent_t search_end
 }
 
 // call_first / call_last: the first / last step of this sphx_step call (they carry the call's start and end events)
-static int one_step(sphx_ctx* ctx, int k, double dist, int first, double fixed_dt, bool call_first, bool call_last) {
+// no_old: drv:484-485, the step behind an insertion (the previous acceleration has another shape: dv = a dt)
+static int one_step(sphx_ctx* ctx, int k, double dist, int first, double fixed_dt, bool call_first, bool call_last, int no_old) {
     const int64_t n = ctx->n;
     const int ring = (int)(ctx->step_count % 3);
     hipEvent_t* ev = ctx->evring[ring];
@@ -790,9 +834,31 @@ static int one_step(sphx_ctx* ctx, int k, double dist, int first, double fixed_d
     if (detail) HIPCHK(hipEventRecord(ev[8], ctx->stream));
     // (dt by drv:222-229 inside the update kernel; the crossing-time vote is reset by the next step's first kernel, or
     //  primed by its pass 2 when that grid build is not the fused one)
-    SPHX_TRY(sphx_integrate(ctx, n, 1, first, fixed_dt));
+    SPHX_TRY(sphx_integrate(ctx, n, 1, first, fixed_dt, no_old));
+    ctx->sums_stale = false;
     if (rec7) HIPCHK(hipEventRecord(ev[7], ctx->stream));
     ctx->step_count++;
+    return SPHX_OK;
+}
+
+// drv:386: the search behind an insertion, on the grown state (ctx->n rows), as the first step's search runs - and what
+// sphx_step leaves behind its last search: the list marked the step's own (the phases read it next, as the driver's
+// drv:399-435 read the list of :386), and the sum of h with the search's counters copied out, so that the next step
+// sizes its cells and its list-mode grid from THIS search over ctx->n rows, not from the one before the insertion.
+int sphx_step_research(sphx_ctx* ctx, int k, double dist) {
+    if (!(dist > 0.0) || !isfinite(dist)) dist = 0.0;
+    ctx->k = k;
+    ctx->map_perm = nullptr;
+    ctx->qorder = nullptr;
+    ctx->blob_lists = false;
+    ctx->blob_split_valid = false;
+    ctx->pass_part = 0;
+    ctx->nbr_api_valid = false;
+    sphx_step_list_drop(ctx);
+    SPHX_TRY(step_search(ctx, k, dist, ctx->ev, /*fresh=*/true));
+    HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
+    SPHX_TRY(step_h_sums_out(ctx, ctx->n, ctx->st.hprev.as<double>(), ctx->stream));
+    ctx->step_list_valid = true; ctx->step_qorder = ctx->qorder; ctx->step_list_n = ctx->n; ctx->step_list_k = k;
     return SPHX_OK;
 }
 
@@ -852,7 +918,9 @@ extern "C" int sphx_step(sphx_ctx* ctx, int nsteps, int k, double dist, int firs
         // each step sizes the grid and takes the search's decisions from the lagged read-backs
         const int ring = (int)(ctx->step_count % 3);
         SPHX_TRY(collect_stats(ctx, ring));            // (the step launched three steps ago, if still uncollected)
-        SPHX_TRY(one_step(ctx, k, dist, first && it == 0, fixed_dt, false, false));
+        const int no_old = ctx->no_old_once ? 1 : 0;       // (one shot: set by sphx_state_insert_rows)
+        ctx->no_old_once = false;
+        SPHX_TRY(one_step(ctx, k, dist, first && it == 0, fixed_dt, false, false, no_old));
         ctx->ev_pending |= 1u << ring;
         SPHX_TRY(collect_stats(ctx, (ring + 1) % 3));  // two steps ago: finished long since, no wait
     }
@@ -898,7 +966,7 @@ extern "C" int sphx_state_download(sphx_ctx* ctx, double* pos, double* vel, doub
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     struct V1 { double* host; const double* dev; };
-    const bool stepped = ctx->step_count > 0;
+    const bool stepped = ctx->step_count > 0 && !ctx->sums_stale;     // (an insertion since: "not stepped yet" for them)
     V1 v1[] = {{E_internal, s.E.as<double>()}, {T, s.T.as<double>()}, {sizes, s.hprev.as<double>()},
                {rho, stepped ? ctx->rho.as<double>() : nullptr},
                {nden, stepped ? ctx->nden.as<double>() : nullptr},
@@ -989,7 +1057,7 @@ __global__ __launch_bounds__(256) void scatter_species_major(int n, int S, const
 }
 extern "C" int sphx_state_download_species(sphx_ctx* ctx, double* F, double* Z, double* agb_dust) {
     if (!ctx) return SPHX_E_ARG;
-    if (!ctx->has_state || ctx->s < 1 || !ctx->fun_id.p || ctx->step_count < 1)
+    if (!ctx->has_state || ctx->s < 1 || !ctx->fun_id.p || ctx->step_count < 1 || ctx->sums_stale)
         return sphx_set_err(ctx, SPHX_E_STATE, "sphx_state_download_species: no species pass has run (state without f_un, "
                                                  "or no step yet)");
     if ((Z || agb_dust) && !ctx->agb_on) return sphx_set_err(ctx, SPHX_E_STATE, "sphx_state_download_species: no AGB table set");

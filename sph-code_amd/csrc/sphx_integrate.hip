@@ -360,7 +360,7 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegArgs a) {
     }
 }
 
-int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt, int first, double fixed_dt) {
+int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt, int first, double fixed_dt, int no_old) {
     StateArrays& s = ctx->st;
     IntegArgs a;
     a.ct_bits = fold_dt ? ctx->scal.as<u64>() + SC_CT_BITS : nullptr;
@@ -382,7 +382,7 @@ int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt, int first, double fixe
     a.G = ctx->loop_forms ? ctx->G.as<double>() : nullptr;
     a.dt = ctx->scal.as<double>() + SC_DT;
     a.m_h = ctx->cst.m_h; a.kB = ctx->cst.k_B;
-    a.no_old = 0;
+    a.no_old = no_old;
     a.counters = ctx->badc.as<u64>();
     hipLaunchKernelGGL(integrate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
@@ -403,7 +403,7 @@ extern "C" int sphx_state_download_pressure(sphx_ctx* ctx, double* pressure) {
     if (!ctx->has_state) return sphx_set_err(ctx, SPHX_E_STATE, "no state uploaded");
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t n = ctx->n;
-    if (ctx->step_count < 1 || !ctx->tprev_valid || !ctx->alt.T.p) { memset(pressure, 0, (size_t)n * sizeof(double)); return SPHX_OK; }
+    if (ctx->step_count < 1 || !ctx->tprev_valid || ctx->sums_stale || !ctx->alt.T.p) { memset(pressure, 0, (size_t)n * sizeof(double)); return SPHX_OK; }
     SPHX_TRY(sphx_ensure(ctx, ctx->out_a, (size_t)n * sizeof(double)));
     hipLaunchKernelGGL(pressure_by_id, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n,
                        ctx->st.id.as<int>(), ctx->nden.as<double>(), ctx->alt.T.as<double>(), ctx->cst.k_B, ctx->out_a.as<double>());

@@ -225,6 +225,10 @@ struct sphx_ctx {
     // k_B T_i of ONE instant at no cost to the step (sphx_state_download_pressure).  (st.T and alt.T are then the same two
     // buffers at the start of every step; the other arrays of st / alt swap roles every step.)
     bool tprev_valid = false;
+    // set by sphx_state_insert_rows (sphx_insert.hip): the next sphx_step's first step integrates with no previous
+    // acceleration (drv:484-485; then cleared), and rho / nden / vh / F of the last step have the old row count until then
+    bool no_old_once = false;
+    bool sums_stale = false;
     bool ct_primed = false;             // SC_CT_BITS holds "none yet" (left so by dt_kernel)
     bool recs_pw = false;         // the records sphx_prep built last feed the pairwise viscous pass (sphx_dev_visc_pairwise checks it)
     // the K-major list in `nbr` is the caller-order list of the last array-API call with this shape
@@ -457,6 +461,15 @@ struct sphx_ctx {
     hipEvent_t sn_ev[SPHX_SN_STAGES + 1] = {nullptr};
     double sn_ms[SPHX_SN_STAGES] = {0};
     int64_t sn_counts[SPHX_SN_NCOUNT] = {0};
+    // the insertion of rows into the resident state (sphx_insert.hip): staged inputs (doubles | ints), the located slots
+    // of sphx_state_download_rows and its gathered rows; events: [0] start, [1] inputs on the device, [2] grown, [3] the
+    // insert kernel, [4] the search (sphx_insert_last_timing); info: buffers reallocated, rows appended, rows rewritten,
+    // rows whose T the clamp moved
+    DevBuf ins_in, ins_rows;
+    std::vector<double> ins_host;       // the call's inputs packed on the host, uploaded from here
+    std::vector<int> ins_ids;           // ... and the sorted ids of the rows to rewrite
+    StageTimer ins_t;
+    int64_t ins_info[4] = {0, 0, 0, 0};
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
@@ -476,6 +489,12 @@ int sphx_set_err(sphx_ctx* ctx, int code, const char* fmt, ...);
 int sphx_ensure(sphx_ctx* ctx, DevBuf& b, size_t bytes, hipStream_t in_use_on);
 static inline int sphx_ensure(sphx_ctx* ctx, DevBuf& b, size_t bytes) { return sphx_ensure(ctx, b, bytes, ctx->stream); }
 void sphx_release(sphx_ctx* ctx, DevBuf& b);      // frees b's allocation now (the caller knows it idle)
+// The keeping variant: at least `bytes` in b with its first `keep` bytes as they were (copied on ctx->stream); an outgrown
+// allocation goes to `retired`, which sphx_free_retired frees behind the stream; *grown counts the reallocations.
+int sphx_ensure_keep(sphx_ctx* ctx, DevBuf& b, size_t bytes, size_t keep, std::vector<void*>& retired, int* grown);
+int sphx_free_retired(sphx_ctx* ctx, std::vector<void*>& retired);
+// drv:386 on the grown resident state (sphx_api.hip; called by sphx_state_insert_rows)
+int sphx_step_research(sphx_ctx* ctx, int k, double dist);
 
 #define HIPCHK(expr)                                                                         \
     do {                                                                                     \
@@ -856,7 +875,8 @@ int sphx_clamp(sphx_ctx* ctx, int64_t n, StateArrays& s);
 int sphx_permute_state(sphx_ctx* ctx, int64_t n, bool split, hipEvent_t after_first);
 int sphx_hsum(sphx_ctx* ctx, int64_t n, const double* h, hipStream_t stream);
 int sphx_compute_dt(sphx_ctx* ctx, int first, double fixed_dt);
-int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt = 0, int first = 0, double fixed_dt = 0.0);
+// no_old: drv:484-485 for every row (the step behind an insertion)
+int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt = 0, int first = 0, double fixed_dt = 0.0, int no_old = 0);
 int sphx_pass_drag(sphx_ctx* ctx, int64_t n, int k, const double* m, const double* ptype, const double* mgm,
                    const double* mcs);
 int sphx_aos_to_soa3(sphx_ctx* ctx, int64_t n, const double* aos, double* x, double* y, double* z);

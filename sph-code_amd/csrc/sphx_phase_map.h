@@ -33,3 +33,26 @@ SPHX_PHASE_HD inline long long sphx_phase_entry64(const int* out, int n, int npa
     const int v = out[sphx_phase_at(kk, npad, i)];
     return v >= 0 ? (long long)v : (long long)n;
 }
+
+#if defined(__HIPCC__)
+// np.sum over a contiguous row of s < 128 values term(0) .. term(s - 1), in NumPy's order (eight running sums over the
+// whole blocks of eight, combined pairwise, then the rest one by one): what Simulation forms mean_grain_mass and
+// mean_cross with
+template <class Term>
+__device__ __forceinline__ double phase_np_sum(int s, Term term) {
+    if (s < 8) {
+        double res = 0.0;
+        for (int t = 0; t < s; ++t) res += term(t);
+        return res;
+    }
+    double r0 = term(0), r1 = term(1), r2 = term(2), r3 = term(3), r4 = term(4), r5 = term(5), r6 = term(6), r7 = term(7);
+    int t = 8;
+    for (; t < s - (s % 8); t += 8) {
+        r0 += term(t); r1 += term(t + 1); r2 += term(t + 2); r3 += term(t + 3);
+        r4 += term(t + 4); r5 += term(t + 5); r6 += term(t + 6); r7 += term(t + 7);
+    }
+    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+    for (; t < s; ++t) res += term(t);
+    return res;
+}
+#endif

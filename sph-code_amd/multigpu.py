@@ -693,6 +693,11 @@ class DistributedSim:
     phase = "setup"                              # the section of step() this process is in (class-wide: one sim per process)
     DT_0, MAX_AGE = DT_0, MAX_AGE
 
+    def supernova_explosion(self, supernova_ids, d_0, t_cmb, **kw):
+        """The insertion of a supernova's particles (Simulation.supernova_explosion, drv:361-396) changes the number of
+        owned particles under the halo protocol: not built for the decomposed step."""
+        raise NotImplementedError("supernova_explosion is not available in the decomposed step (single-GPU Simulation only)")
+
     def __init__(self, state, lo, hi, backend, rank=0, world=1, device="cpu", comm_device=None,
                  halo_scale=1.15, skin_frac=0.15, need_grid=96, migrate_every=4, forms="hydro_update", d=None,
                  with_drag=False, with_species=False, agb=None, visc_mode=None, gravity=None, G=6.67430e-11, gravity_ws=1,

@@ -394,7 +394,7 @@ class Simulation:
         selected ids) as compat.supernova_impulse returns them), sel_count, true_mass, vel, counts (compat.SN_COUNTS).
         The bits are those of compat.supernova_impulses and compat.crossing_time on the downloaded state.  dt_0,
         mass_displaced and supernova_energy default to compat's.  An empty supernova_ids is a no-op: dt is None.  The
-        insertion of the new particles (drv:361-396) changes N and stays with the caller.  Needs one step; not with
+        insertion of the new particles (drv:361-396) changes N: supernova_explosion, below.  Needs one step; not with
         incremental=True."""
         import re
         from . import compat
@@ -438,6 +438,93 @@ class Simulation:
         c.check(c.lib.sphx_sn_last_timing(c.h, dp(ms)))
         return dict(zip(("keys", "bound", "compact", "sort", "walk", "kick"), ms.tolist()))
 
+    # ---- the explosion and the insertion of its particles (code_running.py:361-396) on the resident state: N grows -----
+    def download_rows(self, ids):
+        """The rows `ids` (particle indices of the uploaded state, each once) of the state as it is on the device ->
+        dict: points, velocities (n,3), mass, E_internal (n) and, with with_species=True, f_un (n,S)."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        nr, S = ids.shape[0], self.n_species
+        out = dict(points=np.empty((nr, 3)), velocities=np.empty((nr, 3)), mass=np.empty(nr), E_internal=np.empty(nr))
+        fu = None
+        if S > 0:
+            out["f_un"] = fu = np.empty((nr, S))
+        c = self.ctx
+        c.check(c.lib.sphx_state_download_rows(c.h, nr, _lib.ip(ids), dp(out["points"]), dp(out["velocities"]), dp(out["mass"]),
+                                               dp(out["E_internal"]), dp(fu)))
+        return out
+
+    def supernova_explosion(self, supernova_ids, d_0, t_cmb, noise_dust=None, noise_gas=None, yields=None, mu_specie=None,
+                            gamma=None, star_f_un=None):
+        """code_running.py:361-396 on the state as it is on the device: the rows of the stars supernova_ids come to the
+        host (download_rows), compat.supernova_explosion forms the new particles from those few rows, and
+        sphx_state_insert_rows (include/sphx.h) rewrites the star rows, appends the dust rows and then the gas rows, clamps
+        T at t_cmb, forms mu_array and gamma_array again, and runs the search of drv:386 on the grown state.  The state
+        itself stays on the device.  Afterwards self.n is N + n_dust + n_gas; download(), neighbors(),
+        download_composition(), download_drag(), dust_phase(), rad_phase(), sample() and rad_transfer() work on the grown
+        state at once (densities, num_densities, visc_heat and pressure are zeros until the next step); the next step()
+        integrates dv = a dt for every row, as the driver does behind an insertion (drv:482-485), the one after it
+        averages again.  self.first is left alone.
+        -> dict: n_dust, n_gas, new_ids (the caller ids of the new rows: dust, then gas), dust_len (dust rows per star),
+        explosion (compat.supernova_explosion's 16-tuple, supernova_pos being supernova_ids), info (buffers reallocated,
+        rows appended, rows rewritten, rows whose T the clamp moved).
+        The bits are those of compat.supernova_insert on the downloaded state.  noise_dust, noise_gas, yields: as
+        compat.supernova_explosion takes them; mu_specie, gamma: the tables of drv:393-394, by default the module's.  A
+        state without with_species=True needs the stars' composition rows as star_f_un (n_sn,S); mu_array and gamma_array
+        of its other old rows are then left as they are.  An empty supernova_ids is a no-op (None).  Needs one step; not
+        with incremental=True."""
+        from . import compat
+        ids = np.ascontiguousarray(np.asarray(supernova_ids, dtype=np.int64).reshape(-1))
+        n_sn = ids.shape[0]
+        if n_sn == 0:
+            return None
+        rows = self.download_rows(ids)
+        fu = rows.get("f_un")
+        if fu is None:
+            if star_f_un is None:
+                raise ValueError("a state without with_species=True needs star_f_un, the composition rows of the stars")
+            fu = f64(star_f_un)
+            if fu.ndim != 2 or fu.shape[0] != n_sn:
+                raise ValueError("star_f_un must be (n_sn, S)")
+        S = fu.shape[1]
+        ex = compat.supernova_explosion(rows["mass"], rows["points"], rows["velocities"], rows["E_internal"], np.arange(n_sn), fu,
+                                        d_0=d_0, noise_dust=noise_dust, noise_gas=noise_gas, yields=yields, full=True)
+        (dust_comps, gas_comps, star_comps, dust_mass, gas_mass, stars_mass, newpoints, newvels, newgastype, newdusttype,
+         new_eint_stars, new_eint_dust, new_eint_gas, _, dustpoints, dustvels, extra) = ex
+        cat = lambda a, b: np.ascontiguousarray(np.concatenate((a, b)), dtype=np.float64)
+        a_pos, a_vel = cat(dustpoints, newpoints), cat(dustvels, newvels)
+        a_m, a_pt, a_E, a_f = cat(dust_mass, gas_mass), cat(newdusttype, newgastype), cat(new_eint_dust, new_eint_gas), cat(dust_comps, gas_comps)
+        m_new = a_m.shape[0]
+        mus, gam = compat.chem_table(S, mu_specie, "mu_specie"), compat.chem_table(S, gamma, "gamma")
+        gm = se = None
+        if self._with_drag:
+            gm = np.ascontiguousarray(compat.grain_mass(), dtype=np.float64)
+            se = np.ascontiguousarray(compat.sigma_effective(), dtype=np.float64)
+            if gm.shape != (S,) or se.shape != (S,):
+                raise ValueError("with_drag: grain_mass and sigma_effective hold %d species, the state %d" % (gm.shape[0], S))
+        c = self.ctx
+        c.check(c.lib.sphx_state_insert_rows(c.h, S, n_sn, _lib.ip(ids), dp(f64(stars_mass, (n_sn,))), dp(f64(new_eint_stars, (n_sn,))),
+                                             dp(f64(star_comps, (n_sn, S))), m_new, dp(a_pos), dp(a_vel), dp(a_m), dp(a_pt), dp(a_E), dp(a_f),
+                                             float(t_cmb), dp(mus), dp(gam), dp(gm), dp(se), self.k, self.dist))
+        n_old = self.n
+        self.n = n_old + m_new
+        self._ptype = np.concatenate((self._ptype, a_pt))
+        if hasattr(self, "_n_gas"):
+            del self._n_gas
+        self._phase_ran = True           # (mass, f_un, mu_array and gamma_array on the device are no longer the caller's)
+        info = np.zeros(4, dtype=np.int64)
+        c.check(c.lib.sphx_insert_last_info(c.h, _lib.ip(info)))
+        return dict(n_dust=int(dust_mass.shape[0]), n_gas=int(gas_mass.shape[0]), new_ids=np.arange(n_old, n_old + m_new, dtype=np.int64),
+                    dust_len=np.array(extra["dust_len"]), explosion=ex[:13] + (ids,) + ex[14:16],
+                    info=dict(zip(("reallocated", "appended", "rewritten", "clamped"), (int(v) for v in info))))
+
+    def insert_timing(self):
+        """Device time of the stages of the last supernova_explosion()'s insertion from HIP events -> dict of ms: upload,
+        grow, insert, search."""
+        ms = np.zeros(4)
+        c = self.ctx
+        c.check(c.lib.sphx_insert_last_timing(c.h, dp(ms)))
+        return dict(zip(("upload", "grow", "insert", "search"), ms.tolist()))
+
     # ---- snapshot / restart and per-step diagnostics (SURVEY 8f-4; the reference only wrote summary
     # statistics at the end of a run, sph/code_running.py:670, and printed the mass-weighted net
     # accelerations every step, sph/code_running.py:465-468) ----------------------------------------
@@ -455,6 +542,8 @@ class Simulation:
             out["f_un"] = np.asarray(state["f_un"], dtype=np.float64)
         if self._phase_ran:
             out.update(self.download_composition())
+        if self._ptype.shape[0] != out["particle_type"].shape[0]:      # (a supernova_explosion has appended rows since)
+            out["particle_type"] = self._ptype.copy()
         np.savez(path, **out)
 
     @classmethod
