@@ -102,6 +102,10 @@ typedef struct sphx_stats {
     int64_t visc_launches_skipped; /* pass 3 (fused single-GPU step, LDS passes): launches that returned at once because pass 2
                                       had marked no blob for them - it writes the NaN rows itself and marks the blobs with
                                       other rows; the blobs pass 3 does not walk count in visc_blobs_settled           */
+    int64_t update_split_steps; /* steps (since sphx_reset_stats) whose leapfrog/energy update split its rows in two classes
+                                   by a byte that pass 2 left: rows whose viscous sums are settled (NaN) - neither stored
+                                   by a pass nor loaded by the update - and the rows pass 3 sums (fused single-GPU step,
+                                   LDS passes, neither drag nor gravity); counted on the host                          */
 } sphx_stats;
 
 /* ---- context ----------------------------------------------------------------------- */

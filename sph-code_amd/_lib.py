@@ -29,7 +29,7 @@ class SphxStats(C.Structure):
                 ("outlier_levels", C.c_int64), ("bad_accel", C.c_int64), ("bad_energy", C.c_int64), ("bad_state", C.c_int64),
                 ("bad_h", C.c_int64), ("search_steps", C.c_int64), ("tie_entries", C.c_int64), ("tie_capacity", C.c_int64),
                 ("visc_blobs_settled", C.c_int64), ("pi_waves_settled", C.c_int64),
-                ("visc_launches_skipped", C.c_int64)]
+                ("visc_launches_skipped", C.c_int64), ("update_split_steps", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

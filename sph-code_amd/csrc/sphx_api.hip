@@ -516,6 +516,7 @@ extern "C" int sphx_state_upload(sphx_ctx* ctx, int64_t n, int s, const double* 
     ctx->dt_last = 0.0;
     ctx->no_old_once = false;
     ctx->sums_stale = false;
+    ctx->visc_rows_unfilled = false;
     return SPHX_OK;
 }
 
@@ -713,8 +714,11 @@ static int step_h_sums_out(sphx_ctx* ctx, int64_t n, const double* h, hipStream_
 }
 
 // Phase 2: the sums of hydro_update (or the loop forms) on the list of phase 1.  search_end: the event recorded behind the search.
-static int step_sums(sphx_ctx* ctx, int k, hipEvent_t* ev, hipEvent_t search_end, bool detail) {
+// *rows_by_byte: pass 2 left every row's class in ctx->row_settled and stored no NaNs for the settled rows - the update
+// that follows has to take its rows by those bytes (sphx_update_rows.h)
+static int step_sums(sphx_ctx* ctx, int k, hipEvent_t* ev, hipEvent_t search_end, bool detail, bool* rows_by_byte) {
     const int64_t n = ctx->n;
+    *rows_by_byte = false;
     StateArrays& s = ctx->st;
     const bool pairwise = ctx->visc_mode == 1 && !ctx->loop_forms;     // (what sphx_prep builds RecBC.Bw for)
     // the record build (bandwidth-bound) does not depend on the list dedup (latency-bound): side by side on the side
@@ -776,12 +780,17 @@ static int step_sums(sphx_ctx* ctx, int k, hipEvent_t* ev, hipEvent_t search_end
         } else {
             // the LDS passes on all blobs of one GPU: pass 2 settles pass 3's NaN rows and marks the blobs with others (sphx_blob.hip)
             const bool hand_visc = sphx_blob_can_hand_visc(ctx, n);
+            // ... and where nothing but pass 3 stands between pass 2 and the update (neither drag nor gravity), a settled
+            // row's four NaNs are neither stored nor loaded: pass 2 leaves each row's class in a byte, and the update
+            // takes a settled row's viscous sums as the constant they are (sphx_update_rows.h)
+            const bool by_byte = hand_visc && !ctx->drag && !ctx->gravity;
+            *rows_by_byte = by_byte;
             if (hand_visc) {                       // (pass 2 writes them: sized here, not in front of pass 3)
                 SPHX_TRY(sphx_ensure(ctx, ctx->va, (size_t)n * 3 * sizeof(double)));
                 SPHX_TRY(sphx_ensure(ctx, ctx->vh, (size_t)n * sizeof(double)));
-                SPHX_TRY(sphx_blob_size_marks(ctx, n));
+                SPHX_TRY(sphx_blob_size_marks(ctx, n, by_byte));
             }
-            SPHX_TRY(sphx_pass_pi(ctx, n, k, s.hprev.as<double>(), s.ptype.as<double>(), hand_visc));
+            SPHX_TRY(sphx_pass_pi(ctx, n, k, s.hprev.as<double>(), s.ptype.as<double>(), hand_visc, by_byte));
             if (detail) HIPCHK(hipEventRecord(ev[5], ctx->stream));
             SPHX_TRY(sphx_pass_visc(ctx, n, k, s.m.as<double>(), hand_visc));
         }
@@ -816,7 +825,8 @@ static int one_step(sphx_ctx* ctx, int k, double dist, int first, double fixed_d
     if (rec0) HIPCHK(hipEventRecord(ev[0], ctx->stream));
     SPHX_TRY(step_search(ctx, k, dist, ev));
     HIPCHK(hipEventRecord(ev[2], ctx->stream));
-    SPHX_TRY(step_sums(ctx, k, ev, ev[2], detail));
+    bool rows_by_byte = false;
+    SPHX_TRY(step_sums(ctx, k, ev, ev[2], detail, &rows_by_byte));
     if (detail) HIPCHK(hipEventRecord(ev[6], ctx->stream));
     StateArrays& s = ctx->st;
     if (ctx->gravity) {                          // drv:448-449; softening = median(h), nsc:358
@@ -834,7 +844,9 @@ static int one_step(sphx_ctx* ctx, int k, double dist, int first, double fixed_d
     if (detail) HIPCHK(hipEventRecord(ev[8], ctx->stream));
     // (dt by drv:222-229 inside the update kernel; the crossing-time vote is reset by the next step's first kernel, or
     //  primed by its pass 2 when that grid build is not the fused one)
-    SPHX_TRY(sphx_integrate(ctx, n, 1, first, fixed_dt, no_old));
+    SPHX_TRY(sphx_integrate(ctx, n, 1, first, fixed_dt, no_old, rows_by_byte));
+    if (rows_by_byte) ctx->stats.update_split_steps++;
+    ctx->visc_rows_unfilled = rows_by_byte;            // (sphx_state_download fills ctx->va, ctx->vh in before it reads)
     ctx->sums_stale = false;
     if (rec7) HIPCHK(hipEventRecord(ev[7], ctx->stream));
     ctx->step_count++;
@@ -967,6 +979,8 @@ extern "C" int sphx_state_download(sphx_ctx* ctx, double* pos, double* vel, doub
     }
     struct V1 { double* host; const double* dev; };
     const bool stepped = ctx->step_count > 0 && !ctx->sums_stale;     // (an insertion since: "not stepped yet" for them)
+    // (an update by bytes read no viscous sums for its settled rows, and pass 2 stored none: their NaNs now, once)
+    if (stepped && visc_heat) SPHX_TRY(sphx_settled_visc_fill(ctx, n));
     V1 v1[] = {{E_internal, s.E.as<double>()}, {T, s.T.as<double>()}, {sizes, s.hprev.as<double>()},
                {rho, stepped ? ctx->rho.as<double>() : nullptr},
                {nden, stepped ? ctx->nden.as<double>() : nullptr},

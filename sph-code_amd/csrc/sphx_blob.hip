@@ -296,7 +296,9 @@ __device__ __forceinline__ void visc_settle_store(double* va, double* vh, int o)
 // ---- pass 2: Pi_i, crossing time             nsc:639-649, nsc:776-786 --------------------------
 // Handing on (marks != nullptr; the fused single-GPU step): m Pi_i, which pass 3's vote on "settled" turns on, is in a
 // register at finish.  A settled row gets pass 3's NaNs here; a blob that holds a row that is not is marked, and pass 3
-// walks the marked blobs alone (blob_visc_kernel).
+// walks the marked blobs alone (blob_visc_kernel).  Where the step's update takes its rows by class (row_settled != nullptr;
+// sphx_update_rows.h) the row's class goes out as one byte in place of the four NaNs - for every row that writes, in
+// every launch, so that nothing has to be reset: the update of a settled row reads none of pass 3's outputs.
 struct PiPass {
     typedef RecB Rec;
     struct Sums { double pi; };
@@ -311,6 +313,7 @@ struct PiPass {
     double *Pi, *BwOut;
     double *va, *vh;                                        // pass 3's outputs and, per blob, whether it has rows left to sum
     unsigned char* marks;                                   // (nullptr: nothing is handed on)
+    unsigned char* row_settled;                             // (nullptr: the settled rows get their NaNs)
     __device__ __forceinline__ bool hands_on() const { return marks != nullptr; }
     __device__ __forceinline__ void hand_on(int b, bool any_live) const { marks[b] = any_live ? 1 : 0; }
     struct Row { Q4 r0, rv; double rho_i, cs_i, ms_i, h_i; };
@@ -350,7 +353,8 @@ struct PiPass {
         if (BwOut) BwOut[o] = bw;
         if (marks) {                                                        // (uniform: an argument; the row writes)
             live = !sphx_row_settled(bw, has_first, true);
-            if (!live) visc_settle_store(va, vh, o);
+            if (row_settled) row_settled[o] = live ? 0 : 1;                 // (uniform as well)
+            else if (!live) visc_settle_store(va, vh, o);
         }
         return (r.ms_i > 0.0) ? ct_vote_bits(r.h_i, maxrel) : SPHX_CT_NONE; // gas only     nsc:782
     }
@@ -358,8 +362,8 @@ struct PiPass {
 BLOB_KERNEL blob_pi_kernel(BLOB_COMMON, const int* __restrict__ omap, int n_active, const RecB* __restrict__ recb,
                            const double* __restrict__ rho_s, const RecSelf* __restrict__ selfr, RecBC* bc, double* Pi,
                            double* BwOut, u64* ct_bits, BlobSel sel, u64* counts, double* va, double* vh,
-                           unsigned char* marks) {
-    blob_pass(PiPass{recb, rho_s, selfr, bc, Pi, BwOut, va, vh, marks}, n, npad, k, nblk, nbr, slot16, uniq, qorder, 0, omap,
+                           unsigned char* marks, unsigned char* row_settled) {
+    blob_pass(PiPass{recb, rho_s, selfr, bc, Pi, BwOut, va, vh, marks, row_settled}, n, npad, k, nblk, nbr, slot16, uniq, qorder, 0, omap,
               n_active, ct_bits, sel, counts);
 }
 
@@ -933,18 +937,21 @@ bool sphx_blob_can_hand_visc(sphx_ctx* ctx, int64_t n) {
     const int nblk = (int)((sphx_pad64(n) + BLOB_P - 1) / BLOB_P);
     return nblk <= BLOB_OWN_MAX * sphx_blob_grid(ctx, nblk);
 }
-int sphx_blob_size_marks(sphx_ctx* ctx, int64_t n) {            // one byte per blob, read in 16-B pieces
+int sphx_blob_size_marks(sphx_ctx* ctx, int64_t n, bool row_bytes) {            // one byte per blob, read in 16-B pieces
     const size_t nblk = (size_t)((sphx_pad64(n) + BLOB_P - 1) / BLOB_P);
+    if (row_bytes) SPHX_TRY(sphx_ensure(ctx, ctx->row_settled, (size_t)n));       // ... and one per row (the update by bytes)
     return sphx_ensure(ctx, ctx->visc_live, (nblk + 15) / 16 * 16);
 }
 
 // hand_on: pass 2 settles pass 3's rows and marks the blobs with others (ctx->va, ctx->vh, ctx->visc_live are sized)
-int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits, bool hand_on) {
+// row_bytes (with hand_on): the rows' classes into ctx->row_settled instead of the settled rows' NaNs
+int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits, bool hand_on, bool row_bytes) {
     return blob_launch(ctx, blob_pi_kernel, PiPass::PER_SLOT, 0, n, k, ctx->map_perm, blob_n_active(ctx, n), ctx->recv.as<RecB>(),
                        ctx->rho_s.as<double>(), ctx->self_s.as<RecSelf>(), ctx->bc_s.as<RecBC>(), ctx->Pi.as<double>(),
                        ctx->map_perm ? ctx->Bw.as<double>() : nullptr, ct_bits, sphx_blob_sel(ctx, ctx->pass_part),
                        ctx->scal.as<u64>() + SC_SETTLED, hand_on ? ctx->va.as<double>() : nullptr,
-                       hand_on ? ctx->vh.as<double>() : nullptr, hand_on ? ctx->visc_live.as<unsigned char>() : nullptr);
+                       hand_on ? ctx->vh.as<double>() : nullptr, hand_on ? ctx->visc_live.as<unsigned char>() : nullptr,
+                       hand_on && row_bytes ? ctx->row_settled.as<unsigned char>() : nullptr);
 }
 
 // handed: the pass 2 before it ran with hand_on

@@ -7,6 +7,7 @@
 #include <float.h>
 
 #include "sphx_leapfrog.h"
+#include "sphx_update_rows.h"
 #define nan_to_num sphx_nan_to_num
 
 // ---- drv:233-238: clamp |x| <= 1e11 AU, nan_to_num(x), nan_to_num(v) -----------------------
@@ -293,6 +294,9 @@ struct IntegArgs {
     int first;
     double fixed_dt, dt_0, max_age;
     u64* counters;                                     // failure counters (BAD_*); nullptr: not counted
+    // pass 2's byte per row (sphx_update_rows.h): a row whose byte is set takes va = vh = NaN without loading them.
+    // nullptr: no bytes, every row loads
+    const unsigned char* row_settled;
 };
 __global__ __launch_bounds__(256) void integrate_kernel(IntegArgs a) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -306,10 +310,13 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegArgs a) {
             const double ct = sphx_ct_value(b == SPHX_CT_NONE, __longlong_as_double((long long)b), a.dt_0);   // nsc:783-786
             dt = sphx_dt_rule(ct, a.first, a.dt_0, a.max_age);                                                  // drv:223-229
         }
-        if (i == 0) *a.dt_out = dt;
+        if (sphx_update_writes_dt(i)) *a.dt_out = dt;
     } else {
         dt = *a.dt;
     }
+    // a settled row's viscous sums are NaN (sphx_settled.h): the value, not a load of it, goes through the expressions below
+    const bool visc_in = sphx_update_loads_visc(a.row_settled != nullptr, a.row_settled ? a.row_settled[i] : 0);
+    const double settled_visc = __builtin_nan("");
     const double g = (a.ptype[i] == 0.0) ? 1.0 : 0.0;
     const double v[3] = {a.vx[i], a.vy[i], a.vz[i]};
     double pa[3], vis[3];
@@ -319,10 +326,10 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegArgs a) {
         if (a.G) {                                            // loop forms carry the physical sign themselves
             const double praw = a.G[3 * (size_t)i + c] / a.rho[i] * g;
             pa[c] = nan_to_num(praw);                                       // drv:460
-            vis[c] = a.va[3 * (size_t)i + c];                               // av[0], drv:473
+            vis[c] = visc_in ? a.va[3 * (size_t)i + c] : settled_visc;       // av[0], drv:473
             bad_acc = bad_acc || !sphx_finite(praw) || !sphx_finite(vis[c]);
         } else {
-            const double praw = -a.ha[3 * (size_t)i + c] * g, vraw = -a.va[3 * (size_t)i + c] * g;
+            const double praw = -a.ha[3 * (size_t)i + c] * g, vraw = -(visc_in ? a.va[3 * (size_t)i + c] : settled_visc) * g;
             pa[c] = nan_to_num(praw);                             // physical sign, drv:460
             vis[c] = nan_to_num(vraw);
             bad_acc = bad_acc || !sphx_finite(praw) || !sphx_finite(vraw);
@@ -340,12 +347,20 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) gr[c] = a.grav ? a.grav[3 * (size_t)i + c] : 0.0;
     old[0] = a.ax[i]; old[1] = a.ay[i]; old[2] = a.az[i];
-    sphx_leapfrog_update(dt, x, vv, vis, pa, a.grav ? gr : nullptr, a.no_old ? nullptr : old, tot);   // drv:475-486
+    // drv:475-486.  (The nullable arguments as constants at each call: behind a pointer chosen at run time the arrays
+    //  would live in scratch memory, 64 B per lane written and read back.)
+    if (a.grav) {
+        if (a.no_old) sphx_leapfrog_update(dt, x, vv, vis, pa, gr, nullptr, tot);
+        else sphx_leapfrog_update(dt, x, vv, vis, pa, gr, old, tot);
+    } else {
+        if (a.no_old) sphx_leapfrog_update(dt, x, vv, vis, pa, nullptr, nullptr, tot);
+        else sphx_leapfrog_update(dt, x, vv, vis, pa, nullptr, old, tot);
+    }
     a.x[i] = x[0]; a.y[i] = x[1]; a.z[i] = x[2];
     a.vx[i] = vv[0]; a.vy[i] = vv[1]; a.vz[i] = vv[2];
     a.ax[i] = tot[0]; a.ay[i] = tot[1]; a.az[i] = tot[2];
     double E = a.E[i], T;
-    const double heat = a.vh[i];
+    const double heat = visc_in ? a.vh[i] : settled_visc;
     const bool bad_en = !sphx_finite(E) || !sphx_finite(heat * dt);
     sphx_energy_update(dt, heat, a.mu[i], a.gam[i], a.m[i], a.m_h, a.kB, E, T);   // drv:490-491
     a.E[i] = E;
@@ -360,7 +375,8 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegArgs a) {
     }
 }
 
-int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt, int first, double fixed_dt, int no_old) {
+// by_byte: pass 2 left every row's class in ctx->row_settled and stored no NaNs for the settled ones (sphx_update_rows.h)
+int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt, int first, double fixed_dt, int no_old, bool by_byte) {
     StateArrays& s = ctx->st;
     IntegArgs a;
     a.ct_bits = fold_dt ? ctx->scal.as<u64>() + SC_CT_BITS : nullptr;
@@ -384,10 +400,30 @@ int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt, int first, double fixe
     a.m_h = ctx->cst.m_h; a.kB = ctx->cst.k_B;
     a.no_old = no_old;
     a.counters = ctx->badc.as<u64>();
+    a.row_settled = by_byte ? ctx->row_settled.as<const unsigned char>() : nullptr;
     hipLaunchKernelGGL(integrate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
     { DevBuf t = s.T; s.T = ctx->alt.T; ctx->alt.T = t; }       // st.T: the new temperatures; alt.T: those the sums read
     ctx->tprev_valid = true;
+    return SPHX_OK;
+}
+
+// What pass 3 holds for a settled row, into the rows of ctx->va, ctx->vh that nobody wrote (pass 2 left the byte, the
+// update loaded nothing): for the readers of ctx->vh behind the step (sphx_state_download)
+__global__ __launch_bounds__(256) void settled_visc_fill_kernel(int n, const unsigned char* __restrict__ row_settled,
+                                                                double* va, double* vh) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !row_settled[i]) return;
+    const double q = __builtin_nan("");
+    va[3 * (size_t)i + 0] = q; va[3 * (size_t)i + 1] = q; va[3 * (size_t)i + 2] = q;
+    vh[i] = q;
+}
+int sphx_settled_visc_fill(sphx_ctx* ctx, int64_t n) {
+    if (!ctx->visc_rows_unfilled) return SPHX_OK;
+    hipLaunchKernelGGL(settled_visc_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n,
+                       ctx->row_settled.as<const unsigned char>(), ctx->va.as<double>(), ctx->vh.as<double>());
+    HIPCHK(hipGetLastError());
+    ctx->visc_rows_unfilled = false;
     return SPHX_OK;
 }
 
@@ -526,6 +562,7 @@ extern "C" int sphx_leapfrog(sphx_ctx* ctx, int64_t n, double* points, double* v
     a.m_h = ctx->cst.m_h; a.kB = ctx->cst.k_B;
     a.no_old = old_accel ? 0 : 1;
     a.counters = nullptr;              // (an array call on the caller's arrays: its NaNs are the caller's to see)
+    a.row_settled = nullptr;
     hipLaunchKernelGGL(integrate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
     struct Out { double* host; double *a, *b, *c; } outs[] = {{points, x, y, z}, {velocities, vx, vy, vz}, {total_accel, ax, ay, az}};

@@ -374,6 +374,10 @@ struct sphx_ctx {
     // blob_split: int list[nblk] (interior blobs, then boundary blobs), then cnt[3] {interior, boundary, idle}
     DevBuf blob_class, blob_split;
     DevBuf visc_live;             // one byte per blob: pass 2 found a row that pass 3 has to sum (the fused step's hand-over)
+    // one byte per row: pass 2 found pass 3's result settled (1) or not (0) - the update's two classes of rows
+    // (sphx_update_rows.h); written for every row by every pass 2 that hands on to such an update
+    DevBuf row_settled;
+    bool visc_rows_unfilled = false;   // the last step's update took its rows by those bytes: ctx->va, ctx->vh hold nothing for its settled rows
     DevBuf rho, rhod, nden, G, Pi, Bw, va, vh, ha, F;
     DevBuf scal;                  // small device scalars: ct bits, dt, counters
     DevBuf cell_of, cell_start, cell_fill, perm, inv, scan_tmp, bbox_tmp;      // grid
@@ -668,7 +672,7 @@ int sphx_blob_translate(sphx_ctx* ctx, int64_t n, int k);
 int sphx_blob_density_species(sphx_ctx* ctx, int64_t n, int k, bool lean, int S, const double* fun, const int* row_of,
                               const double* m_sorted, double* F, double* Z, double* agb, int agb_on);
 int sphx_blob_density(sphx_ctx* ctx, int64_t n, int k, bool lean);
-int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits, bool hand_on);
+int sphx_blob_pi(sphx_ctx* ctx, int64_t n, int k, u64* ct_bits, bool hand_on, bool row_bytes);
 int sphx_blob_visc(sphx_ctx* ctx, int64_t n, int k, const double* m, bool handed);
 int sphx_blob_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m, u64* ct_bits);
 int sphx_blob_species(sphx_ctx* ctx, int64_t n, int k, int S, const double* fun, const int* row_of, const double* m_sorted, double* F,
@@ -777,8 +781,8 @@ int sphx_pass_density(sphx_ctx* ctx, int64_t n, int k, bool lean = false);      
 // hand_visc (both or neither; the fused single-GPU step with the LDS passes): pass 2 writes the rows of pass 3 that are
 // settled (sphx_settled.h) and marks the blobs that hold another; pass 3 walks those alone.  Ignored by the gather kernels.
 bool sphx_blob_can_hand_visc(sphx_ctx* ctx, int64_t n);
-int sphx_blob_size_marks(sphx_ctx* ctx, int64_t n);         // ctx->visc_live, which pass 2 then writes
-int sphx_pass_pi(sphx_ctx* ctx, int64_t n, int k, const double* h, const double* ptype, bool hand_visc = false);
+int sphx_blob_size_marks(sphx_ctx* ctx, int64_t n, bool row_bytes);    // ctx->visc_live (and ctx->row_settled), which pass 2 then writes
+int sphx_pass_pi(sphx_ctx* ctx, int64_t n, int k, const double* h, const double* ptype, bool hand_visc = false, bool row_bytes = false);
 int sphx_pass_visc(sphx_ctx* ctx, int64_t n, int k, const double* m, bool hand_visc = false);
 int sphx_pass_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m);   // passes 2 + 3 fused, visc_mode 1
 int sphx_pass_species(sphx_ctx* ctx, int64_t n, int k, int s, const double* fun, double* F);
@@ -876,7 +880,8 @@ int sphx_permute_state(sphx_ctx* ctx, int64_t n, bool split, hipEvent_t after_fi
 int sphx_hsum(sphx_ctx* ctx, int64_t n, const double* h, hipStream_t stream);
 int sphx_compute_dt(sphx_ctx* ctx, int first, double fixed_dt);
 // no_old: drv:484-485 for every row (the step behind an insertion)
-int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt = 0, int first = 0, double fixed_dt = 0.0, int no_old = 0);
+int sphx_integrate(sphx_ctx* ctx, int64_t n, int fold_dt = 0, int first = 0, double fixed_dt = 0.0, int no_old = 0, bool by_byte = false);
+int sphx_settled_visc_fill(sphx_ctx* ctx, int64_t n);      // NaN into the rows of ctx->va, ctx->vh that a step by bytes left unwritten
 int sphx_pass_drag(sphx_ctx* ctx, int64_t n, int k, const double* m, const double* ptype, const double* mgm,
                    const double* mcs);
 int sphx_aos_to_soa3(sphx_ctx* ctx, int64_t n, const double* aos, double* x, double* y, double* z);

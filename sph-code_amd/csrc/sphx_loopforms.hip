@@ -706,6 +706,7 @@ static int loop_pass1_launch(sphx_ctx* ctx, int64_t n, int k, double d, StateArr
 }
 // pass 2: h = each particle's OWN kNN radius (crossing time, nsc:782); an entry of 0 casts no vote
 static int loop_pass2_launch(sphx_ctx* ctx, int64_t n, int k, StateArrays& st, const double* h, u64* ct, int part = 0) {
+    ctx->visc_rows_unfilled = false;      // (ctx->va, ctx->vh are rewritten here, as in sphx_pass_visc)
     const int npad = (int)sphx_pad64(n);
     RecP1* p1 = ctx->lrec_a.as<RecP1>(); RecP2* p2 = ctx->lrec_v.as<RecP2>();
     if (ctx->qorder && ctx->blob_lists) {

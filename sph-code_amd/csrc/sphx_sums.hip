@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void pass_pi_kernel(int n, int npad, int k, co
     block_min_vote<256>(my_ct, ct_bits);
 }
 
-int sphx_pass_pi(sphx_ctx* ctx, int64_t n, int k, const double* h, const double* ptype, bool hand_visc) {
+int sphx_pass_pi(sphx_ctx* ctx, int64_t n, int k, const double* h, const double* ptype, bool hand_visc, bool row_bytes) {
     (void)ptype; (void)h;
     SPHX_TRY(sphx_ensure(ctx, ctx->Pi, (size_t)n * sizeof(double)));
     SPHX_TRY(sphx_ensure(ctx, ctx->Bw, (size_t)n * sizeof(double)));
@@ -243,7 +243,7 @@ int sphx_pass_pi(sphx_ctx* ctx, int64_t n, int k, const double* h, const double*
     // SPHX_CT_NONE = "none yet"; in the fused loop the previous step's dt_kernel left it so
     if (!ctx->ct_primed) SPHX_TRY(sphx_prime_ct(ctx, ct));
     ctx->ct_primed = false;
-    if (ctx->qorder && ctx->blob_lists) return sphx_blob_pi(ctx, n, k, ct, hand_visc);
+    if (ctx->qorder && ctx->blob_lists) return sphx_blob_pi(ctx, n, k, ct, hand_visc, row_bytes);
     hipLaunchKernelGGL(pass_pi_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
                        (int)n, (int)sphx_pad64(n), k, ctx->nbr.as<int>(), ctx->recv.as<RecB>(),
                        ctx->rho_s.as<double>(), ctx->self_s.as<RecSelf>(), ctx->bc_s.as<RecBC>(), ctx->qorder,
@@ -301,6 +301,7 @@ __global__ __launch_bounds__(256) void pass_visc_kernel(int n, int npad, int k, 
 int sphx_pass_visc(sphx_ctx* ctx, int64_t n, int k, const double* m, bool hand_visc) {
     SPHX_TRY(sphx_ensure(ctx, ctx->va, (size_t)n * 3 * sizeof(double)));
     SPHX_TRY(sphx_ensure(ctx, ctx->vh, (size_t)n * sizeof(double)));
+    ctx->visc_rows_unfilled = false;      // (rewritten here; a step whose update goes by bytes says so behind this, one_step)
     if (ctx->qorder && ctx->blob_lists) return sphx_blob_visc(ctx, n, k, m, hand_visc);
     hipLaunchKernelGGL(pass_visc_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
                        (int)n, (int)sphx_pad64(n), k, ctx->clip_grad, ctx->nbr.as<int>(), ctx->recv.as<RecB>(),
@@ -370,6 +371,7 @@ __global__ __launch_bounds__(256) void pass_visc_pw_kernel(int n, int npad, int 
 int sphx_pass_visc_pw(sphx_ctx* ctx, int64_t n, int k, const double* m) {
     SPHX_TRY(sphx_ensure(ctx, ctx->va, (size_t)n * 3 * sizeof(double)));
     SPHX_TRY(sphx_ensure(ctx, ctx->vh, (size_t)n * sizeof(double)));
+    ctx->visc_rows_unfilled = false;      // (rewritten here, as in sphx_pass_visc)
     u64* ct = ctx->scal.as<u64>() + SC_CT_BITS;
     // the crossing-time vote of pass 2 moves here, with its priming protocol
     if (!ctx->ct_primed) SPHX_TRY(sphx_prime_ct(ctx, ct));
