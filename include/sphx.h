@@ -722,6 +722,88 @@ int sphx_state_insert_rows(sphx_ctx* ctx, int s, int64_t n_rew, const int64_t* r
                            double dist);
 int sphx_insert_last_info(sphx_ctx* ctx, int64_t info[4]);
 int sphx_insert_last_timing(sphx_ctx* ctx, double ms[4]);
+/* ---- the adaptive length scale and sizes, the closing block of the time loop                    drv:493-540 ----- *
+ * The length scale, with v_max2 = 80000**2, qf = q / 100 = 90 / 100 as the caller's double, fill = 0.9:
+ *   vel_condition_i = (vx^2 + vy^2) + vz^2            np.sum(v**2, axis=1): NumPy's order over three columns   drv:493
+ *   dist_sq_i       = (x^2 + y^2) + z^2                                                                         drv:515
+ *   slow_i          = vel_condition_i < v_max2        (a NaN speed is not slow)                                 drv:518
+ *   M               = the number of slow rows                                                                   drv:521
+ *   max_dist        = np.percentile(dist_sq[slow], q), method linear:                                           drv:518
+ *                       vi = (M - 1) qf, lo = floor(vi), g = vi - lo; vi >= M - 1: lo = hi = M - 1, else hi = lo + 1
+ *                       a, b the order statistics of rank lo, hi; a + (b - a) g, and b - (b - a)(1 - g) where g >= 0.5
+ *                       NaN when any slow row's dist_sq is NaN
+ *   V_new = max_dist**(3./2.)                                                                                   drv:520
+ *   d     = (V_new / M / fill * n_int)**(1./3.)       n_int: N_INT_PER_PARTICLE                                 drv:521
+ * Not formed: the six coordinate percentiles of drv:495-504 and min_dist (drv:517), dead in the driver.
+ * The device produces M, n_nan and the two exact order statistics a, b (integer histograms over the keys' bits: the same
+ * bits on every run and in every row order); the lerp and the two pow calls run in host C in the order above, each
+ * operation separately rounded (sphx_length_scale_finish, which takes no
+ * context and needs no device).
+ * Ours, where the driver leaves it open:
+ *   1. M = 0: np.percentile raises IndexError; SPHX_E_ARG here, nothing written.
+ *   2. A NaN dist_sq among the slow rows: max_dist and d are NaN, as NumPy gives; the rows are counted (n_nan), a NaN
+ *      orders last (b, and a, may be NaN).  sphx_state_length_scale refuses to apply a NaN d.
+ * Outputs (each but d may be NULL): n_slow = M, n_nan, lo, a, b, max_dist, d.
+ * SPHX_E_ARG: a NULL required pointer, n < 1 or n >= 2^31 - 16, qf outside [0, 1], a NaN v_max2, n_int or fill, M = 0.
+ *
+ * The reverse counts and the adaptation:
+ *   exp_neighbor_count_i = the number of entries of the whole list equal to i                                drv:527-530
+ *   num_nontrivial_i     = the number of entries of row i's list inside [0, n)                               nsc:545
+ *   densities_0 given (the driver: it has n rows):                                                           drv:532-533
+ *     new_smoothing_i = (exp(nan_to_num(-(rho_i - rho0_i) / (3 rho_i))) * 2) / 2. + (cnt_i + nontriv_i - 1 < 2) * 0.1
+ *   densities_0 NULL (the driver: another length - the first pass, the pass behind an insertion):            drv:534-535
+ *     new_smoothing = 1.                                (no bonus either)
+ *   sizes[ptype == 0] = (new_smoothing * sizes)[ptype == 0]                                                  drv:536
+ *   sizes[(ptype == 0) & (sizes > d)] = d                                                                    drv:537
+ *   sizes[ptype == 2] = d_dust                          d_dust = d / raise_factor**(1./3.), formed by the caller   drv:538
+ *   densities_0 = densities                             the caller's (sphx_state_length_scale: kept)         drv:540
+ * nan_to_num is NumPy's (NaN -> 0, +-inf -> +-DBL_MAX); exp is the device library's double exp (within a few ulp of
+ * NumPy's); stars keep their size; a NaN size stays NaN (NaN > d is false).
+ * Ours: an entry outside [0, n) is ignored (the driver's np.unique would give an array of another length and fail on the
+ * broadcast) and counted; a row that nobody lists counts 0 (the driver's arrays would misalign; the step's lists hold
+ * every row itself).
+ * Outputs: sizes_out (n); rev_count_out, nontrivial_out int64[n], new_smoothing_out (n), each or NULL; counts
+ * int64[SPHX_SCALE_NCOUNT] or NULL: rows (of any type) with the bonus, gas rows capped at d, rows (of any type) whose
+ * nan_to_num changed something, missing entries.
+ * SPHX_E_ARG: a NULL required pointer, n < 1 or n >= 2^31 - 16, k < 1 or k > 64.
+ *
+ * sphx_state_length_scale: both on the state as the last sphx_step left it - the resident positions and velocities, the
+ * step's own list (sphx_state_download_neighbors), its radii as sizes, its densities (sphx_state_download's rho); nothing
+ * is gathered into the caller's order.  The bits are those of the two array calls on the downloaded state.  densities_0
+ * is kept on the device by particle id from one applied call to the next; sphx_state_upload and sphx_state_insert_rows
+ * drop it, and the next call then takes the new_smoothing = 1. branch (as drv:532 does behind drv:368); so does a call
+ * behind an insertion and before the next step, whose densities have the old row count (it keeps no densities_0).
+ * apply = 1: the adapted sizes are kept resident beside the step's radii (never IN them: the hinted search reads those)
+ * and are what sphx_state_dust_phase, sphx_state_rad_phase, sphx_state_rad_transfer and the crossing time of
+ * sphx_state_supernova_impulse take as sizes until the next sphx_step, whose search replaces them (drv:437); densities_0
+ * becomes the step's densities; with loop forms on, d becomes their d for the next step (nsc.d = d, drv:523).  Every
+ * applied call starts from the step's radii: one call per pass of the loop.
+ * apply = 0 writes nothing resident (densities_0 included).  sphx_state_download keeps returning the radii as sizes;
+ * sphx_state_download_sizes returns the adapted ones (SPHX_E_STATE when none stand).
+ * Outputs as above, d_dust = d / raise_factor**(1./3.); sizes_out (n), rev_count_out int64[n] in the caller's order, or NULL.
+ * SPHX_E_STATE as sphx_state_dust_phase: no state, no step yet, incremental search, the step's list gone.
+ * SPHX_E_ARG as sphx_length_scale, a NaN raise_factor, and with apply = 1 a NaN d (with loop forms on: a d that is not > 0).
+ * A refused call leaves everything as it was.
+ *
+ * sphx_scale_last_timing: device time of the stages of the family's last call on this context, from HIP events on its
+ * stream, in ms: [0] keys (array call: with the upload), [1] the selection and its one read-back, [2] the reverse counts,
+ * [3] the adaptation, [4] the outputs coming back.  A stage a call does not have reads 0.  Measurement aid.         */
+#define SPHX_SCALE_NCOUNT      4
+int sphx_length_scale_finish(int64_t n_slow, int64_t n_nan, double qf, double a, double b, double n_int, double fill,
+                             double* max_dist, double* d);
+int sphx_length_scale(sphx_ctx* ctx, int64_t n, const double* points, const double* velocities, double v_max2, double qf,
+                      double n_int, double fill, int64_t* n_slow, int64_t* n_nan, int64_t* lo, double* a, double* b,
+                      double* max_dist, double* d);
+int sphx_adapt_sizes(sphx_ctx* ctx, int64_t n, int k, const int64_t* neighbor, const double* densities,
+                     const double* densities_0 /* or NULL */, const double* sizes, const double* ptype, double d, double d_dust,
+                     double* sizes_out, int64_t* rev_count_out /* int64[n] or NULL */, int64_t* nontrivial_out /* int64[n] or NULL */,
+                     double* new_smoothing_out /* (n) or NULL */, int64_t* counts /* int64[SPHX_SCALE_NCOUNT] or NULL */);
+int sphx_state_length_scale(sphx_ctx* ctx, double v_max2, double qf, double n_int, double fill, double raise_factor, int apply,
+                            int64_t* n_slow, int64_t* n_nan, int64_t* lo, double* a, double* b, double* max_dist, double* d,
+                            double* d_dust, int64_t* counts /* int64[SPHX_SCALE_NCOUNT] or NULL */, double* sizes_out /* (n) or NULL */,
+                            int64_t* rev_count_out /* int64[n] or NULL */);
+int sphx_state_download_sizes(sphx_ctx* ctx, double* sizes);
+int sphx_scale_last_timing(sphx_ctx* ctx, double ms[5]);
 /* ---- nsc.chemisputtering_2(points, neighbor, mass, f_un, mu_array, sizes, T, particle_type)      nsc:1265-1416 ----- *
  * Thermal / chemical sputtering of the dust rows and reuptake by the gas entries of their lists, on the list `neighbors`
  * returned (drv:405).  The module globals d and dt are arguments, and so are the per-species tables (nsc:41-52).

@@ -110,6 +110,12 @@ SIGNATURES = {
                                          [C.c_int, C.c_double]),
     "sphx_insert_last_info": (C.c_int, [_P, _I]),
     "sphx_insert_last_timing": (C.c_int, [_P, _D]),
+    "sphx_length_scale_finish": (C.c_int, [C.c_int64, C.c_int64] + [C.c_double] * 5 + [_D, _D]),
+    "sphx_length_scale": (C.c_int, [_P, C.c_int64, _D, _D] + [C.c_double] * 4 + [_I, _I, _I, _D, _D, _D, _D]),
+    "sphx_adapt_sizes": (C.c_int, [_P, C.c_int64, C.c_int, _I, _D, _D, _D, _D, C.c_double, C.c_double, _D, _I, _I, _D, _I]),
+    "sphx_state_length_scale": (C.c_int, [_P] + [C.c_double] * 5 + [C.c_int, _I, _I, _I, _D, _D, _D, _D, _D, _I, _D, _I]),
+    "sphx_state_download_sizes": (C.c_int, [_P, _D]),
+    "sphx_scale_last_timing": (C.c_int, [_P, _D]),
     "sphx_chemisputtering_2": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _D, _I] + [_D] * 6 + [C.c_double, C.c_double] + [_D] * 4 +
                                          [C.c_double] * 3 + [_D, _D, _I]),
     "sphx_chem_last_timing": (C.c_int, [_P, _D]),

@@ -18,6 +18,7 @@ for the functions the driver sph/code_running.py ("drv") calls on the SPH inner 
     supernova_destruction  nsc:1211-1263    drv:411
     chemisputtering_2      nsc:1265-1416    drv:405
     supernova_impulse      nsc:1192-1204    drv:351 (supernova_impulses: the loop drv:350-352)
+    length_scale, adapt_sizes               drv:493-540 (the driver's own lines, no nsc function)
     luminosity_relation    nsc:174-200      (without its unused `imf` argument)
 
 and, under names of their own, the pieces rad_heating (nsc:893-1017) and the driver's radiative block (drv:247-316)
@@ -1409,3 +1410,74 @@ def supernova_insert(state, explosion, t_cmb=None, star_ages=None, sizes=None, d
         mcs[touched] = np.sum(sigma_effective() * fun[touched], axis=1)
         out["mean_grain_mass"], out["mean_cross"] = mgm, mcs
     return out
+
+
+# ==============================================================================================
+# The adaptive length scale and sizes: the closing block of the time loop (drv:493-540)
+# ==============================================================================================
+SCALE_COUNTS = ("bonus", "capped", "nan_to_num", "missing")
+SCALE_STAGES = ("keys", "select", "reverse_counts", "adapt", "write_back")
+
+
+def _scale_result(n_slow, n_nan, lo, a, b, max_dist, d):
+    return dict(n_slow=int(n_slow[0]), n_nan=int(n_nan[0]), lo=int(lo[0]), a=float(a[0]), b=float(b[0]),
+                max_dist=float(max_dist[0]), d=float(d[0]))
+
+
+def _scale_outputs():
+    return [np.zeros(1, dtype=np.int64) for _ in range(3)] + [np.zeros(1) for _ in range(4)]
+
+
+def length_scale(points, velocities, N_INT_PER_PARTICLE, q=90., v_max=80000., fill=0.9, full=False):
+    """drv:493, 515-521 -> d, the driver's global length scale: from the q-th percentile (np.percentile, method linear) of
+    |x|^2 over the rows slower than v_max and from their count (include/sphx.h sphx_length_scale).  The device finds the
+    two order statistics the percentile interpolates between and the count; the result has np.percentile's bits.  No slow
+    row: ValueError (np.percentile raises IndexError).  A NaN position among the slow rows gives NaN, as NumPy does.
+    full=True -> dict: n_slow, n_nan, lo, a, b, max_dist, d."""
+    pts = f64(points)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("points must be (N, 3)")
+    n = pts.shape[0]
+    vel = f64(velocities, (n, 3))
+    o = _scale_outputs()
+    c_ = context()
+    c_.check(c_.lib.sphx_length_scale(c_.h, n, dp(pts), dp(vel), float(v_max) ** 2, float(np.true_divide(q, 100)),
+                                      float(N_INT_PER_PARTICLE), float(fill), ip(o[0]), ip(o[1]), ip(o[2]), dp(o[3]), dp(o[4]),
+                                      dp(o[5]), dp(o[6])))
+    res = _scale_result(*o)
+    return res if full else res["d"]
+
+
+def adapt_sizes(neighbor, densities, densities_0, sizes, particle_type, d, raise_factor, full=False):
+    """drv:527-538 -> the new sizes (N,): the gas rows scaled by exp(-(rho - rho0) / (3 rho)) - plus 0.1 for a row that
+    lists, and is listed by, almost nobody - and capped at d, the dust rows set to d / raise_factor**(1./3.), the stars
+    left (include/sphx.h sphx_adapt_sizes).  densities_0 None, or of another length than densities (drv:532): the scale
+    is 1.  An entry of the list outside [0, N) is ignored.  The given sizes are not modified; drv:540, densities_0 =
+    densities, is the caller's.  full=True -> (sizes, dict: exp_neighbor_count, num_nontrivial (N,) int64, new_smoothing
+    (N,), counts (SCALE_COUNTS))."""
+    nb, n, k_ = _nk(neighbor)
+    rho = f64(densities, (n,))
+    rho0 = None
+    if densities_0 is not None and len(densities_0) == n:
+        rho0 = f64(densities_0, (n,))
+    h, pt = f64(sizes, (n,)), f64(particle_type, (n,))
+    d = float(d)
+    d_dust = d / raise_factor ** (1. / 3.)                                         # drv:538
+    out = np.zeros(n)
+    rev = nt = sm = None
+    if full:
+        rev, nt, sm = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n)
+    counts = np.zeros(len(SCALE_COUNTS), dtype=np.int64)
+    c_ = context()
+    c_.check(c_.lib.sphx_adapt_sizes(c_.h, n, k_, ip(nb), dp(rho), dp(rho0), dp(h), dp(pt), d, float(d_dust), dp(out), ip(rev), ip(nt),
+                                     dp(sm), ip(counts)))
+    if full:
+        return out, dict(exp_neighbor_count=rev, num_nontrivial=nt, new_smoothing=sm,
+                         counts=dict(zip(SCALE_COUNTS, (int(x) for x in counts))))
+    return out
+
+
+def scale_last_timing():
+    """Device time of the last length_scale / adapt_sizes call of this module, from HIP events (include/sphx.h
+    sphx_scale_last_timing) -> dict of ms: keys, select, reverse_counts, adapt, write_back."""
+    return _last_timing("sphx_scale_last_timing", SCALE_STAGES)

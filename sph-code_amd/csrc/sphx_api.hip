@@ -517,6 +517,7 @@ extern "C" int sphx_state_upload(sphx_ctx* ctx, int64_t n, int s, const double* 
     ctx->no_old_once = false;
     ctx->sums_stale = false;
     ctx->visc_rows_unfilled = false;
+    ctx->scale_sizes_valid = false; ctx->scale_d0_valid = false;       // (sphx_scale.hip)
     return SPHX_OK;
 }
 
@@ -867,6 +868,7 @@ int sphx_step_research(sphx_ctx* ctx, int k, double dist) {
     ctx->pass_part = 0;
     ctx->nbr_api_valid = false;
     sphx_step_list_drop(ctx);
+    ctx->scale_sizes_valid = false; ctx->scale_d0_valid = false;       // drv:532 behind drv:368: the lengths differ
     SPHX_TRY(step_search(ctx, k, dist, ctx->ev, /*fresh=*/true));
     HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
     SPHX_TRY(step_h_sums_out(ctx, ctx->n, ctx->st.hprev.as<double>(), ctx->stream));
@@ -923,6 +925,7 @@ extern "C" int sphx_step(sphx_ctx* ctx, int nsteps, int k, double dist, int firs
     HIPCHK(hipSetDevice(ctx->device));
     if (!(dist > 0.0) || !isfinite(dist)) dist = 0.0;
     ctx->k = k;
+    ctx->scale_sizes_valid = false;                        // drv:437: the search replaces the adapted sizes
     const bool per_call = !ctx->timing_detail;             // (else every step times itself)
     // the call's wall time on the stream, over all its steps
     if (per_call) HIPCHK(hipEventRecord(ctx->ev[8], ctx->stream));

@@ -474,6 +474,16 @@ struct sphx_ctx {
     std::vector<int> ins_ids;           // ... and the sorted ids of the rows to rewrite
     StageTimer ins_t;
     int64_t ins_info[4] = {0, 0, 0, 0};
+    // the adaptive length scale and sizes (sphx_scale.hip), buffers of its own: staged inputs of the array calls, work (the
+    // keys, one level's histogram, the device scalars), ints (reverse counts | nontrivial counts, u32 each), outputs
+    // (sizes, new_smoothing, the counts as int64, each in the caller's order).  On the resident state also: the adapted
+    // sizes in STORAGE-SLOT order like st.hprev (scale_sizes; they stand while scale_sizes_valid: until the next search
+    // replaces the radii, drv:437) and densities_0 BY PARTICLE ID (scale_d0: it has to survive the next step's re-ordering;
+    // dropped by sphx_state_upload and sphx_state_insert_rows, as the driver's length comparison drv:532 drops it).
+    // events: [0] start, [1] keys, [2] selected and read back, [3] reverse counts, [4] adapted, [5] outputs on the host
+    DevBuf scale_in, scale_work, scale_int, scale_out, scale_sizes, scale_d0;
+    bool scale_sizes_valid = false, scale_d0_valid = false;
+    StageTimer scale_t{5};
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
@@ -870,6 +880,11 @@ int sphx_phase_back(sphx_ctx* ctx, const PhaseBack& a);
 // the refusal of a state with drag on and no per-species drag tables; gamma (and with drag the two tables) finite
 int sphx_phase_check_tables(sphx_ctx* ctx, const char* who, int s, const double* gamma, const double* grain_mass,
                             const double* sigma_effective);
+// what the resident phases take as `sizes`: the adapted sizes while they stand (sphx_state_length_scale with apply), else
+// the step's radii; both in storage-slot order
+static inline const double* sphx_phase_sizes(const sphx_ctx* ctx) {
+    return ctx->scale_sizes_valid ? ctx->scale_sizes.as<double>() : ctx->st.hprev.as<double>();
+}
 int sphx_phase_need_list(sphx_ctx* ctx, const char* who);                          // SPHX_E_STATE unless the last step's list stands
 int sphx_phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list);       // col (n) and the caller-order K-major list (k npad)
 int sphx_phase_drag_refresh(sphx_ctx* ctx, int64_t n, int s, const double* f, const double* gm, const double* se, double* mgm, double* mcs);

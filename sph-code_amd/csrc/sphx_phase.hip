@@ -390,7 +390,7 @@ extern "C" int sphx_state_dust_phase(sphx_ctx* ctx, double dt, double d, const d
     ga.n = (int)n; ga.qorder = ctx->step_qorder; ga.id = st.id.as<int>();
     ga.x = st.x.as<double>(); ga.y = st.y.as<double>(); ga.z = st.z.as<double>();
     ga.vx = st.vx.as<double>(); ga.vy = st.vy.as<double>(); ga.vz = st.vz.as<double>();
-    ga.m = st.m.as<double>(); ga.mu = st.mu.as<double>(); ga.h = st.hprev.as<double>(); ga.T = st.T.as<double>(); ga.pt = st.ptype.as<double>();
+    ga.m = st.m.as<double>(); ga.mu = st.mu.as<double>(); ga.h = sphx_phase_sizes(ctx); ga.T = st.T.as<double>(); ga.pt = st.ptype.as<double>();
     ga.E = nullptr;
     ga.col = col; ga.pos = cin.pos; ga.sx = ga.sy = ga.sz = nullptr; ga.vel = din.vel; ga.om = cin.m; ga.omu = cin.mu; ga.oh = cin.sizes;
     ga.oT = cin.T; ga.opt = cin.ptype; ga.oE = nullptr;

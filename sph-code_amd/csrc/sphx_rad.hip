@@ -440,7 +440,7 @@ extern "C" int sphx_state_rad_transfer(sphx_ctx* ctx, const double* cross, int64
     PhaseGather ga = {};
     ga.n = (int)n; ga.id = s.id.as<int>();
     ga.x = s.x.as<double>(); ga.y = s.y.as<double>(); ga.z = s.z.as<double>();
-    ga.m = s.m.as<double>(); ga.pt = s.ptype.as<double>(); ga.h = s.hprev.as<double>(); ga.mu = s.mu.as<double>();
+    ga.m = s.m.as<double>(); ga.pt = s.ptype.as<double>(); ga.h = sphx_phase_sizes(ctx); ga.mu = s.mu.as<double>();
     ga.sx = soa; ga.sy = soa + nn; ga.sz = soa + 2 * nn; ga.om = in + 3 * nn; ga.opt = in + 4 * nn; ga.oh = in + 5 * nn; ga.omu = in + 7 * nn;
     SPHX_TRY(sphx_phase_gather(ctx, ga));
     RadPart pa;

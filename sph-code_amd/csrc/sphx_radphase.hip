@@ -431,7 +431,7 @@ extern "C" int sphx_state_rad_phase(sphx_ctx* ctx, double dt, double d, int64_t 
     ga.n = (int)n; ga.qorder = ctx->step_qorder; ga.id = st.id.as<int>();
     ga.x = st.x.as<double>(); ga.y = st.y.as<double>(); ga.z = st.z.as<double>();
     ga.vx = st.vx.as<double>(); ga.vy = st.vy.as<double>(); ga.vz = st.vz.as<double>();
-    ga.m = st.m.as<double>(); ga.mu = st.mu.as<double>(); ga.h = st.hprev.as<double>(); ga.T = st.T.as<double>();
+    ga.m = st.m.as<double>(); ga.mu = st.mu.as<double>(); ga.h = sphx_phase_sizes(ctx); ga.T = st.T.as<double>();
     ga.pt = st.ptype.as<double>(); ga.E = st.E.as<double>();
     ga.col = col; ga.pos = g_pos; ga.sx = g_x; ga.sy = g_y; ga.sz = g_z; ga.vel = g_vel; ga.om = g_m; ga.omu = g_mu; ga.oh = g_h;
     ga.oT = g_T; ga.opt = g_pt; ga.oE = g_E;

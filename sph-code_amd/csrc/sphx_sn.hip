@@ -432,7 +432,7 @@ extern "C" int sphx_state_supernova_impulse(sphx_ctx* ctx, int64_t n_sn, const i
     ga.n = (int)n; ga.qorder = ctx->step_qorder; ga.id = st.id.as<int>();
     ga.x = st.x.as<double>(); ga.y = st.y.as<double>(); ga.z = st.z.as<double>();
     ga.vx = st.vx.as<double>(); ga.vy = st.vy.as<double>(); ga.vz = st.vz.as<double>();
-    ga.m = st.m.as<double>(); ga.mu = st.mu.as<double>(); ga.h = st.hprev.as<double>(); ga.pt = st.ptype.as<double>();
+    ga.m = st.m.as<double>(); ga.mu = st.mu.as<double>(); ga.h = sphx_phase_sizes(ctx); ga.pt = st.ptype.as<double>();
     ga.T = nullptr; ga.E = nullptr;
     ga.col = col; ga.pos = d_pos; ga.sx = ga.sy = ga.sz = nullptr; ga.vel = d_v; ga.om = d_m; ga.omu = d_mu; ga.oh = d_h; ga.opt = d_pt;
     ga.oT = nullptr; ga.oE = nullptr;

@@ -255,6 +255,13 @@ class Simulation:
         c.check(c.lib.sphx_state_download_drag(c.h, dp(mgm), dp(mcs)))
         return mgm, mcs
 
+    def _d_or_remembered(self, d):
+        if d is not None:
+            return d
+        if getattr(self, "_scale_d", None) is None:
+            raise ValueError("d=None needs a length_scale() before it: there is no remembered d")
+        return self._scale_d
+
     def dust_phase(self, dt, d, guard="count", full=False, **tables):
         """code_running.py:399-435 on the state as it is on the device (include/sphx.h sphx_state_dust_phase): f_un
         normalised, the loop-form density, chemisputtering_2, supernova_destruction on its outputs, and the bookkeeping
@@ -268,6 +275,7 @@ class Simulation:
         The bits are those of compat.dust_phase on the downloaded state.  Needs with_species=True and one step."""
         from . import compat
         n = self.n
+        d = self._d_or_remembered(d)     # (None: the d of the last length_scale())
         # (a state without a composition: the library refuses the call; the tables are sized by themselves)
         S = self.n_species or int(np.shape(tables["mu_specie"] if tables.get("mu_specie") is not None else compat.mu_specie)[0])
         t = compat.phase_tables(S, dt=dt, guard=guard, **tables)
@@ -323,6 +331,7 @@ class Simulation:
         neighbors().  Needs with_species=True and one step."""
         from . import compat
         n = self.n
+        d = self._d_or_remembered(d)     # (None: the d of the last length_scale())
         S = self.n_species or int(np.shape(mu_specie if mu_specie is not None else compat.mu_specie)[0])
         code = rad_mode_code(mode)
         mus, gam = compat.chem_table(S, mu_specie, "mu_specie"), compat.chem_table(S, gamma, "gamma")
@@ -524,6 +533,57 @@ class Simulation:
         c = self.ctx
         c.check(c.lib.sphx_insert_last_timing(c.h, dp(ms)))
         return dict(zip(("upload", "grow", "insert", "search"), ms.tolist()))
+
+    # ---- the adaptive length scale and sizes (code_running.py:493-540) on the resident state --------------------------
+    def length_scale(self, N_INT_PER_PARTICLE, raise_factor, apply=True, full=False, q=90., v_max=80000., fill=0.9):
+        """code_running.py:493-540 on the state as the last step() left it (include/sphx.h sphx_state_length_scale): the
+        global d from the q-th percentile of |x|^2 over the rows slower than v_max, and the new sizes - the gas rows' radii
+        scaled by the change of their density since the previous applied call (1 on the first, and behind a
+        supernova_explosion) and capped at d, the dust rows at d / raise_factor**(1./3.).  apply=True keeps them on the
+        device: dust_phase, rad_phase, rad_transfer and supernova_impulse then read them as sizes until the next step(),
+        whose search replaces them (drv:437); with forms="loop" the next step uses the new d; and d is remembered:
+        dust_phase and rad_phase called with d=None use it.  apply=False changes nothing on the device.  -> dict: d,
+        d_dust, max_dist, n_slow, n_nan, lo, a, b, counts (compat.SCALE_COUNTS); full=True adds sizes and
+        exp_neighbor_count in the particle order of the uploaded state.  The bits are those of compat.length_scale and
+        compat.adapt_sizes on download(), neighbors() and the previous call's densities.  No slow row, or a NaN d with
+        apply=True: ValueError, nothing changed.  download() keeps returning the step's radii as sizes: download_sizes()
+        returns the adapted ones.  Needs one step; not with incremental=True."""
+        from . import compat
+        n = self.n
+        o = compat._scale_outputs()
+        dd = np.zeros(1); counts = np.zeros(len(compat.SCALE_COUNTS), dtype=np.int64)
+        sizes = rev = None
+        if full:
+            sizes, rev = np.zeros(n), np.zeros(n, dtype=np.int64)
+        c = self.ctx
+        c.check(c.lib.sphx_state_length_scale(c.h, float(v_max) ** 2, float(np.true_divide(q, 100)), float(N_INT_PER_PARTICLE), float(fill),
+                                              float(raise_factor), 1 if apply else 0, _lib.ip(o[0]), _lib.ip(o[1]), _lib.ip(o[2]), dp(o[3]),
+                                              dp(o[4]), dp(o[5]), dp(o[6]), dp(dd), _lib.ip(counts), dp(sizes), _lib.ip(rev)))
+        out = compat._scale_result(*o)
+        out["d_dust"] = float(dd[0])
+        out["counts"] = dict(zip(compat.SCALE_COUNTS, (int(v) for v in counts)))
+        if full:
+            out["sizes"], out["exp_neighbor_count"] = sizes, rev
+        if apply:
+            self._scale_d = out["d"]
+        return out
+
+    def download_sizes(self):
+        """The adapted sizes of the last length_scale(apply=True) -> (N,) in the particle order of the uploaded state.
+        Raises once a step() has replaced them, or when none were formed."""
+        out = np.empty(self.n)
+        c = self.ctx
+        c.check(c.lib.sphx_state_download_sizes(c.h, dp(out)))
+        return out
+
+    def scale_timing(self):
+        """Device time of the last length_scale() from HIP events -> dict of ms: keys, select, reverse_counts, adapt,
+        write_back."""
+        from . import compat
+        ms = np.zeros(5)
+        c = self.ctx
+        c.check(c.lib.sphx_scale_last_timing(c.h, dp(ms)))
+        return dict(zip(compat.SCALE_STAGES, ms.tolist()))
 
     # ---- snapshot / restart and per-step diagnostics (SURVEY 8f-4; the reference only wrote summary
     # statistics at the end of a run, sph/code_running.py:670, and printed the mass-weighted net
