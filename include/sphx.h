@@ -804,6 +804,68 @@ int sphx_state_length_scale(sphx_ctx* ctx, double v_max2, double qf, double n_in
                             int64_t* rev_count_out /* int64[n] or NULL */);
 int sphx_state_download_sizes(sphx_ctx* ctx, double* sizes);
 int sphx_scale_last_timing(sphx_ctx* ctx, double ms[5]);
+/* ---- the census, the ordered selections and the stellar clock    drv:244, 339-342, 465-468, 604, 616-622, 636, 656-664 -- *
+ * What decides a pass of the loop (which stars explode) and what a run reports and saves, formed on the device: only a
+ * few dozen numbers and the selected rows come back.  Nothing here changes N or the step; the state is only read.
+ *
+ * sphx_census: totals[13 + 3 s] are sums over all n rows of a per-row term; a row outside a quantity's mask contributes
+ * +0.0 by selection, so a NaN of a dust row never reaches a gas sum (the reference's boolean indexing):
+ *   [0..3]   mass over ptype == 0, == 1, == 2 and != 2 (the last is drv:616's denominator, a sum of its own)
+ *   [4]      mass over all rows (drv:636)
+ *   [5..7]   mass * total_accel_c,  [8..10] mass * velocity_c,  [11] mass * ((vx^2 + vy^2) + vz^2),  [12] E_internal
+ *            (the quantities of drv:465-468 and of a kinetic / internal energy; the caller halves [11])
+ *   [13 + ty s + t]   ((f_un[i,t] mu_specie[t]) / rowsum_i) * mass_i over ptype == ty: gas_, star_, dust_mass_by_species of
+ *            drv:656-658, rowsum_i = np.sum(f_un[i] * mu_specie) in NumPy's order.  A row of the type with rowsum 0 gives
+ *            NaN and poisons that type's sums, as in the reference.  drv:637 prints the gas quantity with the
+ *            multiplication by the mass BEFORE the division: other roundings; it is not formed separately.
+ * velocities, total_accel, E_internal NULL: their terms are formed from zeros.  f_un NULL: s counts as 0, 13 totals.
+ * counts[4]: the rows with ptype == 0, == 1, == 2, != 2 (drv:617), exact.  max_star_mass: the largest mass over ptype == 1
+ * (drv:341), a NaN among them handed on, -inf when there is no star.
+ * Order of every sum: by PARTICLE ID in the order of the library's ordered totals - chunks of 256 consecutive ids, each
+ * summed left to right; lane l of 256 adds the chunks l, l + 256, ... in order; then a binary tree over the lanes.  Masked
+ * rows stay in their place as +0.0 (the chunks are over all n ids).  So the totals are the same bits on every call and
+ * do not depend on the order the state is stored in, which changes every step.  No floating-point atomics.
+ *
+ * sphx_state_census: the same on the resident state (mass, ptype, the velocities, the previous total acceleration,
+ * E_internal, and with mu_specie not NULL the resident f_un).  The bits are those of sphx_census on the downloaded state.
+ * SPHX_E_STATE: no state; mu_specie given for a state that carries no composition.
+ *
+ * sphx_census_select / sphx_state_census_select: the rows with ptype == type - with window != 0 also lo < mass / unit < hi
+ * (drv:660) - in ASCENDING PARTICLE ID: ids int64, their mass, T, star_ages and (f_out not NULL) f_un rows.  *count is
+ * always written; ids NULL: the count alone.  The count is checked against cap, the rows the outputs hold, on the host
+ * before anything is copied (SPHX_E_ARG).  T or star_ages NULL (array call): zeros.  Resident: age_out needs the ages
+ * set, f_out a composition (SPHX_E_STATE).
+ *
+ * The stellar clock.  star_ages (n) is kept resident BY PARTICLE ID, beside the state, not in it.
+ *   sphx_state_set_star_ages       ages (n) in the caller's order; NULL drops them
+ *   sphx_state_download_star_ages  the same array back
+ *   sphx_state_advance_star_ages   drv:604: ages[(ptype == 1) & (ages > -2)] += dt
+ *   sphx_advance_star_ages         drv:604 on arrays, star_ages in place
+ * sphx_state_insert_rows extends set ages by -2 for every appended row (drv:371); sphx_state_upload drops them.  A state
+ * without ages behaves as it did.  SPHX_E_STATE: no state; download or advance before the ages are set.
+ * The schedule (drv:244, 339-342) divides by a lifetime with pow inside and compares with 1: the device selects the star
+ * rows (sphx_state_census_select, type 1) and the caller evaluates the ratio on those few rows with the reference's own
+ * expression, which gives the reference's bits.  Gas rows (age -1) and inserted rows (-2) can never pass the test, so the
+ * restriction to ptype == 1 changes nothing in supernova_pos.
+ *
+ * sphx_census_last_timing: device time of the stages of the last sphx_census / sphx_state_census on this context, in ms:
+ * [0] inputs on the device (resident: the id -> slot map), [1] the chunk sums, [2] the totals, [3] the read-back.       */
+int sphx_census(sphx_ctx* ctx, int64_t n, int s, const double* mass, const double* ptype, const double* f_un /* (n,s) or NULL */,
+                const double* mu_specie /* (s) with f_un */, const double* velocities /* (n,3) or NULL */,
+                const double* total_accel /* (n,3) or NULL */, const double* E_internal /* (n) or NULL */,
+                double* totals /* (13 + 3 s) */, int64_t counts[4] /* or NULL */, double* max_star_mass /* or NULL */);
+int sphx_state_census(sphx_ctx* ctx, const double* mu_specie /* (s) or NULL: 13 totals */, double* totals, int64_t counts[4],
+                      double* max_star_mass);
+int sphx_census_select(sphx_ctx* ctx, int64_t n, int s, const double* mass, const double* ptype, const double* T, const double* star_ages,
+                       const double* f_un, int type, int window, double unit, double lo, double hi, int64_t cap, int64_t* count,
+                       int64_t* ids, double* mass_out, double* T_out, double* age_out, double* f_out);
+int sphx_state_census_select(sphx_ctx* ctx, int type, int window, double unit, double lo, double hi, int64_t cap, int64_t* count,
+                             int64_t* ids, double* mass_out, double* T_out, double* age_out, double* f_out);
+int sphx_state_set_star_ages(sphx_ctx* ctx, const double* star_ages);
+int sphx_state_download_star_ages(sphx_ctx* ctx, double* star_ages);
+int sphx_state_advance_star_ages(sphx_ctx* ctx, double dt);
+int sphx_advance_star_ages(sphx_ctx* ctx, int64_t n, double* star_ages, const double* ptype, double dt);
+int sphx_census_last_timing(sphx_ctx* ctx, double ms[4]);
 /* ---- nsc.chemisputtering_2(points, neighbor, mass, f_un, mu_array, sizes, T, particle_type)      nsc:1265-1416 ----- *
  * Thermal / chemical sputtering of the dust rows and reuptake by the gas entries of their lists, on the list `neighbors`
  * returned (drv:405).  The module globals d and dt are arguments, and so are the per-species tables (nsc:41-52).

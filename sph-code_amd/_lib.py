@@ -116,6 +116,16 @@ SIGNATURES = {
     "sphx_state_length_scale": (C.c_int, [_P] + [C.c_double] * 5 + [C.c_int, _I, _I, _I, _D, _D, _D, _D, _D, _I, _D, _I]),
     "sphx_state_download_sizes": (C.c_int, [_P, _D]),
     "sphx_scale_last_timing": (C.c_int, [_P, _D]),
+    "sphx_census": (C.c_int, [_P, C.c_int64, C.c_int] + [_D] * 8 + [_I, _D]),
+    "sphx_state_census": (C.c_int, [_P, _D, _D, _I, _D]),
+    "sphx_census_select": (C.c_int, [_P, C.c_int64, C.c_int] + [_D] * 5 + [C.c_int, C.c_int] + [C.c_double] * 3 +
+                                     [C.c_int64, _I, _I, _D, _D, _D, _D]),
+    "sphx_state_census_select": (C.c_int, [_P, C.c_int, C.c_int] + [C.c_double] * 3 + [C.c_int64, _I, _I, _D, _D, _D, _D]),
+    "sphx_state_set_star_ages": (C.c_int, [_P, _D]),
+    "sphx_state_download_star_ages": (C.c_int, [_P, _D]),
+    "sphx_state_advance_star_ages": (C.c_int, [_P, C.c_double]),
+    "sphx_advance_star_ages": (C.c_int, [_P, C.c_int64, _D, _D, C.c_double]),
+    "sphx_census_last_timing": (C.c_int, [_P, _D]),
     "sphx_chemisputtering_2": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _D, _I] + [_D] * 6 + [C.c_double, C.c_double] + [_D] * 4 +
                                          [C.c_double] * 3 + [_D, _D, _I]),
     "sphx_chem_last_timing": (C.c_int, [_P, _D]),

@@ -20,6 +20,8 @@ for the functions the driver sph/code_running.py ("drv") calls on the SPH inner 
     supernova_impulse      nsc:1192-1204    drv:351 (supernova_impulses: the loop drv:350-352)
     length_scale, adapt_sizes               drv:493-540 (the driver's own lines, no nsc function)
     luminosity_relation    nsc:174-200      (without its unused `imf` argument)
+    census, advance_star_ages, supernova_schedule, run_outputs, select_rows
+                                            drv:244, 339-342, 604, 616-622, 636, 656-664 (the driver's own lines)
 
 and, under names of their own, the pieces rad_heating (nsc:893-1017) and the driver's radiative block (drv:247-316)
 fall into: rad_setup, rad_transfer, stellar_spectrum, rad_ionise, rad_heat_bookkeeping, rad_cool_bookkeeping, and
@@ -1481,3 +1483,155 @@ def scale_last_timing():
     """Device time of the last length_scale / adapt_sizes call of this module, from HIP events (include/sphx.h
     sphx_scale_last_timing) -> dict of ms: keys, select, reverse_counts, adapt, write_back."""
     return _last_timing("sphx_scale_last_timing", SCALE_STAGES)
+
+
+# ==============================================================================================
+# The census, the ordered selections and the stellar clock (drv:244, 339-342, 465-468, 604, 616-622, 636, 656-664)
+# ==============================================================================================
+CENSUS_FIXED = 13                # include/sphx.h sphx_census: the totals before the by-species ones
+CENSUS_STAGES = ("prepare", "chunk_sums", "totals", "read_back")
+AGB_WINDOW = (1., 7.)            # drv:660, solar masses
+
+
+def _census_result(tot, counts, mx, S, have_dyn=True):
+    """The dict of census() from the C call's outputs.  star_massfrac and star_numfrac as drv:616-617 forms them from the
+    sums and counts, in NumPy's division: with no star or no non-dust row they are what NumPy gives (0, nan or inf)."""
+    n_gas, n_star, n_dust, n_nondust = (int(v) for v in counts)
+    out = dict(gas_mass=float(tot[0]), star_mass=float(tot[1]), dust_mass=float(tot[2]), nondust_mass=float(tot[3]),
+               total_mass=float(tot[4]), n_gas=n_gas, n_star=n_star, n_dust=n_dust, n_nondust=n_nondust,
+               max_star_mass=float(mx) if n_star else None)
+    with np.errstate(all="ignore"):
+        out["star_massfrac"] = float(np.float64(tot[1]) / np.float64(tot[3]))
+        out["star_numfrac"] = float(np.float64(n_star) / np.float64(n_nondust))
+        out["net_accel"] = np.array(tot[5:8]) / np.float64(tot[4]) if have_dyn else None
+    out["momentum"] = np.array(tot[8:11]) if have_dyn else None
+    out["kinetic"] = 0.5 * float(tot[11]) if have_dyn else None
+    out["internal"] = float(tot[12]) if have_dyn else None
+    for q, nm in enumerate(("gas_mass_by_species", "star_mass_by_species", "dust_mass_by_species")):
+        out[nm] = np.array(tot[CENSUS_FIXED + q * S:CENSUS_FIXED + (q + 1) * S]) if S else None
+    return out
+
+
+def census(mass, particle_type, f_un=None, mu_specie=None, velocities=None, total_accel=None, E_internal=None):
+    """The sums, counts and the maximum the driver reports every pass and saves at the end (drv:341, 465-468, 616-617, 636,
+    656-658), in one fused pass on the device (include/sphx.h sphx_census) -> dict: gas_mass, star_mass, dust_mass,
+    nondust_mass, total_mass, n_gas, n_star, n_dust, n_nondust, max_star_mass (None without a star), star_massfrac,
+    star_numfrac, and with f_un the (S,) arrays gas_, star_ and dust_mass_by_species (else None); net_accel, momentum,
+    kinetic and internal are formed from velocities, total_accel and E_internal (a missing array counts as zeros; all three
+    missing: None).  Every sum runs over the particle index in the order of the library's ordered totals: the same bits on
+    every call.  A row outside a sum's mask does not enter it, NaN or not."""
+    m = f64(mass).reshape(-1)
+    n = m.shape[0]
+    pt = f64(particle_type, (n,))
+    fu = mus = None
+    S = 0
+    if f_un is not None:
+        fu = f64(f_un)
+        if fu.ndim != 2 or fu.shape[0] != n:
+            raise ValueError("f_un must be (N, S)")
+        S = fu.shape[1]
+        mus = chem_table(S, mu_specie, "mu_specie")
+    vel = None if velocities is None else f64(velocities, (n, 3))
+    acc = None if total_accel is None else f64(total_accel, (n, 3))
+    E = None if E_internal is None else f64(E_internal, (n,))
+    tot = np.zeros(CENSUS_FIXED + 3 * S); counts = np.zeros(4, dtype=np.int64); mx = np.zeros(1)
+    c_ = context()
+    c_.check(c_.lib.sphx_census(c_.h, n, S, dp(m), dp(pt), dp(fu), dp(mus), dp(vel), dp(acc), dp(E), dp(tot), ip(counts), dp(mx)))
+    return _census_result(tot, counts, mx[0], S, have_dyn=not (vel is None and acc is None and E is None))
+
+
+def census_last_timing():
+    """Device time of the last census() of this module from HIP events -> dict of ms (CENSUS_STAGES)."""
+    return _last_timing("sphx_census_last_timing", CENSUS_STAGES)
+
+
+def _select_outputs(cap, S):
+    cap = max(int(cap), 1)
+    return (np.zeros(1, dtype=np.int64), np.zeros(cap, dtype=np.int64), np.zeros(cap), np.zeros(cap), np.zeros(cap),
+            np.zeros((cap, S)) if S else None)
+
+
+def _select_result(o):
+    cnt = int(o[0][0])
+    return dict(ids=o[1][:cnt].copy(), mass=o[2][:cnt].copy(), T=o[3][:cnt].copy(), star_ages=o[4][:cnt].copy(),
+                f_un=None if o[5] is None else o[5][:cnt].copy())
+
+
+def select_rows(mass, particle_type, ptype, T=None, star_ages=None, f_un=None, window=None):
+    """The rows with particle_type == ptype - with window = (lo, hi) also lo < mass / solar_mass < hi (drv:660) - in
+    ascending particle index, selected and compacted on the device (include/sphx.h sphx_census_select) -> dict: ids, mass,
+    T, star_ages (zeros where the array is not given), f_un (rows, or None)."""
+    m = f64(mass).reshape(-1)
+    n = m.shape[0]
+    pt = f64(particle_type, (n,))
+    Tt = None if T is None else f64(T, (n,))
+    ag = None if star_ages is None else f64(star_ages, (n,))
+    fu = None if f_un is None else f64(f_un)
+    S = 0 if fu is None else fu.shape[1]
+    cap = int(np.count_nonzero(pt == ptype))
+    o = _select_outputs(cap, S)
+    lo, hi = (0., 0.) if window is None else window
+    c_ = context()
+    c_.check(c_.lib.sphx_census_select(c_.h, n, S, dp(m), dp(pt), dp(Tt), dp(ag), dp(fu), int(ptype), 0 if window is None else 1,
+                                       float(solar_mass), float(lo), float(hi), cap, ip(o[0]), ip(o[1]), dp(o[2]), dp(o[3]), dp(o[4]),
+                                       dp(o[5])))
+    return _select_result(o)
+
+
+def advance_star_ages(star_ages, particle_type, dt):
+    """drv:604 -> the new star_ages: ages[(particle_type == 1) & (ages > -2)] += dt (include/sphx.h
+    sphx_advance_star_ages).  The given array is not modified."""
+    a = np.array(f64(star_ages).reshape(-1))
+    n = a.shape[0]
+    pt = f64(particle_type, (n,))
+    c_ = context()
+    c_.check(c_.lib.sphx_advance_star_ages(c_.h, n, dp(a), dp(pt), float(dt)))
+    return a
+
+
+def _schedule_of(rows):
+    """drv:244, 339-341 on the compacted star rows (ids ascending, mass, star_ages): the reference's own expression, on the
+    host, so the comparison with 1 has the reference's bits."""
+    ids, m, ages = rows["ids"], rows["mass"], rows["star_ages"]
+    if ids.shape[0] == 0:                # drv:243: the block is skipped without a star
+        return dict(supernova_pos=np.zeros(0, dtype=np.int64), max_rel_age=None, max_star_mass=None, n_star=0)
+    with np.errstate(all="ignore"):
+        rel = ages / luminosity_relation(m / solar_mass, lifetime=1) / (year * 1e10)
+        return dict(supernova_pos=ids[rel > 1.], max_rel_age=float(np.max(rel)), max_star_mass=float(np.max(m / solar_mass)),
+                    n_star=int(ids.shape[0]))
+
+
+def supernova_schedule(star_ages, particle_type, mass):
+    """drv:244, 339-342 -> dict: supernova_pos (ascending indices of the stars whose age exceeds their lifetime),
+    max_rel_age and max_star_mass (solar masses) over the stars, n_star.  The device selects the star rows; the ratio and
+    its comparison are the reference's NumPy expression on those rows.  Gas rows (age -1) and inserted rows (-2) can never
+    pass the test, so leaving them out changes nothing in supernova_pos; max_rel_age is the reference's whenever a star's
+    relative age is the largest (ages of stars are >= 0).  Without a star: an empty supernova_pos, None for the maxima."""
+    return _schedule_of(select_rows(mass, particle_type, 1, star_ages=star_ages))
+
+
+def _agb_outputs(n, rows, OVERALL_AGE, mus):
+    """drv:660-664 from the compacted AGB rows, with the driver's own expressions."""
+    ids, m, ages, fu = rows["ids"], rows["mass"], rows["star_ages"], rows["f_un"]
+    cond = np.zeros(n, dtype=bool)
+    cond[ids] = True
+    fm = fu * mus
+    with np.errstate(all="ignore"):
+        return dict(AGB_condition=cond, AGB_list=m,
+                    AGB_time_until=luminosity_relation(m / solar_mass, lifetime=1) * 1e10 * year - ages + OVERALL_AGE,
+                    AGB_metallicity=np.sum(fm.T[6:], axis=0) / np.sum(fm, axis=1),
+                    AGB_composition=(fm.T / np.sum(fm, axis=1)).T)
+
+
+def run_outputs(mass, particle_type, f_un, star_ages, OVERALL_AGE, mu_specie=None):
+    """The entries of the driver's closing np.savez (drv:670) that depend on the state -> dict: gas_, star_ and
+    dust_mass_by_species (drv:656-658, from census()), AGB_condition, AGB_list, AGB_time_until, AGB_metallicity and
+    AGB_composition (drv:660-664, from the AGB rows the device selects, with the driver's expressions)."""
+    fu = f64(f_un)
+    S = fu.shape[1]
+    mus = chem_table(S, mu_specie, "mu_specie")
+    cen = census(mass, particle_type, fu, mus)
+    out = {nm: cen[nm] for nm in ("gas_mass_by_species", "star_mass_by_species", "dust_mass_by_species")}
+    rows = select_rows(mass, particle_type, 1, star_ages=star_ages, f_un=fu, window=AGB_WINDOW)
+    out.update(_agb_outputs(fu.shape[0], rows, OVERALL_AGE, mus))
+    return out

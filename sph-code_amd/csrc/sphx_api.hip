@@ -518,6 +518,7 @@ extern "C" int sphx_state_upload(sphx_ctx* ctx, int64_t n, int s, const double* 
     ctx->sums_stale = false;
     ctx->visc_rows_unfilled = false;
     ctx->scale_sizes_valid = false; ctx->scale_d0_valid = false;       // (sphx_scale.hip)
+    ctx->star_ages_valid = false;                                      // (sphx_census.hip)
     return SPHX_OK;
 }
 

@@ -259,6 +259,7 @@ extern "C" int sphx_state_insert_rows(sphx_ctx* ctx, int s, int64_t n_rew, const
     if (rc == SPHX_OK) rc = sphx_ensure_keep(ctx, st.id, (size_t)n_new * sizeof(int), (size_t)n * sizeof(int), retired, &grown);
     if (rc == SPHX_OK && has_fun)
         rc = sphx_ensure_keep(ctx, ctx->fun_id, (size_t)n_new * ctx->sp * sizeof(double), (size_t)n * ctx->sp * sizeof(double), retired, &grown);
+    if (rc == SPHX_OK) rc = sphx_star_ages_grow(ctx, n, n_new, retired);       // (the stellar clock, where it is set: sphx_census.hip)
     {
         const int rf = sphx_free_retired(ctx, retired);
         if (rc == SPHX_OK) rc = rf;
@@ -272,6 +273,7 @@ extern "C" int sphx_state_insert_rows(sphx_ctx* ctx, int s, int64_t n_rew, const
     if (!st.id.p || st.id.cap < (size_t)n_new * sizeof(int) || (has_fun && ctx->fun_id.cap < (size_t)n_new * ctx->sp * sizeof(double)))
         return sphx_set_err(ctx, SPHX_E_STATE, "%s: the id or composition buffer does not hold %lld rows", who, (long long)n_new);
     SPHX_TRY(ctx->ins_t.mark(ctx, 2));
+    SPHX_TRY(sphx_star_ages_fill(ctx, n, n_new));                              // drv:371: -2 for every appended row
     // ---- b. one kernel over N + m rows ----
     InsertArgs a;
     a.n_old = (int)n; a.n_app = (int)n_app; a.n_rew = (int)n_rew; a.s = s; a.sp = has_fun ? ctx->sp : 0;

@@ -484,6 +484,16 @@ struct sphx_ctx {
     DevBuf scale_in, scale_work, scale_int, scale_out, scale_sizes, scale_d0;
     bool scale_sizes_valid = false, scale_d0_valid = false;
     StageTimer scale_t{5};
+    // the census and the stellar clock (sphx_census.hip), buffers of its own - it only reads the state: staged inputs of the
+    // array calls, doubles (the chunks' partial sums | the totals, the largest stellar mass and the four counts | the
+    // selections' columns), ints (slot of a particle id | the selection's flags | their scan).  star_ages BY PARTICLE ID
+    // like scale_d0 (no part of StateArrays: the step's permutation does not move it); it stands while star_ages_valid:
+    // set by sphx_state_set_star_ages, extended by sphx_state_insert_rows, dropped by sphx_state_upload.
+    // events: [0] start, [1] inputs on the device / the slot map, [2] the chunk sums, [3] the totals, [4] outputs on the host
+    DevBuf census_in, census_buf, census_int, star_ages;
+    bool star_ages_valid = false;
+    double census_tab[SPHX_MAX_SPECIES] = {0};     // mu_specie on the host, uploaded from here
+    StageTimer census_t;
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
@@ -617,6 +627,7 @@ struct PinnedLag {
     double box[32];           // a grid build's box statistics (sphx_grid.hip: BB_OUT doubles)
     double hs[32];            // SC_HSUM .. SC_KGDBG + 2: the h sums and the search's counters behind them
 };
+#define SPHX_CENSUS_PIN (13 + 3 * SPHX_MAX_SPECIES + 1 + 4 + 2)
 struct PinnedLayout {
     // Read-backs the launching call itself waits for: sphx_step's scalar slots, a synchronous box reduction, the Verlet
     // refresh's and rad_cooling's counts (scal), the side calls' tuples (side).  side.count and side.cand lie INSIDE the
@@ -632,18 +643,22 @@ struct PinnedLayout {
     PinnedLag lag[2];         // the fused loop's lagged read-backs (lag_bslot / lag_hslot say which is current)
     char pad2_[3072 - 1024 - 2 * 512];
     u64 knn_lag[10];          // SC_NFAILQ .. SC_KGDBG + 2, copied out behind a hinted search (sphx_knn.hip)
-    char pad3_[8192 - 3072 - 10 * 8];
+    char pad3_[4096 - 3072 - 10 * 8];
+    // the census' read-back (sphx_census.hip): 13 + 3 s totals, the largest stellar mass, four counts; a selection's count
+    u64 census[SPHX_CENSUS_PIN];
+    char pad4_[8192 - 4096 - SPHX_CENSUS_PIN * 8];
     u64 badc[BADC_BUCKETS * BADC_STRIDE];      // the failure buckets (sphx_badc_read)
 };
 static_assert(sizeof(PinnedLayout) == 16384, "ctx->pinned is 16 KiB");
 static_assert(offsetof(PinnedLayout, side) == 0 && offsetof(PinnedSide, count) == 32 && offsetof(PinnedSide, cand) == 64 &&
                   offsetof(PinnedLayout, hsum) == 256 && offsetof(PinnedLayout, lag) == 1024 && sizeof(PinnedLag) == 512 &&
-                  offsetof(PinnedLag, hs) == 256 && offsetof(PinnedLayout, knn_lag) == 3072 && offsetof(PinnedLayout, badc) == 8192,
+                  offsetof(PinnedLag, hs) == 256 && offsetof(PinnedLayout, knn_lag) == 3072 && offsetof(PinnedLayout, census) == 4096 &&
+                  offsetof(PinnedLayout, badc) == 8192,
               "the offsets in use since the members were byte counts");
 #define SPHX_PIN_APART(a, b) \
     static_assert(offsetof(PinnedLayout, a) + sizeof(PinnedLayout::a) <= offsetof(PinnedLayout, b), #a " overlaps " #b)
 SPHX_PIN_APART(scal, hsum); SPHX_PIN_APART(side, hsum); SPHX_PIN_APART(hsum, lag); SPHX_PIN_APART(lag, knn_lag);
-SPHX_PIN_APART(knn_lag, badc);
+SPHX_PIN_APART(knn_lag, census); SPHX_PIN_APART(census, badc);
 #undef SPHX_PIN_APART
 static_assert(offsetof(PinnedLayout, badc) + sizeof(PinnedLayout::badc) == sizeof(PinnedLayout), "the buckets end the block");
 
@@ -862,6 +877,12 @@ int sphx_rev_build(sphx_ctx* ctx, const char* who, int64_t n, const int* cnt, in
 #define SPHX_TOT_CHUNK 256
 static inline size_t sphx_tot_chunks(int64_t n) { return ((size_t)n + SPHX_TOT_CHUNK - 1) / SPHX_TOT_CHUNK; }
 int sphx_ordered_totals(sphx_ctx* ctx, int64_t n, int nq, const double* pp, double* part, double* tot);
+// its second stage alone, on chunk sums the caller has formed: part (nq, nchunk) -> tot (nq); nothing is copied out
+int sphx_ordered_totals_of_parts(sphx_ctx* ctx, size_t nchunk, int nq, const double* part, double* tot);
+// ---- the stellar clock inside sphx_state_insert_rows (sphx_census.hip) ----
+// ages set: the by-id array grown to n_new rows with its contents kept (grow), and -2 for the rows [n_old, n_new) (fill)
+int sphx_star_ages_grow(sphx_ctx* ctx, int64_t n_old, int64_t n_new, std::vector<void*>& retired);
+int sphx_star_ages_fill(sphx_ctx* ctx, int64_t n_old, int64_t n_new);
 // ---- shared by the two resident phases (sphx_phase.hip) ----
 // The state from the storage slots into the caller's particle order (lane p: the slot of column p, its caller id i;
 // col[i] = p, sphx_phase_map.h) - m, mu, h, ptype always; col, the (n,3) positions, the SoA positions, the (n,3)

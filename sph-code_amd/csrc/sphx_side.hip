@@ -66,14 +66,19 @@ __global__ __launch_bounds__(TOT_WG) void sphx_total_kernel(int nchunk, const do
     }
     if (l == 0) tot[q] = sm[0];
 }
+// the second stage on ready chunk sums (the census forms its own, sphx_census.hip)
+int sphx_ordered_totals_of_parts(sphx_ctx* ctx, size_t nchunk, int nq, const double* part, double* tot) {
+    hipLaunchKernelGGL(sphx_total_kernel, dim3((unsigned)nq), dim3(TOT_WG), 0, ctx->stream, (int)nchunk, part, tot);
+    HIPCHK(hipGetLastError());
+    return SPHX_OK;
+}
 // part: nq sphx_tot_chunks(n) doubles, tot: nq.  The totals' copy into ctx->pinned->scal is queued: the caller reads it
 // after its next synchronise (nq <= SC_NSLOTS: the callers assert it at their enums).
 int sphx_ordered_totals(sphx_ctx* ctx, int64_t n, int nq, const double* pp, double* part, double* tot) {
     hipStream_t st = ctx->stream;
     const size_t nchunk = sphx_tot_chunks(n);
     hipLaunchKernelGGL(sphx_chunksum_kernel, dim3(sphx_blocks((size_t)nq * nchunk, TOT_WG)), dim3(TOT_WG), 0, st, (int)n, nq, (int)nchunk, pp, part);
-    hipLaunchKernelGGL(sphx_total_kernel, dim3((unsigned)nq), dim3(TOT_WG), 0, st, (int)nchunk, part, tot);
-    HIPCHK(hipGetLastError());
+    SPHX_TRY(sphx_ordered_totals_of_parts(ctx, nchunk, nq, part, tot));
     HIPCHK(hipMemcpyAsync(ctx->pinned->scal, tot, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, st));
     return SPHX_OK;
 }

@@ -698,6 +698,10 @@ class DistributedSim:
         owned particles under the halo protocol: not built for the decomposed step."""
         raise NotImplementedError("supernova_explosion is not available in the decomposed step (single-GPU Simulation only)")
 
+    def census(self, *a, **kw):
+        """The census' fixed order of summation runs over one context's particle ids: not built across ranks."""
+        raise NotImplementedError("census is not available in the decomposed step (single-GPU Simulation only)")
+
     def __init__(self, state, lo, hi, backend, rank=0, world=1, device="cpu", comm_device=None,
                  halo_scale=1.15, skin_frac=0.15, need_grid=96, migrate_every=4, forms="hydro_update", d=None,
                  with_drag=False, with_species=False, agb=None, visc_mode=None, gravity=None, G=6.67430e-11, gravity_ws=1,

@@ -20,7 +20,7 @@ log = logging.getLogger("sph_code_amd")
 class Simulation:
     def __init__(self, state, n_neigh=40, dist=None, device=None, with_species=False, ctx=None,
                  incremental=False, with_drag=False, gravity=None, G=6.67430e-11, clip_grad=False,
-                 forms="hydro_update", d=None, gravity_order=2, agb=None, visc_mode="ref_axis0"):
+                 forms="hydro_update", d=None, gravity_order=2, agb=None, visc_mode="ref_axis0", star_ages=None):
         """with_species: carry f_un on the device; every step (hydro_update mode) then also forms the species number
         densities F[s,i] of nsc:624-627 on its own neighbour list.  agb = (splines, mapto, divisor) as
         sph_code_amd.agb.interpolate_amounts returns them: the same pass also leaves the per-particle metallicity
@@ -93,6 +93,9 @@ class Simulation:
             mgm = np.ascontiguousarray(np.sum(compat.grain_mass() * fu_all, axis=1))
             mcs = np.ascontiguousarray(np.sum(compat.sigma_effective() * fu_all, axis=1))
             c.check(c.lib.sphx_state_set_drag(c.h, dp(mgm), dp(mcs)))
+        self._has_ages = False
+        if star_ages is not None:
+            self.set_star_ages(star_ages)
 
     def step(self, nsteps=1, fixed_dt=0.0):
         c = self.ctx
@@ -585,6 +588,96 @@ class Simulation:
         c.check(c.lib.sphx_scale_last_timing(c.h, dp(ms)))
         return dict(zip(compat.SCALE_STAGES, ms.tolist()))
 
+    # ---- the census, the ordered selections and the stellar clock (code_running.py:244, 339-342, 604, 616-622, 636, 656-664) ----
+    def set_star_ages(self, star_ages):
+        """The driver's star_ages (N,) in the particle order of the uploaded state, kept on the device by particle id
+        (include/sphx.h sphx_state_set_star_ages).  supernova_explosion extends them by -2 for every new row (drv:371)."""
+        c = self.ctx
+        c.check(c.lib.sphx_state_set_star_ages(c.h, dp(f64(star_ages, (self.n,)))))
+        self._has_ages = True
+
+    def download_star_ages(self):
+        """-> star_ages (N,) as they are on the device.  Raises before they are set."""
+        out = np.empty(self.n)
+        c = self.ctx
+        c.check(c.lib.sphx_state_download_star_ages(c.h, dp(out)))
+        return out
+
+    def advance_star_ages(self, dt):
+        """drv:604 on the device: star_ages[(particle_type == 1) & (star_ages > -2)] += dt.  Raises before they are set."""
+        c = self.ctx
+        c.check(c.lib.sphx_state_advance_star_ages(c.h, float(dt)))
+
+    def last_dt(self):
+        """The last step's dt (what download()["dt"] holds), with nothing downloaded."""
+        dt = C.c_double(0.0)
+        c = self.ctx
+        none = [None] * 9
+        c.check(c.lib.sphx_state_download(c.h, *none, C.cast(C.byref(dt), _lib.c_double_p)))
+        return dt.value
+
+    def census(self, mu_specie=None):
+        """The sums, counts and the maximum the driver reports every pass (drv:341, 465-468, 616-617, 636, 656-658) from the
+        state as it is on the device (include/sphx.h sphx_state_census) -> compat.census's dict: gas_mass, star_mass,
+        dust_mass, nondust_mass, total_mass, the counts, max_star_mass, star_massfrac, star_numfrac, net_accel, momentum,
+        kinetic, internal and, with with_species=True, gas_, star_ and dust_mass_by_species (else None).  58 numbers come
+        back, no array.  The bits are those of compat.census on download() and download_composition(), whatever order the
+        state is stored in.  The state is only read."""
+        from . import compat
+        S = self.n_species
+        mus = compat.chem_table(S, mu_specie, "mu_specie") if S else None
+        tot = np.zeros(compat.CENSUS_FIXED + 3 * S); counts = np.zeros(4, dtype=np.int64); mx = np.zeros(1)
+        c = self.ctx
+        c.check(c.lib.sphx_state_census(c.h, dp(mus), dp(tot), _lib.ip(counts), dp(mx)))
+        return compat._census_result(tot, counts, mx[0], S)
+
+    def census_timing(self):
+        """Device time of the last census() from HIP events -> dict of ms: prepare (the id -> slot map), chunk_sums, totals,
+        read_back."""
+        from . import compat
+        ms = np.zeros(4)
+        c = self.ctx
+        c.check(c.lib.sphx_census_last_timing(c.h, dp(ms)))
+        return dict(zip(compat.CENSUS_STAGES, ms.tolist()))
+
+    def _select(self, ptype, ages=False, f_un=False, window=None):
+        """The rows of a type in ascending particle id from the device (include/sphx.h sphx_state_census_select)."""
+        from . import compat
+        S = self.n_species if f_un else 0
+        cap = int(np.count_nonzero(self._ptype == ptype))
+        o = compat._select_outputs(cap, S)
+        lo, hi = (0., 0.) if window is None else window
+        c = self.ctx
+        c.check(c.lib.sphx_state_census_select(c.h, int(ptype), 0 if window is None else 1, float(compat.solar_mass), float(lo),
+                                               float(hi), cap, _lib.ip(o[0]), _lib.ip(o[1]), dp(o[2]), dp(o[3]),
+                                               dp(o[4]) if ages else None, dp(o[5])))
+        return compat._select_result(o)
+
+    def dust_temperatures(self):
+        """drv:620: T[particle_type == 2] in the particle order of the uploaded state, compacted on the device."""
+        return self._select(2)["T"]
+
+    def supernova_schedule(self):
+        """drv:244, 339-342 -> compat.supernova_schedule's dict (supernova_pos, max_rel_age, max_star_mass, n_star): the
+        device compacts the star rows (id, mass, age), the host evaluates the reference's expression on them.  Raises
+        before star_ages are set."""
+        from . import compat
+        return compat._schedule_of(self._select(1, ages=True))
+
+    def run_outputs(self, OVERALL_AGE, mu_specie=None):
+        """The entries of the driver's closing np.savez (drv:670) that depend on the state -> compat.run_outputs' dict, from
+        census() and the AGB rows (drv:660-664) compacted on the device.  Needs with_species=True and star_ages."""
+        from . import compat
+        S = self.n_species
+        if S < 1:
+            raise RuntimeError("the simulation carries no composition (with_species=True and a state with f_un)")
+        mus = compat.chem_table(S, mu_specie, "mu_specie")
+        cen = self.census(mus)
+        out = {nm: cen[nm] for nm in ("gas_mass_by_species", "star_mass_by_species", "dust_mass_by_species")}
+        rows = self._select(1, ages=True, f_un=True, window=compat.AGB_WINDOW)
+        out.update(compat._agb_outputs(self.n, rows, OVERALL_AGE, mus))
+        return out
+
     # ---- snapshot / restart and per-step diagnostics (SURVEY 8f-4; the reference only wrote summary
     # statistics at the end of a run, sph/code_running.py:670, and printed the mass-weighted net
     # accelerations every step, sph/code_running.py:465-468) ----------------------------------------
@@ -604,6 +697,8 @@ class Simulation:
             out.update(self.download_composition())
         if self._ptype.shape[0] != out["particle_type"].shape[0]:      # (a supernova_explosion has appended rows since)
             out["particle_type"] = self._ptype.copy()
+        if self._has_ages:
+            out["star_ages"] = self.download_star_ages()
         np.savez(path, **out)
 
     @classmethod
@@ -612,13 +707,16 @@ class Simulation:
         state = {k_: z[k_] for k_ in ("points", "velocities", "total_accel", "E_internal", "T", "mass",
                                        "particle_type", "mu_array", "gamma_array")}
         state["f_un"] = z.get("f_un")
+        if "star_ages" in z and "star_ages" not in kw:
+            kw["star_ages"] = z["star_ages"]
         sim = cls(state, n_neigh=int(z["n_neigh"]), dist=float(z["dist"]), device=device, **kw)
         sim.first = bool(int(z["first"]))
         return sim, state
 
     def diagnostics(self, state):
         """Mass-weighted net acceleration, momentum and energies of the current state
-        (sph/code_running.py:465-468 prints the first of these every step)."""
+        (sph/code_running.py:465-468 prints the first of these every step).  It downloads the whole state: census()
+        forms the same quantities on the device, in a fixed order of summation."""
         d = self.download()
         # (once a dust_phase has run the caller's masses are stale: the device's)
         m = self.download_composition()["mass"] if self._phase_ran else np.asarray(state["mass"], dtype=np.float64)
