@@ -257,6 +257,28 @@ int sphx_gravity_tree(sphx_ctx* ctx, int64_t n, const double* mass, const double
                       const double* sizes, double softening, double G, int ws, int k_cells,
                       double* accel);
 
+/* The gravitational potential beside the two sums above: the same walks, records and softening, one scalar per target.
+ *   per row     phi_i = -G sum_{j != i} m_j / sqrt(|x_j - x_i|^2 + eps^2)   [J/kg], eps taken exactly as the acceleration
+ *               calls take it (sizes != NULL: median(sizes) on the device, else softening)
+ *   self term   row i is left out of its own sum BY INDEX: it is never added and then taken off again
+ *   coincident  a different row at the same position contributes -G m_j / eps; with eps = 0 and r = 0 nothing, as in the
+ *               acceleration sum
+ *   total       U = 1/2 sum_i m_i phi_i   (sphx_state_gravity_potential)
+ *   tree cell   a cell carries M at c and, at order 2, S_ab about c.  With r = c - x and s^2 = r^2 + eps^2 its term is the
+ *               second-order expansion of the same softened kernel,
+ *                   phi_cell = -G [ M / s + 3/2 (r.S.r) / s^5 - 1/2 tr S / s^3 ]
+ *               whose negative gradient in x is the acceleration term of sphx_gravity_tree (7.5, 1.5, 3).  Order 1 keeps
+ *               M / s.  The trace term stays: the softened kernel is not harmonic.
+ * pot (n).  accel (n,3) is nullable; where given it holds the bits of sphx_gravity_direct / sphx_gravity_tree.
+ * sphx_gravity_tree_pot uses the grid (k_cells = 40), pyramid and eps of sphx_gravity_tree, and sphx_set_gravity_order. */
+int sphx_gravity_direct_pot(sphx_ctx* ctx, int64_t n, const double* mass, const double* points,
+                            const double* sizes, double softening, double G, double* accel, double* pot);
+int sphx_gravity_tree_pot(sphx_ctx* ctx, int64_t n, const double* mass, const double* points,
+                          const double* sizes, double softening, double G, int ws, double* accel, double* pot);
+/* Device time of the stages of the last potential call on this context (HIP events), ms: [0] inputs onto the device and
+ * eps, [1] grid and pyramid (tree; the direct sum: 0), [2] the sum and the totals, [3] outputs onto the host.         */
+int sphx_gravpot_last_timing(sphx_ctx* ctx, double ms[4]);
+
 /* The same sum over a cloud held in nparts parts (part_of[i] in 0 .. nparts-1; a part may be empty): the out-of-core /
  * multi-domain form, and the computation a decomposed run does across ranks, on one context.  Each part builds the grid
  * and pyramid over its OWN particles and sums its own field as sphx_gravity_tree does (nparts = 1 gives that call's bits).
@@ -368,6 +390,17 @@ int sphx_state_set_gravity(sphx_ctx* ctx, int mode, double G);
  * softened kernel - ws = 1 then beats the accuracy monopoles need ws = 2 for, at 40 % of the cost
  * (DESIGN 5.7).                                                                                         */
 int sphx_set_gravity_order(sphx_ctx* ctx, int order);
+/* Potential and potential energy of the resident state at its current positions and masses (the ones
+ * sphx_state_download and the composition download return), in the mode of sphx_state_set_gravity (SPHX_E_STATE when
+ * none is set): the state is gathered into particle-id order on the device and handed to the routine behind
+ * sphx_gravity_direct_pot / sphx_gravity_tree_pot (ws and order of the step; eps = median of the state's sizes, 0 before
+ * the first step), so phi by id is that call's bits on the downloaded state.  pot_by_id (n), nullable.
+ * out[0] = U = 1/2 sum_i m_i phi_i, summed over the particle ids in the order of the library's ordered totals (chunks of
+ * 256 ids left to right, lane l of 256 adds chunks l, l + 256, ..., then a binary tree): the same bits on every call and
+ * in every storage order, no floating-point atomic.  out[1] = sum m (same order), out[2] = eps, out[3] = the number of
+ * rows whose phi is not finite.  Tree mode builds a grid and pyramid of its own for the current positions and leaves
+ * everything the next step reads as it was.  Only the potential: no acceleration is written.                          */
+int sphx_state_gravity_potential(sphx_ctx* ctx, double* pot_by_id, double out[4]);
 /* One or more passes of the hot path.  k = N_NEIGH, dist = distance_upper_bound of
  * nsc:544 (<= 0 or inf: unbounded), first != 0: the first step uses dt_0/10 (drv:223-224);
  * fixed_dt > 0 overrides the crossing-time rule (drv:225-229).                           */

@@ -84,6 +84,10 @@ SIGNATURES = {
     "sphx_gravity_tree": (C.c_int, [_P, C.c_int64, _D, _D, _D, C.c_double, C.c_double, C.c_int, C.c_int, _D]),
     "sphx_gravity_tree_parts": (C.c_int, [_P, C.c_int64, _D, _D, _D, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
                                           c_int32_p, _D, _I]),
+    "sphx_gravity_direct_pot": (C.c_int, [_P, C.c_int64, _D, _D, _D, C.c_double, C.c_double, _D, _D]),
+    "sphx_gravity_tree_pot": (C.c_int, [_P, C.c_int64, _D, _D, _D, C.c_double, C.c_double, C.c_int, _D, _D]),
+    "sphx_state_gravity_potential": (C.c_int, [_P, _D, _D]),
+    "sphx_gravpot_last_timing": (C.c_int, [_P, _D]),
     "sphx_step": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double]),
     "sphx_state_download": (C.c_int, [_P] + [_D] * 10),
     "sphx_state_download_pressure": (C.c_int, [_P, _D]),

@@ -318,6 +318,45 @@ def grav_force_tree(mass, points, sizes, G=6.67430e-11, ws=1, order=2):
     return out
 
 
+GRAVPOT_STAGES = ("upload", "build", "sum", "download")
+
+
+def _gravpot_args(mass, points, sizes, return_accel):
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    n = pts.shape[0]
+    return (n, np.ascontiguousarray(mass, dtype=np.float64), pts, np.ascontiguousarray(sizes, dtype=np.float64),
+            np.empty((n, 3)) if return_accel else None, np.empty(n))
+
+
+def grav_potential_direct(mass, points, sizes, G=6.67430e-11, return_accel=False):
+    """The potential of grav_force_direct's sum, (n,) in J/kg: phi_i = -G sum_{j != i} m_j / sqrt(|x_j - x_i|^2 + eps^2),
+    eps = median(sizes); row i is left out of its own sum by index (include/sphx.h: sphx_gravity_direct_pot).
+    U = 0.5 * np.sum(mass * phi).  return_accel: -> (phi, accel), accel the bits of grav_force_direct."""
+    c = context()
+    n, m, pts, h, acc, phi = _gravpot_args(mass, points, sizes, return_accel)
+    c.check(c.lib.sphx_gravity_direct_pot(c.h, n, dp(m), dp(pts), dp(h), 0.0, float(G), dp(acc), dp(phi)))
+    return (phi, acc) if return_accel else phi
+
+
+def grav_potential_tree(mass, points, sizes, G=6.67430e-11, ws=1, order=2, return_accel=False):
+    """The potential of grav_force_tree's sum by the same walk over the same cells (include/sphx.h: sphx_gravity_tree_pot):
+    a cell of order 2 adds -G [M / s + 3/2 (r.S.r) / s^5 - 1/2 tr S / s^3], of order 1 -G M / s.  return_accel:
+    -> (phi, accel), accel the bits of grav_force_tree."""
+    c = context()
+    n, m, pts, h, acc, phi = _gravpot_args(mass, points, sizes, return_accel)
+    c.check(c.lib.sphx_set_gravity_order(c.h, int(order)))
+    try:
+        c.check(c.lib.sphx_gravity_tree_pot(c.h, n, dp(m), dp(pts), dp(h), 0.0, float(G), int(ws), dp(acc), dp(phi)))
+    finally:
+        c.lib.sphx_set_gravity_order(c.h, 2)
+    return (phi, acc) if return_accel else phi
+
+
+def gravpot_last_timing():
+    """Device time of the last grav_potential_* call of this module from HIP events -> dict of ms (GRAVPOT_STAGES)."""
+    return _last_timing("sphx_gravpot_last_timing", GRAVPOT_STAGES)
+
+
 def grav_force_tree_parts(mass, points, sizes, part_of, G=6.67430e-11, ws=1, order=2, return_counts=False):
     """grav_force_tree over a cloud held in parts (domains of an out-of-core run, ranks of a decomposed one): every part
     builds the pyramid over its own particles and sums its own field; to each other part it sends its mass as a flat

@@ -214,7 +214,7 @@ extern "C" void sphx_destroy(sphx_ctx* ctx) {
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (int i = 0; i < 10; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t, &ctx->chem_t, &ctx->phase_t, &ctx->radphase_t, &ctx->radstate_t, &ctx->ins_t})
+    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t, &ctx->chem_t, &ctx->phase_t, &ctx->radphase_t, &ctx->radstate_t, &ctx->ins_t, &ctx->gravpot_t})
         for (int i = 0; i < 6; ++i)
             if (t->ev[i]) (void)hipEventDestroy(t->ev[i]);
     for (int i = 0; i <= SPHX_SN_STAGES; ++i)
@@ -325,6 +325,7 @@ extern "C" int sphx_phase_last_timing(sphx_ctx* ctx, double ms[5]) { return last
 extern "C" int sphx_state_radphase_last_timing(sphx_ctx* ctx, double ms[5]) { return last_timing(ctx, &sphx_ctx::radstate_t, ms); }
 extern "C" int sphx_radphase_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::radphase_t, ms); }
 extern "C" int sphx_insert_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::ins_t, ms); }
+extern "C" int sphx_gravpot_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::gravpot_t, ms); }
 
 // =============================================================================================
 // nsc.neighbors                                                                nsc:541-552

@@ -18,19 +18,26 @@
 
 #define GRAV_TILE 256
 
+// POT: the potential beside the acceleration (include/sphx.h: phi_i = -G sum_{j != i} m_j / s).  Every term's 1 / s is the
+// `inv` its acceleration term forms; row i is left out of its own sum by STORAGE INDEX (at eps > 0 the self term would be
+// m_i / eps, larger than the rest of the sum by D / eps: adding it and taking it off again leaves nothing of the sum).
+// A lane adds its phi terms in the order of its acceleration terms.  POT = false is the kernel without any of it, and
+// POT = true forms the same acceleration bits (acc may then be NULL: nothing stored).
+template <bool POT>
 __global__ __launch_bounds__(GRAV_TILE) void gravity_direct_kernel(int n, const double* __restrict__ x,
                                                                    const double* __restrict__ y,
                                                                    const double* __restrict__ z, int ps,
                                                                    const double* __restrict__ m,
                                                                    const double* eps_ptr, double eps_val, double G,
-                                                                   const int* __restrict__ omap, double* acc) {
+                                                                   const int* __restrict__ omap, double* acc,
+                                                                   double* pot) {
     __shared__ double4 tile[GRAV_TILE];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const double eps = eps_ptr ? *eps_ptr : eps_val;
     const double e2 = eps * eps;
     double xi = 0.0, yi = 0.0, zi = 0.0;
     if (i < n) { xi = x[(size_t)i * ps]; yi = y[(size_t)i * ps]; zi = z[(size_t)i * ps]; }
-    double ax = 0.0, ay = 0.0, az = 0.0;
+    double ax = 0.0, ay = 0.0, az = 0.0, ph = 0.0;
     for (int j0 = 0; j0 < n; j0 += GRAV_TILE) {
         const int j = j0 + threadIdx.x;
         double4 s = make_double4(0.0, 0.0, 0.0, 0.0);          // padding sources have no mass
@@ -53,11 +60,13 @@ __global__ __launch_bounds__(GRAV_TILE) void gravity_direct_kernel(int n, const 
             }
             const double w = q.w * (inv * inv * inv);
             ax += w * dx; ay += w * dy; az += w * dz;
+            if (POT) ph = __builtin_fma(j0 + t == i ? 0.0 : q.w, inv, ph);
         }
     }
     if (i < n) {
         const int o = omap ? omap[i] : i;
-        acc[3 * (size_t)o] = G * ax; acc[3 * (size_t)o + 1] = G * ay; acc[3 * (size_t)o + 2] = G * az;
+        if (!POT || acc) { acc[3 * (size_t)o] = G * ax; acc[3 * (size_t)o + 1] = G * ay; acc[3 * (size_t)o + 2] = G * az; }
+        if (POT) pot[o] = -G * ph;
     }
 }
 
@@ -84,16 +93,27 @@ int sphx_median(sphx_ctx* ctx, int64_t n, const double* v, double* out_dev) {
 int sphx_gravity_launch(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, int ps,
                         const double* m, const double* eps_dev, double eps, double G, const int* omap,
                         double* acc) {
-    hipLaunchKernelGGL(gravity_direct_kernel, dim3((unsigned)((n + GRAV_TILE - 1) / GRAV_TILE)), dim3(GRAV_TILE), 0,
-                       ctx->stream, (int)n, x, y, z, ps, m, eps_dev, eps, G, omap, acc);
+    return sphx_gravity_pot_launch(ctx, n, x, y, z, ps, m, eps_dev, eps, G, omap, acc, nullptr);
+}
+int sphx_gravity_pot_launch(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, int ps,
+                            const double* m, const double* eps_dev, double eps, double G, const int* omap,
+                            double* acc, double* pot) {
+    const dim3 grid((unsigned)((n + GRAV_TILE - 1) / GRAV_TILE)), block(GRAV_TILE);
+    if (pot)
+        hipLaunchKernelGGL(gravity_direct_kernel<true>, grid, block, 0, ctx->stream, (int)n, x, y, z, ps, m, eps_dev, eps, G,
+                           omap, acc, pot);
+    else
+        hipLaunchKernelGGL(gravity_direct_kernel<false>, grid, block, 0, ctx->stream, (int)n, x, y, z, ps, m, eps_dev, eps, G,
+                           omap, acc, pot);
     HIPCHK(hipGetLastError());
     return SPHX_OK;
 }
 
-extern "C" int sphx_gravity_direct(sphx_ctx* ctx, int64_t n, const double* mass, const double* points,
-                                   const double* sizes, double softening, double G, double* accel) {
+// sphx_gravity_direct (pot == NULL) and sphx_gravity_direct_pot (accel nullable) on host arrays
+static int grav_direct_host(sphx_ctx* ctx, const char* who, int64_t n, const double* mass, const double* points,
+                            const double* sizes, double softening, double G, double* accel, double* pot) {
     if (!ctx) return SPHX_E_ARG;
-    if (!mass || !points || !accel) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_gravity_direct: NULL argument");
+    if (!mass || !points || !(pot || accel)) return sphx_set_err(ctx, SPHX_E_ARG, "%s: NULL argument", who);
     if (n < 1 || n > 0x7FFFFFF0ll) return sphx_set_err(ctx, SPHX_E_ARG, "n=%lld out of range", (long long)n);
     if (!sizes && !(softening >= 0.0)) return sphx_set_err(ctx, SPHX_E_ARG, "softening must be >= 0");
     HIPCHK(hipSetDevice(ctx->device));
@@ -101,6 +121,10 @@ extern "C" int sphx_gravity_direct(sphx_ctx* ctx, int64_t n, const double* mass,
     SPHX_TRY(sphx_ensure(ctx, ctx->in_a, 3 * nb));
     SPHX_TRY(sphx_ensure(ctx, ctx->in_b, nb));
     SPHX_TRY(sphx_ensure(ctx, ctx->out_b, 3 * nb));
+    if (pot) {
+        SPHX_TRY(sphx_ensure(ctx, ctx->gravpot_buf, nb));
+        SPHX_TRY(ctx->gravpot_t.begin(ctx));
+    }
     HIPCHK(hipMemcpyAsync(ctx->in_a.p, points, 3 * nb, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->in_b.p, mass, nb, hipMemcpyHostToDevice, ctx->stream));
     const double* eps_dev = nullptr;
@@ -112,11 +136,27 @@ extern "C" int sphx_gravity_direct(sphx_ctx* ctx, int64_t n, const double* mass,
         eps_dev = slot;
     }
     const double* p = ctx->in_a.as<double>();
-    SPHX_TRY(sphx_gravity_launch(ctx, n, p, p + 1, p + 2, 3, ctx->in_b.as<double>(), eps_dev, softening, G, nullptr,
-                                 ctx->out_b.as<double>()));
-    HIPCHK(hipMemcpyAsync(accel, ctx->out_b.p, 3 * nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (pot) { SPHX_TRY(ctx->gravpot_t.mark(ctx, 1)); SPHX_TRY(ctx->gravpot_t.mark(ctx, 2)); }
+    SPHX_TRY(sphx_gravity_pot_launch(ctx, n, p, p + 1, p + 2, 3, ctx->in_b.as<double>(), eps_dev, softening, G, nullptr,
+                                     accel ? ctx->out_b.as<double>() : nullptr, pot ? ctx->gravpot_buf.as<double>() : nullptr));
+    if (pot) SPHX_TRY(ctx->gravpot_t.mark(ctx, 3));
+    if (accel) HIPCHK(hipMemcpyAsync(accel, ctx->out_b.p, 3 * nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (pot) {
+        HIPCHK(hipMemcpyAsync(pot, ctx->gravpot_buf.p, nb, hipMemcpyDeviceToHost, ctx->stream));
+        SPHX_TRY(ctx->gravpot_t.mark(ctx, 4));
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    return SPHX_OK;
+    return pot ? ctx->gravpot_t.end(ctx) : SPHX_OK;
+}
+extern "C" int sphx_gravity_direct(sphx_ctx* ctx, int64_t n, const double* mass, const double* points,
+                                   const double* sizes, double softening, double G, double* accel) {
+    if (ctx && !accel) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_gravity_direct: NULL argument");
+    return grav_direct_host(ctx, "sphx_gravity_direct", n, mass, points, sizes, softening, G, accel, nullptr);
+}
+extern "C" int sphx_gravity_direct_pot(sphx_ctx* ctx, int64_t n, const double* mass, const double* points,
+                                       const double* sizes, double softening, double G, double* accel, double* pot) {
+    if (ctx && !pot) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_gravity_direct_pot: NULL argument");
+    return grav_direct_host(ctx, "sphx_gravity_direct_pot", n, mass, points, sizes, softening, G, accel, pot);
 }
 
 // =================================================================================================
@@ -233,8 +273,18 @@ __global__ __launch_bounds__(256) void pyr_up_kernel(Pyr py, int l, double4* pyr
 // s2 = 0 (no softening, and the cell's centre exactly on the particle: the wave kernel also runs, with f = 0, over the
 // lane's own cell, and a lone particle's cell IS the particle) contributes nothing - as a coincident pair does in the
 // direct sum; without the guard that term is 0 * inf.
+// POT (every term below): the potential of the same record into *ph, as the positive sum the kernels store as -G ph -
+//   a particle or monopole   qp / s                                         (qp: the mass the potential counts, 0 for the
+//                                                                            lane's own row and for a masked record)
+//   a cell of order 2        f [ M / s + 3/2 (r.S.r) / s^5 - 1/2 tr S / s^3 ]
+// the second-order expansion of 1 / sqrt(|c + d - x|^2 + eps^2) in d summed over the cell, whose negative gradient in x is
+// the acceleration term beside it.  1 / s is the `inv` the term has formed (no second rsqrt), so s2 = 0 gives nothing
+// here too.  The fmas are written out: the wave kernel and the per-thread walk then round alike whatever the compiler
+// contracts around them.  POT = false: the code without it.
+template <bool POT = false>
 __device__ __forceinline__ void grav_term_quad(double4 a4, double4 b4, double4 c4, double f, double xi, double yi,
-                                               double zi, double e2, double& ax, double& ay, double& az) {
+                                               double zi, double e2, double& ax, double& ay, double& az,
+                                               double* ph = nullptr) {
     const double dx = a4.y - xi, dy = a4.z - yi, dz = a4.w - zi;
     const double r2 = dx * dx + dy * dy + dz * dz + e2;
     const double y0 = r2 > 0.0 ? __builtin_amdgcn_rsq(r2) : 0.0;
@@ -247,20 +297,29 @@ __device__ __forceinline__ void grav_term_quad(double4 a4, double4 b4, double4 c
     const double tr = b4.x + b4.y + b4.z;
     const double cr = f * (a4.x * inv3 + 7.5 * rsr * inv7 - 1.5 * tr * inv5), cq = f * 3.0 * inv5;
     ax += cr * dx - cq * srx; ay += cr * dy - cq * sry; az += cr * dz - cq * srz;
+    if (POT) {
+        const double pc = __builtin_fma(1.5 * rsr, inv5, __builtin_fma(-0.5 * tr, inv3, a4.x * inv));
+        *ph = __builtin_fma(f, pc, *ph);
+    }
 }
 
 // the same term where the softening guarantees r2 > 0 (no guard, no select)
+template <bool POT = false>
 __device__ __forceinline__ void grav_term_soft(double qx, double qy, double qz, double qm, double xi, double yi,
-                                               double zi, double e2, double& ax, double& ay, double& az) {
+                                               double zi, double e2, double& ax, double& ay, double& az,
+                                               double qp = 0.0, double* ph = nullptr) {
     const double dx = qx - xi, dy = qy - yi, dz = qz - zi;
     const double r2 = dx * dx + dy * dy + dz * dz + e2;
     const double y0 = __builtin_amdgcn_rsq(r2);
     const double inv = y0 * __builtin_fma(-0.5 * r2 * y0, y0, 1.5);
     const double w = qm * (inv * inv * inv);
     ax += w * dx; ay += w * dy; az += w * dz;
+    if (POT) *ph = __builtin_fma(qp, inv, *ph);
 }
+template <bool POT = false>
 __device__ __forceinline__ void grav_term(double qx, double qy, double qz, double qm, double xi, double yi, double zi,
-                                          double e2, double& ax, double& ay, double& az) {
+                                          double e2, double& ax, double& ay, double& az, double qp = 0.0,
+                                          double* ph = nullptr) {
     const double dx = qx - xi, dy = qy - yi, dz = qz - zi;
     const double r2 = dx * dx + dy * dy + dz * dz + e2;
     // 1/sqrt: the hardware seed (v_rsq_f64, ~2^-26) and one Newton step (~2^-51) instead of the library
@@ -273,15 +332,18 @@ __device__ __forceinline__ void grav_term(double qx, double qy, double qz, doubl
     }
     const double w = qm * (inv * inv * inv);
     ax += w * dx; ay += w * dy; az += w * dz;
+    if (POT) *ph = __builtin_fma(qp, inv, *ph);
 }
 
 // per-lane walks (each thread its own loops and loads): the per-thread kernel, and the wave kernel's
 // fall-back where a wave's particles are not neighbours (blob order has a few long jumps)
+// (POT: i is the lane's own row in x, y, z, m - left out of its potential by index)
+template <bool POT>
 __device__ __forceinline__ void near_walk_lane(const GridParams& g, int ws, int fx, int fy, int fz,
                                                const int* __restrict__ cell_start, const double* __restrict__ x,
                                                const double* __restrict__ y, const double* __restrict__ z,
                                                const double* __restrict__ m, double xi, double yi, double zi, double e2,
-                                               double& ax, double& ay, double& az) {
+                                               double& ax, double& ay, double& az, int i, double* ph) {
     const int X = fx >> 1, Y = fy >> 1, Z = fz >> 1;
     const int x0 = max(2 * (X - ws), 0), x1 = min(2 * (X + ws) + 2, g.nx);
     const int y0 = max(2 * (Y - ws), 0), y1 = min(2 * (Y + ws) + 2, g.ny);
@@ -290,13 +352,17 @@ __device__ __forceinline__ void near_walk_lane(const GridParams& g, int ws, int 
         for (int ky = y0; ky < y1; ++ky) {
             const int row = (kz * g.ny + ky) * g.nx;
             const int s = cell_start[row + x0], e = cell_start[row + x1];
-            for (int j = s; j < e; ++j) grav_term(x[j], y[j], z[j], m[j], xi, yi, zi, e2, ax, ay, az);
+            for (int j = s; j < e; ++j) {
+                const double mj = m[j];
+                grav_term<POT>(x[j], y[j], z[j], mj, xi, yi, zi, e2, ax, ay, az, POT ? (j == i ? 0.0 : mj) : 0.0, ph);
+            }
         }
 }
+template <bool POT>
 __device__ __forceinline__ void far_walk_lane(int ws, int X, int Y, int Z, int nxl, int nyl, int nzl,
                                               const double4* __restrict__ lev, const double4* __restrict__ qlev,
                                               double xi, double yi, double zi,
-                                              double e2, double& ax, double& ay, double& az) {
+                                              double e2, double& ax, double& ay, double& az, double* ph) {
     const int PX = X >> 1, PY = Y >> 1, PZ = Z >> 1;
     const int x0 = max(2 * (PX - ws), 0), x1 = min(2 * (PX + ws) + 1, nxl - 1);
     const int y0 = max(2 * (PY - ws), 0), y1 = min(2 * (PY + ws) + 1, nyl - 1);
@@ -312,15 +378,16 @@ __device__ __forceinline__ void far_walk_lane(int ws, int X, int Y, int Z, int n
                 if (!(q.x > 0.0)) continue;
                 if (qlev) {
                     const size_t cc = ((size_t)kz * nyl + ky) * nxl + kx;
-                    grav_term_quad(q, qlev[2 * cc], qlev[2 * cc + 1], 1.0, xi, yi, zi, e2, ax, ay, az);
+                    grav_term_quad<POT>(q, qlev[2 * cc], qlev[2 * cc + 1], 1.0, xi, yi, zi, e2, ax, ay, az, ph);
                 } else {
-                    grav_term(q.y, q.z, q.w, q.x, xi, yi, zi, e2, ax, ay, az);
+                    grav_term<POT>(q.y, q.z, q.w, q.x, xi, yi, zi, e2, ax, ay, az, q.x, ph);
                 }
             }
         }
     }
 }
 
+template <bool POT>
 __global__ __launch_bounds__(256) void gravity_tree_kernel(int n, GridParams g, Pyr py, int ws,
                                                            const int* __restrict__ cell_of_sorted,
                                                            const int* __restrict__ cell_start,
@@ -330,7 +397,7 @@ __global__ __launch_bounds__(256) void gravity_tree_kernel(int n, GridParams g, 
                                                            const double4* __restrict__ quad, const double* eps_ptr,
                                                            double eps_val, double G, GravRef ref,
                                                            const int* __restrict__ qorder,
-                                                           const int* __restrict__ omap, double* acc) {
+                                                           const int* __restrict__ omap, double* acc, double* pot) {
     const int p = xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const int i = qorder ? qorder[p] : p;
@@ -339,14 +406,15 @@ __global__ __launch_bounds__(256) void gravity_tree_kernel(int n, GridParams g, 
     const double xi = x[i], yi = y[i], zi = z[i];
     const int c0 = cell_of_sorted[i];
     const int fx = c0 % g.nx, fy = (c0 / g.nx) % g.ny, fz = c0 / (g.nx * g.ny);
-    double ax = 0.0, ay = 0.0, az = 0.0;
-    near_walk_lane(g, ws, fx, fy, fz, cell_start, x, y, z, m, xi, yi, zi, e2, ax, ay, az);
+    double ax = 0.0, ay = 0.0, az = 0.0, ph = 0.0;
+    near_walk_lane<POT>(g, ws, fx, fy, fz, cell_start, x, y, z, m, xi, yi, zi, e2, ax, ay, az, i, &ph);
     const double xr = xi - ref.x, yr = yi - ref.y, zr = zi - ref.z;          // the cells' frame
     for (int l = 1; l < py.nlev; ++l)
-        far_walk_lane(ws, fx >> l, fy >> l, fz >> l, py.nx[l], py.ny[l], py.nz[l], pyr + py.off[l],
-                      quad ? quad + 2 * py.off[l] : nullptr, xr, yr, zr, e2, ax, ay, az);
+        far_walk_lane<POT>(ws, fx >> l, fy >> l, fz >> l, py.nx[l], py.ny[l], py.nz[l], pyr + py.off[l],
+                           quad ? quad + 2 * py.off[l] : nullptr, xr, yr, zr, e2, ax, ay, az, &ph);
     const int o = omap ? omap[i] : i;
-    acc[3 * (size_t)o] = G * ax; acc[3 * (size_t)o + 1] = G * ay; acc[3 * (size_t)o + 2] = G * az;
+    if (!POT || acc) { acc[3 * (size_t)o] = G * ax; acc[3 * (size_t)o + 1] = G * ay; acc[3 * (size_t)o + 2] = G * az; }
+    if (POT) pot[o] = -G * ph;
 }
 
 // ---- the same sum, one WAVE per 64 particles working through LDS -----------------------------------
@@ -384,7 +452,9 @@ __device__ __forceinline__ void lds_sync() {
 }
 
 // QUAD: cells carry quadrupoles too (three 32-B pieces per staged cell, half as many cells per stage)
-template <bool QUAD>
+// POT: the potential beside it.  A staged near-field record t of a batch is row j0 + t of the arrays, so the lane knows
+// its own record by index; a masked record adds +0.0 to phi as it does to the acceleration.
+template <bool QUAD, bool POT>
 __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParams g, Pyr py, int ws,
                                                                 const int* __restrict__ cell_of_sorted,
                                                                 const int* __restrict__ cell_start,
@@ -394,7 +464,7 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
                                                                 const double4* __restrict__ quad, const double* eps_ptr,
                                                                 double eps_val, double G, GravRef ref,
                                                                 const int* __restrict__ qorder,
-                                                                const int* __restrict__ omap, double* acc) {
+                                                                const int* __restrict__ omap, double* acc, double* pot) {
     constexpr int CB = QUAD ? GT_CB / 2 : GT_CB;      // cells staged at a time
     __shared__ double4 cbuf_all[4][QUAD ? 3 * (GT_CB / 2) : GT_CB];
     __shared__ int ibuf_all[4][64];
@@ -412,7 +482,7 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
     int c0 = cell_of_sorted[i];
     c0 = act ? c0 : __builtin_amdgcn_readfirstlane(c0);             // idle lanes (last wave) shadow lane 0
     const int fx = c0 % g.nx, fy = (c0 / g.nx) % g.ny, fz = c0 / (g.nx * g.ny);
-    double ax = 0.0, ay = 0.0, az = 0.0;
+    double ax = 0.0, ay = 0.0, az = 0.0, ph = 0.0;
     // ---- near field: particles of the level-1 cells within +-ws of the lane's level-1 cell ---------
     {
         const int X = fx >> 1, Y = fy >> 1, Z = fz >> 1;
@@ -425,7 +495,7 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
         // the wave's particles are neighbours: its union box is little more than one lane's box
         const int own = 4 * ws + 2 + GT_SLACK;
         const bool compact = ux1 - ux0 < own && uy1 - uy0 < own && uz1 - uz0 < own;
-        if (!compact) near_walk_lane(g, ws, fx, fy, fz, cell_start, x, y, z, m, xi, yi, zi, e2, ax, ay, az);
+        if (!compact) near_walk_lane<POT>(g, ws, fx, fy, fz, cell_start, x, y, z, m, xi, yi, zi, e2, ax, ay, az, i, &ph);
         for (int kz = uz0; compact && kz <= uz1; ++kz) {
             const bool zin = kz >= lz0 && kz <= lz1;
             for (int ky = uy0; ky <= uy1; ++ky) {
@@ -445,7 +515,8 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
                         const double4 q = cbuf[t];
                         const int cx = ibuf[t];
                         const bool mine = rowin && cx >= lx0 && cx <= lx1;
-                        grav_term(q.x, q.y, q.z, mine ? q.w : 0.0, xi, yi, zi, e2, ax, ay, az);
+                        grav_term<POT>(q.x, q.y, q.z, mine ? q.w : 0.0, xi, yi, zi, e2, ax, ay, az,
+                                       POT ? ((mine && j0 + t != i) ? q.w : 0.0) : 0.0, &ph);
                     }
                     lds_sync();
                 }
@@ -469,8 +540,8 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
         const int own = 4 * ws + 2 + GT_SLACK;
         if (W > 32 || W > own || uy1 - uy0 >= own || uz1 - uz0 >= own) {
             // a wave spread over more cells than neighbours would be: the per-lane walk
-            far_walk_lane(ws, X, Y, Z, nxl, nyl, nzl, lev, QUAD ? quad + 2 * py.off[l] : nullptr, xr, yr, zr, e2,
-                          ax, ay, az);
+            far_walk_lane<POT>(ws, X, Y, Z, nxl, nyl, nzl, lev, QUAD ? quad + 2 * py.off[l] : nullptr, xr, yr, zr, e2,
+                               ax, ay, az, &ph);
             continue;
         }
         const double4* qlev = QUAD ? quad + 2 * py.off[l] : nullptr;
@@ -499,26 +570,30 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
                         for (int t = 0; t < W; ++t) {
                             const double4 q = rowq[t];
                             if (!(q.x > 0.0)) continue;                           // (uniform: an empty cell)
-                            grav_term_quad(q, rowq[CB + t], rowq[2 * CB + t], ((bits >> t) & 1u) ? 1.0 : 0.0, xr, yr, zr,
-                                           e2, ax, ay, az);
+                            grav_term_quad<POT>(q, rowq[CB + t], rowq[2 * CB + t], ((bits >> t) & 1u) ? 1.0 : 0.0, xr, yr, zr,
+                                                e2, ax, ay, az, &ph);
                         }
                     } else if (soft) {
                         // r2 >= eps^2 > 0: no guard; two records in flight per trip
                         int t = 0;
                         for (; t + 1 < W; t += 2) {
                             const double4 q0 = rowq[t], q1 = rowq[t + 1];
-                            grav_term_soft(q0.y, q0.z, q0.w, ((bits >> t) & 1u) ? q0.x : 0.0, xr, yr, zr, e2, ax, ay, az);
-                            grav_term_soft(q1.y, q1.z, q1.w, ((bits >> (t + 1)) & 1u) ? q1.x : 0.0, xr, yr, zr, e2, ax, ay, az);
+                            grav_term_soft<POT>(q0.y, q0.z, q0.w, ((bits >> t) & 1u) ? q0.x : 0.0, xr, yr, zr, e2, ax, ay, az,
+                                                POT ? (((bits >> t) & 1u) ? q0.x : 0.0) : 0.0, &ph);
+                            grav_term_soft<POT>(q1.y, q1.z, q1.w, ((bits >> (t + 1)) & 1u) ? q1.x : 0.0, xr, yr, zr, e2, ax, ay, az,
+                                                POT ? (((bits >> (t + 1)) & 1u) ? q1.x : 0.0) : 0.0, &ph);
                         }
                         if (t < W) {
                             const double4 q0 = rowq[t];
-                            grav_term_soft(q0.y, q0.z, q0.w, ((bits >> t) & 1u) ? q0.x : 0.0, xr, yr, zr, e2, ax, ay, az);
+                            grav_term_soft<POT>(q0.y, q0.z, q0.w, ((bits >> t) & 1u) ? q0.x : 0.0, xr, yr, zr, e2, ax, ay, az,
+                                                POT ? (((bits >> t) & 1u) ? q0.x : 0.0) : 0.0, &ph);
                         }
                     } else {
                         for (int t = 0; t < W; ++t) {
                             const double4 q = rowq[t];
                             if (!(q.x > 0.0)) continue;                           // (uniform: an empty cell)
-                            grav_term(q.y, q.z, q.w, ((bits >> t) & 1u) ? q.x : 0.0, xr, yr, zr, e2, ax, ay, az);
+                            grav_term<POT>(q.y, q.z, q.w, ((bits >> t) & 1u) ? q.x : 0.0, xr, yr, zr, e2, ax, ay, az,
+                                           POT ? (((bits >> t) & 1u) ? q.x : 0.0) : 0.0, &ph);
                         }
                     }
                 }
@@ -528,7 +603,8 @@ __global__ __launch_bounds__(256) void gravity_tree_wave_kernel(int n, GridParam
     }
     if (act) {
         const int o = omap ? omap[i] : i;
-        acc[3 * (size_t)o] = G * ax; acc[3 * (size_t)o + 1] = G * ay; acc[3 * (size_t)o + 2] = G * az;
+        if (!POT || acc) { acc[3 * (size_t)o] = G * ax; acc[3 * (size_t)o + 1] = G * ay; acc[3 * (size_t)o + 2] = G * az; }
+        if (POT) pot[o] = -G * ph;
     }
 }
 
@@ -590,22 +666,23 @@ static int grav_pyramid(sphx_ctx* ctx, int64_t n, const double* x, const double*
 // the walk over a pyramid grav_pyramid built for these particles
 static int grav_tree_walk(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, const double* m,
                           const Pyr& py, const GravRef& ref, int ws, const double* eps_dev, double eps, double G,
-                          const int* omap, double* acc) {
+                          const int* omap, double* acc, double* pot = nullptr) {
     const GridParams g = ctx->grid;
     const double4* pyr = ctx->grav_pyr.as<double4>();
     const double4* quad = ctx->grav_order >= 2 ? ctx->grav_quad.as<double4>() : nullptr;
-    if (ctx->grav_per_thread)         // SPHX_GRAV_KERNEL=0: the per-thread walk (the wave kernel's reference)
-        hipLaunchKernelGGL(gravity_tree_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n, g, py,
-                           ws, ctx->grav_cell.as<int>(), ctx->cell_start.as<int>(), x, y, z, m, pyr, quad, eps_dev, eps, G,
-                           ref, ctx->qorder, omap, acc);
-    else if (quad)
-        hipLaunchKernelGGL(gravity_tree_wave_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (int)n, g, py, ws, ctx->grav_cell.as<int>(), ctx->cell_start.as<int>(), x, y, z, m, pyr, quad,
-                           eps_dev, eps, G, ref, ctx->qorder, omap, acc);
-    else
-        hipLaunchKernelGGL(gravity_tree_wave_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (int)n, g, py, ws, ctx->grav_cell.as<int>(), ctx->cell_start.as<int>(), x, y, z, m, pyr, quad,
-                           eps_dev, eps, G, ref, ctx->qorder, omap, acc);
+    // (one argument list; pot == NULL: the kernels without the potential)
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n, g, py, ws,
+                           ctx->grav_cell.as<int>(), ctx->cell_start.as<int>(), x, y, z, m, pyr, quad, eps_dev, eps, G, ref,
+                           ctx->qorder, omap, acc, pot);
+    };
+    if (ctx->grav_per_thread) {       // SPHX_GRAV_KERNEL=0: the per-thread walk (the wave kernel's reference)
+        if (pot) launch(gravity_tree_kernel<true>); else launch(gravity_tree_kernel<false>);
+    } else if (quad) {
+        if (pot) launch(gravity_tree_wave_kernel<true, true>); else launch(gravity_tree_wave_kernel<true, false>);
+    } else {
+        if (pot) launch(gravity_tree_wave_kernel<false, true>); else launch(gravity_tree_wave_kernel<false, false>);
+    }
     HIPCHK(hipGetLastError());
     return SPHX_OK;
 }
@@ -621,45 +698,165 @@ int sphx_gravity_tree_launch(sphx_ctx* ctx, int64_t n, const double* x, const do
     return grav_tree_walk(ctx, n, x, y, z, m, py, ref, ws, eps_dev, eps, G, omap, acc);
 }
 
-extern "C" int sphx_gravity_tree(sphx_ctx* ctx, int64_t n, const double* mass, const double* points,
-                                 const double* sizes, double softening, double G, int ws, int k_cells,
-                                 double* accel) {
-    if (!ctx) return SPHX_E_ARG;
-    if (!mass || !points || !accel) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_gravity_tree: NULL argument");
-    if (n < 1 || n > 0x7FFFFFF0ll) return sphx_set_err(ctx, SPHX_E_ARG, "n=%lld out of range", (long long)n);
-    if (ws < 1 || ws > 4) return sphx_set_err(ctx, SPHX_E_ARG, "ws=%d not in 1..4", ws);
-    if (!sizes && !(softening >= 0.0)) return sphx_set_err(ctx, SPHX_E_ARG, "softening must be >= 0");
-    if (k_cells < 1) k_cells = 40;
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->map_perm = nullptr;
-    ctx->qorder = nullptr;
-    const size_t nb = (size_t)n * sizeof(double);
-    DevBuf* bufs[] = {&ctx->in_b, &ctx->in_c, &ctx->in_d, &ctx->in_e, &ctx->in_f, &ctx->in_g, &ctx->in_h, &ctx->in_i};
-    for (DevBuf* b : bufs) SPHX_TRY(sphx_ensure(ctx, *b, nb));
-    SPHX_TRY(sphx_ensure(ctx, ctx->in_a, 3 * nb));
-    SPHX_TRY(sphx_ensure(ctx, ctx->out_b, 3 * nb));
-    HIPCHK(hipMemcpyAsync(ctx->in_a.p, points, 3 * nb, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->in_h.p, mass, nb, hipMemcpyHostToDevice, ctx->stream));
+// The array call's route on the device, for a cloud in any order: x, y, z in ctx->in_b, in_c, in_d and the masses in
+// ctx->in_h (n each; in_e .. in_g, in_i: sized by the caller) -> a fresh grid over them (k_cells), the cell-sorted copies,
+// the pyramid and the walk; acc (n,3) and pot (n) in the caller's order.  pot == NULL: sphx_gravity_tree's launches.
+// pot != NULL: the caller has begun ctx->gravpot_t; its stage 2 (grid and pyramid done) is marked here.
+// sphx_state_gravity_potential comes through here with the state in id order: hence that call's bits.
+static int grav_tree_side(sphx_ctx* ctx, int64_t n, int k_cells, int ws, const double* eps_dev, double eps, double G,
+                          double* acc, double* pot) {
     double *x = ctx->in_b.as<double>(), *y = ctx->in_c.as<double>(), *z = ctx->in_d.as<double>();
     double *xs = ctx->in_e.as<double>(), *ys = ctx->in_f.as<double>(), *zs = ctx->in_g.as<double>();
-    SPHX_TRY(sphx_aos_to_soa3(ctx, n, ctx->in_a.as<double>(), x, y, z));
+    ctx->map_perm = nullptr;
+    ctx->qorder = nullptr;
     ctx->clip_valid = false;
     SPHX_TRY(sphx_build_grid(ctx, n, k_cells, x, y, z, 0.0));
     SPHX_TRY(sphx_gather3(ctx, n, ctx->perm.as<int>(), x, y, z, xs, ys, zs));
     hipLaunchKernelGGL(gather1_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n,
                        ctx->perm.as<int>(), ctx->in_h.as<double>(), ctx->in_i.as<double>());
+    Pyr py;
+    GravRef ref;
+    SPHX_TRY(grav_pyramid(ctx, n, xs, ys, zs, ctx->in_i.as<double>(), py, ref));
+    if (pot) SPHX_TRY(ctx->gravpot_t.mark(ctx, 2));
+    return grav_tree_walk(ctx, n, xs, ys, zs, ctx->in_i.as<double>(), py, ref, ws, eps_dev, eps, G, ctx->perm.as<int>(), acc, pot);
+}
+static int grav_tree_side_bufs(sphx_ctx* ctx, size_t nb) {
+    DevBuf* bufs[] = {&ctx->in_b, &ctx->in_c, &ctx->in_d, &ctx->in_e, &ctx->in_f, &ctx->in_g, &ctx->in_h, &ctx->in_i};
+    for (DevBuf* b : bufs) SPHX_TRY(sphx_ensure(ctx, *b, nb));
+    return SPHX_OK;
+}
+
+// sphx_gravity_tree (pot == NULL) and sphx_gravity_tree_pot (accel nullable) on host arrays
+static int grav_tree_host(sphx_ctx* ctx, const char* who, int64_t n, const double* mass, const double* points,
+                          const double* sizes, double softening, double G, int ws, int k_cells, double* accel, double* pot) {
+    if (!ctx) return SPHX_E_ARG;
+    if (!mass || !points || !(pot || accel)) return sphx_set_err(ctx, SPHX_E_ARG, "%s: NULL argument", who);
+    if (n < 1 || n > 0x7FFFFFF0ll) return sphx_set_err(ctx, SPHX_E_ARG, "n=%lld out of range", (long long)n);
+    if (ws < 1 || ws > 4) return sphx_set_err(ctx, SPHX_E_ARG, "ws=%d not in 1..4", ws);
+    if (!sizes && !(softening >= 0.0)) return sphx_set_err(ctx, SPHX_E_ARG, "softening must be >= 0");
+    if (k_cells < 1) k_cells = 40;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t nb = (size_t)n * sizeof(double);
+    SPHX_TRY(grav_tree_side_bufs(ctx, nb));
+    SPHX_TRY(sphx_ensure(ctx, ctx->in_a, 3 * nb));
+    SPHX_TRY(sphx_ensure(ctx, ctx->out_b, 3 * nb));
+    if (pot) {
+        SPHX_TRY(sphx_ensure(ctx, ctx->gravpot_buf, nb));
+        SPHX_TRY(ctx->gravpot_t.begin(ctx));
+    }
+    HIPCHK(hipMemcpyAsync(ctx->in_a.p, points, 3 * nb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->in_h.p, mass, nb, hipMemcpyHostToDevice, ctx->stream));
+    SPHX_TRY(sphx_aos_to_soa3(ctx, n, ctx->in_a.as<double>(), ctx->in_b.as<double>(), ctx->in_c.as<double>(),
+                              ctx->in_d.as<double>()));
     const double* eps_dev = nullptr;
-    if (sizes) {
+    if (sizes) {                                   // (in_a is free again: the positions are in in_b .. in_d)
         HIPCHK(hipMemcpyAsync(ctx->in_a.p, sizes, nb, hipMemcpyHostToDevice, ctx->stream));
         double* slot = ctx->scal.as<double>() + SC_GRAV_EPS;
         SPHX_TRY(sphx_median(ctx, n, ctx->in_a.as<double>(), slot));
         eps_dev = slot;
     }
-    SPHX_TRY(sphx_gravity_tree_launch(ctx, n, xs, ys, zs, ctx->in_i.as<double>(), ws, eps_dev, softening, G,
-                                      ctx->perm.as<int>(), ctx->out_b.as<double>()));
-    HIPCHK(hipMemcpyAsync(accel, ctx->out_b.p, 3 * nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (pot) SPHX_TRY(ctx->gravpot_t.mark(ctx, 1));
+    SPHX_TRY(grav_tree_side(ctx, n, k_cells, ws, eps_dev, softening, G, accel ? ctx->out_b.as<double>() : nullptr,
+                            pot ? ctx->gravpot_buf.as<double>() : nullptr));
+    if (pot) SPHX_TRY(ctx->gravpot_t.mark(ctx, 3));
+    if (accel) HIPCHK(hipMemcpyAsync(accel, ctx->out_b.p, 3 * nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (pot) {
+        HIPCHK(hipMemcpyAsync(pot, ctx->gravpot_buf.p, nb, hipMemcpyDeviceToHost, ctx->stream));
+        SPHX_TRY(ctx->gravpot_t.mark(ctx, 4));
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    return SPHX_OK;
+    return pot ? ctx->gravpot_t.end(ctx) : SPHX_OK;
+}
+extern "C" int sphx_gravity_tree(sphx_ctx* ctx, int64_t n, const double* mass, const double* points,
+                                 const double* sizes, double softening, double G, int ws, int k_cells,
+                                 double* accel) {
+    if (ctx && !accel) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_gravity_tree: NULL argument");
+    return grav_tree_host(ctx, "sphx_gravity_tree", n, mass, points, sizes, softening, G, ws, k_cells, accel, nullptr);
+}
+extern "C" int sphx_gravity_tree_pot(sphx_ctx* ctx, int64_t n, const double* mass, const double* points,
+                                     const double* sizes, double softening, double G, int ws, double* accel, double* pot) {
+    if (ctx && !pot) return sphx_set_err(ctx, SPHX_E_ARG, "sphx_gravity_tree_pot: NULL argument");
+    return grav_tree_host(ctx, "sphx_gravity_tree_pot", n, mass, points, sizes, softening, G, ws, 40, accel, pot);
+}
+
+// ---- potential and potential energy of the resident state (include/sphx.h: sphx_state_gravity_potential) ----
+// The state goes into particle-id order first (the order sphx_state_download hands out), then through the array calls'
+// own routes: phi by id is then the array call's bits on the downloaded state in every storage order, and the total is
+// an ordered one over the ids.  Buffers of its own and the array calls' staging; the state itself is only read.
+// the terms of the totals by id: pp (2, n) = {1/2 m phi, m}; tail[2] = eps, tail[3] = the count of non-finite phi (u64,
+// an integer atomic per wave that saw one; zeroed by the caller)
+__global__ __launch_bounds__(256) void gravpot_terms_kernel(int n, const double* __restrict__ m, const double* __restrict__ phi,
+                                                            const double* __restrict__ eps_ptr, double* __restrict__ pp,
+                                                            double* __restrict__ tail) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < n;
+    double ph = 0.0;
+    if (live) {
+        const double mi = m[i];
+        ph = phi[i];
+        pp[i] = 0.5 * mi * ph;
+        pp[(size_t)n + i] = mi;
+    }
+    const u64 bad = __ballot(live && !sphx_finite(ph));
+    if ((threadIdx.x & (SPHX_WAVE - 1)) == 0 && bad) atomicAdd((u64*)(tail + 3), (u64)__popcll(bad));
+    if (i == 0) tail[2] = *eps_ptr;
+}
+
+extern "C" int sphx_state_gravity_potential(sphx_ctx* ctx, double* pot_by_id, double out[4]) {
+    if (!ctx) return SPHX_E_ARG;
+    const char* who = "sphx_state_gravity_potential";
+    if (!ctx->has_state) return sphx_set_err(ctx, SPHX_E_STATE, "%s: no state uploaded", who);
+    if (!ctx->gravity) return sphx_set_err(ctx, SPHX_E_STATE, "%s: no gravity mode is set (sphx_state_set_gravity)", who);
+    NEED(out);
+    const int64_t n = ctx->n;
+    if (n < 1 || n > 0x7FFFFFF0ll) return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld out of range", who, (long long)n);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t nn = (size_t)n, nb = nn * sizeof(double), nchunk = sphx_tot_chunks(n);
+    if (ctx->gravity == 1) {
+        for (DevBuf* b : {&ctx->in_b, &ctx->in_c, &ctx->in_d, &ctx->in_h}) SPHX_TRY(sphx_ensure(ctx, *b, nb));
+    } else {
+        SPHX_TRY(grav_tree_side_bufs(ctx, nb));
+    }
+    // ctx->gravpot_buf: phi by id (n) | pp (2, n) | part (2, nchunk) | tot: U, sum m, eps, bad (4)
+    SPHX_TRY(sphx_ensure(ctx, ctx->gravpot_buf, (3 * nn + 2 * nchunk + 4) * sizeof(double)));
+    double* phi = ctx->gravpot_buf.as<double>();
+    double *pp = phi + nn, *part = pp + 2 * nn, *tot = part + 2 * nchunk;
+    SPHX_TRY(ctx->gravpot_t.begin(ctx));
+    const StateArrays& s = ctx->st;
+    const int* id = s.id.as<int>();
+    double *x = ctx->in_b.as<double>(), *y = ctx->in_c.as<double>(), *z = ctx->in_d.as<double>(), *m = ctx->in_h.as<double>();
+    SPHX_TRY(sphx_scatter_rows_by_id(ctx, n, 1, id, s.x.as<double>(), x));
+    SPHX_TRY(sphx_scatter_rows_by_id(ctx, n, 1, id, s.y.as<double>(), y));
+    SPHX_TRY(sphx_scatter_rows_by_id(ctx, n, 1, id, s.z.as<double>(), z));
+    SPHX_TRY(sphx_scatter_rows_by_id(ctx, n, 1, id, s.m.as<double>(), m));
+    double* eps = ctx->scal.as<double>() + SC_GRAV_EPS;             // (the step forms its own before it reads the slot)
+    SPHX_TRY(sphx_median(ctx, n, s.hprev.as<double>(), eps));
+    SPHX_TRY(ctx->gravpot_t.mark(ctx, 1));
+    int rc;
+    if (ctx->gravity == 1) {
+        SPHX_TRY(ctx->gravpot_t.mark(ctx, 2));
+        rc = sphx_gravity_pot_launch(ctx, n, x, y, z, 1, m, eps, 0.0, ctx->grav_G, nullptr, nullptr, phi);
+    } else {
+        // a grid of its own between two steps, as sphx_state_sample builds one: the host side goes back as it was
+        const GridHostState saved = sphx_grid_host_save(ctx);
+        rc = grav_tree_side(ctx, n, 40, ctx->grav_ws, eps, 0.0, ctx->grav_G, nullptr, phi);
+        sphx_grid_host_restore(ctx, saved);
+    }
+    SPHX_TRY(rc);
+    HIPCHK(hipMemsetAsync(tot, 0, 4 * sizeof(double), st));
+    hipLaunchKernelGGL(gravpot_terms_kernel, dim3(sphx_blocks(nn, 256)), dim3(256), 0, st, (int)n, m, phi, eps, pp, tot);
+    HIPCHK(hipGetLastError());
+    SPHX_TRY(sphx_ordered_totals(ctx, n, 2, pp, part, tot));
+    SPHX_TRY(ctx->gravpot_t.mark(ctx, 3));
+    u64* back = ctx->pinned->census;
+    HIPCHK(hipMemcpyAsync(back, tot, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (pot_by_id) HIPCHK(hipMemcpyAsync(pot_by_id, phi, nb, hipMemcpyDeviceToHost, st));
+    SPHX_TRY(ctx->gravpot_t.mark(ctx, 4));
+    HIPCHK(hipStreamSynchronize(st));
+    memcpy(out, back, 3 * sizeof(double));
+    out[3] = (double)back[3];
+    return ctx->gravpot_t.end(ctx);
 }
 
 // =================================================================================================

@@ -494,6 +494,12 @@ struct sphx_ctx {
     bool star_ages_valid = false;
     double census_tab[SPHX_MAX_SPECIES] = {0};     // mu_specie on the host, uploaded from here
     StageTimer census_t;
+    // the potential calls (sphx_gravity.hip).  gravpot_buf: phi (n) of the array calls; of the resident call phi by id |
+    // 1/2 m phi | m (n each) | their chunk sums (2 x chunks) | U, sum m, eps, the count of non-finite phi (4).  The state by
+    // particle id is staged in in_b, in_c, in_d, in_h like an array call's input.  The state itself is only read.
+    // events: [0] start, [1] inputs on the device and eps, [2] grid and pyramid (tree), [3] the sums, [4] outputs on the host
+    DevBuf gravpot_buf;
+    StageTimer gravpot_t;
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
@@ -678,6 +684,11 @@ int sphx_gravity_launch(sphx_ctx* ctx, int64_t n, const double* x, const double*
 int sphx_gravity_tree_launch(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z,
                              const double* m, int ws, const double* eps_dev, double eps, double G, const int* omap,
                              double* acc);
+// the direct sum with the potential beside it (pot (n), J/kg, at omap[i] or i; acc may then be NULL).  pot == NULL: the
+// call above, kernel for kernel.
+int sphx_gravity_pot_launch(sphx_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, int ps,
+                            const double* m, const double* eps_dev, double eps, double G, const int* omap,
+                            double* acc, double* pot);
 int sphx_dev_collect(sphx_ctx* ctx);
 int sphx_loop_step_sums(sphx_ctx* ctx, int64_t n, int k, double d);
 // defer_scatter: the order's last scatter is left to the kernel that permutes the state next (sphx_permute_state finds

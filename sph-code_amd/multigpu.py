@@ -702,6 +702,15 @@ class DistributedSim:
         """The census' fixed order of summation runs over one context's particle ids: not built across ranks."""
         raise NotImplementedError("census is not available in the decomposed step (single-GPU Simulation only)")
 
+    def gravity_potential(self, *a, **kw):
+        """The potential's walk and its ordered total run over one context's particles: the exported multipoles between
+        ranks carry no potential (out of scope)."""
+        raise NotImplementedError("gravity_potential is not available in the decomposed step (single-GPU Simulation only)")
+
+    def energy(self, *a, **kw):
+        """Needs census() and gravity_potential(): neither is built across ranks."""
+        raise NotImplementedError("energy is not available in the decomposed step (single-GPU Simulation only)")
+
     def __init__(self, state, lo, hi, backend, rank=0, world=1, device="cpu", comm_device=None,
                  halo_scale=1.15, skin_frac=0.15, need_grid=96, migrate_every=4, forms="hydro_update", d=None,
                  with_drag=False, with_species=False, agb=None, visc_mode=None, gravity=None, G=6.67430e-11, gravity_ws=1,

@@ -640,6 +640,47 @@ class Simulation:
         c.check(c.lib.sphx_census_last_timing(c.h, dp(ms)))
         return dict(zip(compat.CENSUS_STAGES, ms.tolist()))
 
+    # ---- what the run's self-gravity does to its energy (include/sphx.h sphx_state_gravity_potential) ----
+    def gravity_potential(self, by_id=False):
+        """Potential energy of the state as it is on the device, in the mode of the step's gravity (gravity="direct", or
+        "tree" with the step's kernels, ws and order - over a side grid built for the call as compat.grav_potential_tree
+        builds it, not over the step's own cells; raises when the simulation has no gravity) -> dict: U = 1/2 sum m phi [J] in the
+        order of the ordered totals over the particle ids (the same bits in every storage order), eps (the softening:
+        median of the sizes, 0 before the first step), total_mass, bad (rows whose phi is not finite) and, with by_id,
+        phi (n,) [J/kg] - the bits of compat.grav_potential_direct / _tree on download() and download_composition()'s
+        mass.  Four numbers come back unless by_id.  The state and what the next step reads are left as they were."""
+        phi = np.empty(self.n) if by_id else None
+        out = np.zeros(4)
+        c = self.ctx
+        c.check(c.lib.sphx_state_gravity_potential(c.h, dp(phi), dp(out)))
+        res = dict(U=float(out[0]), total_mass=float(out[1]), eps=float(out[2]), bad=int(out[3]))
+        if by_id:
+            res["phi"] = phi
+        return res
+
+    def gravpot_timing(self):
+        """Device time of the last gravity_potential() from HIP events -> dict of ms (compat.GRAVPOT_STAGES)."""
+        from . import compat
+        ms = np.zeros(4)
+        c = self.ctx
+        c.check(c.lib.sphx_gravpot_last_timing(c.h, dp(ms)))
+        return dict(zip(compat.GRAVPOT_STAGES, ms.tolist()))
+
+    def energy(self):
+        """The energy budget of a self-gravitating run -> dict: kinetic and internal as census() forms them (its bits; the
+        sums by species are left out, so no mu_specie table is needed), potential from gravity_potential(), total (their
+        sum) and virial = 2 kinetic / |potential|.  No N-sized array is downloaded."""
+        from . import compat
+        tot = np.zeros(compat.CENSUS_FIXED); counts = np.zeros(4, dtype=np.int64); mx = np.zeros(1)
+        c = self.ctx
+        c.check(c.lib.sphx_state_census(c.h, None, dp(tot), _lib.ip(counts), dp(mx)))      # (no sums by species: no table needed)
+        cen = compat._census_result(tot, counts, mx[0], 0)
+        pot = self.gravity_potential()
+        kin, inte, U = float(cen["kinetic"]), float(cen["internal"]), pot["U"]
+        with np.errstate(all="ignore"):
+            virial = float(np.float64(2.0 * kin) / np.float64(abs(U)))
+        return dict(kinetic=kin, internal=inte, potential=U, total=kin + inte + U, virial=virial)
+
     def _select(self, ptype, ages=False, f_un=False, window=None):
         """The rows of a type in ascending particle id from the device (include/sphx.h sphx_state_census_select)."""
         from . import compat
