@@ -214,9 +214,6 @@ extern "C" void sphx_destroy(sphx_ctx* ctx) {
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (int i = 0; i < 10; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    for (StageTimer* t : {&ctx->arb_t, &ctx->rad_t, &ctx->cool_t, &ctx->dust_t, &ctx->chem_t, &ctx->phase_t, &ctx->radphase_t, &ctx->radstate_t, &ctx->ins_t, &ctx->gravpot_t})
-        for (int i = 0; i < 6; ++i)
-            if (t->ev[i]) (void)hipEventDestroy(t->ev[i]);
     for (int i = 0; i <= SPHX_SN_STAGES; ++i)
         if (ctx->sn_ev[i]) (void)hipEventDestroy(ctx->sn_ev[i]);
     for (int r = 0; r < 3; ++r)
@@ -308,12 +305,6 @@ int StageTimer::end(sphx_ctx* ctx) {
         HIPCHK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
         ms[i] = t;
     }
-    return SPHX_OK;
-}
-// Device time of the stages of the family's last call on this context, from HIP events on its stream.
-static int last_timing(sphx_ctx* ctx, StageTimer sphx_ctx::*t, double* ms) {
-    if (!ctx || !ms) return SPHX_E_ARG;
-    for (int i = 0; i < (ctx->*t).stages; ++i) ms[i] = (ctx->*t).ms[i];
     return SPHX_OK;
 }
 extern "C" int sphx_arb_last_timing(sphx_ctx* ctx, double ms[4]) { return last_timing(ctx, &sphx_ctx::arb_t, ms); }

@@ -422,33 +422,39 @@ struct ArbHostOut { double *density, *dust_density, *temperature, *dust_temperat
 
 // device output block [6][m] in ctx->arb_out, pointers only for what the caller wants and the inputs allow
 static int arb_out_ptrs(sphx_ctx* ctx, int64_t m, const ArbHostOut& h, bool has_sizes, bool has_T, bool has_ph, ArbOutPtrs* o) {
-    SPHX_TRY(sphx_ensure(ctx, ctx->arb_out, (size_t)(m > 0 ? m : 1) * 6 * sizeof(double)));
-    double* b = ctx->arb_out.as<double>();
-    o->density = h.density ? b : nullptr;
-    o->dust_density = (h.dust_density && has_sizes) ? b + m : nullptr;
-    o->temperature = (h.temperature && has_T) ? b + 2 * m : nullptr;
-    o->dust_temperature = (h.dust_temperature && has_sizes && has_T) ? b + 3 * m : nullptr;
-    o->photoionization = (h.photoionization && has_ph) ? b + 4 * m : nullptr;
-    o->count = h.count ? reinterpret_cast<long long*>(b + 5 * m) : nullptr;
+    const size_t mm = (size_t)(m > 0 ? m : 1);
+    Carve c;
+    c.take(o->density, mm); c.take(o->dust_density, mm); c.take(o->temperature, mm); c.take(o->dust_temperature, mm);
+    c.take(o->photoionization, mm); c.take(o->count, mm);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->arb_out, c));
+    if (!h.density) o->density = nullptr;
+    if (!(h.dust_density && has_sizes)) o->dust_density = nullptr;
+    if (!(h.temperature && has_T)) o->temperature = nullptr;
+    if (!(h.dust_temperature && has_sizes && has_T)) o->dust_temperature = nullptr;
+    if (!(h.photoionization && has_ph)) o->photoionization = nullptr;
+    if (!h.count) o->count = nullptr;
     return SPHX_OK;
 }
-static int arb_out_download(sphx_ctx* ctx, int64_t m, const ArbHostOut& h, const ArbOutPtrs& o, int64_t* candidates) {
+static int arb_out_download(sphx_ctx* ctx, int64_t m, const ArbHostOut& h, const ArbOutPtrs& o, const u64* cand_dev, int64_t* candidates) {
     const size_t md = (size_t)m;                           // (count: int64, the width of a double)
     const CopyF64 ps[] = {{h.density, o.density, md}, {h.dust_density, o.dust_density, md}, {h.temperature, o.temperature, md},
                           {h.dust_temperature, o.dust_temperature, md}, {h.photoionization, o.photoionization, md},
                           {h.count, o.count, md}};
     SPHX_TRY(sphx_download_f64(ctx, ps, 6));
     u64* cand = &ctx->pinned->side.cand;
-    HIPCHK(hipMemcpyAsync(cand, ctx->arb_red.as<double>() + 8, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(cand, cand_dev, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     SPHX_TRY(ctx->arb_t.mark(ctx, 4));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (candidates) *candidates = (int64_t)*cand;
     return ctx->arb_t.end(ctx);
 }
-// ctx->arb_red: [0..3] the reduction's result, [8] the candidates counter (u64), [16 ..] block partials
-static int arb_red_prepare(sphx_ctx* ctx) {
-    SPHX_TRY(sphx_ensure(ctx, ctx->arb_red, (size_t)(16 + 4 * ARB_RED_BLOCKS) * sizeof(double)));
-    HIPCHK(hipMemsetAsync(ctx->arb_red.p, 0, 16 * sizeof(double), ctx->stream));
+// ctx->arb_red: the reduction's result (4 of 8 doubles) | the candidates counter | from the next 128-byte line, block partials
+struct ArbRed { double* res; u64* cand; double* part; };
+static int arb_red_prepare(sphx_ctx* ctx, ArbRed* r) {
+    Carve c;
+    c.take(r->res, 8); c.take(r->cand, 1); c.take(r->part, 4 * ARB_RED_BLOCKS, 128);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->arb_red, c));
+    HIPCHK(hipMemsetAsync(r->res, 0, (size_t)(r->part - r->res) * sizeof(double), ctx->stream));
     return SPHX_OK;
 }
 
@@ -462,8 +468,8 @@ static bool arb_ball_hit(const sphx_ctx* ctx, int64_t ball_id, int64_t n, int64_
 // are formed (no records, no sums).
 static int arb_run_grid(sphx_ctx* ctx, int64_t n, const ArbPartIn& in, int64_t m, const double* arb_points, double radius,
                         const ArbHostOut& hout, int64_t* candidates, int64_t ball_id, bool hit) {
-    SPHX_TRY(arb_red_prepare(ctx));
-    double* red = ctx->arb_red.as<double>();
+    ArbRed red;
+    SPHX_TRY(arb_red_prepare(ctx, &red));
     const bool has_ph = in.npart && in.value;
     ArbOutPtrs o;
     SPHX_TRY(arb_out_ptrs(ctx, m, hout, in.sizes != nullptr, in.T != nullptr, has_ph, &o));
@@ -473,29 +479,35 @@ static int arb_run_grid(sphx_ctx* ctx, int64_t n, const ArbPartIn& in, int64_t m
     if (!hit) {
         ctx->arb_ball_id = 0;                              // (the held geometry is being replaced)
         SPHX_TRY(sphx_ensure(ctx, ctx->arb_q, (size_t)m * 3 * sizeof(double)));
-        SPHX_TRY(sphx_ensure(ctx, ctx->arb_key, (size_t)mpad * 4 * sizeof(int)));
         HIPCHK(hipMemcpyAsync(ctx->arb_q.p, arb_points, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     }
-    SPHX_TRY(sphx_ensure(ctx, ctx->arb_acc, (size_t)mpad * (ARB_NACC * sizeof(double) + sizeof(int))));
+    // the query points' keys and order, and their sorted copies (a hit: the buffer stands, with the sorted order in it)
+    int *key, *idx, *key2, *idx2;
+    Carve ck;
+    ck.take(key, (size_t)mpad); ck.take(idx, (size_t)mpad); ck.take(key2, (size_t)mpad); ck.take(idx2, (size_t)mpad);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->arb_key, ck));
+    // the points' sums, then their counts
+    ArbGridArgs a;
+    Carve ca;
+    ca.take(a.acc, ARB_NACC * (size_t)mpad); ca.take(a.cnt, (size_t)mpad);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->arb_acc, ca));
     SPHX_TRY(ctx->arb_t.mark(ctx, 1));
     // supports: the ball's radius and, for a new geometry, the cell size
     double R = radius, cell_hint = 0.0;
     if (!hit || !(radius > 0.0)) {
         int rb = (int)((n + 255) / 256);
         if (rb > ARB_RED_BLOCKS) rb = ARB_RED_BLOCKS;
-        hipLaunchKernelGGL(arb_reduce_kernel, dim3(rb), dim3(256), 0, ctx->stream, (int)n, in, red + 16);
-        hipLaunchKernelGGL(arb_reduce_final, dim3(1), dim3(64), 0, ctx->stream, rb, red + 16, red);
+        hipLaunchKernelGGL(arb_reduce_kernel, dim3(rb), dim3(256), 0, ctx->stream, (int)n, in, red.part);
+        hipLaunchKernelGGL(arb_reduce_final, dim3(1), dim3(64), 0, ctx->stream, rb, red.part, red.res);
         HIPCHK(hipGetLastError());
         const double* rd = ctx->pinned->side.red;
-        HIPCHK(hipMemcpyAsync(ctx->pinned->side.red, red, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->pinned->side.red, red.res, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         if (!(radius > 0.0)) R = rd[0];
         cell_hint = rd[3] > 0.0 ? rd[2] / rd[3] : 0.0;     // the mean support
     }
     if (!(R > 0.0) || !(R <= DBL_MAX))
         return sphx_set_err(ctx, SPHX_E_ARG, "sphx_arb_fields: no ball radius (radius <= 0 and no positive finite sizes)");
-    int* key = ctx->arb_key.as<int>();
-    int *idx = key + mpad, *key2 = key + 2 * mpad, *idx2 = key + 3 * mpad;
     if (!hit) {
         ctx->map_perm = nullptr;
         ctx->qorder = nullptr;
@@ -533,11 +545,15 @@ static int arb_run_grid(sphx_ctx* ctx, int64_t n, const ArbPartIn& in, int64_t m
     ArbRec* rec = nullptr;
     if (sums) {                                            // records, wide list, per-cell maxima
         SPHX_TRY(sphx_ensure(ctx, ctx->arb_rec, (size_t)n * sizeof(ArbRec)));
-        SPHX_TRY(sphx_ensure(ctx, ctx->arb_flag, ((size_t)n + 8) * 2 * sizeof(int) + 64));
+        // the wide flags (n + 1 and four of head-room) | their scan, 16-byte aligned: the single-launch scan wants it
+        // (the room as it has been: 2 (n + 8) ints and 64 bytes)
+        int *wide, *woff;
+        Carve cf;
+        cf.take(wide, (size_t)n + 5, 16); cf.take(woff, (size_t)n + 11, 16);
+        cf.slack(64);
+        SPHX_TRY(sphx_carve_into(ctx, ctx->arb_flag, cf));
         SPHX_TRY(sphx_ensure(ctx, ctx->arb_cmax, (size_t)g.ncells * sizeof(double)));
         rec = ctx->arb_rec.as<ArbRec>();
-        int* wide = ctx->arb_flag.as<int>();
-        int* woff = wide + ((n + 8) & ~int64_t(3));                    // (16-byte aligned: the single-launch scan wants it)
         hipLaunchKernelGGL(arb_record_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, ctx->stream, (int)n, in, perm, sp,
                            wcut, rec, wide);
         HIPCHK(hipGetLastError());
@@ -553,7 +569,6 @@ static int arb_run_grid(sphx_ctx* ctx, int64_t n, const ArbPartIn& in, int64_t m
                                wide, woff, ctx->arb_wrec.as<ArbRec>());
     }
     SPHX_TRY(ctx->arb_t.mark(ctx, 2));
-    ArbGridArgs a;
     a.m = (int)m;
     a.q = ctx->arb_q.as<double>();
     a.qidx = idx2;
@@ -568,16 +583,14 @@ static int arb_run_grid(sphx_ctx* ctx, int64_t n, const ArbPartIn& in, int64_t m
     a.R = R; a.R2 = R * R;
     a.wcut = wcut;
     for (int c = 0; c < 6; ++c) a.tb[c] = ctx->arb_tb[c];
-    a.acc = ctx->arb_acc.as<double>();
-    a.cnt = reinterpret_cast<int*>(a.acc + ARB_NACC * (size_t)mpad);
-    a.candidates = reinterpret_cast<u64*>(red + 8);
+    a.candidates = red.cand;
     const unsigned nb = (unsigned)(mpad / 64);
     if (sums) hipLaunchKernelGGL(arb_grid_kernel, dim3(nb), dim3(64), 0, ctx->stream, a);
-    else HIPCHK(hipMemsetAsync(a.acc, 0, (size_t)mpad * (ARB_NACC * sizeof(double) + sizeof(int)), ctx->stream));
+    else HIPCHK(hipMemsetAsync(a.acc, 0, ca.bytes(), ctx->stream));
     hipLaunchKernelGGL(arb_gate_kernel, dim3(nb), dim3(64), 0, ctx->stream, a, hout.count ? 1 : 0, o);
     HIPCHK(hipGetLastError());
     SPHX_TRY(ctx->arb_t.mark(ctx, 3));
-    return arb_out_download(ctx, m, hout, o, candidates);
+    return arb_out_download(ctx, m, hout, o, red.cand, candidates);
 }
 
 static int arb_check_common(sphx_ctx* ctx, const char* who, int64_t n, int64_t m, const void* arb_points) {
@@ -655,7 +668,8 @@ extern "C" int sphx_arb_fields_list(sphx_ctx* ctx, int64_t n, const double* poin
     ctx->arb_ball_id = 0;                                  // (the query buffers of a held ball are overwritten below)
     ArbPartIn in;
     SPHX_TRY(arb_stage_particles(ctx, n, points, mass, particle_type, sizes, T, n_part, value, d, &in));
-    SPHX_TRY(arb_red_prepare(ctx));
+    ArbRed red;
+    SPHX_TRY(arb_red_prepare(ctx, &red));
     const ArbHostOut hout{density, dust_density, temperature, dust_temperature, photoionization, count};
     ArbOutPtrs o;
     SPHX_TRY(arb_out_ptrs(ctx, m, hout, sizes != nullptr, T != nullptr, n_part && value, &o));
@@ -674,10 +688,10 @@ extern "C" int sphx_arb_fields_list(sphx_ctx* ctx, int64_t n, const double* poin
     SPHX_TRY(ctx->arb_t.mark(ctx, 2));
     hipLaunchKernelGGL(arb_list_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, (int)m, (int)n,
                        ctx->arb_q.as<double>(), ctx->arb_key.as<long long>(), ctx->arb_tmp.as<long long>(),
-                       ctx->arb_rec.as<ArbRec>(), o, reinterpret_cast<u64*>(ctx->arb_red.as<double>() + 8));
+                       ctx->arb_rec.as<ArbRec>(), o, red.cand);
     HIPCHK(hipGetLastError());
     SPHX_TRY(ctx->arb_t.mark(ctx, 3));
-    return arb_out_download(ctx, m, hout, o, candidates);
+    return arb_out_download(ctx, m, hout, o, red.cand, candidates);
 }
 
 // The grid form on the step loop's resident state.  The grid build works in buffers the step rebuilds from scratch

@@ -171,16 +171,24 @@ __global__ __launch_bounds__(CEN_WG) void census_fill_kernel(long long first, lo
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-static size_t cen_pad4(size_t ints) { return (ints + 3) & ~(size_t)3; }       // (the scan wants 16-byte boundaries)
 static int cen_check_n(sphx_ctx* ctx, const char* who, int64_t n) {
     if (n < 1 || n > 0x7FFFFFF0ll) return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld (need 1 <= n < 2^31 - 16)", who, (long long)n);
     return SPHX_OK;
 }
+// ctx->census_int: slot | flag | start (n + 1 each; the scan wants 16-byte boundaries)
+struct CenInts { int *slot, *flag, *start; };
+static int cen_ints(sphx_ctx* ctx, int64_t n, CenInts* o) {
+    Carve c;
+    c.take(o->slot, (size_t)n + 1, 16); c.take(o->flag, (size_t)n + 1, 16); c.take(o->start, (size_t)n + 1, 16);
+    c.pad(16);
+    return sphx_carve_into(ctx, ctx->census_int, c);
+}
 // the slot map of the resident state into ctx->census_int
 static int cen_slot_map(sphx_ctx* ctx, const int** slot) {
     const size_t nn = (size_t)ctx->n;
-    SPHX_TRY(sphx_ensure(ctx, ctx->census_int, (3 * cen_pad4(nn + 1)) * sizeof(int)));
-    int* s = ctx->census_int.as<int>();
+    CenInts ci;
+    SPHX_TRY(cen_ints(ctx, ctx->n, &ci));
+    int* s = ci.slot;
     HIPCHK(hipMemsetAsync(s, 0, nn * sizeof(int), ctx->stream));
     hipLaunchKernelGGL(census_slot_kernel, dim3(sphx_blocks(nn, CEN_WG)), dim3(CEN_WG), 0, ctx->stream, (int)ctx->n, ctx->st.id.as<int>(), s);
     HIPCHK(hipGetLastError());
@@ -193,12 +201,10 @@ static int cen_run(sphx_ctx* ctx, CensusArgs a, double* totals, int64_t* counts,
     hipStream_t st = ctx->stream;
     const size_t nchunk = sphx_tot_chunks(a.n), nq = (size_t)a.nq;
     // ctx->census_buf: tot (nq) | max (1) | counts (4 u64) | pmax (nchunk) | part (nq, nchunk)
-    SPHX_TRY(sphx_ensure(ctx, ctx->census_buf, (nq + 5 + nchunk + nq * nchunk) * sizeof(double)));
-    double* tot = ctx->census_buf.as<double>();
-    double* gmax = tot + nq;
-    a.cnt = (u64*)(gmax + 1);
-    a.pmax = gmax + 5;
-    a.part = a.pmax + nchunk;
+    double *tot, *gmax;
+    Carve c;
+    c.take(tot, nq); c.take(gmax, 1); c.take(a.cnt, 4); c.take(a.pmax, nchunk); c.take(a.part, nq * nchunk);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->census_buf, c));
     a.nchunk = (int)nchunk;
     HIPCHK(hipMemsetAsync(a.cnt, 0, 4 * sizeof(u64), st));
     hipLaunchKernelGGL(census_kernel, dim3((unsigned)nchunk), dim3(CEN_WG), 0, st, a);
@@ -236,9 +242,11 @@ extern "C" int sphx_census(sphx_ctx* ctx, int64_t n, int s, const double* mass, 
     HIPCHK(hipSetDevice(ctx->device));
     const size_t nn = (size_t)n, S = (size_t)s;
     // ctx->census_in: mass | ptype | E (n each) | velocities | total_accel (n,3) | f_un (n,s) | mu_specie (s)
-    SPHX_TRY(sphx_ensure(ctx, ctx->census_in, (9 * nn + nn * S + S + 1) * sizeof(double)));
-    double* p = ctx->census_in.as<double>();
-    double *d_m = p, *d_pt = p + nn, *d_E = p + 2 * nn, *d_v = p + 3 * nn, *d_a = p + 6 * nn, *d_f = p + 9 * nn, *d_mus = d_f + nn * S;
+    double *d_m, *d_pt, *d_E, *d_v, *d_a, *d_f, *d_mus;
+    Carve c;
+    c.take(d_m, nn); c.take(d_pt, nn); c.take(d_E, nn); c.take(d_v, 3 * nn); c.take(d_a, 3 * nn); c.take(d_f, nn * S); c.take(d_mus, S);
+    c.slack(sizeof(double));
+    SPHX_TRY(sphx_carve_into(ctx, ctx->census_in, c));
     SPHX_TRY(ctx->census_t.begin(ctx));
     const CopyF64 us[] = {{mass, d_m, nn}, {ptype, d_pt, nn}, {E_internal, d_E, nn}, {velocities, d_v, 3 * nn}, {total_accel, d_a, 3 * nn},
                           {f_un, d_f, nn * S}, {f_un ? ctx->census_tab : nullptr, d_mus, S}};
@@ -283,9 +291,7 @@ extern "C" int sphx_state_census(sphx_ctx* ctx, const double* mu_specie, double*
 }
 
 extern "C" int sphx_census_last_timing(sphx_ctx* ctx, double ms[4]) {
-    if (!ctx || !ms) return SPHX_E_ARG;
-    for (int i = 0; i < ctx->census_t.stages; ++i) ms[i] = ctx->census_t.ms[i];
-    return SPHX_OK;
+    return last_timing(ctx, &sphx_ctx::census_t, ms);
 }
 
 // flags, scan, the count on the host, the capacity check, the scatter, the rows out.  a: everything but flag, start and
@@ -293,10 +299,10 @@ extern "C" int sphx_census_last_timing(sphx_ctx* ctx, double ms[4]) {
 static int cen_select(sphx_ctx* ctx, const char* who, SelectArgs a, int64_t cap, int64_t* count, int64_t* ids, double* mass_out,
                       double* T_out, double* age_out, double* f_out) {
     hipStream_t st = ctx->stream;
-    const size_t nn = (size_t)a.n, S = (size_t)a.s, seg = cen_pad4(nn + 1);
-    SPHX_TRY(sphx_ensure(ctx, ctx->census_int, 3 * seg * sizeof(int)));      // slot | flag | start (a.slot lies in the first)
-    int* flag = ctx->census_int.as<int>() + seg;
-    int* start = flag + seg;
+    const size_t nn = (size_t)a.n, S = (size_t)a.s;
+    CenInts ci;                                      // (a.slot, where set, lies in the first part)
+    SPHX_TRY(cen_ints(ctx, a.n, &ci));
+    int *flag = ci.flag, *start = ci.start;
     a.flag = flag; a.start = start;
     hipLaunchKernelGGL(census_flag_kernel, dim3(sphx_blocks(nn + 1, CEN_WG)), dim3(CEN_WG), 0, st, a);
     HIPCHK(hipGetLastError());
@@ -313,9 +319,11 @@ static int cen_select(sphx_ctx* ctx, const char* who, SelectArgs a, int64_t cap,
     const size_t nc = (size_t)cnt;
     const bool want_f = f_out != nullptr;
     // ctx->census_buf: ids (count int64) | mass | T | age (count) | f (count, s)
-    SPHX_TRY(sphx_ensure(ctx, ctx->census_buf, (4 * nc + (want_f ? nc * S : 0)) * sizeof(double)));
-    a.oid = (long long*)ctx->census_buf.p;
-    a.om = ctx->census_buf.as<double>() + nc; a.oT = a.om + nc; a.oage = a.oT + nc; a.of = want_f ? a.oage + nc : nullptr;
+    Carve c;
+    c.take(a.oid, nc); c.take(a.om, nc); c.take(a.oT, nc); c.take(a.oage, nc);
+    a.of = nullptr;
+    if (want_f) c.take(a.of, nc * S);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->census_buf, c));
     hipLaunchKernelGGL(census_pick_kernel, dim3(sphx_blocks(nn, CEN_WG)), dim3(CEN_WG), 0, st, a);
     HIPCHK(hipGetLastError());
     const CopyF64 ds[] = {{ids, a.oid, nc}, {mass_out, a.om, nc}, {T_out, a.oT, nc}, {age_out, a.oage, nc}, {f_out, a.of, nc * S}};
@@ -345,13 +353,16 @@ extern "C" int sphx_census_select(sphx_ctx* ctx, int64_t n, int s, const double*
     if (!f_un) s = 0;
     HIPCHK(hipSetDevice(ctx->device));
     const size_t nn = (size_t)n, S = (size_t)s;
-    SPHX_TRY(sphx_ensure(ctx, ctx->census_in, (4 * nn + nn * S + 1) * sizeof(double)));
-    double* p = ctx->census_in.as<double>();
-    const CopyF64 us[] = {{mass, p, nn}, {ptype, p + nn, nn}, {T, p + 2 * nn, nn}, {star_ages, p + 3 * nn, nn}, {f_un, p + 4 * nn, nn * S}};
+    double *d_m, *d_pt, *d_T, *d_age, *d_f;
+    Carve c;
+    c.take(d_m, nn); c.take(d_pt, nn); c.take(d_T, nn); c.take(d_age, nn); c.take(d_f, nn * S);
+    c.slack(sizeof(double));
+    SPHX_TRY(sphx_carve_into(ctx, ctx->census_in, c));
+    const CopyF64 us[] = {{mass, d_m, nn}, {ptype, d_pt, nn}, {T, d_T, nn}, {star_ages, d_age, nn}, {f_un, d_f, nn * S}};
     SPHX_TRY(sphx_upload_f64(ctx, us, 5));
     SelectArgs a;
     a.n = (int)n; a.s = s; a.fs = s; a.type = type; a.window = window; a.slot = nullptr;
-    a.m = p; a.pt = p + nn; a.T = T ? p + 2 * nn : nullptr; a.age = star_ages ? p + 3 * nn : nullptr; a.fun = f_un ? p + 4 * nn : nullptr;
+    a.m = d_m; a.pt = d_pt; a.T = T ? d_T : nullptr; a.age = star_ages ? d_age : nullptr; a.fun = f_un ? d_f : nullptr;
     a.unit = unit; a.lo = lo; a.hi = hi;
     return cen_select(ctx, who, a, cap, count, ids, mass_out, T_out, age_out, f_out);
 }
@@ -421,11 +432,13 @@ extern "C" int sphx_advance_star_ages(sphx_ctx* ctx, int64_t n, double* star_age
     SPHX_TRY(cen_check_n(ctx, "sphx_advance_star_ages", n));
     HIPCHK(hipSetDevice(ctx->device));
     const size_t nn = (size_t)n;
-    SPHX_TRY(sphx_ensure(ctx, ctx->census_in, 2 * nn * sizeof(double)));
-    double* p = ctx->census_in.as<double>();
-    const CopyF64 us[] = {{star_ages, p, nn}, {ptype, p + nn, nn}};
+    double *p, *d_pt;
+    Carve c;
+    c.take(p, nn); c.take(d_pt, nn);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->census_in, c));
+    const CopyF64 us[] = {{star_ages, p, nn}, {ptype, d_pt, nn}};
     SPHX_TRY(sphx_upload_f64(ctx, us, 2));
-    hipLaunchKernelGGL(census_advance_kernel, dim3(sphx_blocks(nn, CEN_WG)), dim3(CEN_WG), 0, ctx->stream, (int)n, (const int*)nullptr, p + nn, dt, p);
+    hipLaunchKernelGGL(census_advance_kernel, dim3(sphx_blocks(nn, CEN_WG)), dim3(CEN_WG), 0, ctx->stream, (int)n, (const int*)nullptr, d_pt, dt, p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(star_ages, p, nn * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));

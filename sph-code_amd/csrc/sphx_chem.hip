@@ -417,22 +417,25 @@ int sphx_chem_tables(sphx_ctx* ctx, const char* who, int s, const double* mu_spe
     return SPHX_OK;
 }
 
-// ints per particle: nbr (k npad) | isd | ord | cnt | cur | start (n + 1 each, a multiple of four).  -> the K-major list's place
-int sphx_chem_ints(sphx_ctx* ctx, int64_t n, int k, int** nbr) {
-    const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), n1 = (nn + 4) & ~size_t(3);
-    SPHX_TRY(sphx_ensure(ctx, ctx->chem_int, ((size_t)k * npad + 5 * n1) * sizeof(int)));
-    *nbr = ctx->chem_int.as<int>();
-    return SPHX_OK;
+// ints per particle: nbr (k npad, the K-major list's place) | isd | ord | cnt | cur | start (n + 1 each, on 16-byte boundaries)
+int sphx_chem_ints(sphx_ctx* ctx, int64_t n, int k, ChemInts* out) {
+    const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n);
+    Carve c;
+    c.take(out->nbr, (size_t)k * npad);
+    c.take(out->isd, nn + 1, 16); c.take(out->ord, nn + 1, 16); c.take(out->cnt, nn + 1, 16); c.take(out->cur, nn + 1, 16);
+    c.take(out->start, nn + 1, 16);
+    c.pad(16);
+    c.take(out->end, 0);
+    return sphx_carve_into(ctx, ctx->chem_int, c);
 }
 
 // inputs in ctx->chem_in: points (3n) | mass | mu | sizes | T | ptype (n each) | f_un (n s) | the tables (4 s)
 int sphx_chem_inputs(sphx_ctx* ctx, int64_t n, int s, ChemDev* in) {
-    const size_t nn = (size_t)n, ns_ = nn * (size_t)s;
-    SPHX_TRY(sphx_ensure(ctx, ctx->chem_in, (8 * nn + ns_ + 4 * (size_t)s) * sizeof(double)));
-    double* p = ctx->chem_in.as<double>();
-    in->pos = p; in->m = p + 3 * nn; in->mu = p + 4 * nn; in->sizes = p + 5 * nn; in->T = p + 6 * nn; in->ptype = p + 7 * nn;
-    in->fun = p + 8 * nn; in->tab = p + 8 * nn + ns_;
-    return SPHX_OK;
+    const size_t nn = (size_t)n;
+    Carve c;
+    c.take(in->pos, 3 * nn); c.take(in->m, nn); c.take(in->mu, nn); c.take(in->sizes, nn); c.take(in->T, nn); c.take(in->ptype, nn);
+    c.take(in->fun, nn * (size_t)s); c.take(in->tab, 4 * (size_t)s);
+    return sphx_carve_into(ctx, ctx->chem_in, c);
 }
 
 // the host arrays and the (n,k) int64 list onto the device; the list into its K-major int32 form
@@ -447,12 +450,12 @@ static int chem_stage_host(sphx_ctx* ctx, int64_t n, int k, int s, const double*
                           {ptype, in->ptype, nn}, {f_un, in->fun, ns_}, {ctx->chem_tab, in->tab, 4 * (size_t)s}};
     SPHX_TRY(sphx_upload_f64(ctx, us, 8));
     HIPCHK(hipMemcpyAsync(ctx->chem_nb.p, neighbor, nk * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    int* nbr;
-    SPHX_TRY(sphx_chem_ints(ctx, n, k, &nbr));
+    ChemInts ci;
+    SPHX_TRY(sphx_chem_ints(ctx, n, k, &ci));
     hipLaunchKernelGGL(chem_list_kernel, dim3(sphx_blocks(nk, CHEM_WG)), dim3(CHEM_WG), 0, st, (int)n, (int)npad, k,
-                       (const long long*)ctx->chem_nb.p, nbr);
+                       (const long long*)ctx->chem_nb.p, ci.nbr);
     HIPCHK(hipGetLastError());
-    *nbr_out = nbr;
+    *nbr_out = ci.nbr;
     return SPHX_OK;
 }
 
@@ -471,17 +474,18 @@ int sphx_chem_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
     SPHX_TRY(sphx_ensure(ctx, ctx->chem_rec, nn * sizeof(ChemRec)));
     const size_t nchunk = (nn + CHEM_CHUNK - 1) / CHEM_CHUNK;
     // per particle: counters (CH_HEADER u64) | num0 (n s) | numfin (n s) | mass_new (n) | f_un_new (n s) | partial sums (2 nchunk s) | factors (2 s)
-    SPHX_TRY(sphx_ensure(ctx, ctx->chem_out, (CH_HEADER + 3 * ns_ + nn + 2 * nchunk * (size_t)s + 2 * (size_t)s) * sizeof(double)));
-    unsigned long long* d_cnt = (unsigned long long*)ctx->chem_out.p;
-    double *num0 = ctx->chem_out.as<double>() + CH_HEADER, *numfin = num0 + ns_, *d_mass = numfin + ns_, *d_fnew = d_mass + nn,
-           *part = d_fnew + ns_, *fac = part + 2 * nchunk * (size_t)s;
+    unsigned long long* d_cnt;
+    double *num0, *numfin, *d_mass, *d_fnew, *part, *fac;
+    Carve co;
+    co.take(d_cnt, CH_HEADER); co.take(num0, ns_); co.take(numfin, ns_); co.take(d_mass, nn); co.take(d_fnew, ns_);
+    co.take(part, 2 * nchunk * (size_t)s); co.take(fac, 2 * (size_t)s);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->chem_out, co));
     HIPCHK(hipMemsetAsync(d_cnt, 0, CH_HEADER * sizeof(double), st));
     // ints (sphx_chem_ints): isd | ord | cnt | cur | start behind the list's place
-    const size_t n1 = (nn + 4) & ~size_t(3);
-    int* own;
-    SPHX_TRY(sphx_chem_ints(ctx, n, k, &own));
-    int *isd = own + (size_t)k * npad, *ord = isd + n1, *cnt = ord + n1, *cur = cnt + n1, *start = cur + n1;
-    HIPCHK(hipMemsetAsync(isd, 0, 5 * n1 * sizeof(int), st));
+    ChemInts ci;
+    SPHX_TRY(sphx_chem_ints(ctx, n, k, &ci));
+    int *isd = ci.isd, *ord = ci.ord, *cnt = ci.cnt, *cur = ci.cur, *start = ci.start;
+    HIPCHK(hipMemsetAsync(isd, 0, (size_t)(ci.end - isd) * sizeof(int), st));
     ChemPrep pa;
     pa.n = (int)n; pa.s = s; pa.pos = d_pos; pa.m = d_m; pa.mu = d_mu; pa.T = d_T; pa.ptype = d_pt; pa.fun = d_fun; pa.mus = d_tab;
     pa.d = d; pa.m0 = par.m_0; pa.rec = ctx->chem_rec.as<ChemRec>(); pa.num0 = num0; pa.numfin = numfin; pa.isd = isd;
@@ -502,25 +506,26 @@ int sphx_chem_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
         // ---- the row passes ----
         const size_t ndpad = (size_t)sphx_pad64((int64_t)nd), row = ndpad * (size_t)ns;
         // per dust row: wg, wk (k ndpad each) | tsph, scd3, scd4, selfw (ndpad each) | new0, sumc x 2, new2 x 2 (ndpad ns each)
-        SPHX_TRY(sphx_ensure(ctx, ctx->chem_row, (2 * (size_t)k * ndpad + 4 * ndpad + 5 * row) * sizeof(double)));
-        // ints per dust row: dustid, contrib (ndpad each) | pos (k ndpad)
-        SPHX_TRY(sphx_ensure(ctx, ctx->chem_rowi, (2 * ndpad + (size_t)k * ndpad) * sizeof(int)));
         ChemRows ra;
+        double *sumc[2], *new2[2];
+        Carve cr;
+        cr.take(ra.wg, (size_t)k * ndpad); cr.take(ra.wk, (size_t)k * ndpad);
+        cr.take(ra.tsph, ndpad); cr.take(ra.scd3, ndpad); cr.take(ra.scd4, ndpad); cr.take(ra.selfw, ndpad);
+        cr.take(ra.new0, row); cr.take(sumc[0], row); cr.take(sumc[1], row); cr.take(new2[0], row); cr.take(new2[1], row);
+        SPHX_TRY(sphx_carve_into(ctx, ctx->chem_row, cr));
+        // ints per dust row: dustid, contrib (ndpad each) | pos (k ndpad)
+        int* pos;
+        Carve cri;
+        cri.take(ra.dustid, ndpad); cri.take(ra.contrib, ndpad); cri.take(pos, (size_t)k * ndpad);
+        SPHX_TRY(sphx_carve_into(ctx, ctx->chem_rowi, cri));
         ra.n = (int)n; ra.npad = (int)npad; ra.k = k; ra.s = s; ra.ns = ns; ra.nd = (int)nd; ra.ndpad = (int)ndpad;
         ra.nbr = nbr; ra.isd = isd; ra.ord = ord;
-        ra.dustid = ctx->chem_rowi.as<int>(); ra.contrib = ra.dustid + ndpad;
-        int* pos = ra.contrib + ndpad;
-        HIPCHK(hipMemsetAsync(ra.dustid, 0, 2 * ndpad * sizeof(int), st));
+        HIPCHK(hipMemsetAsync(ra.dustid, 0, (size_t)(pos - ra.dustid) * sizeof(int), st));
         ra.rec = pa.rec; ra.fun = d_fun; ra.num0 = num0; ra.sizes = d_sz; ra.m = d_m;
         ra.tab.mu = d_tab; ra.tab.j0 = d_tab + s; ra.tab.b = d_tab + 2 * s; ra.tab.sy = d_tab + 3 * s;
         ra.tab.symax = par.symax; ra.tab.kB = par.k_B; ra.tab.dt = par.dt;
         const double d2 = d * d, d4 = d2 * d2;
         ra.d9 = d4 * d4 * d;
-        ra.wg = ctx->chem_row.as<double>(); ra.wk = ra.wg + (size_t)k * ndpad;
-        ra.tsph = ra.wk + (size_t)k * ndpad; ra.scd3 = ra.tsph + ndpad; ra.scd4 = ra.scd3 + ndpad; ra.selfw = ra.scd4 + ndpad;
-        ra.new0 = ra.selfw + ndpad;
-        double* sumc[2] = {ra.new0 + row, ra.new0 + 2 * row};
-        double* new2[2] = {ra.new0 + 3 * row, ra.new0 + 4 * row};
         ra.sumc0 = sumc[0]; ra.new20 = new2[0];
         ra.counts = d_cnt;
         const unsigned rblk = sphx_blocks(nd * (size_t)ns, CHEM_WG);

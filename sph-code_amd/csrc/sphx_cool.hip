@@ -197,13 +197,15 @@ int sphx_cool_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
     const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), ns = nn * (size_t)s, nk = nn * (size_t)k;
     // ---- records; the K-major list, the rows' flags, the counts ----
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_rec, nn * sizeof(CoolRec)));
-    // ints: nbr (k npad) | cnt (n + 1) | cur (n + 1) | flag (n + 1) | start (n + 1), each part a multiple of four
-    const size_t n1 = (nn + 4) & ~size_t(3);
-    SPHX_TRY(sphx_ensure(ctx, ctx->cool_int, ((size_t)k * npad + 4 * n1) * sizeof(int)));
-    int* own = ctx->cool_int.as<int>();
+    // ints: nbr (k npad) | cnt (n + 1) | cur (n + 1) | flag (n + 1) | start (n + 1), each part on a 16-byte boundary
+    int *own, *cnt, *cur, *flag, *start;
+    Carve ci;
+    ci.take(own, (size_t)k * npad);
+    ci.take(cnt, nn + 1, 16); ci.take(cur, nn + 1, 16); ci.take(flag, nn + 1, 16); ci.take(start, nn + 1, 16);
+    ci.pad(16);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->cool_int, ci));
     int* nbr = nb64 ? own : const_cast<int*>(kmajor);
-    int *cnt = own + (size_t)k * npad, *cur = cnt + n1, *flag = cur + n1, *start = flag + n1;
-    HIPCHK(hipMemsetAsync(cnt, 0, 3 * n1 * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(cnt, 0, (size_t)(start - cnt) * sizeof(int), st));
     CoolPrep pa;
     pa.n = (int)n; pa.s = s; pa.pos = in.pos; pa.ptype = in.pt; pa.m = in.m; pa.mu = in.mu; pa.T = in.T; pa.fun = in.fun;
     pa.d = d; pa.m0 = ctx->cst.m_0; pa.m_h = ctx->cst.m_h; pa.kB = ctx->cst.k_B;
@@ -230,10 +232,11 @@ int sphx_cool_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
                            in.pt, start_, cur, rev_raw);
     }, &rl));
     // ---- gather and epilogue: final_comp (n s) | energy (n) | rec_array (s n) ----
-    SPHX_TRY(sphx_ensure(ctx, ctx->cool_out, (2 * ns + nn) * sizeof(double)));
     CoolGather ga;
     ga.n = (int)n; ga.s = s; ga.start = start; ga.rev = rl.rev; ga.rec = pa.rec; ga.tab = ra.tab; ga.fun = in.fun; ga.d = d;
-    ga.final_comp = ctx->cool_out.as<double>(); ga.energy = ga.final_comp + ns; ga.rec_array = ga.energy + nn;
+    Carve co;
+    co.take(ga.final_comp, ns); co.take(ga.energy, nn); co.take(ga.rec_array, ns);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->cool_out, co));
     hipLaunchKernelGGL(cool_gather_kernel, dim3(nblk), dim3(COOL_WG), 0, st, ga);
     HIPCHK(hipGetLastError());
     if (t) SPHX_TRY(t->mark(ctx, 3));
@@ -263,10 +266,11 @@ extern "C" int sphx_rad_cooling(sphx_ctx* ctx, int64_t n, int k, int s, const do
     hipStream_t st = ctx->stream;
     const size_t nn = (size_t)n, ns = nn * (size_t)s, nk = nn * (size_t)k;
     // ---- inputs: points (3n) | ptype | mass | mu | T (n each) | f_un (n s); the list as given ----
-    SPHX_TRY(sphx_ensure(ctx, ctx->cool_in, (7 * nn + ns) * sizeof(double)));
+    double *d_pos, *d_pt, *d_m, *d_mu, *d_T, *d_fun;
+    Carve c;
+    c.take(d_pos, 3 * nn); c.take(d_pt, nn); c.take(d_m, nn); c.take(d_mu, nn); c.take(d_T, nn); c.take(d_fun, ns);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->cool_in, c));
     SPHX_TRY(sphx_ensure(ctx, ctx->cool_nb, nk * sizeof(int64_t)));
-    double* in = ctx->cool_in.as<double>();
-    double *d_pos = in, *d_pt = in + 3 * nn, *d_m = in + 4 * nn, *d_mu = in + 5 * nn, *d_T = in + 6 * nn, *d_fun = in + 7 * nn;
     const CopyF64 us[] = {{points, d_pos, 3 * nn}, {ptype, d_pt, nn}, {mass, d_m, nn}, {mu, d_mu, nn}, {T, d_T, nn}, {f_un, d_fun, ns}};
     SPHX_TRY(sphx_upload_f64(ctx, us, 6));
     HIPCHK(hipMemcpyAsync(ctx->cool_nb.p, neighbor, nk * sizeof(int64_t), hipMemcpyHostToDevice, st));

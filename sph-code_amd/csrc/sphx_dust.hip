@@ -251,11 +251,10 @@ int sphx_dust_params(sphx_ctx* ctx, const char* who, int s, double crit_mass, do
 // inputs in ctx->dust_in: points, velocities (3n each) | mass | mu | sizes | densities | ptype (n each) | f_un (n s)
 int sphx_dust_inputs(sphx_ctx* ctx, int64_t n, int s, DustDev* in) {
     const size_t nn = (size_t)n;
-    SPHX_TRY(sphx_ensure(ctx, ctx->dust_in, (11 * nn + nn * (size_t)s) * sizeof(double)));
-    double* p = ctx->dust_in.as<double>();
-    in->pos = p; in->vel = p + 3 * nn; in->m = p + 6 * nn; in->mu = p + 7 * nn; in->sizes = p + 8 * nn; in->dens = p + 9 * nn;
-    in->ptype = p + 10 * nn; in->fun = p + 11 * nn;
-    return SPHX_OK;
+    Carve c;
+    c.take(in->pos, 3 * nn); c.take(in->vel, 3 * nn); c.take(in->m, nn); c.take(in->mu, nn); c.take(in->sizes, nn); c.take(in->dens, nn);
+    c.take(in->ptype, nn); c.take(in->fun, nn * (size_t)s);
+    return sphx_carve_into(ctx, ctx->dust_in, c);
 }
 
 static int dust_stage_host(sphx_ctx* ctx, int64_t n, int k, int s, const double* points, const double* velocities,
@@ -282,18 +281,24 @@ int sphx_dust_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
     const double *d_pt = in.ptype;
     // ---- records; the K-major list, the rows' flags, the counts ----
     SPHX_TRY(sphx_ensure(ctx, ctx->dust_rec, nn * sizeof(DustRec)));
-    // ints: nbr (k npad) | cnt (n + 1) | cur (n + 1) | flag (n + 1) | start (n + 1) | msk (k npad), each part a multiple of four
-    const size_t n1 = (nn + 4) & ~size_t(3);
-    SPHX_TRY(sphx_ensure(ctx, ctx->dust_int, (2 * (size_t)k * npad + 4 * n1) * sizeof(int)));
-    int* own = ctx->dust_int.as<int>();
-    int *cnt = own + (size_t)k * npad, *cur = cnt + n1, *flag = cur + n1, *start = flag + n1;
-    unsigned* msk = (unsigned*)(start + n1);
+    // ints: nbr (k npad) | cnt (n + 1) | cur (n + 1) | flag (n + 1) | start (n + 1) | msk (k npad), each part on a 16-byte boundary
+    int *own, *cnt, *cur, *flag, *start;
+    unsigned* msk;
+    Carve ci;
+    ci.take(own, (size_t)k * npad);
+    ci.take(cnt, nn + 1, 16); ci.take(cur, nn + 1, 16); ci.take(flag, nn + 1, 16); ci.take(start, nn + 1, 16);
+    ci.take(msk, (size_t)k * npad, 16);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->dust_int, ci));
     const int* nbr = nbr_given ? nbr_given : own;
-    HIPCHK(hipMemsetAsync(cnt, 0, 3 * n1 * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(cnt, 0, (size_t)(start - cnt) * sizeof(int), st));
     // outputs: counters (8 u64) | the knots (40 doubles) | frac_destruction (n s) | frac_reuptake (n s)
-    SPHX_TRY(sphx_ensure(ctx, ctx->dust_out, (48 + 2 * ns) * sizeof(double)));
-    HIPCHK(hipMemsetAsync(ctx->dust_out.p, 0, 8 * sizeof(double), st));
-    HIPCHK(hipMemcpyAsync(ctx->dust_out.as<double>() + 8, &kn, sizeof(DustKnots), hipMemcpyHostToDevice, st));
+    DustWalk wa;
+    double* knots;
+    Carve co;
+    co.take(wa.counts, 8); co.take(knots, 40); co.take(wa.destr, ns); co.take(wa.reup, ns);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->dust_out, co));
+    HIPCHK(hipMemsetAsync(wa.counts, 0, 8 * sizeof(double), st));
+    HIPCHK(hipMemcpyAsync(knots, &kn, sizeof(DustKnots), hipMemcpyHostToDevice, st));
     DustPrep pa;
     pa.n = (int)n; pa.pos = in.pos; pa.vel = in.vel; pa.m = in.m; pa.mu = in.mu; pa.sizes = in.sizes;
     pa.crit_mass = par.crit_mass; pa.amu = par.amu;
@@ -315,7 +320,6 @@ int sphx_dust_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
     }, &rl));
     if (t) SPHX_TRY(t->mark(ctx, 2));
     // ---- the dust pass, then the row pass ----
-    DustWalk wa;
     wa.sel = par.sel; wa.si = par.si;
     wa.n = (int)n; wa.npad = (int)npad; wa.k = k; wa.s = s;
     wa.fraction = par.fraction;
@@ -323,9 +327,7 @@ int sphx_dust_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const
     wa.dens = in.dens; wa.fun = in.fun; wa.ptype = d_pt;
     wa.crit_density = par.crit_density;
     wa.msk = msk;
-    wa.counts = (unsigned long long*)ctx->dust_out.p;
-    wa.kn = reinterpret_cast<const DustKnots*>(ctx->dust_out.as<double>() + 8);
-    wa.destr = ctx->dust_out.as<double>() + 48; wa.reup = wa.destr + ns;
+    wa.kn = reinterpret_cast<const DustKnots*>(knots);
     hipLaunchKernelGGL(dust_pass_kernel, dim3(nblk), dim3(DUST_WG), 0, st, wa);
     HIPCHK(hipGetLastError());
     if (t) SPHX_TRY(t->mark(ctx, 3));

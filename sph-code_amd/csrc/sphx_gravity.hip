@@ -819,9 +819,10 @@ extern "C" int sphx_state_gravity_potential(sphx_ctx* ctx, double* pot_by_id, do
         SPHX_TRY(grav_tree_side_bufs(ctx, nb));
     }
     // ctx->gravpot_buf: phi by id (n) | pp (2, n) | part (2, nchunk) | tot: U, sum m, eps, bad (4)
-    SPHX_TRY(sphx_ensure(ctx, ctx->gravpot_buf, (3 * nn + 2 * nchunk + 4) * sizeof(double)));
-    double* phi = ctx->gravpot_buf.as<double>();
-    double *pp = phi + nn, *part = pp + 2 * nn, *tot = part + 2 * nchunk;
+    double *phi, *pp, *part, *tot;
+    Carve cb;
+    cb.take(phi, nn); cb.take(pp, 2 * nn); cb.take(part, 2 * nchunk); cb.take(tot, 4);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->gravpot_buf, cb));
     SPHX_TRY(ctx->gravpot_t.begin(ctx));
     const StateArrays& s = ctx->st;
     const int* id = s.id.as<int>();

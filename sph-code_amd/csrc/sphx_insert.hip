@@ -159,19 +159,22 @@ extern "C" int sphx_state_download_rows(sphx_ctx* ctx, int64_t n_rows, const int
     HIPCHK(hipSetDevice(ctx->device));
     const size_t nr = (size_t)n_rows, s = (size_t)ctx->s;
     // ins_rows: pos | vel (nr,3) | m | E (nr) | f (nr,s) | sorted ids | order (ints)
-    SPHX_TRY(sphx_ensure(ctx, ctx->ins_rows, (8 * nr + nr * s) * sizeof(double) + 2 * nr * sizeof(int)));
-    double* d = ctx->ins_rows.as<double>();
-    int* di = (int*)(d + 8 * nr + nr * s);
-    HIPCHK(hipMemcpyAsync(di, sorted.data(), nr * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(di + nr, order.data(), nr * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    const StateArrays& st = ctx->st;
     RowsArgs a;
+    double* d_f;
+    int *d_ids, *d_order;
+    Carve c;
+    c.take(a.pos, 3 * nr); c.take(a.vel, 3 * nr); c.take(a.om, nr); c.take(a.oE, nr); c.take(d_f, nr * s);
+    c.take(d_ids, nr); c.take(d_order, nr);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->ins_rows, c));
+    HIPCHK(hipMemcpyAsync(d_ids, sorted.data(), nr * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_order, order.data(), nr * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    const StateArrays& st = ctx->st;
     a.n = (int)ctx->n; a.nr = (int)n_rows; a.s = ctx->s; a.sp = ctx->sp;
-    a.id = st.id.as<int>(); a.ids = di; a.order = di + nr;
+    a.id = st.id.as<int>(); a.ids = d_ids; a.order = d_order;
     a.x = st.x.as<double>(); a.y = st.y.as<double>(); a.z = st.z.as<double>();
     a.vx = st.vx.as<double>(); a.vy = st.vy.as<double>(); a.vz = st.vz.as<double>();
     a.m = st.m.as<double>(); a.E = st.E.as<double>(); a.fun = ctx->fun_id.as<double>();
-    a.pos = d; a.vel = d + 3 * nr; a.om = d + 6 * nr; a.oE = d + 7 * nr; a.of = f_un ? d + 8 * nr : nullptr;
+    a.of = f_un ? d_f : nullptr;
     hipLaunchKernelGGL(ins_rows_kernel, dim3(sphx_blocks((size_t)ctx->n, INS_WG)), dim3(INS_WG), 0, ctx->stream, a);
     HIPCHK(hipGetLastError());
     const CopyF64 ds[] = {{pos, a.pos, 3 * nr}, {vel, a.vel, 3 * nr}, {mass, a.om, nr}, {E_internal, a.oE, nr}, {f_un, a.of, nr * s}};
@@ -215,13 +218,20 @@ extern "C" int sphx_state_insert_rows(sphx_ctx* ctx, int s, int64_t n_rew, const
     const size_t nr = (size_t)n_rew, na = (size_t)n_app, S = (size_t)s;
     const bool drag = ctx->drag;
     // ---- the inputs in one staging block; doubles: rew_m | rew_E (nr) | rew_f (nr S) | app_pos | app_vel (na 3) | app_m |
-    //      app_pt | app_E (na) | app_f (na S) | mus | gamma | gm | se (S); then the clamp count (u64) and the sorted ids ----
-    const size_t nd = 2 * nr + nr * S + 9 * na + na * S + 4 * S;
+    //      app_pt | app_E (na) | app_f (na S) | mus | gamma | gm | se (S); then the clamp count (u64) and the sorted ids.
+    //      The one layout is bound twice: to the host's copy, which is filled here, then to the device's ----
+    struct Stage { double *rew_m, *rew_E, *rew_f, *app_pos, *app_vel, *app_m, *app_pt, *app_E, *app_f, *tab; u64* moved; double* end; int* ids; };
+    Stage dv;
+    Carve c;
+    c.take(dv.rew_m, nr); c.take(dv.rew_E, nr); c.take(dv.rew_f, nr * S); c.take(dv.app_pos, 3 * na); c.take(dv.app_vel, 3 * na);
+    c.take(dv.app_m, na); c.take(dv.app_pt, na); c.take(dv.app_E, na); c.take(dv.app_f, na * S); c.take(dv.tab, 4 * S);
+    c.take(dv.moved, 1); c.take(dv.end, 0); c.take(dv.ids, nr + 1);
     std::vector<double>& h = ctx->ins_host;          // (held by the context: the upload reads it)
-    h.assign(nd + 1, 0.0);
-    double* hp = h.data();
-    double *h_rm = hp, *h_rE = hp + nr, *h_rf = hp + 2 * nr, *h_ap = h_rf + nr * S, *h_av = h_ap + 3 * na, *h_am = h_av + 3 * na,
-           *h_apt = h_am + na, *h_aE = h_apt + na, *h_af = h_aE + na, *h_tab = h_af + na * S;
+    h.assign(c.bytes() / sizeof(double) + 1, 0.0);
+    c.bind(h.data());
+    const Stage hs = dv;
+    double *h_rm = hs.rew_m, *h_rE = hs.rew_E, *h_rf = hs.rew_f, *h_ap = hs.app_pos, *h_av = hs.app_vel, *h_am = hs.app_m,
+           *h_apt = hs.app_pt, *h_aE = hs.app_E, *h_af = hs.app_f, *h_tab = hs.tab;
     for (size_t r = 0; r < nr; ++r) {
         const size_t o = (size_t)order[r];
         h_rm[r] = rew_mass[o]; h_rE[r] = rew_E[o];
@@ -237,12 +247,9 @@ extern "C" int sphx_state_insert_rows(sphx_ctx* ctx, int s, int64_t n_rew, const
         h_tab[2 * S + q] = drag ? grain_mass[q] : 0.0; h_tab[3 * S + q] = drag ? sigma_effective[q] : 0.0;
     }
     ctx->ins_ids = sorted;
-    SPHX_TRY(sphx_ensure(ctx, ctx->ins_in, (nd + 1) * sizeof(double) + (nr + 1) * sizeof(int)));
-    double* d = ctx->ins_in.as<double>();
-    u64* d_moved = (u64*)(d + nd);
-    int* d_ids = (int*)(d + nd + 1);
-    HIPCHK(hipMemcpyAsync(d, hp, (nd + 1) * sizeof(double), hipMemcpyHostToDevice, stream));      // (the count's slot: zero)
-    if (nr) HIPCHK(hipMemcpyAsync(d_ids, ctx->ins_ids.data(), nr * sizeof(int), hipMemcpyHostToDevice, stream));
+    SPHX_TRY(sphx_carve_into(ctx, ctx->ins_in, c));
+    HIPCHK(hipMemcpyAsync(dv.rew_m, h.data(), (size_t)(dv.end - dv.rew_m) * sizeof(double), hipMemcpyHostToDevice, stream));   // (the count's slot: zero)
+    if (nr) HIPCHK(hipMemcpyAsync(dv.ids, ctx->ins_ids.data(), nr * sizeof(int), hipMemcpyHostToDevice, stream));
     SPHX_TRY(ctx->ins_t.mark(ctx, 1));
     // ---- a. grow, contents kept ----
     const int64_t n_new = n + n_app;
@@ -284,16 +291,15 @@ extern "C" int sphx_state_insert_rows(sphx_ctx* ctx, int s, int64_t n_rew, const
     a.hprev = st.hprev.as<double>(); a.ptype = st.ptype.as<double>(); a.id = st.id.as<int>();
     a.fun = has_fun ? ctx->fun_id.as<double>() : nullptr;
     a.mgm = drag ? st.mgm.as<double>() : nullptr; a.mcs = drag ? st.mcs.as<double>() : nullptr;
-    a.rew_ids = d_ids;
-    a.rew_m = d; a.rew_E = d + nr; a.rew_f = d + 2 * nr;
-    a.app_pos = a.rew_f + nr * S; a.app_vel = a.app_pos + 3 * na; a.app_m = a.app_vel + 3 * na; a.app_pt = a.app_m + na; a.app_E = a.app_pt + na;
-    a.app_f = a.app_E + na;
-    a.mus = a.app_f + na * S; a.gas = a.mus + S; a.gm = a.gas + S; a.se = a.gm + S;
+    a.rew_ids = dv.ids;
+    a.rew_m = dv.rew_m; a.rew_E = dv.rew_E; a.rew_f = dv.rew_f;
+    a.app_pos = dv.app_pos; a.app_vel = dv.app_vel; a.app_m = dv.app_m; a.app_pt = dv.app_pt; a.app_E = dv.app_E; a.app_f = dv.app_f;
+    a.mus = dv.tab; a.gas = dv.tab + S; a.gm = dv.tab + 2 * S; a.se = dv.tab + 3 * S;
     a.t_cmb = t_cmb;
-    a.moved = d_moved;
+    a.moved = dv.moved;
     hipLaunchKernelGGL(insert_kernel, dim3(sphx_blocks((size_t)n_new, INS_WG)), dim3(INS_WG), 0, stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&ctx->pinned->scal[0], d_moved, sizeof(u64), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&ctx->pinned->scal[0], dv.moved, sizeof(u64), hipMemcpyDeviceToHost, stream));
     SPHX_TRY(ctx->ins_t.mark(ctx, 3));
     // ---- e. what no longer fits N + m ----
     ctx->n = n_new;

@@ -10,6 +10,7 @@
 #include <functional>
 #include "../../include/sphx.h"
 #include "sphx_agb.h"
+#include "sphx_carve.h"
 
 #define SPHX_WAVE 64
 #define SPHX_W6_C 1.5666814710608448    /* 315 / (64 pi), nsc:588 */
@@ -156,6 +157,8 @@ struct StageTimer {
     int begin(sphx_ctx* ctx);           // creates the events, zeroes ms, records ev[0]
     int mark(sphx_ctx* ctx, int i);     // records ev[i]
     int end(sphx_ctx* ctx);             // ms[i] = ev[i] .. ev[i + 1]; after the call's last synchronise
+    // (at delete ctx, behind sphx_destroy's hipSetDevice)
+    ~StageTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 #define SPHX_LDS_KERNELS 16           // room in sphx_ctx::lds_raised (the LDS kernels of sphx_blob.hip and sphx_loopforms.hip: 11)
@@ -543,6 +546,20 @@ int sphx_step_research(sphx_ctx* ctx, int k, double dist);
         if (r_ != SPHX_OK) return r_;                                                        \
     } while (0)
 
+// A buffer of several arrays (sphx_carve.h): at least the layout's bytes in b, then every piece's pointer written.
+template <int CAP> static inline int sphx_carve_into(sphx_ctx* ctx, DevBuf& b, const CarveN<CAP>& c) {
+    if (c.overflowed()) return sphx_set_err(ctx, SPHX_E_ARG, "a buffer layout of more than %d pieces", CAP);
+    SPHX_TRY(sphx_ensure(ctx, b, c.bytes()));
+    c.bind(b.p);
+    return SPHX_OK;
+}
+// Device time of the stages of a family's last call on this context, from HIP events on its stream.
+static inline int last_timing(sphx_ctx* ctx, StageTimer sphx_ctx::*t, double* ms) {
+    if (!ctx || !ms) return SPHX_E_ARG;
+    for (int i = 0; i < (ctx->*t).stages; ++i) ms[i] = (ctx->*t).ms[i];
+    return SPHX_OK;
+}
+
 static inline void sphx_step_list_drop(sphx_ctx* ctx) { ctx->step_list_valid = false; ctx->step_qorder = nullptr; }
 static inline int64_t sphx_pad64(int64_t n) { return (n + 63) & ~int64_t(63); }
 // workgroups of wg lanes that cover `lanes` lanes
@@ -846,7 +863,8 @@ int sphx_chem_check_shape(sphx_ctx* ctx, const char* who, int64_t n, int k, int 
 int sphx_chem_check_scalars(sphx_ctx* ctx, const char* who, double d, double dt, const double mrn[2], double k_B, double amu, double m_0);
 int sphx_chem_tables(sphx_ctx* ctx, const char* who, int s, const double* mu_specie, const double* mineral_densities,
                      const double* sputtering_yields, const double mrn[2], double amu, double* symax_out);
-int sphx_chem_ints(sphx_ctx* ctx, int64_t n, int k, int** nbr);
+struct ChemInts { int *nbr, *isd, *ord, *cnt, *cur, *start, *end; };            // ctx->chem_int; end: behind the last block
+int sphx_chem_ints(sphx_ctx* ctx, int64_t n, int k, ChemInts* out);
 int sphx_chem_inputs(sphx_ctx* ctx, int64_t n, int s, ChemDev* in);
 int sphx_chem_run(sphx_ctx* ctx, const char* who, int64_t n, int k, int s, const ChemDev& in, const int* nbr, const ChemPar& par,
                   StageTimer* t, ChemRes* res);
@@ -918,6 +936,8 @@ static inline const double* sphx_phase_sizes(const sphx_ctx* ctx) {
     return ctx->scale_sizes_valid ? ctx->scale_sizes.as<double>() : ctx->st.hprev.as<double>();
 }
 int sphx_phase_need_list(sphx_ctx* ctx, const char* who);                          // SPHX_E_STATE unless the last step's list stands
+struct PhaseInts { int *col, *list; };                                             // ctx->phase_int: npad | k npad ints
+int sphx_phase_ints(sphx_ctx* ctx, int64_t n, int k, PhaseInts* out);
 int sphx_phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list);       // col (n) and the caller-order K-major list (k npad)
 int sphx_phase_drag_refresh(sphx_ctx* ctx, int64_t n, int s, const double* f, const double* gm, const double* se, double* mgm, double* mcs);
 

@@ -177,13 +177,12 @@ int sphx_phase_check_tables(sphx_ctx* ctx, const char* who, int s, const double*
 struct PhaseOut { double *dens, *m, *mu, *gam, *mgm, *mcs, *f, *pp, *part, *tot, *tab; size_t nchunk; };
 static int phase_out(sphx_ctx* ctx, int64_t n, int s, PhaseOut* o) {
     const size_t nn = (size_t)n, nchunk = sphx_tot_chunks(n);
-    SPHX_TRY(sphx_ensure(ctx, ctx->phase_out, (6 * nn + nn * (size_t)s + PQ_N * nn + PQ_N * nchunk + PQ_N + 4 * (size_t)s) * sizeof(double)));
-    double* p = ctx->phase_out.as<double>();
-    o->dens = p; o->m = p + nn; o->mu = p + 2 * nn; o->gam = p + 3 * nn; o->mgm = p + 4 * nn; o->mcs = p + 5 * nn;
-    o->f = p + 6 * nn; o->pp = o->f + nn * (size_t)s; o->part = o->pp + PQ_N * nn; o->tot = o->part + PQ_N * nchunk;
-    o->tab = o->tot + PQ_N;
+    Carve c;
+    c.take(o->dens, nn); c.take(o->m, nn); c.take(o->mu, nn); c.take(o->gam, nn); c.take(o->mgm, nn); c.take(o->mcs, nn);
+    c.take(o->f, nn * (size_t)s); c.take(o->pp, PQ_N * nn); c.take(o->part, PQ_N * nchunk); c.take(o->tot, PQ_N);
+    c.take(o->tab, 4 * (size_t)s);
     o->nchunk = nchunk;
-    return SPHX_OK;
+    return sphx_carve_into(ctx, ctx->phase_out, c);
 }
 
 // the bookkeeping kernel and the sums behind it; the totals' copy to the host is queued (phase_totals reads it after a synchronise)
@@ -218,9 +217,10 @@ extern "C" int sphx_dust_bookkeeping(sphx_ctx* ctx, int64_t n, int s, const doub
     PhaseOut o;
     SPHX_TRY(phase_out(ctx, n, s, &o));
     // inputs in ctx->chem_in: mass | mu | mass_before (n each) | f_un | destr | reup (n s each)
-    SPHX_TRY(sphx_ensure(ctx, ctx->chem_in, (3 * nn + 3 * ns) * sizeof(double)));
-    double* in = ctx->chem_in.as<double>();
-    double *d_m = in, *d_mu = in + nn, *d_mb = in + 2 * nn, *d_f = in + 3 * nn, *d_de = d_f + ns, *d_re = d_de + ns;
+    double *d_m, *d_mu, *d_mb, *d_f, *d_de, *d_re;
+    Carve c;
+    c.take(d_m, nn); c.take(d_mu, nn); c.take(d_mb, nn); c.take(d_f, ns); c.take(d_de, ns); c.take(d_re, ns);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->chem_in, c));
     std::memcpy(ctx->phase_tab, mu_specie, (size_t)s * sizeof(double));       // (held by the context: the upload reads it)
     std::memcpy(ctx->phase_tab + s, gamma_specie, (size_t)s * sizeof(double));
     const CopyF64 us[] = {{mass, d_m, nn}, {mu_array, d_mu, nn}, {mass_before, d_mb, nn}, {f_un, d_f, ns}, {frac_destruction, d_de, ns},
@@ -253,6 +253,13 @@ int sphx_phase_need_list(sphx_ctx* ctx, const char* who) {
     if (!ctx->step_list_valid || ctx->step_list_n != ctx->n || ctx->step_list_k != ctx->k || !ctx->nbr.p || ctx->k < 1)
         return sphx_set_err(ctx, SPHX_E_STATE, "%s: the last step's list is gone (a call on this context has overwritten it since)", who);
     return SPHX_OK;
+}
+// ctx->phase_int: col (npad ints) | the caller-order K-major list (k npad ints)
+int sphx_phase_ints(sphx_ctx* ctx, int64_t n, int k, PhaseInts* out) {
+    const size_t npad = (size_t)sphx_pad64(n);
+    Carve c;
+    c.take(out->col, npad); c.take(out->list, (size_t)k * npad);
+    return sphx_carve_into(ctx, ctx->phase_int, c);
 }
 // col (n ints) and the caller-order K-major list (k npad ints) into `list`
 int sphx_phase_translate(sphx_ctx* ctx, int* col, bool col_done, int* list) {
@@ -289,11 +296,11 @@ extern "C" int sphx_state_download_neighbors(sphx_ctx* ctx, int64_t* neighbor) {
     const int64_t n = ctx->n;
     const int k = ctx->k;
     const size_t npad = (size_t)sphx_pad64(n), nk = (size_t)n * (size_t)k;
-    SPHX_TRY(sphx_ensure(ctx, ctx->phase_int, (npad + (size_t)k * npad) * sizeof(int)));
+    PhaseInts pi;
+    SPHX_TRY(sphx_phase_ints(ctx, n, k, &pi));
     SPHX_TRY(sphx_ensure(ctx, ctx->idx64, nk * sizeof(int64_t)));
-    int* col = ctx->phase_int.as<int>();
-    int* list = col + npad;
-    SPHX_TRY(sphx_phase_translate(ctx, col, false, list));
+    const int* list = pi.list;
+    SPHX_TRY(sphx_phase_translate(ctx, pi.col, false, pi.list));
     hipLaunchKernelGGL(phase_list64_kernel, dim3(phase_blocks(nk)), dim3(PHASE_WG), 0, ctx->stream, (int)n, (int)npad, k, list,
                        (long long*)ctx->idx64.p);
     HIPCHK(hipGetLastError());
@@ -373,18 +380,19 @@ extern "C" int sphx_state_dust_phase(sphx_ctx* ctx, double dt, double d, const d
     HIPCHK(hipSetDevice(ctx->device));
     SPHX_TRY(ctx->phase_t.begin(ctx));
     hipStream_t stream = ctx->stream;
-    const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n), ns = nn * (size_t)s;
+    const size_t nn = (size_t)n, ns = nn * (size_t)s;
     // ---- the state into caller order (straight into the stages' input buffers), the list into caller ids ----
     ChemDev cin;
     DustDev din;
-    int* list;
+    ChemInts ci;
+    PhaseInts pi;
     PhaseOut o;
     SPHX_TRY(sphx_chem_inputs(ctx, n, s, &cin));
     SPHX_TRY(sphx_dust_inputs(ctx, n, s, &din));
-    SPHX_TRY(sphx_chem_ints(ctx, n, k, &list));
+    SPHX_TRY(sphx_chem_ints(ctx, n, k, &ci));
     SPHX_TRY(phase_out(ctx, n, s, &o));
-    SPHX_TRY(sphx_ensure(ctx, ctx->phase_int, (npad + (size_t)k * npad) * sizeof(int)));
-    int* col = ctx->phase_int.as<int>();
+    SPHX_TRY(sphx_phase_ints(ctx, n, k, &pi));
+    int *list = ci.nbr, *col = pi.col;                // (the translated list goes straight into chem's place for it)
     const StateArrays& st = ctx->st;
     PhaseGather ga;
     ga.n = (int)n; ga.qorder = ctx->step_qorder; ga.id = st.id.as<int>();

@@ -258,24 +258,22 @@ static int rad_run(sphx_ctx* ctx, const char* who, RadPart pa, int64_t n_src, co
     const int64_t n = pa.n;
     const int64_t R = n_src * n_dst;
     // rays, their outputs, the sources' luminosities: src | dst | lum | blocked | sd | bs
-    const size_t ray_d = (size_t)(3 * n_src + 3 * n_dst + n_src + 3 * R + 8);
-    SPHX_TRY(sphx_ensure(ctx, ctx->rad_ray, ray_d * sizeof(double)));
-    double* d_src = ctx->rad_ray.as<double>();
-    double* d_dst = d_src + 3 * n_src;
-    double* d_lum = d_dst + 3 * n_dst;
-    double* d_blocked = d_lum + n_src;
-    double* d_sd = d_blocked + R;
-    double* d_bs = d_sd + R;
+    double *d_src, *d_dst, *d_lum, *d_blocked, *d_sd, *d_bs;
+    Carve cr;
+    cr.take(d_src, 3 * (size_t)n_src); cr.take(d_dst, 3 * (size_t)n_dst); cr.take(d_lum, (size_t)n_src);
+    cr.take(d_blocked, (size_t)R); cr.take(d_sd, (size_t)R); cr.take(d_bs, (size_t)R);
+    cr.slack(8 * sizeof(double));
+    SPHX_TRY(sphx_carve_into(ctx, ctx->rad_ray, cr));
     if (n_src > 0) HIPCHK(hipMemcpyAsync(d_src, src, (size_t)n_src * 3 * sizeof(double), ray_copy, ctx->stream));
     if (n_dst > 0) HIPCHK(hipMemcpyAsync(d_dst, dst, (size_t)n_dst * 3 * sizeof(double), ray_copy, ctx->stream));
     if (transfer && n_src > 0) HIPCHK(hipMemcpyAsync(d_lum, lum, (size_t)n_src * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    // per particle
-    const size_t ints = ((size_t)n + 8) & ~size_t(3);
-    SPHX_TRY(sphx_ensure(ctx, ctx->rad_gas, 3 * ints * sizeof(int) + (16 + 3 * RAD_RED_BLOCKS) * sizeof(double)));
-    int* flag = ctx->rad_gas.as<int>();
-    int* off = flag + ints;
-    int* gidx = off + ints;
-    double* red = reinterpret_cast<double*>(gidx + ints);
+    // per particle: flag | off | gidx (n + 1 entries each and four of head-room, on 16-byte boundaries) | the reductions
+    int *flag, *off, *gidx;
+    double* red;
+    Carve cg;
+    cg.take(flag, (size_t)n + 5, 16); cg.take(off, (size_t)n + 5, 16); cg.take(gidx, (size_t)n + 5, 16);
+    cg.take(red, 16 + 3 * RAD_RED_BLOCKS, 16);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->rad_gas, cg));
     pa.flag = transfer ? flag : nullptr;
     hipLaunchKernelGGL(rad_prep_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, ctx->stream, pa, ctx->cst.amu);
     HIPCHK(hipGetLastError());
@@ -330,9 +328,10 @@ static int rad_run(sphx_ctx* ctx, const char* who, RadPart pa, int64_t n_src, co
     double *o_lf2 = nullptr, *o_ext = nullptr, *o_mom = nullptr, *o_lumf = nullptr;
     if (transfer && ng > 0) {
         const bool want_lumf = ho.lum_factor != nullptr;
-        SPHX_TRY(sphx_ensure(ctx, ctx->rad_out, (size_t)ng * (size_t)(5 + (want_lumf ? n_src : 0)) * sizeof(double)));
-        o_lf2 = ctx->rad_out.as<double>(); o_ext = o_lf2 + ng; o_mom = o_ext + ng;
-        o_lumf = want_lumf ? o_mom + 3 * ng : nullptr;
+        Carve co;
+        co.take(o_lf2, (size_t)ng); co.take(o_ext, (size_t)ng); co.take(o_mom, 3 * (size_t)ng);
+        if (want_lumf) co.take(o_lumf, (size_t)n_src * (size_t)ng);
+        SPHX_TRY(sphx_carve_into(ctx, ctx->rad_out, co));
         RadDepArgs da;
         da.ng = (int)ng; da.gidx = gidx;
         da.x = pa.x; da.y = pa.y; da.z = pa.z; da.w = pa.w; da.m = pa.m; da.sizes = pa.sizes;
@@ -353,26 +352,45 @@ static int rad_run(sphx_ctx* ctx, const char* who, RadPart pa, int64_t n_src, co
     return t ? t->end(ctx) : SPHX_OK;
 }
 
+// the two buffers of the particles' attributes, nn doubles an array
+struct RadIn { double *points, *m, *ptype, *sizes, *cross, *mu; };
+struct RadSoa { double *x, *y, *z, *h2, *w; };
+static int rad_in_carve(sphx_ctx* ctx, size_t nn, RadIn* in) {
+    Carve c;
+    c.take(in->points, 3 * nn); c.take(in->m, nn); c.take(in->ptype, nn); c.take(in->sizes, nn); c.take(in->cross, nn); c.take(in->mu, nn);
+    return sphx_carve_into(ctx, ctx->rad_in, c);
+}
+static int rad_soa_carve(sphx_ctx* ctx, size_t nn, RadSoa* soa) {
+    Carve c;
+    c.take(soa->x, nn); c.take(soa->y, nn); c.take(soa->z, nn); c.take(soa->h2, nn); c.take(soa->w, nn);
+    return sphx_carve_into(ctx, ctx->rad_soa, c);
+}
+static RadPart rad_part(int64_t n, const RadIn& in, const RadSoa& soa) {
+    RadPart pa;
+    pa.n = (int)n;
+    pa.x = soa.x; pa.y = soa.y; pa.z = soa.z; pa.h2 = soa.h2; pa.w = soa.w;
+    pa.m = in.m; pa.ptype = in.ptype; pa.sizes = in.sizes; pa.cross = in.cross; pa.mu = in.mu;
+    pa.flag = nullptr;
+    return pa;
+}
+
 // host arrays -> ctx->rad_in / rad_soa; fills pa's inputs and outputs (ptype may be NULL)
 static int rad_stage_host(sphx_ctx* ctx, int64_t n, const double* points, const double* ptype, const double* mass,
                           const double* sizes, const double* cross, const double* mu, RadPart* pa) {
     const size_t nn = (size_t)(n > 0 ? n : 1);
-    SPHX_TRY(sphx_ensure(ctx, ctx->rad_in, 8 * nn * sizeof(double)));
-    SPHX_TRY(sphx_ensure(ctx, ctx->rad_soa, 5 * nn * sizeof(double)));
-    double* in = ctx->rad_in.as<double>();
-    double* soa = ctx->rad_soa.as<double>();
+    RadIn in;
+    RadSoa soa;
+    SPHX_TRY(rad_in_carve(ctx, nn, &in));
+    SPHX_TRY(rad_soa_carve(ctx, nn, &soa));
     const size_t nd = (size_t)n;
-    const CopyF64 us[] = {{points, in, 3 * nd}, {mass, in + 3 * nn, nd}, {ptype, in + 4 * nn, nd}, {sizes, in + 5 * nn, nd},
-                          {cross, in + 6 * nn, nd}, {mu, in + 7 * nn, nd}};
+    const CopyF64 us[] = {{points, in.points, 3 * nd}, {mass, in.m, nd}, {ptype, in.ptype, nd}, {sizes, in.sizes, nd},
+                          {cross, in.cross, nd}, {mu, in.mu, nd}};
     if (n > 0) {
         SPHX_TRY(sphx_upload_f64(ctx, us, 6));
-        SPHX_TRY(sphx_aos_to_soa3(ctx, n, in, soa, soa + nn, soa + 2 * nn));
+        SPHX_TRY(sphx_aos_to_soa3(ctx, n, in.points, soa.x, soa.y, soa.z));
     }
-    pa->n = (int)n;
-    pa->x = soa; pa->y = soa + nn; pa->z = soa + 2 * nn; pa->h2 = soa + 3 * nn; pa->w = soa + 4 * nn;
-    pa->m = in + 3 * nn; pa->ptype = ptype ? in + 4 * nn : nullptr; pa->sizes = in + 5 * nn; pa->cross = in + 6 * nn;
-    pa->mu = in + 7 * nn;
-    pa->flag = nullptr;
+    *pa = rad_part(n, in, soa);
+    if (!ptype) pa->ptype = nullptr;
     return SPHX_OK;
 }
 
@@ -429,11 +447,11 @@ extern "C" int sphx_state_rad_transfer(sphx_ctx* ctx, const double* cross, int64
     HIPCHK(hipSetDevice(ctx->device));
     SPHX_TRY(ctx->rad_t.begin(ctx));
     const size_t nn = (size_t)n;
-    SPHX_TRY(sphx_ensure(ctx, ctx->rad_in, 8 * nn * sizeof(double)));
-    SPHX_TRY(sphx_ensure(ctx, ctx->rad_soa, 5 * nn * sizeof(double)));
-    double* in = ctx->rad_in.as<double>();
-    double* soa = ctx->rad_soa.as<double>();
-    HIPCHK(hipMemcpyAsync(in + 6 * nn, cross, nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    RadIn in;
+    RadSoa soa;
+    SPHX_TRY(rad_in_carve(ctx, nn, &in));
+    SPHX_TRY(rad_soa_carve(ctx, nn, &soa));
+    HIPCHK(hipMemcpyAsync(in.cross, cross, nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     const StateArrays& s = ctx->st;
     // the resident state (storage order) into the caller's order: the SoA positions, m, ptype, hprev, mu (slot by slot: no
     // list is read here, so no processing order and no col)
@@ -441,13 +459,9 @@ extern "C" int sphx_state_rad_transfer(sphx_ctx* ctx, const double* cross, int64
     ga.n = (int)n; ga.id = s.id.as<int>();
     ga.x = s.x.as<double>(); ga.y = s.y.as<double>(); ga.z = s.z.as<double>();
     ga.m = s.m.as<double>(); ga.pt = s.ptype.as<double>(); ga.h = sphx_phase_sizes(ctx); ga.mu = s.mu.as<double>();
-    ga.sx = soa; ga.sy = soa + nn; ga.sz = soa + 2 * nn; ga.om = in + 3 * nn; ga.opt = in + 4 * nn; ga.oh = in + 5 * nn; ga.omu = in + 7 * nn;
+    ga.sx = soa.x; ga.sy = soa.y; ga.sz = soa.z; ga.om = in.m; ga.opt = in.ptype; ga.oh = in.sizes; ga.omu = in.mu;
     SPHX_TRY(sphx_phase_gather(ctx, ga));
-    RadPart pa;
-    pa.n = (int)n;
-    pa.x = soa; pa.y = soa + nn; pa.z = soa + 2 * nn; pa.h2 = soa + 3 * nn; pa.w = soa + 4 * nn;
-    pa.m = in + 3 * nn; pa.ptype = in + 4 * nn; pa.sizes = in + 5 * nn; pa.cross = in + 6 * nn; pa.mu = in + 7 * nn;
-    pa.flag = nullptr;
+    const RadPart pa = rad_part(n, in, soa);
     const RadHostOut ho{lf2, momentum, extinction, blocked, star_distance, lum_factor};
     return rad_run(ctx, "sphx_state_rad_transfer", pa, n_src, src, luminosities, n_dst, dst, dt, mode, true, ho, false, &ctx->rad_t, nullptr);
 }
@@ -460,12 +474,11 @@ int sphx_rad_run_dev(sphx_ctx* ctx, const char* who, int64_t n, const double* x,
                      const double* src_dev, const double* lum_host, int64_t n_dst, const double* dst_dev, double dt, int mode,
                      RadDevOut* out) {
     SPHX_TRY(rad_check(ctx, who, n, n_src, src_dev, n_dst, dst_dev, mode));
-    const size_t nn = (size_t)n;
-    SPHX_TRY(sphx_ensure(ctx, ctx->rad_soa, 5 * nn * sizeof(double)));
-    double* soa = ctx->rad_soa.as<double>();
+    RadSoa soa;                                      // (h2 and w alone: the positions are the caller's)
+    SPHX_TRY(rad_soa_carve(ctx, (size_t)n, &soa));
     RadPart pa;
     pa.n = (int)n;
-    pa.x = x; pa.y = y; pa.z = z; pa.h2 = soa + 3 * nn; pa.w = soa + 4 * nn;
+    pa.x = x; pa.y = y; pa.z = z; pa.h2 = soa.h2; pa.w = soa.w;
     pa.m = m; pa.ptype = ptype; pa.sizes = sizes; pa.cross = cross; pa.mu = mu;
     pa.flag = nullptr;
     const RadHostOut ho{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -145,12 +145,8 @@ __global__ __launch_bounds__(RP_WG) void rp_book_kernel(RpBook a) {
 // host side
 // =====================================================================================================================
 
-// doubles out of ctx->radphase_buf, one after the other
-struct RpBump {
-    double* p;
-    double* take(size_t count) { double* r = p; p += (count + 1) & ~size_t(1); return r; }
-};
-static size_t rp_even(size_t c) { return (c + 1) & ~size_t(1); }
+// (the arrays of ctx->radphase_buf and ctx->radstate_buf each start on a 16-byte boundary: RP_AL)
+#define RP_AL 16
 
 static int rp_check(sphx_ctx* ctx, const char* who, int64_t n, int s, int64_t n_gas) {
     if (n < 1 || n > 0x7FFFFFF0ll || s < 6 || s > SPHX_MAX_SPECIES)
@@ -162,10 +158,11 @@ static int rp_check(sphx_ctx* ctx, const char* who, int64_t n, int s, int64_t n_
 // (n_gas < 0: no number is expected; *count_out, if given, receives the number found)
 static int rp_ordinals(sphx_ctx* ctx, const char* who, int64_t n, const double* d_pt, int64_t n_gas, int** off_out,
                        int64_t* count_out = nullptr) {
-    const size_t ints = ((size_t)n + 8) & ~size_t(3);
-    SPHX_TRY(sphx_ensure(ctx, ctx->radphase_int, 2 * ints * sizeof(int)));
-    int* flag = ctx->radphase_int.as<int>();
-    int* off = flag + ints;
+    int *flag, *off;                                 // n + 1 entries each and four of head-room, on 16-byte boundaries
+    Carve c;
+    c.take(flag, (size_t)n + 5, 16); c.take(off, (size_t)n + 5, 16);
+    c.pad(16);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->radphase_int, c));
     hipLaunchKernelGGL(rp_flag_kernel, dim3(sphx_blocks((size_t)n + 1, 256)), dim3(256), 0, ctx->stream, (int)n, d_pt, flag);
     HIPCHK(hipGetLastError());
     SPHX_TRY(sphx_excl_scan_int(ctx, flag, off, (int)n));
@@ -192,11 +189,13 @@ extern "C" int sphx_rad_ionise(sphx_ctx* ctx, int64_t n, int s, int64_t n_gas, c
     HIPCHK(hipSetDevice(ctx->device));
     SPHX_TRY(ctx->radphase_t.begin(ctx));
     const size_t nn = (size_t)n, ns = nn * (size_t)s, ng = (size_t)n_gas;
-    SPHX_TRY(sphx_ensure(ctx, ctx->radphase_buf, (2 * rp_even(ns) + 2 * rp_even(nn) + rp_even(ng) + rp_even(3 * ng) + rp_even(3 * (size_t)s) + 8) *
-                                                     sizeof(double)));
-    RpBump b{ctx->radphase_buf.as<double>()};
-    double *d_f = b.take(ns), *d_fo = b.take(ns), *d_pt = b.take(nn), *d_m = b.take(nn), *d_lf2 = b.take(ng), *d_fr = b.take(3 * ng);
-    double* d_tab = b.take(3 * (size_t)s);
+    double *d_f, *d_fo, *d_pt, *d_m, *d_lf2, *d_fr, *d_tab;
+    Carve b;
+    b.take(d_f, ns, RP_AL); b.take(d_fo, ns, RP_AL); b.take(d_pt, nn, RP_AL); b.take(d_m, nn, RP_AL); b.take(d_lf2, ng, RP_AL);
+    b.take(d_fr, 3 * ng, RP_AL); b.take(d_tab, 3 * (size_t)s, RP_AL);
+    b.pad(RP_AL);
+    b.slack(8 * sizeof(double));
+    SPHX_TRY(sphx_carve_into(ctx, ctx->radphase_buf, b));
     double* tab = ctx->radphase_tab;                 // (held by the context: the upload reads it)
     std::memcpy(tab, mu_specie, (size_t)s * sizeof(double));
     std::memcpy(tab + s, cross_sections, (size_t)s * sizeof(double));
@@ -259,13 +258,14 @@ static int rp_book_host(sphx_ctx* ctx, const char* who, bool cool, int64_t n, in
     HIPCHK(hipSetDevice(ctx->device));
     SPHX_TRY(ctx->radphase_t.begin(ctx));
     const size_t nn = (size_t)n, ns = nn * (size_t)s, ng = (size_t)n_gas, nchunk = sphx_tot_chunks(n);
-    SPHX_TRY(sphx_ensure(ctx, ctx->radphase_buf, (rp_even(ns) + 12 * rp_even(nn) + 2 * rp_even(3 * nn) + rp_even(ng) + rp_even(3 * ng) +
-                                                  rp_even(3 * (size_t)s) + rp_even(RQ_N * nn) + rp_even(RQ_N * nchunk) + RQ_N + 8) * sizeof(double)));
-    RpBump b{ctx->radphase_buf.as<double>()};
-    double *d_f = b.take(ns), *d_pt = b.take(nn), *d_m = b.take(nn), *d_E = b.take(nn), *d_T = b.take(nn), *d_x = b.take(nn), *d_en = b.take(nn);
-    double *d_mu = b.take(nn), *d_g = b.take(nn), *d_cr = b.take(nn), *d_Eo = b.take(nn), *d_To = b.take(nn);
-    double *d_v = b.take(3 * nn), *d_vo = b.take(3 * nn), *d_lf2 = b.take(ng), *d_mom = b.take(3 * ng), *d_tab = b.take(3 * (size_t)s);
-    double *d_pp = b.take(RQ_N * nn), *d_part = b.take(RQ_N * nchunk), *d_tot = b.take(RQ_N);
+    double *d_f, *d_pt, *d_m, *d_E, *d_T, *d_x, *d_en, *d_mu, *d_g, *d_cr, *d_Eo, *d_To, *d_v, *d_vo, *d_lf2, *d_mom, *d_tab, *d_pp, *d_part, *d_tot;
+    Carve b;
+    b.take(d_f, ns, RP_AL);
+    for (double** v : {&d_pt, &d_m, &d_E, &d_T, &d_x, &d_en, &d_mu, &d_g, &d_cr, &d_Eo, &d_To}) b.take(*v, nn, RP_AL);
+    b.take(d_v, 3 * nn, RP_AL); b.take(d_vo, 3 * nn, RP_AL); b.take(d_lf2, ng, RP_AL); b.take(d_mom, 3 * ng, RP_AL);
+    b.take(d_tab, 3 * (size_t)s, RP_AL); b.take(d_pp, RQ_N * nn, RP_AL); b.take(d_part, RQ_N * nchunk, RP_AL); b.take(d_tot, RQ_N, RP_AL);
+    b.slack(8 * sizeof(double));
+    SPHX_TRY(sphx_carve_into(ctx, ctx->radphase_buf, b));
     double* tab = ctx->radphase_tab;
     std::memcpy(tab, mu_specie, (size_t)s * sizeof(double));
     std::memcpy(tab + s, gamma_specie, (size_t)s * sizeof(double));
@@ -397,22 +397,23 @@ extern "C" int sphx_state_rad_phase(sphx_ctx* ctx, double dt, double d, int64_t 
     SPHX_TRY(ctx->radstate_t.begin(ctx));
     // ---- buffers ----
     const size_t nchunk = sphx_tot_chunks(n), g = (size_t)ng;
-    const size_t doubles = 4 * rp_even(3 * nn) + 20 * rp_even(nn) + 2 * rp_even(ns) + rp_even(3 * g) + rp_even(3 * (size_t)n_src) +
-                           rp_even(3 * (size_t)n_dst) + rp_even(8 * ss) + rp_even(RQ_N * nn) + rp_even(RQ_N * nchunk) + RQ_N + 16;
-    SPHX_TRY(sphx_ensure(ctx, ctx->radstate_buf, doubles * sizeof(double)));
-    RpBump b{ctx->radstate_buf.as<double>()};
-    double *g_pos = b.take(3 * nn), *g_x = b.take(nn), *g_y = b.take(nn), *g_z = b.take(nn), *g_vel = b.take(3 * nn), *g_m = b.take(nn);
-    double *g_mu = b.take(nn), *g_h = b.take(nn), *g_T = b.take(nn), *g_pt = b.take(nn), *g_E = b.take(nn);
-    double *f0 = b.take(ns), *f1 = b.take(ns), *cross0 = b.take(nn), *d_fr = b.take(3 * g);
-    double *h_mu = b.take(nn), *h_g = b.take(nn), *h_cr = b.take(nn), *h_E = b.take(nn), *h_T = b.take(nn);
-    double *c_mu = b.take(nn), *c_g = b.take(nn), *c_cr = b.take(nn), *c_E = b.take(nn), *c_T = b.take(nn), *c_vel = b.take(3 * nn);
-    double *d_mgm = b.take(nn), *d_mcs = b.take(nn), *d_src = b.take(3 * (size_t)n_src), *d_dst = b.take(3 * (size_t)n_dst);
-    double *d_tab = b.take(8 * ss), *d_pp = b.take(RQ_N * nn), *d_part = b.take(RQ_N * nchunk), *d_tot = b.take(RQ_N);
-    const size_t nid = ((size_t)(n_src + n_dst) + 4) & ~size_t(3);
-    SPHX_TRY(sphx_ensure(ctx, ctx->radstate_int, (npad + (size_t)k * npad + nid) * sizeof(int)));
-    int* col = ctx->radstate_int.as<int>();
-    int* list = col + npad;
-    int* d_ids = list + (size_t)k * npad;
+    double *g_pos, *g_x, *g_y, *g_z, *g_vel, *g_m, *g_mu, *g_h, *g_T, *g_pt, *g_E, *f0, *f1, *cross0, *d_fr, *h_mu, *h_g, *h_cr, *h_E, *h_T;
+    double *c_mu, *c_g, *c_cr, *c_E, *c_T, *c_vel, *d_mgm, *d_mcs, *d_src, *d_dst, *d_tab, *d_pp, *d_part, *d_tot;
+    CarveN<40> b;
+    b.take(g_pos, 3 * nn, RP_AL); b.take(g_x, nn, RP_AL); b.take(g_y, nn, RP_AL); b.take(g_z, nn, RP_AL); b.take(g_vel, 3 * nn, RP_AL);
+    for (double** v : {&g_m, &g_mu, &g_h, &g_T, &g_pt, &g_E}) b.take(*v, nn, RP_AL);
+    b.take(f0, ns, RP_AL); b.take(f1, ns, RP_AL); b.take(cross0, nn, RP_AL); b.take(d_fr, 3 * g, RP_AL);
+    for (double** v : {&h_mu, &h_g, &h_cr, &h_E, &h_T, &c_mu, &c_g, &c_cr, &c_E, &c_T}) b.take(*v, nn, RP_AL);
+    b.take(c_vel, 3 * nn, RP_AL); b.take(d_mgm, nn, RP_AL); b.take(d_mcs, nn, RP_AL);
+    b.take(d_src, 3 * (size_t)n_src, RP_AL); b.take(d_dst, 3 * (size_t)n_dst, RP_AL);
+    b.take(d_tab, 8 * ss, RP_AL); b.take(d_pp, RQ_N * nn, RP_AL); b.take(d_part, RQ_N * nchunk, RP_AL); b.take(d_tot, RQ_N, RP_AL);
+    b.slack(16 * sizeof(double));
+    SPHX_TRY(sphx_carve_into(ctx, ctx->radstate_buf, b));
+    int *col, *list, *d_ids;                         // ids: the sources', then the targets', and one more
+    Carve bi;
+    bi.take(col, npad); bi.take(list, (size_t)k * npad); bi.take(d_ids, (size_t)(n_src + n_dst) + 1);
+    bi.pad(16);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->radstate_int, bi));
     // tables: [0,3s) mu_specie | nsc cross_sections | frac_dest (ionise); [3s,6s) mu_specie | gamma | driver cross (bookkeeping);
     // [6s,8s) grain_mass | sigma_effective
     double* tab = ctx->radstate_tab;                 // (held by the context: the upload below reads it)

@@ -244,10 +244,9 @@ extern "C" int sphx_length_scale_finish(int64_t n_slow, int64_t n_nan, double qf
 
 struct ScaleWork { u64 *key, *hist, *scal; };
 static int scale_work(sphx_ctx* ctx, int64_t n, ScaleWork* w) {
-    SPHX_TRY(sphx_ensure(ctx, ctx->scale_work, ((size_t)n + SCALE_BINS + SS_N) * sizeof(u64)));
-    w->key = ctx->scale_work.as<u64>();
-    w->hist = w->key + (size_t)n; w->scal = w->hist + SCALE_BINS;
-    return SPHX_OK;
+    Carve c;
+    c.take(w->key, (size_t)n); c.take(w->hist, SCALE_BINS); c.take(w->scal, SS_N);
+    return sphx_carve_into(ctx, ctx->scale_work, c);
 }
 static unsigned scale_blocks(size_t lanes) { return sphx_blocks(lanes, SCALE_WG); }
 static unsigned scale_grid(int64_t n) {
@@ -310,12 +309,14 @@ extern "C" int sphx_length_scale(sphx_ctx* ctx, int64_t n, const double* points,
     const size_t nn = (size_t)n;
     ScaleWork w;
     SPHX_TRY(scale_work(ctx, n, &w));
-    SPHX_TRY(sphx_ensure(ctx, ctx->scale_in, 6 * nn * sizeof(double)));
-    double* p = ctx->scale_in.as<double>();
+    double *p, *v;
+    Carve c;
+    c.take(p, 3 * nn); c.take(v, 3 * nn);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->scale_in, c));
     SPHX_TRY(ctx->scale_t.begin(ctx));
-    const CopyF64 us[] = {{points, p, 3 * nn}, {velocities, p + 3 * nn, 3 * nn}};
+    const CopyF64 us[] = {{points, p, 3 * nn}, {velocities, v, 3 * nn}};
     SPHX_TRY(sphx_upload_f64(ctx, us, 2));
-    const ScaleKeys ka{(int)n, p, p + 1, p + 2, 3, p + 3 * nn, p + 3 * nn + 1, p + 3 * nn + 2, 3, v_max2};
+    const ScaleKeys ka{(int)n, p, p + 1, p + 2, 3, v, v + 1, v + 2, 3, v_max2};
     ScaleSel sel;
     SPHX_TRY(scale_select(ctx, who, ka, qf, n_int, fill, w, &sel));
     for (int i = 3; i <= 5; ++i) SPHX_TRY(ctx->scale_t.mark(ctx, i));
@@ -328,11 +329,11 @@ extern "C" int sphx_length_scale(sphx_ctx* ctx, int64_t n, const double* points,
 struct ScaleBufs { unsigned *rev, *nontriv; double *sizes, *smooth; long long *rev64, *nontriv64; };
 static int scale_bufs(sphx_ctx* ctx, int64_t n, ScaleBufs* o) {
     const size_t nn = (size_t)n;
-    SPHX_TRY(sphx_ensure(ctx, ctx->scale_int, 2 * nn * sizeof(unsigned)));
-    SPHX_TRY(sphx_ensure(ctx, ctx->scale_out, 4 * nn * sizeof(double)));
-    o->rev = ctx->scale_int.as<unsigned>(); o->nontriv = o->rev + nn;
-    o->sizes = ctx->scale_out.as<double>(); o->smooth = o->sizes + nn;
-    o->rev64 = (long long*)(o->smooth + nn); o->nontriv64 = o->rev64 + nn;
+    Carve ci, co;
+    ci.take(o->rev, nn); ci.take(o->nontriv, nn);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->scale_int, ci));
+    co.take(o->sizes, nn); co.take(o->smooth, nn); co.take(o->rev64, nn); co.take(o->nontriv64, nn);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->scale_out, co));
     HIPCHK(hipMemsetAsync(o->rev, 0, 2 * nn * sizeof(unsigned), ctx->stream));
     return SPHX_OK;
 }
@@ -358,19 +359,21 @@ extern "C" int sphx_adapt_sizes(sphx_ctx* ctx, int64_t n, int k, const int64_t* 
     ScaleBufs o;
     SPHX_TRY(scale_bufs(ctx, n, &o));
     // inputs: densities | densities_0 | sizes | ptype (n each) | the list (n k int64)
-    SPHX_TRY(sphx_ensure(ctx, ctx->scale_in, (4 * nn + nk) * sizeof(double)));
-    double* p = ctx->scale_in.as<double>();
-    long long* nb = (long long*)(p + 4 * nn);
+    double *d_rho, *d_rho0, *d_sz, *d_pt;
+    long long* nb;
+    Carve c;
+    c.take(d_rho, nn); c.take(d_rho0, nn); c.take(d_sz, nn); c.take(d_pt, nn); c.take(nb, nk);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->scale_in, c));
     SPHX_TRY(ctx->scale_t.begin(ctx));
     HIPCHK(hipMemsetAsync(w.scal, 0, SS_N * sizeof(u64), st));
-    const CopyF64 us[] = {{densities, p, nn}, {densities_0, p + nn, nn}, {sizes, p + 2 * nn, nn}, {ptype, p + 3 * nn, nn}, {neighbor, nb, nk}};
+    const CopyF64 us[] = {{densities, d_rho, nn}, {densities_0, d_rho0, nn}, {sizes, d_sz, nn}, {ptype, d_pt, nn}, {neighbor, nb, nk}};
     SPHX_TRY(sphx_upload_f64(ctx, us, 5));
     SPHX_TRY(ctx->scale_t.mark(ctx, 1));
     SPHX_TRY(ctx->scale_t.mark(ctx, 2));
     hipLaunchKernelGGL(scale_count_rows_kernel, dim3(scale_blocks(nk)), dim3(SCALE_WG), 0, st, (int)n, k, nb, o.rev, o.nontriv, w.scal);
     HIPCHK(hipGetLastError());
     SPHX_TRY(ctx->scale_t.mark(ctx, 3));
-    const ScaleAdapt a{(int)n, nullptr, o.rev, o.nontriv, p, densities_0 ? p + nn : nullptr, p + 2 * nn, p + 3 * nn, d, d_dust,
+    const ScaleAdapt a{(int)n, nullptr, o.rev, o.nontriv, d_rho, densities_0 ? d_rho0 : nullptr, d_sz, d_pt, d, d_dust,
                        nullptr, o.sizes, o.smooth, nullptr, o.rev64, o.nontriv64};
     SPHX_TRY(scale_adapt_run(ctx, a, w.scal));
     SPHX_TRY(ctx->scale_t.mark(ctx, 4));
@@ -466,7 +469,5 @@ extern "C" int sphx_state_download_sizes(sphx_ctx* ctx, double* sizes) {
 }
 
 extern "C" int sphx_scale_last_timing(sphx_ctx* ctx, double ms[5]) {
-    if (!ctx || !ms) return SPHX_E_ARG;
-    for (int i = 0; i < ctx->scale_t.stages; ++i) ms[i] = ctx->scale_t.ms[i];
-    return SPHX_OK;
+    return last_timing(ctx, &sphx_ctx::scale_t, ms);
 }

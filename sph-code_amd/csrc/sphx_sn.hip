@@ -206,10 +206,12 @@ static int sn_select(sphx_ctx* ctx, const char* who, int64_t n, const double* ma
                      int64_t* nsel, bool* crossed, double** cm_out, int** cid_out) {
     hipStream_t st = ctx->stream;
     const int P = sn_pow2(c);
-    SPHX_TRY(sphx_ensure(ctx, ctx->sn_cand, (size_t)P * (sizeof(u64) + sizeof(double) + sizeof(int))));      // keys | masses | ids
-    u64* ckey = ctx->sn_cand.as<u64>();
-    double* cm = (double*)(ckey + P);
-    int* cid = (int*)(cm + P);
+    u64* ckey;
+    double* cm;
+    int* cid;
+    Carve cc;
+    cc.take(ckey, (size_t)P); cc.take(cm, (size_t)P); cc.take(cid, (size_t)P);      // keys | masses | ids
+    SPHX_TRY(sphx_carve_into(ctx, ctx->sn_cand, cc));
     HIPCHK(hipMemsetAsync(scal + SNS_CURSOR, 0, sizeof(u64), st));
     hipLaunchKernelGGL(sn_pad_kernel, dim3(sphx_blocks((size_t)P, SN_WG)), dim3(SN_WG), 0, st, P, ckey, cid);
     hipLaunchKernelGGL(sn_compact_kernel, dim3(sphx_blocks((size_t)n, SN_WG)), dim3(SN_WG), 0, st, (int)n, key, ptype, mass, bound, P, ckey, cid,
@@ -284,6 +286,23 @@ static int sn_bound(sphx_ctx* ctx, int64_t n, const double* mass, const double* 
     return SPHX_OK;
 }
 
+// ctx->sn_work: keys (n) | histograms (2 SN_BINS) | scalars (SNS_N) | chunk sums | total
+struct SnWork { u64 *key, *hist, *scal; double *part, *tot; };
+static int sn_work_carve(sphx_ctx* ctx, int64_t n, SnWork* w) {
+    Carve c;
+    c.take(w->key, (size_t)n); c.take(w->hist, 2 * SN_BINS); c.take(w->scal, SNS_N); c.take(w->part, sphx_tot_chunks(n)); c.take(w->tot, 1);
+    c.slack(7 * sizeof(double));
+    return sphx_carve_into(ctx, ctx->sn_work, c);
+}
+// ctx->sn_in: points (n,3) | velocities (n,3) | masses | ptypes (n each); gathered from the state: | sizes | mu (n each)
+struct SnIn { double *pos, *vel, *m, *pt, *h, *mu; };
+static int sn_in_carve(sphx_ctx* ctx, size_t nn, bool gathered, SnIn* in) {
+    Carve c;
+    c.take(in->pos, 3 * nn); c.take(in->vel, 3 * nn); c.take(in->m, nn); c.take(in->pt, nn);
+    if (gathered) { c.take(in->h, nn); c.take(in->mu, nn); }
+    return sphx_carve_into(ctx, ctx->sn_in, c);
+}
+
 int sphx_sn_check(sphx_ctx* ctx, const char* who, int64_t n, int64_t n_sn, const int64_t* supernova_pos, double mass_displaced, int64_t cap) {
     if (n < 1 || n > 0x7FFFFFF0ll || n_sn < 0 || cap < 0 || cap > 0x7FFFFFF0ll)
         return sphx_set_err(ctx, SPHX_E_ARG, "%s: n=%lld, n_sn=%lld, cap=%lld (need 1 <= n < 2^31, n_sn >= 0, 0 <= cap < 2^31)", who, (long long)n,
@@ -308,16 +327,14 @@ int sphx_sn_run(sphx_ctx* ctx, const char* who, int64_t n, const double* pos, co
     for (int i = 0; i < SPHX_SN_STAGES; ++i) ctx->sn_ms[i] = 0.0;
     for (int i = 0; i < SPHX_SN_NCOUNT; ++i) ctx->sn_counts[i] = 0;
     const size_t nn = (size_t)n, ns = (size_t)(n_sn > 0 ? n_sn : 1), cp = (size_t)(cap > 0 ? cap : 1);
-    // work: keys (n) | histograms (2 SN_BINS) | scalars (SNS_N) | chunk sums | total
-    const size_t nchunk = sphx_tot_chunks(n);
-    SPHX_TRY(sphx_ensure(ctx, ctx->sn_work, (nn + 2 * SN_BINS + SNS_N + nchunk + 8) * sizeof(double)));
-    u64* key = ctx->sn_work.as<u64>();
-    u64 *hist = key + nn, *scal = hist + 2 * SN_BINS;
-    double *part = (double*)(scal + SNS_N), *tot = part + nchunk;
+    SnWork w;
+    SPHX_TRY(sn_work_carve(ctx, n, &w));
+    u64 *key = w.key, *hist = w.hist, *scal = w.scal;
+    double *part = w.part, *tot = w.tot;
     // outputs: d_vels (cap,3) | true_mass (n_sn) | vel (n_sn) | sel_ids (cap) int64
-    SPHX_TRY(sphx_ensure(ctx, ctx->sn_out, (4 * cp + 2 * ns) * sizeof(double)));
-    res->d_vels = ctx->sn_out.as<double>(); res->true_mass = res->d_vels + 3 * cp; res->vel = res->true_mass + ns;
-    res->sel_ids = (long long*)(res->vel + ns);
+    Carve co;
+    co.take(res->d_vels, 3 * cp); co.take(res->true_mass, ns); co.take(res->vel, ns); co.take(res->sel_ids, cp);
+    SPHX_TRY(sphx_carve_into(ctx, ctx->sn_out, co));
     res->sel_count.assign((size_t)n_sn, 0);
     res->total = 0;
     HIPCHK(hipMemsetAsync(scal, 0, SNS_N * sizeof(u64), st));
@@ -379,10 +396,9 @@ extern "C" int sphx_supernova_impulse(sphx_ctx* ctx, int64_t n, const double* po
     SPHX_TRY(sphx_sn_check(ctx, "sphx_supernova_impulse", n, n_sn, supernova_pos, mass_displaced, cap));
     HIPCHK(hipSetDevice(ctx->device));
     const size_t nn = (size_t)n;
-    // inputs: points (n,3) | velocities (n,3) | masses (n) | ptypes (n)
-    SPHX_TRY(sphx_ensure(ctx, ctx->sn_in, 8 * nn * sizeof(double)));
-    double* p = ctx->sn_in.as<double>();
-    double *d_pos = p, *d_v = p + 3 * nn, *d_m = p + 6 * nn, *d_pt = p + 7 * nn;
+    SnIn in;
+    SPHX_TRY(sn_in_carve(ctx, nn, false, &in));
+    double *d_pos = in.pos, *d_v = in.vel, *d_m = in.m, *d_pt = in.pt;
     const CopyF64 us[] = {{points, d_pos, 3 * nn}, {velocities_inout, d_v, 3 * nn}, {masses, d_m, nn}, {ptypes, d_pt, nn}};
     SPHX_TRY(sphx_upload_f64(ctx, us, 4));
     SnRes res;
@@ -419,14 +435,13 @@ extern "C" int sphx_state_supernova_impulse(sphx_ctx* ctx, int64_t n_sn, const i
     const int k = ctx->k;
     SPHX_TRY(sphx_sn_check(ctx, who, n, n_sn, ids, mass_displaced, cap));
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t nn = (size_t)n, npad = (size_t)sphx_pad64(n);
-    // gathered: points (n,3) | velocities (n,3) | masses | ptypes | sizes | mu (not read) (n each)
-    SPHX_TRY(sphx_ensure(ctx, ctx->sn_in, 10 * nn * sizeof(double)));
-    double* p = ctx->sn_in.as<double>();
-    double *d_pos = p, *d_v = p + 3 * nn, *d_m = p + 6 * nn, *d_pt = p + 7 * nn, *d_h = p + 8 * nn, *d_mu = p + 9 * nn;
-    SPHX_TRY(sphx_ensure(ctx, ctx->phase_int, (npad + (size_t)k * npad) * sizeof(int)));
-    int* col = ctx->phase_int.as<int>();
-    int* list = col + npad;
+    // gathered (mu is not read)
+    SnIn in;
+    SPHX_TRY(sn_in_carve(ctx, (size_t)n, true, &in));
+    double *d_pos = in.pos, *d_v = in.vel, *d_m = in.m, *d_pt = in.pt, *d_h = in.h, *d_mu = in.mu;
+    PhaseInts pi;
+    SPHX_TRY(sphx_phase_ints(ctx, n, k, &pi));
+    int *col = pi.col, *list = pi.list;
     const StateArrays& st = ctx->st;
     PhaseGather ga;
     ga.n = (int)n; ga.qorder = ctx->step_qorder; ga.id = st.id.as<int>();
@@ -443,7 +458,9 @@ extern "C" int sphx_state_supernova_impulse(sphx_ctx* ctx, int64_t n_sn, const i
     if (res.total > cap)
         return sphx_set_err(ctx, SPHX_E_ARG, "%s: cap=%lld, the selections hold %lld rows", who, (long long)cap, (long long)res.total);
     // drv:357: crossing_time on the step's list, the KICKED velocities, the step's radii
-    u64* ct_bits = ctx->sn_work.as<u64>() + nn + 2 * SN_BINS + SNS_CT;
+    SnWork w;
+    SPHX_TRY(sn_work_carve(ctx, n, &w));            // (as sphx_sn_run has just carved it)
+    u64* ct_bits = w.scal + SNS_CT;
     SPHX_TRY(sphx_loop_ct_dev(ctx, n, k, list, d_v, d_h, d_pt, ct_bits));
     const PhaseBack ba{(int)n, st.id.as<int>(), d_v, st.vx.as<double>(), st.vy.as<double>(), st.vz.as<double>(), 0,
                        {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}};
