@@ -899,6 +899,58 @@ int sphx_state_download_star_ages(sphx_ctx* ctx, double* star_ages);
 int sphx_state_advance_star_ages(sphx_ctx* ctx, double dt);
 int sphx_advance_star_ages(sphx_ctx* ctx, int64_t n, double* star_ages, const double* ptype, double dt);
 int sphx_census_last_timing(sphx_ctx* ctx, double ms[4]);
+/* ---- the projected maps: the state integrated along a line of sight onto a pixel grid       drv:563-597 ----- *
+ * The driver draws the cloud every pass (gas by log T, dust by its temperature, stars by mass, in the y-z plane).  What
+ * stands behind such a picture is the projection, formed here on the device: column density of gas and of dust and the
+ * column-weighted temperature of both, at the centres of n_u x n_v pixels.
+ *
+ * The image.  axes = (a_u, a_v), two different coordinate indices; the line of sight is the third.  center (c_u, c_v),
+ * half_width (w_u, w_v) > 0, npix (n_u, n_v).  Pixel (i, j) has its centre at
+ *     u_i = c_u - w_u + (i + 1/2) 2 w_u / n_u     (evaluated left to right),   v_j likewise.
+ * Outputs are (n_v, n_u), row-major: out[j n_u + i].
+ *
+ * Particle k.  Footprint radius R_k = h(m_k) = (m_k/m_0)^(1/3) d for gas (type 0), sizes[k] for dust (type 2); no other
+ * type has one, and such a row contributes to nothing.  With b^2 = (u_i - x_k,a_u)^2 + (v_j - x_k,a_v)^2, s = R_k^2 - b^2:
+ *     sigma_k = c_k s^3 sqrt(s) for s > 0, else 0,    c_k = m_k (9/(2 pi)) / R_k^9   (formed once per particle)
+ * - the poly6 weight of Weigh2 (nsc:673-681) integrated along the line of sight: the integral of (R^2 - b^2 - z^2)^3 over
+ * the chord is (32/35)(R^2 - b^2)^(7/2), times 315/(64 pi).
+ * depth = (lo, hi), or NULL: only particles whose line-of-sight coordinate lies in [lo, hi) count.
+ * A gas or dust row with a NaN or infinite coordinate (any of the three), mass or radius, or with R_k <= 0, contributes
+ * to nothing and is counted in *skipped (whatever the depth says).
+ *
+ * The fields, per pixel:
+ *   gas_column        sum of sigma_k over the gas rows with s > 0
+ *   dust_column       the same over the dust rows
+ *   gas_temperature   sum(sigma_k T_k) / sum(sigma_k) over the gas terms with sigma_k T_k > 0 (temperature_arb's mask,
+ *                     nsc:1474-1480: a negative T drops out as it does in sphx_arb_fields); 0 where the denominator is 0
+ *   dust_temperature  sum(sigma_k T_k) / sum(sigma_k) over the dust terms with sigma_k > 0; 0 where the denominator is 0
+ *   count (int64)     the gas and dust rows with s > 0 at the pixel
+ * Every sum runs in ASCENDING PARTICLE ID: the same bits on every call, whatever order the state is stored in.  No
+ * floating-point atomics.  Any output pointer may be NULL; a NULL output's sums are not formed, the others keep their bits.
+ * *pairs: the (particle, tile) pairs the call listed - the image is cut into tiles of 16 x 16 pixels, and a particle is
+ * listed in the tiles that hold a pixel with |u_i - x_u| <= R_k and |v_j - x_v| <= R_k (decided on the pixel centres
+ * themselves: a disc between centres lists nothing); a tile evaluates its whole list at each of its 256 pixels.  More
+ * than 2^31 - 1 pairs, or a failed allocation: SPHX_E_NOMEM and nothing is written (a window far inside a cloud of wide
+ * particles: project a narrower depth, or fewer pixels).
+ * SPHX_E_ARG: a NULL required pointer, n < 1 or n >= 2^31 - 16, equal or out-of-range axes, a half-width that is not
+ * positive and finite, a non-finite centre, n_u or n_v < 1, n_u n_v > 2^28, lo >= hi (or a NaN among them).
+ *
+ * sphx_project_maps: arrays in (points (n,3), the others (n)), maps out.
+ * sphx_state_project: the same on the resident state - the positions, masses, types, T and sizes sphx_state_sample reads
+ * (sizes: the step's radii).  SPHX_E_STATE before the first sphx_step.  The bits are those of sphx_project_maps on the
+ * downloaded state.  The state is only read, in buffers of the call's own: the loop is not disturbed.
+ * sphx_map_last_timing: device time of the stages of the last of the two calls on this context, in ms: [0] inputs on the
+ * device (resident: the id -> slot map) and the footprints, [1] counts per tile, their scan and the pair count on the
+ * host, [2] the tile lists filled and sorted, [3] the tile kernel, [4] the read-back.                                   */
+int sphx_project_maps(sphx_ctx* ctx, int64_t n, const double* points, const double* mass, const double* particle_type,
+                      const double* sizes, const double* T, double d, const int axes[2], const double center[2],
+                      const double half_width[2], const int npix[2], const double* depth /* (lo, hi) or NULL */,
+                      double* gas_column, double* dust_column, double* gas_temperature, double* dust_temperature,
+                      int64_t* count, int64_t* skipped, int64_t* pairs);
+int sphx_state_project(sphx_ctx* ctx, double d, const int axes[2], const double center[2], const double half_width[2],
+                       const int npix[2], const double* depth, double* gas_column, double* dust_column,
+                       double* gas_temperature, double* dust_temperature, int64_t* count, int64_t* skipped, int64_t* pairs);
+int sphx_map_last_timing(sphx_ctx* ctx, double ms[5]);
 /* ---- nsc.chemisputtering_2(points, neighbor, mass, f_un, mu_array, sizes, T, particle_type)      nsc:1265-1416 ----- *
  * Thermal / chemical sputtering of the dust rows and reuptake by the gas entries of their lists, on the list `neighbors`
  * returned (drv:405).  The module globals d and dt are arguments, and so are the per-species tables (nsc:41-52).

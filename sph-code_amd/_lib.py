@@ -130,6 +130,9 @@ SIGNATURES = {
     "sphx_state_advance_star_ages": (C.c_int, [_P, C.c_double]),
     "sphx_advance_star_ages": (C.c_int, [_P, C.c_int64, _D, _D, C.c_double]),
     "sphx_census_last_timing": (C.c_int, [_P, _D]),
+    "sphx_project_maps": (C.c_int, [_P, C.c_int64] + [_D] * 5 + [C.c_double, c_int32_p, _D, _D, c_int32_p, _D] + [_D] * 4 + [_I, _I, _I]),
+    "sphx_state_project": (C.c_int, [_P, C.c_double, c_int32_p, _D, _D, c_int32_p, _D] + [_D] * 4 + [_I, _I, _I]),
+    "sphx_map_last_timing": (C.c_int, [_P, _D]),
     "sphx_chemisputtering_2": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _D, _I] + [_D] * 6 + [C.c_double, C.c_double] + [_D] * 4 +
                                          [C.c_double] * 3 + [_D, _D, _I]),
     "sphx_chem_last_timing": (C.c_int, [_P, _D]),

@@ -16,7 +16,7 @@ SOURCES = ["sphx_api.hip", "sphx_grid.hip", "sphx_knn.hip", "sphx_knn_group.hip"
            "sphx_integrate.hip", "sphx_loopforms.hip", "sphx_dev.hip", "sphx_refresh.hip", "sphx_blob.hip",
            "sphx_agb.hip", "sphx_gravity.hip", "sphx_arb.hip", "sphx_rad.hip", "sphx_cool.hip",
            "sphx_dust.hip", "sphx_chem.hip", "sphx_phase.hip", "sphx_radphase.hip", "sphx_side.hip", "sphx_sn.hip",
-           "sphx_insert.hip", "sphx_scale.hip", "sphx_census.hip"]
+           "sphx_insert.hip", "sphx_scale.hip", "sphx_census.hip", "sphx_map.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + \
           [os.path.join(os.path.dirname(HERE), "include", "sphx.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]

@@ -22,6 +22,7 @@ for the functions the driver sph/code_running.py ("drv") calls on the SPH inner 
     luminosity_relation    nsc:174-200      (without its unused `imf` argument)
     census, advance_star_ages, supernova_schedule, run_outputs, select_rows
                                             drv:244, 339-342, 604, 616-622, 636, 656-664 (the driver's own lines)
+    project_maps                            drv:563-597 (what the driver's scatter plot approximates: the projection)
 
 and, under names of their own, the pieces rad_heating (nsc:893-1017) and the driver's radiative block (drv:247-316)
 fall into: rad_setup, rad_transfer, stellar_spectrum, rad_ionise, rad_heat_bookkeeping, rad_cool_bookkeeping, and
@@ -1674,3 +1675,70 @@ def run_outputs(mass, particle_type, f_un, star_ages, OVERALL_AGE, mu_specie=Non
     rows = select_rows(mass, particle_type, 1, star_ages=star_ages, f_un=fu, window=AGB_WINDOW)
     out.update(_agb_outputs(fu.shape[0], rows, OVERALL_AGE, mus))
     return out
+
+
+# ==============================================================================================
+# The projected maps: the state integrated along a line of sight onto a pixel grid (drv:563-597 draws the cloud each pass)
+# ==============================================================================================
+MAP_FIELDS = ("gas_column", "dust_column", "gas_temperature", "dust_temperature", "count")
+MAP_STAGES = ("footprints", "count_scan", "list_build", "tiles", "read_back")
+
+
+def _map_args(axes, center, half_width, npix, depth, fields):
+    """The image's arguments as the C calls take them, and the zeroed (n_v, n_u) outputs of the fields asked for."""
+    ax = np.ascontiguousarray(np.asarray(axes, dtype=np.int32).reshape(-1))
+    np_ = np.ascontiguousarray(np.broadcast_to(np.asarray(npix, dtype=np.int32), (2,)))
+    ce = np.ascontiguousarray(np.broadcast_to(np.asarray(center, dtype=np.float64), (2,)))
+    hw = np.ascontiguousarray(np.broadcast_to(np.asarray(half_width, dtype=np.float64), (2,)))
+    if ax.shape != (2,):
+        raise ValueError("axes must be two coordinate indices")
+    dep = None if depth is None else f64(depth, (2,))
+    for f in fields:
+        if f not in MAP_FIELDS:
+            raise ValueError("unknown field %r (one of %s)" % (f, ", ".join(MAP_FIELDS)))
+    if int(np_[0]) * int(np_[1]) > 1 << 28:       # (the C call's own limit, before the outputs are allocated)
+        raise ValueError("npix: %d x %d pixels (at most 2^28)" % (np_[0], np_[1]))
+    shape = (max(int(np_[1]), 0), max(int(np_[0]), 0))
+    out = {f: np.zeros(shape, dtype=np.int64 if f == "count" else np.float64) for f in MAP_FIELDS if f in fields}
+    return ax, ce, hw, np_, dep, out
+
+
+def _map_call(fn, head, geom, out):
+    """One of the two C calls: head are its arguments in front of the image's -> the dict of project_maps."""
+    ax, ce, hw, np_, dep = geom
+    sk, pr = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    c32 = lambda a: a.ctypes.data_as(_lib.c_int32_p)
+    rc = fn(*head, c32(ax), dp(ce), dp(hw), c32(np_), dp(dep), *[dp(out.get(f)) for f in MAP_FIELDS[:4]], ip(out.get("count")),
+            ip(sk), ip(pr))
+    res = dict(out)
+    res["skipped"], res["pairs"] = int(sk[0]), int(pr[0])
+    return rc, res
+
+
+def project_maps(points, mass, particle_type, sizes, T, d, axes=(1, 2), center=(0, 0), half_width=1.0, npix=256, depth=None,
+                 fields=MAP_FIELDS):
+    """The particles integrated along a coordinate axis onto a pixel grid (include/sphx.h sphx_project_maps) -> dict of
+    (n_v, n_u) arrays - gas_column and dust_column [kg/m^2], gas_temperature and dust_temperature (column-weighted, 0 where
+    there is nothing), count (int64: particles over the pixel) - of the `fields` asked for, plus skipped (gas and dust rows
+    that are not finite or have no positive radius) and pairs ((particle, 16 x 16 tile) pairs listed).  axes = (a_u, a_v):
+    the image's horizontal and vertical coordinate, the line of sight is the third; center, half_width and npix: a pair
+    (u, v) or one value for both; depth = (lo, hi): only particles with lo <= line-of-sight coordinate < hi.  Gas has the
+    footprint h(m) = (m/m_0)^(1/3) d, dust its sizes; stars have none.  Values are at pixel centres, every sum in ascending
+    particle index: the same bits on every call."""
+    pts = f64(points)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("points must be (N, 3)")
+    n = pts.shape[0]
+    m, pt, sz, Tt = f64(mass).reshape(-1), f64(particle_type, (n,)), f64(sizes, (n,)), f64(T, (n,))
+    if m.shape != (n,):
+        raise ValueError("mass must be (N,)")
+    *geom, out = _map_args(axes, center, half_width, npix, depth, fields)
+    c_ = context()
+    rc, res = _map_call(c_.lib.sphx_project_maps, (c_.h, n, dp(pts), dp(m), dp(pt), dp(sz), dp(Tt), float(d)), geom, out)
+    c_.check(rc)
+    return res
+
+
+def map_last_timing():
+    """Device time of the last project_maps() of this module from HIP events -> dict of ms (MAP_STAGES)."""
+    return _last_timing("sphx_map_last_timing", MAP_STAGES)

@@ -185,14 +185,17 @@ static int cen_ints(sphx_ctx* ctx, int64_t n, CenInts* o) {
 }
 // the slot map of the resident state into ctx->census_int
 static int cen_slot_map(sphx_ctx* ctx, const int** slot) {
-    const size_t nn = (size_t)ctx->n;
     CenInts ci;
     SPHX_TRY(cen_ints(ctx, ctx->n, &ci));
-    int* s = ci.slot;
-    HIPCHK(hipMemsetAsync(s, 0, nn * sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(census_slot_kernel, dim3(sphx_blocks(nn, CEN_WG)), dim3(CEN_WG), 0, ctx->stream, (int)ctx->n, ctx->st.id.as<int>(), s);
+    SPHX_TRY(sphx_slot_map(ctx, ci.slot));
+    *slot = ci.slot;
+    return SPHX_OK;
+}
+int sphx_slot_map(sphx_ctx* ctx, int* slot) {
+    const size_t nn = (size_t)ctx->n;
+    HIPCHK(hipMemsetAsync(slot, 0, nn * sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(census_slot_kernel, dim3(sphx_blocks(nn, CEN_WG)), dim3(CEN_WG), 0, ctx->stream, (int)ctx->n, ctx->st.id.as<int>(), slot);
     HIPCHK(hipGetLastError());
-    *slot = s;
     return SPHX_OK;
 }
 

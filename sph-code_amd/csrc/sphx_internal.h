@@ -503,6 +503,14 @@ struct sphx_ctx {
     // events: [0] start, [1] inputs on the device and eps, [2] grid and pyramid (tree), [3] the sums, [4] outputs on the host
     DevBuf gravpot_buf;
     StageTimer gravpot_t;
+    // the projected maps (sphx_map.hip), buffers of its own - it only reads the state: staged inputs of the array call, the
+    // footprints by particle id (SphxMapRec | the tile range, int4), ints (slot of a particle id | counts per tile | their
+    // scan | the fill's cursors), the tile lists (as filled | sorted, sphx_revlist.h) and their sort's scratch, outputs (the
+    // pair count and the skipped rows, u64 | the images asked for | count, int64)
+    // events: [0] start, [1] footprints, [2] counts, scan and the pair count on the host, [3] tile lists filled and sorted,
+    // [4] the tile kernel, [5] outputs on the host (sphx_map_last_timing)
+    DevBuf map_in, map_rec, map_int, map_rev, map_tmp, map_out;
+    StageTimer map_t{5};
     StateArrays st, alt;          // simulation state
     DevBuf badc;                  // failure counters, BADC_BUCKETS x BADC_STRIDE u64 (zeroed at sphx_create / sphx_reset_stats)
     DevBuf scal_tmp;                    // step_scalars_kernel's per-block partials + its ticket
@@ -666,7 +674,9 @@ struct PinnedLayout {
     PinnedLag lag[2];         // the fused loop's lagged read-backs (lag_bslot / lag_hslot say which is current)
     char pad2_[3072 - 1024 - 2 * 512];
     u64 knn_lag[10];          // SC_NFAILQ .. SC_KGDBG + 2, copied out behind a hinted search (sphx_knn.hip)
-    char pad3_[4096 - 3072 - 10 * 8];
+    // the projected maps' read-back (sphx_map.hip): the pair count in 64 bits, the skipped rows, the scan's total
+    u64 map[4];
+    char pad3_[4096 - 3072 - 10 * 8 - 4 * 8];
     // the census' read-back (sphx_census.hip): 13 + 3 s totals, the largest stellar mass, four counts; a selection's count
     u64 census[SPHX_CENSUS_PIN];
     char pad4_[8192 - 4096 - SPHX_CENSUS_PIN * 8];
@@ -681,7 +691,7 @@ static_assert(offsetof(PinnedLayout, side) == 0 && offsetof(PinnedSide, count) =
 #define SPHX_PIN_APART(a, b) \
     static_assert(offsetof(PinnedLayout, a) + sizeof(PinnedLayout::a) <= offsetof(PinnedLayout, b), #a " overlaps " #b)
 SPHX_PIN_APART(scal, hsum); SPHX_PIN_APART(side, hsum); SPHX_PIN_APART(hsum, lag); SPHX_PIN_APART(lag, knn_lag);
-SPHX_PIN_APART(knn_lag, census); SPHX_PIN_APART(census, badc);
+SPHX_PIN_APART(knn_lag, map); SPHX_PIN_APART(map, census); SPHX_PIN_APART(census, badc);
 #undef SPHX_PIN_APART
 static_assert(offsetof(PinnedLayout, badc) + sizeof(PinnedLayout::badc) == sizeof(PinnedLayout), "the buckets end the block");
 
@@ -902,12 +912,18 @@ int sphx_sn_run(sphx_ctx* ctx, const char* who, int64_t n, const double* pos, co
 struct RevList { size_t M; const int* rev; };
 int sphx_rev_build(sphx_ctx* ctx, const char* who, int64_t n, const int* cnt, int* start, size_t pairs, unsigned long long key_end,
                    const std::function<void(const int* start, int* rev_raw)>& fill, RevList* out);
+// its second half for a caller that has scanned its counts and checked the total M on the host itself: the fill and the
+// sort of every slice, into buffers the caller names (rev: sphx_rev_ints(M) ints, tmp: the sort's scratch)
+int sphx_rev_fill_sort(sphx_ctx* ctx, int64_t n, const int* start, size_t M, unsigned long long key_end,
+                       const std::function<void(const int* start, int* rev_raw)>& fill, DevBuf& rev, DevBuf& tmp, RevList* out);
 // the sums over n particles of nq per-particle terms pp (nq, n), in a fixed order, queued into ctx->pinned->scal
 #define SPHX_TOT_CHUNK 256
 static inline size_t sphx_tot_chunks(int64_t n) { return ((size_t)n + SPHX_TOT_CHUNK - 1) / SPHX_TOT_CHUNK; }
 int sphx_ordered_totals(sphx_ctx* ctx, int64_t n, int nq, const double* pp, double* part, double* tot);
 // its second stage alone, on chunk sums the caller has formed: part (nq, nchunk) -> tot (nq); nothing is copied out
 int sphx_ordered_totals_of_parts(sphx_ctx* ctx, size_t nchunk, int nq, const double* part, double* tot);
+// slot[id[j]] = j of the resident state: where the particle with an id lies (sphx_census.hip); slot holds n ints
+int sphx_slot_map(sphx_ctx* ctx, int* slot);
 // ---- the stellar clock inside sphx_state_insert_rows (sphx_census.hip) ----
 // ages set: the by-id array grown to n_new rows with its contents kept (grow), and -2 for the rows [n_old, n_new) (fill)
 int sphx_star_ages_grow(sphx_ctx* ctx, int64_t n_old, int64_t n_new, std::vector<void*>& retired);

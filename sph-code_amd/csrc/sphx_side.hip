@@ -21,8 +21,15 @@ int sphx_rev_build(sphx_ctx* ctx, const char* who, int64_t n, const int* cnt, in
     HIPCHK(hipStreamSynchronize(st));
     const size_t M = (size_t)ctx->pinned->side.count;
     if (M > pairs) return sphx_set_err(ctx, SPHX_E_HIP, "%s: reverse list of %zu entries from %zu pairs", who, M, pairs);
-    SPHX_TRY(sphx_ensure(ctx, ctx->side_rev, sphx_rev_ints(M) * sizeof(int)));
-    int* rev_raw = ctx->side_rev.as<int>();
+    return sphx_rev_fill_sort(ctx, n, start, M, key_end, fill, ctx->side_rev, ctx->side_tmp, out);
+}
+// The fill and the segmented sort alone, into the caller's buffers (the projected maps, sphx_map.hip: segments are tiles,
+// entries particle ids, and the total has been checked on the host against a 64-bit count before anything is sized).
+int sphx_rev_fill_sort(sphx_ctx* ctx, int64_t n, const int* start, size_t M, unsigned long long key_end,
+                       const std::function<void(const int* start, int* rev_raw)>& fill, DevBuf& rev_buf, DevBuf& tmp_buf, RevList* out) {
+    hipStream_t st = ctx->stream;
+    SPHX_TRY(sphx_ensure(ctx, rev_buf, sphx_rev_ints(M) * sizeof(int)));
+    int* rev_raw = rev_buf.as<int>();
     int* rev = rev_raw + sphx_rev_sorted_at(M);
     if (M > 0) {
         fill(start, rev_raw);
@@ -30,8 +37,8 @@ int sphx_rev_build(sphx_ctx* ctx, const char* who, int64_t n, const int* cnt, in
         const unsigned bits = sphx_rev_bits(key_end);
         size_t sort_bytes = 0;
         HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
-        SPHX_TRY(sphx_ensure(ctx, ctx->side_tmp, sort_bytes + 64));
-        HIPCHK(rocprim::segmented_radix_sort_keys(ctx->side_tmp.p, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
+        SPHX_TRY(sphx_ensure(ctx, tmp_buf, sort_bytes + 64));
+        HIPCHK(rocprim::segmented_radix_sort_keys(tmp_buf.p, sort_bytes, rev_raw, rev, (unsigned)M, (unsigned)n, start, start + 1, 0u, bits, st));
     }
     out->M = M; out->rev = rev;
     return SPHX_OK;

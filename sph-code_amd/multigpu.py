@@ -702,6 +702,10 @@ class DistributedSim:
         """The census' fixed order of summation runs over one context's particle ids: not built across ranks."""
         raise NotImplementedError("census is not available in the decomposed step (single-GPU Simulation only)")
 
+    def project(self, *a, **kw):
+        """A pixel's sum runs over one context's particle ids in ascending order: not built across ranks."""
+        raise NotImplementedError("project is not available in the decomposed step (single-GPU Simulation only)")
+
     def gravity_potential(self, *a, **kw):
         """The potential's walk and its ordered total run over one context's particles: the exported multipoles between
         ranks carry no potential (out of scope)."""

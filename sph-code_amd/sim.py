@@ -640,6 +640,50 @@ class Simulation:
         c.check(c.lib.sphx_census_last_timing(c.h, dp(ms)))
         return dict(zip(compat.CENSUS_STAGES, ms.tolist()))
 
+    # ---- the picture of the cloud (code_running.py:563-597): the state projected onto a pixel grid ----
+    def project(self, half_width, npix, d=None, axes=(1, 2), center=(0, 0), depth=None, fields=None, stars=False):
+        """The state as it is on the device integrated along a coordinate axis onto a pixel grid (include/sphx.h
+        sphx_state_project; after the first step) -> compat.project_maps' dict: (n_v, n_u) arrays gas_column, dust_column,
+        gas_temperature, dust_temperature, count (those of `fields`; None: all), skipped and pairs.  Only the images come
+        back, no N-sized array.  d: the driver's global d (drv:68); None: the d remembered from the last
+        length_scale(apply=True).  axes = (a_u, a_v), the line of sight is the third coordinate; center, half_width and
+        npix: a pair (u, v) or one value for both; depth = (lo, hi) keeps the particles with lo <= line-of-sight
+        coordinate < hi.  Sizes are the step's radii (download()["sizes"]), as sample() reads them.  The driver's own
+        window (drv:563-597) is axes=(1, 2), center=0, half_width=sqrt(length_scale()["max_dist"] * 11 / 9).
+        stars=True adds star_ids, star_uv (n, 2) and star_mass of the stars inside the window (and the depth), in
+        ascending particle id.  The bits are those of compat.project_maps on download(), whatever order the state is
+        stored in.  The step loop is not disturbed."""
+        from . import compat
+        d = self._d_or_remembered(d)
+        flds = compat.MAP_FIELDS if fields is None else tuple(fields)
+        *geom, out = compat._map_args(axes, center, half_width, npix, depth, flds)
+        c = self.ctx
+        rc, res = compat._map_call(c.lib.sphx_state_project, (c.h, float(d)), geom, out)
+        c.check(rc)
+        if stars:
+            ax, ce, hw, _, dep = geom
+            sel = self._select(1)
+            rows = self.download_rows(sel["ids"]) if sel["ids"].shape[0] else dict(points=np.zeros((0, 3)))
+            p = rows["points"]
+            au, av = int(ax[0]), int(ax[1])
+            keep = (np.abs(p[:, au] - ce[0]) <= hw[0]) & (np.abs(p[:, av] - ce[1]) <= hw[1])
+            if dep is not None:
+                w = p[:, 3 - au - av]
+                keep &= (w >= dep[0]) & (w < dep[1])
+            res["star_ids"] = sel["ids"][keep]
+            res["star_uv"] = np.ascontiguousarray(p[keep][:, [au, av]])
+            res["star_mass"] = sel["mass"][keep]
+        return res
+
+    def map_timing(self):
+        """Device time of the last project() from HIP events -> dict of ms: footprints (with the id -> slot map),
+        count_scan (with the host's wait for the pair count), list_build, tiles, read_back."""
+        from . import compat
+        ms = np.zeros(5)
+        c = self.ctx
+        c.check(c.lib.sphx_map_last_timing(c.h, dp(ms)))
+        return dict(zip(compat.MAP_STAGES, ms.tolist()))
+
     # ---- what the run's self-gravity does to its energy (include/sphx.h sphx_state_gravity_potential) ----
     def gravity_potential(self, by_id=False):
         """Potential energy of the state as it is on the device, in the mode of the step's gravity (gravity="direct", or
